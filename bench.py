@@ -2,20 +2,31 @@
 """Headline benchmark: images/sec of one QuadtreeCNN training step (forward +
 backward + gradient all-reduce + Adam) at 224x224, batch 256 per GPU, bf16.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is what the reference's hot loop does per batch
-(/root/reference/Quadtree_from scratch/Quadtree_train.py:62-66): zero_grad,
+(Quadtree_from scratch/Quadtree_train.py:62-66 of the reference): zero_grad,
 model(images, numerical), CrossEntropyLoss, backward, Adam(lr 1e-4, wd 1e-4).step.
 Inputs are synthetic and already resident in HBM; weights are the deterministic
-synthetic fill.  Rank 0 prints ONE JSON line (contract in the task statement)
-with two extra objects:
+synthetic fill.  Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs if --dump-outputs is given, and prints the line.  --full adds what takes
+runs of its own after the timed steps:
+  forward       eval-mode forward of the same model and batch, timed on its own
   roofline      the MFMA implicit-GEMM kernels (dominant kernel family), timed per
                 launch with HIP events on their own stream in extra steps right
                 after the timed region (event pairs would perturb `value`)
+  hbm, mfma_pmc the committed PMC summaries under profiles/ against this run's step time
   cpu_baseline  the CPU oracle (torch fp32 restatement, "port") on this box's host
                 cores, bounded sample, N=1 only
+Without --full these keys are null (cpu_baseline absent).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed
+its caller as DIR/<name>.npy (float32): logits and loss of the train step (logits
+only with --forward-only), and a fixed, seeded sample of the parameters, their
+gradients and the floating-point buffers (BatchNorm running statistics) after it.
 """
 import os
 
@@ -202,12 +213,63 @@ def parse():
     ap.add_argument("--forward-only", action="store_true", help="time eval-mode forward instead of the train step")
     ap.add_argument("--optimizer", default="fused", choices=["fused", "torch"],
                     help="Adam(lr 1e-4, wd 1e-4) by the package's FusedAdam kernel (default) or torch.optim.Adam(fused=True)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the eval-forward leg, the per-launch roofline steps, the PMC "
+                         "summaries and the CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, a seeded sample of large ones)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-forward-leg", action="store_true",
-                    help="skip the eval-forward timing after the train step (profiling runs: keeps kernel counts per step exact)")
+                    help="--full: skip the eval-forward timing after the train step (profiling runs: keeps kernel counts "
+                         "per step exact)")
     ap.add_argument("--cpu-batch", type=int, default=16)
-    ap.add_argument("--profile-steps", type=int, default=2)
+    ap.add_argument("--profile-steps", type=int, default=2, help="--full: extra steps timed per launch for the roofline")
     return ap.parse_args()
+
+
+DUMP_SAMPLE_PER_TENSOR = 4096   # elements kept of each larger parameter / gradient / buffer
+DUMP_MAX_BYTES = 64 << 20
+
+
+def sample_flat(named, seed=0, per_tensor=DUMP_SAMPLE_PER_TENSOR):
+    """One float32 vector from `named` [(name, tensor)] in the given order: a tensor of at most `per_tensor` elements whole,
+    a larger one at `per_tensor` positions drawn by a CPU generator seeded with `seed` (same model and seed -> same
+    positions, whatever the device)."""
+    g = torch.Generator().manual_seed(seed)
+    parts = []
+    for _, t in named:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > per_tensor:
+            idx = torch.randint(0, flat.numel(), (per_tensor,), generator=g).to(flat.device)
+            flat = flat.index_select(0, idx)
+        parts.append(flat.float().cpu())
+    return torch.cat(parts) if parts else torch.zeros(0)
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy in float32; refuses to write more than DUMP_MAX_BYTES in all."""
+    import numpy as np
+    out = {k: v.detach().float().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(out)
+
+
+def step_outputs(model, logits, loss):
+    """What a caller of the timed step receives after it: logits (and loss) plus samples of the updated parameters, their
+    gradients and the running statistics the forward updated."""
+    params = [(n, p) for n, p in model.named_parameters()]
+    arrays = {"logits": logits}
+    if loss is not None:
+        arrays["loss"] = loss.reshape(1)
+        arrays["grads"] = sample_flat([(n, p.grad) for n, p in params if p.grad is not None], seed=1)
+    arrays["params"] = sample_flat(params, seed=0)
+    arrays["buffers"] = sample_flat([(n, b) for n, b in model.named_buffers() if b.is_floating_point()], seed=2)
+    return arrays
 
 
 def host_cores():
@@ -415,6 +477,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)       # no launcher: become one (nothing has touched the GPU yet)
     rank = int(os.environ.get("RANK", "0"))
@@ -463,6 +527,9 @@ def main():
     dp = importlib.import_module(PKG + ".dp")
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     C, B = 12, args.batch
+    # the dropout masks of a train step are drawn from torch's default generator, which this torch seeds differently in
+    # every process: fixed here, so that the same arguments give the same step (--dump-outputs compares runs)
+    torch.manual_seed(1234 + rank)
     if args.model == "quadtree3d" and args.seq_len == 16:
         args.seq_len = 8   # (the default of --seq-len is config 5's 16; config 4 quotes T = 8)
     if args.model in ("cnn_lstm", "quadtree3d") and B % args.seq_len:
@@ -506,16 +573,17 @@ def main():
 
         def step():
             with torch.no_grad():
-                return model(images, feats)
+                return model(images, feats), None
     else:
         model.train()
 
         def step():
             opt.zero_grad(set_to_none=True)
-            loss = crit(model(images, feats), labels)
+            logits = model(images, feats)
+            loss = crit(logits, labels)
             loss.backward()
             opt.step()
-            return loss
+            return logits, loss
 
     def fence():
         torch.cuda.synchronize()
@@ -531,7 +599,7 @@ def main():
         red0.measure_tail = True   # two events per join: how long the last compute kernel had been done before the all-reduce was
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     host_issue = time.perf_counter() - t0   # host time to ISSUE the K steps (no sync): close to `elapsed` = host-bound
     fence()
     elapsed = time.perf_counter() - t0
@@ -543,11 +611,14 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # before --full runs further steps on the same model
+        dump_outputs(args.dump_outputs, step_outputs(model, *last))
+    del last
 
     # ---- roofline of the MFMA kernels: per-launch HIP events in extra steps ----
     roofline = None
     eng = getattr(model, "_engine", None)
-    if eng is not None and args.profile_steps > 0:
+    if eng is not None and args.full and args.profile_steps > 0:
         L = eng.L
         L.qt_plan_profile_begin.argtypes = [ctypes.c_void_p]
         L.qt_plan_profile_end.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -594,7 +665,7 @@ def main():
                                                  "gradients run beside the main chain): not a serial time, may exceed ms_per_step",
                         "steps_profiled": args.profile_steps, "by_kernel": per}
 
-    if eng is None and args.model == "quadtree3d" and args.profile_steps > 0:
+    if eng is None and args.model == "quadtree3d" and args.full and args.profile_steps > 0:
         # no plan behind the clip models: the Conv3d launches (qt_conv2d_igemm with 27 taps, forward + data gradient; block 1's
         # qt_conv3d_first_fwd) are timed per launch with HIP events on their stream in extra steps (video3d.py::_Ops.igemm)
         v3d = importlib.import_module(PKG + ".video3d")
@@ -630,15 +701,15 @@ def main():
     # collected on exactly these kernel sources (otherwise null + the reason)
     hbm = mfma_pmc = None
     headline = args.batch == 256 and args.dtype == "bf16" and args.model == "quadtree" and not args.freeze_backbone
-    if (headline or args.model == "quadtree3d") and not args.forward_only and not args.freeze_backbone:
+    if args.full and (headline or args.model == "quadtree3d") and not args.forward_only and not args.freeze_backbone:
         hbm = guarded("hbm summary", step_hbm, args.model, args.batch, args.dtype, elapsed / args.steps)
-    if headline:
+    if args.full and headline:
         mfma_pmc = guarded("mfma_busy summary", step_mfma_busy, args.model, args.batch, args.dtype,
                            "eval" if args.forward_only else "train", elapsed / args.steps)
 
     # ---- the north-star quantity on the same line: eval-mode forward of the same model, timed after the train step ----
     forward = None
-    if not args.forward_only and not args.no_forward_leg:
+    if args.full and not args.forward_only and not args.no_forward_leg:
         model.eval()
 
         def fwd():
@@ -737,7 +808,7 @@ def main():
         "mfma_pmc": mfma_pmc,
         "hbm": hbm,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args)
         except Exception as e:  # the checker must never take the measurement down

@@ -394,11 +394,13 @@ int qt_stem_bn_bwd_apply(int dtype, const void* dpooled, const unsigned char* ar
 /* Stem backward in one launch (bf16): the gradient of conv1's output (max-pool backward + ReLU mask + BatchNorm backward,
  * the arithmetic of qt_stem_bn_bwd_apply) is computed tile by tile in LDS and contracted with the packed input at once:
  * dw[64][7][32] (the layout qt_unpack_stem_wgrad reads, zeroed by the caller) += conv1's weight gradient.  The 411 MB map
- * d(loss)/d(conv1 output) is neither written nor read.  QT_ERR_UNSUPPORTED for f32 / QTCNN_STEM_BWD_FUSED=0: use
- * qt_stem_bn_bwd_apply + qt_conv2d_wgrad. */
-int qt_stem_bn_bwd_wgrad(int dtype, const void* dpooled, const unsigned char* argmax, const void* y, const float* scale,
-                         const float* shift, const float* mean, const float* invstd, const float* coef, const void* xpad,
-                         float* dw, int batch, void* stream);
+ * d(loss)/d(conv1 output) is neither written nor read.  Each workgroup writes its partial filter to `workspace`
+ * (qt_stem_bn_bwd_wgrad_workspace_bytes(batch)) and a second launch adds them to dw in workgroup order: the same bits on
+ * every run.  QT_ERR_UNSUPPORTED for f32 / QTCNN_STEM_BWD_FUSED=0: use qt_stem_bn_bwd_apply + qt_conv2d_wgrad. */
+size_t qt_stem_bn_bwd_wgrad_workspace_bytes(int batch);
+int qt_stem_bn_bwd_wgrad_ws(int dtype, const void* dpooled, const unsigned char* argmax, const void* y, const float* scale,
+                            const float* shift, const float* mean, const float* invstd, const float* coef, const void* xpad,
+                            float* dw, void* workspace, size_t workspace_bytes, int batch, void* stream);
 /* AdaptiveAvgPool2d(1,1)+flatten into columns [col0, col0+C) of the fused feature
  * matrix (Quadtree_from scratch/models.py:242,289-294) and its backward fused with the
  * ReLU mask of the pooled map. */
@@ -455,6 +457,12 @@ int qt_dropout(int dtype, void* x, long long rows, int cols, int ld, unsigned lo
 int qt_relu_mask_scale(int dtype, void* g, const void* act, long long n, float mul, void* stream);
 /* out[c] (+)= sum_r x[r*ld+c]  (bias gradients) */
 int qt_col_sum(int dtype, const void* x, long long rows, int cols, int ld, float* out, int accumulate, void* stream);
+/* The same, deterministic: row chunks (at most 1024) write their column sums to `workspace` (qt_col_sum_workspace_bytes), a
+ * second launch adds them in chunk order (qt_col_sum's atomics depend on the order the chunks finish in once there are more
+ * than two) */
+size_t qt_col_sum_workspace_bytes(long long rows, int cols);
+int qt_col_sum_ws(int dtype, const void* x, long long rows, int cols, int ld, float* out, int accumulate, void* workspace,
+                  size_t workspace_bytes, void* stream);
 
 /* nn.Linear on a small batch with a large weight matrix (classifier.0: Linear(5376 -> 2688) + ReLU,
  * Quadtree_from scratch/models.py:266-268, and its backward-input product), bf16:

@@ -414,6 +414,7 @@ struct StemWgArgs {
   const bf16_t* dy;   // [B][112][112][64]  (FUSED: the raw conv1 output y)
   const bf16_t* x;    // [B][230][232][4]
   float* dw;          // [64][7][32], accumulated into
+  float* part;        // null: atomics into dw; else [gridDim.x][64 * 7 * 32] partial filters, summed in block order
   int ntiles;         // B * 56
   // FUSED
   const bf16_t* dpooled;            // [B][56][56][64]
@@ -619,9 +620,20 @@ __global__ __launch_bounds__(512) void stem_wgrad_rows_kernel(StemWgArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int co = i * 16 + lg * 4 + r, n = h * 16 + li;
-          atomicAdd(p.dw + (co * 7 + wave) * 32 + n, acc[i][h][r]);
+          if (p.part) p.part[(long long)blockIdx.x * (64 * 7 * 32) + (co * 7 + wave) * 32 + n] = acc[i][h][r];
+          else atomicAdd(p.dw + (co * 7 + wave) * 32 + n, acc[i][h][r]);
         }
   }
+}
+
+// dw[i] += the partial filters of stem_wgrad_rows_kernel summed in block order (the same bits on every run)
+__global__ __launch_bounds__(256) void stem_part_sum_kernel(const float* __restrict__ part, int nparts, float* __restrict__ dw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 64 * 7 * 32) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int b = 0; b < nparts; ++b) s += part[(long long)b * (64 * 7 * 32) + i];
+  dw[i] += s;
 }
 
 int launch_stem_rows(const void* dy, const void* x, float* dw, int batch, hipStream_t stream) {
@@ -646,18 +658,18 @@ int qt_wgrad_patch_launch(const qt_conv_desc* d, const void* dy, const void* x, 
 // Stem backward in one launch (bf16): max-pool backward + ReLU mask + BatchNorm backward of conv1's output computed tile by
 // tile in LDS and contracted with the packed input at once: dw[64][7][32] += conv1's weight gradient (qt_unpack_stem_wgrad
 // layout).  Inputs as qt_stem_bn_bwd_apply; d(loss)/d(conv1 output) is never materialised.
-extern "C" int qt_stem_bn_bwd_wgrad(int dtype, const void* dpooled, const unsigned char* argmax, const void* y,
-                                    const float* scale, const float* shift, const float* mean, const float* invstd,
-                                    const float* coef, const void* xpad, float* dw, int batch, void* stream) {
-  QT_CHECK_ARG(dpooled && argmax && y && scale && shift && mean && invstd && coef && xpad && dw && batch > 0,
-               "qt_stem_bn_bwd_wgrad: bad argument");
+static int stem_bn_bwd_wgrad(int dtype, const void* dpooled, const unsigned char* argmax, const void* y, const float* scale,
+                             const float* shift, const float* mean, const float* invstd, const float* coef, const void* xpad,
+                             float* dw, void* workspace, size_t workspace_bytes, int batch, void* stream) {
+  QT_CHECK_ARG(dpooled && argmax && y && scale && shift && mean && invstd && coef && xpad && dw && workspace && batch > 0,
+               "qt_stem_bn_bwd_wgrad_ws: bad argument");
   static int on = -1;
   if (on < 0) {
     const char* e = getenv("QTCNN_STEM_BWD_FUSED");
     on = e ? atoi(e) : 1;
   }
   if (dtype != QT_BF16 || !on) {
-    qt_set_error("qt_stem_bn_bwd_wgrad: bf16 only (use qt_stem_bn_bwd_apply + qt_conv2d_wgrad)");
+    qt_set_error("qt_stem_bn_bwd_wgrad_ws: bf16 only (use qt_stem_bn_bwd_apply + qt_conv2d_wgrad)");
     return QT_ERR_UNSUPPORTED;
   }
   StemWgArgs a;
@@ -667,9 +679,29 @@ extern "C" int qt_stem_bn_bwd_wgrad(int dtype, const void* dpooled, const unsign
   static std::atomic<unsigned long long> lds_limit_set{0};  // per device
   if (int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(stem_wgrad_rows_kernel<true>), SW_LDS_F, lds_limit_set)) return rc;
   const int grid = a.ntiles < 256 ? a.ntiles : 256;
-  hipLaunchKernelGGL(stem_wgrad_rows_kernel<true>, dim3(grid), dim3(512), SW_LDS_F, static_cast<hipStream_t>(stream), a);
+  QT_CHECK_ARG(workspace_bytes >= (size_t)grid * 64 * 7 * 32 * 4, "qt_stem_bn_bwd_wgrad_ws: workspace of %zu bytes < %zu",
+               workspace_bytes, (size_t)grid * 64 * 7 * 32 * 4);
+  a.part = static_cast<float*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(stem_wgrad_rows_kernel<true>, dim3(grid), dim3(512), SW_LDS_F, s, a);
+  hipLaunchKernelGGL(stem_part_sum_kernel, dim3(qt_cdiv(64 * 7 * 32, 256)), dim3(256), 0, s, a.part, grid, dw);
   QT_CHECK_LAUNCH();
   return QT_OK;
+}
+
+// One partial filter per workgroup in the workspace of qt_stem_bn_bwd_wgrad_workspace_bytes(batch), summed in workgroup
+// order: the same bits on every run (atomics into dw would depend on the order the workgroups finish in).
+extern "C" size_t qt_stem_bn_bwd_wgrad_workspace_bytes(int batch) {
+  const int grid = batch * 56 < 256 ? batch * 56 : 256;
+  return (size_t)grid * 64 * 7 * 32 * 4;
+}
+
+extern "C" int qt_stem_bn_bwd_wgrad_ws(int dtype, const void* dpooled, const unsigned char* argmax, const void* y,
+                                       const float* scale, const float* shift, const float* mean, const float* invstd,
+                                       const float* coef, const void* xpad, float* dw, void* workspace, size_t workspace_bytes,
+                                       int batch, void* stream) {
+  return stem_bn_bwd_wgrad(dtype, dpooled, argmax, y, scale, shift, mean, invstd, coef, xpad, dw, workspace, workspace_bytes,
+                           batch, stream);
 }
 
 // conv_wgrad_s2.hip: the stride-2 convolutions of a transition block (3x3 / 2 pad 1, 1x1 / 2) on parity planes (bf16)

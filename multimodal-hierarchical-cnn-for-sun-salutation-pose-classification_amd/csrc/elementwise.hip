@@ -832,10 +832,11 @@ __global__ void relu_mask_scale_kernel(T* __restrict__ g, const T* __restrict__ 
   }
 }
 
-// out[c] += sum over this block's row chunk of x[r*ld + c]  (out pre-zeroed unless accumulating)
+// out[c] += sum over this block's row chunk of x[r*ld + c]  (out pre-zeroed unless accumulating); with `part`, the chunk's
+// sum goes to part[blockIdx.y][c] instead and col_sum_finish_kernel adds the chunks in order
 template <typename T>
 __global__ void col_sum_kernel(const T* __restrict__ x, long long rows, int cols, int ld, float* __restrict__ out,
-                               int rows_per_block) {
+                               int rows_per_block, float* __restrict__ part) {
   __shared__ float red[4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
@@ -847,7 +848,30 @@ __global__ void col_sum_kernel(const T* __restrict__ x, long long rows, int cols
     for (long long r = r0 + rl; r < r1; r += 4) s += qt_to_f32<T>(x[r * ld + c]);
   red[rl][cl] = s;
   __syncthreads();
-  if (rl == 0 && c < cols) atomicAdd(out + c, red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl]);
+  if (rl == 0 && c < cols) {
+    const float v = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
+    if (part) part[(long long)blockIdx.y * cols + c] = v;
+    else atomicAdd(out + c, v);
+  }
+}
+
+// out[c] (+)= sum of part[0..nparts)[c] in a fixed order (1024 threads: 16 lanes per column, then the lanes in order)
+__global__ __launch_bounds__(1024) void col_sum_finish_kernel(const float* __restrict__ part, int nparts, int cols,
+                                                              float* __restrict__ out, int accumulate) {
+  __shared__ float red[16][64];
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  float s = 0.f;
+  if (c < cols)
+    for (int b = rl; b < nparts; b += 16) s += part[(long long)b * cols + c];
+  red[rl][cl] = s;
+  __syncthreads();
+  if (rl == 0 && c < cols) {
+    float v = 0.f;
+#pragma unroll
+    for (int l = 0; l < 16; ++l) v += red[l][cl];
+    out[c] = accumulate ? out[c] + v : v;
+  }
 }
 
 }  // namespace
@@ -1301,8 +1325,37 @@ extern "C" int qt_col_sum(int dtype, const void* x, long long rows, int cols, in
   by_dtype(dtype, [&](auto tag) {
     using T = QT_T(tag);
     hipLaunchKernelGGL(col_sum_kernel<T>, dim3(qt_cdiv(cols, 64), qt_cdiv(rows, rpb)), dim3(256), 0, s, (const T*)x,
-                       rows, cols, ld, out, rpb);
+                       rows, cols, ld, out, rpb, (float*)nullptr);
   });
+  QT_CHECK_LAUNCH();
+  return QT_OK;
+}
+
+// Deterministic form: row chunks of 128 rows (at most 1024 chunks), each chunk's column sums written to the workspace, then
+// added in chunk order (the same bits on every run; qt_col_sum's atomics depend on the order the chunks finish in)
+constexpr int kColSumMaxParts = 1024;
+extern "C" size_t qt_col_sum_workspace_bytes(long long rows, int cols) {
+  const long long nparts = rows < 1 ? 1 : (qt_cdiv(rows, 128) < kColSumMaxParts ? qt_cdiv(rows, 128) : kColSumMaxParts);
+  return (size_t)nparts * (cols < 1 ? 1 : cols) * 4;
+}
+
+extern "C" int qt_col_sum_ws(int dtype, const void* x, long long rows, int cols, int ld, float* out, int accumulate,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  QT_DT_OK(dtype, "qt_col_sum_ws");
+  QT_CHECK_ARG(x && out && workspace && rows > 0 && cols > 0 && ld >= cols, "qt_col_sum_ws: bad argument");
+  QT_CHECK_ARG(workspace_bytes >= qt_col_sum_workspace_bytes(rows, cols), "qt_col_sum_ws: workspace of %zu bytes < %zu",
+               workspace_bytes, qt_col_sum_workspace_bytes(rows, cols));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nparts = qt_cdiv(rows, 128) < kColSumMaxParts ? qt_cdiv(rows, 128) : kColSumMaxParts;
+  const int rpb = qt_cdiv(rows, nparts);
+  float* part = static_cast<float*>(workspace);
+  by_dtype(dtype, [&](auto tag) {
+    using T = QT_T(tag);
+    hipLaunchKernelGGL(col_sum_kernel<T>, dim3(qt_cdiv(cols, 64), qt_cdiv(rows, rpb)), dim3(256), 0, s, (const T*)x,
+                       rows, cols, ld, out, rpb, part);
+  });
+  hipLaunchKernelGGL(col_sum_finish_kernel, dim3(qt_cdiv(cols, 64)), dim3(1024), 0, s, (const float*)part,
+                     qt_cdiv(rows, rpb), cols, out, accumulate);
   QT_CHECK_LAUNCH();
   return QT_OK;
 }

@@ -387,7 +387,8 @@ void layout_workspace(qt_plan* p) {
   }
   p->dw_end = ws.off;
   // one partial filter per range of positions (at most 256 workgroups x 64 x 9 x 64 f32, whatever the
-  // batch): the streaming weight-gradient launches run one after another on the side stream and share it
+  // batch): the streaming weight-gradient launches run one after another on the side stream and share it, as do the
+  // deterministic stem weight gradient (<= 256 x 64 x 7 x 32 f32) and region-bias column sums (<= 1024 x 128 f32) there
   p->wgrad_part_bytes = (size_t)256 * 64 * 9 * 64 * 4;
   p->wgrad_part = ws.take(p->wgrad_part_bytes);
   {
@@ -1456,7 +1457,8 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
       e.run(qt_region_avgpool_bwd(dt, e.at(p->dfused), dt, e.at(cq.y), e.at(cq.gy), B, 2, 196, 128, p->fused_ld, 512, stream));
       if (e.gf(cq.bias)) {
         e.fork();
-        e.run(qt_col_sum(dt, e.at(cq.gy), (long long)B * 4 * 196, 128, 128, e.gf(cq.bias), 0, e.wstream ? e.wstream : stream));
+        e.run(qt_col_sum_ws(dt, e.at(cq.gy), (long long)B * 4 * 196, 128, 128, e.gf(cq.bias), 0, e.at(p->wgrad_part), p->wgrad_part_bytes,
+                          e.wstream ? e.wstream : stream));   // (wgrad_part: same stream as the wgrad launches)
       }
       e.wgrad(cq, e.region_desc(cq, 2, QT_CONV_FWD), e.at(p->blocks[3].out), false);
       // ---- attention gate (models.py:81-89), then the sub-quadrant vectors ----
@@ -1487,7 +1489,8 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
       e.run(qt_region_avgpool_bwd(dt, e.at(p->dvsub), QT_F32, e.at(cs.y), e.at(cs.gy), B, 4, 49, 64, 16 * 64, 0, stream));
       if (e.gf(cs.bias)) {
         e.fork();
-        e.run(qt_col_sum(dt, e.at(cs.gy), (long long)B * 16 * 49, 64, 64, e.gf(cs.bias), 0, e.wstream ? e.wstream : stream));
+        e.run(qt_col_sum_ws(dt, e.at(cs.gy), (long long)B * 16 * 49, 64, 64, e.gf(cs.bias), 0, e.at(p->wgrad_part), p->wgrad_part_bytes,
+                          e.wstream ? e.wstream : stream));   // (wgrad_part: same stream as the wgrad launches)
       }
       e.wgrad(cs, e.region_desc(cs, 4, QT_CONV_FWD), e.at(p->blocks[3].out), false);
     }
@@ -1497,7 +1500,8 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
       e.run(qt_quad_pool_bwd(dt, e.at(p->dfused), e.at(p->q), e.at(p->dq), B, p->fused_ld, 512, stream));
       if (e.gf(cq.bias)) {
         e.fork();
-        e.run(qt_col_sum(dt, e.at(p->dq), (long long)B * 196, 128, 128, e.gf(cq.bias), 0, e.wstream ? e.wstream : stream));
+        e.run(qt_col_sum_ws(dt, e.at(p->dq), (long long)B * 196, 128, 128, e.gf(cq.bias), 0, e.at(p->wgrad_part), p->wgrad_part_bytes,
+                          e.wstream ? e.wstream : stream));   // (wgrad_part: same stream as the wgrad launches)
       }
       e.wgrad(cq, e.quad_desc(QT_CONV_FWD), e.at(p->blocks[5].out), false);
     }
@@ -1618,10 +1622,11 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
         e.fork();
         void* ws_ = e.wstream;
         const int slot = e.begin_timed(e.conv_flops(e.stem_desc(true)), 2, ws_, e.wgrad_bytes(c0, e.stem_desc(true)));
-        const int st = qt_stem_bn_bwd_wgrad(dt, e.at(p->g_p0), e.at<unsigned char>(p->argmax), e.at(c0.y),
-                                            e.at<float>(bn0.scale), e.at<float>(bn0.shift), e.at<float>(bn0.mean),
-                                            e.at<float>(bn0.invstd), e.at<float>(bn0.coef), e.at(p->xpad),
-                                            e.at<float>(c0.dw), B, ws_);
+        // (deterministic form: partial filters in wgrad_part, which only launches on this same stream use)
+        const int st = qt_stem_bn_bwd_wgrad_ws(dt, e.at(p->g_p0), e.at<unsigned char>(p->argmax), e.at(c0.y),
+                                               e.at<float>(bn0.scale), e.at<float>(bn0.shift), e.at<float>(bn0.mean),
+                                               e.at<float>(bn0.invstd), e.at<float>(bn0.coef), e.at(p->xpad),
+                                               e.at<float>(c0.dw), e.at(p->wgrad_part), p->wgrad_part_bytes, B, ws_);
         e.end_timed(slot, ws_);
         if (st == QT_OK) {
           e.run(qt_unpack_stem_wgrad(e.at<float>(c0.dw), e.gf(c0.w), 0, ws_));

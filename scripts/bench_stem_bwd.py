@@ -1,5 +1,5 @@
-"""Developer aid: the one-launch stem backward (qt_stem_bn_bwd_wgrad) alone, B = 256 (QTCNN_STEM_BWD_FUSED=1|2 picks the form)."""
-import os, sys, torch
+"""Developer aid: the one-launch stem backward (qt_stem_bn_bwd_wgrad_ws: kernel + partial-filter sum) alone, B = 256 (QTCNN_STEM_BWD_FUSED=1|2 picks the form)."""
+import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from _util import pkg
@@ -15,8 +15,11 @@ am = torch.randint(0, 9, (B, 56, 56, 64), dtype=torch.uint8, device=dev)
 v = [torch.rand(64, device=dev) + 0.5 for _ in range(4)]
 coef = torch.rand(3, 64, device=dev)
 dw = torch.zeros(64, 7, 32, device=dev)
-fn = lambda: L.check(lib.qt_stem_bn_bwd_wgrad(qdt, L.ptr(dp), L.ptr(am), L.ptr(y), L.ptr(v[0]), L.ptr(v[1]), L.ptr(v[2]), L.ptr(v[3]),
-                                              L.ptr(coef), L.ptr(xpad), L.ptr(dw), B, st), "fused")
+lib.qt_stem_bn_bwd_wgrad_workspace_bytes.restype = ctypes.c_size_t
+nws = lib.qt_stem_bn_bwd_wgrad_workspace_bytes(B)
+ws = torch.empty(nws // 4, device=dev)
+fn = lambda: L.check(lib.qt_stem_bn_bwd_wgrad_ws(qdt, L.ptr(dp), L.ptr(am), L.ptr(y), L.ptr(v[0]), L.ptr(v[1]), L.ptr(v[2]), L.ptr(v[3]),
+                                                 L.ptr(coef), L.ptr(xpad), L.ptr(dw), L.ptr(ws), ctypes.c_size_t(nws), B, st), "fused")
 for _ in range(3): fn()
 torch.cuda.synchronize()
 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -93,3 +93,32 @@ def test_guarded_turns_an_exception_into_a_field():
         raise KeyError("families")
     out = bench.guarded("hbm summary", boom)
     assert "families" in out["error"]
+
+
+def test_dump_samples_are_seeded_and_bounded(tmp_path):
+    """--dump-outputs: small tensors whole, larger ones at positions fixed by the seed; float32 .npy files, 64 MB at most."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(7)
+    named = [("big", torch.randn(3 * bench.DUMP_SAMPLE_PER_TENSOR, generator=g).double()), ("small", torch.arange(5.0))]
+    a, b = bench.sample_flat(named, seed=3), bench.sample_flat(named, seed=3)
+    assert a.dtype == torch.float32 and a.numel() == bench.DUMP_SAMPLE_PER_TENSOR + 5
+    assert torch.equal(a, b) and not torch.equal(a, bench.sample_flat(named, seed=4))
+    assert torch.equal(a[-5:], torch.arange(5.0)) and bool(torch.isin(a[:-5], named[0][1].float()).all())
+    names = bench.dump_outputs(str(tmp_path / "d"), {"x": a, "loss": torch.tensor([1.5], dtype=torch.float64)})
+    assert names == ["loss", "x"]
+    x = np.load(tmp_path / "d" / "x.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, a.numpy())
+    assert np.load(tmp_path / "d" / "loss.npy").tolist() == [1.5]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "e"), {"huge": torch.zeros(bench.DUMP_MAX_BYTES // 4 + 1)})
+    assert not (tmp_path / "e").exists()
+
+
+def test_plain_and_full_options_parse(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 4 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"

@@ -792,3 +792,37 @@ def test_linear_splitk_bf16(cfg):
     # uncovered shapes are reported, not mangled
     assert lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), relu, L.ptr(y), 300, N, K, L.ptr(ws), ctypes.c_size_t(nbytes),
                               L.stream_ptr()) == -3   # QT_ERR_UNSUPPORTED
+
+
+@pytest.mark.parametrize("dt,rows,cols,ld", [(torch.bfloat16, 50176, 128, 128), (torch.float32, 12544, 64, 80),
+                                              (torch.bfloat16, 300, 1, 1), (torch.bfloat16, 200704, 128, 128)])
+def test_col_sum_ws_is_deterministic(dt, rows, cols, ld):
+    """qt_col_sum_ws (bias gradients of the region heads): the column sums of qt_col_sum, added in a fixed chunk order --
+    the same bits on every run, also when accumulating into `out`."""
+    dev = _dev()
+    L = pkg("_lib")
+    lib = L.lib()
+    st = L.stream_ptr()
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(rows, ld, generator=g).to(dt).to(dev)
+    ref = x[:, :cols].double().sum(0).cpu()
+    lib.qt_col_sum_workspace_bytes.restype = ctypes.c_size_t
+    nws = lib.qt_col_sum_workspace_bytes(ctypes.c_longlong(rows), cols)
+    assert nws == min(-(-rows // 128), 1024) * cols * 4
+    runs = []
+    for acc in (0, 0, 1):
+        ws = torch.full((nws // 4,), float("nan"), device=dev)
+        out = torch.ones(cols, device=dev)
+        L.check(lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(x), ctypes.c_longlong(rows), cols, ld, L.ptr(out), acc, L.ptr(ws),
+                                  ctypes.c_size_t(nws), st), "qt_col_sum_ws")
+        torch.cuda.synchronize()
+        runs.append(out.cpu())
+    assert torch.equal(runs[0], runs[1])
+    assert torch.equal(runs[2], runs[0] + 1)
+    assert rel_err(runs[0], ref) <= 1e-5
+    atomic = torch.empty(cols, device=dev)
+    L.check(lib.qt_col_sum(L.qt_dtype(dt), L.ptr(x), ctypes.c_longlong(rows), cols, ld, L.ptr(atomic), 0, st), "qt_col_sum")
+    torch.cuda.synchronize()
+    assert rel_err(runs[0], atomic.cpu()) <= 1e-5
+    assert lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(x), ctypes.c_longlong(rows), cols, ld, L.ptr(atomic), 0, L.ptr(ws),
+                             ctypes.c_size_t(nws - 4), st) != 0

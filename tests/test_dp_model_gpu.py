@@ -172,7 +172,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
     env = dict(os.environ, QTCNN_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", "--profile-steps", "0"]
+           "--full", "--no-cpu-baseline", "--profile-steps", "0"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

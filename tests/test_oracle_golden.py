@@ -98,8 +98,11 @@ def test_oracle_attention_model(golden_attn):
         smp, gold = summary(leaves[n].grad)["sample"], golden_attn[f"train/grad/{n}/sample"]
         head = n.split(".")[0] in ("quadrant_processor", "sub_quadrant_processor", "attention_gate", "numerical_mlp", "classifier")
         tol = 1e-4 if head else 5e-2  # an isolated ReLU may flip under another summation order (tests/test_model_gpu.py)
-        # attention_gate.2.bias: softmax is shift invariant, the gradient is rounding noise around zero
-        scale = max(float(np.abs(gold).max()), 1e-6 if n == "attention_gate.2.bias" else 1e-30)
+        # attention_gate.2.bias: softmax is shift invariant, the gradient is rounding noise around zero whose size follows
+        # the host's summation order (1.5e-9 when the vectors were made, 1.3e-8 on another CPU): measured against the
+        # gradient of the same layer's weight, i.e. it must vanish relative to the gradients that flow through the gate
+        floor = float(np.abs(golden_attn["train/grad/attention_gate.2.weight/sample"]).max()) if n == "attention_gate.2.bias" else 1e-30
+        scale = max(float(np.abs(gold).max()), floor)
         assert float(np.abs(smp - gold).max()) <= tol * scale, n
     for k in golden_attn.files:
         if k.startswith("train/buf/") and k.endswith("/shape"):

@@ -130,15 +130,28 @@ def test_stem_pool_and_fused_backward(dt, tol):
     d.src_pix_stride, d.src_row_stride, d.src_img_stride = 4, 232 * 4, 230 * 232 * 4
     dw_ref = torch.zeros(64, 7, 32, **f32)
     L.check(lib.qt_conv2d_wgrad(ctypes.byref(d), L.ptr(dy), L.ptr(xpad), L.ptr(dw_ref), st), "qt_conv2d_wgrad")
-    dw = torch.zeros(64, 7, 32, **f32)
-    rc = lib.qt_stem_bn_bwd_wgrad(qdt, L.ptr(dpd), L.ptr(argmax), L.ptr(yd), L.ptr(sc), L.ptr(sh), L.ptr(mu), L.ptr(isd),
-                                  L.ptr(coef), L.ptr(xpad), L.ptr(dw), B, st)
-    torch.cuda.synchronize()
+    # (partial filters per workgroup in a workspace, summed in workgroup order: the same sums, the same bits on every run)
+    lib.qt_stem_bn_bwd_wgrad_workspace_bytes.restype = ctypes.c_size_t
+    nws = lib.qt_stem_bn_bwd_wgrad_workspace_bytes(B)
+    assert nws == min(B * 56, 256) * 64 * 7 * 32 * 4
+
+    def fused(ws_bytes):
+        ws = torch.full((nws // 4,), float("nan"), **f32)
+        dw = torch.zeros(64, 7, 32, **f32)
+        rc = lib.qt_stem_bn_bwd_wgrad_ws(qdt, L.ptr(dpd), L.ptr(argmax), L.ptr(yd), L.ptr(sc), L.ptr(sh), L.ptr(mu), L.ptr(isd),
+                                         L.ptr(coef), L.ptr(xpad), L.ptr(dw), L.ptr(ws), ctypes.c_size_t(ws_bytes), B, st)
+        torch.cuda.synchronize()
+        return rc, dw.cpu()
+
+    rc, dw = fused(nws)
     if dt == torch.float32:
         assert rc != 0                                        # (the f32 build keeps the two-kernel form)
     else:
         assert rc == 0, L.last_error()
-        assert rel_err(dw.cpu(), dw_ref.cpu()) <= 2e-3        # same bf16 gradient values, another summation order
+        assert rel_err(dw, dw_ref.cpu()) <= 2e-3              # same bf16 gradient values, another summation order
+        rc2, dw2 = fused(nws)
+        assert rc2 == 0 and torch.equal(dw, dw2)
+        assert fused(nws - 4)[0] != 0                         # a workspace too small is refused
 
 
 def _stem_conv(L, dt, image, w, taps, want_stats, scale=None, shift=None, relu=0):
