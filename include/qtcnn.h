@@ -401,6 +401,12 @@ size_t qt_stem_bn_bwd_wgrad_workspace_bytes(int batch);
 int qt_stem_bn_bwd_wgrad_ws(int dtype, const void* dpooled, const unsigned char* argmax, const void* y, const float* scale,
                             const float* shift, const float* mean, const float* invstd, const float* coef, const void* xpad,
                             float* dw, void* workspace, size_t workspace_bytes, int batch, void* stream);
+/* Data gradient of conv1 down to the image: dx [B][3][224][224] f32 NCHW (written, not accumulated) =
+ * conv_transpose2d(dy, w, stride 2, padding 3) from dy = d(loss)/d(conv1 output) [B][112][112][64] in `dtype` (bf16 or
+ * f32; 16-byte aligned) and conv1's f32 OIHW master weight [64][3][7][7].  One MFMA GEMM over 2 x 2 image blocks
+ * (K = 4 x 4 dy positions x 64 channels, N = 3 channels x 4 parities); the bf16 build splits the weight into two bf16
+ * halves, so dy's own rounding is the only one.  QT_ERR_UNSUPPORTED for any other dtype or alignment. */
+int qt_stem_dgrad(int dtype, const void* dy, const float* w_oihw, float* dx, int batch, void* stream);
 /* AdaptiveAvgPool2d(1,1)+flatten into columns [col0, col0+C) of the fused feature
  * matrix (Quadtree_from scratch/models.py:242,289-294) and its backward fused with the
  * ReLU mask of the pooled map. */
@@ -640,6 +646,14 @@ int qt_avgpool_tb_bwd(int dtype, const float* d, void* g, int frames, int batch,
  *                          QT_BWD_LAYER32 = layers 3 and 2, QT_BWD_LAYER1 = layer1 and the stem
  *                          (lets the caller start the gradient all-reduce of a bucket while the
  *                          next phase runs; the last bucket is 0.6 MB).
+ *   qt_plan_backward_dx  : the same, and with dimage != NULL also d(loss)/d(image) [B,3,224,224] f32 NCHW (written,
+ *                          not accumulated, in the QT_BWD_LAYER1 phase, for the batch of the last forward): the backbone
+ *                          is walked for its data gradients even where no backbone gradient is requested (frozen
+ *                          backbone: BatchNorm backward and data gradients, no weight gradient), and qt_stem_dgrad
+ *                          runs on conv1's output gradient.  Parameter gradients are the same bits as without dimage.
+ *                          Needs qt_plan_pack_weights(for_backward = 1) and a forward with training 1 or 2;
+ *                          QT_ERR_UNSUPPORTED after training == 0 and for QT_MODEL_CNN_LSTM.  dimage == NULL is
+ *                          qt_plan_backward.
  * ------------------------------------------------------------------------ */
 enum { QT_MODEL_QUADTREE = 0, QT_MODEL_STANDARD_RESNET = 1, QT_MODEL_ATTENTION = 2, QT_MODEL_CNN_LSTM = 3 };
 enum { QT_MODE_FUSION = 0, QT_MODE_IMAGE_ONLY = 1, QT_MODE_NUMERICAL_ONLY = 2 };
@@ -703,6 +717,8 @@ int qt_plan_forward(qt_plan* plan, void* workspace, void* const* tensors, const 
                     float* logits, int batch, int training, unsigned long long seed, void* stream);
 int qt_plan_backward(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads, const float* numerical,
                      const float* dlogits, int phases, void* stream);
+int qt_plan_backward_dx(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads,
+                        const float* numerical, const float* dlogits, int phases, float* dimage, void* stream);
 
 #ifdef __cplusplus
 }

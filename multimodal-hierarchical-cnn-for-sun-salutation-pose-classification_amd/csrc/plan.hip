@@ -1278,7 +1278,19 @@ struct Bwd : Exec {
 };
 
 int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const float* numerical,
-             const float* dlogits, int phases, void* stream) {
+             const float* dlogits, int phases, float* dimage, void* stream) {
+  if (dimage && p->lstm) {
+    qt_set_error("qt_plan_backward_dx: CnnLstm has no input gradient (its ResNet-18 is frozen and gradients through the "
+                 "LSTM into the backbone are not implemented)");
+    return QT_ERR_UNSUPPORTED;
+  }
+  if (dimage && p->has_image && p->last_training == 0) {
+    qt_set_error("qt_plan_backward_dx: the last forward ran fused eval kernels (training = 0) and kept nothing for a "
+                 "backward to the image; run it with training = 2 (eval statistics, tensors kept)");
+    return QT_ERR_UNSUPPORTED;
+  }
+  QT_CHECK_ARG(!dimage || !p->has_image || p->packed_bwd,
+               "qt_plan_backward_dx: the data-gradient operands are not packed (qt_plan_pack_weights with for_backward = 1)");
   Bwd e;
   e.p = p; e.ws = static_cast<unsigned char*>(workspace); e.T = T; e.stream = stream; e.B = p->last_batch;
   e.dt = p->d.dtype; e.G = G;
@@ -1299,6 +1311,10 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
       if ((int)i == p->quad_conv || (int)i == p->sub_conv) continue;
       if (G[p->convs[i].w]) backbone_grads = true;
     }
+  // d(loss)/d(image) wanted: the backbone is walked for its data gradients even where it is frozen (weight gradients
+  // are skipped per tensor: wgrad and the BatchNorm finalize take NULL gradients)
+  const bool want_dx = dimage != nullptr && p->has_image;
+  const bool walk = backbone_grads || want_dx;
   if (backbone_grads && p->last_training == 0) {
     qt_set_error("qt_plan_backward: the last forward ran fused eval kernels (training = 0) and kept nothing for a backbone "
                  "backward; run it with training = 2 (eval statistics, tensors kept)");
@@ -1399,7 +1415,7 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
         e.end_timed(slot, ss);
       }
     }
-    const bool need_dfused = p->has_numerical || (p->has_image && (!p->standard || backbone_grads));
+    const bool need_dfused = p->has_numerical || (p->has_image && (!p->standard || walk));
     if (need_dfused)
       e.linear(e.linear_desc(p->cls0.in, p->cls0.out, QT_CONV_DGRAD), e.at(p->dhidden), e.at(p->cls0.w_dgrad), e.at(p->dfused),
                nullptr, 0);
@@ -1514,7 +1530,7 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
   // parameters), QT_BWD_LAYER32 (blocks 5..2: 2.6 M), QT_BWD_LAYER1 (blocks 1, 0 and the stem: 0.16 M) -- so
   // that a data-parallel caller reduces each bucket while the next phase runs and only 0.6 MB of gradients
   // is left to reduce after the last kernel.
-  if ((phases & QT_BWD_BACKBONE) && backbone_grads) {
+  if ((phases & QT_BWD_BACKBONE) && walk) {
     const bool do_l4 = (phases & QT_BWD_LAYER4) != 0, do_l32 = (phases & QT_BWD_LAYER32) != 0;
     const bool do_rest = (phases & QT_BWD_LAYER1) != 0;  // the last phase: layer1 and the stem
     int rows_bn2 = 0;  // partial rows of bn2 / downsample-BN of the block being entered (0 = none yet)
@@ -1635,7 +1651,7 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
           e.run(st);
         }
       }
-      if (!stem_done)
+      if (!stem_done || want_dx)   // (with the one-launch form on the side stream: the map for qt_stem_dgrad only)
         e.run(qt_stem_bn_bwd_apply(dt, e.at(p->g_p0), e.at<unsigned char>(p->argmax), e.at(c0.y), e.at<float>(bn0.scale),
                                    e.at<float>(bn0.shift), e.at<float>(bn0.mean), e.at<float>(bn0.invstd),
                                    e.at<float>(bn0.coef), e.at(c0.gy), B, stream));
@@ -1645,10 +1661,12 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
       e.bn_backward(c0, e.at(c0.gy), nullptr);
     }
     if (!stem_done) e.wgrad(c0, e.stem_desc(true), e.at(p->xpad), true);
+    // d(loss)/d(image) on the main stream, beside the stem's weight gradient on the side stream
+    if (want_dx) e.run(qt_stem_dgrad(dt, e.at(c0.gy), e.tf(c0.w), dimage, B, stream));
     }
   }
   // the last phase (or a head-only model) joins: afterwards the caller's stream sees every gradient
-  if ((phases & QT_BWD_LAYER1) || !backbone_grads) {
+  if ((phases & QT_BWD_LAYER1) || !walk) {
     e.forked = e.forked || (p->side != nullptr && e.wstream == p->side);
     e.join();
   }
@@ -1845,5 +1863,14 @@ extern "C" int qt_plan_backward(qt_plan* p, void* workspace, void* const* tensor
   QT_CHECK_ARG(p && workspace && tensors && grads && dlogits, "qt_plan_backward: null argument");
   QT_CHECK_ARG(p->last_batch > 0, "qt_plan_backward: no forward pass recorded");
   QT_CHECK_ARG(!p->has_numerical || numerical, "qt_plan_backward: numerical input required");
-  return backward(p, workspace, tensors, grads, numerical, dlogits, phases, stream);
+  return backward(p, workspace, tensors, grads, numerical, dlogits, phases, nullptr, stream);
+}
+
+extern "C" int qt_plan_backward_dx(qt_plan* p, void* workspace, void* const* tensors, float* const* grads,
+                                   const float* numerical, const float* dlogits, int phases, float* dimage, void* stream) {
+  if (!dimage) return qt_plan_backward(p, workspace, tensors, grads, numerical, dlogits, phases, stream);
+  QT_CHECK_ARG(p && workspace && tensors && grads && dlogits, "qt_plan_backward_dx: null argument");
+  QT_CHECK_ARG(p->last_batch > 0, "qt_plan_backward_dx: no forward pass recorded");
+  QT_CHECK_ARG(!p->has_numerical || numerical, "qt_plan_backward_dx: numerical input required");
+  return backward(p, workspace, tensors, grads, numerical, dlogits, phases, dimage, stream);
 }

@@ -67,6 +67,8 @@ def _bind_api(L):
                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_void_p]
     L.qt_plan_backward.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    L.qt_plan_backward_dx.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.qt_plan_side_fence.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.qt_plan_adam_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.POINTER(AdamDesc), ctypes.c_int, ctypes.c_void_p]
@@ -248,12 +250,14 @@ class PlanEngine:
             ends[b] = max(ends[b], ends[b - 1])
         return offs, sizes, ends, total
 
-    def backward(self, dlogits, numerical, wanted):
+    def backward(self, dlogits, numerical, wanted, dimage=None):
         """wanted: list of (plan tensor index, shape) in the order gradients are
         returned.  Gradients are views of one flat f32 buffer laid out
         [head | layer4 | layer3 + layer2 | layer1 + stem]: the order in which backward finishes them, so a
         data-parallel caller all-reduces four buckets (59 / 34 / 10.5 / 0.6 MB), each while the next phase
-        runs; only the last, smallest one is exposed."""
+        runs; only the last, smallest one is exposed.
+        dimage: optional contiguous f32 [B,3,224,224] tensor that receives d(loss)/d(image) (written by the
+        last phase, qt_plan_backward_dx)."""
         offs, sizes, ends, total = self.gradient_buckets(self.names, wanted)
         # One flat buffer per (layout): re-used across steps unless a previous step's gradient views are still
         # referenced by the caller (`.grad` kept with zero_grad(set_to_none=False), accumulation, retained graphs):
@@ -273,9 +277,15 @@ class PlanEngine:
             self._weights_stale = True
 
         def run(phase):
-            _lib.check(self.L.qt_plan_backward(self.handle, self.ws_ptr, self._tensor_ptrs, grad_ptrs,
-                                               _lib.ptr(numerical), _lib.ptr(dlogits), phase, _lib.stream_ptr()),
-                       "qt_plan_backward")
+            if dimage is None:
+                _lib.check(self.L.qt_plan_backward(self.handle, self.ws_ptr, self._tensor_ptrs, grad_ptrs,
+                                                   _lib.ptr(numerical), _lib.ptr(dlogits), phase, _lib.stream_ptr()),
+                           "qt_plan_backward")
+            else:
+                _lib.check(self.L.qt_plan_backward_dx(self.handle, self.ws_ptr, self._tensor_ptrs, grad_ptrs,
+                                                      _lib.ptr(numerical), _lib.ptr(dlogits), phase, _lib.ptr(dimage),
+                                                      _lib.stream_ptr()),
+                           "qt_plan_backward_dx")
 
         if self.grad_sync is None:
             run(QT_BWD_ALL)
@@ -309,6 +319,9 @@ class PlanFunction(torch.autograd.Function):
         ctx.numerical = numerical
         ctx.param_index = owner._param_plan_index
         ctx.param_shapes = [tuple(p.shape) for p in params]
+        ctx.image_shape = None if image is None else tuple(image.shape)
+        # d(loss)/d(image): the 2-D models (decided in _PlanModel._run, which also kept what the backward needs)
+        ctx.image_grad = getattr(owner, "_image_grad", False)
         owner._fire_layer4_forward_hooks(engine, logits.shape[0])
         return logits
 
@@ -321,7 +334,10 @@ class PlanFunction(torch.autograd.Function):
         needs = ctx.needs_input_grad[3:]
         wanted = [(ctx.param_index[i], ctx.param_shapes[i]) for i, need in enumerate(needs)
                   if need and ctx.param_index[i] >= 0]
-        grads = engine.backward(dlogits.contiguous().float(), ctx.numerical, wanted)
+        dimage = None
+        if ctx.needs_input_grad[1] and ctx.image_grad and ctx.image_shape is not None:
+            dimage = torch.empty(ctx.image_shape, dtype=torch.float32, device=engine.device)
+        grads = engine.backward(dlogits.contiguous().float(), ctx.numerical, wanted, dimage)
         ctx.owner._fire_layer4_backward_hooks(engine, dlogits.shape[0])
         out, k = [], 0
         for i, need in enumerate(needs):
@@ -330,4 +346,4 @@ class PlanFunction(torch.autograd.Function):
                 k += 1
             else:
                 out.append(None)
-        return (None, None, None, *out)
+        return (None, dimage, None, *out)

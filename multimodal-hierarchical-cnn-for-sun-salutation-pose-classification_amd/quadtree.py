@@ -34,6 +34,7 @@ class _PlanModel(nn.Module):
         self._param_plan_index = None
         self._grad_sync = None  # set by dp.attach_data_parallel
         self._eval_keep_for_backward = False
+        self._image_grad = False  # the last forward's image requires grad and the plan serves it (qt_plan_backward_dx)
 
     # engines hold device memory and ctypes handles: keep them out of pickles / deepcopy
     def __getstate__(self):
@@ -179,9 +180,13 @@ class _PlanModel(nn.Module):
         with torch.cuda.device(device):
             eng = self._ensure_engine(batch, device)
             version = self._bind(eng)
-            need_bwd = torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list)
+            # d(loss)/d(image) is served for the 2-D models (not CnnLstm): it needs the backbone's data-gradient operands
+            # packed and, in eval(), a forward that keeps what the backward reads -- as a trainable backbone does
+            self._image_grad = torch.is_grad_enabled() and image_input is not None and image_input.requires_grad and \
+                self._model_kind != _engine.QT_MODEL_CNN_LSTM
+            need_bwd = torch.is_grad_enabled() and (self._image_grad or any(p.requires_grad for p in self._param_list))
             eng.pack_weights(version, need_bwd)
-            self._eval_keep_for_backward = (not self.training) and self._eval_needs_backbone_backward()
+            self._eval_keep_for_backward = (not self.training) and (self._image_grad or self._eval_needs_backbone_backward())
             return _engine.PlanFunction.apply(self, image_input, numerical_input, *self._param_list)
 
 
