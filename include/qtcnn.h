@@ -261,7 +261,8 @@ int qt_pack_conv_weight(int dtype, const float* w_oihw, void* w_fwd, void* w_dgr
  * result as qt_pack_conv_weight, or, with stride2_dgrad != 0 and k == 3, w_dgrad in the parity-class
  * layout of qt_pack_dgrad_s2 (stride2_dgrad = 1) or the merged layout of qt_pack_dgrad_s2_merged (= 2; only the
  * nine real taps are written: the zero slots of w_dgrad must have been zeroed once).  O and I must be multiples of
- * 32 (k = 3) or 64 (k = 1); at most 32 items. */
+ * 32 (k = 3) or 64 (k = 1); at most 32 items.  Every pointer (masters, copies, and for the Adam form gradients and
+ * moments) must be 16-byte aligned: the f32 streams move as float4. */
 typedef struct qt_pack_item {
   const float* w_oihw;
   void* w_fwd;   /* nullable */
@@ -713,6 +714,18 @@ int qt_plan_pack_weights(qt_plan* plan, void* workspace, void* const* tensors, i
  * updated inside the one-launch packing kernel, the rest by qt_adam_multi. */
 int qt_plan_adam_step(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads, float* const* exp_avg,
                       float* const* exp_avg_sq, const qt_adam_desc* adam, int for_backward, void* stream);
+/* qt_plan_adam_step with its bulk beside the fused stem backward.  When the plan's last operation was a full
+ * qt_plan_backward (QT_BWD_ALL, no image gradient, bf16, side stream on) whose stem backward ran on `stream`, the batched
+ * Adam + re-pack and the plain tensors are enqueued on the plan's side stream, which that backward ordered behind
+ * everything it launched before that kernel; conv1's filter (the only gradient the stem backward produces) is updated and packed on `stream`, and `stream`
+ * waits for the side stream before the call returns: afterwards the whole step is ordered before later work on
+ * `stream`, exactly as for qt_plan_adam_step.  In every other state the call IS qt_plan_adam_step.
+ * The side stream is ordered behind the plan's own launches only.  The caller guarantees that nothing enqueued on
+ * `stream` since that backward writes the gradients or the optimizer state, or reads or writes the parameters.
+ * *overlapped (may be NULL) receives 1 if the overlapped order was used, 0 for the serial one. */
+int qt_plan_adam_step_overlapped(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads,
+                                 float* const* exp_avg, float* const* exp_avg_sq, const qt_adam_desc* adam, int for_backward,
+                                 void* stream, int* overlapped);
 int qt_plan_forward(qt_plan* plan, void* workspace, void* const* tensors, const float* image, const float* numerical,
                     float* logits, int batch, int training, unsigned long long seed, void* stream);
 int qt_plan_backward(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads, const float* numerical,

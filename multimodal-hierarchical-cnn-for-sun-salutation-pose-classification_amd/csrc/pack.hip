@@ -6,6 +6,7 @@
 //    -> [O][kh][kw][I] forward operand and [I][kh][kw][O] data-gradient operand.
 //  * [O][kh][kw][I] f32 weight gradients -> OIHW f32 .grad tensors.
 #include <math.h>
+#include <stdint.h>
 #include <string.h>
 
 #include "qt_common.h"
@@ -61,10 +62,10 @@ __global__ void pack_conv_weight_kernel(const float* __restrict__ w, T* __restri
   }
 }
 
-// All conv / linear weights of a model in ONE launch.  A block transposes a 32(o) x 32(i) x taps
+// All conv / linear weights of a model in ONE launch.  A block transposes a 16(o) x 32(i) x 9 (3x3) or 64 x 64 (1x1)
 // tile through LDS: the OIHW rows are read as contiguous runs of 32*taps floats, the forward operand
 // [o][tap][i] is written in runs of 32 i, the data-gradient operand [i][tap][o] (or its parity-class
-// form for stride-2 convs, see pack_dgrad_s2_kernel) in runs of 32 o.  The per-element kernels above
+// form for stride-2 convs, see pack_dgrad_s2_kernel) in runs of 16 o.  The per-element kernels above
 // scatter 2-byte stores with a stride of taps*O elements and need one launch per layer (0.42 ms per
 // training step for the 26 M parameters of QuadtreeCNN); this one moves the same bytes in ~60 us.
 // Adam with L2-in-gradient weight decay, torch.optim.Adam semantics (amsgrad / maximize off):
@@ -78,12 +79,16 @@ struct AdamScalars {
   float grad_scale;    // multiplies the incoming gradient (1 = none)
   int enabled;
 };
+// Every rounding is spelled out, so that the scalar and the float4 callers, and any compiler version, produce the same
+// bits: four fused multiply-adds, and the second moment as two rounded products and a rounded sum.
 __device__ __forceinline__ float adam_update(float p, float g, float& m, float& v, const AdamScalars& h) {
-  g = g * h.grad_scale + h.wd * p;
-  m = h.b1 * m + (1.f - h.b1) * g;
-  v = h.b2 * v + (1.f - h.b2) * g * g;
-  const float denom = sqrtf(v) * h.inv_sqrt_bc2 + h.eps;
-  return p - h.step_size * (m / denom);
+  g = __builtin_fmaf(h.wd, p, g * h.grad_scale);
+  m = __builtin_fmaf(h.b1, m, (1.f - h.b1) * g);
+  float v_old = h.b2 * v, v_new = (1.f - h.b2) * g * g;
+  asm("" : "+v"(v_old), "+v"(v_new));  // (the build contracts any product it can see into the sum, -ffp-contract=fast)
+  v = v_old + v_new;
+  const float denom = __builtin_fmaf(sqrtf(v), h.inv_sqrt_bc2, h.eps);
+  return __builtin_fmaf(-h.step_size, m / denom, p);
 }
 
 constexpr int PK_MAX_ITEMS = 32;
@@ -101,51 +106,66 @@ struct PackBatchArgs {
   int n;
 };
 
-template <typename T> struct PackPair;  // two consecutive elements as one store
-template <> struct PackPair<float> {
-  static __device__ __forceinline__ void store(float* p, float a, float b) { *reinterpret_cast<float2*>(p) = make_float2(a, b); }
+template <typename T> struct PackQuad;  // four consecutive elements as one store
+template <> struct PackQuad<float> {
+  static __device__ __forceinline__ void store(float* p, float a, float b, float c, float d) {
+    *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
+  }
 };
-template <> struct PackPair<bf16_t> {
-  static __device__ __forceinline__ void store(bf16_t* p, float a, float b) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    bf16x2 v = {(bf16_t)a, (bf16_t)b};
-    *reinterpret_cast<bf16x2*>(p) = v;
+template <> struct PackQuad<bf16_t> {
+  static __device__ __forceinline__ void store(bf16_t* p, bf16_t a, bf16_t b, bf16_t c, bf16_t d) {
+    bf16x4 v = {a, b, c, d};
+    *reinterpret_cast<bf16x4*>(p) = v;
   }
 };
 
-// one TO(o) x TI(i) x TAPS tile; `tile` holds it as [o][i*TAPS + tap] with an odd row stride
+// one TO(o) x TI(i) x TAPS tile; `tile` holds it, already rounded to the compute dtype, as [o][i*TAPS + tap] with a
+// padded row stride.  The four f32 streams (master, gradient, both moments) move as float4: a row of the tile is
+// TI*TAPS contiguous floats that start 16-byte aligned (TI is a multiple of 4, the base pointers are checked).
 template <typename T, int TAPS, int TO, int TI>
-__device__ __forceinline__ void pack_tile(float* tile, const float* w, T* __restrict__ fwd, T* __restrict__ dg,
+__device__ __forceinline__ void pack_tile(T* tile, const float* w, T* __restrict__ fwd, T* __restrict__ dg,
                                           int O, int I, int o0, int i0, int s2, const AdamScalars& adam,
                                           const float* __restrict__ g, float* m, float* v) {
-  constexpr int RUN = TI * TAPS, S = RUN + 1, TOTAL = TO * RUN;
-  for (int e = threadIdx.x; e < TOTAL; e += 256) {
-    const int o = e / RUN, r = e - o * RUN;
+  constexpr int RUN = TI * TAPS, S = RUN + (TAPS == 1 ? 2 : 4), TOTAL = TO * RUN;
+  static_assert(RUN % 4 == 0 && TO % 4 == 0 && TI % 4 == 0, "tiles move in groups of four");
+#pragma unroll 1
+  for (int e = threadIdx.x; e < TOTAL / 4; e += 256) {
+    const int o = e / (RUN / 4), r = (e - o * (RUN / 4)) * 4;
     const long long idx = ((long long)(o0 + o) * I + i0) * TAPS + r;
-    float pv = w[idx];
+    float4 pv = *reinterpret_cast<const float4*>(w + idx);
     if (adam.enabled) {  // optimizer step on the f32 master, then the fresh value is what gets packed
-      float mv = m[idx], vv = v[idx];
-      pv = adam_update(pv, g[idx], mv, vv, adam);
-      m[idx] = mv;
-      v[idx] = vv;
-      const_cast<float*>(w)[idx] = pv;
+      float4 gv = *reinterpret_cast<const float4*>(g + idx);
+      float4 mv = *reinterpret_cast<const float4*>(m + idx), vv = *reinterpret_cast<const float4*>(v + idx);
+      pv.x = adam_update(pv.x, gv.x, mv.x, vv.x, adam);
+      asm volatile("" : "+v"(pv.x), "+v"(gv.y));
+      pv.y = adam_update(pv.y, gv.y, mv.y, vv.y, adam);
+      asm volatile("" : "+v"(pv.y), "+v"(gv.z));
+      pv.z = adam_update(pv.z, gv.z, mv.z, vv.z, adam);
+      asm volatile("" : "+v"(pv.z), "+v"(gv.w));
+      pv.w = adam_update(pv.w, gv.w, mv.w, vv.w, adam);
+      *reinterpret_cast<float4*>(m + idx) = mv;
+      *reinterpret_cast<float4*>(v + idx) = vv;
+      *reinterpret_cast<float4*>(const_cast<float*>(w) + idx) = pv;
     }
-    tile[o * S + r] = pv;
+    T* t = tile + o * S + r;
+    t[0] = qt_from_f32<T>(pv.x); t[1] = qt_from_f32<T>(pv.y); t[2] = qt_from_f32<T>(pv.z); t[3] = qt_from_f32<T>(pv.w);
   }
   __syncthreads();
   if (fwd) {
-    for (int e = threadIdx.x; e < TOTAL / 2; e += 256) {
-      const int i = (e % (TI / 2)) * 2, ot = e / (TI / 2);
+#pragma unroll 1
+    for (int e = threadIdx.x; e < TOTAL / 4; e += 256) {
+      const int i = (e % (TI / 4)) * 4, ot = e / (TI / 4);
       const int o = ot / TAPS, tap = ot - o * TAPS;
-      const float* t = tile + o * S + i * TAPS + tap;
-      PackPair<T>::store(fwd + ((long long)(o0 + o) * TAPS + tap) * I + i0 + i, t[0], t[TAPS]);
+      const T* t = tile + o * S + i * TAPS + tap;
+      PackQuad<T>::store(fwd + ((long long)(o0 + o) * TAPS + tap) * I + i0 + i, t[0], t[TAPS], t[2 * TAPS], t[3 * TAPS]);
     }
   }
   if (dg) {
-    for (int e = threadIdx.x; e < TOTAL / 2; e += 256) {
-      const int o = (e % (TO / 2)) * 2, it2 = e / (TO / 2);
+#pragma unroll 1
+    for (int e = threadIdx.x; e < TOTAL / 4; e += 256) {
+      const int o = (e % (TO / 4)) * 4, it2 = e / (TO / 4);
       const int i = it2 / TAPS, tap = it2 - i * TAPS;
-      const float* t = tile + o * S + i * TAPS + tap;
+      const T* t = tile + o * S + i * TAPS + tap;
       long long dst;
       if (TAPS == 1 && s2 == 4) {
         // the fifth tap slot of the block's merged stride-2 operand (rows of class (0,0), five slots per row)
@@ -166,17 +186,21 @@ __device__ __forceinline__ void pack_tile(float* tile, const float* w, T* __rest
         if (s2 == 2) dst = (((long long)cls * I + i0 + i) * 4 + th * 2 + tw) * O + o0 + o;
         if (s2 == 3) dst = (((long long)cls * I + i0 + i) * 5 + th * 2 + tw) * O + o0 + o;   // (five slots per row, slot 4: see above)
       }
-      PackPair<T>::store(dg + dst, t[0], t[S]);
+      PackQuad<T>::store(dg + dst, t[0], t[S], t[2 * S], t[3 * S]);
     }
   }
 }
 
-constexpr int PK_T1 = 64;  // tile edge of 1x1 filters; 3x3 filters use 32
+// tile edges: 1x1 filters 64(o) x 64(i), 3x3 filters 16(o) x 32(i).  Staged in the compute dtype, a bf16 tile takes
+// 9.1 KB of LDS: the workgroups are light enough to be resident beside a kernel that owns most of a CU's LDS (the
+// fused stem backward, see qt_plan_adam_step_overlapped).
+constexpr int PK_T1 = 64, PK_T3O = 16, PK_T3I = 32;
+constexpr int PK_TILE_ELEMS = PK_T3O * (PK_T3I * 9 + 4);
 
 template <typename T>
 __global__ __launch_bounds__(256) void pack_weights_batched_kernel(PackBatchArgs a) {
-  __shared__ float tile[32 * (32 * 9 + 1)];
-  static_assert(PK_T1 * (PK_T1 + 1) <= 32 * (32 * 9 + 1), "1x1 tile fits the 3x3 tile's LDS");
+  __shared__ __attribute__((aligned(16))) T tile[PK_TILE_ELEMS];
+  static_assert(PK_T1 * (PK_T1 + 2) <= PK_TILE_ELEMS, "1x1 tile fits the 3x3 tile's LDS");
   int it = 0;
   while (it + 1 < a.n && (int)blockIdx.x >= a.first_block[it + 1]) ++it;
   const int O = a.O[it], I = a.I[it];
@@ -188,9 +212,9 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(PackBatchArgs
     pack_tile<T, 1, PK_T1, PK_T1>(tile, a.w[it], fwd, dg, O, I, (b / tiles_i) * PK_T1, (b % tiles_i) * PK_T1, (int)a.s2[it], a.adam,
                                   a.g[it], a.m[it], a.v[it]);
   } else {
-    const int tiles_i = I >> 5;
-    pack_tile<T, 9, 32, 32>(tile, a.w[it], fwd, dg, O, I, (b / tiles_i) << 5, (b % tiles_i) << 5, (int)a.s2[it], a.adam,
-                            a.g[it], a.m[it], a.v[it]);
+    const int tiles_i = I / PK_T3I;
+    pack_tile<T, 9, PK_T3O, PK_T3I>(tile, a.w[it], fwd, dg, O, I, (b / tiles_i) * PK_T3O, (b % tiles_i) * PK_T3I, (int)a.s2[it],
+                                    a.adam, a.g[it], a.m[it], a.v[it]);
   }
 }
 
@@ -410,6 +434,10 @@ static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item
                      q.I % te == 0,
                  "qt_pack_weights_batched: item %d: O=%d I=%d must be multiples of %d for k=%d (k in {1,3})", j, q.O, q.I,
                  te, q.k);
+    auto al16 = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
+    QT_CHECK_ARG(al16(q.w_oihw) && al16(q.w_fwd) && al16(q.w_dgrad) &&
+                     (!opt || (al16(opt[j].grad) && al16(opt[j].exp_avg) && al16(opt[j].exp_avg_sq))),
+                 "qt_pack_weights_batched: item %d: every pointer must be 16-byte aligned", j);
     a.w[j] = q.w_oihw; a.fwd[j] = q.w_fwd; a.dgrad[j] = q.w_dgrad;
     if (opt) {
       const qt_adam_item& u = opt[j];
@@ -422,7 +450,7 @@ static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item
     QT_CHECK_ARG(q.stride2_dgrad != 4 || q.k == 1, "qt_pack_weights_batched: item %d: stride2_dgrad = 4 is for 1x1 filters", j);
     QT_CHECK_ARG(q.stride2_dgrad != 3 || q.k == 3, "qt_pack_weights_batched: item %d: stride2_dgrad = 3 is for 3x3 filters", j);
     a.first_block[j] = blocks;
-    blocks += (q.O / te) * (q.I / te);
+    blocks += q.k == 1 ? (q.O / PK_T1) * (q.I / PK_T1) : (q.O / PK_T3O) * (q.I / PK_T3I);
   }
   a.first_block[n] = blocks;
   a.n = n;

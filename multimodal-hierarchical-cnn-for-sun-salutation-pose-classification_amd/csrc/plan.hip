@@ -142,6 +142,10 @@ struct qt_plan {
   bool use_side = true;
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // The plan's last operation was a full qt_plan_backward that ran the fused stem backward on the caller's stream and
+  // ordered the side stream behind everything before it: every gradient but conv1's filter is complete or queued on the
+  // side stream, nothing reads the packed operand copies any more, and qt_plan_adam_step_overlapped may use that stream.
+  bool tail_ready = false;
   // state of the last forward
   int last_batch = 0, last_training = 0;
   unsigned long long last_seed = 0;
@@ -811,6 +815,7 @@ unsigned long long weight_sig(const qt_plan* p, void* const* T) {
 
 int pack_weights(qt_plan* p, void* workspace, void* const* T, int for_backward, void* stream) {
   Exec e{p, static_cast<unsigned char*>(workspace), T, stream, p->d.batch, p->d.dtype};
+  p->tail_ready = false;
   // one launch for every conv / linear operand (plus the 9 K-element stem filter)
   std::vector<qt_pack_item> items;
   auto add = [&](const float* w, void* fwd, void* dgrad, int O, int I, int k, int s2) {
@@ -842,11 +847,19 @@ int pack_weights(qt_plan* p, void* workspace, void* const* T, int for_backward, 
 // linear weights that have packed copies are updated INSIDE the packing kernel, everything else by the
 // plain multi-tensor kernel; tensors without a gradient are only re-packed.
 int adam_step(qt_plan* p, void* workspace, void* const* T, float* const* G, float* const* M1, float* const* M2,
-              const qt_adam_desc* adam, int for_backward, void* stream) {
+              const qt_adam_desc* adam, int for_backward, void* stream, bool overlap, int* overlapped) {
   Exec e{p, static_cast<unsigned char*>(workspace), T, stream, p->d.batch, p->d.dtype};
+  // Overlapped form (qt_plan_adam_step_overlapped right after a full backward): the bulk -- the batched Adam + re-pack and
+  // the plain tensors -- goes to the side stream, which the backward ordered behind everything but the fused stem backward,
+  // and runs beside that kernel (it leaves two thirds of the HBM bandwidth idle); conv1's filter, whose gradient that
+  // kernel produces, stays on the caller's stream.
+  const bool ov = overlap && p->tail_ready && p->use_side && p->side != nullptr && p->has_image;
+  p->tail_ready = false;
+  if (overlapped) *overlapped = ov;
+  void* bulk = ov ? static_cast<void*>(p->side) : stream;
   std::vector<bool> fused(p->tensors.size(), false);
   std::vector<qt_pack_item> upd_items, pack_items;
-  std::vector<qt_adam_item> upd_state, plain;
+  std::vector<qt_adam_item> upd_state, plain, stem_w;
   auto numel_of = [&](int idx) {
     long long n = 1;
     for (int d = 0; d < p->tensors[idx].ndim; ++d) n *= p->tensors[idx].shape[d];
@@ -882,21 +895,26 @@ int adam_step(qt_plan* p, void* workspace, void* const* T, float* const* G, floa
                  p->tensors[i].name.c_str());
     qt_adam_item u;
     u.param = e.tf((int)i); u.grad = G[i]; u.exp_avg = M1[i]; u.exp_avg_sq = M2[i]; u.numel = numel_of((int)i);
-    plain.push_back(u);
+    (ov && (int)i == p->convs[0].w ? stem_w : plain).push_back(u);
   }
-  if (!plain.empty()) e.run(qt_adam_multi(plain.data(), (int)plain.size(), adam, stream));
-  if (p->has_image)  // conv1's filter was updated by the plain kernel above
+  if (!plain.empty() && e.ok()) e.run(qt_adam_multi(plain.data(), (int)plain.size(), adam, bulk));
+  if (!stem_w.empty() && e.ok()) e.run(qt_adam_multi(stem_w.data(), 1, adam, stream));
+  if (p->has_image)  // conv1's filter was updated by a plain kernel above
     e.run(qt_pack_stem_weight(e.dt, e.tf(p->convs[0].w), e.at(p->convs[0].w_fwd), e.stem_taps(), stream));
   for (size_t j = 0; j < upd_items.size() && e.ok(); j += 32) {
     const int cnt = (int)std::min<size_t>(32, upd_items.size() - j);
-    e.run(qt_adam_pack_weights_batched(e.dt, upd_items.data() + j, upd_state.data() + j, adam, cnt, stream));
+    e.run(qt_adam_pack_weights_batched(e.dt, upd_items.data() + j, upd_state.data() + j, adam, cnt, bulk));
   }
   // weights without a gradient did not change: their copies are re-packed only if they are not known to be current
   const unsigned long long sig = weight_sig(p, T);
   const bool frozen_current = p->packed_fwd && (!for_backward || p->packed_bwd) && p->packed_sig == sig;
   if (!frozen_current)
     for (size_t j = 0; j < pack_items.size() && e.ok(); j += 32)
-      e.run(qt_pack_weights_batched(e.dt, pack_items.data() + j, (int)std::min<size_t>(32, pack_items.size() - j), stream));
+      e.run(qt_pack_weights_batched(e.dt, pack_items.data() + j, (int)std::min<size_t>(32, pack_items.size() - j), bulk));
+  if (ov) {  // the caller's stream has waited for the whole step when this call returns (also after an error above)
+    (void)hipEventRecord(p->ev_join, p->side);
+    (void)hipStreamWaitEvent(static_cast<hipStream_t>(stream), p->ev_join, 0);
+  }
   p->packed_fwd = e.ok();
   p->packed_bwd = e.ok() && (for_backward != 0);
   p->packed_sig = sig;
@@ -907,6 +925,7 @@ int forward(qt_plan* p, void* workspace, void* const* T, const float* image, con
             int batch, int training, unsigned long long seed, void* stream) {
   Exec e{p, static_cast<unsigned char*>(workspace), T, stream, batch, p->d.dtype};
   e.setup_side();
+  p->tail_ready = false;
   const int dt = e.dt;
   const bool tr = training == 1;   // batch statistics, running-stat update, dropout
   const bool unf = training != 0;  // unfused: raw conv outputs, pooling argmax ... are kept for qt_plan_backward
@@ -1295,6 +1314,7 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
   e.p = p; e.ws = static_cast<unsigned char*>(workspace); e.T = T; e.stream = stream; e.B = p->last_batch;
   e.dt = p->d.dtype; e.G = G;
   e.setup_side();
+  p->tail_ready = false;
   if ((phases & QT_BWD_HEAD) || p->dw_dirty) {  // once per backward, before any weight-gradient launch
     e.run(zero(e.at(p->dw_begin), p->dw_end - p->dw_begin, stream));
     p->dw_dirty = false;
@@ -1635,10 +1655,22 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
       // bf16: BatchNorm / ReLU / max-pool backward of conv1's output AND conv1's weight gradient in one launch on the
       // weight-gradient stream (the map d(loss)/d(conv1 output) never exists); otherwise the apply pass, then wgrad below
       if (e.gf(c0.w)) {
-        e.fork();
-        void* ws_ = e.wstream;
+        // Without an image gradient it runs on the CALLER's stream (its inputs, the two launches above, are there), so
+        // that the side stream is free for the optimizer's bulk (adam_step): the caller's stream first waits for the side
+        // stream's weight-gradient launches, which share wgrad_part, and the side stream is ordered behind the caller's
+        // stream HERE, before the stem launch is enqueued.  (A wait enqueued later, at the optimizer step, was measured to
+        // hold the side stream until the stem backward had finished, although the event had been recorded before it.)
+        const bool on_main = dt == QT_BF16 && !want_dx && e.wstream != stream;
+        if (on_main) {
+          e.forked = true;
+          e.join();
+          e.fork();
+        } else {
+          e.fork();
+        }
+        void* ws_ = on_main ? stream : e.wstream;
         const int slot = e.begin_timed(e.conv_flops(e.stem_desc(true)), 2, ws_, e.wgrad_bytes(c0, e.stem_desc(true)));
-        // (deterministic form: partial filters in wgrad_part, which only launches on this same stream use)
+        // (deterministic form: partial filters in wgrad_part, which no launch on the other stream is using)
         const int st = qt_stem_bn_bwd_wgrad_ws(dt, e.at(p->g_p0), e.at<unsigned char>(p->argmax), e.at(c0.y),
                                                e.at<float>(bn0.scale), e.at<float>(bn0.shift), e.at<float>(bn0.mean),
                                                e.at<float>(bn0.invstd), e.at<float>(bn0.coef), e.at(p->xpad),
@@ -1647,6 +1679,7 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
         if (st == QT_OK) {
           e.run(qt_unpack_stem_wgrad(e.at<float>(c0.dw), e.gf(c0.w), 0, ws_));
           stem_done = true;
+          p->tail_ready = on_main && e.ok() && (phases & QT_BWD_ALL) == QT_BWD_ALL;
         } else if (st != QT_ERR_UNSUPPORTED) {
           e.run(st);
         }
@@ -1843,7 +1876,14 @@ extern "C" int qt_plan_adam_step(qt_plan* p, void* workspace, void* const* tenso
                                  float* const* exp_avg, float* const* exp_avg_sq, const qt_adam_desc* adam, int for_backward,
                                  void* stream) {
   QT_CHECK_ARG(p && workspace && tensors && grads && exp_avg && exp_avg_sq && adam, "qt_plan_adam_step: null argument");
-  return adam_step(p, workspace, tensors, grads, exp_avg, exp_avg_sq, adam, for_backward, stream);
+  return adam_step(p, workspace, tensors, grads, exp_avg, exp_avg_sq, adam, for_backward, stream, false, nullptr);
+}
+
+extern "C" int qt_plan_adam_step_overlapped(qt_plan* p, void* workspace, void* const* tensors, float* const* grads,
+                                            float* const* exp_avg, float* const* exp_avg_sq, const qt_adam_desc* adam,
+                                            int for_backward, void* stream, int* overlapped) {
+  QT_CHECK_ARG(p && workspace && tensors && grads && exp_avg && exp_avg_sq && adam, "qt_plan_adam_step_overlapped: null argument");
+  return adam_step(p, workspace, tensors, grads, exp_avg, exp_avg_sq, adam, for_backward, stream, true, overlapped);
 }
 
 extern "C" int qt_plan_forward(qt_plan* p, void* workspace, void* const* tensors, const float* image,

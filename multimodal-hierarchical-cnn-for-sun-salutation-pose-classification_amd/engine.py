@@ -72,6 +72,7 @@ def _bind_api(L):
     L.qt_plan_side_fence.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.qt_plan_adam_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.POINTER(AdamDesc), ctypes.c_int, ctypes.c_void_p]
+    L.qt_plan_adam_step_overlapped.argtypes = L.qt_plan_adam_step.argtypes + [ctypes.POINTER(ctypes.c_int)]
     L.qt_plan_find_buffer.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t)]
     L._plan_bound = True
 
@@ -127,6 +128,10 @@ class PlanEngine:
         self.fwd_counter = 0
         self.grad_sync = None  # optional callable(bucket: Tensor, phase: int) for data parallelism
         self._flat_grad = None       # flat f32 gradient buffer of the last backward (re-used when nobody holds its views)
+        # what the last full backward handed out: (flat buffer, its _version, {plan index: data_ptr}); None once an
+        # optimizer step or a forward consumed it (adam_overlap_ok)
+        self._handed_out = None
+        self.last_adam_overlapped = False   # the last adam_step ran its bulk beside the stem backward (tests, scripts)
 
     @staticmethod
     def _storage_idle(t):
@@ -180,10 +185,27 @@ class PlanEngine:
                 self._weights_stale = True      # a parameter was replaced (load / .to() / new storage)
             self._tensor_ptrs[i] = ptr
 
-    def adam_step(self, by_index, desc):
+    def adam_overlap_ok(self, by_index):
+        """May this optimizer step start on the plan's side stream, beside the stem backward?  The side stream is
+        ordered behind the plan's own launches only, so everything Adam reads must be exactly what the last full
+        backward produced: every gradient is still the view of the flat buffer that backward handed out, no in-place
+        torch op has touched the buffer since (its version counter is unchanged), no step has used these gradients
+        yet, and no data-parallel all-reduce (which joins on the caller's stream) is attached."""
+        h = self._handed_out
+        if h is None or self.grad_sync is not None:
+            return False
+        flat, version, ptrs = h
+        if flat is not self._flat_grad or flat._version != version or set(by_index) != set(ptrs):
+            return False
+        return all(by_index[idx][0].data_ptr() == ptr for idx, ptr in ptrs.items())
+
+    def adam_step(self, by_index, desc, overlap=False):
         """Fused optimizer step + operand re-packing (qt_plan_adam_step).  by_index: plan tensor
         index -> (grad, exp_avg, exp_avg_sq) f32 tensors on this device; the parameters themselves
-        are the tensors bound by the last forward."""
+        are the tensors bound by the last forward.  overlap: the caller allows the bulk of the step on the plan's side
+        stream (qt_plan_adam_step_overlapped); it is used only if adam_overlap_ok(by_index) holds as well."""
+        overlap = bool(overlap) and self.adam_overlap_ok(by_index)
+        self._handed_out = None
         n = len(self.names)
         g, m, v = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
         for idx, (gt, mt, vt) in by_index.items():
@@ -191,8 +213,15 @@ class PlanEngine:
                 if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
                     raise QtError(f"{self.names[idx]}: gradient / Adam state must be contiguous f32 on {self.device}")
             g[idx], m[idx], v[idx] = gt.data_ptr(), mt.data_ptr(), vt.data_ptr()
-        _lib.check(self.L.qt_plan_adam_step(self.handle, self.ws_ptr, self._tensor_ptrs, g, m, v, ctypes.byref(desc), 1,
-                                            _lib.stream_ptr()), "qt_plan_adam_step")
+        took = ctypes.c_int(0)
+        if overlap:
+            _lib.check(self.L.qt_plan_adam_step_overlapped(self.handle, self.ws_ptr, self._tensor_ptrs, g, m, v,
+                                                           ctypes.byref(desc), 1, _lib.stream_ptr(), ctypes.byref(took)),
+                       "qt_plan_adam_step_overlapped")
+        else:
+            _lib.check(self.L.qt_plan_adam_step(self.handle, self.ws_ptr, self._tensor_ptrs, g, m, v, ctypes.byref(desc), 1,
+                                                _lib.stream_ptr()), "qt_plan_adam_step")
+        self.last_adam_overlapped = bool(took.value)
         self._weights_stale = False   # the step re-packed every operand copy from the updated masters
         if self._packed_version is not None:
             self._packed_version = (self._packed_version[0], True)
@@ -224,6 +253,7 @@ class PlanEngine:
                                           int(training), ctypes.c_ulonglong(seed), _lib.stream_ptr()),
                    "qt_plan_forward")
         self.fwd_counter += 1
+        self._handed_out = None
         return logits
 
     @staticmethod
@@ -287,8 +317,11 @@ class PlanEngine:
                                                       _lib.stream_ptr()),
                            "qt_plan_backward_dx")
 
+        self._handed_out = None
         if self.grad_sync is None:
             run(QT_BWD_ALL)
+            if dimage is None:
+                self._handed_out = (flat, flat._version, {idx: int(grad_ptrs[idx]) for idx, _ in wanted})
         else:
             begin = 0
             for b, phase in enumerate((QT_BWD_HEAD, QT_BWD_LAYER4, QT_BWD_LAYER32, QT_BWD_LAYER1)):

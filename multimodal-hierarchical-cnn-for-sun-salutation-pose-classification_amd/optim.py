@@ -9,11 +9,19 @@ one-launch kernel that re-packs them into the MFMA operand layouts, so masters, 
 copies are each read / written once per step; the remaining small tensors take one multi-tensor
 launch.  SURVEY.md 8(f) rank 1.
 
+Right after a full `backward()` the bulk of the step runs on the plan's side stream, beside the fused stem backward
+(the last kernel of the backward, which produces only conv1's weight gradient and leaves most of the HBM bandwidth
+idle); conv1's filter is updated on the caller's stream, which has waited for the whole step when `step()` returns.
+This order is taken only when nothing but the plan can have touched what Adam reads (`overlap_allowed`,
+`PlanEngine.adam_overlap_ok`); otherwise, and with `QTCNN_ADAM_OVERLAP=0`, the step runs serially on the caller's
+stream.  Both orders compute the same bits.
+
     opt = FusedAdam(model.parameters(), lr=1e-4, weight_decay=1e-4, model=model)
 
 Without `model=` (or for parameters the plan does not know) it is a plain fused multi-tensor Adam.
 """
 import ctypes
+import os
 
 import torch
 
@@ -28,6 +36,18 @@ _raw_updates = 0
 
 def raw_update_count():
     return _raw_updates
+
+
+def overlap_allowed(engine, by_index, created_state, n_groups, n_steps):
+    """The optimizer's half of the eligibility test for the overlapped step: the switch is on, one param group and one
+    step value (the conditions of the fused call), and no optimizer state was created in this step() -- the first
+    step's zeros_like run on the caller's stream, which the side stream does not wait for.  The engine checks the
+    gradients (PlanEngine.adam_overlap_ok)."""
+    if os.environ.get("QTCNN_ADAM_OVERLAP", "1") == "0":
+        return False
+    if created_state or n_groups != 1 or n_steps != 1:
+        return False
+    return engine is not None and engine.adam_overlap_ok(by_index)
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -52,6 +72,7 @@ class FusedAdam(torch.optim.Optimizer):
         fused_groups = 0
         for group in self.param_groups:
             todo = []
+            created_state = False
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -60,6 +81,7 @@ class FusedAdam(torch.optim.Optimizer):
                 st = self.state[p]
                 if not st:
                     st["step"] = 0
+                    created_state = True
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
@@ -78,7 +100,8 @@ class FusedAdam(torch.optim.Optimizer):
                 if in_plan and engine is not None and fused_groups == 0 and len(steps) == 1 and \
                         len(self.param_groups) == 1:
                     with torch.cuda.device(engine.device):
-                        engine.adam_step(in_plan, desc)
+                        engine.adam_step(in_plan, desc, overlap=overlap_allowed(
+                            engine, in_plan, created_state, len(self.param_groups), len(steps)))
                     fused_groups += 1
                 else:
                     rest = part
