@@ -526,10 +526,7 @@ int c3_grid(int items) {
 }
 
 bool c3_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("QTCNN_CONV3D_FIRST");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = qt_env_int("QTCNN_CONV3D_FIRST", 1) != 0;
   return on;
 }
 

@@ -446,19 +446,13 @@ int s3_grid(int items) {
 }
 
 bool s3_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("QTCNN_CONV3D_SLAB");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = qt_env_int("QTCNN_CONV3D_SLAB", 1) != 0;
   return on;
 }
 
 // QTCNN_S3_CPW (default 2): 16-channel blocks per wave of the forward / data-gradient slab kernel (1: the eight-wave form of round 3)
 int s3_cpw() {
-  static const int v = [] {
-    const char* e = getenv("QTCNN_S3_CPW");
-    return (e && e[0] == '1') ? 1 : 2;
-  }();
+  static const int v = qt_env_int("QTCNN_S3_CPW", 2) == 1 ? 1 : 2;
   return v;
 }
 

@@ -430,10 +430,7 @@ extern "C" void qt_set_patch_conv(int mode) { g_patch_enabled = mode < 0 ? 2 : (
 static bool l1_ring_shape(const qt_conv_desc* d);
 
 bool qt_patch_eligible(const qt_conv_desc* d) {
-  if (g_patch_enabled < 0) {
-    const char* v = getenv("QTCNN_PATCH_CONV");
-    g_patch_enabled = v ? atoi(v) : 2;
-  }
+  if (g_patch_enabled < 0) g_patch_enabled = qt_env_int("QTCNN_PATCH_CONV", 2);
   // 0: never; otherwise the shape served by the persistent ring kernel
   if (!g_patch_enabled) return false;
   return l1_ring_shape(d) && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && !d->quad && !d->dst_sub &&

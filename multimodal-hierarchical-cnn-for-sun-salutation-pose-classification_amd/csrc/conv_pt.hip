@@ -752,19 +752,13 @@ unsigned long long* g_pt_prof = nullptr;
 int g_pt_stagger[2] = {-1, -1};   // forward, backward
 inline int pt_stagger(bool bwd) {
   if (g_pt_stagger[0] < 0) {
-    const char* e = getenv("QTCNN_PT_STAGGER_FWD");
-    g_pt_stagger[0] = e ? atoi(e) : 0;
-    e = getenv("QTCNN_PT_STAGGER_BWD");
-    g_pt_stagger[1] = e ? atoi(e) : 0;
+    g_pt_stagger[0] = qt_env_int("QTCNN_PT_STAGGER_FWD", 0);
+    g_pt_stagger[1] = qt_env_int("QTCNN_PT_STAGGER_BWD", 0);
   }
   return g_pt_stagger[bwd ? 1 : 0];
 }
 inline int pt_workgroups() {
-  static int persist = -1;
-  if (persist < 0) {
-    const char* e = getenv("QTCNN_PT_PERSIST");
-    persist = e ? atoi(e) : 1;
-  }
+  static const int persist = qt_env_int("QTCNN_PT_PERSIST", 1);
   if (g_pt_max_wgs_fwd > 0) return g_pt_max_wgs_fwd;
   if (!persist) return 1 << 30;
   int dev = 0, cus = 256, v = 0;
@@ -795,14 +789,11 @@ int launch(PtArgs q, hipStream_t stream) {
 
 // QTCNN_PT_KSPLIT (default 1): the 128-channel tile of the bf16 build in its K-split form (see the kernel); 0: the persistent
 // M-split form
-inline bool ksplit_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("QTCNN_PT_KSPLIT");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0;
+inline int pt_ksplit() {
+  static const int v = qt_env_int("QTCNN_PT_KSPLIT", 1);
+  return v;
 }
+inline bool ksplit_enabled() { return pt_ksplit() != 0; }
 
 // merged stride-2 data gradient (four tap slots, 128-channel tiles of the 4 C class channels)
 template <typename T>
@@ -818,10 +809,7 @@ int dispatch_merged(const PtArgs& q, hipStream_t stream) {
   return QT_ERR_UNSUPPORTED;
 }
 
-inline bool ksplit_enabled_rows() {   // QTCNN_PT_KSPLIT=2: also the 28x28 stage (measurement)
-  const char* e = getenv("QTCNN_PT_KSPLIT");
-  return e && atoi(e) >= 2;
-}
+inline bool ksplit_enabled_rows() { return pt_ksplit() >= 2; }   // QTCNN_PT_KSPLIT=2: also the 28x28 stage (measurement)
 
 template <typename T, bool DGRAD>
 int dispatch(const PtArgs& q, hipStream_t stream) {
@@ -849,21 +837,14 @@ int dispatch(const PtArgs& q, hipStream_t stream) {
 // QTCNN_PT_MERGED (default 1): the merged stride-2 data gradients take this kernel's four-tap instantiation; 0: the generic
 // tile (same-box A/B)
 inline bool merged_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("QTCNN_PT_MERGED");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0;
+  static const bool on = qt_env_int("QTCNN_PT_MERGED", 1) != 0;
+  return on;
 }
 
 // 0: off, 1: on (default).  QTCNN_PT_CONV / qt_set_pt_conv: same-box A/B against the generic kernel.
 int g_pt_enabled = -1;
 inline int pt_enabled() {
-  if (g_pt_enabled < 0) {
-    const char* e = getenv("QTCNN_PT_CONV");
-    g_pt_enabled = e ? atoi(e) : 1;
-  }
+  if (g_pt_enabled < 0) g_pt_enabled = qt_env_int("QTCNN_PT_CONV", 1);
   return g_pt_enabled;
 }
 

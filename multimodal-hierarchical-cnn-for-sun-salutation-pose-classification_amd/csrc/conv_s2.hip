@@ -442,10 +442,7 @@ __global__ __launch_bounds__(kNT, 2) void conv_s2_kernel(S2Args q) {
 
 int g_s2_enabled = -1, g_s2_max_wgs = 0;
 inline int s2_enabled() {
-  if (g_s2_enabled < 0) {
-    const char* e = getenv("QTCNN_S2_CONV");
-    g_s2_enabled = e ? atoi(e) : 1;
-  }
+  if (g_s2_enabled < 0) g_s2_enabled = qt_env_int("QTCNN_S2_CONV", 1);
   return g_s2_enabled;
 }
 

@@ -394,10 +394,7 @@ __global__ __launch_bounds__(512) void conv_stem_pool_kernel(StemPoolArgs p) {
 
 int g_stem_enabled = -1;
 bool stem_enabled() {
-  if (g_stem_enabled < 0) {
-    const char* e = getenv("QTCNN_STEM_CONV");
-    g_stem_enabled = e ? atoi(e) : 1;
-  }
+  if (g_stem_enabled < 0) g_stem_enabled = qt_env_int("QTCNN_STEM_CONV", 1);
   return g_stem_enabled != 0;
 }
 
@@ -472,11 +469,7 @@ extern "C" int qt_stem_conv_pool_nchw(int dtype, const float* image_nchw, const 
                                       const float* shift, void* pooled, int batch, void* stream) {
   QT_CHECK_ARG(image_nchw && weight && scale && shift && pooled && batch > 0 && (taps == 7 || taps == 8),
                "qt_stem_conv_pool_nchw: bad argument");
-  static int raw_on = -1;
-  if (raw_on < 0) {
-    const char* e = getenv("QTCNN_STEM_NCHW");
-    raw_on = e ? atoi(e) : 1;
-  }
+  static const int raw_on = qt_env_int("QTCNN_STEM_NCHW", 1);
   if (dtype != QT_BF16 || !stem_enabled() || !raw_on || ((uintptr_t)image_nchw % 16) != 0) {
     qt_set_error("qt_stem_conv_pool_nchw: bf16 and a 16-byte aligned image only (use qt_pack_stem_input + qt_stem_conv_pool)");
     return QT_ERR_UNSUPPORTED;

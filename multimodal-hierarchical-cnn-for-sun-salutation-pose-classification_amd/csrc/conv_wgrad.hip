@@ -663,11 +663,7 @@ static int stem_bn_bwd_wgrad(int dtype, const void* dpooled, const unsigned char
                              float* dw, void* workspace, size_t workspace_bytes, int batch, void* stream) {
   QT_CHECK_ARG(dpooled && argmax && y && scale && shift && mean && invstd && coef && xpad && dw && workspace && batch > 0,
                "qt_stem_bn_bwd_wgrad_ws: bad argument");
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("QTCNN_STEM_BWD_FUSED");
-    on = e ? atoi(e) : 1;
-  }
+  static const int on = qt_env_int("QTCNN_STEM_BWD_FUSED", 1);
   if (dtype != QT_BF16 || !on) {
     qt_set_error("qt_stem_bn_bwd_wgrad_ws: bf16 only (use qt_stem_bn_bwd_apply + qt_conv2d_wgrad)");
     return QT_ERR_UNSUPPORTED;
@@ -781,11 +777,7 @@ extern "C" int qt_conv2d_wgrad_ws(const qt_conv_desc* d, const void* dy, const v
   if (d->dtype == QT_BF16) {
     if (stem) {
       // QTCNN_STEM_WGRAD_ROWS (default 1): the raw-row kernel for the canonical stem geometry; 0: the generic kernel
-      static int rows_on = -1;
-      if (rows_on < 0) {
-        const char* e = getenv("QTCNN_STEM_WGRAD_ROWS");
-        rows_on = e ? atoi(e) : 1;
-      }
+      static const int rows_on = qt_env_int("QTCNN_STEM_WGRAD_ROWS", 1);
       if (rows_on && d->kh == 7 && d->stride == 2 && d->pad == 0 && d->out_h == 112 && d->out_w == 112 &&
           d->in_h == QT_STEM_PAD_H && d->in_w == QT_STEM_PAD_W && d->src_pix_stride == 4 &&
           d->src_row_stride == QT_STEM_PAD_W * 4 && d->src_img_stride == (long long)QT_STEM_PAD_H * QT_STEM_PAD_W * 4 && !d->quad)

@@ -715,11 +715,7 @@ int sum_partials(const float* part, float* dw, int nq, int nsplit, int KC, int l
     (void)hipEventDestroy(ev);   // (deferred until the event has completed)
     stream = g_sum_stream;
   }
-  static int light = -1;
-  if (light < 0) {
-    const char* e = getenv("QTCNN_WGRAD_SUM");
-    light = e ? atoi(e) : 1;
-  }
+  static const int light = qt_env_int("QTCNN_WGRAD_SUM", 1);
   if (light && nsplit > 16)   // (few ranges: half of the light form's lanes would idle; r04v trace: 78-83 us against 45-71 in the step)
     hipLaunchKernelGGL(wgrad_partial_sum_light_kernel, dim3(qt_cdiv(nq, 32)), dim3(256), 0, stream, part, dw, nq, nsplit,
                        (long long)nq, KC, layout);
@@ -736,10 +732,7 @@ int sum_partials(const float* part, float* dw, int nq, int nsplit, int KC, int l
 int g_wgrad_patch_min_w = -1;  // smallest image width routed here; 0 = off
 
 int min_w() {
-  if (g_wgrad_patch_min_w < 0) {
-    const char* e = getenv("QTCNN_WGRAD_PATCH_MIN_W");
-    g_wgrad_patch_min_w = e ? atoi(e) : 7;
-  }
+  if (g_wgrad_patch_min_w < 0) g_wgrad_patch_min_w = qt_env_int("QTCNN_WGRAD_PATCH_MIN_W", 7);
   return g_wgrad_patch_min_w;
 }
 
@@ -792,12 +785,9 @@ struct TileGeo {
 TileGeo tile_geometry(int PW, int PP) {
   TileGeo g{0, (PW + 1 + 7) / 8 * 8, 0, 0, 0, 0};
   if (g.hl > PP) return g;
-  static int lds_kb = -1;  // LDS the kernel may take: what it leaves is what the main stream's small kernels find
-  if (lds_kb < 0) {
-    const char* e = getenv("QTCNN_WT_LDS_KB");
-    lds_kb = e ? atoi(e) : 160;
-    if (lds_kb < 80 || lds_kb > 160) lds_kb = 160;
-  }
+  // LDS the kernel may take: what it leaves is what the main stream's small kernels find
+  static const int lds_kb_env = qt_env_int("QTCNN_WT_LDS_KB", 160);
+  const int lds_kb = (lds_kb_env < 80 || lds_kb_env > 160) ? 160 : lds_kb_env;
   for (int nt = 8; nt >= 4; nt -= 2) {
     const unsigned xb = (unsigned)(nt * WP_CH + 2 * g.hl) * 128u, bufb = xb + (unsigned)nt * WP_CH * 128u;
     const unsigned lds = 2u * bufb + 2u * (unsigned)(PP + 8) * 4u + 1024u;  // tables + the spare KiB of empty DMA slots
@@ -848,10 +838,7 @@ int launch_tile(WPArgs a, size_t part_bytes, int oihw, hipStream_t stream) {
 
 int g_wp_variant = -1;  // 3: tile-resident kernel (default), 0: ring kernel, one wave group, 2: ring kernel, two groups
 int wp_variant() {
-  if (g_wp_variant < 0) {
-    const char* e = getenv("QTCNN_WP_VARIANT");
-    g_wp_variant = e ? atoi(e) : 3;
-  }
+  if (g_wp_variant < 0) g_wp_variant = qt_env_int("QTCNN_WP_VARIANT", 3);
   return g_wp_variant;
 }
 
@@ -936,11 +923,7 @@ int qt_wgrad_patch_launch(const qt_conv_desc* d, const void* dy, const void* x, 
   a.tiles = (a.N / 64) * a.tilesC;
   a.adv_h = a.adv_w = a.pps = a.nsplit = 0;
   const int variant = wp_variant();
-  static int use_ws = -1;
-  if (use_ws < 0) {
-    const char* e = getenv("QTCNN_WGRAD_WS");
-    use_ws = e ? atoi(e) : 1;
-  }
+  static const int use_ws = qt_env_int("QTCNN_WGRAD_WS", 1);
   if (!use_ws && !oihw) a.part = nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // Alone, two wave groups win (56x56 64->64, atomics: 99 us vs 122 us): a second wave per SIMD

@@ -275,20 +275,13 @@ __global__ __launch_bounds__(512) void conv_wgrad_s2_kernel(WS2Args a) {
 
 int g_wgrad_s2 = -1;   // QTCNN_WGRAD_S2 (default 1): 0 = the generic kernel (same-box A/B)
 bool s2_enabled() {
-  if (g_wgrad_s2 < 0) {
-    const char* e = getenv("QTCNN_WGRAD_S2");
-    g_wgrad_s2 = e ? atoi(e) : 1;
-  }
+  if (g_wgrad_s2 < 0) g_wgrad_s2 = qt_env_int("QTCNN_WGRAD_S2", 1);
   return g_wgrad_s2 != 0;
 }
 
 // QTCNN_S2_BUFFERS (default 3): tile buffers of the stride-2 weight-gradient kernel where the LDS holds them (2: round-4 first form)
 int s2_buffers() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("QTCNN_S2_BUFFERS");
-    v = e ? atoi(e) : 3;
-  }
+  static const int v = qt_env_int("QTCNN_S2_BUFFERS", 3);
   return v;
 }
 

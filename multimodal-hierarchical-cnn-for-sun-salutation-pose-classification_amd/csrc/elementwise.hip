@@ -1008,11 +1008,7 @@ extern "C" int qt_bn_bwd_apply(int dtype, const void* g, const void* mask, const
   QT_CHECK_ARG(g && y && mean && invstd && coef && dy && M > 0 && C > 0 && C % 8 == 0, "qt_bn_bwd_apply: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int grid = grid_for(M * (C / 8));
-  static int light = -1;
-  if (light < 0) {
-    const char* e = getenv("QTCNN_BN_APPLY_LIGHT");
-    light = e ? atoi(e) : 1;
-  }
+  static const int light = qt_env_int("QTCNN_BN_APPLY_LIGHT", 1);
   const int cgs = C / 4;   // (4-channel groups per row)
   const int lgrid = grid_for(M * cgs);
   if (light && dtype == QT_BF16 && !mask && !g_out && ((long long)lgrid * 256) % cgs == 0 && M * cgs < (1ll << 29)) {
@@ -1182,11 +1178,7 @@ extern "C" int qt_stem_bn_bwd_sums(int dtype, const void* dpooled, const void* y
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int grid = stem_sums_rows(batch);
   const long long total = (long long)batch * 56 * 56 * 8;
-  static int light = -1;   // QTCNN_STEM_SUMS_LIGHT (default 1): 0 = the general kernel (same-box A/B)
-  if (light < 0) {
-    const char* e = getenv("QTCNN_STEM_SUMS_LIGHT");
-    light = e ? atoi(e) : 1;
-  }
+  static const int light = qt_env_int("QTCNN_STEM_SUMS_LIGHT", 1);   // (default 1): 0 = the general kernel (same-box A/B)
   if (light && dtype == QT_BF16 && total * 2 < (1ll << 30)) {
     hipLaunchKernelGGL(stem_bn_bwd_sums_light_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)dpooled, (const bf16_t*)y_at_max,
                        scale, shift, mean, invstd, partial, (unsigned)(total * 2));

@@ -160,10 +160,7 @@ int pick_split(int ntn, int ksteps) {
 
 int g_linear_enabled = -1;
 bool linear_enabled() {
-  if (g_linear_enabled < 0) {
-    const char* e = getenv("QTCNN_LINEAR_SPLITK");
-    g_linear_enabled = e ? atoi(e) : 1;
-  }
+  if (g_linear_enabled < 0) g_linear_enabled = qt_env_int("QTCNN_LINEAR_SPLITK", 1);
   return g_linear_enabled != 0;
 }
 

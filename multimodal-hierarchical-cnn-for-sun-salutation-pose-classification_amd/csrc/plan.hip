@@ -26,24 +26,16 @@
 // QTCNN_S2_DGRAD_MERGED (default 1): the data gradient of a 3x3 stride-2 conv is one 2x2-tap launch over the gradient
 // map (qt_conv_desc.dst_merge) instead of four parity-class gathers (0: same-box A/B; identical sums up to f32 order)
 static bool merged_s2_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("QTCNN_S2_DGRAD_MERGED");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool on = qt_env_int("QTCNN_S2_DGRAD_MERGED", 1) != 0;
+  return on;
 }
 
 // QTCNN_DS_SLOT (default 1): where the generic tile runs the merged stride-2 data gradient (28x28 / 14x14 gradient maps), the
 // block's 1x1 / stride-2 downsample rides in the same launch as a fifth tap slot (qt_conv_desc.dst_merge_extra) instead of
 // a launch of its own whose output is then re-read as a residual (0: same-box A/B)
 static bool ds_slot_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("QTCNN_DS_SLOT");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool on = qt_env_int("QTCNN_DS_SLOT", 1) != 0;
+  return on;
 }
 
 namespace {
@@ -317,6 +309,58 @@ void build_graph(qt_plan* p) {
   p->cls3 = p->add_linear("classifier.3", p->hidden_dim, d.num_classes);
 }
 
+// ---- qt_conv_desc builders (shared by the workspace layout and the executor) ----
+// a zeroed descriptor: k x k taps over `batch` images
+qt_conv_desc base_desc(int dtype, int mode, int batch, int k, int stride, int pad) {
+  qt_conv_desc d{};
+  d.dtype = dtype; d.mode = mode; d.batch = batch;
+  d.kh = d.kw = k; d.stride = stride; d.pad = pad;
+  return d;
+}
+// the launch reads a dense [h][w][channels] source map per image, `channels` per tap, and writes n_out columns
+void set_source(qt_conv_desc& d, int channels, int n_out, int h, int w) {
+  d.k_per_tap = channels; d.n_out = n_out;
+  d.src_pix_stride = channels; d.src_row_stride = w * channels; d.src_img_stride = (long long)h * w * channels;
+}
+// conv c as it runs forward (QT_CONV_FWD) or as the stride-1 gather of its data gradient (QT_CONV_DGRAD: reads c.gy)
+qt_conv_desc conv_desc(int dtype, int batch, const ConvL& c, int mode) {
+  qt_conv_desc d = base_desc(dtype, mode, batch, c.k, c.stride, c.pad);
+  if (mode == QT_CONV_FWD) {
+    d.in_h = d.in_w = c.hin; d.out_h = d.out_w = c.hout;
+    set_source(d, c.cin, c.cout, c.hin, c.hin);
+  } else {
+    d.in_h = d.in_w = c.hout; d.out_h = d.out_w = c.hin;
+    set_source(d, c.cout, c.cin, c.hout, c.hout);
+  }
+  return d;
+}
+// a head conv applied to each of the S x S regions of a shared map, zero halo at the seams
+// (AttentionHierarchicalCNN, models.py:62-78): FWD reads the un-split map, DGRAD scatters back onto it
+qt_conv_desc region_desc(int dtype, int batch, const ConvL& c, int S, int mode) {
+  qt_conv_desc d = base_desc(dtype, mode, batch, c.k, 1, c.pad);
+  d.quad = S;
+  d.in_h = d.in_w = c.hin;
+  if (mode == QT_CONV_FWD) {
+    d.out_h = d.out_w = c.hin;
+    set_source(d, c.cin, c.cout, S * c.hin, S * c.hin);
+  } else {
+    d.out_h = d.out_w = S * c.hin;
+    set_source(d, c.cout, c.cin, c.hin, c.hin);
+  }
+  return d;
+}
+
+// qt_pack_item.stride2_dgrad of a conv's data-gradient operand, and where it lives: a downsample whose data gradient rides
+// in its block's merged launch writes the fifth tap slot of conv1's operand instead of an operand of its own
+int dgrad_layout(const ConvL& c) {
+  if (c.stride != 2) return 0;
+  if (c.k == 1) return c.slot_conv >= 0 ? 4 : 1;
+  return c.merged5 ? 3 : (c.merged_dgrad ? 2 : 1);
+}
+size_t dgrad_operand(const qt_plan* p, const ConvL& c) {
+  return (c.k == 1 && c.slot_conv >= 0) ? p->convs[c.slot_conv].w_dgrad : c.w_dgrad;
+}
+
 void layout_workspace(qt_plan* p) {
   Bump ws;
   const size_t B = (size_t)p->d.batch;
@@ -376,15 +420,8 @@ void layout_workspace(qt_plan* p) {
     const size_t n = (i == 0) ? (size_t)64 * 8 * 32 : (size_t)c.cout * c.cin * c.k * c.k;
     bool scratch = i == 0;
     if (!scratch && c.k != 1) {   // (the descriptor Exec::conv_desc / quad_desc / region_desc hands to wgrad())
-      qt_conv_desc d;
-      memset(&d, 0, sizeof(d));
       const int S = c.regions == 16 ? 4 : (c.regions == 4 ? 2 : 1);
-      d.dtype = p->d.dtype; d.mode = QT_CONV_FWD; d.batch = (int)B;
-      d.kh = d.kw = c.k; d.stride = c.stride; d.pad = c.pad;
-      d.in_h = d.in_w = c.hin; d.out_h = d.out_w = c.hout; d.k_per_tap = c.cin; d.n_out = c.cout;
-      d.quad = S == 1 ? 0 : S;
-      d.src_pix_stride = c.cin; d.src_row_stride = S * c.hin * c.cin;
-      d.src_img_stride = (long long)S * c.hin * S * c.hin * c.cin;
+      const qt_conv_desc d = S == 1 ? conv_desc(p->d.dtype, (int)B, c, QT_CONV_FWD) : region_desc(p->d.dtype, (int)B, c, S, QT_CONV_FWD);
       scratch = qt_conv2d_wgrad_workspace_bytes(&d) == 0;
     }
     c.dw = scratch ? ws.take(n * 4) : 0;
@@ -512,6 +549,11 @@ struct Exec {
     hip(hipStreamWaitEvent(p->side, p->ev_fork, 0), "hipStreamWaitEvent");
     forked = true;
   }
+  // fork(), then the stream that takes the branch: the side stream when enabled, else the caller's
+  void* side() {
+    fork();
+    return wstream ? wstream : stream;
+  }
   // side-stream work happens before anything enqueued on `stream` afterwards
   void join() {
     if (wstream == stream || !wstream || !forked || !ok()) return;
@@ -538,90 +580,74 @@ struct Exec {
     if (status == QT_OK && st != QT_OK) status = st;
   }
 
-  qt_conv_desc conv_desc(const ConvL& c, int mode) const {
-    qt_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = dt;
-    d.mode = mode;
-    d.batch = B;
-    d.kh = d.kw = c.k;
-    d.stride = c.stride;
-    d.pad = c.pad;
-    if (mode == QT_CONV_FWD) {
-      d.in_h = d.in_w = c.hin; d.out_h = d.out_w = c.hout;
-      d.k_per_tap = c.cin; d.n_out = c.cout;
-      d.src_pix_stride = c.cin; d.src_row_stride = c.hin * c.cin; d.src_img_stride = (long long)c.hin * c.hin * c.cin;
-    } else {
-      d.in_h = d.in_w = c.hout; d.out_h = d.out_w = c.hin;
-      d.k_per_tap = c.cout; d.n_out = c.cin;
-      d.src_pix_stride = c.cout; d.src_row_stride = c.hout * c.cout; d.src_img_stride = (long long)c.hout * c.hout * c.cout;
-    }
+  qt_conv_desc conv_desc(const ConvL& c, int mode) const { return ::conv_desc(dt, B, c, mode); }
+  qt_conv_desc region_desc(const ConvL& c, int S, int mode) const { return ::region_desc(dt, B, c, S, mode); }
+  // the quadrant head of the QuadtreeCNN: 2 x 2 regions of layer3's map (qt_conv_desc.quad = 1, the older code for them)
+  qt_conv_desc quad_desc(int mode) const {
+    qt_conv_desc d = region_desc(p->convs[p->quad_conv], 2, mode);
+    d.quad = 1;
     return d;
   }
   // bf16: a 32-element tap is half a K-step, so the forward runs 8 row taps (the
   // 8th has zero weights); the weight gradient always uses the 7 real taps.
   int stem_taps() const { return dt == QT_BF16 ? 8 : 7; }
+  // conv1 over the packed input ([QT_STEM_PAD_H][QT_STEM_PAD_W] pixels of 4 channels): a row tap is 8 pixels = 32 elements
   qt_conv_desc stem_desc(bool for_wgrad = false) const {
-    qt_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = dt; d.mode = QT_CONV_FWD; d.batch = B;
+    qt_conv_desc d = base_desc(dt, QT_CONV_FWD, B, 1, 2, 0);
+    d.kh = for_wgrad ? 7 : stem_taps();
     d.in_h = QT_STEM_PAD_H; d.in_w = QT_STEM_PAD_W; d.out_h = d.out_w = 112;
-    d.k_per_tap = 32; d.n_out = 64; d.kh = for_wgrad ? 7 : stem_taps(); d.kw = 1; d.stride = 2; d.pad = 0;
-    d.src_pix_stride = 4; d.src_row_stride = QT_STEM_PAD_W * 4;
-    d.src_img_stride = (long long)QT_STEM_PAD_H * QT_STEM_PAD_W * 4;
-    return d;
-  }
-  qt_conv_desc quad_desc(int mode) const {
-    const ConvL& c = p->convs[p->quad_conv];
-    qt_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = dt; d.mode = mode; d.batch = B; d.kh = d.kw = 3; d.stride = 1; d.pad = 1; d.quad = 1;
-    if (mode == QT_CONV_FWD) {
-      d.in_h = d.in_w = 7; d.out_h = d.out_w = 7; d.k_per_tap = c.cin; d.n_out = c.cout;
-      d.src_pix_stride = c.cin; d.src_row_stride = 14 * c.cin; d.src_img_stride = 14ll * 14 * c.cin;
-    } else {
-      d.in_h = d.in_w = 7; d.out_h = d.out_w = 14; d.k_per_tap = c.cout; d.n_out = c.cin;
-      d.src_pix_stride = c.cout; d.src_row_stride = 7 * c.cout; d.src_img_stride = 49ll * c.cout;
-    }
-    return d;
-  }
-  // a head conv applied to each of the S x S regions of a shared map, zero halo at the seams
-  // (AttentionHierarchicalCNN, models.py:62-78): FWD reads the un-split map, DGRAD scatters back onto it
-  qt_conv_desc region_desc(const ConvL& c, int S, int mode) const {
-    qt_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = dt; d.mode = mode; d.batch = B; d.kh = d.kw = c.k; d.stride = 1; d.pad = c.pad; d.quad = S;
-    d.in_h = d.in_w = c.hin;
-    if (mode == QT_CONV_FWD) {
-      d.out_h = d.out_w = c.hin; d.k_per_tap = c.cin; d.n_out = c.cout;
-      d.src_pix_stride = c.cin; d.src_row_stride = S * c.hin * c.cin;
-      d.src_img_stride = (long long)S * c.hin * S * c.hin * c.cin;
-    } else {
-      d.out_h = d.out_w = S * c.hin; d.k_per_tap = c.cout; d.n_out = c.cin;
-      d.src_pix_stride = c.cout; d.src_row_stride = c.hin * c.cout; d.src_img_stride = (long long)c.hin * c.hin * c.cout;
-    }
+    set_source(d, 4, 64, QT_STEM_PAD_H, QT_STEM_PAD_W);
+    d.k_per_tap = 32;
     return d;
   }
   // y [rows][out] = x [rows][in] W^T (W [out][in]) as a 1x1 convolution on 1x1 images, f32 MFMA whatever the plan's dtype
   qt_conv_desc dense_f32(int rows, int in, int out) const {
-    qt_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = QT_F32; d.mode = QT_CONV_FWD; d.batch = rows; d.in_h = d.in_w = d.out_h = d.out_w = 1;
-    d.kh = d.kw = 1; d.stride = 1; d.pad = 0;
-    d.k_per_tap = in; d.n_out = out; d.src_pix_stride = in; d.src_row_stride = in; d.src_img_stride = in;
+    qt_conv_desc d = base_desc(QT_F32, QT_CONV_FWD, rows, 1, 1, 0);
+    d.in_h = d.in_w = d.out_h = d.out_w = 1;
+    set_source(d, in, out, 1, 1);
     return d;
   }
   qt_conv_desc linear_desc(int in, int out, int mode) const {
-    qt_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = dt; d.mode = mode; d.batch = B; d.in_h = d.in_w = d.out_h = d.out_w = 1;
-    d.kh = d.kw = 1; d.stride = 1; d.pad = 0;
-    if (mode == QT_CONV_FWD) {
-      d.k_per_tap = in; d.n_out = out; d.src_pix_stride = in; d.src_row_stride = in; d.src_img_stride = in;
-    } else {
-      d.k_per_tap = out; d.n_out = in; d.src_pix_stride = out; d.src_row_stride = out; d.src_img_stride = out;
-    }
+    qt_conv_desc d = base_desc(dt, mode, B, 1, 1, 0);
+    d.in_h = d.in_w = d.out_h = d.out_w = 1;
+    if (mode == QT_CONV_FWD)
+      set_source(d, in, out, 1, 1);
+    else
+      set_source(d, out, in, 1, 1);
     return d;
+  }
+
+  // ---- thin dense products of an nn.Linear (W [out][in] f32), qt_gemm_small on stream `on`; ld_* = row strides ----
+  // y [rows][out] = relu?(x [rows][in] W^T + bias)
+  void dense_fwd(const void* x, int x_dt, const float* W, const float* bias, void* y, int y_dt, int rows, int in, int out,
+                 int relu, long long ld_x, long long ld_y, void* on) {
+    qt_gemm_small_desc g{};
+    g.M = rows; g.N = out; g.K = in;
+    g.a_dtype = x_dt; g.b_dtype = QT_F32; g.c_dtype = y_dt;
+    g.a_row_stride = ld_x; g.a_k_stride = 1; g.b_row_stride = in; g.b_k_stride = 1;
+    g.c_row_stride = ld_y; g.relu = relu;
+    run(qt_gemm_small(&g, x, W, bias, y, on));
+  }
+  // dx [rows][in] = dy [rows][out] W
+  void dense_dx(const void* dy, int dy_dt, const float* W, void* dx, int dx_dt, int rows, int in, int out, long long ld_dy,
+                long long ld_dx, void* on) {
+    qt_gemm_small_desc g{};
+    g.M = rows; g.N = in; g.K = out;
+    g.a_dtype = dy_dt; g.b_dtype = QT_F32; g.c_dtype = dx_dt;
+    g.a_row_stride = ld_dy; g.a_k_stride = 1; g.b_row_stride = 1; g.b_k_stride = in;
+    g.c_row_stride = ld_dx;
+    run(qt_gemm_small(&g, dy, W, nullptr, dx, on));
+  }
+  // dW [out][in] = dy^T x (contraction over the rows); dW == nullptr: the gradient is not wanted
+  void dense_dw(const void* dy, int dy_dt, const void* x, int x_dt, float* dW, int rows, int in, int out, long long ld_dy,
+                long long ld_x, void* on) {
+    if (!dW) return;
+    qt_gemm_small_desc g{};
+    g.M = out; g.N = in; g.K = rows;
+    g.a_dtype = dy_dt; g.b_dtype = x_dt; g.c_dtype = QT_F32;
+    g.a_row_stride = 1; g.a_k_stride = ld_dy; g.b_row_stride = 1; g.b_k_stride = ld_x;
+    g.c_row_stride = in;
+    run(qt_gemm_small(&g, dy, x, nullptr, dW, on));
   }
 
   struct BnLink {  // a BatchNorm that consumes the gradient a dgrad launch writes
@@ -630,6 +656,11 @@ struct Exec {
     const float* invstd = nullptr;
     float* partial = nullptr;
   };
+  // the BatchNorm behind conv c, its dgrad-epilogue partial sums at workspace offset partial_off
+  BnLink link_of(const ConvL& c, size_t partial_off) const {
+    const BnL& bn = p->bns[c.bn];
+    return {at(c.y), at<float>(bn.mean), at<float>(bn.invstd), at<float>(partial_off)};
+  }
   void igemm(const qt_conv_desc& d, const void* src, const void* w, void* dst, const float* scale, const float* shift,
              const void* res, const void* mask, float* stats, int relu, int kind = -1, const BnLink* links = nullptr,
              int nlinks = 0, const unsigned char* mask_bits = nullptr, const void* extra_src = nullptr) {
@@ -681,7 +712,7 @@ struct Exec {
   // algorithmic HBM bytes of a conv launch: source map, weights, destination and every per-pixel epilogue operand, each once
   double conv_bytes(const qt_conv_desc& d, const qt_conv_io& io) const {
     const double es = d.dtype == QT_F32 ? 4.0 : 2.0;
-    const double imgs = (double)d.batch * (d.mode == QT_CONV_FWD ? 1.0 : 1.0);
+    const double imgs = (double)d.batch;
     const bool stem = d.k_per_tap == 32 && d.kw == 1 && d.stride == 2 && d.n_out == 64;
     const double regions = qt_quad_regions(d.quad);
     const double src = stem ? imgs * d.in_h * d.in_w * 4.0 * es
@@ -714,10 +745,17 @@ struct Exec {
 
   long long rows_of(const ConvL& c) const { return (long long)B * c.hout * c.hout; }
 
+  // batch statistics of a BatchNorm over `count` values per channel from `rows` rows of partial sums: mean / invstd, the
+  // folded scale / shift and the running statistics
+  void bn_finalize(const BnL& bn, float* partial, int rows, long long count) {
+    run(qt_bn_finalize(partial, rows, bn.C, count, tf(bn.gamma), tf(bn.beta), tf(bn.rmean), tf(bn.rvar),
+                       static_cast<long long*>(T[bn.nbt]), p->d.bn_momentum, p->d.bn_eps, at<float>(bn.mean),
+                       at<float>(bn.invstd), at<float>(bn.scale), at<float>(bn.shift), stream));
+  }
+
   // conv (+ train-mode statistics -> scale/shift of its BatchNorm)
   // training: 1 = batch statistics, 2 = eval statistics but the raw conv output is kept for backward, 0 = nothing here
   void conv_bn_stats(const ConvL& c, const qt_conv_desc& d, const void* src, int training) {
-    BnL& bn = p->bns[c.bn];
     if (training == 2) {
       igemm(d, src, at(c.w_fwd), at(c.y), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
       return;
@@ -726,10 +764,7 @@ struct Exec {
       float* part = at<float>(stats_off == (size_t)-1 ? p->stats : stats_off);
       igemm(d, src, at(c.w_fwd), at(c.y), nullptr, nullptr, nullptr, nullptr, part, 0);
       if (!ok()) return;
-      const int rows = qt_conv2d_stats_rows(&d);
-      run(qt_bn_finalize(part, rows, bn.C, rows_of(c), tf(bn.gamma), tf(bn.beta), tf(bn.rmean),
-                         tf(bn.rvar), static_cast<long long*>(T[bn.nbt]), p->d.bn_momentum, p->d.bn_eps,
-                         at<float>(bn.mean), at<float>(bn.invstd), at<float>(bn.scale), at<float>(bn.shift), stream));
+      bn_finalize(p->bns[c.bn], part, qt_conv2d_stats_rows(&d), rows_of(c));
     }
     // eval: scale / shift of every BatchNorm were set by eval_affines() at the start of the forward
   }
@@ -742,14 +777,12 @@ struct Exec {
     const ConvL& c1 = p->convs[blk.conv1];
     const ConvL& cd = p->convs[blk.ds];
     if (c1.k != 3 || c1.stride != 2 || c1.pad != 1 || cd.k != 1 || cd.stride != 2 || cd.pad != 0) return false;
-    qt_conv_s2_desc d;
-    memset(&d, 0, sizeof(d));
+    qt_conv_s2_desc d{};
     d.dtype = dt; d.batch = B; d.in_h = d.in_w = c1.hin; d.c_in = c1.cin; d.c_out = c1.cout;
     if (!qt_conv_s2_pair_supported(&d)) return false;
-    BnL& b1 = p->bns[c1.bn];
-    BnL& bd = p->bns[cd.bn];
-    qt_conv_s2_io io;
-    memset(&io, 0, sizeof(io));
+    const BnL& b1 = p->bns[c1.bn];
+    const BnL& bd = p->bns[cd.bn];
+    qt_conv_s2_io io{};
     io.src = x; io.w_conv = at(c1.w_fwd); io.w_down = at(cd.w_fwd);
     io.y_conv = training == 0 ? at(blk.a1) : at(c1.y);
     io.y_down = at(cd.y);
@@ -769,12 +802,8 @@ struct Exec {
     end_timed(slot);
     if (training == 1 && ok()) {
       const int rows = qt_conv_s2_pair_stats_rows(&d);
-      run(qt_bn_finalize(at<float>(p->stats), rows, b1.C, rows_of(c1), tf(b1.gamma), tf(b1.beta), tf(b1.rmean), tf(b1.rvar),
-                         static_cast<long long*>(T[b1.nbt]), p->d.bn_momentum, p->d.bn_eps, at<float>(b1.mean),
-                         at<float>(b1.invstd), at<float>(b1.scale), at<float>(b1.shift), stream));
-      run(qt_bn_finalize(at<float>(p->stats_ds), rows, bd.C, rows_of(cd), tf(bd.gamma), tf(bd.beta), tf(bd.rmean), tf(bd.rvar),
-                         static_cast<long long*>(T[bd.nbt]), p->d.bn_momentum, p->d.bn_eps, at<float>(bd.mean),
-                         at<float>(bd.invstd), at<float>(bd.scale), at<float>(bd.shift), stream));
+      bn_finalize(b1, at<float>(p->stats), rows, rows_of(c1));
+      bn_finalize(bd, at<float>(p->stats_ds), rows, rows_of(cd));
     }
     return true;
   }
@@ -792,18 +821,28 @@ struct Exec {
     for (size_t j = 0; j < items.size() && ok(); j += 32)
       run(qt_bn_eval_affine_batched(items.data() + j, (int)std::min<size_t>(32, items.size() - j), p->d.bn_eps, stream));
   }
-};
 
-// qt_pack_item.stride2_dgrad of a conv's data-gradient operand, and where it lives: a downsample whose data gradient rides
-// in its block's merged launch writes the fifth tap slot of conv1's operand instead of an operand of its own
-int dgrad_layout(const ConvL& c) {
-  if (c.stride != 2) return 0;
-  if (c.k == 1) return c.slot_conv >= 0 ? 4 : 1;
-  return c.merged5 ? 3 : (c.merged_dgrad ? 2 : 1);
-}
-size_t dgrad_operand(const qt_plan* p, const ConvL& c) {
-  return (c.k == 1 && c.slot_conv >= 0) ? p->convs[c.slot_conv].w_dgrad : c.w_dgrad;
-}
+  // Every weight that has packed operand copies besides the stem filter (packed by qt_pack_stem_weight), in packing order:
+  // fn(tensor index, forward copy, data-gradient copy or nullptr, O, I, k, qt_pack_item.stride2_dgrad) -> status; stops at
+  // the first status that is not QT_OK and returns it
+  template <typename F> int for_each_packed(int for_backward, F&& fn) const {
+    if (p->has_image)
+      for (size_t i = 1; i < p->convs.size(); ++i) {
+        const ConvL& c = p->convs[i];
+        if (int st = fn(c.w, at(c.w_fwd), for_backward ? at(dgrad_operand(p, c)) : nullptr, c.cout, c.cin, c.k, dgrad_layout(c)))
+          return st;
+      }
+    if (!p->lstm)  // (CnnLstm's classifier is a thin f32 product: no packed copy)
+      if (int st = fn(p->cls0.w, at(p->cls0.w_fwd), for_backward ? at(p->cls0.w_dgrad) : nullptr, p->cls0.out, p->cls0.in, 1, 0))
+        return st;
+    return QT_OK;
+  }
+  qt_pack_item pack_item(int widx, void* fwd, void* dgrad, int O, int I, int k, int s2) const {
+    qt_pack_item q;
+    q.w_oihw = tf(widx); q.w_fwd = fwd; q.w_dgrad = dgrad; q.O = O; q.I = I; q.k = k; q.stride2_dgrad = s2;
+    return q;
+  }
+};
 
 unsigned long long weight_sig(const qt_plan* p, void* const* T) {
   unsigned long long h = 1469598103934665603ull;
@@ -817,24 +856,12 @@ int pack_weights(qt_plan* p, void* workspace, void* const* T, int for_backward, 
   Exec e{p, static_cast<unsigned char*>(workspace), T, stream, p->d.batch, p->d.dtype};
   p->tail_ready = false;
   // one launch for every conv / linear operand (plus the 9 K-element stem filter)
+  if (p->has_image) e.run(qt_pack_stem_weight(e.dt, e.tf(p->convs[0].w), e.at(p->convs[0].w_fwd), e.stem_taps(), stream));
   std::vector<qt_pack_item> items;
-  auto add = [&](const float* w, void* fwd, void* dgrad, int O, int I, int k, int s2) {
-    qt_pack_item q;
-    q.w_oihw = w; q.w_fwd = fwd; q.w_dgrad = dgrad; q.O = O; q.I = I; q.k = k; q.stride2_dgrad = s2;
-    items.push_back(q);
-  };
-  if (p->has_image) {
-    for (size_t i = 0; i < p->convs.size(); ++i) {
-      const ConvL& c = p->convs[i];
-      if (i == 0)
-        e.run(qt_pack_stem_weight(e.dt, e.tf(c.w), e.at(c.w_fwd), e.stem_taps(), stream));
-      else
-        add(e.tf(c.w), e.at(c.w_fwd), for_backward ? e.at(dgrad_operand(p, c)) : nullptr, c.cout, c.cin, c.k, dgrad_layout(c));
-    }
-  }
-  if (!p->lstm)  // (CnnLstm's classifier is a thin f32 product: no packed copy)
-    add(e.tf(p->cls0.w), e.at(p->cls0.w_fwd), for_backward ? e.at(p->cls0.w_dgrad) : nullptr, p->cls0.out, p->cls0.in, 1,
-        false);
+  e.for_each_packed(for_backward, [&](int widx, void* fwd, void* dgrad, int O, int I, int k, int s2) {
+    items.push_back(e.pack_item(widx, fwd, dgrad, O, I, k, s2));
+    return (int)QT_OK;
+  });
   for (size_t j = 0; j < items.size() && e.ok(); j += 32)
     e.run(qt_pack_weights_batched(e.dt, items.data() + j, (int)std::min<size_t>(32, items.size() - j), stream));
   p->packed_fwd = e.ok();
@@ -865,9 +892,8 @@ int adam_step(qt_plan* p, void* workspace, void* const* T, float* const* G, floa
     for (int d = 0; d < p->tensors[idx].ndim; ++d) n *= p->tensors[idx].shape[d];
     return n;
   };
-  auto add = [&](int widx, void* fwd, void* dgrad, int O, int I, int k, int s2) -> int {
-    qt_pack_item q;
-    q.w_oihw = e.tf(widx); q.w_fwd = fwd; q.w_dgrad = dgrad; q.O = O; q.I = I; q.k = k; q.stride2_dgrad = s2;
+  const int st = e.for_each_packed(for_backward, [&](int widx, void* fwd, void* dgrad, int O, int I, int k, int s2) -> int {
+    const qt_pack_item q = e.pack_item(widx, fwd, dgrad, O, I, k, s2);
     if (G[widx]) {
       QT_CHECK_ARG(M1[widx] && M2[widx], "qt_plan_adam_step: %s has a gradient but no optimizer state",
                    p->tensors[widx].name.c_str());
@@ -880,15 +906,8 @@ int adam_step(qt_plan* p, void* workspace, void* const* T, float* const* G, floa
     }
     fused[widx] = true;
     return (int)QT_OK;
-  };
-  if (p->has_image)
-    for (size_t i = 1; i < p->convs.size(); ++i) {
-      const ConvL& c = p->convs[i];
-      if (int st = add(c.w, e.at(c.w_fwd), for_backward ? e.at(dgrad_operand(p, c)) : nullptr, c.cout, c.cin, c.k, dgrad_layout(c))) return st;
-    }
-  if (!p->lstm)
-    if (int st = add(p->cls0.w, e.at(p->cls0.w_fwd), for_backward ? e.at(p->cls0.w_dgrad) : nullptr, p->cls0.out, p->cls0.in, 1, false))
-      return st;
+  });
+  if (st != QT_OK) return st;
   for (size_t i = 0; i < p->tensors.size(); ++i) {
     if (p->tensors[i].kind != 0 || fused[i] || !G[i]) continue;
     QT_CHECK_ARG(T[i] && M1[i] && M2[i], "qt_plan_adam_step: %s has a gradient but no parameter / optimizer state",
@@ -921,172 +940,146 @@ int adam_step(qt_plan* p, void* workspace, void* const* T, float* const* G, floa
   return e.status;
 }
 
-int forward(qt_plan* p, void* workspace, void* const* T, const float* image, const float* numerical, float* logits,
-            int batch, int training, unsigned long long seed, void* stream) {
-  Exec e{p, static_cast<unsigned char*>(workspace), T, stream, batch, p->d.dtype};
-  e.setup_side();
-  p->tail_ready = false;
-  const int dt = e.dt;
-  const bool tr = training == 1;   // batch statistics, running-stat update, dropout
-  const bool unf = training != 0;  // unfused: raw conv outputs, pooling argmax ... are kept for qt_plan_backward
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  // The quadrant head (needs layer3's output) and the numerical MLP (needs nothing) are independent
-  // of layer4: they run on the side stream and are joined before the classifier.
-  auto quad_branch = [&]() {
-    const ConvL& cq = p->convs[p->quad_conv];
-    e.igemm(e.quad_desc(QT_CONV_FWD), e.at(p->blocks[5].out), e.at(cq.w_fwd), e.at(p->q), nullptr, e.tf(cq.bias),
-            nullptr, nullptr, nullptr, 1);
-    e.run(qt_quad_pool(dt, e.at(p->q), e.at(p->fused), batch, p->fused_ld, 512, e.stream));
-  };
-  auto mlp_branch = [&]() {
-    qt_gemm_small_desc g;
-    memset(&g, 0, sizeof(g));
-    g.M = batch; g.N = p->mlp0.out; g.K = p->mlp0.in;
-    g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-    g.a_row_stride = p->mlp0.in; g.a_k_stride = 1; g.b_row_stride = p->mlp0.in; g.b_k_stride = 1;
-    g.c_row_stride = p->mlp0.out; g.relu = 1;
-    e.run(qt_gemm_small(&g, numerical, e.tf(p->mlp0.w), e.tf(p->mlp0.b), e.at(p->h1), e.stream));
-    if (tr && p->d.dropout_p > 0.f && !p->lstm)  // (CnnLstm's MLP has no dropout, cnn+lstm/models.py:32-36)
-      e.run(qt_dropout(QT_F32, e.at(p->h1), batch, p->mlp0.out, p->mlp0.out, seed, p->d.dropout_p, e.stream));
-    g.N = p->mlp1.out; g.K = p->mlp1.in;
-    g.a_row_stride = p->mlp1.in; g.b_row_stride = p->mlp1.in; g.c_dtype = dt; g.c_row_stride = p->fused_ld; g.relu = 0;
-    e.run(qt_gemm_small(&g, e.at(p->h1), e.tf(p->mlp1.w), e.tf(p->mlp1.b),
-                        e.at<unsigned char>(p->fused) + (size_t)p->mlp_col0 * p->esz, e.stream));
-  };
-  // AttentionHierarchicalCNN (models.py:57-97): quadrant and sub-quadrant heads on layer2's map, the attention
-  // gate over the 16 sub-quadrant vectors and the one-layer numerical MLP; all of it only needs layer2's output.
-  auto attn_branch = [&]() {
-    const ConvL& cq = p->convs[p->quad_conv];
-    const ConvL& cs = p->convs[p->sub_conv];
-    const void* base = e.at(p->blocks[3].out);
-    e.igemm(e.region_desc(cq, 2, QT_CONV_FWD), base, e.at(cq.w_fwd), e.at(cq.y), nullptr, e.tf(cq.bias), nullptr, nullptr,
-            nullptr, 1);
-    e.run(qt_region_avgpool(dt, e.at(cq.y), e.at(p->fused), dt, batch, 2, 196, 128, p->fused_ld, 512, e.stream));
-    e.igemm(e.region_desc(cs, 4, QT_CONV_FWD), base, e.at(cs.w_fwd), e.at(cs.y), nullptr, e.tf(cs.bias), nullptr, nullptr,
-            nullptr, 1);
-    e.run(qt_region_avgpool(dt, e.at(cs.y), e.at(p->vsub), QT_F32, batch, 4, 49, 64, 16 * 64, 0, e.stream));
-    e.run(qt_attention_gate(dt, e.at<float>(p->vsub), e.tf(p->att0.w), e.tf(p->att0.b), e.tf(p->att2.w), e.tf(p->att2.b),
-                            e.at<float>(p->att_act), e.at<float>(p->att_alpha), e.at(p->fused), batch, p->fused_ld,
-                            512 + 4 * 128, e.stream));
-    qt_gemm_small_desc g;
-    memset(&g, 0, sizeof(g));
-    g.M = batch; g.N = p->mlp0.out; g.K = p->mlp0.in;
-    g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = dt;
-    g.a_row_stride = p->mlp0.in; g.a_k_stride = 1; g.b_row_stride = p->mlp0.in; g.b_k_stride = 1;
-    g.c_row_stride = p->fused_ld; g.relu = 1;
-    unsigned char* z = e.at<unsigned char>(p->fused) + (size_t)p->mlp_col0 * p->esz;
-    e.run(qt_gemm_small(&g, numerical, e.tf(p->mlp0.w), e.tf(p->mlp0.b), z, e.stream));
-    if (tr && p->d.dropout_p > 0.f) e.run(qt_dropout(dt, z, batch, p->mlp0.out, p->fused_ld, seed, p->d.dropout_p, e.stream));
-  };
+// One forward pass, in launch order: stem() -> blocks() (which starts the head branches on the side stream) -> join ->
+// classifier() or lstm_tail()
+struct Fwd : Exec {
+  const float* image;
+  const float* numerical;
+  float* logits;
+  int training;
+  unsigned long long seed;
+  bool tr;    // batch statistics, running-stat update, dropout
+  bool unf;   // unfused: raw conv outputs, pooling argmax ... are kept for qt_plan_backward
   // The numerical MLP needs nothing of the image branch: its thin kernels go to the side stream FIRST, next to the
   // stem's byte-moving kernels.  (Until round 3 they were forked behind layer3 and their workgroups trickled onto CUs
   // that layer4's whole-CU convolutions released: 58 + 90 us on the side queue, layer4's convs 67 -> 88-100 us.)
-  const bool mlp_early = p->has_image && p->has_numerical && !p->attention && !p->lstm && !p->standard;
-  if (mlp_early) {
-    e.fork();
-    e.on_side(p->stats_ds, [&] { mlp_branch(); });
+  bool mlp_early;
+  bool dropout() const { return tr && p->d.dropout_p > 0.f; }
+
+  // The quadrant head (needs layer3's output) and the numerical MLP (needs nothing) are independent
+  // of layer4: they run on the side stream and are joined before the classifier.
+  void quad_branch() {
+    const ConvL& cq = p->convs[p->quad_conv];
+    igemm(quad_desc(QT_CONV_FWD), at(p->blocks[5].out), at(cq.w_fwd), at(p->q), nullptr, tf(cq.bias), nullptr, nullptr,
+          nullptr, 1);
+    run(qt_quad_pool(dt, at(p->q), at(p->fused), B, p->fused_ld, 512, stream));
   }
-  if (p->has_image) {
-    if (!tr) e.eval_affines(unf);
-    // ---- stem: pack -> conv7x7/2 (7 row taps x 32) -> BN -> ReLU -> maxpool ----
+  void mlp_branch() {
+    const LinL& m0 = p->mlp0;
+    const LinL& m1 = p->mlp1;
+    dense_fwd(numerical, QT_F32, tf(m0.w), tf(m0.b), at(p->h1), QT_F32, B, m0.in, m0.out, 1, m0.in, m0.out, stream);
+    if (dropout() && !p->lstm)  // (CnnLstm's MLP has no dropout, cnn+lstm/models.py:32-36)
+      run(qt_dropout(QT_F32, at(p->h1), B, m0.out, m0.out, seed, p->d.dropout_p, stream));
+    dense_fwd(at(p->h1), QT_F32, tf(m1.w), tf(m1.b), at<unsigned char>(p->fused) + (size_t)p->mlp_col0 * p->esz, dt, B, m1.in,
+              m1.out, 0, m1.in, p->fused_ld, stream);
+  }
+  // AttentionHierarchicalCNN (models.py:57-97): quadrant and sub-quadrant heads on layer2's map, the attention
+  // gate over the 16 sub-quadrant vectors and the one-layer numerical MLP; all of it only needs layer2's output.
+  void attn_branch() {
+    const ConvL& cq = p->convs[p->quad_conv];
+    const ConvL& cs = p->convs[p->sub_conv];
+    const LinL& m0 = p->mlp0;
+    const void* base = at(p->blocks[3].out);
+    igemm(region_desc(cq, 2, QT_CONV_FWD), base, at(cq.w_fwd), at(cq.y), nullptr, tf(cq.bias), nullptr, nullptr, nullptr, 1);
+    run(qt_region_avgpool(dt, at(cq.y), at(p->fused), dt, B, 2, 196, 128, p->fused_ld, 512, stream));
+    igemm(region_desc(cs, 4, QT_CONV_FWD), base, at(cs.w_fwd), at(cs.y), nullptr, tf(cs.bias), nullptr, nullptr, nullptr, 1);
+    run(qt_region_avgpool(dt, at(cs.y), at(p->vsub), QT_F32, B, 4, 49, 64, 16 * 64, 0, stream));
+    run(qt_attention_gate(dt, at<float>(p->vsub), tf(p->att0.w), tf(p->att0.b), tf(p->att2.w), tf(p->att2.b),
+                          at<float>(p->att_act), at<float>(p->att_alpha), at(p->fused), B, p->fused_ld, 512 + 4 * 128,
+                          stream));
+    unsigned char* z = at<unsigned char>(p->fused) + (size_t)p->mlp_col0 * p->esz;
+    dense_fwd(numerical, QT_F32, tf(m0.w), tf(m0.b), z, dt, B, m0.in, m0.out, 1, m0.in, p->fused_ld, stream);
+    if (dropout()) run(qt_dropout(dt, z, B, m0.out, p->fused_ld, seed, p->d.dropout_p, stream));
+  }
+
+  // ---- stem: pack -> conv7x7/2 (7 row taps x 32) -> BN -> ReLU -> maxpool ----
+  void stem() {
     const ConvL& c0 = p->convs[0];
     const BnL& bn0 = p->bns[c0.bn];
-    const qt_conv_desc sd = e.stem_desc();
+    const qt_conv_desc sd = stem_desc();
     // eval (bf16): the f32 NCHW image -> packing, conv1, folded bn1, ReLU and the max pool in ONE kernel; neither the packed
     // copy of the input nor the conv1 map is materialised
     int fused = QT_ERR_UNSUPPORTED;
     if (!unf) {
-      const int slot = e.begin_timed(e.conv_flops(sd), 0, nullptr,
-                                     (double)batch * (3.0 * 224 * 224 * 4 + p->esz * 56.0 * 56 * 64));
-      fused = qt_stem_conv_pool_nchw(dt, image, e.at(c0.w_fwd), e.stem_taps(), e.at<float>(bn0.scale),
-                                     e.at<float>(bn0.shift), e.at(p->p0), batch, stream);
-      e.end_timed(slot);
-      if (fused != QT_ERR_UNSUPPORTED) e.run(fused);
+      const int slot = begin_timed(conv_flops(sd), 0, nullptr, (double)B * (3.0 * 224 * 224 * 4 + p->esz * 56.0 * 56 * 64));
+      fused = qt_stem_conv_pool_nchw(dt, image, at(c0.w_fwd), stem_taps(), at<float>(bn0.scale), at<float>(bn0.shift),
+                                     at(p->p0), B, stream);
+      end_timed(slot);
+      if (fused != QT_ERR_UNSUPPORTED) run(fused);
     }
-    if (fused == QT_ERR_UNSUPPORTED) e.run(qt_pack_stem_input(dt, image, e.at(p->xpad), batch, stream));
-    if (fused == QT_ERR_UNSUPPORTED) e.conv_bn_stats(c0, sd, e.at(p->xpad), training);
+    if (fused == QT_ERR_UNSUPPORTED) run(qt_pack_stem_input(dt, image, at(p->xpad), B, stream));
+    if (fused == QT_ERR_UNSUPPORTED) conv_bn_stats(c0, sd, at(p->xpad), training);
     if (unf) {
-      e.run(qt_stem_pool(dt, e.at(c0.y), e.at<float>(bn0.scale), e.at<float>(bn0.shift), e.at(p->p0),
-                         e.at<unsigned char>(p->argmax), e.at(p->ymax), batch, stream));
+      run(qt_stem_pool(dt, at(c0.y), at<float>(bn0.scale), at<float>(bn0.shift), at(p->p0), at<unsigned char>(p->argmax),
+                       at(p->ymax), B, stream));
     } else if (fused == QT_ERR_UNSUPPORTED) {
       // conv1 + folded bn1 + ReLU + max pool on the packed input (f32 build: two kernels)
-      const int slot = e.begin_timed(e.conv_flops(sd), 0, nullptr,
-                                     (double)batch * p->esz * ((double)QT_STEM_PAD_H * QT_STEM_PAD_W * 4 + 56.0 * 56 * 64));
-      fused = qt_stem_conv_pool(dt, e.at(p->xpad), e.at(c0.w_fwd), e.stem_taps(), e.at<float>(bn0.scale),
-                                e.at<float>(bn0.shift), e.at(p->p0), batch, stream);
-      e.end_timed(slot);
+      const int slot = begin_timed(conv_flops(sd), 0, nullptr,
+                                   (double)B * p->esz * ((double)QT_STEM_PAD_H * QT_STEM_PAD_W * 4 + 56.0 * 56 * 64));
+      fused = qt_stem_conv_pool(dt, at(p->xpad), at(c0.w_fwd), stem_taps(), at<float>(bn0.scale), at<float>(bn0.shift),
+                                at(p->p0), B, stream);
+      end_timed(slot);
       if (fused == QT_ERR_UNSUPPORTED) {
-        e.igemm(sd, e.at(p->xpad), e.at(c0.w_fwd), e.at(c0.y), e.at<float>(bn0.scale), e.at<float>(bn0.shift), nullptr,
-                nullptr, nullptr, 1);
-        e.run(qt_stem_pool(dt, e.at(c0.y), e.at<float>(p->ones), e.at<float>(p->zeros), e.at(p->p0), nullptr, nullptr,
-                           batch, stream));
+        igemm(sd, at(p->xpad), at(c0.w_fwd), at(c0.y), at<float>(bn0.scale), at<float>(bn0.shift), nullptr, nullptr, nullptr, 1);
+        run(qt_stem_pool(dt, at(c0.y), at<float>(p->ones), at<float>(p->zeros), at(p->p0), nullptr, nullptr, B, stream));
       } else {
-        e.run(fused);
+        run(fused);
       }
     }
-    // ---- residual stages ----
+  }
+
+  // BatchNorm (+ residual) -> ReLU behind conv c of a block, into `out`.  Training forms: c.y holds the raw conv output
+  // (conv_bn_stats), one pass applies the BatchNorm and writes the ReLU mask bits; res_bn: the residual is a raw
+  // downsample output whose own BatchNorm is applied in the same pass.  Eval: the conv runs here with the folded
+  // BatchNorm, the residual and the ReLU in its epilogue (conv_in_eval = false: the fused transition pair already did)
+  void bn_relu(const ConvL& c, const qt_conv_desc& d, const void* src, const void* res, const BnL* res_bn, size_t out,
+               size_t out_bits, bool conv_in_eval = true) {
+    const BnL& bn = p->bns[c.bn];
+    if (unf)
+      run(qt_bn_act_mask(dt, at(c.y), at<float>(bn.scale), at<float>(bn.shift), res, res_bn ? at<float>(res_bn->scale) : nullptr,
+                         res_bn ? at<float>(res_bn->shift) : nullptr, 1, at(out), at<unsigned char>(out_bits),
+                         rows_of(c), c.cout, stream));
+    else if (conv_in_eval)
+      igemm(d, src, at(c.w_fwd), at(out), at<float>(bn.scale), at<float>(bn.shift), res, nullptr, nullptr, 1);
+  }
+
+  // ---- residual stages, then the global branch: avgpool(layer4) -> fused[:, 0:512] ----
+  void blocks() {
     size_t x = p->p0;
     for (const Block& blk : p->blocks) {
       const ConvL& c1 = p->convs[blk.conv1];
       const ConvL& c2 = p->convs[blk.conv2];
-      const BnL& b1 = p->bns[c1.bn];
-      const BnL& b2 = p->bns[c2.bn];
-      const qt_conv_desc d1 = e.conv_desc(c1, QT_CONV_FWD), d2 = e.conv_desc(c2, QT_CONV_FWD);
-      const long long M = e.rows_of(c2);
+      const qt_conv_desc d1 = conv_desc(c1, QT_CONV_FWD), d2 = conv_desc(c2, QT_CONV_FWD);
       // a transition block: conv1 and the downsample in one launch where the fused kernel covers the problem
-      const bool pair = blk.ds >= 0 && e.transition_pair(blk, e.at(x), training);
+      const bool pair = blk.ds >= 0 && transition_pair(blk, at(x), training);
       if (blk.ds >= 0 && !pair) {
-        const ConvL& cd = p->convs[blk.ds];
-        const BnL& bd = p->bns[cd.bn];
-        const qt_conv_desc dd = e.conv_desc(cd, QT_CONV_FWD);
-        e.fork();
-        e.on_side(p->stats_ds, [&] {
-          e.conv_bn_stats(cd, dd, e.at(x), training);
-          if (!unf)
-            e.igemm(dd, e.at(x), e.at(cd.w_fwd), e.at(cd.y), e.at<float>(bd.scale), e.at<float>(bd.shift), nullptr,
-                    nullptr, nullptr, 0);
-        });
-      }
-      if (!pair) e.conv_bn_stats(c1, d1, e.at(x), training);
-      if (unf) {
-        e.run(qt_bn_act_mask(dt, e.at(c1.y), e.at<float>(b1.scale), e.at<float>(b1.shift), nullptr, nullptr, nullptr, 1,
-                             e.at(blk.a1), e.at<unsigned char>(blk.a1_bits), M, c1.cout, stream));
-      } else if (!pair) {
-        e.igemm(d1, e.at(x), e.at(c1.w_fwd), e.at(blk.a1), e.at<float>(b1.scale), e.at<float>(b1.shift), nullptr,
-                nullptr, nullptr, 1);
-      }
-      if (blk.ds >= 0) {
         // the 1x1 downsample branch only needs the block input: it runs on the side stream next
         // to conv1 -> BN -> conv2 and is joined before the residual add
         const ConvL& cd = p->convs[blk.ds];
         const BnL& bd = p->bns[cd.bn];
-        const qt_conv_desc dd = e.conv_desc(cd, QT_CONV_FWD);
-        // (fork happened before conv1, see below)
-        e.conv_bn_stats(c2, d2, e.at(blk.a1), training);
-        if (!pair) e.join();   // (the fused pair ran on this stream: a head branch forked earlier keeps running beside layer4)
-        if (unf) {
-          e.run(qt_bn_act_mask(dt, e.at(c2.y), e.at<float>(b2.scale), e.at<float>(b2.shift), e.at(cd.y),
-                               e.at<float>(bd.scale), e.at<float>(bd.shift), 1, e.at(blk.out),
-                               e.at<unsigned char>(blk.out_bits), M, c2.cout, stream));
-        } else {
-          e.igemm(d2, e.at(blk.a1), e.at(c2.w_fwd), e.at(blk.out), e.at<float>(b2.scale), e.at<float>(b2.shift),
-                  e.at(cd.y), nullptr, nullptr, 1);
-        }
-        (void)dd;
+        const qt_conv_desc dd = conv_desc(cd, QT_CONV_FWD);
+        fork();
+        on_side(p->stats_ds, [&] {
+          conv_bn_stats(cd, dd, at(x), training);
+          if (!unf)
+            igemm(dd, at(x), at(cd.w_fwd), at(cd.y), at<float>(bd.scale), at<float>(bd.shift), nullptr, nullptr, nullptr, 0);
+        });
+      }
+      if (!pair) conv_bn_stats(c1, d1, at(x), training);
+      bn_relu(c1, d1, at(x), nullptr, nullptr, blk.a1, blk.a1_bits, !pair);
+      conv_bn_stats(c2, d2, at(blk.a1), training);
+      if (blk.ds >= 0) {
+        const ConvL& cd = p->convs[blk.ds];
+        if (!pair) join();   // (the fused pair ran on this stream: a head branch forked earlier keeps running beside layer4)
+        // training: the downsample's BatchNorm is applied to its raw output here; eval: cd.y holds the finished branch
+        bn_relu(c2, d2, at(blk.a1), at(cd.y), unf ? &p->bns[cd.bn] : nullptr, blk.out, blk.out_bits);
       } else {
-        e.conv_bn_stats(c2, d2, e.at(blk.a1), training);
-        if (unf) {
-          e.run(qt_bn_act_mask(dt, e.at(c2.y), e.at<float>(b2.scale), e.at<float>(b2.shift), e.at(x), nullptr, nullptr, 1,
-                               e.at(blk.out), e.at<unsigned char>(blk.out_bits), M, c2.cout, stream));
-        } else {
-          e.igemm(d2, e.at(blk.a1), e.at(c2.w_fwd), e.at(blk.out), e.at<float>(b2.scale), e.at<float>(b2.shift),
-                  e.at(x), nullptr, nullptr, 1);
-        }
+        bn_relu(c2, d2, at(blk.a1), at(x), nullptr, blk.out, blk.out_bits);
       }
       x = blk.out;
       if (&blk == &p->blocks[p->attention ? 3 : 5] && !p->standard) {  // the heads' input is done: start the side branches
-        e.fork();
-        e.on_side(p->stats_ds, [&] {
+        fork();
+        on_side(p->stats_ds, [&] {
           if (p->attention) {
             attn_branch();
           } else {
@@ -1096,64 +1089,69 @@ int forward(qt_plan* p, void* workspace, void* const* T, const float* image, con
         });
       }
     }
-    // ---- global branch: avgpool(layer4) -> fused[:, 0:512] ----
-    e.run(qt_avgpool(dt, e.at(p->blocks[7].out), e.at(p->fused), batch, 49, 512, p->fused_ld, 0, stream));
+    run(qt_avgpool(dt, at(p->blocks[7].out), at(p->fused), B, 49, 512, p->fused_ld, 0, stream));
   }
-  if (p->has_numerical && (!p->has_image || p->lstm)) mlp_branch();  // numerical_only / CnnLstm: nothing to overlap with
-  e.join();  // quadrant + MLP columns of the fused matrix are complete
-  if (p->lstm) {
-    // ---- cnn+lstm/models.py:76-89: [frames][640] -> 2-layer LSTM over seq_len steps -> last step -> classifier ----
-    const int T = p->seq_len, S = batch / T, H = p->lstm_h;
-    qt_gemm_small_desc g;
-    for (int l = 0; l < 2 && e.ok(); ++l) {
+
+  // ---- cnn+lstm/models.py:76-89: [frames][640] -> 2-layer LSTM over seq_len steps -> last step -> classifier ----
+  void lstm_tail() {
+    const int T = p->seq_len, S = B / T, H = p->lstm_h;
+    for (int l = 0; l < 2 && ok(); ++l) {
       const qt_plan::LstmL& L = p->lstm_l[l];
       // x W_ih^T + b_ih for all frames at once on the f32 MFMA path (W_ih [4H][in] is already the operand layout)
-      if (l == 0) e.run(qt_cast_f32(dt, e.at(p->fused), e.at<float>(p->lstm_x0), (long long)batch * L.in, stream));
-      e.igemm(e.dense_f32(batch, L.in, 4 * H), l == 0 ? e.at(p->lstm_x0) : e.at(p->lstm_x1), e.tf(L.w_ih), e.at(L.xproj),
-              nullptr, e.tf(L.b_ih), nullptr, nullptr, nullptr, 0);
-      e.run(qt_transpose_f32(e.tf(L.w_hh), e.at<float>(L.whh_t), 4 * H, H, stream));
-      e.run(qt_lstm_forward(e.at<float>(L.xproj), e.at<float>(L.whh_t), e.tf(L.b_hh), e.at<float>(L.gates),
-                            e.at<float>(L.cell), e.at<float>(L.hprev), e.at<float>(L.hout), S, T, H, stream));
+      if (l == 0) run(qt_cast_f32(dt, at(p->fused), at<float>(p->lstm_x0), (long long)B * L.in, stream));
+      igemm(dense_f32(B, L.in, 4 * H), l == 0 ? at(p->lstm_x0) : at(p->lstm_x1), tf(L.w_ih), at(L.xproj), nullptr, tf(L.b_ih),
+            nullptr, nullptr, nullptr, 0);
+      run(qt_transpose_f32(tf(L.w_hh), at<float>(L.whh_t), 4 * H, H, stream));
+      run(qt_lstm_forward(at<float>(L.xproj), at<float>(L.whh_t), tf(L.b_hh), at<float>(L.gates), at<float>(L.cell),
+                          at<float>(L.hprev), at<float>(L.hout), S, T, H, stream));
       if (l == 0) {  // nn.LSTM's inter-layer dropout acts on layer 0's outputs only as layer 1's input
-        e.hip(hipMemcpyAsync(e.at(p->lstm_x1), e.at(L.hout), (size_t)batch * H * 4, hipMemcpyDeviceToDevice, hs), "hipMemcpyAsync");
-        if (tr && p->d.dropout_p > 0.f)
-          e.run(qt_dropout(QT_F32, e.at(p->lstm_x1), batch, H, H, seed ^ 0x3C3C3C3CC3C3C3C3ull, p->d.dropout_p, stream));
+        hip(hipMemcpyAsync(at(p->lstm_x1), at(L.hout), (size_t)B * H * 4, hipMemcpyDeviceToDevice,
+                           static_cast<hipStream_t>(stream)), "hipMemcpyAsync");
+        if (dropout())
+          run(qt_dropout(QT_F32, at(p->lstm_x1), B, H, H, seed ^ 0x3C3C3C3CC3C3C3C3ull, p->d.dropout_p, stream));
       }
     }
-    const float* last = e.at<float>(p->lstm_l[1].hout) + (size_t)(T - 1) * H;  // h_{T-1} of every sequence
-    memset(&g, 0, sizeof(g));
-    g.M = S; g.N = 128; g.K = H;
-    g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-    g.a_row_stride = (long long)T * H; g.a_k_stride = 1; g.b_row_stride = H; g.b_k_stride = 1; g.c_row_stride = 128; g.relu = 1;
-    e.run(qt_gemm_small(&g, last, e.tf(p->cls0.w), e.tf(p->cls0.b), e.at(p->lstm_hid), stream));
-    if (tr && p->d.dropout_p > 0.f)
-      e.run(qt_dropout(QT_F32, e.at(p->lstm_hid), S, 128, 128, seed ^ 0xA5A5A5A55A5A5A5Aull, p->d.dropout_p, stream));
-    memset(&g, 0, sizeof(g));
-    g.M = S; g.N = p->cls3.out; g.K = 128;
-    g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-    g.a_row_stride = 128; g.a_k_stride = 1; g.b_row_stride = 128; g.b_k_stride = 1; g.c_row_stride = p->cls3.out;
-    e.run(qt_gemm_small(&g, e.at(p->lstm_hid), e.tf(p->cls3.w), e.tf(p->cls3.b), logits, stream));
-    p->last_batch = batch;
-    p->last_training = training;
-    p->last_seed = seed;
-    return e.status;
+    const float* last = at<float>(p->lstm_l[1].hout) + (size_t)(T - 1) * H;  // h_{T-1} of every sequence
+    dense_fwd(last, QT_F32, tf(p->cls0.w), tf(p->cls0.b), at(p->lstm_hid), QT_F32, S, H, 128, 1, (long long)T * H, 128, stream);
+    if (dropout())
+      run(qt_dropout(QT_F32, at(p->lstm_hid), S, 128, 128, seed ^ 0xA5A5A5A55A5A5A5Aull, p->d.dropout_p, stream));
+    dense_fwd(at(p->lstm_hid), QT_F32, tf(p->cls3.w), tf(p->cls3.b), logits, QT_F32, S, 128, p->cls3.out, 0, 128, p->cls3.out,
+              stream);
   }
+
   // ---- classifier: Linear -> ReLU -> Dropout -> Linear ----
-  e.linear(e.linear_desc(p->cls0.in, p->cls0.out, QT_CONV_FWD), e.at(p->fused), e.at(p->cls0.w_fwd), e.at(p->hidden),
-           e.tf(p->cls0.b), 1);
-  if (tr && p->d.dropout_p > 0.f)
-    e.run(qt_dropout(dt, e.at(p->hidden), batch, p->hidden_dim, p->hidden_dim, seed ^ 0xA5A5A5A55A5A5A5Aull,
-                     p->d.dropout_p, stream));
-  {
-    qt_gemm_small_desc g;
-    memset(&g, 0, sizeof(g));
-    g.M = batch; g.N = p->cls3.out; g.K = p->cls3.in;
-    g.a_dtype = dt; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-    g.a_row_stride = p->cls3.in; g.a_k_stride = 1; g.b_row_stride = p->cls3.in; g.b_k_stride = 1;
-    g.c_row_stride = p->cls3.out;
-    e.run(qt_gemm_small(&g, e.at(p->hidden), e.tf(p->cls3.w), e.tf(p->cls3.b), logits, stream));
+  void classifier() {
+    linear(linear_desc(p->cls0.in, p->cls0.out, QT_CONV_FWD), at(p->fused), at(p->cls0.w_fwd), at(p->hidden), tf(p->cls0.b), 1);
+    if (dropout())
+      run(qt_dropout(dt, at(p->hidden), B, p->hidden_dim, p->hidden_dim, seed ^ 0xA5A5A5A55A5A5A5Aull, p->d.dropout_p, stream));
+    dense_fwd(at(p->hidden), dt, tf(p->cls3.w), tf(p->cls3.b), logits, QT_F32, B, p->cls3.in, p->cls3.out, 0, p->cls3.in,
+              p->cls3.out, stream);
   }
-  (void)hs;
+};
+
+int forward(qt_plan* p, void* workspace, void* const* T, const float* image, const float* numerical, float* logits,
+            int batch, int training, unsigned long long seed, void* stream) {
+  Fwd e{{p, static_cast<unsigned char*>(workspace), T, stream, batch, p->d.dtype}, image, numerical, logits, training, seed};
+  e.tr = training == 1;
+  e.unf = training != 0;
+  e.mlp_early = p->has_image && p->has_numerical && !p->attention && !p->lstm && !p->standard;
+  e.setup_side();
+  p->tail_ready = false;
+  if (e.mlp_early) {
+    e.fork();
+    e.on_side(p->stats_ds, [&] { e.mlp_branch(); });
+  }
+  if (p->has_image) {
+    if (!e.tr) e.eval_affines(e.unf);
+    e.stem();
+    e.blocks();
+  }
+  if (p->has_numerical && (!p->has_image || p->lstm)) e.mlp_branch();  // numerical_only / CnnLstm: nothing to overlap with
+  e.join();  // quadrant + MLP columns of the fused matrix are complete
+  if (p->lstm)
+    e.lstm_tail();
+  else
+    e.classifier();
   p->last_batch = batch;
   p->last_training = training;
   p->last_seed = seed;
@@ -1170,12 +1168,29 @@ int zero(void* ptr, size_t bytes, void* stream) {
   return QT_OK;
 }
 
+// One qt_plan_backward call, in launch order: backward_head() (or backward_lstm_head()) -> backward_blocks() ->
+// backward_stem(), each if its phase was asked for
 struct Bwd : Exec {
   float* const* G;  // gradient pointers (same indexing as T), NULL = not wanted
+  const float* numerical;
+  const float* dlogits;
+  float* dimage;
+  int phases;
+  bool tr;          // the forward ran in training mode (batch statistics, dropout)
+  float drop_mul;   // 1 / (1 - p) where the forward applied dropout, else 1
+  // d(loss)/d(image) wanted: the backbone is walked for its data gradients even where it is frozen (weight gradients
+  // are skipped per tensor: wgrad and the BatchNorm finalize take NULL gradients)
+  bool want_dx;
+  bool walk;        // the backbone phases have work: backbone gradients or want_dx
   float* gf(int idx) const { return idx < 0 ? nullptr : G[idx]; }
   bool evalbn = false;  // the forward ran BatchNorm on running statistics (training == 2): no batch-mean terms
   long long bn_count(long long M) const { return evalbn ? 0 : M; }
 
+  // d(gamma), d(beta) and the coefficients of the apply pass from `rows` rows of partial sums over M values per channel
+  void bn_bwd_finalize(const BnL& bn, float* partial, int rows, long long M) {
+    run(qt_bn_bwd_finalize(partial, rows, bn.C, bn_count(M), tf(bn.gamma), at<float>(bn.invstd), gf(bn.gamma), gf(bn.beta), 0,
+                           at<float>(bn.coef), stream));
+  }
   // BatchNorm backward for conv c given g (in gy or external): dy -> c.gy
   void bn_backward(const ConvL& c, const void* g, void* g_out, float* pre_partial = nullptr, int pre_rows = 0) {
     if (!ok()) return;
@@ -1188,10 +1203,18 @@ struct Bwd : Exec {
       if (!ok()) return;
       rows = qt_bn_bwd_partial_rows(M, bn.C);
     }
-    run(qt_bn_bwd_finalize(part, rows, bn.C, bn_count(M), tf(bn.gamma), at<float>(bn.invstd), gf(bn.gamma), gf(bn.beta), 0,
-                           at<float>(bn.coef), stream));
+    bn_bwd_finalize(bn, part, rows, M);
     run(qt_bn_bwd_apply(dt, g, nullptr, at(c.y), at<float>(bn.mean), at<float>(bn.invstd), at<float>(bn.coef),
                         at(c.gy), g_out, M, bn.C, stream));
+  }
+  // the data gradient of a stride-2 conv as stride-1 gathers over its gradient map c.gy, each writing every second pixel
+  // of the input map; the caller sets the taps (kh, kw), n_out and the destination pixel class / merge fields
+  qt_conv_desc s2_gather_desc(const ConvL& c) const {
+    qt_conv_desc d = base_desc(dt, QT_CONV_FWD, B, 0, 1, 0);
+    d.in_h = d.in_w = c.hout; d.out_h = d.out_w = c.hin / 2;
+    set_source(d, c.cout, c.cin, c.hout, c.hout);
+    d.dst_sub = 2; d.dst_h = d.dst_w = c.hin;
+    return d;
   }
   // data gradient of conv c: dst = conv_transpose(c.gy) (+resid) (* (mask > 0)).  A stride-2
   // conv is run as four stride-1 gathers, one per parity class of the destination pixel, so no
@@ -1209,14 +1232,9 @@ struct Bwd : Exec {
       return qt_conv2d_stats_rows(&d);
     }
     if (c.merged_dgrad) {  // all four parity classes in one 2x2-tap launch over the gradient map
-      qt_conv_desc d;
-      memset(&d, 0, sizeof(d));
-      d.dtype = dt; d.mode = QT_CONV_FWD; d.batch = B;
-      d.in_h = d.in_w = c.hout; d.out_h = d.out_w = c.hin / 2;
-      d.k_per_tap = c.cout; d.n_out = 4 * c.cin;
-      d.kh = d.kw = 2; d.stride = 1; d.pad = 0;
-      d.src_pix_stride = c.cout; d.src_row_stride = c.hout * c.cout; d.src_img_stride = (long long)c.hout * c.hout * c.cout;
-      d.dst_sub = 2; d.dst_h = d.dst_w = c.hin; d.dst_merge = c.cin; d.dst_merge_res0 = sparse ? 1 : 0;
+      qt_conv_desc d = s2_gather_desc(c);
+      d.kh = d.kw = 2; d.n_out = 4 * c.cin;
+      d.dst_merge = c.cin; d.dst_merge_res0 = sparse ? 1 : 0;
       d.dst_merge_extra = c.merged5 ? 1 : 0;   // (+ the downsample's gradient map through the fifth tap slot)
       igemm(d, at(c.gy), at(c.w_dgrad), dst, nullptr, nullptr, resid, mask, nullptr, 0, 1, links, nlinks, mask_bits,
             c.merged5 ? at(p->convs[c.slot_conv].gy) : nullptr);
@@ -1235,14 +1253,9 @@ struct Bwd : Exec {
     int rows = 0;
     for (int cls = 0; cls < 4 && ok(); ++cls) {
       if (c.cls_kh[cls] * c.cls_kw[cls] == 0) continue;
-      qt_conv_desc d;
-      memset(&d, 0, sizeof(d));
-      d.dtype = dt; d.mode = QT_CONV_FWD; d.batch = B;
-      d.in_h = d.in_w = c.hout; d.out_h = d.out_w = c.hin / 2;
-      d.k_per_tap = c.cout; d.n_out = c.cin;
-      d.kh = c.cls_kh[cls]; d.kw = c.cls_kw[cls]; d.stride = 1; d.pad = 0;
-      d.src_pix_stride = c.cout; d.src_row_stride = c.hout * c.cout; d.src_img_stride = (long long)c.hout * c.hout * c.cout;
-      d.dst_sub = 2; d.dst_h = d.dst_w = c.hin; d.dst_off_h = cls >> 1; d.dst_off_w = cls & 1;
+      qt_conv_desc d = s2_gather_desc(c);
+      d.kh = c.cls_kh[cls]; d.kw = c.cls_kw[cls];
+      d.dst_off_h = cls >> 1; d.dst_off_w = cls & 1;
       BnLink l2[2];
       for (int k = 0; k < nlinks && k < 2; ++k) {
         l2[k] = links[k];
@@ -1262,8 +1275,7 @@ struct Bwd : Exec {
   // weight gradient of conv c: dy = c.gy, x = src
   void wgrad(const ConvL& c, const qt_conv_desc& fwd_desc, const void* src, bool stem) {
     if (!ok() || !gf(c.w)) return;
-    fork();
-    void* ws_ = wstream;
+    void* ws_ = side();
     const size_t n = stem ? (size_t)64 * 7 * 32 : (size_t)c.cout * c.cin * c.k * c.k;
     if (!stem && qt_conv2d_wgrad_workspace_bytes(&fwd_desc) > 0) {
       // streaming kernels (3x3 stride 1; the stride-2 pair of a transition block): the fixed-order sum of the partial
@@ -1294,6 +1306,290 @@ struct Bwd : Exec {
     else
       run(qt_unpack_conv_wgrad(at<float>(c.dw), gf(c.w), c.cout, c.cin, c.k, c.k, 0, ws_));
   }
+  // bias and weight gradients of a region head conv (dy = c.gy over all regions, x = src) on the weight-gradient stream
+  void head_conv_grads(const ConvL& c, const qt_conv_desc& fwd_desc, const void* src) {
+    if (gf(c.bias))   // (wgrad_part: same stream as the wgrad launches)
+      run(qt_col_sum_ws(dt, at(c.gy), (long long)B * c.regions * c.hout * c.hout, c.cout, c.cout, gf(c.bias), 0,
+                        at(p->wgrad_part), p->wgrad_part_bytes, side()));
+    wgrad(c, fwd_desc, src, false);
+  }
+  // bias gradient of an nn.Linear: column sums of dy [rows][n] (row stride ld)
+  void bias_grad(int dy_dt, const void* dy, int rows, int n, int ld, float* db, void* on) {
+    if (db) run(qt_col_sum(dy_dt, dy, rows, n, ld, db, 0, on));
+  }
+
+  // ---- CnnLstm: classifier -> last step -> LSTM layer 1 -> (dropout) -> LSTM layer 0 -> pose MLP; everything f32 and thin ----
+  void backward_lstm_head() {
+    const int T = p->seq_len, S = B / T, H = p->lstm_h;
+    const LinL &c0 = p->cls0, &c3 = p->cls3, &m0 = p->mlp0, &m1 = p->mlp1;
+    const float* last = at<float>(p->lstm_l[1].hout) + (size_t)(T - 1) * H;
+    float* dhid = at<float>(p->lstm_dhid);
+    dense_dx(dlogits, QT_F32, tf(c3.w), dhid, QT_F32, S, 128, c3.out, c3.out, 128, stream);
+    run(qt_relu_mask_scale(QT_F32, dhid, at(p->lstm_hid), (long long)S * 128, drop_mul, stream));
+    bias_grad(QT_F32, dlogits, S, c3.out, c3.out, gf(c3.b), stream);
+    dense_dw(dlogits, QT_F32, at(p->lstm_hid), QT_F32, gf(c3.w), S, 128, c3.out, c3.out, 128, stream);
+    bias_grad(QT_F32, dhid, S, 128, 128, gf(c0.b), stream);
+    dense_dw(dhid, QT_F32, last, QT_F32, gf(c0.w), S, H, 128, 128, (long long)T * H, stream);
+    dense_dx(dhid, QT_F32, tf(c0.w), at(p->lstm_dlast), QT_F32, S, H, 128, 128, H, stream);
+    for (int l = 1; l >= 0 && ok(); --l) {
+      const qt_plan::LstmL& L = p->lstm_l[l];
+      run(qt_lstm_backward(l == 1 ? nullptr : at<float>(p->lstm_dx1), l == 1 ? at<float>(p->lstm_dlast) : nullptr,
+                           at<float>(L.gates), at<float>(L.cell), tf(L.w_hh), at<float>(L.dgates), S, T, H, stream));
+      const float* dG = at<float>(L.dgates);
+      // dW_ih = dgates^T x, dW_hh = dgates^T h_prev: weight-gradient kernel (f32 MFMA), contraction over the frames
+      auto wgrad_dense = [&](const void* X, int in, float* dw) {
+        if (!dw || !ok()) return;
+        const qt_conv_desc wd = dense_f32(B, in, 4 * H);
+        run(zero(dw, (size_t)4 * H * in * 4, stream));
+        run(qt_conv2d_wgrad(&wd, dG, X, dw, stream));
+      };
+      wgrad_dense(l == 0 ? at(p->lstm_x0) : at(p->lstm_x1), L.in, gf(L.w_ih));
+      wgrad_dense(at(L.hprev), H, gf(L.w_hh));
+      run(qt_transpose_f32(tf(L.w_ih), at<float>(L.wih_t), 4 * H, L.in, stream));  // [in][4H]: operand of dx
+      bias_grad(QT_F32, dG, B, 4 * H, 4 * H, gf(L.b_ih), stream);
+      bias_grad(QT_F32, dG, B, 4 * H, 4 * H, gf(L.b_hh), stream);
+      if (l == 1) {
+        igemm(dense_f32(B, 4 * H, H), dG, at(L.wih_t), at(p->lstm_dx1), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+        if (tr && p->d.dropout_p > 0.f)
+          run(qt_scale_by_nonzero(at<float>(p->lstm_dx1), at<float>(p->lstm_x1), (long long)B * H, drop_mul, stream));
+      } else {  // only the pose-MLP columns of the fused features have trainable producers
+        igemm(dense_f32(B, 4 * H, 128), dG, at<float>(L.wih_t) + (size_t)p->mlp_col0 * 4 * H, at(p->lstm_dz), nullptr, nullptr,
+              nullptr, nullptr, nullptr, 0);
+      }
+    }
+    const float* dz = at<float>(p->lstm_dz);
+    bias_grad(QT_F32, dz, B, 128, 128, gf(m1.b), stream);
+    dense_dw(dz, QT_F32, at(p->h1), QT_F32, gf(m1.w), B, 128, 128, 128, 128, stream);
+    dense_dx(dz, QT_F32, tf(m1.w), at(p->dh1), QT_F32, B, 128, 128, 128, 128, stream);
+    run(qt_relu_mask_scale(QT_F32, at(p->dh1), at(p->h1), (long long)B * 128, 1.f, stream));
+    bias_grad(QT_F32, at(p->dh1), B, 128, 128, gf(m0.b), stream);
+    dense_dw(at(p->dh1), QT_F32, numerical, QT_F32, gf(m0.w), B, m0.in, 128, 128, m0.in, stream);
+  }
+
+  // ---- numerical MLP: small dependent kernels that only need dfused; they run on the side
+  // stream (behind classifier.0's weight gradient) while the main stream enters the backbone ----
+  void backward_mlp() {
+    const LinL &m0 = p->mlp0, &m1 = p->mlp1;
+    void* ms = side();
+    if (p->attention) {
+      // numerical_mlp = Linear -> ReLU -> Dropout (models.py:43-46), output inside the fused matrix
+      run(qt_relu_mask_cols(dt, at(p->dfused), at(p->fused), at<float>(p->dh1), B, m0.out, p->fused_ld, p->mlp_col0, drop_mul, ms));
+    } else {
+      const unsigned char* dz = at<unsigned char>(p->dfused) + (size_t)p->mlp_col0 * p->esz;
+      bias_grad(dt, dz, B, m1.out, p->fused_ld, gf(m1.b), ms);
+      dense_dw(dz, dt, at(p->h1), QT_F32, gf(m1.w), B, m1.in, m1.out, p->fused_ld, m1.in, ms);
+      dense_dx(dz, dt, tf(m1.w), at(p->dh1), QT_F32, B, m1.in, m1.out, p->fused_ld, m1.in, ms);
+      run(qt_relu_mask_scale(QT_F32, at(p->dh1), at(p->h1), (long long)B * m0.out, drop_mul, ms));
+    }
+    bias_grad(QT_F32, at(p->dh1), B, m0.out, m0.out, gf(m0.b), ms);
+    dense_dw(at(p->dh1), QT_F32, numerical, QT_F32, gf(m0.w), B, m0.in, m0.out, m0.out, m0.in, ms);
+  }
+
+  // ---- AttentionHierarchicalCNN: quadrant vectors, the attention gate (models.py:81-89), the sub-quadrant vectors ----
+  void backward_attention_heads() {
+    const ConvL& cq = p->convs[p->quad_conv];
+    const ConvL& cs = p->convs[p->sub_conv];
+    // mean-pool backward (+ReLU mask) -> conv bias / weight gradients
+    run(qt_region_avgpool_bwd(dt, at(p->dfused), dt, at(cq.y), at(cq.gy), B, 2, 196, 128, p->fused_ld, 512, stream));
+    head_conv_grads(cq, region_desc(cq, 2, QT_CONV_FWD), at(p->blocks[3].out));
+    run(qt_attention_gate_bwd(dt, at(p->dfused), at<float>(p->vsub), at<float>(p->att_act), at<float>(p->att_alpha),
+                              tf(p->att0.w), tf(p->att2.w), at<float>(p->att_ds), at<float>(p->att_dpre), at<float>(p->dvsub),
+                              B, p->fused_ld, 512 + 4 * 128, stream));
+    {
+      void* as = side();
+      const int rows = B * 16;
+      dense_dw(at(p->att_dpre), QT_F32, at(p->vsub), QT_F32, gf(p->att0.w), rows, 64, 32, 32, 64, as);  // [32][64] = dpre^T v
+      bias_grad(QT_F32, at(p->att_dpre), rows, 32, 32, gf(p->att0.b), as);
+      if (gf(p->att2.w)) {  // [1][32] = ds^T act  (one output row, a_row_stride 0: not dense_dw's shape)
+        qt_gemm_small_desc g{};
+        g.M = 1; g.N = 32; g.K = rows;
+        g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
+        g.a_row_stride = 0; g.a_k_stride = 1; g.b_row_stride = 1; g.b_k_stride = 32; g.c_row_stride = 32;
+        run(qt_gemm_small(&g, at(p->att_ds), at(p->att_act), nullptr, gf(p->att2.w), as));
+      }
+      bias_grad(QT_F32, at(p->att_ds), rows, 1, 1, gf(p->att2.b), as);
+    }
+    run(qt_region_avgpool_bwd(dt, at(p->dvsub), QT_F32, at(cs.y), at(cs.gy), B, 4, 49, 64, 16 * 64, 0, stream));
+    head_conv_grads(cs, region_desc(cs, 4, QT_CONV_FWD), at(p->blocks[3].out));
+  }
+
+  // ---- classifier, numerical MLP, attention / quadrant heads ----
+  // The chain the backbone waits for is  dlogits -> dhidden -> dfused -> (pool backward); bias sums and
+  // weight gradients hang off it and go to the side stream as soon as their inputs exist.
+  void backward_head() {
+    const LinL &c0 = p->cls0, &c3 = p->cls3;
+    // ---- classifier.3: d(loss)/d(hidden), then ReLU + dropout backward ----
+    dense_dx(dlogits, QT_F32, tf(c3.w), at(p->dhidden), dt, B, c3.in, c3.out, c3.out, c3.in, stream);
+    run(qt_relu_mask_scale(dt, at(p->dhidden), at(p->hidden), (long long)B * p->hidden_dim, drop_mul, stream));
+    const qt_conv_desc lf = linear_desc(c0.in, c0.out, QT_CONV_FWD);
+    {
+      void* ss = side();
+      bias_grad(QT_F32, dlogits, B, c3.out, c3.out, gf(c3.b), ss);
+      dense_dw(dlogits, QT_F32, at(p->hidden), dt, gf(c3.w), B, c3.in, c3.out, c3.out, c3.in, ss);
+      // ---- classifier.0: bias and weight gradients ----
+      bias_grad(dt, at(p->dhidden), B, c0.out, c0.out, gf(c0.b), ss);
+      if (gf(c0.w)) {   // written, not accumulated: no 58 MB zero fill, no float atomics (one row range per tile)
+        const int slot = begin_timed(conv_flops(lf), 2, ss);
+        run(qt_linear_wgrad(dt, at(p->dhidden), at(p->fused), gf(c0.w), B, c0.out, c0.in, ss));
+        end_timed(slot, ss);
+      }
+    }
+    const bool need_dfused = p->has_numerical || (p->has_image && (!p->standard || walk));
+    if (need_dfused)
+      linear(linear_desc(c0.in, c0.out, QT_CONV_DGRAD), at(p->dhidden), at(c0.w_dgrad), at(p->dfused), nullptr, 0);
+    if (p->has_numerical) backward_mlp();
+    if (p->attention) backward_attention_heads();
+    // ---- quadrant head (weights are trainable in every variant) ----
+    if (p->has_image && !p->standard && !p->attention) {
+      const ConvL& cq = p->convs[p->quad_conv];
+      run(qt_quad_pool_bwd(dt, at(p->dfused), at(p->q), at(p->dq), B, p->fused_ld, 512, stream));
+      head_conv_grads(cq, quad_desc(QT_CONV_FWD), at(p->blocks[5].out));
+    }
+  }
+
+  // The backbone can be run in three calls -- QT_BWD_LAYER4 (blocks 7, 6: 8.4 M of the 11.2 M backbone
+  // parameters), QT_BWD_LAYER32 (blocks 5..2: 2.6 M), QT_BWD_LAYER1 (blocks 1, 0 and the stem: 0.16 M) -- so
+  // that a data-parallel caller reduces each bucket while the next phase runs and only 0.6 MB of gradients
+  // is left to reduce after the last kernel.
+  void backward_blocks() {
+    const bool do_l4 = (phases & QT_BWD_LAYER4) != 0, do_l32 = (phases & QT_BWD_LAYER32) != 0;
+    const bool do_rest = (phases & QT_BWD_LAYER1) != 0;  // the last phase: layer1 and the stem
+    int rows_bn2 = 0;  // partial rows of bn2 / downsample-BN of the block being entered (0 = none yet)
+    if (do_l4) {
+      // gradient of layer4's output through avgpool (+ ReLU mask of the block output)
+      run(qt_avgpool_bwd(dt, at(p->dfused), at(p->blocks[7].out), at(p->blocks[7].gout), B, 49, 512, p->fused_ld, 0, stream));
+    } else {
+      rows_bn2 = p->bwd_rows_bn2;
+    }
+    const int bi_hi = do_l4 ? 7 : (do_l32 ? 5 : 1), bi_lo = do_rest ? 0 : (do_l32 ? 2 : 6);
+    // ReLU masks of the data-gradient epilogues as one bit per element (written by the training forward's qt_bn_act_mask
+    // launches): 1/16 of the bytes of the bf16 activation they replace as an operand.  QTCNN_MASK_BITS=0: the activations.
+    static const bool mask_bits = qt_env_int("QTCNN_MASK_BITS", 1) != 0;
+    for (int bi = bi_hi; bi >= bi_lo; --bi) {
+      const Block& blk = p->blocks[bi];
+      const ConvL& c1 = p->convs[blk.conv1];
+      const ConvL& c2 = p->convs[blk.conv2];
+      const size_t x = bi == 0 ? p->p0 : p->blocks[bi - 1].out;
+      const qt_conv_desc f1 = conv_desc(c1, QT_CONV_FWD), f2 = conv_desc(c2, QT_CONV_FWD);
+      // bn2 / conv2: the partial sums were emitted by the dgrad that wrote blk.gout
+      bn_backward(c2, at(blk.gout), nullptr, rows_bn2 ? at<float>(p->stats_bn2) : nullptr, rows_bn2);
+      wgrad(c2, f2, at(blk.a1), false);
+      {
+        const BnLink l = link_of(c1, p->stats_bn1);
+        const int r1 = mask_bits ? dgrad(c2, at(c1.gy), nullptr, nullptr, &l, 1, false, at<unsigned char>(blk.a1_bits))
+                                 : dgrad(c2, at(c1.gy), nullptr, at(blk.a1), &l, 1);
+        // bn1 / conv1
+        bn_backward(c1, at(c1.gy), nullptr, at<float>(p->stats_bn1), r1);
+      }
+      wgrad(c1, f1, at(x), false);
+      // gradient w.r.t. the block input = conv1 dgrad + identity path (+ quadrant head for layer3's output)
+      const void* resid = at(blk.gout);
+      // the downsample's data gradient reaches one pixel in four: if nothing else reads the map densely (the region
+      // heads below do), leave the rest unwritten and let only that parity class of conv1's data gradient add it
+      const bool sparse_ds = blk.ds >= 0 && c1.stride == 2 && c1.k == 3 && !c1.merged5 && !(bi == 4 && p->attention) &&
+                             !(bi == 6 && !p->standard && !p->attention);
+      if (blk.ds >= 0) {
+        const ConvL& cd = p->convs[blk.ds];
+        bn_backward(cd, at(blk.gout), nullptr, rows_bn2 ? at<float>(p->stats_ds) : nullptr, rows_bn2);
+        wgrad(cd, conv_desc(cd, QT_CONV_FWD), at(x), false);
+        if (c1.merged5) {   // the downsample's data gradient is the fifth tap slot of conv1's launch below: no map, no residual
+          resid = nullptr;
+        } else {
+          dgrad(cd, at(blk.gtmp), nullptr, nullptr, nullptr, 0, sparse_ds);
+          resid = at(blk.gtmp);
+        }
+      }
+      if (bi == 4 && p->attention) {  // layer2's output also feeds the two heads
+        const ConvL& cq = p->convs[p->quad_conv];
+        const ConvL& cs = p->convs[p->sub_conv];
+        igemm(region_desc(cq, 2, QT_CONV_DGRAD), at(cq.gy), at(cq.w_dgrad), at(p->gbase_tmp), nullptr, nullptr, resid, nullptr,
+              nullptr, 0);
+        igemm(region_desc(cs, 4, QT_CONV_DGRAD), at(cs.gy), at(cs.w_dgrad), at(p->gbase_tmp2), nullptr, nullptr,
+              at(p->gbase_tmp), nullptr, nullptr, 0);
+        resid = at(p->gbase_tmp2);
+      }
+      if (bi == 6 && !p->standard && !p->attention) {
+        const ConvL& cq = p->convs[p->quad_conv];
+        igemm(quad_desc(QT_CONV_DGRAD), at(p->dq), at(cq.w_dgrad), at(p->gbase_tmp), nullptr, nullptr, resid, nullptr, nullptr, 0);
+        resid = at(p->gbase_tmp);
+      }
+      void* gprev = bi == 0 ? at(p->g_p0) : at(p->blocks[bi - 1].gout);
+      const void* mask = (bi == 0 || mask_bits) ? nullptr : at(x);
+      const unsigned char* mbits = (bi > 0 && mask_bits) ? at<unsigned char>(p->blocks[bi - 1].out_bits) : nullptr;
+      BnLink links[2];
+      int nlinks = 0;
+      if (bi > 0) {  // gprev feeds bn2 (and the downsample BN) of the previous block
+        const Block& pb = p->blocks[bi - 1];
+        links[nlinks++] = link_of(p->convs[pb.conv2], p->stats_bn2);
+        if (pb.ds >= 0) links[nlinks++] = link_of(p->convs[pb.ds], p->stats_ds);
+      }
+      rows_bn2 = dgrad(c1, gprev, resid, mask, links, nlinks, sparse_ds, mbits);
+      if (bi == 0) rows_bn2 = 0;
+    }
+    p->bwd_rows_bn2 = rows_bn2;
+  }
+
+  // ---- stem ----
+  void backward_stem() {
+    const ConvL& c0 = p->convs[0];
+    const BnL& bn0 = p->bns[c0.bn];
+    // max-pool backward + ReLU mask + bn1 backward without materialising d(loss)/d(relu output):
+    // the BatchNorm sums come from the pooled side (each pooled cell feeds exactly one conv1
+    // position: 2 x 103 MB read instead of a pass over two 411 MB maps), then one kernel gathers
+    // the <= 4 pooled cells of every conv1 position and writes d(loss)/d(conv1 output) directly.
+    // QTCNN_STEM_FUSED=0 keeps the three-pass form (pool backward, reduce, apply) for A/B runs.
+    static const bool fused = qt_env_int("QTCNN_STEM_FUSED", 1) != 0;
+    bool stem_done = false;   // conv1's weight gradient has been produced by the one-launch stem backward
+    if (fused) {
+      const int rows = qt_stem_bn_bwd_sums_rows(B);
+      run(qt_stem_bn_bwd_sums(dt, at(p->g_p0), at(p->ymax), at<float>(bn0.scale), at<float>(bn0.shift), at<float>(bn0.mean),
+                              at<float>(bn0.invstd), at<float>(p->stats), B, stream));
+      bn_bwd_finalize(bn0, at<float>(p->stats), rows, (long long)B * 112 * 112);
+      // bf16: BatchNorm / ReLU / max-pool backward of conv1's output AND conv1's weight gradient in one launch on the
+      // weight-gradient stream (the map d(loss)/d(conv1 output) never exists); otherwise the apply pass, then wgrad below
+      if (gf(c0.w)) {
+        // Without an image gradient it runs on the CALLER's stream (its inputs, the two launches above, are there), so
+        // that the side stream is free for the optimizer's bulk (adam_step): the caller's stream first waits for the side
+        // stream's weight-gradient launches, which share wgrad_part, and the side stream is ordered behind the caller's
+        // stream HERE, before the stem launch is enqueued.  (A wait enqueued later, at the optimizer step, was measured to
+        // hold the side stream until the stem backward had finished, although the event had been recorded before it.)
+        const bool on_main = dt == QT_BF16 && !want_dx && wstream != stream;
+        if (on_main) {
+          forked = true;
+          join();
+          fork();
+        } else {
+          fork();
+        }
+        void* ws_ = on_main ? stream : wstream;
+        const int slot = begin_timed(conv_flops(stem_desc(true)), 2, ws_, wgrad_bytes(c0, stem_desc(true)));
+        // (deterministic form: partial filters in wgrad_part, which no launch on the other stream is using)
+        const int st = qt_stem_bn_bwd_wgrad_ws(dt, at(p->g_p0), at<unsigned char>(p->argmax), at(c0.y), at<float>(bn0.scale),
+                                               at<float>(bn0.shift), at<float>(bn0.mean), at<float>(bn0.invstd),
+                                               at<float>(bn0.coef), at(p->xpad), at<float>(c0.dw), at(p->wgrad_part),
+                                               p->wgrad_part_bytes, B, ws_);
+        end_timed(slot, ws_);
+        if (st == QT_OK) {
+          run(qt_unpack_stem_wgrad(at<float>(c0.dw), gf(c0.w), 0, ws_));
+          stem_done = true;
+          p->tail_ready = on_main && ok() && (phases & QT_BWD_ALL) == QT_BWD_ALL;
+        } else if (st != QT_ERR_UNSUPPORTED) {
+          run(st);
+        }
+      }
+      if (!stem_done || want_dx)   // (with the one-launch form on the side stream: the map for qt_stem_dgrad only)
+        run(qt_stem_bn_bwd_apply(dt, at(p->g_p0), at<unsigned char>(p->argmax), at(c0.y), at<float>(bn0.scale),
+                                 at<float>(bn0.shift), at<float>(bn0.mean), at<float>(bn0.invstd), at<float>(bn0.coef),
+                                 at(c0.gy), B, stream));
+    } else {
+      run(qt_stem_pool_bwd(dt, at(p->g_p0), at<unsigned char>(p->argmax), at(c0.y), at<float>(bn0.scale), at<float>(bn0.shift),
+                           at(c0.gy), B, stream));
+      bn_backward(c0, at(c0.gy), nullptr);
+    }
+    if (!stem_done) wgrad(c0, stem_desc(true), at(p->xpad), true);
+    // d(loss)/d(image) on the main stream, beside the stem's weight gradient on the side stream
+    if (want_dx) run(qt_stem_dgrad(dt, at(c0.gy), tf(c0.w), dimage, B, stream));
+  }
 };
 
 int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const float* numerical,
@@ -1310,9 +1606,7 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
   }
   QT_CHECK_ARG(!dimage || !p->has_image || p->packed_bwd,
                "qt_plan_backward_dx: the data-gradient operands are not packed (qt_plan_pack_weights with for_backward = 1)");
-  Bwd e;
-  e.p = p; e.ws = static_cast<unsigned char*>(workspace); e.T = T; e.stream = stream; e.B = p->last_batch;
-  e.dt = p->d.dtype; e.G = G;
+  Bwd e{{p, static_cast<unsigned char*>(workspace), T, stream, p->last_batch, p->d.dtype}, G, numerical, dlogits, dimage, phases};
   e.setup_side();
   p->tail_ready = false;
   if ((phases & QT_BWD_HEAD) || p->dw_dirty) {  // once per backward, before any weight-gradient launch
@@ -1320,21 +1614,17 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
     p->dw_dirty = false;
   }
   if (phases & QT_BWD_LAYER1) p->dw_dirty = true;
-  const int dt = e.dt;
-  const int B = e.B;
-  const bool tr = p->last_training == 1;
+  e.tr = p->last_training == 1;
   e.evalbn = p->last_training == 2;
-  const float drop_mul = (tr && p->d.dropout_p > 0.f) ? 1.f / (1.f - p->d.dropout_p) : 1.f;
+  e.drop_mul = (e.tr && p->d.dropout_p > 0.f) ? 1.f / (1.f - p->d.dropout_p) : 1.f;
   bool backbone_grads = false;
   if (p->has_image)
     for (size_t i = 0; i < p->convs.size(); ++i) {
       if ((int)i == p->quad_conv || (int)i == p->sub_conv) continue;
       if (G[p->convs[i].w]) backbone_grads = true;
     }
-  // d(loss)/d(image) wanted: the backbone is walked for its data gradients even where it is frozen (weight gradients
-  // are skipped per tensor: wgrad and the BatchNorm finalize take NULL gradients)
-  const bool want_dx = dimage != nullptr && p->has_image;
-  const bool walk = backbone_grads || want_dx;
+  e.want_dx = dimage != nullptr && p->has_image;
+  e.walk = backbone_grads || e.want_dx;
   if (backbone_grads && p->last_training == 0) {
     qt_set_error("qt_plan_backward: the last forward ran fused eval kernels (training = 0) and kept nothing for a backbone "
                  "backward; run it with training = 2 (eval statistics, tensors kept)");
@@ -1346,360 +1636,18 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
       return QT_ERR_UNSUPPORTED;
     }
     if (!(phases & QT_BWD_HEAD)) return QT_OK;
-    // ---- classifier -> last step -> LSTM layer 1 -> (dropout) -> LSTM layer 0 -> pose MLP; everything f32 and thin ----
-    const int T = p->seq_len, S = B / T, H = p->lstm_h;
-    qt_gemm_small_desc g;
-    auto gemm = [&](int M, int N, int K, const void* A, int adt, long long ars, long long aks, const void* Bm, int bdt,
-                    long long brs, long long bks, void* C, long long crs) {
-      memset(&g, 0, sizeof(g));
-      g.M = M; g.N = N; g.K = K; g.a_dtype = adt; g.b_dtype = bdt; g.c_dtype = QT_F32;
-      g.a_row_stride = ars; g.a_k_stride = aks; g.b_row_stride = brs; g.b_k_stride = bks; g.c_row_stride = crs;
-      if (C) e.run(qt_gemm_small(&g, A, Bm, nullptr, C, stream));
-    };
-    const float* last = e.at<float>(p->lstm_l[1].hout) + (size_t)(T - 1) * H;
-    float* dhid = e.at<float>(p->lstm_dhid);
-    gemm(S, 128, p->cls3.out, dlogits, QT_F32, p->cls3.out, 1, e.tf(p->cls3.w), QT_F32, 1, 128, dhid, 128);
-    e.run(qt_relu_mask_scale(QT_F32, dhid, e.at(p->lstm_hid), (long long)S * 128, drop_mul, stream));
-    if (e.gf(p->cls3.b)) e.run(qt_col_sum(QT_F32, dlogits, S, p->cls3.out, p->cls3.out, e.gf(p->cls3.b), 0, stream));
-    gemm(p->cls3.out, 128, S, dlogits, QT_F32, 1, p->cls3.out, e.at(p->lstm_hid), QT_F32, 1, 128, e.gf(p->cls3.w), 128);
-    if (e.gf(p->cls0.b)) e.run(qt_col_sum(QT_F32, dhid, S, 128, 128, e.gf(p->cls0.b), 0, stream));
-    gemm(128, H, S, dhid, QT_F32, 1, 128, last, QT_F32, 1, (long long)T * H, e.gf(p->cls0.w), H);
-    gemm(S, H, 128, dhid, QT_F32, 128, 1, e.tf(p->cls0.w), QT_F32, 1, H, e.at(p->lstm_dlast), H);
-    for (int l = 1; l >= 0 && e.ok(); --l) {
-      const qt_plan::LstmL& L = p->lstm_l[l];
-      e.run(qt_lstm_backward(l == 1 ? nullptr : e.at<float>(p->lstm_dx1), l == 1 ? e.at<float>(p->lstm_dlast) : nullptr,
-                             e.at<float>(L.gates), e.at<float>(L.cell), e.tf(L.w_hh), e.at<float>(L.dgates), S, T, H, stream));
-      const float* dG = e.at<float>(L.dgates);
-      // dW_ih = dgates^T x, dW_hh = dgates^T h_prev: weight-gradient kernel (f32 MFMA), contraction over the frames
-      auto wgrad_dense = [&](const void* X, int in, float* dw) {
-        if (!dw || !e.ok()) return;
-        const qt_conv_desc wd = e.dense_f32(B, in, 4 * H);
-        e.run(zero(dw, (size_t)4 * H * in * 4, stream));
-        e.run(qt_conv2d_wgrad(&wd, dG, X, dw, stream));
-      };
-      wgrad_dense(l == 0 ? e.at(p->lstm_x0) : e.at(p->lstm_x1), L.in, e.gf(L.w_ih));
-      wgrad_dense(e.at(L.hprev), H, e.gf(L.w_hh));
-      e.run(qt_transpose_f32(e.tf(L.w_ih), e.at<float>(L.wih_t), 4 * H, L.in, stream));  // [in][4H]: operand of dx
-      if (e.gf(L.b_ih)) e.run(qt_col_sum(QT_F32, dG, B, 4 * H, 4 * H, e.gf(L.b_ih), 0, stream));
-      if (e.gf(L.b_hh)) e.run(qt_col_sum(QT_F32, dG, B, 4 * H, 4 * H, e.gf(L.b_hh), 0, stream));
-      if (l == 1) {
-        e.igemm(e.dense_f32(B, 4 * H, H), dG, e.at(L.wih_t), e.at(p->lstm_dx1), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-        if (tr && p->d.dropout_p > 0.f)
-          e.run(qt_scale_by_nonzero(e.at<float>(p->lstm_dx1), e.at<float>(p->lstm_x1), (long long)B * H, drop_mul, stream));
-      } else {  // only the pose-MLP columns of the fused features have trainable producers
-        e.igemm(e.dense_f32(B, 4 * H, 128), dG, e.at<float>(L.wih_t) + (size_t)p->mlp_col0 * 4 * H, e.at(p->lstm_dz), nullptr,
-                nullptr, nullptr, nullptr, nullptr, 0);
-      }
-    }
-    const float* dz = e.at<float>(p->lstm_dz);
-    if (e.gf(p->mlp1.b)) e.run(qt_col_sum(QT_F32, dz, B, 128, 128, e.gf(p->mlp1.b), 0, stream));
-    gemm(128, 128, B, dz, QT_F32, 1, 128, e.at(p->h1), QT_F32, 1, 128, e.gf(p->mlp1.w), 128);
-    gemm(B, 128, 128, dz, QT_F32, 128, 1, e.tf(p->mlp1.w), QT_F32, 1, 128, e.at(p->dh1), 128);
-    e.run(qt_relu_mask_scale(QT_F32, e.at(p->dh1), e.at(p->h1), (long long)B * 128, 1.f, stream));
-    if (e.gf(p->mlp0.b)) e.run(qt_col_sum(QT_F32, e.at(p->dh1), B, 128, 128, e.gf(p->mlp0.b), 0, stream));
-    gemm(128, p->mlp0.in, B, e.at(p->dh1), QT_F32, 1, 128, numerical, QT_F32, 1, p->mlp0.in, e.gf(p->mlp0.w), p->mlp0.in);
+    e.backward_lstm_head();
     return e.status;
   }
-
-  if (phases & QT_BWD_HEAD) {
-    qt_gemm_small_desc g;
-    // The chain the backbone waits for is  dlogits -> dhidden -> dfused -> (pool backward); bias sums and
-    // weight gradients hang off it and go to the side stream as soon as their inputs exist.
-    // ---- classifier.3: d(loss)/d(hidden), then ReLU + dropout backward ----
-    memset(&g, 0, sizeof(g));
-    g.M = B; g.N = p->cls3.in; g.K = p->cls3.out;
-    g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = dt;
-    g.a_row_stride = p->cls3.out; g.a_k_stride = 1; g.b_row_stride = 1; g.b_k_stride = p->cls3.in;
-    g.c_row_stride = p->cls3.in;
-    e.run(qt_gemm_small(&g, dlogits, e.tf(p->cls3.w), nullptr, e.at(p->dhidden), stream));
-    e.run(qt_relu_mask_scale(dt, e.at(p->dhidden), e.at(p->hidden), (long long)B * p->hidden_dim, drop_mul, stream));
-    const qt_conv_desc lf = e.linear_desc(p->cls0.in, p->cls0.out, QT_CONV_FWD);
-    {
-      e.fork();
-      void* ss = e.wstream ? e.wstream : stream;
-      void* ts = ss;
-      if (e.gf(p->cls3.b)) e.run(qt_col_sum(QT_F32, dlogits, B, p->cls3.out, p->cls3.out, e.gf(p->cls3.b), 0, ts));
-      if (e.gf(p->cls3.w)) {
-        memset(&g, 0, sizeof(g));
-        g.M = p->cls3.out; g.N = p->cls3.in; g.K = B;
-        g.a_dtype = QT_F32; g.b_dtype = dt; g.c_dtype = QT_F32;
-        g.a_row_stride = 1; g.a_k_stride = p->cls3.out; g.b_row_stride = 1; g.b_k_stride = p->cls3.in;
-        g.c_row_stride = p->cls3.in;
-        e.run(qt_gemm_small(&g, dlogits, e.at(p->hidden), nullptr, e.gf(p->cls3.w), ts));
-      }
-      // ---- classifier.0: bias and weight gradients ----
-      if (e.gf(p->cls0.b)) e.run(qt_col_sum(dt, e.at(p->dhidden), B, p->cls0.out, p->cls0.out, e.gf(p->cls0.b), 0, ts));
-      if (e.gf(p->cls0.w)) {   // written, not accumulated: no 58 MB zero fill, no float atomics (one row range per tile)
-        const int slot = e.begin_timed(e.conv_flops(lf), 2, ss);
-        e.run(qt_linear_wgrad(dt, e.at(p->dhidden), e.at(p->fused), e.gf(p->cls0.w), B, p->cls0.out, p->cls0.in, ss));
-        e.end_timed(slot, ss);
-      }
-    }
-    const bool need_dfused = p->has_numerical || (p->has_image && (!p->standard || walk));
-    if (need_dfused)
-      e.linear(e.linear_desc(p->cls0.in, p->cls0.out, QT_CONV_DGRAD), e.at(p->dhidden), e.at(p->cls0.w_dgrad), e.at(p->dfused),
-               nullptr, 0);
-    // ---- numerical MLP: seven small dependent kernels that only need dfused; they run on the side
-    // stream (behind classifier.0's weight gradient) while the main stream enters the backbone ----
-    if (p->attention) {
-      // numerical_mlp = Linear -> ReLU -> Dropout (models.py:43-46), output inside the fused matrix
-      e.fork();
-      void* ms = e.wstream ? e.wstream : stream;
-      e.run(qt_relu_mask_cols(dt, e.at(p->dfused), e.at(p->fused), e.at<float>(p->dh1), B, p->mlp0.out, p->fused_ld,
-                              p->mlp_col0, drop_mul, ms));
-      if (e.gf(p->mlp0.b)) e.run(qt_col_sum(QT_F32, e.at(p->dh1), B, p->mlp0.out, p->mlp0.out, e.gf(p->mlp0.b), 0, ms));
-      if (e.gf(p->mlp0.w)) {
-        memset(&g, 0, sizeof(g));
-        g.M = p->mlp0.out; g.N = p->mlp0.in; g.K = B;
-        g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-        g.a_row_stride = 1; g.a_k_stride = p->mlp0.out; g.b_row_stride = 1; g.b_k_stride = p->mlp0.in;
-        g.c_row_stride = p->mlp0.in;
-        e.run(qt_gemm_small(&g, e.at(p->dh1), numerical, nullptr, e.gf(p->mlp0.w), ms));
-      }
-    } else if (p->has_numerical) {
-      e.fork();
-      void* ms = e.wstream ? e.wstream : stream;
-      const unsigned char* dz = e.at<unsigned char>(p->dfused) + (size_t)p->mlp_col0 * p->esz;
-      if (e.gf(p->mlp1.b)) e.run(qt_col_sum(dt, dz, B, p->mlp1.out, p->fused_ld, e.gf(p->mlp1.b), 0, ms));
-      if (e.gf(p->mlp1.w)) {
-        memset(&g, 0, sizeof(g));
-        g.M = p->mlp1.out; g.N = p->mlp1.in; g.K = B;
-        g.a_dtype = dt; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-        g.a_row_stride = 1; g.a_k_stride = p->fused_ld; g.b_row_stride = 1; g.b_k_stride = p->mlp1.in;
-        g.c_row_stride = p->mlp1.in;
-        e.run(qt_gemm_small(&g, dz, e.at(p->h1), nullptr, e.gf(p->mlp1.w), ms));
-      }
-      memset(&g, 0, sizeof(g));
-      g.M = B; g.N = p->mlp1.in; g.K = p->mlp1.out;
-      g.a_dtype = dt; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-      g.a_row_stride = p->fused_ld; g.a_k_stride = 1; g.b_row_stride = 1; g.b_k_stride = p->mlp1.in;
-      g.c_row_stride = p->mlp1.in;
-      e.run(qt_gemm_small(&g, dz, e.tf(p->mlp1.w), nullptr, e.at(p->dh1), ms));
-      e.run(qt_relu_mask_scale(QT_F32, e.at(p->dh1), e.at(p->h1), (long long)B * p->mlp0.out, drop_mul, ms));
-      if (e.gf(p->mlp0.b)) e.run(qt_col_sum(QT_F32, e.at(p->dh1), B, p->mlp0.out, p->mlp0.out, e.gf(p->mlp0.b), 0, ms));
-      if (e.gf(p->mlp0.w)) {
-        memset(&g, 0, sizeof(g));
-        g.M = p->mlp0.out; g.N = p->mlp0.in; g.K = B;
-        g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-        g.a_row_stride = 1; g.a_k_stride = p->mlp0.out; g.b_row_stride = 1; g.b_k_stride = p->mlp0.in;
-        g.c_row_stride = p->mlp0.in;
-        e.run(qt_gemm_small(&g, e.at(p->dh1), numerical, nullptr, e.gf(p->mlp0.w), ms));
-      }
-    }
-    if (p->attention) {
-      // ---- quadrant vectors: mean-pool backward (+ReLU mask) -> conv bias / weight gradients ----
-      const ConvL& cq = p->convs[p->quad_conv];
-      const ConvL& cs = p->convs[p->sub_conv];
-      e.run(qt_region_avgpool_bwd(dt, e.at(p->dfused), dt, e.at(cq.y), e.at(cq.gy), B, 2, 196, 128, p->fused_ld, 512, stream));
-      if (e.gf(cq.bias)) {
-        e.fork();
-        e.run(qt_col_sum_ws(dt, e.at(cq.gy), (long long)B * 4 * 196, 128, 128, e.gf(cq.bias), 0, e.at(p->wgrad_part), p->wgrad_part_bytes,
-                          e.wstream ? e.wstream : stream));   // (wgrad_part: same stream as the wgrad launches)
-      }
-      e.wgrad(cq, e.region_desc(cq, 2, QT_CONV_FWD), e.at(p->blocks[3].out), false);
-      // ---- attention gate (models.py:81-89), then the sub-quadrant vectors ----
-      e.run(qt_attention_gate_bwd(dt, e.at(p->dfused), e.at<float>(p->vsub), e.at<float>(p->att_act),
-                                  e.at<float>(p->att_alpha), e.tf(p->att0.w), e.tf(p->att2.w), e.at<float>(p->att_ds),
-                                  e.at<float>(p->att_dpre), e.at<float>(p->dvsub), B, p->fused_ld, 512 + 4 * 128, stream));
-      {
-        e.fork();
-        void* as = e.wstream ? e.wstream : stream;
-        const int rows = B * 16;
-        if (e.gf(p->att0.w)) {  // [32][64] = dpre^T v
-          memset(&g, 0, sizeof(g));
-          g.M = 32; g.N = 64; g.K = rows;
-          g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-          g.a_row_stride = 1; g.a_k_stride = 32; g.b_row_stride = 1; g.b_k_stride = 64; g.c_row_stride = 64;
-          e.run(qt_gemm_small(&g, e.at(p->att_dpre), e.at(p->vsub), nullptr, e.gf(p->att0.w), as));
-        }
-        if (e.gf(p->att0.b)) e.run(qt_col_sum(QT_F32, e.at(p->att_dpre), rows, 32, 32, e.gf(p->att0.b), 0, as));
-        if (e.gf(p->att2.w)) {  // [1][32] = ds^T act
-          memset(&g, 0, sizeof(g));
-          g.M = 1; g.N = 32; g.K = rows;
-          g.a_dtype = QT_F32; g.b_dtype = QT_F32; g.c_dtype = QT_F32;
-          g.a_row_stride = 0; g.a_k_stride = 1; g.b_row_stride = 1; g.b_k_stride = 32; g.c_row_stride = 32;
-          e.run(qt_gemm_small(&g, e.at(p->att_ds), e.at(p->att_act), nullptr, e.gf(p->att2.w), as));
-        }
-        if (e.gf(p->att2.b)) e.run(qt_col_sum(QT_F32, e.at(p->att_ds), rows, 1, 1, e.gf(p->att2.b), 0, as));
-      }
-      e.run(qt_region_avgpool_bwd(dt, e.at(p->dvsub), QT_F32, e.at(cs.y), e.at(cs.gy), B, 4, 49, 64, 16 * 64, 0, stream));
-      if (e.gf(cs.bias)) {
-        e.fork();
-        e.run(qt_col_sum_ws(dt, e.at(cs.gy), (long long)B * 16 * 49, 64, 64, e.gf(cs.bias), 0, e.at(p->wgrad_part), p->wgrad_part_bytes,
-                          e.wstream ? e.wstream : stream));   // (wgrad_part: same stream as the wgrad launches)
-      }
-      e.wgrad(cs, e.region_desc(cs, 4, QT_CONV_FWD), e.at(p->blocks[3].out), false);
-    }
-    // ---- quadrant head (weights are trainable in every variant) ----
-    if (p->has_image && !p->standard && !p->attention) {
-      const ConvL& cq = p->convs[p->quad_conv];
-      e.run(qt_quad_pool_bwd(dt, e.at(p->dfused), e.at(p->q), e.at(p->dq), B, p->fused_ld, 512, stream));
-      if (e.gf(cq.bias)) {
-        e.fork();
-        e.run(qt_col_sum_ws(dt, e.at(p->dq), (long long)B * 196, 128, 128, e.gf(cq.bias), 0, e.at(p->wgrad_part), p->wgrad_part_bytes,
-                          e.wstream ? e.wstream : stream));   // (wgrad_part: same stream as the wgrad launches)
-      }
-      e.wgrad(cq, e.quad_desc(QT_CONV_FWD), e.at(p->blocks[5].out), false);
-    }
-  }
-
+  if (phases & QT_BWD_HEAD) e.backward_head();
   // (no join after a partial phase: the caller orders its consumer behind the side stream with
   //  qt_plan_side_fence, so the main chain never stalls on the weight-gradient stream)
-
-  // The backbone can be run in three calls -- QT_BWD_LAYER4 (blocks 7, 6: 8.4 M of the 11.2 M backbone
-  // parameters), QT_BWD_LAYER32 (blocks 5..2: 2.6 M), QT_BWD_LAYER1 (blocks 1, 0 and the stem: 0.16 M) -- so
-  // that a data-parallel caller reduces each bucket while the next phase runs and only 0.6 MB of gradients
-  // is left to reduce after the last kernel.
-  if ((phases & QT_BWD_BACKBONE) && walk) {
-    const bool do_l4 = (phases & QT_BWD_LAYER4) != 0, do_l32 = (phases & QT_BWD_LAYER32) != 0;
-    const bool do_rest = (phases & QT_BWD_LAYER1) != 0;  // the last phase: layer1 and the stem
-    int rows_bn2 = 0;  // partial rows of bn2 / downsample-BN of the block being entered (0 = none yet)
-    if (do_l4) {
-      // gradient of layer4's output through avgpool (+ ReLU mask of the block output)
-      e.run(qt_avgpool_bwd(dt, e.at(p->dfused), e.at(p->blocks[7].out), e.at(p->blocks[7].gout), B, 49, 512,
-                           p->fused_ld, 0, stream));
-    } else {
-      rows_bn2 = p->bwd_rows_bn2;
-    }
-    const int bi_hi = do_l4 ? 7 : (do_l32 ? 5 : 1), bi_lo = do_rest ? 0 : (do_l32 ? 2 : 6);
-    // ReLU masks of the data-gradient epilogues as one bit per element (written by the training forward's qt_bn_act_mask
-    // launches): 1/16 of the bytes of the bf16 activation they replace as an operand.  QTCNN_MASK_BITS=0: the activations.
-    static const bool mask_bits = !(getenv("QTCNN_MASK_BITS") && atoi(getenv("QTCNN_MASK_BITS")) == 0);
-    for (int bi = bi_hi; bi >= bi_lo; --bi) {
-      const Block& blk = p->blocks[bi];
-      const ConvL& c1 = p->convs[blk.conv1];
-      const ConvL& c2 = p->convs[blk.conv2];
-      const size_t x = bi == 0 ? p->p0 : p->blocks[bi - 1].out;
-      const qt_conv_desc f1 = e.conv_desc(c1, QT_CONV_FWD), f2 = e.conv_desc(c2, QT_CONV_FWD);
-      // bn2 / conv2: the partial sums were emitted by the dgrad that wrote blk.gout
-      e.bn_backward(c2, e.at(blk.gout), nullptr, rows_bn2 ? e.at<float>(p->stats_bn2) : nullptr, rows_bn2);
-      e.wgrad(c2, f2, e.at(blk.a1), false);
-      {
-        const BnL& b1 = p->bns[c1.bn];
-        Exec::BnLink l = {e.at(c1.y), e.at<float>(b1.mean), e.at<float>(b1.invstd), e.at<float>(p->stats_bn1)};
-        const int r1 = mask_bits ? e.dgrad(c2, e.at(c1.gy), nullptr, nullptr, &l, 1, false, e.at<unsigned char>(blk.a1_bits))
-                                 : e.dgrad(c2, e.at(c1.gy), nullptr, e.at(blk.a1), &l, 1);
-        // bn1 / conv1
-        e.bn_backward(c1, e.at(c1.gy), nullptr, e.at<float>(p->stats_bn1), r1);
-      }
-      e.wgrad(c1, f1, e.at(x), false);
-      // gradient w.r.t. the block input = conv1 dgrad + identity path (+ quadrant head for layer3's output)
-      const void* resid = e.at(blk.gout);
-      // the downsample's data gradient reaches one pixel in four: if nothing else reads the map densely (the region
-      // heads below do), leave the rest unwritten and let only that parity class of conv1's data gradient add it
-      const bool sparse_ds = blk.ds >= 0 && c1.stride == 2 && c1.k == 3 && !c1.merged5 && !(bi == 4 && p->attention) &&
-                             !(bi == 6 && !p->standard && !p->attention);
-      if (blk.ds >= 0) {
-        const ConvL& cd = p->convs[blk.ds];
-        e.bn_backward(cd, e.at(blk.gout), nullptr, rows_bn2 ? e.at<float>(p->stats_ds) : nullptr, rows_bn2);
-        e.wgrad(cd, e.conv_desc(cd, QT_CONV_FWD), e.at(x), false);
-        if (c1.merged5) {   // the downsample's data gradient is the fifth tap slot of conv1's launch below: no map, no residual
-          resid = nullptr;
-        } else {
-          e.dgrad(cd, e.at(blk.gtmp), nullptr, nullptr, nullptr, 0, sparse_ds);
-          resid = e.at(blk.gtmp);
-        }
-      }
-      if (bi == 4 && p->attention) {  // layer2's output also feeds the two heads
-        const ConvL& cq = p->convs[p->quad_conv];
-        const ConvL& cs = p->convs[p->sub_conv];
-        e.igemm(e.region_desc(cq, 2, QT_CONV_DGRAD), e.at(cq.gy), e.at(cq.w_dgrad), e.at(p->gbase_tmp), nullptr, nullptr,
-                resid, nullptr, nullptr, 0);
-        e.igemm(e.region_desc(cs, 4, QT_CONV_DGRAD), e.at(cs.gy), e.at(cs.w_dgrad), e.at(p->gbase_tmp2), nullptr, nullptr,
-                e.at(p->gbase_tmp), nullptr, nullptr, 0);
-        resid = e.at(p->gbase_tmp2);
-      }
-      if (bi == 6 && !p->standard && !p->attention) {
-        const ConvL& cq = p->convs[p->quad_conv];
-        e.igemm(e.quad_desc(QT_CONV_DGRAD), e.at(p->dq), e.at(cq.w_dgrad), e.at(p->gbase_tmp), nullptr, nullptr, resid,
-                nullptr, nullptr, 0);
-        resid = e.at(p->gbase_tmp);
-      }
-      void* gprev = bi == 0 ? e.at(p->g_p0) : e.at(p->blocks[bi - 1].gout);
-      const void* mask = (bi == 0 || mask_bits) ? nullptr : e.at(x);
-      const unsigned char* mbits = (bi > 0 && mask_bits) ? e.at<unsigned char>(p->blocks[bi - 1].out_bits) : nullptr;
-      Exec::BnLink links[2];
-      int nlinks = 0;
-      if (bi > 0) {  // gprev feeds bn2 (and the downsample BN) of the previous block
-        const Block& pb = p->blocks[bi - 1];
-        const ConvL& pc2 = p->convs[pb.conv2];
-        const BnL& pb2 = p->bns[pc2.bn];
-        links[nlinks++] = {e.at(pc2.y), e.at<float>(pb2.mean), e.at<float>(pb2.invstd), e.at<float>(p->stats_bn2)};
-        if (pb.ds >= 0) {
-          const ConvL& pcd = p->convs[pb.ds];
-          const BnL& pbd = p->bns[pcd.bn];
-          links[nlinks++] = {e.at(pcd.y), e.at<float>(pbd.mean), e.at<float>(pbd.invstd), e.at<float>(p->stats_ds)};
-        }
-      }
-      rows_bn2 = e.dgrad(c1, gprev, resid, mask, links, nlinks, sparse_ds, mbits);
-      if (bi == 0) rows_bn2 = 0;
-    }
-    p->bwd_rows_bn2 = rows_bn2;
-    if (do_rest) {
-    // ---- stem ----
-    const ConvL& c0 = p->convs[0];
-    const BnL& bn0 = p->bns[c0.bn];
-    // max-pool backward + ReLU mask + bn1 backward without materialising d(loss)/d(relu output):
-    // the BatchNorm sums come from the pooled side (each pooled cell feeds exactly one conv1
-    // position: 2 x 103 MB read instead of a pass over two 411 MB maps), then one kernel gathers
-    // the <= 4 pooled cells of every conv1 position and writes d(loss)/d(conv1 output) directly.
-    // QTCNN_STEM_FUSED=0 keeps the three-pass form (pool backward, reduce, apply) for A/B runs.
-    static const bool fused = !(getenv("QTCNN_STEM_FUSED") && atoi(getenv("QTCNN_STEM_FUSED")) == 0);
-    bool stem_done = false;   // conv1's weight gradient has been produced by the one-launch stem backward
-    if (fused) {
-      const int rows = qt_stem_bn_bwd_sums_rows(B);
-      e.run(qt_stem_bn_bwd_sums(dt, e.at(p->g_p0), e.at(p->ymax), e.at<float>(bn0.scale), e.at<float>(bn0.shift),
-                                e.at<float>(bn0.mean), e.at<float>(bn0.invstd), e.at<float>(p->stats), B, stream));
-      e.run(qt_bn_bwd_finalize(e.at<float>(p->stats), rows, bn0.C, e.bn_count((long long)B * 112 * 112), e.tf(bn0.gamma),
-                               e.at<float>(bn0.invstd), e.gf(bn0.gamma), e.gf(bn0.beta), 0, e.at<float>(bn0.coef), stream));
-      // bf16: BatchNorm / ReLU / max-pool backward of conv1's output AND conv1's weight gradient in one launch on the
-      // weight-gradient stream (the map d(loss)/d(conv1 output) never exists); otherwise the apply pass, then wgrad below
-      if (e.gf(c0.w)) {
-        // Without an image gradient it runs on the CALLER's stream (its inputs, the two launches above, are there), so
-        // that the side stream is free for the optimizer's bulk (adam_step): the caller's stream first waits for the side
-        // stream's weight-gradient launches, which share wgrad_part, and the side stream is ordered behind the caller's
-        // stream HERE, before the stem launch is enqueued.  (A wait enqueued later, at the optimizer step, was measured to
-        // hold the side stream until the stem backward had finished, although the event had been recorded before it.)
-        const bool on_main = dt == QT_BF16 && !want_dx && e.wstream != stream;
-        if (on_main) {
-          e.forked = true;
-          e.join();
-          e.fork();
-        } else {
-          e.fork();
-        }
-        void* ws_ = on_main ? stream : e.wstream;
-        const int slot = e.begin_timed(e.conv_flops(e.stem_desc(true)), 2, ws_, e.wgrad_bytes(c0, e.stem_desc(true)));
-        // (deterministic form: partial filters in wgrad_part, which no launch on the other stream is using)
-        const int st = qt_stem_bn_bwd_wgrad_ws(dt, e.at(p->g_p0), e.at<unsigned char>(p->argmax), e.at(c0.y),
-                                               e.at<float>(bn0.scale), e.at<float>(bn0.shift), e.at<float>(bn0.mean),
-                                               e.at<float>(bn0.invstd), e.at<float>(bn0.coef), e.at(p->xpad),
-                                               e.at<float>(c0.dw), e.at(p->wgrad_part), p->wgrad_part_bytes, B, ws_);
-        e.end_timed(slot, ws_);
-        if (st == QT_OK) {
-          e.run(qt_unpack_stem_wgrad(e.at<float>(c0.dw), e.gf(c0.w), 0, ws_));
-          stem_done = true;
-          p->tail_ready = on_main && e.ok() && (phases & QT_BWD_ALL) == QT_BWD_ALL;
-        } else if (st != QT_ERR_UNSUPPORTED) {
-          e.run(st);
-        }
-      }
-      if (!stem_done || want_dx)   // (with the one-launch form on the side stream: the map for qt_stem_dgrad only)
-        e.run(qt_stem_bn_bwd_apply(dt, e.at(p->g_p0), e.at<unsigned char>(p->argmax), e.at(c0.y), e.at<float>(bn0.scale),
-                                   e.at<float>(bn0.shift), e.at<float>(bn0.mean), e.at<float>(bn0.invstd),
-                                   e.at<float>(bn0.coef), e.at(c0.gy), B, stream));
-    } else {
-      e.run(qt_stem_pool_bwd(dt, e.at(p->g_p0), e.at<unsigned char>(p->argmax), e.at(c0.y), e.at<float>(bn0.scale),
-                             e.at<float>(bn0.shift), e.at(c0.gy), B, stream));
-      e.bn_backward(c0, e.at(c0.gy), nullptr);
-    }
-    if (!stem_done) e.wgrad(c0, e.stem_desc(true), e.at(p->xpad), true);
-    // d(loss)/d(image) on the main stream, beside the stem's weight gradient on the side stream
-    if (want_dx) e.run(qt_stem_dgrad(dt, e.at(c0.gy), e.tf(c0.w), dimage, B, stream));
-    }
+  if ((phases & QT_BWD_BACKBONE) && e.walk) {
+    e.backward_blocks();
+    if (phases & QT_BWD_LAYER1) e.backward_stem();
   }
   // the last phase (or a head-only model) joins: afterwards the caller's stream sees every gradient
-  if ((phases & QT_BWD_LAYER1) || !walk) {
+  if ((phases & QT_BWD_LAYER1) || !e.walk) {
     e.forked = e.forked || (p->side != nullptr && e.wstream == p->side);
     e.join();
   }
@@ -1728,7 +1676,7 @@ extern "C" int qt_plan_create(const qt_plan_desc* desc, qt_plan** out) {
   qt_plan* p = new qt_plan();
   p->d = *desc;
   p->esz = desc->dtype == QT_F32 ? 4 : 2;
-  if (const char* v = getenv("QTCNN_SIDE_STREAM")) p->use_side = atoi(v) != 0;
+  p->use_side = qt_env_int("QTCNN_SIDE_STREAM", 1) != 0;   // (per plan: read at every qt_plan_create)
   build_graph(p);
   layout_workspace(p);
   *out = p;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/qtcnn.h"
 
@@ -16,6 +17,13 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 // thread-local last-error text (qt_last_error)
 void qt_set_error(const char* fmt, ...);
+
+// value of environment switch `name` (atoi), or `dflt` when unset; each call site caches it in a function-local static
+// (or in the global its qt_set_* setter writes) at first use, so a switch is read once per process
+static inline int qt_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 #define QT_CHECK_ARG(cond, ...)            \
   do {                                     \

@@ -558,10 +558,7 @@ extern "C" int qt_pack_conv3d_block(int dtype, const float* w, void* w_fwd, void
   const long long total = (first ? (long long)O_pad * 128 : (long long)O_pad * 27 * I_pad) + 5ll * O_pad;
   const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  static const bool tiled = [] {
-    const char* e = getenv("QTCNN_PACK3D_TILED");
-    return !(e && e[0] == '0');
-  }();
+  static const bool tiled = qt_env_int("QTCNN_PACK3D_TILED", 1) != 0;
   if (!first && tiled && O_pad % 64 == 0 && I_pad % 64 == 0 && I % PK3_TI == 0 && ((uintptr_t)w % 16) == 0) {
     const int blocks = (O_pad / PK3_TO) * (I_pad / PK3_TI) + 1;
     if (dtype == QT_F32)
@@ -697,10 +694,7 @@ extern "C" int qt_pool3d_bn_bwd_apply(int dtype, const void* dout, const unsigne
   QT_CHECK_ARG((pool_t == 1 || pool_t == 2) && frames >= pool_t, "qt_pool3d_bn_bwd_apply: pool_t=%d", pool_t);
   const long long n = (long long)frames * batch * h * w * (dy_channels / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  static const bool light = [] {
-    const char* e = getenv("QTCNN_POOL3D_APPLY_LIGHT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool light = qt_env_int("QTCNN_POOL3D_APPLY_LIGHT", 1) != 0;
   if (light && dtype == QT_BF16 && C == y_channels && C == dy_channels && 256 % (C / 8) == 0 && n >= g_pool3d_light_min.load()) {
     const dim3 lgrid(256 * 5), blk(256);   // (92 VGPRs: five waves per SIMD; a multiple of C / 8 threads: the channel group is loop invariant)
     if (pool_t == 1)
