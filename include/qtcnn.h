@@ -350,6 +350,8 @@ int qt_bn_act_mask(int dtype, const void* y, const float* scale, const float* sh
                    long long M, int C, void* stream);
 /* backward: g = d(loss)/d(BN output) (masked by `mask` > 0 if given).  qt_bn_bwd_finalize with count == 0 is the backward of
  * an eval-mode BatchNorm (running statistics in mean / invstd): dx = g*gamma*invstd without the batch-mean terms. */
+/* qt_bn_bwd_partial_rows: rows qt_bn_bwd_reduce writes, or QT_ERR_INVALID_ARG for the channel counts it refuses (C a multiple of 8,
+ * at most 2048, with C / 8 dividing 256) */
 int qt_bn_bwd_partial_rows(long long M, int C);
 int qt_bn_bwd_reduce(int dtype, const void* g, const void* mask, const void* y, const float* mean, const float* invstd,
                      float* partial, long long M, int C, void* stream);

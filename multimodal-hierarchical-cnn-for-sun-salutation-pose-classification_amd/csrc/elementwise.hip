@@ -966,7 +966,8 @@ static int bn_bwd_rows_per_block(long long M, int C) {
 }
 
 extern "C" int qt_bn_bwd_partial_rows(long long M, int C) {
-  if (M <= 0 || C <= 0 || C % 8 || C > 2048) return QT_ERR_INVALID_ARG;
+  // (the same channel counts as qt_bn_bwd_reduce: its 256 threads are whole rows of C / 8 channel groups)
+  if (M <= 0 || C <= 0 || C % 8 || C > 2048 || 256 % (C / 8)) return QT_ERR_INVALID_ARG;
   return qt_cdiv(M, bn_bwd_rows_per_block(M, C));
 }
 
