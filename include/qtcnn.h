@@ -610,6 +610,16 @@ int qt_conv3d_first_wgrad_fused(int dtype, const float* clips, const void* y, co
                                 int batch, int frames, int h, int w, void* stream);
 int qt_conv3d_first_fwd(int dtype, const float* clips, const void* w_packed, void* y, const float* scale, const float* shift,
                         int relu, float* stats, int batch, int frames, int h, int w, void* stream);
+/* ... and its data gradient down to the clip (`image_sequence.grad`): dclips [B][T][3][H][W] f32, the clip's own layout,
+ * every element WRITTEN exactly once (no zero fill by the caller, no atomics, the same bits on every run) =
+ * conv_transpose3d(dy, w, padding 1) from dy = d(loss)/d(conv output) [T][B][H][W][32] in `dtype` (bf16 or f32; 32-channel
+ * rows, what qt_pool3d_bn_bwd_apply writes with dy_channels = 32) and the f32 master filter [32][3][3][3][3] in nn.Conv3d's
+ * layout.  bf16 dy in the shapes qt_conv3d_first_fwd takes (H % 4 == 0, W % 16 == 0, W <= 256, 16-byte aligned dy): bf16 MFMA
+ * with f32 accumulation, each dy frame slab staged in LDS once for the three frames it reaches; every other shape and f32
+ * dy: a direct f32 kernel, one thread per pixel.  bf16 dy is multiplied by the filter rounded to bf16, the rounding
+ * qt_pack_conv3d_block applies for the forward.  QT_ERR_UNSUPPORTED only for another dtype. */
+int qt_conv3d_first_dgrad(int dtype, const void* dy, const float* w_oidhw, float* dclips, int batch, int frames, int h, int w,
+                          void* stream);
 /* nn.AdaptiveAvgPool3d((1,1,1)) + flatten(1) into columns [col0, col0+C) of an f32 [B][ld] matrix, and its backward */
 int qt_avgpool_tb(int dtype, const void* x, float* dst, int frames, int batch, int hw, int C, int ld, int col0, void* stream);
 int qt_avgpool_tb_bwd(int dtype, const float* d, void* g, int frames, int batch, int hw, int C, int ld, int col0,

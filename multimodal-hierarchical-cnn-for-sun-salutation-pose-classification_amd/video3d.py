@@ -235,12 +235,24 @@ class _Ops:
                    "qt_bn_bwd_finalize")
         if not apply:
             return coef, dgb[0], dgb[1]
+        return self.pool_bn_apply(dt, dout, arg, pooled, y, stats, coef, T, B, H, W, C, pt, dev, cy, cd), dgb[0], dgb[1]
+
+    def pool_bn_apply(self, dt, dout, arg, pooled, y, stats, coef, T, B, H, W, C, pt, dev, cy=None, cd=None):
+        """dy [T*B*H*W][cd] from pool_bn_backward's coefficients: max-pool backward + ReLU mask + BatchNorm backward in one pass"""
         cy, cd = cy or C, cd or cy or C
-        dy = torch.empty(Mrows, cd, dtype=dt, device=dev)
-        self.check(self.L.qt_pool3d_bn_bwd_apply(q, _ptr(dout), _ptr(arg), _ptr(pooled), _ptr(y), _ptr(stats[0]), _ptr(stats[1]),
-                                                 _ptr(coef), _ptr(dy), T, B, H, W, C, cy, cd, pt, _lib.stream_ptr()),
-                   "qt_pool3d_bn_bwd_apply")
-        return dy, dgb[0], dgb[1]
+        dy = torch.empty(T * B * H * W, cd, dtype=dt, device=dev)
+        self.check(self.L.qt_pool3d_bn_bwd_apply(_lib.qt_dtype(dt), _ptr(dout), _ptr(arg), _ptr(pooled), _ptr(y), _ptr(stats[0]),
+                                                 _ptr(stats[1]), _ptr(coef), _ptr(dy), T, B, H, W, C, cy, cd, pt,
+                                                 _lib.stream_ptr()), "qt_pool3d_bn_bwd_apply")
+        return dy
+
+    def conv3d_first_dgrad(self, dt, dy, w, B, T, H, W):
+        """d(loss)/d(clip) [B][T][3][H][W] f32 from conv3d_block1's dy [T*B*H*W][32] and its f32 master filter
+        (csrc/conv3d_first_dgrad.hip); every element is written by the kernel"""
+        dx = torch.empty(B, T, 3, H, W, dtype=torch.float32, device=dy.device)
+        self.check(self.L.qt_conv3d_first_dgrad(_lib.qt_dtype(dt), _ptr(dy), _ptr(w), _ptr(dx), B, T, H, W, _lib.stream_ptr()),
+                   "qt_conv3d_first_dgrad")
+        return dx
 
     def pool_bwd(self, dt, dout, arg, dx, T, B, H, W, C, pt):
         self.check(self.L.qt_pool3d_max_bwd(_lib.qt_dtype(dt), _ptr(dout), _ptr(arg), _ptr(dx), T, B, H, W, C, pt,
@@ -531,9 +543,10 @@ class _ConvBlock:
         hi = min(T, T + 1 - kt)
         return lo, lo + kt - 1, max(0, hi - lo)
 
-    def backward(self, dt, dout, saved, wside=None):
+    def backward(self, dt, dout, saved, wside=None, want_dx=False):
         """dout: d/d(block output) -> (dx or None, dW, db, dgamma, dbeta).  wside: a _Side whose stream takes the weight
-        gradient (the caller joins it before dW is used)"""
+        gradient (the caller joins it before dW is used).  want_dx (first block only): dx = d/d(clip), f32 [B][T][3][H][W];
+        the weight-gradient path does not change with it (the same launches on the same operands)"""
         o = ops()
         x, y, a, arg, stats, (T, B, H, W), training, pooled, ymax = saved
         dev = x.device
@@ -630,6 +643,16 @@ class _ConvBlock:
         else:
             dW = weight_gradient()
         dx = None
+        if self.first and want_dx:
+            # the clip gradient (csrc/conv3d_first_dgrad.hip) reads dy in 32-channel rows.  Where the weight gradient formed dy
+            # inside its own kernel it is written out here from the same coefficients; rows padded to 64 channels (the packed
+            # first layer: f32 build, shapes the raw kernels do not take) are narrowed
+            if coef is not None:
+                dy32 = o.pool_bn_apply(dt, dout, arg, pooled, y, stats, coef, T, B, H, W, pooled.shape[1], self.pool_t, dev,
+                                       cy=32, cd=32)
+            else:
+                dy32 = dy if dy.shape[1] == 32 else dy[:, :32].contiguous()
+            dx = o.conv3d_first_dgrad(dt, dy32, self.conv.weight.detach(), B, T, H, W)
         if not self.first:   # data gradient: one 27-tap launch; conv3d_block2's on the slab-resident kernel (two passes)
             dx = torch.empty(rows, x.shape[1], dtype=dt, device=dev)   # (rows as wide as the input's: the previous block's pooled map)
             nscr = 0
@@ -740,14 +763,29 @@ class _ClipModel(nn.Module):
 
     def _check_hooks(self):
         """The whole forward / backward is one autograd node that never calls the leaf modules: a hook registered on a
-        submodule (the reference's Grad-CAM API targets `conv3d_final_features`, 3dcnn/models.py:181-182) would silently
-        never fire.  Same policy as the 2-D models (quadtree.py::_check_hooks): raise instead of staying dead."""
+        submodule would silently never fire.  Same policy as the 2-D models (quadtree.py::_check_hooks): the one module the
+        reference's Grad-CAM API targets (`conv3d_final_features`, 3dcnn/models.py:178-182) is served from the saved
+        tensors, every other submodule hook raises instead of staying dead."""
+        served = self._hooked_module()
         for name, mod in self.named_modules():
             if mod is self:
                 continue
+            if mod is served:   # a forward hook and a full backward hook are served from the saved tensors
+                if not (mod._forward_pre_hooks or mod._backward_pre_hooks):
+                    continue
             if mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks:
                 raise QtError(f"hook registered on submodule {name!r}: the clip models run as one fused autograd node and "
-                              "serve no submodule hooks (hooks on the model itself work); they would never fire")
+                              "serve only a forward hook and a full backward hook on Quadtree3DCNN.conv3d_final_features "
+                              "(the Grad-CAM recipe) and hooks on the model itself; this one would never fire")
+
+    def _hooked_module(self):
+        """the submodule whose forward / full backward hooks are served (None: no submodule hooks)"""
+        return None
+
+    @staticmethod
+    def _ncthw(x, B, t, h, w, C):
+        """time-major rows [t*B*h*w][>= C] in the compute dtype -> f32 [B][C][t][h][w], padding channels stripped"""
+        return x.view(t, B, h, w, x.shape[1])[..., :C].permute(1, 4, 0, 2, 3).float().contiguous()
 
     def _cached_blocks(self, specs):
         """the conv blocks' executors (packed filter buffers) live as long as their modules do"""
@@ -784,7 +822,8 @@ class _ClipFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, owner, images, numerical, *params):
         # (grad mode is off inside Function.forward; `needs_input_grad` tells whether a backward may follow)
-        keep = owner._grad_mode and any(ctx.needs_input_grad[3:])
+        # (... or the clip does: d(logits)/d(clip) runs the same backward)
+        keep = owner._grad_mode and (ctx.needs_input_grad[1] or any(ctx.needs_input_grad[3:]))
         with torch.cuda.device(images.device):
             logits = owner._forward_impl(images, numerical, keep)
         ctx.owner = owner
@@ -798,8 +837,10 @@ class _ClipFunction(torch.autograd.Function):
             raise QtError("backward() after a later forward() on the same model: one set of activations is kept")
         with torch.cuda.device(dlogits.device):
             sync = getattr(owner, "_grad_sync", None)
+            want_dx = bool(ctx.needs_input_grad[1])   # the clip gradient: f32 [B,T,3,H,W], the layout the user passed
             if sync is None:
-                return (None, None, None, *owner._backward_impl(dlogits.contiguous().float()))
+                grads = owner._backward_impl(dlogits.contiguous().float(), want_dx=want_dx)
+                return (None, owner.__dict__.pop("_dclip", None), None, *grads)
             # Data parallelism (dp.attach_data_parallel).  There is no plan behind the clip models, but their backward still
             # finishes its gradients in a known order: the dense head first, then the conv blocks from the last to the first.
             # _backward_impl hands them over in buckets as they become final (emit): each bucket is packed into one flat f32
@@ -817,7 +858,7 @@ class _ClipFunction(torch.autograd.Function):
                 sync(flat, phase)
                 buckets.append((live, flat))
 
-            grads = owner._backward_impl(dlogits.contiguous().float(), emit)
+            grads = owner._backward_impl(dlogits.contiguous().float(), emit, want_dx)
             sync(None, 0)   # join: the compute stream sees the averaged buckets
             by_name = {}
             for live, flat in buckets:
@@ -830,7 +871,7 @@ class _ClipFunction(torch.autograd.Function):
             if missing:
                 raise QtError(f"data parallelism: gradients of {missing} were produced but never handed over in a bucket")
             grads = [None if g0 is None else by_name[n] for n, g0 in zip(names, grads)]
-        return (None, None, None, *grads)
+        return (None, owner.__dict__.pop("_dclip", None), None, *grads)
 
 
 class _Head:
@@ -923,6 +964,9 @@ class Quadtree3DCNN(_ClipModel):
     def save_activation_hook(self, module, input, output):
         self.activations = output
 
+    def _hooked_module(self):
+        return self.conv3d_final_features
+
     def _conv_blocks(self):
         seqs = (self.conv3d_block1, self.conv3d_block2, self.conv3d_block3, self.conv3d_block4_new, self.conv3d_final_features)
         pools = (1, 2, 2, 1, 0)
@@ -960,8 +1004,17 @@ class Quadtree3DCNN(_ClipModel):
         t, h, w = T, H, W
         for blk in blocks:
             blk.pack(dt, keep, self.__dict__.get("_bwd_count", 0))
+            x_in = x
             x, (t, h, w), sv = blk.forward(dt, x, t, B, h, w, training, keep)
             saved_blocks.append(sv)
+        final = self.conv3d_final_features
+        if final._forward_hooks:
+            # Grad-CAM (3dcnn/models.py:178-182): the module never runs, its forward hooks get the tensors torch would have
+            # passed -- block 4's output and the block's post-BatchNorm / ReLU output as f32 [B,C,t,h,w] (no pool: same t, h, w)
+            inp = self._ncthw(x_in, B, t, h, w, blocks[-1].cin)
+            out = self._ncthw(x, B, t, h, w, self.cnn_3d_feature_dim)
+            for hook in list(final._forward_hooks.values()):
+                hook(final, (inp,), out)
         F_img = self.cnn_3d_feature_dim
         ld = self.final_classifier_input_dim
         fused = torch.empty(B, ld, dtype=torch.float32, device=dev)
@@ -985,8 +1038,9 @@ class Quadtree3DCNN(_ClipModel):
         self._saved = (blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, last, p) if keep else None
         return logits
 
-    def _backward_impl(self, dlogits, emit=None):
-        """emit(g, names, phase): data-parallel hand-over of the gradients `names` of dict g, final as of this point"""
+    def _backward_impl(self, dlogits, emit=None, want_dx=False):
+        """emit(g, names, phase): data-parallel hand-over of the gradients `names` of dict g, final as of this point.
+        want_dx: the clip gradient is left in self._dclip"""
         self.__dict__["_bwd_count"] = self.__dict__.get("_bwd_count", 0) + 1   # gradients exist: packed weights may go stale
         o, dt = ops(), self.compute_dtype
         blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, last, p = self._saved
@@ -1019,6 +1073,12 @@ class Quadtree3DCNN(_ClipModel):
                     g[f"numerical_lstm.{nm}_l{k}"] = lg[4 * k + j]
         else:
             side = None
+        final = self.conv3d_final_features
+        if final._backward_hooks:
+            # its output only feeds the global average pool: d(loss)/d(output) is dfused[:, :F] / (t h w) at every position
+            gout = (dfused[:, :F_img] / float(t * h * w)).view(B, F_img, 1, 1, 1).expand(B, F_img, t, h, w).contiguous()
+            for hook in list(final._backward_hooks.values()):
+                hook(final, (None,), (gout,))
         if emit is not None:   # bucket 1: the dense head (the LSTM's gradients are still running on the side stream)
             emit(g, [k for k in g if k.startswith(("classifier.", "numerical_projection."))], 1)
         # image branch
@@ -1029,7 +1089,7 @@ class Quadtree3DCNN(_ClipModel):
         names = ("conv3d_block1", "conv3d_block2", "conv3d_block3", "conv3d_block4_new", "conv3d_final_features")
         wside = _Side(dev, 1) if WGRAD_SIDE else None
         for blk, sv, nm in zip(reversed(blocks), reversed(saved_blocks), reversed(names)):
-            dout, dW, db, dgamma, dbeta = blk.backward(dt, dout, sv, wside)
+            dout, dW, db, dgamma, dbeta = blk.backward(dt, dout, sv, wside, want_dx and blk.first)
             g[f"{nm}.0.weight"], g[f"{nm}.0.bias"], g[f"{nm}.1.weight"], g[f"{nm}.1.bias"] = dW, db, dgamma, dbeta
             if emit is not None and nm == "conv3d_final_features":   # bucket 2: 7.1 M of the 9.9 M parameters, ready first
                 if wside is not None:
@@ -1042,6 +1102,7 @@ class Quadtree3DCNN(_ClipModel):
         if emit is not None:   # bucket 3: conv blocks 4 .. 1 and the LSTM (joined above)
             emit(g, [k for k in g if k.startswith(("conv3d_block", "numerical_lstm."))], 4)
         self._saved = None
+        self.__dict__["_dclip"] = dout if want_dx else None   # (the first block's data gradient)
         return [g.get(n) for n, _ in self.named_parameters()]
 
 
@@ -1105,7 +1166,7 @@ class Ji3DCNN(_ClipModel):
         self._saved = (blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, p) if keep else None
         return logits
 
-    def _backward_impl(self, dlogits, emit=None):
+    def _backward_impl(self, dlogits, emit=None, want_dx=False):
         self.__dict__["_bwd_count"] = self.__dict__.get("_bwd_count", 0) + 1   # gradients exist: packed weights may go stale
         o, dt = ops(), self.compute_dtype
         blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, p = self._saved
@@ -1131,11 +1192,12 @@ class Ji3DCNN(_ClipModel):
                 "qt_avgpool_tb_bwd")
         wside = _Side(dev, 1) if WGRAD_SIDE else None
         for blk, sv, nm in zip(reversed(blocks), reversed(saved_blocks), ("visual_stream.4", "visual_stream.2", "visual_stream.0")):
-            dout, dW, db, dgamma, dbeta = blk.backward(dt, dout, sv, wside)
+            dout, dW, db, dgamma, dbeta = blk.backward(dt, dout, sv, wside, want_dx and blk.first)
             g[f"{nm}.0.weight"], g[f"{nm}.0.bias"], g[f"{nm}.1.weight"], g[f"{nm}.1.bias"] = dW, db, dgamma, dbeta
         if wside is not None:
             wside.join(*[g[f"{nm}.0.weight"] for nm in ("visual_stream.4", "visual_stream.2", "visual_stream.0")])
         if emit is not None:   # bucket 2: the three conv blocks (0.3 M parameters)
             emit(g, [k for k in g if k.startswith("visual_stream.")], 2)
         self._saved = None
+        self.__dict__["_dclip"] = dout if want_dx else None   # (the first block's data gradient)
         return [g.get(n) for n, _ in self.named_parameters()]
