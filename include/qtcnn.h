@@ -296,6 +296,26 @@ typedef struct qt_adam_item {
 int qt_adam_multi(const qt_adam_item* items, int n, const qt_adam_desc* adam, void* stream);
 int qt_adam_pack_weights_batched(int dtype, const qt_pack_item* items, const qt_adam_item* opt, const qt_adam_desc* adam,
                                  int n, void* stream);
+/* The same two calls with a second gradient factor that lives in DEVICE memory: the effective scale is
+ * grad_scale * (*grad_scale_dev), applied where grad_scale is applied (one f32, 4-byte aligned, read by the kernel when
+ * it runs, so a kernel earlier on the stream may produce it: qt_grad_norm_multi's clip_coef).  NULL: exactly
+ * qt_adam_multi / qt_adam_pack_weights_batched, bit for bit. */
+int qt_adam_multi_scaled(const qt_adam_item* items, int n, const qt_adam_desc* adam, const float* grad_scale_dev,
+                         void* stream);
+int qt_adam_pack_weights_batched_scaled(int dtype, const qt_pack_item* items, const qt_adam_item* opt,
+                                        const qt_adam_desc* adam, const float* grad_scale_dev, int n, void* stream);
+/* Global 2-norm of a list of f32 tensors and the clip coefficient of torch.nn.utils.clip_grad_norm_, without a host
+ * round trip.  Of every item only `grad` (4-byte aligned, any numel >= 1) and `numel` are read.  Two deterministic
+ * stages (fixed chunks, fixed summation order, no atomics): one sum of squares per 8192-element chunk into `workspace`
+ * (at least qt_grad_norm_workspace_bytes of device memory; every slot used is written, nothing needs zeroing), then
+ *   out2[0] = total_norm = sqrt(sum)
+ *   out2[1] = clip_coef  = min(1, max_norm * (1 / (total_norm + 1e-6)))       all f32, torch's own evaluation order
+ * in device memory.  A non-finite norm gives what torch gives (inf -> 0, NaN -> NaN).  One launch per 48 tensors plus
+ * one.  max_norm <= 0 or NaN: QT_ERR_INVALID_ARG.  The workspace size depends on the pointers' alignment as well as on
+ * the element counts: ask for it with the list that is passed (returns 0 and sets the error text for a bad list). */
+size_t qt_grad_norm_workspace_bytes(const qt_adam_item* items, int n);
+int qt_grad_norm_multi(const qt_adam_item* items, int n, float max_norm, void* workspace, size_t workspace_bytes,
+                       float* out2, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of
@@ -738,6 +758,16 @@ int qt_plan_adam_step(qt_plan* plan, void* workspace, void* const* tensors, floa
 int qt_plan_adam_step_overlapped(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads,
                                  float* const* exp_avg, float* const* exp_avg_sq, const qt_adam_desc* adam, int for_backward,
                                  void* stream, int* overlapped);
+/* qt_plan_adam_step with global-norm gradient clipping, all on `stream`: qt_grad_norm_multi over every non-NULL
+ * gradient of the plan plus the n_extra gradients of `extra` (tensors outside the plan that share the norm; may be
+ * NULL / 0), then the fused step with the gradients scaled by out2[1] as they are read.  The gradients themselves are
+ * not written.  `extra` is not updated here: step it with qt_adam_multi_scaled(..., out2 + 1, stream) afterwards.
+ * norm_workspace: the size qt_grad_norm_workspace_bytes gives for the same set of gradients (any order).
+ * out2: {total_norm, clip_coef} in device memory, as for qt_grad_norm_multi. */
+int qt_plan_adam_step_clipped(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads,
+                              float* const* exp_avg, float* const* exp_avg_sq, const qt_adam_desc* adam, int for_backward,
+                              float max_norm, const qt_adam_item* extra, int n_extra, void* norm_workspace,
+                              size_t norm_workspace_bytes, float* out2, void* stream);
 int qt_plan_forward(qt_plan* plan, void* workspace, void* const* tensors, const float* image, const float* numerical,
                     float* logits, int batch, int training, unsigned long long seed, void* stream);
 int qt_plan_backward(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads, const float* numerical,

@@ -78,7 +78,13 @@ struct AdamScalars {
   float inv_sqrt_bc2;  // 1 / sqrt(1 - b2^t)
   float grad_scale;    // multiplies the incoming gradient (1 = none)
   int enabled;
+  const float* grad_scale_dev;  // optional second factor read from device memory (qt_grad_norm_multi's clip_coef)
 };
+// the scalars with the device factor folded into grad_scale; a null pointer leaves them as they are
+__device__ __forceinline__ AdamScalars adam_with_device_scale(AdamScalars h) {
+  if (h.grad_scale_dev) h.grad_scale *= *h.grad_scale_dev;
+  return h;
+}
 // Every rounding is spelled out, so that the scalar and the float4 callers, and any compiler version, produce the same
 // bits: four fused multiply-adds, and the second moment as two rounded products and a rounded sum.
 __device__ __forceinline__ float adam_update(float p, float g, float& m, float& v, const AdamScalars& h) {
@@ -207,14 +213,15 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(PackBatchArgs
   const int b = blockIdx.x - a.first_block[it];
   T* fwd = static_cast<T*>(a.fwd[it]);
   T* dg = static_cast<T*>(a.dgrad[it]);
+  const AdamScalars adam = adam_with_device_scale(a.adam);
   if (a.k[it] == 1) {
     const int tiles_i = I / PK_T1;
-    pack_tile<T, 1, PK_T1, PK_T1>(tile, a.w[it], fwd, dg, O, I, (b / tiles_i) * PK_T1, (b % tiles_i) * PK_T1, (int)a.s2[it], a.adam,
+    pack_tile<T, 1, PK_T1, PK_T1>(tile, a.w[it], fwd, dg, O, I, (b / tiles_i) * PK_T1, (b % tiles_i) * PK_T1, (int)a.s2[it], adam,
                                   a.g[it], a.m[it], a.v[it]);
   } else {
     const int tiles_i = I / PK_T3I;
     pack_tile<T, 9, PK_T3O, PK_T3I>(tile, a.w[it], fwd, dg, O, I, (b / tiles_i) * PK_T3O, (b % tiles_i) * PK_T3I, (int)a.s2[it],
-                                    a.adam, a.g[it], a.m[it], a.v[it]);
+                                    adam, a.g[it], a.m[it], a.v[it]);
   }
 }
 
@@ -240,12 +247,13 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatchArgs a) {
   const float* __restrict__ g = a.g[it];
   float* __restrict__ m = a.m[it];
   float* __restrict__ v = a.v[it];
+  const AdamScalars adam = adam_with_device_scale(a.adam);
 #pragma unroll 4
   for (int k = 0; k < AD_CHUNK / 256; ++k) {
     const long long i = base + k * 256 + threadIdx.x;
     if (i < n) {
       float mv = m[i], vv = v[i];
-      p[i] = adam_update(p[i], g[i], mv, vv, a.adam);
+      p[i] = adam_update(p[i], g[i], mv, vv, adam);
       m[i] = mv;
       v[i] = vv;
     }
@@ -375,26 +383,41 @@ static int make_adam_scalars(const qt_adam_desc* d, AdamScalars* h) {
   h->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   h->grad_scale = d->grad_scale == 0.f ? 1.f : d->grad_scale;
   h->enabled = 1;
+  h->grad_scale_dev = nullptr;
   return QT_OK;
 }
 
-static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item* opt, const qt_adam_desc* adam, int n,
-                        void* stream);
+static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item* opt, const qt_adam_desc* adam,
+                        const float* grad_scale_dev, int n, void* stream);
 
 extern "C" int qt_pack_weights_batched(int dtype, const qt_pack_item* items, int n, void* stream) {
-  return pack_batched(dtype, items, nullptr, nullptr, n, stream);
+  return pack_batched(dtype, items, nullptr, nullptr, nullptr, n, stream);
 }
 
 extern "C" int qt_adam_pack_weights_batched(int dtype, const qt_pack_item* items, const qt_adam_item* opt,
                                             const qt_adam_desc* adam, int n, void* stream) {
   QT_CHECK_ARG(opt && adam, "qt_adam_pack_weights_batched: null optimizer state");
-  return pack_batched(dtype, items, opt, adam, n, stream);
+  return pack_batched(dtype, items, opt, adam, nullptr, n, stream);
+}
+
+extern "C" int qt_adam_pack_weights_batched_scaled(int dtype, const qt_pack_item* items, const qt_adam_item* opt,
+                                                   const qt_adam_desc* adam, const float* grad_scale_dev, int n,
+                                                   void* stream) {
+  QT_CHECK_ARG(opt && adam, "qt_adam_pack_weights_batched_scaled: null optimizer state");
+  return pack_batched(dtype, items, opt, adam, grad_scale_dev, n, stream);
 }
 
 extern "C" int qt_adam_multi(const qt_adam_item* items, int n, const qt_adam_desc* adam, void* stream) {
+  return qt_adam_multi_scaled(items, n, adam, nullptr, stream);
+}
+
+extern "C" int qt_adam_multi_scaled(const qt_adam_item* items, int n, const qt_adam_desc* adam, const float* grad_scale_dev,
+                                    void* stream) {
   QT_CHECK_ARG(items && n > 0, "qt_adam_multi: no tensors");
+  QT_CHECK_ARG((reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) == 0, "qt_adam_multi_scaled: misaligned grad_scale_dev");
   AdamScalars h;
   if (int st = make_adam_scalars(adam, &h)) return st;
+  h.grad_scale_dev = grad_scale_dev;
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int j0 = 0; j0 < n; j0 += AD_MAX_ITEMS) {
     AdamBatchArgs a;
@@ -417,14 +440,16 @@ extern "C" int qt_adam_multi(const qt_adam_item* items, int n, const qt_adam_des
   return QT_OK;
 }
 
-static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item* opt, const qt_adam_desc* adam, int n,
-                        void* stream) {
+static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item* opt, const qt_adam_desc* adam,
+                        const float* grad_scale_dev, int n, void* stream) {
   QT_CHECK_ARG(items && n > 0 && n <= PK_MAX_ITEMS, "qt_pack_weights_batched: 1..%d items", PK_MAX_ITEMS);
   QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_weights_batched: bad dtype %d", dtype);
   PackBatchArgs a;
   memset(&a, 0, sizeof(a));
   if (opt) {
     if (int st = make_adam_scalars(adam, &a.adam)) return st;
+    QT_CHECK_ARG((reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) == 0, "qt_adam_pack_weights_batched_scaled: misaligned grad_scale_dev");
+    a.adam.grad_scale_dev = grad_scale_dev;
   }
   int blocks = 0;
   for (int j = 0; j < n; ++j) {

@@ -874,7 +874,8 @@ int pack_weights(qt_plan* p, void* workspace, void* const* T, int for_backward, 
 // linear weights that have packed copies are updated INSIDE the packing kernel, everything else by the
 // plain multi-tensor kernel; tensors without a gradient are only re-packed.
 int adam_step(qt_plan* p, void* workspace, void* const* T, float* const* G, float* const* M1, float* const* M2,
-              const qt_adam_desc* adam, int for_backward, void* stream, bool overlap, int* overlapped) {
+              const qt_adam_desc* adam, int for_backward, void* stream, bool overlap, int* overlapped,
+              const float* grad_scale_dev = nullptr) {
   Exec e{p, static_cast<unsigned char*>(workspace), T, stream, p->d.batch, p->d.dtype};
   // Overlapped form (qt_plan_adam_step_overlapped right after a full backward): the bulk -- the batched Adam + re-pack and
   // the plain tensors -- goes to the side stream, which the backward ordered behind everything but the fused stem backward,
@@ -916,13 +917,14 @@ int adam_step(qt_plan* p, void* workspace, void* const* T, float* const* G, floa
     u.param = e.tf((int)i); u.grad = G[i]; u.exp_avg = M1[i]; u.exp_avg_sq = M2[i]; u.numel = numel_of((int)i);
     (ov && (int)i == p->convs[0].w ? stem_w : plain).push_back(u);
   }
-  if (!plain.empty() && e.ok()) e.run(qt_adam_multi(plain.data(), (int)plain.size(), adam, bulk));
-  if (!stem_w.empty() && e.ok()) e.run(qt_adam_multi(stem_w.data(), 1, adam, stream));
+  if (!plain.empty() && e.ok()) e.run(qt_adam_multi_scaled(plain.data(), (int)plain.size(), adam, grad_scale_dev, bulk));
+  if (!stem_w.empty() && e.ok()) e.run(qt_adam_multi_scaled(stem_w.data(), 1, adam, grad_scale_dev, stream));
   if (p->has_image)  // conv1's filter was updated by a plain kernel above
     e.run(qt_pack_stem_weight(e.dt, e.tf(p->convs[0].w), e.at(p->convs[0].w_fwd), e.stem_taps(), stream));
   for (size_t j = 0; j < upd_items.size() && e.ok(); j += 32) {
     const int cnt = (int)std::min<size_t>(32, upd_items.size() - j);
-    e.run(qt_adam_pack_weights_batched(e.dt, upd_items.data() + j, upd_state.data() + j, adam, cnt, bulk));
+    e.run(qt_adam_pack_weights_batched_scaled(e.dt, upd_items.data() + j, upd_state.data() + j, adam, grad_scale_dev, cnt,
+                                              bulk));
   }
   // weights without a gradient did not change: their copies are re-packed only if they are not known to be current
   const unsigned long long sig = weight_sig(p, T);
@@ -1825,6 +1827,28 @@ extern "C" int qt_plan_adam_step(qt_plan* p, void* workspace, void* const* tenso
                                  void* stream) {
   QT_CHECK_ARG(p && workspace && tensors && grads && exp_avg && exp_avg_sq && adam, "qt_plan_adam_step: null argument");
   return adam_step(p, workspace, tensors, grads, exp_avg, exp_avg_sq, adam, for_backward, stream, false, nullptr);
+}
+
+extern "C" int qt_plan_adam_step_clipped(qt_plan* p, void* workspace, void* const* tensors, float* const* grads,
+                                         float* const* exp_avg, float* const* exp_avg_sq, const qt_adam_desc* adam,
+                                         int for_backward, float max_norm, const qt_adam_item* extra, int n_extra,
+                                         void* norm_workspace, size_t norm_workspace_bytes, float* out2, void* stream) {
+  QT_CHECK_ARG(p && workspace && tensors && grads && exp_avg && exp_avg_sq && adam, "qt_plan_adam_step_clipped: null argument");
+  QT_CHECK_ARG(n_extra >= 0 && (extra || n_extra == 0), "qt_plan_adam_step_clipped: n_extra = %d without a list", n_extra);
+  // the norm needs conv1's weight gradient, the last thing a backward produces: the whole step is serial on `stream`
+  std::vector<qt_adam_item> all;
+  for (size_t i = 0; i < p->tensors.size(); ++i) {
+    if (p->tensors[i].kind != 0 || !grads[i]) continue;
+    qt_adam_item u;
+    u.param = nullptr; u.grad = grads[i]; u.exp_avg = nullptr; u.exp_avg_sq = nullptr; u.numel = 1;
+    for (int d = 0; d < p->tensors[i].ndim; ++d) u.numel *= p->tensors[i].shape[d];
+    all.push_back(u);
+  }
+  all.insert(all.end(), extra, extra + n_extra);
+  QT_CHECK_ARG(!all.empty(), "qt_plan_adam_step_clipped: no gradients");
+  if (int st = qt_grad_norm_multi(all.data(), (int)all.size(), max_norm, norm_workspace, norm_workspace_bytes, out2, stream))
+    return st;
+  return adam_step(p, workspace, tensors, grads, exp_avg, exp_avg_sq, adam, for_backward, stream, false, nullptr, out2 + 1);
 }
 
 extern "C" int qt_plan_adam_step_overlapped(qt_plan* p, void* workspace, void* const* tensors, float* const* grads,

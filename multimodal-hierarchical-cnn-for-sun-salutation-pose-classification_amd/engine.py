@@ -73,6 +73,16 @@ def _bind_api(L):
     L.qt_plan_adam_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.POINTER(AdamDesc), ctypes.c_int, ctypes.c_void_p]
     L.qt_plan_adam_step_overlapped.argtypes = L.qt_plan_adam_step.argtypes + [ctypes.POINTER(ctypes.c_int)]
+    L.qt_plan_adam_step_clipped.argtypes = L.qt_plan_adam_step.argtypes[:-1] + [
+        ctypes.c_float, ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+        ctypes.c_void_p]
+    L.qt_adam_multi.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.POINTER(AdamDesc), ctypes.c_void_p]
+    L.qt_adam_multi_scaled.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.POINTER(AdamDesc), ctypes.c_void_p,
+                                       ctypes.c_void_p]
+    L.qt_grad_norm_workspace_bytes.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int]
+    L.qt_grad_norm_workspace_bytes.restype = ctypes.c_size_t
+    L.qt_grad_norm_multi.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
+                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     L.qt_plan_find_buffer.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t)]
     L._plan_bound = True
 
@@ -199,12 +209,15 @@ class PlanEngine:
             return False
         return all(by_index[idx][0].data_ptr() == ptr for idx, ptr in ptrs.items())
 
-    def adam_step(self, by_index, desc, overlap=False):
+    def adam_step(self, by_index, desc, overlap=False, clip=None):
         """Fused optimizer step + operand re-packing (qt_plan_adam_step).  by_index: plan tensor
         index -> (grad, exp_avg, exp_avg_sq) f32 tensors on this device; the parameters themselves
         are the tensors bound by the last forward.  overlap: the caller allows the bulk of the step on the plan's side
-        stream (qt_plan_adam_step_overlapped); it is used only if adam_overlap_ok(by_index) holds as well."""
-        overlap = bool(overlap) and self.adam_overlap_ok(by_index)
+        stream (qt_plan_adam_step_overlapped); it is used only if adam_overlap_ok(by_index) holds as well.
+        clip: None, or (max_norm, extra AdamItem array or None, its length, workspace tensor, out2 tensor) for
+        qt_plan_adam_step_clipped: the norm covers by_index's gradients and the extra ones, the whole step is serial on
+        the caller's stream (the norm needs conv1's weight gradient, the last thing the backward produces)."""
+        overlap = clip is None and bool(overlap) and self.adam_overlap_ok(by_index)
         self._handed_out = None
         n = len(self.names)
         g, m, v = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
@@ -214,7 +227,13 @@ class PlanEngine:
                     raise QtError(f"{self.names[idx]}: gradient / Adam state must be contiguous f32 on {self.device}")
             g[idx], m[idx], v[idx] = gt.data_ptr(), mt.data_ptr(), vt.data_ptr()
         took = ctypes.c_int(0)
-        if overlap:
+        if clip is not None:
+            max_norm, extra, n_extra, ws, out2 = clip
+            _lib.check(self.L.qt_plan_adam_step_clipped(self.handle, self.ws_ptr, self._tensor_ptrs, g, m, v,
+                                                        ctypes.byref(desc), 1, max_norm, extra, n_extra, ws.data_ptr(),
+                                                        ws.numel() * ws.element_size(), out2.data_ptr(),
+                                                        _lib.stream_ptr()), "qt_plan_adam_step_clipped")
+        elif overlap:
             _lib.check(self.L.qt_plan_adam_step_overlapped(self.handle, self.ws_ptr, self._tensor_ptrs, g, m, v,
                                                            ctypes.byref(desc), 1, _lib.stream_ptr(), ctypes.byref(took)),
                        "qt_plan_adam_step_overlapped")

@@ -19,14 +19,29 @@ stream.  Both orders compute the same bits.
     opt = FusedAdam(model.parameters(), lr=1e-4, weight_decay=1e-4, model=model)
 
 Without `model=` (or for parameters the plan does not know) it is a plain fused multi-tensor Adam.
+
+Gradient clipping by the global 2-norm (the reference's trainers call `torch.nn.utils.clip_grad_norm_(model.parameters(),
+1.0)` between backward() and step(): 3dcnn/train_3D_Quadtree_cnn_model.py:111-125) is part of the step:
+
+    opt = FusedAdam(model.parameters(), lr=1e-4, weight_decay=1e-4, model=model, max_grad_norm=1.0)
+
+One deterministic kernel pair (csrc/grad_norm.hip) reads the gradients once and leaves the norm and torch's clip
+coefficient `min(1, max_norm / (norm + 1e-6))` in device memory; the Adam kernels multiply each gradient by that
+coefficient as they read it.  The norm covers every parameter of every group of this optimizer that has a gradient in
+this step.  Nothing is copied to the host and nothing waits for the device.  `opt.last_grad_norm` (the norm before
+clipping) and `opt.last_clip_coef` are 0-dim f32 device tensors afterwards.  One difference from torch: `p.grad` is left
+UNSCALED, because the scaling happens inside the update.  A clipped step runs serially on the caller's stream (the norm
+needs conv1's weight gradient, the last thing the backward produces).  `grad_norm(parameters)` gives the same norm alone,
+for logging.
 """
 import ctypes
+import math
 import os
 
 import torch
 
 from . import _lib
-from .engine import AdamDesc, AdamItem
+from .engine import AdamDesc, AdamItem, _bind_api
 
 
 # Parameter updates made through raw pointers (qt_adam_multi) do not bump torch's version counters: consumers that cache
@@ -50,12 +65,85 @@ def overlap_allowed(engine, by_index, created_state, n_groups, n_steps):
     return engine is not None and engine.adam_overlap_ok(by_index)
 
 
+def _norm_items(grads):
+    """AdamItem array for the norm kernel (it reads `grad` and `numel` only)."""
+    items = (AdamItem * len(grads))()
+    for j, g in enumerate(grads):
+        if g.is_sparse or g.dtype != torch.float32 or g.device.type != "cuda" or not g.is_contiguous() or \
+                g.device != grads[0].device:
+            raise _lib.QtError("the gradient norm kernel handles dense contiguous f32 gradients on one GPU")
+        items[j] = AdamItem(None, g.data_ptr(), None, None, g.numel())
+    return items
+
+
+def _norm_workspace(L, items, n, device, cached=None):
+    need = L.qt_grad_norm_workspace_bytes(items, n)
+    if need == 0:
+        _lib.check(-1, "qt_grad_norm_workspace_bytes")
+    if cached is not None and cached.device == device and cached.numel() * 4 >= need:
+        return cached
+    return torch.empty(need // 4, dtype=torch.float32, device=device)
+
+
+def grad_norm(parameters):
+    """Global 2-norm of the gradients of `parameters` (a tensor or an iterable; those without .grad are skipped) as a 0-dim
+    f32 device tensor: what torch.nn.utils.clip_grad_norm_ returns, from the kernel FusedAdam(max_grad_norm=...) uses,
+    without scaling anything and without a host sync."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        raise _lib.QtError("grad_norm: no parameter has a gradient")
+    grads = [g.contiguous() for g in grads]
+    L = _lib.lib()
+    _bind_api(L)
+    items = _norm_items(grads)
+    dev = grads[0].device
+    with torch.cuda.device(dev):
+        ws = _norm_workspace(L, items, len(grads), dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.check(L.qt_grad_norm_multi(items, len(grads), 1.0, ws.data_ptr(), ws.numel() * 4, out.data_ptr(),
+                                        _lib.stream_ptr()), "qt_grad_norm_multi")
+    return out[0]
+
+
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, model=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, model=None, max_grad_norm=None):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
             raise ValueError("FusedAdam: invalid hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0 or math.isnan(max_grad_norm):
+                raise ValueError("FusedAdam: max_grad_norm must be a positive number or None")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
         self._model = model
+        self.last_grad_norm = None    # after a clipped step(): 0-dim f32 device tensors
+        self.last_clip_coef = None
+        self._norm_ws = None
+
+    def _max_grad_norm(self):
+        """One value for the whole optimizer (per-group clipping is not offered); read from the param groups, which is
+        where load_state_dict() puts it."""
+        values = {g.get("max_grad_norm") for g in self.param_groups}
+        if len(values) > 1:
+            raise ValueError("FusedAdam: every param group must carry the same max_grad_norm")
+        return values.pop() if values else None
+
+    def _begin_clip(self, L, max_norm):
+        """Everything the clipped step needs before its first update: the gradients of all groups (the norm is global),
+        the norm kernel's workspace and the two output floats.  No device work yet."""
+        _bind_api(L)
+        grads = [(id(p), p.grad.contiguous()) for group in self.param_groups for p in group["params"] if p.grad is not None]
+        self.last_grad_norm = self.last_clip_coef = None
+        if not grads:
+            return None
+        items = _norm_items([g for _, g in grads])
+        dev = grads[0][1].device
+        with torch.cuda.device(dev):
+            self._norm_ws = _norm_workspace(L, items, len(grads), dev, self._norm_ws)
+            out = torch.empty(2, dtype=torch.float32, device=dev)   # fresh per step: earlier steps' values stay readable
+        self.last_grad_norm, self.last_clip_coef = out[0], out[1]
+        return {"grads": grads, "items": items, "ws": self._norm_ws, "out": out, "done": False}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -69,6 +157,8 @@ class FusedAdam(torch.optim.Optimizer):
             plan_index = {id(p): i for p, i in zip(self._model._param_list, self._model._param_plan_index) if i >= 0}
         L = _lib.lib()
         L.qt_adam_multi.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.POINTER(AdamDesc), ctypes.c_void_p]
+        max_norm = self._max_grad_norm()
+        clip = self._begin_clip(L, max_norm) if max_norm is not None else None
         fused_groups = 0
         for group in self.param_groups:
             todo = []
@@ -100,8 +190,14 @@ class FusedAdam(torch.optim.Optimizer):
                 if in_plan and engine is not None and fused_groups == 0 and len(steps) == 1 and \
                         len(self.param_groups) == 1:
                     with torch.cuda.device(engine.device):
-                        engine.adam_step(in_plan, desc, overlap=overlap_allowed(
-                            engine, in_plan, created_state, len(self.param_groups), len(steps)))
+                        if clip is None:
+                            engine.adam_step(in_plan, desc, overlap=overlap_allowed(
+                                engine, in_plan, created_state, len(self.param_groups), len(steps)))
+                        else:   # one norm over the plan's gradients and the rest, one coefficient for both calls
+                            extra = [g for pid, g in clip["grads"] if pid not in plan_index]
+                            engine.adam_step(in_plan, desc, clip=(max_norm, _norm_items(extra) if extra else None,
+                                                                  len(extra), clip["ws"], clip["out"]))
+                            clip["done"] = True
                     fused_groups += 1
                 else:
                     rest = part
@@ -116,8 +212,19 @@ class FusedAdam(torch.optim.Optimizer):
                         items[j] = AdamItem(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
                                             st["exp_avg_sq"].data_ptr(), p.numel())
                     with torch.cuda.device(rest[0][0].device):
-                        _lib.check(L.qt_adam_multi(items, len(rest), ctypes.byref(desc), _lib.stream_ptr()),
-                                   "qt_adam_multi")
+                        if clip is None:
+                            _lib.check(L.qt_adam_multi(items, len(rest), ctypes.byref(desc), _lib.stream_ptr()),
+                                       "qt_adam_multi")
+                        else:
+                            if not clip["done"]:
+                                _lib.check(L.qt_grad_norm_multi(clip["items"], len(clip["grads"]), max_norm,
+                                                                clip["ws"].data_ptr(), clip["ws"].numel() * 4,
+                                                                clip["out"].data_ptr(), _lib.stream_ptr()),
+                                           "qt_grad_norm_multi")
+                                clip["done"] = True
+                            _lib.check(L.qt_adam_multi_scaled(items, len(rest), ctypes.byref(desc),
+                                                              clip["out"].data_ptr() + 4, _lib.stream_ptr()),
+                                       "qt_adam_multi_scaled")
                     global _raw_updates
                     _raw_updates += 1
         return loss

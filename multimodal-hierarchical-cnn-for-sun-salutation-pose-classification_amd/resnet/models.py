@@ -14,6 +14,7 @@ if os.path.dirname(_PKG_DIR) not in sys.path:
 _impl = importlib.import_module(_PKG + ".quadtree")
 QtError = importlib.import_module(_PKG + "._lib").QtError
 FusedAdam = importlib.import_module(_PKG + ".optim").FusedAdam  # optional replacement of optim.Adam(...)
+grad_norm = importlib.import_module(_PKG + ".optim").grad_norm  # global gradient norm on the device (logging)
 
 StandardResNetCNN = _impl.StandardResNetCNN
 
