@@ -316,6 +316,54 @@ int qt_adam_pack_weights_batched_scaled(int dtype, const qt_pack_item* items, co
 size_t qt_grad_norm_workspace_bytes(const qt_adam_item* items, int n);
 int qt_grad_norm_multi(const qt_adam_item* items, int n, float max_norm, void* workspace, size_t workspace_bytes,
                        float* out2, void* stream);
+/* Loss head: replaces nn.CrossEntropyLoss()(outputs, labels) and its backward (3dcnn/train_3D_Quadtree_cnn_model.py:108-111,
+ * every other trainer alike), FocalLoss (3dcnn/models.py:8-47) and the per-step bookkeeping of the trainers
+ * (loss.item(), torch.max(outputs.data, 1), (predicted == labels).sum().item(): :127-137) without a host round trip.
+ * logits: f32 [rows][C], row stride ld >= C elements (views are fine); labels: int64 [rows]; 1 <= C <= 1024, rows >= 1.
+ * QT_ERR_UNSUPPORTED for another dtype, C > 1024 and 0 < gamma < 1; QT_ERR_INVALID_ARG for every other bad argument.
+ * With p = softmax(z), w = class_weight (NULL: all ones), y = label:
+ *   QT_LOSS_CROSS_ENTROPY  loss_i = (1-eps) w[y] (-log p_y) + (eps/C) sum_c w[c] (-log p_c); a row whose label equals
+ *                          ignore_index contributes 0 and gets a zero gradient; MEAN divides by the sum of w[y] over the
+ *                          other rows (no such row: NaN) -- torch.nn.functional.cross_entropy with class-index targets;
+ *   QT_LOSS_FOCAL          loss_i = -w[y] (1-p_y)^gamma log p_y, w = the reference's alpha; MEAN divides by rows;
+ *                          ignore_index and label_smoothing are not read; gamma = 0 or gamma >= 1.
+ * A label outside [0, C) that is not an ignored one cannot be refused by the host.  The kernels never index with it: such
+ * a row's loss is NaN, which makes the reduced loss and (MEAN / SUM) every gradient NaN; with NONE only that row's loss
+ * and gradient row are NaN.  Its pred entry is still the argmax.
+ * Both calls enqueue on `stream` only: no allocation, no atomics, no zero fill, no host synchronisation, the same bits on
+ * every run.  One launch each while the rows fit one workgroup (256 rows for C <= 16, 16 for C <= 64, else 4); above
+ * that the forward is per-workgroup partial sums in `workspace` (qt_loss_workspace_bytes; 0 = none needed, NULL is fine)
+ * plus a one-workgroup finalize that adds them in double in a fixed order.
+ * qt_loss_forward writes
+ *   loss       one f32 (MEAN / SUM) or [rows] (NONE)
+ *   row_state  [rows][2] f32 {max logit, log(sum exp(z - max))} for the backward; NULL when no backward follows
+ *   stats      double[3] {sum of loss_i, denominator the reduction divides by (1 for SUM / NONE), #(pred == label)}
+ *   pred       int64 [rows] argmax as torch.max(outputs, 1) on the CPU gives it: the first index wins a tie, a NaN logit
+ *              wins its row; or NULL
+ *   meter      double[4] {loss_sum, samples, correct, skipped_steps} owned by the caller, updated by one thread after the
+ *              reduction, or NULL.  Reduced loss finite: loss_sum += loss * rows (MEAN) or += loss (SUM; NONE: the sum of
+ *              loss_i), samples += rows, correct += stats[2].  Otherwise skipped_steps += 1 and nothing else.
+ * qt_loss_backward reads the same logits / labels, row_state and stats, and the upstream gradient grad_out from DEVICE
+ * memory (one f32; [rows] for NONE), and writes dlogits [rows][ld_d] (columns >= C untouched):
+ *   cross-entropy  [(1-eps) w[y] (p_k - [k == y]) + (eps/C) (p_k sum_c w[c] - w[k])] * grad_out / stats[1]
+ *   focal          w[y] [(1-p_y)^gamma - gamma p_y (1-p_y)^(gamma-1) log p_y] (p_k - [k == y]) * grad_out / stats[1] */
+enum { QT_LOSS_CROSS_ENTROPY = 0, QT_LOSS_FOCAL = 1 };
+enum { QT_LOSS_REDUCE_MEAN = 0, QT_LOSS_REDUCE_SUM = 1, QT_LOSS_REDUCE_NONE = 2 };
+typedef struct qt_loss_desc {
+  int dtype;                  /* of the logits: QT_F32 */
+  int kind, reduction;
+  long long ignore_index;     /* torch's default: -100 */
+  float label_smoothing;      /* eps in [0, 1] */
+  float gamma;
+  const float* class_weight;  /* device, [C], or NULL */
+} qt_loss_desc;
+size_t qt_loss_workspace_bytes(long long rows, int C);
+int qt_loss_forward(const qt_loss_desc* desc, const float* logits, long long ld, const long long* labels, long long rows, int C,
+                    float* loss, float* row_state, double* stats, long long* pred, double* meter, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int qt_loss_backward(const qt_loss_desc* desc, const float* logits, long long ld, const long long* labels, long long rows, int C,
+                     const float* row_state, const double* stats, const float* grad_out, float* dlogits, long long ld_d,
+                     void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of
