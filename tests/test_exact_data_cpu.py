@@ -1,0 +1,261 @@
+"""The integer-grid cases of tests/_exact.py without a GPU: every table row meets its conditions on the float64 reference
+alone; a torch-f32 computation in the kernel's place (two memory formats: two summation orders) passes the same torch.equal
+checks tests/test_conv_exact_gpu.py applies to the HIP kernels; and each listed kind of damage to that stand-in is caught."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import _exact as E
+from _exact import BF, F32
+
+
+def _formats(x):
+    fmt = torch.channels_last if x.dim() == 4 else torch.channels_last_3d
+    return [x.contiguous(), x.contiguous(memory_format=fmt)]
+
+
+def _conv32(x, w, s, p):
+    """f32 convolution of f64-held integers, once per memory format of the input"""
+    return [E._conv(xf, w.float(), s, p) for xf in _formats(x.float())]
+
+
+FWD, FWD_IDS = E.expand(E.FWD_ROWS)
+
+
+@pytest.mark.parametrize("row,dt", FWD, ids=FWD_IDS)
+def test_forward_rows(row, dt):
+    c = E.fwd_data(row)
+    E.fwd_conditions(c, dt)
+    mode = row["mode"]
+    _, _, _, _, _, s, p = row["cfg"]
+    for raw in _conv32(c["x"], c["w"], s, p):
+        assert torch.equal(raw.double(), c["raw"])                       # f32 in any order == float64
+        assert E.same(raw.to(dt), c["raw"], dt)
+        act = F.relu(raw * E.bcast(c["scale"].float(), raw) + E.bcast(c["shift"].float(), raw) + c["res"].float())
+        assert E.same(act.to(dt), c["act"], dt)
+        if mode == "A":
+            rows = raw.movedim(1, -1).reshape(-1, raw.shape[1])              # [M][C] as the kernels see it
+            part = torch.stack([torch.stack([t.sum(0), (t * t).sum(0)]) for t in rows.split(128)])
+            assert E.stats_equal(part, c["raw"])
+
+
+S2, S2_IDS = E.expand(E.S2_ROWS)
+
+
+@pytest.mark.parametrize("row,dt", S2, ids=S2_IDS)
+def test_stride2_pair_rows(row, dt):
+    c = E.s2_data(row)
+    E.s2_conditions(c, dt)
+    mode = row["mode"]
+    for raw, rawd in zip(_conv32(c["x"], c["w"], 2, 1), _conv32(c["x"], c["wd"], 2, 0)):
+        assert E.same(raw.to(dt), c["raw"], dt) and E.same(rawd.to(dt), c["rawd"], dt)
+        act = F.relu(raw * E.bcast(c["sc"].float(), raw) + E.bcast(c["sh"].float(), raw))
+        assert E.same(act.to(dt), c["act"], dt)
+        assert E.same((rawd * E.bcast(c["sd"].float(), raw) + E.bcast(c["shd"].float(), raw)).to(dt), c["pred"], dt)
+
+
+@pytest.mark.parametrize("row", E.STEM_ROWS, ids=E.ids(E.STEM_ROWS))
+def test_stem_rows(row):
+    c = E.stem_data(row)
+    mode = row["mode"]
+    E.conditions(c["raw"], c["araw"], BF, mode, w=c["w"], acts=[c["x"]], stats=(mode == "A"))
+    E.conditions(c["pre"], c["apre"], BF, mode, zeros=False)
+    for raw in _conv32(c["x"], c["w"], 2, 3):
+        assert E.same(raw.to(BF), c["raw"], BF)
+        act = F.relu(raw * E.bcast(c["scale"].float(), raw) + E.bcast(c["shift"].float(), raw)).to(BF)
+        assert E.same(act, c["act"], BF)
+        assert E.same(F.max_pool2d(act.float(), 3, 2, 1).to(BF), c["pooled"], BF)
+
+
+DG, DG_IDS = E.expand(E.DGRAD_ROWS + E.S2D_ROWS)
+
+
+@pytest.mark.parametrize("row,dt", DG, ids=DG_IDS)
+def test_data_gradient_rows(row, dt):
+    c = E.s2d_data(row) if "form" in row else E.dgrad_data(row)
+    E.dgrad_conditions(c, dt)
+    B, Cin, Cout, H, k, s, p = row["cfg"]
+    for dyf in _formats(c["dy"].float()):
+        dx = torch.nn.grad.conv2d_input((B, Cin, H, H), c["w"].float(), dyf, s, p)
+        if "wd" in c:
+            dx = dx + torch.nn.grad.conv2d_input((B, Cin, H, H), c["wd"].float(), c["dyd"].float(), 2, 0)
+        out = torch.where(c["act"].to(dt).float() > 0, dx + c["other"].float(), torch.zeros(()))
+        assert E.same(out.to(dt), c["out"], dt)
+
+
+WG, WG_IDS = E.expand(E.WGRAD_ROWS)
+
+
+@pytest.mark.parametrize("row,dt", WG, ids=WG_IDS)
+def test_weight_gradient_rows(row, dt):
+    c = E.wgrad_data(row)
+    E.wgrad_conditions(c)
+    _, _, _, _, _, s, p = row["cfg"]
+    for xf in _formats(c["x"].float()):
+        dw = torch.nn.grad.conv2d_weight(xf, tuple(c["dw"].shape), c["dy"].float(), s, p)
+        assert E.same(dw, c["dw"], F32)
+
+
+@pytest.mark.parametrize("row", E.LWGRAD_ROWS, ids=E.ids(E.LWGRAD_ROWS))
+def test_linear_weight_gradient_rows(row):
+    c = E.lwgrad_data(row)
+    E.lwgrad_conditions(c)
+    assert E.same(c["dy"].float().t() @ c["x"].float(), c["dw"], F32)
+    assert E.same((c["x"].float().t() @ c["dy"].float()).t().contiguous(), c["dw"], F32)
+
+
+@pytest.mark.parametrize("row", E.LINEAR_ROWS, ids=E.ids(E.LINEAR_ROWS))
+def test_linear_rows(row):
+    c = E.gemm_data(row)
+    E.gemm_conditions(c, BF)
+    b = c["bias"].float() if c["bias"] is not None else None
+    for y in (F.linear(c["x"].float(), c["w"].float(), b), (c["w"].float() @ c["x"].float().t()).t() + (b if b is not None else 0)):
+        y = F.relu(y) if row["relu"] else y
+        assert E.same(y.to(BF), c["out"], BF)
+
+
+SD, SD_IDS = E.expand(E.STEMD_ROWS)
+
+
+@pytest.mark.parametrize("row,dt", SD, ids=SD_IDS)
+def test_stem_data_gradient_rows(row, dt):
+    """qt_stem_dgrad writes the f32 image gradient whatever the type of the gradient map"""
+    c = E.dgrad_data(row)
+    E.dgrad_conditions(c, F32)
+    for dyf in _formats(c["dy"].float()):
+        assert E.same(torch.nn.grad.conv2d_input((1, 3, 224, 224), c["w"].float(), dyf, 2, 3), c["dx"], F32)
+
+
+SW, SW_IDS = E.expand(E.STEMW_ROWS)
+
+
+@pytest.mark.parametrize("row,dt", SW, ids=SW_IDS)
+def test_stem_weight_gradient_rows(row, dt):
+    c = E.wgrad_data(row)
+    E.wgrad_conditions(c)
+    for xf in _formats(c["x"].float()):
+        assert E.same(torch.nn.grad.conv2d_weight(xf, (64, 3, 7, 7), c["dy"].float(), 2, 3), c["dw"], F32)
+
+
+C3 = [(r, dt, ci, co) for rows, ci, co in ((E.C3F_ROWS, 3, 32), (E.C32_ROWS, 32, 64)) for r in rows for dt in r["dts"]]
+C3_IDS = [f"{r['name']}-{'bf16' if dt == BF else 'f32'}" for r, dt, _, _ in C3]
+
+
+@pytest.mark.parametrize("row,dt,cin,cout", C3, ids=C3_IDS)
+def test_conv3d_rows(row, dt, cin, cout):
+    c = E.c3_data(row, cin, cout)
+    first = cin == 3
+    if "fwd" in row["only"]:
+        E.c3_conditions(c, dt, "fwd")
+        for raw in _conv32(c["x"], c["w"], 1, 1):
+            assert E.same(raw.to(dt), c["raw"], dt)
+            act = F.relu(raw * E.bcast(c["scale"].float(), raw) + E.bcast(c["shift"].float(), raw)).to(dt)
+            assert E.same(act, c["act"], dt)
+            assert E.same(F.max_pool3d(act.float(), (1, 2, 2)).to(dt), c["pooled"], dt)
+    if "dgrad" in row["only"]:
+        ddt = F32 if first else dt          # the first convolution's data gradient is the f32 clip gradient
+        E.c3_conditions(c, ddt, "dgrad")
+        for dyf in _formats(c["dyf"].float()):
+            assert E.same(torch.nn.grad.conv3d_input(c["x1"].shape, c["wg"].float(), dyf, 1, 1).to(ddt), c["dx"], ddt)
+    if "wgrad" in row["only"]:
+        E.c3_conditions(c, F32, "wgrad")
+        for xf in _formats(c["x1"].float()):
+            assert E.same(torch.nn.grad.conv3d_weight(xf, c["w"].shape, c["dy"].float(), 1, 1), c["dw"], F32)
+
+
+FUSED = [(r, cp) for r in E.C3F_ROWS if "fused" in r["only"] for cp in (32, 64)]
+
+
+def _fused_dy32(f, gate_ge=False):
+    """the kernel's own form in f32: dy = ka g + kb - y kc with ka = a, kc = a invstd c, kb = a (mean invstd c - b), as bf16"""
+    y = f["y"].float()
+    a, b, c = (E.bcast(f["coef"][j, :32].float(), y) for j in range(3))
+    mu, inv = E.bcast(f["mean"].float(), y), E.bcast(f["invstd"].float(), y)
+    pre = y * E.bcast(f["scale"].float(), y) + E.bcast(f["shift"].float(), y)
+    up = f["dout"][:, :32].float().repeat_interleave(2, 3).repeat_interleave(2, 4)
+    on = (pre >= 0) if gate_ge else (pre > 0)
+    g = torch.where(f["gate"] & on, up, torch.zeros(()))
+    return (a * g + a * (mu * inv * c - b) - y * (a * inv * c)).to(BF)
+
+
+@pytest.mark.parametrize("row,cp", FUSED, ids=[f"{r['name']}-cp{cp}" for r, cp in FUSED])
+def test_fused_first_conv3d_weight_gradient_rows(row, cp):
+    f = E.c3_fused_data(E.c3_data(row, 3, 32), cp)
+    E.c3_fused_conditions(f)
+    dy = _fused_dy32(f)
+    assert E.same(dy, f["dy"], BF)
+    for xf in _formats(f["x1"].float()):
+        assert E.same(torch.nn.grad.conv3d_weight(xf, f["w"].shape, dy.float(), 1, 1), f["dw"], F32)
+    # a gate that lets y * scale + shift == 0 through is caught
+    bad = _fused_dy32(f, gate_ge=True)
+    assert not E.same(torch.nn.grad.conv3d_weight(f["x1"].float(), f["w"].shape, bad.float(), 1, 1), f["dw"], F32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# damage: each of these must make the comparison fail
+# ----------------------------------------------------------------------------------------------------------------------
+def _row(rows, name):
+    return next(r for r in rows if r["name"] == name)
+
+
+DAMAGE_ROWS = [_row(E.FWD_ROWS, "generic_3x3"), _row(E.FWD_ROWS, "ring_b1"), _row(E.FWD_ROWS, "generic_m49")]
+
+
+@pytest.mark.parametrize("row", DAMAGE_ROWS, ids=E.ids(DAMAGE_ROWS))
+def test_a_skipped_tap_a_dropped_k_element_and_a_missing_tile_are_caught(row):
+    c = E.fwd_data(row)
+    dt = BF
+    _, _, Cout, _, k, s, p = row["cfg"]
+    x, w = c["x"].float(), c["w"].float()
+    raw = F.conv2d(x, w, None, s, p)
+    assert E.same(raw.to(dt), c["raw"], dt)
+    # the centre tap skipped at the first output column of one channel
+    ch = Cout // 3
+    only = torch.zeros_like(w)
+    only[ch, :, k // 2, k // 2] = w[ch, :, k // 2, k // 2]
+    hurt = raw.clone()
+    hurt[:, ch, :, 0] -= F.conv2d(x, only, None, s, p)[:, ch, :, 0]
+    assert not E.same(hurt.to(dt), c["raw"], dt)
+    assert E.first_mismatch(hurt.to(dt), c["raw"], dt)[0][1] == ch
+    # one k element dropped
+    o, i, a, b = (int(v) for v in (w != 0).nonzero()[len((w != 0).nonzero()) // 2])
+    w2 = w.clone()
+    w2[o, i, a, b] = 0
+    assert not E.same(F.conv2d(x, w2, None, s, p).to(dt), c["raw"], dt)
+    # the last (ragged) 128-row tile left out of the statistics
+    rows = raw.movedim(1, -1).reshape(-1, Cout)
+    tiles = rows.split(128)
+    part = torch.stack([torch.stack([t.sum(0), (t * t).sum(0)]) for t in tiles])
+    assert E.stats_equal(part, c["raw"])
+    assert tiles[-1].shape[0] <= 128 and not E.stats_equal(part[:-1], c["raw"])
+
+
+ROUNDED = [_row(E.FWD_ROWS, "generic_3x3_rounded"), _row(E.FWD_ROWS, "ring_rounded"), _row(E.FWD_ROWS, "pt_14_rounded")]
+
+
+@pytest.mark.parametrize("row", ROUNDED, ids=E.ids(ROUNDED))
+def test_a_truncating_store_is_caught(row):
+    c = E.fwd_data(row)
+    _, _, _, _, _, s, p = row["cfg"]
+    raw = F.conv2d(c["x"].float(), c["w"].float(), None, s, p)
+    assert E.same(raw.to(BF), c["raw"], BF)
+    trunc = (raw.view(torch.int32) & ~0xFFFF).view(torch.float32).to(BF)
+    assert not E.same(trunc, c["raw"], BF)
+    # round-half-up instead of round-half-to-even
+    up = ((raw.view(torch.int32) + 0x8000) & ~0xFFFF).view(torch.float32).to(BF)
+    assert not E.same(up, c["raw"], BF)
+
+
+MASKED = [_row(E.DGRAD_ROWS, "generic_3x3"), _row(E.DGRAD_ROWS, "pt_7_ragged"), _row(E.S2D_ROWS, "merged5_small")]
+
+
+@pytest.mark.parametrize("row", MASKED, ids=E.ids(MASKED))
+def test_a_mask_that_lets_zeros_through_is_caught(row):
+    c = E.s2d_data(row) if "form" in row else E.dgrad_data(row)
+    pre = c["pre"].float()
+    act = c["act"].to(BF).float()
+    zero = torch.zeros(())
+    assert E.same(torch.where(act > 0, pre, zero).to(BF), c["out"], BF)
+    assert not E.same(torch.where(act >= 0, pre, zero).to(BF), c["out"], BF)
+    # a mask read from the sign bit alone: +0 passes, -0 masks
+    assert not E.same(torch.where(~torch.signbit(act), pre, zero).to(BF), c["out"], BF)
