@@ -717,7 +717,8 @@ extern "C" int qt_pool3d_bn_bwd_apply(int dtype, const void* dout, const unsigne
 
 extern "C" int qt_avgpool_tb(int dtype, const void* x, float* dst, int frames, int batch, int hw, int C, int ld, int col0,
                              void* stream) {
-  QT_CHECK_ARG(x && dst && frames > 0 && batch > 0 && hw > 0 && C % 8 == 0 && ld >= col0 + C, "qt_avgpool_tb: bad argument");
+  QT_CHECK_ARG(x && dst && frames > 0 && batch > 0 && hw > 0 && C > 0 && C % 8 == 0 && col0 >= 0 && ld >= col0 + C,
+               "qt_avgpool_tb: bad argument");
   QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_avgpool_tb: bad dtype %d", dtype);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype == QT_F32)
@@ -730,7 +731,8 @@ extern "C" int qt_avgpool_tb(int dtype, const void* x, float* dst, int frames, i
 
 extern "C" int qt_avgpool_tb_bwd(int dtype, const float* d, void* g, int frames, int batch, int hw, int C, int ld, int col0,
                                  void* stream) {
-  QT_CHECK_ARG(d && g && frames > 0 && batch > 0 && hw > 0 && C % 8 == 0 && ld >= col0 + C, "qt_avgpool_tb_bwd: bad argument");
+  QT_CHECK_ARG(d && g && frames > 0 && batch > 0 && hw > 0 && C > 0 && C % 8 == 0 && col0 >= 0 && ld >= col0 + C,
+               "qt_avgpool_tb_bwd: bad argument");
   QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_avgpool_tb_bwd: bad dtype %d", dtype);
   const long long n = (long long)frames * batch * hw * (C / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);

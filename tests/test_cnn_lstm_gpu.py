@@ -32,7 +32,7 @@ def _oracle():
     return o
 
 
-@pytest.mark.parametrize("H,I", [(256, 640), (64, 47)])
+@pytest.mark.parametrize("H,I", [(256, 640), (64, 47), (188, 47)])
 def test_lstm_layer_forward_backward(H, I):
     """one nn.LSTM layer: forward states and the gradient w.r.t. the pre-activation gates (-> dx, dW_ih, dW_hh, db)"""
     dev = _dev()
