@@ -18,8 +18,10 @@ layer (3 input channels) is packed to one 128-wide K row per pixel (27 taps x 3 
 thin dense products from csrc/gemm_small.hip.  The whole forward / backward is ONE autograd node; PyTorch only owns the
 buffers.  There is no torch / CPU fallback.
 """
+import contextlib
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -56,17 +58,31 @@ class _Ops:
     """ctypes view of the C ABI used by the clip models; every call checks its status."""
 
     def __init__(self):
-        self.L = _lib.lib()
-        L = self.L
-        L.qt_stats_capacity_rows.restype = _c.c_int
-        L.qt_conv2d_wgrad_workspace_bytes.restype = _c.c_size_t
-        self._wgrad_ws = None
-        self.timed = None   # list while bench.py profiles: (start event, end event, algorithmic flops, bytes, mode) per conv launch
+        self.L = L = _lib.lib()
+        # every return type that is not ctypes' default int (a byte count would be cut to 32 bits) and every 64-bit argument
+        # of a function called with plain Python ints: declared here, once, for all call sites
+        for fn in (L.qt_conv2d_wgrad_workspace_bytes, L.qt_conv3d_c32_dgrad_scratch_bytes, L.qt_conv3d_c32_wgrad_workspace_bytes,
+                   L.qt_conv3d_first_wgrad_workspace_bytes):
+            fn.restype = _c.c_size_t
         L.qt_bn_stats_rows.argtypes = [_c.c_longlong, _c.c_int]
         L.qt_bn_bwd_partial_rows.argtypes = [_c.c_longlong, _c.c_int]
+        self._wgrad_ws = None
+        self.timed = None   # list while bench.py profiles: (start event, end event, algorithmic flops, bytes, mode) per conv launch
 
     def check(self, rc, what):
         _lib.check(rc, what)
+
+    @contextlib.contextmanager
+    def _timed(self, mode, flops, nbytes):
+        """bench.py's roofline: HIP events around one conv launch on its stream (= torch's current stream here)"""
+        if self.timed is None:
+            yield
+            return
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        yield
+        ev[1].record()
+        self.timed.append((ev[0], ev[1], float(flops), float(nbytes), int(mode)))
 
     # ---- convolutions -------------------------------------------------------------------------------------
     @staticmethod
@@ -85,14 +101,8 @@ class _Ops:
     def igemm(self, d, src, w, dst, scale=None, shift=None, residual=None, relu=0, stats=None, flops=0.0, nbytes=0.0):
         d.relu = relu
         io = _lib.ConvIO(src, w, dst, _ptr(scale), _ptr(shift), residual, None, _ptr(stats))
-        ev = None
-        if self.timed is not None:   # bench.py's roofline: HIP events on the launch stream (= torch's current stream here)
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        self.check(self.L.qt_conv2d_igemm(_c.byref(d), _c.byref(io), _lib.stream_ptr()), "qt_conv2d_igemm")
-        if ev is not None:
-            ev[1].record()
-            self.timed.append((ev[0], ev[1], float(flops), float(nbytes), int(d.mode)))
+        with self._timed(d.mode, flops, nbytes):
+            self.check(self.L.qt_conv2d_igemm(_c.byref(d), _c.byref(io), _lib.stream_ptr()), "qt_conv2d_igemm")
 
     def wgrad(self, d, dy, x, dw):
         """dw [n_out][taps][k_per_tap] f32 (zeroed by the caller).  Where the tile-resident kernel covers the shape (bf16,
@@ -128,12 +138,7 @@ class _Ops:
         part = torch.empty(self.L.qt_stats_capacity_rows(rows), 2, C, dtype=torch.float32, device=dev)
         self.check(self.L.qt_bn_stats(_lib.qt_dtype(dt), _ptr(y), _c.c_longlong(Mrows), C, _ptr(part), _lib.stream_ptr()),
                    "qt_bn_stats")
-        out = torch.empty(4, C, dtype=torch.float32, device=dev)   # mean, invstd, scale, shift
-        self.check(self.L.qt_bn_finalize(_ptr(part), rows, C, _c.c_longlong(Mrows), _ptr(gamma), _ptr(beta), _ptr(rmean),
-                                         _ptr(rvar), _ptr(nbt), _c.c_float(BN_MOMENTUM), _c.c_float(BN_EPS),
-                                         _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _lib.stream_ptr()),
-                   "qt_bn_finalize")
-        return out
+        return self.bn_finalize(part, rows, Mrows, C, gamma, beta, rmean, rvar, nbt, dev)
 
     def bn_eval(self, gamma, beta, rmean, rvar, C, dev):
         out = torch.empty(4, C, dtype=torch.float32, device=dev)   # running mean, 1/sqrt(running var + eps), scale, shift
@@ -149,20 +154,24 @@ class _Ops:
 
     def bn_backward(self, dt, g, act, y, stats, gamma, Mrows, C, dev, batch_stats):
         """g = d/d(relu(bn(y))) -> (dy, dgamma, dbeta); `act` is the ReLU output (its mask)."""
-        rows = self.L.qt_bn_bwd_partial_rows(_c.c_longlong(Mrows), C)
+        coef, dgamma, dbeta = self._bn_bwd_coef(dt, g, act, y, stats, gamma, Mrows, Mrows, C, dev, batch_stats)
+        dy = torch.empty_like(y)
+        self.check(self.L.qt_bn_bwd_apply(_lib.qt_dtype(dt), _ptr(g), _ptr(act), _ptr(y), _ptr(stats[0]), _ptr(stats[1]), _ptr(coef),
+                                          _ptr(dy), None, _c.c_longlong(Mrows), C, _lib.stream_ptr()), "qt_bn_bwd_apply")
+        return dy, dgamma, dbeta
+
+    def _bn_bwd_coef(self, dt, g, mask, y, stats, gamma, n, Mrows, C, dev, batch_stats):
+        """the BatchNorm backward's sums over the n rows of g -> (coefficients [3][C], dgamma, dbeta); Mrows: the batch's count"""
+        rows = self.L.qt_bn_bwd_partial_rows(_c.c_longlong(n), C)
         part = torch.empty(self.L.qt_stats_capacity_rows(rows), 2, C, dtype=torch.float32, device=dev)
-        q = _lib.qt_dtype(dt)
-        self.check(self.L.qt_bn_bwd_reduce(q, _ptr(g), _ptr(act), _ptr(y), _ptr(stats[0]), _ptr(stats[1]), _ptr(part),
-                                           _c.c_longlong(Mrows), C, _lib.stream_ptr()), "qt_bn_bwd_reduce")
+        self.check(self.L.qt_bn_bwd_reduce(_lib.qt_dtype(dt), _ptr(g), _ptr(mask), _ptr(y), _ptr(stats[0]), _ptr(stats[1]), _ptr(part),
+                                           _c.c_longlong(n), C, _lib.stream_ptr()), "qt_bn_bwd_reduce")
         dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
         coef = torch.empty(3, C, dtype=torch.float32, device=dev)
         self.check(self.L.qt_bn_bwd_finalize(_ptr(part), rows, C, _c.c_longlong(Mrows if batch_stats else 0), _ptr(gamma),
                                              _ptr(stats[1]), _ptr(dgb[0]), _ptr(dgb[1]), 0, _ptr(coef), _lib.stream_ptr()),
                    "qt_bn_bwd_finalize")
-        dy = torch.empty_like(y)
-        self.check(self.L.qt_bn_bwd_apply(q, _ptr(g), _ptr(act), _ptr(y), _ptr(stats[0]), _ptr(stats[1]), _ptr(coef), _ptr(dy),
-                                          None, _c.c_longlong(Mrows), C, _lib.stream_ptr()), "qt_bn_bwd_apply")
-        return dy, dgb[0], dgb[1]
+        return coef, dgb[0], dgb[1]
 
     def pack_clip(self, dt, clip, B, T, H, W):
         x = torch.empty(T * B * H * W, 128, dtype=dt, device=clip.device)
@@ -170,41 +179,23 @@ class _Ops:
         return x
 
     def conv3d_first(self, dt, clip, wf, y, part, B, T, H, W, flops, nbytes, pooled=None):
-        ev = None
-        if self.timed is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        if pooled is not None:   # y is the pooled map; pooled = the folded BatchNorm3d's (.., .., scale, shift)
-            self.check(self.L.qt_conv3d_first_fwd_pool(_lib.qt_dtype(dt), _ptr(clip), _ptr(wf), _ptr(y), y.shape[1], _ptr(pooled[2]),
-                                                       _ptr(pooled[3]), B, T, H, W, _lib.stream_ptr()), "qt_conv3d_first_fwd_pool")
-        else:
-            self.check(self.L.qt_conv3d_first_fwd(_lib.qt_dtype(dt), _ptr(clip), _ptr(wf), _ptr(y), None, None, 0, _ptr(part), B, T, H, W,
-                                                  _lib.stream_ptr()), "qt_conv3d_first_fwd")
-        if ev is not None:
-            ev[1].record()
-            self.timed.append((ev[0], ev[1], float(flops), float(nbytes), int(_lib.QT_CONV_FWD)))
+        with self._timed(_lib.QT_CONV_FWD, flops, nbytes):
+            if pooled is not None:   # y is the pooled map; pooled = the folded BatchNorm3d's (.., .., scale, shift)
+                self.check(self.L.qt_conv3d_first_fwd_pool(_lib.qt_dtype(dt), _ptr(clip), _ptr(wf), _ptr(y), y.shape[1], _ptr(pooled[2]),
+                                                           _ptr(pooled[3]), B, T, H, W, _lib.stream_ptr()), "qt_conv3d_first_fwd_pool")
+            else:
+                self.check(self.L.qt_conv3d_first_fwd(_lib.qt_dtype(dt), _ptr(clip), _ptr(wf), _ptr(y), None, None, 0, _ptr(part), B, T,
+                                                      H, W, _lib.stream_ptr()), "qt_conv3d_first_fwd")
 
     def conv3d_c32(self, dt, x, xc, wf, y, B, T, H, W, scale=None, shift=None, relu=0, stats=None, flops=0.0, nbytes=0.0):
-        ev = None
-        if self.timed is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        self.check(self.L.qt_conv3d_c32_fwd(_lib.qt_dtype(dt), _ptr(x), xc, _ptr(wf), _ptr(y), _ptr(scale), _ptr(shift), relu, _ptr(stats),
-                                            B, T, H, W, _lib.stream_ptr()), "qt_conv3d_c32_fwd")
-        if ev is not None:
-            ev[1].record()
-            self.timed.append((ev[0], ev[1], float(flops), float(nbytes), int(_lib.QT_CONV_FWD)))
+        with self._timed(_lib.QT_CONV_FWD, flops, nbytes):
+            self.check(self.L.qt_conv3d_c32_fwd(_lib.qt_dtype(dt), _ptr(x), xc, _ptr(wf), _ptr(y), _ptr(scale), _ptr(shift), relu,
+                                                _ptr(stats), B, T, H, W, _lib.stream_ptr()), "qt_conv3d_c32_fwd")
 
     def conv3d_c32_dgrad(self, dt, dy, wd, dx, dxc, scr, nscr, B, T, H, W, flops=0.0, nbytes=0.0):
-        ev = None
-        if self.timed is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        self.check(self.L.qt_conv3d_c32_dgrad(_lib.qt_dtype(dt), _ptr(dy), _ptr(wd), _ptr(dx), dxc, _ptr(scr), _c.c_size_t(nscr), B, T,
-                                              H, W, _lib.stream_ptr()), "qt_conv3d_c32_dgrad")
-        if ev is not None:
-            ev[1].record()
-            self.timed.append((ev[0], ev[1], float(flops), float(nbytes), int(_lib.QT_CONV_DGRAD)))
+        with self._timed(_lib.QT_CONV_DGRAD, flops, nbytes):
+            self.check(self.L.qt_conv3d_c32_dgrad(_lib.qt_dtype(dt), _ptr(dy), _ptr(wd), _ptr(dx), dxc, _ptr(scr), _c.c_size_t(nscr), B,
+                                                  T, H, W, _lib.stream_ptr()), "qt_conv3d_c32_dgrad")
 
     def pool(self, dt, x, out, arg, T, B, H, W, C, pt):
         self.check(self.L.qt_pool3d_max(_lib.qt_dtype(dt), _ptr(x), _ptr(out), _ptr(arg), T, B, H, W, C, pt,
@@ -222,20 +213,10 @@ class _Ops:
         position), then max-pool backward + ReLU mask + BatchNorm backward in one pass; no full-size gradient map in between.
         apply = False: no dy, the coefficients [3][C] instead (the consumer forms dy itself: qt_conv3d_first_wgrad_fused)"""
         cells = (T // pt) * B * (H // 2) * (W // 2)
-        Mrows = T * B * H * W
-        rows = self.L.qt_bn_bwd_partial_rows(_c.c_longlong(cells), C)
-        part = torch.empty(self.L.qt_stats_capacity_rows(rows), 2, C, dtype=torch.float32, device=dev)
-        q = _lib.qt_dtype(dt)
-        self.check(self.L.qt_bn_bwd_reduce(q, _ptr(dout), _ptr(pooled), _ptr(ymax), _ptr(stats[0]), _ptr(stats[1]), _ptr(part),
-                                           _c.c_longlong(cells), C, _lib.stream_ptr()), "qt_bn_bwd_reduce")
-        dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
-        coef = torch.empty(3, C, dtype=torch.float32, device=dev)
-        self.check(self.L.qt_bn_bwd_finalize(_ptr(part), rows, C, _c.c_longlong(Mrows if batch_stats else 0), _ptr(gamma),
-                                             _ptr(stats[1]), _ptr(dgb[0]), _ptr(dgb[1]), 0, _ptr(coef), _lib.stream_ptr()),
-                   "qt_bn_bwd_finalize")
+        coef, dgamma, dbeta = self._bn_bwd_coef(dt, dout, pooled, ymax, stats, gamma, cells, T * B * H * W, C, dev, batch_stats)
         if not apply:
-            return coef, dgb[0], dgb[1]
-        return self.pool_bn_apply(dt, dout, arg, pooled, y, stats, coef, T, B, H, W, C, pt, dev, cy, cd), dgb[0], dgb[1]
+            return coef, dgamma, dbeta
+        return self.pool_bn_apply(dt, dout, arg, pooled, y, stats, coef, T, B, H, W, C, pt, dev, cy, cd), dgamma, dbeta
 
     def pool_bn_apply(self, dt, dout, arg, pooled, y, stats, coef, T, B, H, W, C, pt, dev, cy=None, cd=None):
         """dy [T*B*H*W][cd] from pool_bn_backward's coefficients: max-pool backward + ReLU mask + BatchNorm backward in one pass"""
@@ -267,11 +248,6 @@ class _Ops:
         d = _GemmDesc(Mr, N, K, _lib.QT_F32, _lib.QT_F32, _lib.QT_F32, a_rs, a_ks, b_rs, b_ks, c_rs, relu, 0)
         self.check(self.L.qt_gemm_small(_c.byref(d), _ptr(A, a_off * 4), _ptr(Bm), _ptr(bias), _ptr(Cm, c_off * 4),
                                         _lib.stream_ptr()), "qt_gemm_small")
-
-    def linear(self, x, x_ld, x_off, W, b, rows, out, out_ld, out_off, relu):
-        """out[r, out_off:out_off+N] = relu?(x[r, x_off:x_off+K] W^T + b)  (nn.Linear; W [N,K])"""
-        N, K = W.shape
-        self.gemm(rows, N, K, x, x_ld, 1, W, K, 1, out, out_ld, b, relu, x_off, out_off)
 
     def dropout(self, x, rows, cols, ld, off, seed, p):
         self.check(self.L.qt_dropout(_lib.QT_F32, _ptr(x, off * 4), _c.c_longlong(rows), cols, ld, _c.c_ulonglong(seed),
@@ -306,7 +282,10 @@ class _Side:
     """fork / join of a per-device second stream around a branch; tensors made there and used on the main stream are
     recorded on it (the caching allocator's pools are per stream)"""
 
-    def __init__(self, dev, slot=0):
+    def __init__(self, dev, slot=0, enabled=True):
+        self.side = None   # (disabled: the branch runs in line, fork() is a null context and reads() / join() do nothing)
+        if not enabled:
+            return
         self.main = torch.cuda.current_stream(dev)
         key = ((dev.index if dev.index is not None else torch.cuda.current_device()), slot)
         if key not in _side_streams:
@@ -314,10 +293,20 @@ class _Side:
         self.side = _side_streams[key]
 
     def fork(self):
+        if self.side is None:
+            return contextlib.nullcontext()
         self.side.wait_stream(self.main)
         return torch.cuda.stream(self.side)
 
+    def reads(self, *tensors):
+        """tensors of the main stream that the branch reads"""
+        if self.side is not None:
+            for t in tensors:
+                t.record_stream(self.side)
+
     def join(self, *tensors):
+        if self.side is None:
+            return
         self.main.wait_stream(self.side)
         for t in tensors:
             if t is not None:
@@ -337,6 +326,57 @@ def ops():
 def _cpad(c):
     """channel count the conv kernels see: K rows are whole 128-byte chunks (64 bf16 / 32 f32 -> 64 covers both)"""
     return max(64, (c + 63) // 64 * 64)
+
+
+RAW, PACKED, SLAB, GEMM = "raw", "packed", "slab", "gemm"
+
+
+class _Route(NamedTuple):
+    """how a conv block runs one forward (_ConvBlock.route); its backward reads the same record"""
+    kernel: str        # RAW: from the f32 clip; PACKED: qt_pack_clip27 + the implicit GEMM as a 1x1; SLAB; GEMM: 27 taps
+    prow: int          # partial-sum rows of the conv epilogue's BatchNorm3d statistics (0 where none are taken)
+    fused_eval: bool   # eval without backward: BatchNorm3d + ReLU (RAW: + MaxPool3d) in the conv epilogue
+    fused_pool: bool   # BatchNorm3d + ReLU + MaxPool3d in one pass over the raw conv output
+    width: int         # channels per row of the block's output map
+
+
+class _Saved(NamedTuple):
+    """what a conv block keeps of one forward for its backward"""
+    route: _Route
+    x: torch.Tensor         # the block's input: the f32 clip (RAW), its packed rows (PACKED), else the previous block's map
+    y: torch.Tensor         # the raw conv output (bias-free accumulator)
+    act: torch.Tensor       # relu(bn(y)) where it was materialised (no fused pool), else None
+    arg: torch.Tensor       # the pool's argmax codes (None: no pool)
+    stats: torch.Tensor     # mean, invstd, scale, shift
+    shape: tuple            # (T, B, H, W) of the input
+    training: bool
+    out: torch.Tensor       # the block's output map
+    ymax: torch.Tensor      # fused pool: y at the argmax
+
+
+class _State(NamedTuple):
+    """what a clip model keeps of one forward for its backward"""
+    blocks: list
+    saved: list             # one _Saved per block
+    thw: tuple              # (t, h, w) of the last block's map
+    fused: torch.Tensor     # the classifier's input [B][ld]
+    hid: torch.Tensor       # its hidden activations (after ReLU and dropout)
+    lstm: object            # the _Lstm that ran (None: image only)
+    last: torch.Tensor      # Quadtree3DCNN: the LSTM's last step [B][H]
+    mul: float              # 1 / (1 - p) of this forward's dropout
+    T: int
+
+
+def _slab_rows(dt, cin, cout, B, T, H, W):
+    """partial-sum rows of a cin -> cout block on the slab kernels at this shape (csrc/conv3d_slab.hip: forward, data gradient
+    and weight gradient all cover it); 0: not a slab shape.  The one statement of that test: conv3d_block2's own route, and
+    conv3d_block1's choice of 32-channel pooled rows for it."""
+    if not (SLAB_C32 and dt == torch.bfloat16 and cin == 32 and cout == 64):
+        return 0
+    L = ops().L
+    rows = L.qt_conv3d_c32_stats_rows(B, T, H, W)
+    ok = rows > 0 and L.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W) > 0 and L.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W) > 0
+    return rows if ok else 0
 
 
 class _ConvBlock:
@@ -387,9 +427,9 @@ class _ConvBlock:
 
     def _desc(self, dt, mode, T, B, H, W):
         if self.first:
-            return o_desc(dt, mode, T * B, H, W, 128, self.cout_p, 1, 0)
+            return _Ops.conv_desc(dt, mode, T * B, H, W, 128, self.cout_p, 1, 0)
         kin, kout = (self.cin_p, self.cout_p) if mode == _lib.QT_CONV_FWD else (self.cout_p, self.cin_p)
-        d = o_desc(dt, mode, T * B, H, W, kin, kout, 3, 1)
+        d = _Ops.conv_desc(dt, mode, T * B, H, W, kin, kout, 3, 1)
         d.kt, d.frames = 3, T
         return d
 
@@ -398,143 +438,132 @@ class _ConvBlock:
         but the first: three launches per block and step)"""
         return v if v.shape[0] == self.cout and v.is_contiguous() else v[:self.cout].clone()
 
-    def _pooled_width(self, dt, B, T, H, W):
-        """channels per row of this block's pooled map [T][B][H][W][.]: 32 (no padding) when the next block's forward, data
-        gradient and weight gradient all run on the slab kernels at that size, else the padded width every other kernel reads"""
-        if not (POOLED32 and self.narrow_out and SLAB_C32 and dt == torch.bfloat16 and self.cout == 32):
-            return self.cout_p
+    def route(self, dt, B, T, H, W, training, keep, aligned):
+        """The kernels of one forward of this block on [T][B][H][W] (aligned: its input starts on a 16-byte boundary).  The
+        module's switches and QTCNN_CONV3D_FIRST are read here, per call; backward takes the route from the saved record."""
         L = ops().L
-        L.qt_conv3d_c32_dgrad_scratch_bytes.restype = _c.c_size_t
-        ok = (L.qt_conv3d_c32_stats_rows(B, T, H, W) > 0 and int(L.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W)) > 0
-              and self._slab_wgrad_bytes(B, T, H, W) > 0)
-        return 32 if ok else self.cout_p
+        fused_eval = not training and not keep
+        if self.first:
+            # the first layer from the f32 clip itself (csrc/conv3d_first.hip) where it covers the shape, else the packed form
+            prow = 0
+            if (FUSED_POOL and self.pool_t and dt == torch.bfloat16 and self.cin == 3 and self.cout == 32 and aligned
+                    and os.environ.get("QTCNN_CONV3D_FIRST", "1") != "0"):
+                prow = L.qt_conv3d_first_stats_rows(B, T, H, W)
+            if prow > 0:
+                # 32-channel pooled rows (no padding) where the next block runs on the slab kernels at the pooled size, else
+                # the padded width every other kernel reads; eval without backward at pool_t = 1: the whole block in one launch
+                narrow = POOLED32 and self.narrow_out and _slab_rows(dt, self.cout, 64, B, T // self.pool_t, H // 2, W // 2) > 0
+                fused_eval = fused_eval and self.pool_t == 1
+                return _Route(RAW, prow, fused_eval, not fused_eval, 32 if narrow else self.cout_p)
+            kernel, prow = PACKED, 0
+        else:
+            # conv3d_block2 (32 -> 64 channels) with its frame slabs resident in LDS (csrc/conv3d_slab.hip) where the shape fits
+            prow = _slab_rows(dt, self.cin, self.cout, B, T, H, W) if aligned else 0
+            kernel = SLAB if prow else GEMM
+        if training and not prow:
+            prow = L.qt_conv2d_stats_rows(_c.byref(self._desc(dt, _lib.QT_CONV_FWD, T, B, H, W)))
+        return _Route(kernel, prow if training else 0, fused_eval, bool(self.pool_t and not fused_eval and FUSED_POOL), self.cout_p)
 
-    @staticmethod
-    def _slab_wgrad_bytes(B, T, H, W):
-        L = ops().L
-        L.qt_conv3d_c32_wgrad_workspace_bytes.restype = _c.c_size_t
-        return int(L.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W))
+    def _batch_stats(self, conv, prow, rows, dev):
+        """conv(partial sums), then BatchNorm3d's batch statistics (mean, invstd, scale, shift) and running statistics.
+        Under batch statistics BatchNorm3d(conv + bias) = BatchNorm3d(conv): a per-channel constant moves the mean with it.
+        y holds the bias-free accumulator and the epilogue's statistics are of exactly that value; the bias only enters
+        the running mean the reference tracks (mean of conv + bias), added here."""
+        o = ops()
+        part = torch.empty(o.L.qt_stats_capacity_rows(prow), 2, self.cout_p, dtype=torch.float32, device=dev)
+        conv(part)
+        stats = o.bn_finalize(part, prow, rows, self.cout_p, self.gamma_p, self.beta_p, self.rmean_p, self.rvar_p,
+                              self.bn.num_batches_tracked, dev)
+        self.rmean_p.add_(self.bias_p, alpha=BN_MOMENTUM)
+        self.bn.running_mean.copy_(self.rmean_p[:self.cout])
+        self.bn.running_var.copy_(self.rvar_p[:self.cout])
+        return stats
 
-    def _raw_rows(self, dt, x, T, B, H, W):
-        """the first layer from the f32 clip itself (csrc/conv3d_first.hip): partial-sum rows, 0 = take the packed form"""
-        if not (self.first and FUSED_POOL and self.pool_t and dt == torch.bfloat16 and self.cin == 3 and self.cout == 32):
-            return 0
-        if x.data_ptr() % 16:
-            return 0
-        return ops().L.qt_conv3d_first_stats_rows(B, T, H, W) if os.environ.get("QTCNN_CONV3D_FIRST", "1") != "0" else 0
+    def _pool(self, dt, y, stats, T, B, H, W, width, keep, act=None, cy=None):
+        """MaxPool3d into rows of `width` channels -> (pooled, argmax, raw values at the argmax, (To, Ho, Wo)): of `act`, or
+        BatchNorm3d + ReLU + MaxPool3d of y (rows of cy channels) in one pass.  relu(bn(y)) is read by nothing but the pool (the
+        next block takes the pooled map, the backward's ReLU mask is `pooled > 0` at the argmax), so it is not materialised."""
+        o, dev = ops(), y.device
+        To, Ho, Wo = T // self.pool_t, H // 2, W // 2
+        out = torch.empty(To * B * Ho * Wo, width, dtype=dt, device=dev)
+        arg = torch.empty(To * B * Ho * Wo, width, dtype=torch.uint8, device=dev) if keep else None
+        ymax = None
+        if act is None:
+            ymax = torch.empty_like(out) if keep else None
+            o.pool_bn(dt, y, stats, out, arg, ymax, T, B, H, W, width, self.pool_t, cy=cy)
+        else:
+            o.pool(dt, act, out, arg, T, B, H, W, width, self.pool_t)
+        return out, arg, ymax, (To, Ho, Wo)
 
-    def _forward_raw(self, dt, clip, T, B, H, W, training, keep, prow):
+    def _forward_raw(self, dt, clip, T, B, H, W, training, keep, r):
         """conv3d_block1 without the packed K rows: conv from the f32 clip (y: 32-channel rows, bias-free), then BatchNorm3d +
-        ReLU + MaxPool3d in one pass into the 64-channel rows the next layer reads"""
+        ReLU + MaxPool3d in one pass into the rows the next layer reads"""
         o, dev = ops(), clip.device
         rows = T * B * H * W
-        y = torch.empty(rows, 32, dtype=dt, device=dev) if (training or keep or self.pool_t != 1) else None
+        y = None if r.fused_eval else torch.empty(rows, 32, dtype=dt, device=dev)
         fl = 2.0 * rows * 27 * self.cin * self.cout
         nb = 4.0 * rows * 3 + 2.0 * rows * 32
         if training:
-            part = torch.empty(o.L.qt_stats_capacity_rows(prow), 2, self.cout_p, dtype=torch.float32, device=dev)
-            o.conv3d_first(dt, clip, self.wf, y, part, B, T, H, W, fl, nb)
-            stats = o.bn_finalize(part, prow, rows, self.cout_p, self.gamma_p, self.beta_p, self.rmean_p, self.rvar_p,
-                                  self.bn.num_batches_tracked, dev)
-            self.rmean_p.add_(self.bias_p, alpha=BN_MOMENTUM)
-            self.bn.running_mean.copy_(self.rmean_p[:self.cout])
-            self.bn.running_var.copy_(self.rvar_p[:self.cout])
+            stats = self._batch_stats(lambda part: o.conv3d_first(dt, clip, self.wf, y, part, B, T, H, W, fl, nb), r.prow, rows, dev)
         else:
             stats = o.bn_eval(self.gamma_p, self.beta_p, self.rmean_p, self.rvar_p, self.cout_p, dev)
             # y is the bias-free accumulator: BatchNorm3d(y + bias) = y * scale + (shift + scale * bias), xhat = (y - (mean - bias)) invstd
             stats[3].addcmul_(stats[2], self.bias_p)
             stats[0].sub_(self.bias_p)
-            if not keep and self.pool_t == 1:   # eval without backward: the whole block in one launch, y never exists
-                out = torch.empty(T * B * (H // 2) * (W // 2), self._pooled_width(dt, B, T, H // 2, W // 2), dtype=dt, device=dev)
+            if r.fused_eval:   # y never exists
+                out = torch.empty(T * B * (H // 2) * (W // 2), r.width, dtype=dt, device=dev)
                 o.conv3d_first(dt, clip, self.wf, out, None, B, T, H, W, fl, 4.0 * rows * 3 + 2.0 * out.numel(), pooled=stats)
                 return out, (T, H // 2, W // 2), None
             o.conv3d_first(dt, clip, self.wf, y, None, B, T, H, W, fl, nb)
-        To, Ho, Wo = T // self.pool_t, H // 2, W // 2
-        cp = self._pooled_width(dt, B, To, Ho, Wo)
-        out = torch.empty(To * B * Ho * Wo, cp, dtype=dt, device=dev)
-        arg = torch.empty(To * B * Ho * Wo, cp, dtype=torch.uint8, device=dev) if keep else None
-        ymax = torch.empty_like(out) if keep else None
-        o.pool_bn(dt, y, stats, out, arg, ymax, T, B, H, W, cp, self.pool_t, cy=32)
-        saved = (clip, y, None, arg, stats, (T, B, H, W), training, out, ymax) if keep else None
-        return out, (To, Ho, Wo), saved
+        out, arg, ymax, thw = self._pool(dt, y, stats, T, B, H, W, r.width, keep, cy=32)
+        return out, thw, _Saved(r, clip, y, None, arg, stats, (T, B, H, W), training, out, ymax) if keep else None
 
     def forward(self, dt, x, T, B, H, W, training, keep):
+        """x: the previous block's map, or (first block) the f32 clip [B][T][3][H][W] -> (map, (To, Ho, Wo), _Saved or None)"""
         o, dev = ops(), x.device
-        rows = T * B * H * W
-        if self.first:   # x is the f32 clip [B][T][3][H][W]
-            prow = self._raw_rows(dt, x, T, B, H, W)
-            if prow > 0:
-                return self._forward_raw(dt, x, T, B, H, W, training, keep, prow)
+        r = self.route(dt, B, T, H, W, training, keep, x.data_ptr() % 16 == 0)
+        if r.kernel == RAW:
+            return self._forward_raw(dt, x, T, B, H, W, training, keep, r)
+        if r.kernel == PACKED:
             x = o.pack_clip(dt, x, B, T, H, W)
-        d = self._desc(dt, _lib.QT_CONV_FWD, T, B, H, W)
+        rows = T * B * H * W
         y = torch.empty(rows, self.cout_p, dtype=dt, device=dev)
-        fused_eval = not training and not keep   # eval without backward: BatchNorm3d + ReLU in the conv epilogue, no second pass
         esz = 2 if dt == torch.bfloat16 else 4
         fl = 2.0 * rows * 27 * self.cin * self.cout            # algorithmic: the Conv3d as the reference computes it
-        nb = esz * (rows * (self.cin_p + self.cout_p) + 27.0 * self.cin_p * self.cout_p)
-        tk = dict(flops=fl, nbytes=nb)
-        # conv3d_block2 (32 -> 64 channels) with its frame slabs resident in LDS (csrc/conv3d_slab.hip) where the shape fits:
-        # slab = its partial-sum rows, 0 = the 27-tap implicit GEMM
-        slab = 0
-        if (SLAB_C32 and dt == torch.bfloat16 and self.cin == 32 and self.cout == 64 and self.cin_p == 64 and self.cout_p == 64
-                and x.data_ptr() % 16 == 0):
-            slab = o.L.qt_conv3d_c32_stats_rows(B, T, H, W)
-        if slab:
-            tk = dict(flops=fl, nbytes=esz * (rows * (self.cin + self.cout_p) + 27.0 * self.cin * self.cout_p))
+        if r.kernel == SLAB:
+            nb = esz * (rows * (self.cin + self.cout_p) + 27.0 * self.cin * self.cout_p)
 
             def conv(**kw):
-                o.conv3d_c32(dt, x, x.shape[1], self.wf, y, B, T, H, W, **kw, **tk)
+                o.conv3d_c32(dt, x, x.shape[1], self.wf, y, B, T, H, W, flops=fl, nbytes=nb, **kw)
         else:
             if x.shape[1] != self.cin_p:
                 raise QtError(f"conv block: input rows of {x.shape[1]} channels, the implicit GEMM reads {self.cin_p}")
+            d = self._desc(dt, _lib.QT_CONV_FWD, T, B, H, W)
+            nb = esz * (rows * (self.cin_p + self.cout_p) + 27.0 * self.cin_p * self.cout_p)
 
             def conv(**kw):
-                o.igemm(d, _ptr(x), _ptr(self.wf), _ptr(y), **kw, **tk)
+                o.igemm(d, _ptr(x), _ptr(self.wf), _ptr(y), flops=fl, nbytes=nb, **kw)
         if training:
-            prow = slab or o.L.qt_conv2d_stats_rows(_c.byref(d))
-            part = torch.empty(o.L.qt_stats_capacity_rows(prow), 2, self.cout_p, dtype=torch.float32, device=dev)
-            # Under batch statistics BatchNorm3d(conv + bias) = BatchNorm3d(conv): a per-channel constant moves the mean with it.
-            # y holds the bias-free accumulator and the epilogue's statistics are of exactly that value; the bias only enters
-            # the running mean the reference tracks (mean of conv + bias), added below.
-            conv(stats=part)
-            stats = o.bn_finalize(part, prow, rows, self.cout_p, self.gamma_p, self.beta_p, self.rmean_p, self.rvar_p,
-                                  self.bn.num_batches_tracked, dev)
-            self.rmean_p.add_(self.bias_p, alpha=BN_MOMENTUM)
-            self.bn.running_mean.copy_(self.rmean_p[:self.cout])
-            self.bn.running_var.copy_(self.rvar_p[:self.cout])
+            stats = self._batch_stats(lambda part: conv(stats=part), r.prow, rows, dev)
         else:
             stats = o.bn_eval(self.gamma_p, self.beta_p, self.rmean_p, self.rvar_p, self.cout_p, dev)
-            if fused_eval:   # relu(scale * (conv + bias) + shift)
+            if r.fused_eval:   # relu(scale * (conv + bias) + shift): BatchNorm3d + ReLU in the conv epilogue, no second pass
                 shift = torch.addcmul(stats[3], stats[2], self.bias_p)
                 conv(scale=stats[2], shift=shift, relu=1)
-            elif slab:   # (its epilogue has no shift-only form: conv * 1 + bias)
+            elif r.kernel == SLAB:   # (its epilogue has no shift-only form: conv * 1 + bias)
                 conv(scale=torch.ones_like(self.bias_p), shift=self.bias_p)
             else:
                 conv(shift=self.bias_p)
-        ymax = None
-        if self.pool_t and not fused_eval and FUSED_POOL:
-            # BatchNorm3d + ReLU + MaxPool3d in one pass: relu(bn(y)) is read by nothing but the pool (the next block takes the
-            # pooled map, the backward's ReLU mask is `pooled > 0` at the argmax), so it is not materialised
-            a = None
-            To, Ho, Wo = T // self.pool_t, H // 2, W // 2
-            out = torch.empty(To * B * Ho * Wo, self.cout_p, dtype=dt, device=dev)
-            arg = torch.empty(To * B * Ho * Wo, self.cout_p, dtype=torch.uint8, device=dev) if keep else None
-            ymax = torch.empty_like(out) if keep else None
-            o.pool_bn(dt, y, stats, out, arg, ymax, T, B, H, W, self.cout_p, self.pool_t)
-        else:
-            if fused_eval:
-                a = y
-            else:
+        a = None
+        if not r.fused_pool:
+            a = y
+            if not r.fused_eval:
                 a = torch.empty_like(y)
                 o.bn_act(dt, y, stats, a, rows, self.cout_p)
-            arg, out, To, Ho, Wo = None, a, T, H, W
-            if self.pool_t:
-                To, Ho, Wo = T // self.pool_t, H // 2, W // 2
-                out = torch.empty(To * B * Ho * Wo, self.cout_p, dtype=dt, device=dev)
-                arg = torch.empty(To * B * Ho * Wo, self.cout_p, dtype=torch.uint8, device=dev) if keep else None
-                o.pool(dt, a, out, arg, T, B, H, W, self.cout_p, self.pool_t)
-        saved = (x, y, a, arg, stats, (T, B, H, W), training, out, ymax) if keep else None
-        return out, (To, Ho, Wo), saved
+        out, arg, ymax, thw = a, None, None, (T, H, W)
+        if self.pool_t:
+            out, arg, ymax, thw = self._pool(dt, y, stats, T, B, H, W, r.width, keep, act=a)
+        return out, thw, _Saved(r, x, y, a, arg, stats, (T, B, H, W), training, out, ymax) if keep else None
 
     @staticmethod
     def _ranges(T, kt):
@@ -543,137 +572,129 @@ class _ConvBlock:
         hi = min(T, T + 1 - kt)
         return lo, lo + kt - 1, max(0, hi - lo)
 
-    def backward(self, dt, dout, saved, wside=None, want_dx=False):
-        """dout: d/d(block output) -> (dx or None, dW, db, dgamma, dbeta).  wside: a _Side whose stream takes the weight
-        gradient (the caller joins it before dW is used).  want_dx (first block only): dx = d/d(clip), f32 [B][T][3][H][W];
-        the weight-gradient path does not change with it (the same launches on the same operands)"""
-        o = ops()
-        x, y, a, arg, stats, (T, B, H, W), training, pooled, ymax = saved
-        dev = x.device
-        esz = 2 if dt == torch.bfloat16 else 4
-        rows = T * B * H * W
-        raw = self.first and x.dtype == torch.float32 and x.dim() == 5   # saved by _forward_raw: the clip itself, y 32 wide
-        raw_ws, coef = 0, None
-        if raw:
-            o.L.qt_conv3d_first_wgrad_workspace_bytes.restype = _c.c_size_t
-            raw_ws = int(o.L.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W))
-            # (the pooled side's row width: 32 where block 2 runs on the slab kernels, else padded -- _pooled_width)
-            fused_dy = bool(FIRST_WGRAD_FUSED and raw_ws and self.pool_t == 1 and dt == torch.bfloat16 and dout.data_ptr() % 16 == 0)
-            dy, dgamma, dbeta = o.pool_bn_backward(dt, dout, arg, pooled, ymax, y, stats, self.gamma_p, T, B, H, W, pooled.shape[1],
-                                                   self.pool_t, dev, training, cy=32, cd=32 if raw_ws else self.cout_p,
-                                                   apply=not fused_dy)
-            coef = dy if fused_dy else None   # (apply = False returns the coefficients in dy's place)
-            if not raw_ws:   # (a width the raw weight-gradient kernel does not take: the packed rows after all)
-                x = o.pack_clip(dt, x, B, T, H, W)
-        elif ymax is not None:
-            dy, dgamma, dbeta = o.pool_bn_backward(dt, dout, arg, pooled, ymax, y, stats, self.gamma_p, T, B, H, W, self.cout_p,
-                                                   self.pool_t, dev, training)
-        else:
-            if self.pool_t:
-                da = torch.empty_like(a)
-                o.pool_bwd(dt, dout, arg, da, T, B, H, W, self.cout_p, self.pool_t)
-            else:
-                da = dout
-            dy, dgamma, dbeta = o.bn_backward(dt, da, a, y, stats, self.gamma_p, rows, self.cout_p, dev, training)
+    def backward(self, dt, dout, s, wside, want_dx=False):
+        """dout: d/d(block output), s: forward's _Saved -> (dx or None, dW, db, dgamma, dbeta).  wside: the _Side whose
+        stream takes the weight gradient (the caller joins it before dW is used).  want_dx (first block only): dx = d/d(clip),
+        f32 [B][T][3][H][W]; the weight-gradient path does not change with it (the same launches on the same operands)"""
+        o, r, x = ops(), s.route, s.x
+        T, B, H, W = s.shape
+        # conv3d_block1 from the clip: dy in 32-channel rows for the raw weight-gradient kernel, or formed inside it
+        # (fused_dy: pool_bn_backward returns the coefficients in dy's place); a width that kernel does not take: packed rows
+        raw_ws = int(o.L.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W)) if r.kernel == RAW else 0
+        fused_dy = bool(FIRST_WGRAD_FUSED and raw_ws and self.pool_t == 1 and dt == torch.bfloat16 and dout.data_ptr() % 16 == 0)
+        cd = (32 if raw_ws else self.cout_p) if r.kernel == RAW else None
+        dy, dgamma, dbeta = self._bn_pool_backward(dt, dout, s, cd, not fused_dy)
+        coef = dy if fused_dy else None
+        if r.kernel == RAW and not raw_ws:
+            x = o.pack_clip(dt, x, B, T, H, W)
         # conv bias gradient = column sums of dy.  No pass over dy is needed (it was 0.5 ms of the step): with
         # dy = ca (g - cb - xhat cc), ca = gamma invstd, the sum over positions is ca (sum g - M cb - cc sum xhat);
         # under batch statistics cb = sum g / M and sum xhat = 0: the gradient of a bias in front of a train-mode
         # BatchNorm is zero (the reference's autograd returns rounding noise there); under running statistics
         # cb = cc = 0 and it is gamma invstd sum g = gamma invstd dbeta.
         nv = dbeta.shape[0]   # (cout_p, or cout where the pooled side has no padding channels)
-        if training:
-            db = torch.zeros(nv, dtype=torch.float32, device=dev)
+        if s.training:
+            db = torch.zeros(nv, dtype=torch.float32, device=x.device)
         else:
-            db = self.gamma_p.detach().float()[:nv] * stats[1][:nv] * dbeta
-        slab = (SLAB_C32 and dt == torch.bfloat16 and self.cin == 32 and self.cout == 64 and self.cin_p == 64 and self.cout_p == 64
-                and dy.data_ptr() % 16 == 0)
-
-        def weight_gradient():
-            """dW from (x, dy): the kernels below only read what the chain above has produced"""
-            dW = torch.empty_like(self.conv.weight)
-            if raw_ws:
-                ws = torch.empty(raw_ws, dtype=torch.uint8, device=dev)
-                if coef is not None:   # dy = the pool / ReLU / BatchNorm3d backward of dout, formed inside the kernel
-                    o.check(o.L.qt_conv3d_first_wgrad_fused(_lib.qt_dtype(dt), _ptr(x), _ptr(y), _ptr(dout), _ptr(arg), dout.shape[1],
-                                                            _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]), _ptr(coef),
-                                                            _ptr(dW), _ptr(ws), _c.c_size_t(raw_ws), B, T, H, W, _lib.stream_ptr()),
-                            "qt_conv3d_first_wgrad_fused")
-                    return dW
-                o.check(o.L.qt_conv3d_first_wgrad(_lib.qt_dtype(dt), _ptr(x), _ptr(dy), _ptr(dW), _ptr(ws), _c.c_size_t(raw_ws), B, T,
-                                                  H, W, _lib.stream_ptr()), "qt_conv3d_first_wgrad")
-                return dW
-            if self.first:
-                d = self._desc(dt, _lib.QT_CONV_FWD, T, B, H, W)
-                dw = torch.zeros(self.cout_p, 128, dtype=torch.float32, device=dev)
-                o.wgrad(d, _ptr(dy), _ptr(x), dw)
-            elif slab and x.data_ptr() % 16 == 0 and self._slab_wgrad_bytes(B, T, H, W):
-                # conv3d_block2: weight gradient on the slab-resident kernel (csrc/conv3d_slab.hip)
-                nws = self._slab_wgrad_bytes(B, T, H, W)
-                ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-                o.check(o.L.qt_conv3d_c32_wgrad(_lib.qt_dtype(dt), _ptr(x), x.shape[1], _ptr(dy), _ptr(dW), _ptr(ws), _c.c_size_t(nws), B,
-                                                T, H, W, _lib.stream_ptr()), "qt_conv3d_c32_wgrad")
-                return dW
-            else:
-                if x.shape[1] != self.cin_p:
-                    raise QtError(f"conv block: input rows of {x.shape[1]} channels, the tile weight gradient reads {self.cin_p}")
-                # one launch per frame tap over the contiguous range of frames the tap connects (the contraction runs over
-                # pixels: f32 sums, nothing accumulates through an activation map); with a workspace the bf16 build takes the
-                # tile-resident kernel and its fixed-order partial sums: deterministic, no float atomics
-                frame_in, frame_out = B * H * W * self.cin_p * esz, B * H * W * self.cout_p * esz
-                dw = torch.zeros(3, self.cout_p, 9, self.cin_p, dtype=torch.float32, device=dev)
-                for kt in range(3):
-                    dlo, slo, cnt = self._ranges(T, kt)   # forward: out[dlo + i] read in[slo + i]
-                    if cnt == 0:
-                        continue
-                    d2 = o_desc(dt, _lib.QT_CONV_FWD, cnt * B, H, W, self.cin_p, self.cout_p, 3, 1)
-                    o.wgrad(d2, _ptr(dy, dlo * frame_out), _ptr(x, slo * frame_in), dw[kt])
-            o.check(o.L.qt_unpack_conv3d_wgrad(_ptr(dw), _ptr(dW), self.cout, self.cin, self.cout_p, self.cin_p,
-                                               1 if self.first else 0, _lib.stream_ptr()), "qt_unpack_conv3d_wgrad")
-            return dW
-
+            db = self.gamma_p.detach().float()[:nv] * s.stats[1][:nv] * dbeta
+        slab = r.kernel == SLAB and dy.data_ptr() % 16 == 0
         # The weight gradient hangs off the chain  dout -> dy -> dx -> (next block): on the weight-gradient stream (wside) its
         # MFMA kernels run beside the byte-moving BatchNorm / pooling passes of the NEXT block's backward (round 4; the 2-D
         # plan's arrangement, csrc/plan.hip).  x and dy were allocated on the compute stream: recorded on the side stream so
         # that the caching allocator does not hand their memory out again while it still reads them.
-        if wside is not None:
-            for t_ in ((x, y, dout, arg, dy) + tuple(stats) if raw and coef is not None else (x, dy)):
-                t_.record_stream(wside.side)
-            with wside.fork():
-                dW = weight_gradient()
+        wside.reads(*((x, s.y, dout, s.arg, dy) + tuple(s.stats) if coef is not None else (x, dy)))
+        with wside.fork():
+            dW = self._weight_gradient(dt, s, x, dy, dout, coef, raw_ws, slab)
+        dx = self._data_gradient(dt, s, dy, dout, coef, slab, want_dx)
+        return dx, dW, self._vec_grad(db), self._vec_grad(dgamma), self._vec_grad(dbeta)
+
+    def _bn_pool_backward(self, dt, dout, s, cd, apply):
+        """d/d(block output) -> (dy, dgamma, dbeta) through MaxPool3d, ReLU and BatchNorm3d.  cd: channels per row of dy (None:
+        cout_p); apply = False: the coefficients in dy's place"""
+        o, dev = ops(), dout.device
+        T, B, H, W = s.shape
+        if s.route.fused_pool:   # (the pooled side's row width: 32 where block 2 runs on the slab kernels, else padded)
+            return o.pool_bn_backward(dt, dout, s.arg, s.out, s.ymax, s.y, s.stats, self.gamma_p, T, B, H, W, s.out.shape[1],
+                                      self.pool_t, dev, s.training, cy=32 if s.route.kernel == RAW else None, cd=cd, apply=apply)
+        da = dout
+        if self.pool_t:
+            da = torch.empty_like(s.act)
+            o.pool_bwd(dt, dout, s.arg, da, T, B, H, W, self.cout_p, self.pool_t)
+        return o.bn_backward(dt, da, s.act, s.y, s.stats, self.gamma_p, T * B * H * W, self.cout_p, dev, s.training)
+
+    def _weight_gradient(self, dt, s, x, dy, dout, coef, raw_ws, slab):
+        """dW from (x, dy): the kernels below only read what the chain in backward() has produced"""
+        o, dev = ops(), dout.device
+        T, B, H, W = s.shape
+        q, st = _lib.qt_dtype(dt), _lib.stream_ptr()
+        dW = torch.empty_like(self.conv.weight)
+        nws = raw_ws or (int(o.L.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W)) if slab and x.data_ptr() % 16 == 0 else 0)
+        if nws:
+            ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+            if coef is not None:   # dy = the pool / ReLU / BatchNorm3d backward of dout, formed inside the kernel
+                o.check(o.L.qt_conv3d_first_wgrad_fused(q, _ptr(x), _ptr(s.y), _ptr(dout), _ptr(s.arg), dout.shape[1], _ptr(s.stats[0]),
+                                                        _ptr(s.stats[1]), _ptr(s.stats[2]), _ptr(s.stats[3]), _ptr(coef), _ptr(dW),
+                                                        _ptr(ws), _c.c_size_t(nws), B, T, H, W, st), "qt_conv3d_first_wgrad_fused")
+            elif raw_ws:
+                o.check(o.L.qt_conv3d_first_wgrad(q, _ptr(x), _ptr(dy), _ptr(dW), _ptr(ws), _c.c_size_t(nws), B, T, H, W, st),
+                        "qt_conv3d_first_wgrad")
+            else:   # conv3d_block2: weight gradient on the slab-resident kernel (csrc/conv3d_slab.hip)
+                o.check(o.L.qt_conv3d_c32_wgrad(q, _ptr(x), x.shape[1], _ptr(dy), _ptr(dW), _ptr(ws), _c.c_size_t(nws), B, T, H, W, st),
+                        "qt_conv3d_c32_wgrad")
+            return dW
+        if self.first:
+            dw = torch.zeros(self.cout_p, 128, dtype=torch.float32, device=dev)
+            o.wgrad(self._desc(dt, _lib.QT_CONV_FWD, T, B, H, W), _ptr(dy), _ptr(x), dw)
         else:
-            dW = weight_gradient()
-        dx = None
-        if self.first and want_dx:
+            if x.shape[1] != self.cin_p:
+                raise QtError(f"conv block: input rows of {x.shape[1]} channels, the tile weight gradient reads {self.cin_p}")
+            # one launch per frame tap over the contiguous range of frames the tap connects (the contraction runs over
+            # pixels: f32 sums, nothing accumulates through an activation map); with a workspace the bf16 build takes the
+            # tile-resident kernel and its fixed-order partial sums: deterministic, no float atomics
+            esz = 2 if dt == torch.bfloat16 else 4
+            frame_in, frame_out = B * H * W * self.cin_p * esz, B * H * W * self.cout_p * esz
+            dw = torch.zeros(3, self.cout_p, 9, self.cin_p, dtype=torch.float32, device=dev)
+            for kt in range(3):
+                dlo, slo, cnt = self._ranges(T, kt)   # forward: out[dlo + i] read in[slo + i]
+                if cnt == 0:
+                    continue
+                d2 = _Ops.conv_desc(dt, _lib.QT_CONV_FWD, cnt * B, H, W, self.cin_p, self.cout_p, 3, 1)
+                o.wgrad(d2, _ptr(dy, dlo * frame_out), _ptr(x, slo * frame_in), dw[kt])
+        o.check(o.L.qt_unpack_conv3d_wgrad(_ptr(dw), _ptr(dW), self.cout, self.cin, self.cout_p, self.cin_p,
+                                           1 if self.first else 0, st), "qt_unpack_conv3d_wgrad")
+        return dW
+
+    def _data_gradient(self, dt, s, dy, dout, coef, slab, want_dx):
+        """d/d(block input): one 27-tap launch, conv3d_block2's on the slab-resident kernel (two passes); first block: the clip
+        gradient where it is wanted, else None"""
+        o, dev = ops(), dout.device
+        T, B, H, W = s.shape
+        if self.first:
+            if not want_dx:
+                return None
             # the clip gradient (csrc/conv3d_first_dgrad.hip) reads dy in 32-channel rows.  Where the weight gradient formed dy
             # inside its own kernel it is written out here from the same coefficients; rows padded to 64 channels (the packed
             # first layer: f32 build, shapes the raw kernels do not take) are narrowed
             if coef is not None:
-                dy32 = o.pool_bn_apply(dt, dout, arg, pooled, y, stats, coef, T, B, H, W, pooled.shape[1], self.pool_t, dev,
+                dy32 = o.pool_bn_apply(dt, dout, s.arg, s.out, s.y, s.stats, coef, T, B, H, W, s.out.shape[1], self.pool_t, dev,
                                        cy=32, cd=32)
             else:
                 dy32 = dy if dy.shape[1] == 32 else dy[:, :32].contiguous()
-            dx = o.conv3d_first_dgrad(dt, dy32, self.conv.weight.detach(), B, T, H, W)
-        if not self.first:   # data gradient: one 27-tap launch; conv3d_block2's on the slab-resident kernel (two passes)
-            dx = torch.empty(rows, x.shape[1], dtype=dt, device=dev)   # (rows as wide as the input's: the previous block's pooled map)
-            nscr = 0
-            if slab:
-                o.L.qt_conv3d_c32_dgrad_scratch_bytes.restype = _c.c_size_t
-                nscr = int(o.L.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W))
-            if nscr:
-                scr = torch.empty(nscr, dtype=torch.uint8, device=dev)
-                o.conv3d_c32_dgrad(dt, dy, self.wd, dx, dx.shape[1], scr, nscr, B, T, H, W, flops=2.0 * rows * 27 * self.cin * self.cout,
-                                   nbytes=esz * (rows * (self.cin + self.cout_p) + 27.0 * self.cin * self.cout_p))
-            else:
-                if dx.shape[1] != self.cin_p:
-                    raise QtError(f"conv block: input rows of {dx.shape[1]} channels, the implicit GEMM writes {self.cin_p}")
-                dd = self._desc(dt, _lib.QT_CONV_DGRAD, T, B, H, W)
-                o.igemm(dd, _ptr(dy), _ptr(self.wd), _ptr(dx), flops=2.0 * rows * 27 * self.cin * self.cout,
-                        nbytes=esz * (rows * (self.cin_p + self.cout_p) + 27.0 * self.cin_p * self.cout_p))
-        return dx, dW, self._vec_grad(db), self._vec_grad(dgamma), self._vec_grad(dbeta)
-
-
-def o_desc(dt, mode, images, h, w, k_per_tap, n_out, k, pad):
-    return _Ops.conv_desc(dt, mode, images, h, w, k_per_tap, n_out, k, pad)
+            return o.conv3d_first_dgrad(dt, dy32, self.conv.weight.detach(), B, T, H, W)
+        rows, esz = T * B * H * W, 2 if dt == torch.bfloat16 else 4
+        fl = 2.0 * rows * 27 * self.cin * self.cout
+        dx = torch.empty(rows, s.x.shape[1], dtype=dt, device=dev)   # (rows as wide as the input's: the previous block's pooled map)
+        nscr = int(o.L.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W)) if slab else 0
+        if nscr:
+            scr = torch.empty(nscr, dtype=torch.uint8, device=dev)
+            o.conv3d_c32_dgrad(dt, dy, self.wd, dx, dx.shape[1], scr, nscr, B, T, H, W, flops=fl,
+                               nbytes=esz * (rows * (self.cin + self.cout_p) + 27.0 * self.cin * self.cout_p))
+        else:
+            if dx.shape[1] != self.cin_p:
+                raise QtError(f"conv block: input rows of {dx.shape[1]} channels, the implicit GEMM writes {self.cin_p}")
+            o.igemm(self._desc(dt, _lib.QT_CONV_DGRAD, T, B, H, W), _ptr(dy), _ptr(self.wd), _ptr(dx), flops=fl,
+                    nbytes=esz * (rows * (self.cin_p + self.cout_p) + 27.0 * self.cin_p * self.cout_p))
+        return dx
 
 
 class _Lstm:
@@ -748,6 +769,7 @@ class _ClipModel(nn.Module):
     def _init_clip_state(self, compute_dtype):
         self.compute_dtype = compute_dtype or default_compute_dtype()
         self._blocks = None
+        self._fwd_counter = 0
 
     def _check_inputs(self, image_sequence, numerical_sequence, need_numerical):
         if image_sequence.dim() != 5 or image_sequence.shape[2] != 3:
@@ -792,7 +814,7 @@ class _ClipModel(nn.Module):
         key = tuple((id(c), id(b), p, f) for c, b, p, f in specs)
         if self.__dict__.get("_blocks_key") != key:
             blocks = [_ConvBlock(c, b, p, f) for c, b, p, f in specs]
-            for prev, nxt in zip(blocks, blocks[1:]):   # conv3d_block1 -> conv3d_block2 (32 -> 64): see _pooled_width
+            for prev, nxt in zip(blocks, blocks[1:]):   # conv3d_block1 -> conv3d_block2 (32 -> 64): see _ConvBlock.route
                 prev.narrow_out = prev.first and bool(prev.pool_t) and nxt.cin == 32 and nxt.cout == 64
             self.__dict__["_blocks"] = blocks
             self.__dict__["_blocks_key"] = key
@@ -816,6 +838,82 @@ class _ClipModel(nn.Module):
         # every activation and never took the fused eval kernels
         self._grad_mode = torch.is_grad_enabled()
         return _ClipFunction.apply(self, image_sequence, numerical_sequence, *params)
+
+    # ---- the parts of the graph both models share ----------------------------------------------------------------
+    def _forward_impl(self, images, numerical, keep):
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.training else 0
+        logits, state = self._forward_graph(images, numerical, keep, seed, self.dropout_rate if self.training else 0.0)
+        self._fwd_counter += 1
+        self._saved = state if keep else None
+        return logits
+
+    def _backward_impl(self, dlogits, emit=None, want_dx=False):
+        """emit(g, names, phase): data-parallel hand-over of the gradients `names` of dict g, final as of this point.
+        want_dx: the clip gradient is left in self._dclip"""
+        self.__dict__["_bwd_count"] = self.__dict__.get("_bwd_count", 0) + 1   # gradients exist: packed weights may go stale
+        g = {}
+        dclip = self._backward_graph(self._saved, dlogits, g, emit, want_dx)
+        self._saved = None
+        self.__dict__["_dclip"] = dclip if want_dx else None   # (the first block's data gradient)
+        return [g.get(n) for n, _ in self.named_parameters()]
+
+    def _conv_forward(self, images, keep, ld):
+        """the conv blocks on the f32 clip, then nn.AdaptiveAvgPool3d((1,1,1)) + flatten into the first columns of an f32
+        [B][ld] matrix -> (that matrix, last block's input and output maps, (t, h, w), blocks, their _Saved records)"""
+        o, dev, dt = ops(), images.device, self.compute_dtype
+        B, t, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[3]), int(images.shape[4])
+        blocks = self._conv_blocks()
+        x, saved = images, []   # conv3d_block1 reads the f32 clip itself (or packs it: _ConvBlock.forward)
+        for blk in blocks:
+            blk.pack(dt, keep, self.__dict__.get("_bwd_count", 0))
+            x_in = x
+            x, (t, h, w), sv = blk.forward(dt, x, t, B, h, w, self.training, keep)
+            saved.append(sv)
+        fused = torch.empty(B, ld, dtype=torch.float32, device=dev)
+        o.check(o.L.qt_avgpool_tb(_lib.qt_dtype(dt), _ptr(x), _ptr(fused), t, B, h * w, blocks[-1].cout_p, ld, 0,
+                                  _lib.stream_ptr()), "qt_avgpool_tb")
+        return fused, x_in, x, (t, h, w), blocks, saved
+
+    def _classify(self, fused, seed, p):
+        """self.classifier (Linear - ReLU - Dropout - Linear) on f32 [B][ld] -> (logits, the hidden activations)"""
+        B, ld = fused.shape
+        nh = self.classifier[0].weight.shape[0]
+        hid = torch.empty(B, nh, dtype=torch.float32, device=fused.device)
+        _Head.linear_fwd(fused, ld, 0, self.classifier[0], B, hid, nh, 0, 1)
+        if p > 0:
+            ops().dropout(hid, B, nh, nh, 0, seed + 2, p)
+        logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=fused.device)
+        _Head.linear_fwd(hid, nh, 0, self.classifier[3], B, logits, self.num_classes, 0, 0)
+        return logits, hid
+
+    def _classify_backward(self, st, dlogits, g):
+        """the classifier's four gradients into g -> d/d(fused) [B][ld]"""
+        (B, ld), nh = st.fused.shape, st.hid.shape[1]
+        dhid = torch.empty(B, nh, dtype=torch.float32, device=dlogits.device)
+        g["classifier.3.weight"], g["classifier.3.bias"] = _Head.linear_bwd(dlogits, self.num_classes, st.hid, nh, self.classifier[3],
+                                                                            B, dhid, nh)
+        _Head.relu_dropout_bwd(dhid, st.hid, B * nh, st.mul)
+        dfused = torch.empty(B, ld, dtype=torch.float32, device=dlogits.device)
+        g["classifier.0.weight"], g["classifier.0.bias"] = _Head.linear_bwd(dhid, nh, st.fused, ld, self.classifier[0], B, dfused, ld)
+        return dfused
+
+    def _conv_backward(self, st, dfused, g, names, want_dx, emit=None, early=None):
+        """the average pool's backward, then the conv blocks (parameter prefixes `names`) from the last to the first, their
+        weight gradients on a stream of their own -> (d/d(clip) or None, that stream's _Side: the caller joins it).
+        early = (prefix, phase): that block's gradients are handed to emit as soon as they are final"""
+        o, dt, dev = ops(), self.compute_dtype, dfused.device
+        (t, h, w), B, C_last = st.thw, dfused.shape[0], st.blocks[-1].cout_p
+        dout = torch.empty(t * B * h * w, C_last, dtype=dt, device=dev)
+        o.check(o.L.qt_avgpool_tb_bwd(_lib.qt_dtype(dt), _ptr(dfused), _ptr(dout), t, B, h * w, C_last, dfused.shape[1], 0,
+                                      _lib.stream_ptr()), "qt_avgpool_tb_bwd")
+        wside = _Side(dev, 1, WGRAD_SIDE)
+        for blk, sv, nm in zip(reversed(st.blocks), reversed(st.saved), reversed(names)):
+            dout, dW, db, dgamma, dbeta = blk.backward(dt, dout, sv, wside, want_dx and blk.first)
+            g[f"{nm}.0.weight"], g[f"{nm}.0.bias"], g[f"{nm}.1.weight"], g[f"{nm}.1.bias"] = dW, db, dgamma, dbeta
+            if emit is not None and early is not None and nm == early[0]:
+                wside.join(dW)   # (the bucket is packed on the compute stream)
+                emit(g, [k for k in g if k.startswith(nm + ".")], early[1])
+        return dout, wside
 
 
 class _ClipFunction(torch.autograd.Function):
@@ -879,26 +977,21 @@ class _Head:
 
     @staticmethod
     def linear_fwd(x, x_ld, x_off, lin, rows, out, out_ld, out_off, relu):
-        ops().linear(x, x_ld, x_off, lin.weight.detach(), lin.bias.detach(), rows, out, out_ld, out_off, relu)
+        """out[r, out_off:out_off+N] = relu?(x[r, x_off:x_off+K] W^T + b)  (nn.Linear; W [N,K])"""
+        N, K = lin.weight.shape
+        ops().gemm(rows, N, K, x, x_ld, 1, lin.weight.detach(), K, 1, out, out_ld, lin.bias.detach(), relu, x_off, out_off)
 
     @staticmethod
-    def linear_bwd(dy, dy_ld, dy_off, x, x_ld, x_off, lin, rows, want_dx, dx=None, dx_ld=0, dx_off=0):
+    def linear_bwd(dy, dy_ld, x, x_ld, lin, rows, dx, dx_ld):
+        """nn.Linear backward on f32 rows -> (dW, db); dx [rows][dx_ld] is written"""
         o = ops()
         W = lin.weight.detach()
         N, K = W.shape
-        dev = W.device
-        dW = torch.empty(N, K, dtype=torch.float32, device=dev)
-        db = torch.empty(N, dtype=torch.float32, device=dev)
-        # dW[n][k] = sum_r dy[r][dy_off + n] * x[r][x_off + k]: A = dy^T (row stride 1, k stride dy_ld)
-        d = _GemmDesc(N, K, rows, _lib.QT_F32, _lib.QT_F32, _lib.QT_F32, 1, dy_ld, 1, x_ld, K, 0, 0)
-        o.check(o.L.qt_gemm_small(_c.byref(d), _ptr(dy, dy_off * 4), _ptr(x, x_off * 4), None, _ptr(dW), _lib.stream_ptr()),
-                "qt_gemm_small")
-        o.check(o.L.qt_col_sum(_lib.QT_F32, _ptr(dy, dy_off * 4), _c.c_longlong(rows), N, dy_ld, _ptr(db), 0, _lib.stream_ptr()),
-                "qt_col_sum")
-        if want_dx:   # dx[r][dx_off + k] = sum_n dy[r][dy_off + n] * W[n][k]
-            d = _GemmDesc(rows, K, N, _lib.QT_F32, _lib.QT_F32, _lib.QT_F32, dy_ld, 1, 1, K, dx_ld, 0, 0)
-            o.check(o.L.qt_gemm_small(_c.byref(d), _ptr(dy, dy_off * 4), _ptr(W), None, _ptr(dx, dx_off * 4), _lib.stream_ptr()),
-                    "qt_gemm_small")
+        dW = torch.empty(N, K, dtype=torch.float32, device=W.device)
+        db = torch.empty(N, dtype=torch.float32, device=W.device)
+        o.gemm(N, K, rows, dy, 1, dy_ld, x, 1, x_ld, dW, K)       # dW[n][k] = sum_r dy[r][n] * x[r][k]: A = dy^T
+        o.col_sum(torch.float32, dy, rows, N, dy_ld, db)
+        o.gemm(rows, K, N, dy, dy_ld, 1, W, 1, K, dx, dx_ld)      # dx[r][k] = sum_n dy[r][n] * W[n][k]
         return dW, db
 
     @staticmethod
@@ -953,7 +1046,6 @@ class Quadtree3DCNN(_ClipModel):
                                         M.Linear(w // 2, num_classes))
         self.gradients = None
         self.activations = None
-        self._fwd_counter = 0
         self._init_clip_state(compute_dtype)
         if self.numerical_lstm_output_dim not in (256, 188, 64):
             raise ValueError("the gfx950 LSTM kernel is instantiated for hidden sizes 256, 188 (= 4 x 47) and 64")
@@ -981,129 +1073,72 @@ class Quadtree3DCNN(_ClipModel):
                          numerical_sequence_input.contiguous().float() if fusion else None)
 
     # ---- the graph --------------------------------------------------------------------------------------------
-    def _forward_impl(self, images, numerical, keep):
-        o, dev, dt = ops(), images.device, self.compute_dtype
-        B, T, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[3]), int(images.shape[4])
-        training = self.training
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if training else 0
-        blocks = self._conv_blocks()
+    _BLOCK_NAMES = ("conv3d_block1", "conv3d_block2", "conv3d_block3", "conv3d_block4_new", "conv3d_final_features")
+
+    def _forward_graph(self, images, numerical, keep, seed, p):
+        dev = images.device
+        B, T = int(images.shape[0]), int(images.shape[1])
         fusion = self.mode == 'quadtree_3d_fusion'
-        lstm = last = side = None
+        lstm = last = None
+        side = _Side(dev, 0, fusion and LSTM_SIDE)
         if fusion:   # the numerical branch first: on the second stream it runs under the conv blocks
             lstm = _Lstm(self.numerical_lstm)
-            side = _Side(dev) if LSTM_SIDE else None
-            if side is not None:
-                with side.fork():
-                    hout = lstm.forward(numerical.view(B * T, -1), B, T, training, seed)
-                    last = hout.view(B, T, lstm.H)[:, -1, :].contiguous()
-            else:
-                hout = lstm.forward(numerical.view(B * T, -1), B, T, training, seed)
+            with side.fork():
+                hout = lstm.forward(numerical.view(B * T, -1), B, T, self.training, seed)
                 last = hout.view(B, T, lstm.H)[:, -1, :].contiguous()
-        x = images   # conv3d_block1 reads the f32 clip itself (or packs it: _ConvBlock.forward)
-        saved_blocks = []
-        t, h, w = T, H, W
-        for blk in blocks:
-            blk.pack(dt, keep, self.__dict__.get("_bwd_count", 0))
-            x_in = x
-            x, (t, h, w), sv = blk.forward(dt, x, t, B, h, w, training, keep)
-            saved_blocks.append(sv)
+        F_img, ld = self.cnn_3d_feature_dim, self.final_classifier_input_dim
+        fused, x_in, x, (t, h, w), blocks, saved = self._conv_forward(images, keep, ld)
         final = self.conv3d_final_features
         if final._forward_hooks:
             # Grad-CAM (3dcnn/models.py:178-182): the module never runs, its forward hooks get the tensors torch would have
             # passed -- block 4's output and the block's post-BatchNorm / ReLU output as f32 [B,C,t,h,w] (no pool: same t, h, w)
             inp = self._ncthw(x_in, B, t, h, w, blocks[-1].cin)
-            out = self._ncthw(x, B, t, h, w, self.cnn_3d_feature_dim)
+            out = self._ncthw(x, B, t, h, w, F_img)
             for hook in list(final._forward_hooks.values()):
                 hook(final, (inp,), out)
-        F_img = self.cnn_3d_feature_dim
-        ld = self.final_classifier_input_dim
-        fused = torch.empty(B, ld, dtype=torch.float32, device=dev)
-        o.check(o.L.qt_avgpool_tb(_lib.qt_dtype(dt), _ptr(x), _ptr(fused), t, B, h * w, blocks[-1].cout_p, ld, 0,
-                                  _lib.stream_ptr()), "qt_avgpool_tb")
-        p = self.dropout_rate if training else 0.0
         if fusion:
-            if side is not None:
-                side.join(last)
-            Hn = lstm.H
-            _Head.linear_fwd(last, Hn, 0, self.numerical_projection[0], B, fused, ld, F_img, 1)
+            side.join(last)
+            _Head.linear_fwd(last, lstm.H, 0, self.numerical_projection[0], B, fused, ld, F_img, 1)
             if p > 0:
-                o.dropout(fused, B, self.numerical_final_dim, ld, F_img, seed + 1, p)
-        hid = torch.empty(B, ld // 2, dtype=torch.float32, device=dev)
-        _Head.linear_fwd(fused, ld, 0, self.classifier[0], B, hid, ld // 2, 0, 1)
-        if p > 0:
-            o.dropout(hid, B, ld // 2, ld // 2, 0, seed + 2, p)
-        logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=dev)
-        _Head.linear_fwd(hid, ld // 2, 0, self.classifier[3], B, logits, self.num_classes, 0, 0)
-        self._fwd_counter += 1
-        self._saved = (blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, last, p) if keep else None
-        return logits
+                ops().dropout(fused, B, self.numerical_final_dim, ld, F_img, seed + 1, p)
+        logits, hid = self._classify(fused, seed, p)
+        return logits, _State(blocks, saved, (t, h, w), fused, hid, lstm, last, 1.0 / (1.0 - p), T)
 
-    def _backward_impl(self, dlogits, emit=None, want_dx=False):
-        """emit(g, names, phase): data-parallel hand-over of the gradients `names` of dict g, final as of this point.
-        want_dx: the clip gradient is left in self._dclip"""
-        self.__dict__["_bwd_count"] = self.__dict__.get("_bwd_count", 0) + 1   # gradients exist: packed weights may go stale
-        o, dt = ops(), self.compute_dtype
-        blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, last, p = self._saved
-        dev = dlogits.device
-        ld, F_img = self.final_classifier_input_dim, self.cnn_3d_feature_dim
-        mul = 1.0 / (1.0 - p) if p > 0 else 1.0
-        g = {}
-        dhid = torch.empty(B, ld // 2, dtype=torch.float32, device=dev)
-        g["classifier.3.weight"], g["classifier.3.bias"] = _Head.linear_bwd(
-            dlogits, self.num_classes, 0, hid, ld // 2, 0, self.classifier[3], B, True, dhid, ld // 2, 0)
-        _Head.relu_dropout_bwd(dhid, hid, B * (ld // 2), mul)
-        dfused = torch.empty(B, ld, dtype=torch.float32, device=dev)
-        g["classifier.0.weight"], g["classifier.0.bias"] = _Head.linear_bwd(
-            dhid, ld // 2, 0, fused, ld, 0, self.classifier[0], B, True, dfused, ld, 0)
+    def _backward_graph(self, st, dlogits, g, emit, want_dx):
+        dev, lstm = dlogits.device, st.lstm
+        B, F_img = dlogits.shape[0], self.cnn_3d_feature_dim
+        dfused = self._classify_backward(st, dlogits, g)
+        side = _Side(dev, 0, lstm is not None and LSTM_SIDE)
         if lstm is not None:
             Hn, Fn = lstm.H, self.numerical_final_dim
             dproj = dfused[:, F_img:].contiguous()
-            _Head.relu_dropout_bwd(dproj, fused[:, F_img:].contiguous(), B * Fn, mul)
+            _Head.relu_dropout_bwd(dproj, st.fused[:, F_img:].contiguous(), B * Fn, st.mul)
             dlast = torch.empty(B, Hn, dtype=torch.float32, device=dev)
             g["numerical_projection.0.weight"], g["numerical_projection.0.bias"] = _Head.linear_bwd(
-                dproj, Fn, 0, last, Hn, 0, self.numerical_projection[0], B, True, dlast, Hn, 0)
-            side = _Side(dev) if LSTM_SIDE else None
-            if side is not None:   # (joined after the image branch's backward)
-                with side.fork():
-                    lg = lstm.backward(dlast, B, T)
-            else:
-                lg = lstm.backward(dlast, B, T)
+                dproj, Fn, st.last, Hn, self.numerical_projection[0], B, dlast, Hn)
+            with side.fork():   # (joined after the image branch's backward)
+                lg = lstm.backward(dlast, B, st.T)
             for k in range(lstm.layers):
                 for j, nm in enumerate(("weight_ih", "weight_hh", "bias_ih", "bias_hh")):
                     g[f"numerical_lstm.{nm}_l{k}"] = lg[4 * k + j]
-        else:
-            side = None
         final = self.conv3d_final_features
         if final._backward_hooks:
             # its output only feeds the global average pool: d(loss)/d(output) is dfused[:, :F] / (t h w) at every position
+            t, h, w = st.thw
             gout = (dfused[:, :F_img] / float(t * h * w)).view(B, F_img, 1, 1, 1).expand(B, F_img, t, h, w).contiguous()
             for hook in list(final._backward_hooks.values()):
                 hook(final, (None,), (gout,))
         if emit is not None:   # bucket 1: the dense head (the LSTM's gradients are still running on the side stream)
             emit(g, [k for k in g if k.startswith(("classifier.", "numerical_projection."))], 1)
-        # image branch
-        C_last = blocks[-1].cout_p
-        dout = torch.empty(t * B * h * w, C_last, dtype=dt, device=dev)
-        o.check(o.L.qt_avgpool_tb_bwd(_lib.qt_dtype(dt), _ptr(dfused), _ptr(dout), t, B, h * w, C_last, ld, 0, _lib.stream_ptr()),
-                "qt_avgpool_tb_bwd")
-        names = ("conv3d_block1", "conv3d_block2", "conv3d_block3", "conv3d_block4_new", "conv3d_final_features")
-        wside = _Side(dev, 1) if WGRAD_SIDE else None
-        for blk, sv, nm in zip(reversed(blocks), reversed(saved_blocks), reversed(names)):
-            dout, dW, db, dgamma, dbeta = blk.backward(dt, dout, sv, wside, want_dx and blk.first)
-            g[f"{nm}.0.weight"], g[f"{nm}.0.bias"], g[f"{nm}.1.weight"], g[f"{nm}.1.bias"] = dW, db, dgamma, dbeta
-            if emit is not None and nm == "conv3d_final_features":   # bucket 2: 7.1 M of the 9.9 M parameters, ready first
-                if wside is not None:
-                    wside.join(dW)   # (the bucket is packed on the compute stream)
-                emit(g, [k for k in g if k.startswith(nm + ".")], 2)
-        if wside is not None:
-            wside.join(*[g[f"{nm}.0.weight"] for nm in names])
-        if side is not None:
+        # image branch; bucket 2: conv3d_final_features, 7.1 M of the 9.9 M parameters, ready first
+        names = self._BLOCK_NAMES
+        dclip, wside = self._conv_backward(st, dfused, g, names, want_dx, emit, (names[-1], 2))
+        wside.join(*[g[f"{nm}.0.weight"] for nm in names])
+        if lstm is not None:
             side.join(*lg)
         if emit is not None:   # bucket 3: conv blocks 4 .. 1 and the LSTM (joined above)
             emit(g, [k for k in g if k.startswith(("conv3d_block", "numerical_lstm."))], 4)
-        self._saved = None
-        self.__dict__["_dclip"] = dout if want_dx else None   # (the first block's data gradient)
-        return [g.get(n) for n, _ in self.named_parameters()]
+        return dclip
 
 
 class Ji3DCNN(_ClipModel):
@@ -1123,7 +1158,6 @@ class Ji3DCNN(_ClipModel):
             conv_3d_block(64, 128), M.AdaptiveAvgPool3d((1, 1, 1)))
         self.numerical_lstm = M.LSTM(numerical_feature_dim, 64, num_layers=1, batch_first=True)
         self.classifier = nn.Sequential(M.Linear(128 + 64, 128), M.ReLU(), M.Dropout(dropout_rate), M.Linear(128, num_classes))
-        self._fwd_counter = 0
         self._init_clip_state(compute_dtype)
 
     def _conv_blocks(self):
@@ -1135,69 +1169,25 @@ class Ji3DCNN(_ClipModel):
         self._check_inputs(image_sequence, numerical_sequence, True)
         return self._run(image_sequence.contiguous().float(), numerical_sequence.contiguous().float())
 
-    def _forward_impl(self, images, numerical, keep):
-        o, dev, dt = ops(), images.device, self.compute_dtype
-        B, T, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[3]), int(images.shape[4])
-        training = self.training
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if training else 0
-        blocks = self._conv_blocks()
-        x = images   # conv3d_block1 reads the f32 clip itself (or packs it: _ConvBlock.forward)
-        saved_blocks = []
-        t, h, w = T, H, W
-        for blk in blocks:
-            blk.pack(dt, keep, self.__dict__.get("_bwd_count", 0))
-            x, (t, h, w), sv = blk.forward(dt, x, t, B, h, w, training, keep)
-            saved_blocks.append(sv)
-        ld = 128 + 64
-        fused = torch.empty(B, ld, dtype=torch.float32, device=dev)
-        o.check(o.L.qt_avgpool_tb(_lib.qt_dtype(dt), _ptr(x), _ptr(fused), t, B, h * w, blocks[-1].cout_p, ld, 0,
-                                  _lib.stream_ptr()), "qt_avgpool_tb")
-        lstm = _Lstm(self.numerical_lstm)
-        hout = lstm.forward(numerical.view(B * T, -1), B, T, training, seed)
+    def _forward_graph(self, images, numerical, keep, seed, p):
+        B, T = int(images.shape[0]), int(images.shape[1])
+        fused, _, _, thw, blocks, saved = self._conv_forward(images, keep, 128 + 64)
+        lstm = _Lstm(self.numerical_lstm)   # (in line, after the visual stream)
+        hout = lstm.forward(numerical.view(B * T, -1), B, T, self.training, seed)
         fused[:, 128:].copy_(hout.view(B, T, 64)[:, -1, :])      # torch.cat((v_out, n_out), dim=1)
-        p = self.dropout_rate if training else 0.0
-        hid = torch.empty(B, 128, dtype=torch.float32, device=dev)
-        _Head.linear_fwd(fused, ld, 0, self.classifier[0], B, hid, 128, 0, 1)
-        if p > 0:
-            o.dropout(hid, B, 128, 128, 0, seed + 2, p)
-        logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=dev)
-        _Head.linear_fwd(hid, 128, 0, self.classifier[3], B, logits, self.num_classes, 0, 0)
-        self._fwd_counter += 1
-        self._saved = (blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, p) if keep else None
-        return logits
+        logits, hid = self._classify(fused, seed, p)
+        return logits, _State(blocks, saved, thw, fused, hid, lstm, None, 1.0 / (1.0 - p), T)
 
-    def _backward_impl(self, dlogits, emit=None, want_dx=False):
-        self.__dict__["_bwd_count"] = self.__dict__.get("_bwd_count", 0) + 1   # gradients exist: packed weights may go stale
-        o, dt = ops(), self.compute_dtype
-        blocks, saved_blocks, (t, h, w, B, T), fused, hid, lstm, p = self._saved
-        dev = dlogits.device
-        ld = 128 + 64
-        mul = 1.0 / (1.0 - p) if p > 0 else 1.0
-        g = {}
-        dhid = torch.empty(B, 128, dtype=torch.float32, device=dev)
-        g["classifier.3.weight"], g["classifier.3.bias"] = _Head.linear_bwd(
-            dlogits, self.num_classes, 0, hid, 128, 0, self.classifier[3], B, True, dhid, 128, 0)
-        _Head.relu_dropout_bwd(dhid, hid, B * 128, mul)
-        dfused = torch.empty(B, ld, dtype=torch.float32, device=dev)
-        g["classifier.0.weight"], g["classifier.0.bias"] = _Head.linear_bwd(
-            dhid, 128, 0, fused, ld, 0, self.classifier[0], B, True, dfused, ld, 0)
-        lg = lstm.backward(dfused[:, 128:].contiguous(), B, T)
+    def _backward_graph(self, st, dlogits, g, emit, want_dx):
+        dfused = self._classify_backward(st, dlogits, g)
+        lg = st.lstm.backward(dfused[:, 128:].contiguous(), dlogits.shape[0], st.T)
         for j, nm in enumerate(("weight_ih", "weight_hh", "bias_ih", "bias_hh")):
             g[f"numerical_lstm.{nm}_l0"] = lg[j]
         if emit is not None:   # bucket 1: classifier + LSTM (this model's LSTM runs on the compute stream)
             emit(g, list(g), 1)
-        C_last = blocks[-1].cout_p
-        dout = torch.empty(t * B * h * w, C_last, dtype=dt, device=dev)
-        o.check(o.L.qt_avgpool_tb_bwd(_lib.qt_dtype(dt), _ptr(dfused), _ptr(dout), t, B, h * w, C_last, ld, 0, _lib.stream_ptr()),
-                "qt_avgpool_tb_bwd")
-        wside = _Side(dev, 1) if WGRAD_SIDE else None
-        for blk, sv, nm in zip(reversed(blocks), reversed(saved_blocks), ("visual_stream.4", "visual_stream.2", "visual_stream.0")):
-            dout, dW, db, dgamma, dbeta = blk.backward(dt, dout, sv, wside, want_dx and blk.first)
-            g[f"{nm}.0.weight"], g[f"{nm}.0.bias"], g[f"{nm}.1.weight"], g[f"{nm}.1.bias"] = dW, db, dgamma, dbeta
-        if wside is not None:
-            wside.join(*[g[f"{nm}.0.weight"] for nm in ("visual_stream.4", "visual_stream.2", "visual_stream.0")])
+        names = ("visual_stream.0", "visual_stream.2", "visual_stream.4")
+        dclip, wside = self._conv_backward(st, dfused, g, names, want_dx)
+        wside.join(*[g[f"{nm}.0.weight"] for nm in reversed(names)])
         if emit is not None:   # bucket 2: the three conv blocks (0.3 M parameters)
             emit(g, [k for k in g if k.startswith("visual_stream.")], 2)
-        self._saved = None
-        self.__dict__["_dclip"] = dout if want_dx else None   # (the first block's data gradient)
-        return [g.get(n) for n, _ in self.named_parameters()]
+        return dclip

@@ -599,7 +599,7 @@ def test_quadtree3d_config4_size_matches_oracle():
 
 def test_block1_pooled_map_in_32_channel_rows(monkeypatch):
     """Round 4: where conv3d_block2 runs on the slab kernels, conv3d_block1's pooled map, its argmax / raw-value companions and
-    the gradient coming back are 32-channel rows (video3d._ConvBlock._pooled_width) instead of rows padded to 64: the same
+    the gradient coming back are 32-channel rows (video3d._ConvBlock.route) instead of rows padded to 64: the same
     forward bits, and the same gradients up to the order of the BatchNorm-backward partial sums."""
     dev = _dev()
     v3d = pkg("video3d")
