@@ -364,6 +364,34 @@ int qt_loss_forward(const qt_loss_desc* desc, const float* logits, long long ld,
 int qt_loss_backward(const qt_loss_desc* desc, const float* logits, long long ld, const long long* labels, long long rows, int C,
                      const float* row_state, const double* stats, const float* grad_out, float* dlogits, long long ld_d,
                      void* stream);
+/* Frame preprocessing: what the reference's loaders do per image on the host (RandomResizedCrop / Resize -> ToTensor ->
+ * Normalize, RandomHorizontalFlip; experiment/test_on_video_cnn.py:228-254, cnn+lstm/prepare_sequential_dataset.py:30-33,
+ * 3dcnn/dataloaders.py:99-102), from decoded uint8 frames to the f32 [batch][3][out_h][out_w] tensor the models take, in one
+ * launch.  A clip [B][T][H][W][3] -> [B][T][3][h][w] is the same call with batch = B * T.
+ * Per image: crop `box`, resize the crop to out_h x out_w with torch's antialiased bilinear rule
+ * (interpolate(mode='bilinear', antialias=True); PIL's BILINEAR resize without its uint8 rounding between the two passes:
+ * at most one grey level away), mirror the columns where flips[b] != 0, then (v / 255 - mean[c]) * inv_std[c].
+ * For an axis of crop length `in` and output length `out`: scale = in / out, support = max(scale, 1), center = scale (i + 0.5),
+ * taps j in [max(floor(center - support + 0.5), 0), min(floor(center + support + 0.5), in)) relative to the crop, raw weight
+ * max(0, 1 - |(j - center + 0.5) / support|), divided by their sum; no pixel outside the box is read.
+ * boxes and flips are read on the device: nothing is synchronised, nothing allocated, no atomics, no intermediate in HBM,
+ * the same bits on every run.  A box that is not inside its frame (or has height < 1 or width < 1) cannot be refused by the
+ * host: that image's output is all NaN, nothing of its frame is read, the other images are unaffected.
+ * QT_ERR_INVALID_ARG (before any device call) for non-positive sizes, strides smaller than a row / an image, null or
+ * misaligned pointers; QT_ERR_UNSUPPORTED (before any launch) for a frame more than 24 x the output on an axis (the
+ * downscale limit: the taps of a tile must fit one workgroup's LDS) and for sizes above 2^22. */
+typedef struct qt_preprocess_desc {
+  int batch, src_h, src_w;          /* frames are uint8 HWC, 3 channels, interleaved */
+  long long src_row_stride;         /* bytes, >= 3*src_w */
+  long long src_image_stride;       /* bytes, >= src_h*src_row_stride */
+  int out_h, out_w;
+  int bgr;                          /* 1: source channel order is B,G,R (cv2 frames); output is always R,G,B planes */
+  float mean[3], inv_std[3];        /* per output channel (R,G,B) */
+} qt_preprocess_desc;
+int qt_preprocess_u8(const qt_preprocess_desc* desc, const unsigned char* src,
+                     const int* boxes,          /* device, [batch][4] = top,left,height,width; NULL = whole frame */
+                     const unsigned char* flips,/* device, [batch], nonzero = mirror left-right; NULL = none */
+                     float* dst, long long dst_image_stride /* floats, >= 3*out_h*out_w */, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of
