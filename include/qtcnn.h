@@ -392,6 +392,48 @@ int qt_preprocess_u8(const qt_preprocess_desc* desc, const unsigned char* src,
                      const int* boxes,          /* device, [batch][4] = top,left,height,width; NULL = whole frame */
                      const unsigned char* flips,/* device, [batch], nonzero = mirror left-right; NULL = none */
                      float* dst, long long dst_image_stride /* floats, >= 3*out_h*out_w */, void* stream);
+/* Training augmentations: the middle of the reference's training transform (Quadtree_from scratch/dataloader.py:29-37,
+ * resnet/dataloader.py:32-40), ColorJitter -> RandomRotation -> GaussianBlur -> Normalize, on f32 [batch][3][h][w] planes with
+ * values in [0, 1] (what qt_preprocess_u8 writes with mean 0, inv_std 1), by the rule of torchvision's float-tensor path
+ * (without PIL's uint8 rounding between the steps: about a grey level apart per stage).
+ * params: device, [batch][QT_AUGMENT_PARAMS] f32, read on the device only:
+ *   0-3   brightness, contrast, saturation factor, hue shift
+ *   4-7   the order: four slots, each -1 (skip) or an op id 0 = brightness, 1 = contrast, 2 = saturation, 3 = hue; no id twice
+ *   8, 9  cos, sin of the rotation angle (counter-clockwise); (1, 0) = no rotation
+ *   10    blur sigma (> 0 when a blur kernel is set)       11  reserved, 0
+ * A malformed row (a non-finite entry, a slot outside {-1, 0, 1, 2, 3}, a repeated id, sigma <= 0 while blur is on, op 1 while
+ * use_contrast == 0) makes that image's output all NaN; the other images are unaffected.
+ * With gray = 0.2989 r + 0.587 g + 0.114 b and blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1), in the slots' order:
+ *   brightness blend(img, 0, f); contrast blend(img, m, f), m = mean of gray over the whole image as it stands when the op is
+ *   reached; saturation blend(img, gray(img), f); hue RGB -> HSV, h = (h + shift) mod 1, HSV -> RGB:
+ *     v = maxc, s = (maxc - minc) / maxc, rc = (maxc - r) / (maxc - minc) (g, b likewise; a zero divisor is replaced by 1),
+ *     h = [maxc == r] (bc - gc) + [maxc == g, != r] (2 + rc - bc) + [maxc != g, != r] (4 + gc - rc), h = fmod(h / 6 + 1, 1);
+ *     i = floor(6 h), f = 6 h - i, p = clamp(v (1 - s)), q = clamp(v (1 - s f)), t = clamp(v (1 - s (1 - f))),
+ *     (r, g, b) = (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q) for i mod 6 = 0 .. 5.
+ * Rotation: nearest neighbour about the image centre, same size, fill 0 (not jittered): output pixel (i, j) has
+ *   x = j + 0.5 - w/2, y = i + 0.5 - h/2 and reads column round(cos x - sin y + w/2 - 0.5), row round(sin x + cos y + h/2 - 0.5).
+ * Blur: separable, blur_kx taps along a row and blur_ky along a column, weight exp(-0.5 (d / sigma)^2) / sum for offset d, the
+ *   border reflected without repeating the edge pixel (index -1 reads 1); (1, 1) = no blur.  Then (v - mean[c]) * inv_std[c].
+ * clamp keeps a NaN (torch.clamp): a NaN input pixel is NaN wherever the rule carries it.
+ * No intermediate image in HBM, no atomics, no zero fill, no host synchronisation, the same bits on every run.  With
+ * use_contrast == 1 a first launch writes QT_AUGMENT_PARTS partial sums per image into the workspace
+ * (qt_augment_workspace_bytes; 0 and NULL when use_contrast == 0, the caller's promise that no row names op 1).
+ * QT_ERR_INVALID_ARG (before any device call) for non-positive sizes, a blur size that is even or above 15, an image the blur
+ * reflects beyond (needs w > blur_kx / 2, h > blur_ky / 2), strides below 3*h*w, null or misaligned pointers, a workspace that
+ * is too small, source and destination that overlap (rotation and blur gather); QT_ERR_UNSUPPORTED for sizes above 2^22. */
+#define QT_AUGMENT_PARAMS 12
+#define QT_AUGMENT_PARTS 16
+typedef struct qt_augment_desc {
+  int batch, h, w;
+  long long src_image_stride;       /* floats, >= 3*h*w */
+  long long dst_image_stride;       /* floats, >= 3*h*w */
+  int blur_kx, blur_ky;             /* odd, <= 15 */
+  float mean[3], inv_std[3];
+  int use_contrast;
+} qt_augment_desc;
+size_t qt_augment_workspace_bytes(int batch, int use_contrast);
+int qt_augment_f32(const qt_augment_desc* desc, const float* src, const float* params, float* dst, void* workspace,
+                   size_t workspace_bytes, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

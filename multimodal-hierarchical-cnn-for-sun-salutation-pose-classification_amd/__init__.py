@@ -7,6 +7,7 @@ or put `<this dir>/quadtree_from_scratch` (or `/resnet`) on sys.path and keep th
 reference's `from models import get_model`.
 """
 from ._lib import LIB_PATH, QtError  # noqa: F401
+from .augment import FrameAugmenter  # noqa: F401
 from .loss import CrossEntropyLoss, FocalLoss, LossMeter  # noqa: F401
 from .optim import FusedAdam, grad_norm  # noqa: F401
 from .preprocess import FramePreprocessor, random_flips, random_resized_crop_boxes  # noqa: F401
@@ -14,5 +15,5 @@ from .quadtree import AttentionHierarchicalCNN, CnnLstm, QuadtreeCNN, StandardRe
 from .video3d import Ji3DCNN, Quadtree3DCNN  # noqa: F401
 
 __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnLstm", "Quadtree3DCNN", "Ji3DCNN", "FusedAdam", "grad_norm",
-           "CrossEntropyLoss", "FocalLoss", "LossMeter", "FramePreprocessor", "random_resized_crop_boxes", "random_flips",
+           "CrossEntropyLoss", "FocalLoss", "LossMeter", "FramePreprocessor", "random_resized_crop_boxes", "random_flips", "FrameAugmenter",
            "QtError", "LIB_PATH"]
