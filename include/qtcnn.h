@@ -223,8 +223,8 @@ int qt_conv2d_wgrad_oihw(const qt_conv_desc* desc, const void* dy, const void* x
                          size_t workspace_bytes, void* stream);
 /* The same, with the sum of the partial filters enqueued on `sum_stream` (behind the kernel through an event) instead of the
  * kernel's stream, which is then free for its next launch at once.  `workspace` must stay untouched until that sum has run:
- * the caller orders its next use of it behind sum_stream (csrc/plan.hip alternates two workspaces).  sum_stream NULL or ==
- * stream: qt_conv2d_wgrad_oihw. */
+ * the caller orders its next use of it behind sum_stream (for instance two workspaces used in turn).  The plan executor does
+ * not use this entry point.  sum_stream NULL or == stream: qt_conv2d_wgrad_oihw. */
 int qt_conv2d_wgrad_oihw_on(const qt_conv_desc* desc, const void* dy, const void* x, float* grad_oihw, void* workspace,
                             size_t workspace_bytes, void* stream, void* sum_stream);
 /* bf16 3x3 / stride 1 / pad 1 weight gradients of images at least `min_width` wide take the

@@ -7,16 +7,10 @@
 //   * a strided ReLU/dropout mask for the single-layer numerical MLP (:43-46) that lives inside the fused
 //     feature matrix.
 // All HBM / latency bound (the 16x64 vectors of an image fit in 4 KB of LDS); nothing here is GEMM-shaped.
-#include <type_traits>
 
 #include "qt_common.h"
 
 namespace {
-
-int grid_for(long long total, int block = 256, int cap = 16384) {
-  long long g = (total + block - 1) / block;
-  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
 
 // The convolution numbers the S x S regions of an image row-major (rr*S + rc).  The reference appends
 // quadrants in the order TL, TR, BL, BR (:62-65) and, for each quadrant in that order, its four
@@ -235,15 +229,6 @@ __global__ void relu_mask_cols_kernel(const T* __restrict__ d, const T* __restri
   }
 }
 
-template <typename F> void by_dtype(int dtype, F&& f) {
-  if (dtype == QT_F32)
-    f(static_cast<float*>(nullptr));
-  else
-    f(static_cast<bf16_t*>(nullptr));
-}
-#define QT_T(tag) std::remove_pointer_t<decltype(tag)>
-#define QT_DT_OK(dtype, name) QT_CHECK_ARG((dtype) == QT_F32 || (dtype) == QT_BF16, name ": bad dtype %d", (dtype))
-
 }  // namespace
 
 extern "C" int qt_region_avgpool(int dtype, const void* x, void* dst, int dst_dtype, int batch, int split, int hw, int C,
@@ -256,13 +241,13 @@ extern "C" int qt_region_avgpool(int dtype, const void* x, void* dst, int dst_dt
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nimg = batch * split * split;
   const int grid = (int)(((long long)nimg * (C / 8) * 4 + 255) / 256);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
     if (dst_dtype == dtype)
-      hipLaunchKernelGGL((region_avgpool_kernel<T, T>), dim3(grid), dim3(256), 0, s, (const T*)x, (T*)dst, nimg, split, hw,
+      hipLaunchKernelGGL((region_avgpool_kernel<T, T>), dim3(grid), dim3(256), 0, s, qt_as<T>(x), qt_as<T>(dst), nimg, split, hw,
                          C, ld, col0);
     else
-      hipLaunchKernelGGL((region_avgpool_kernel<T, float>), dim3(grid), dim3(256), 0, s, (const T*)x, (float*)dst, nimg,
+      hipLaunchKernelGGL((region_avgpool_kernel<T, float>), dim3(grid), dim3(256), 0, s, qt_as<T>(x), (float*)dst, nimg,
                          split, hw, C, ld, col0);
   });
   QT_CHECK_LAUNCH();
@@ -278,15 +263,15 @@ extern "C" int qt_region_avgpool_bwd(int dtype, const void* d, int d_dtype, cons
                "qt_region_avgpool_bwd: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nimg = batch * split * split;
-  const int grid = grid_for((long long)nimg * hw * (C / 8));
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
+  const int grid = qt_grid_for((long long)nimg * hw * (C / 8), 256, 16384);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
     if (d_dtype == dtype)
-      hipLaunchKernelGGL((region_avgpool_bwd_kernel<T, T>), dim3(grid), dim3(256), 0, s, (const T*)d, (const T*)x, (T*)g,
+      hipLaunchKernelGGL((region_avgpool_bwd_kernel<T, T>), dim3(grid), dim3(256), 0, s, qt_as<T>(d), qt_as<T>(x), qt_as<T>(g),
                          nimg, split, hw, C, ld, col0);
     else
-      hipLaunchKernelGGL((region_avgpool_bwd_kernel<T, float>), dim3(grid), dim3(256), 0, s, (const float*)d, (const T*)x,
-                         (T*)g, nimg, split, hw, C, ld, col0);
+      hipLaunchKernelGGL((region_avgpool_bwd_kernel<T, float>), dim3(grid), dim3(256), 0, s, (const float*)d, qt_as<T>(x),
+                         qt_as<T>(g), nimg, split, hw, C, ld, col0);
   });
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -299,9 +284,9 @@ extern "C" int qt_attention_gate(int dtype, const float* v, const float* w1, con
   QT_CHECK_ARG(v && w1 && b1 && w2 && b2 && act && alpha && out && batch > 0 && col0 >= 0 && col0 + DV <= ld,
                "qt_attention_gate: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(attention_fwd_kernel<T>, dim3(batch), dim3(64), 0, s, v, w1, b1, w2, b2, act, alpha, (T*)out, ld,
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(attention_fwd_kernel<T>, dim3(batch), dim3(64), 0, s, v, w1, b1, w2, b2, act, alpha, qt_as<T>(out), ld,
                        col0);
   });
   QT_CHECK_LAUNCH();
@@ -315,9 +300,9 @@ extern "C" int qt_attention_gate_bwd(int dtype, const void* d, const float* v, c
   QT_CHECK_ARG(d && v && act && alpha && w1 && w2 && ds && dpre && dv && batch > 0 && col0 >= 0 && col0 + DV <= ld,
                "qt_attention_gate_bwd: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(attention_bwd_kernel<T>, dim3(batch), dim3(64), 0, s, (const T*)d, v, act, alpha, w1, w2, ds, dpre,
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(attention_bwd_kernel<T>, dim3(batch), dim3(64), 0, s, qt_as<T>(d), v, act, alpha, w1, w2, ds, dpre,
                        dv, ld, col0);
   });
   QT_CHECK_LAUNCH();
@@ -329,9 +314,9 @@ extern "C" int qt_relu_mask_cols(int dtype, const void* d, const void* act, floa
   QT_DT_OK(dtype, "qt_relu_mask_cols");
   QT_CHECK_ARG(d && act && out && rows > 0 && cols > 0 && col0 >= 0 && col0 + cols <= ld, "qt_relu_mask_cols: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(relu_mask_cols_kernel<T>, dim3(grid_for(rows * cols)), dim3(256), 0, s, (const T*)d, (const T*)act,
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(relu_mask_cols_kernel<T>, dim3(qt_grid_for(rows * cols, 256, 16384)), dim3(256), 0, s, qt_as<T>(d), qt_as<T>(act),
                        out, rows, cols, ld, col0, mul);
   });
   QT_CHECK_LAUNCH();

@@ -257,6 +257,7 @@ extern "C" int qt_conv3d_first_dgrad(int dtype, const void* dy, const float* w_o
     return QT_ERR_UNSUPPORTED;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
+  // (a dtype branch: f32 has the direct kernel only, the staged kernel below is bf16)
   if (dtype == QT_F32) return d1_launch_direct<float>(dy, w_oidhw, dclips, batch, frames, h, w, s);
   // (the staging plan keeps 32-bit element offsets inside one image)
   const bool fast = h % D1_R == 0 && w % 16 == 0 && w <= 256 && ((uintptr_t)dy % 16) == 0 && (long long)h * w * 32 < (1LL << 31);

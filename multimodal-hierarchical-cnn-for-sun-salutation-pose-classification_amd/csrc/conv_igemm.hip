@@ -18,7 +18,7 @@
 // fusing scale/shift (+residual) (+ReLU) (+ReLU-mask) and BatchNorm partial sums.
 #include <stdlib.h>
 
-#include "conv_args.h"
+#include "qt_internal.h"
 
 namespace {
 
@@ -675,22 +675,13 @@ int dispatch(const qt_conv_desc* d, const ConvArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// conv_patch.hip: 3x3 stride-1 convs of the 56x56 / 28x28 stages with the input patch held in LDS
-bool qt_patch_eligible(const qt_conv_desc* d);
-int qt_patch_stats_rows(const qt_conv_desc* d);
-int qt_patch_launch(const qt_conv_desc* d, const qt_conv_io* io, void* stream);
-// conv_stem.hip: the packed 7x7/2 stem convolution (bf16) with its input rows held in LDS
-bool qt_stem_eligible(const qt_conv_desc* d, const qt_conv_io* io);
-int qt_stem_stats_rows(const qt_conv_desc* d);
-int qt_stem_launch(const qt_conv_desc* d, const qt_conv_io* io, void* stream);
-
 extern "C" int qt_conv2d_stats_rows(const qt_conv_desc* d) {
   if (!d) return QT_ERR_INVALID_ARG;
   const bool kt3 = d->kt > 1;   // (frame taps: always the generic tile)
   if (!kt3 && qt_patch_eligible(d)) return qt_patch_stats_rows(d);
   if (!kt3 && qt_stem_eligible(d, nullptr)) return qt_stem_stats_rows(d);
   const long long M = (long long)d->batch * (d->mode == QT_CONV_FWD ? qt_quad_regions(d->quad) : 1) * d->out_h * d->out_w;
-  const int esz = d->dtype == QT_F32 ? 4 : 2;
+  const int esz = qt_dtype_size(d->dtype);
   {
     ConvArgs a = {};
     a.M = (int)M; a.N = d->n_out; a.KC = d->k_per_tap; a.ntaps = d->kh * d->kw + (d->dst_merge_extra ? 1 : 0); a.KW = d->kw; a.stride = d->stride;
@@ -711,10 +702,10 @@ extern "C" void qt_set_igemm_prof(unsigned long long* buf) { g_igemm_prof = buf;
 
 extern "C" int qt_conv2d_igemm(const qt_conv_desc* d, const qt_conv_io* io, void* stream) {
   QT_CHECK_ARG(d && io, "qt_conv2d_igemm: null descriptor");
-  QT_CHECK_ARG(d->dtype == QT_F32 || d->dtype == QT_BF16, "qt_conv2d_igemm: bad dtype %d", d->dtype);
+  QT_DT_OK(d->dtype, "qt_conv2d_igemm");
   QT_CHECK_ARG(d->mode == QT_CONV_FWD || d->mode == QT_CONV_DGRAD, "qt_conv2d_igemm: bad mode %d", d->mode);
   QT_CHECK_ARG(io->src && io->weight && io->dst, "qt_conv2d_igemm: null src/weight/dst");
-  const int bk = d->dtype == QT_F32 ? 32 : 64;
+  const int bk = kRowBytes / qt_dtype_size(d->dtype);   // elements of a K-step
   QT_CHECK_ARG(d->k_per_tap > 0 && (d->k_per_tap % bk == 0 || (2 * d->k_per_tap == bk && (d->kh * d->kw) % 2 == 0)),
                "qt_conv2d_igemm: k_per_tap=%d must be a multiple of %d (or half of it with an even tap count)",
                d->k_per_tap, bk);
@@ -727,7 +718,7 @@ extern "C" int qt_conv2d_igemm(const qt_conv_desc* d, const qt_conv_io* io, void
   QT_CHECK_ARG(d->quad == 0 || d->quad == 1 || d->quad == 2 || d->quad == 4, "qt_conv2d_igemm: quad must be 0, 1 (= 2), 2 or 4");
   QT_CHECK_ARG(d->kh * d->kw <= 32, "qt_conv2d_igemm: at most 32 taps (kh*kw=%d)", d->kh * d->kw);
   QT_CHECK_ARG(2 * d->k_per_tap != bk || d->kw == 1, "qt_conv2d_igemm: half-K-step taps need kw == 1");
-  const int esz = d->dtype == QT_F32 ? 4 : 2;
+  const int esz = qt_dtype_size(d->dtype);
   QT_CHECK_ARG(((uintptr_t)io->src % 16) == 0 && ((uintptr_t)io->weight % 16) == 0 && ((uintptr_t)io->dst % 16) == 0,
                "qt_conv2d_igemm: pointers must be 16-byte aligned");
   QT_CHECK_ARG((d->src_pix_stride * esz) % 8 == 0 && ((long long)d->src_row_stride * esz) % 16 == 0 &&
@@ -806,5 +797,5 @@ extern "C" int qt_conv2d_igemm(const qt_conv_desc* d, const qt_conv_io* io, void
                "qt_conv2d_igemm: bad destination mapping");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (KT == 1 && qt_pt_eligible(a, d->dtype, d->mode == QT_CONV_DGRAD)) return qt_pt_launch(a, d->dtype, d->mode == QT_CONV_DGRAD, s);
-  return d->dtype == QT_F32 ? dispatch<float>(d, a, s) : dispatch<bf16_t>(d, a, s);
+  return qt_by_dtype(d->dtype, [&](auto* t) { return dispatch<QT_T(t)>(d, a, s); });
 }

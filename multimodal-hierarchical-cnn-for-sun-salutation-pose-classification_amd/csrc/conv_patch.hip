@@ -17,7 +17,7 @@
 
 #include <type_traits>
 
-#include "qt_common.h"
+#include "qt_internal.h"
 
 namespace {
 

@@ -33,7 +33,7 @@
 
 #include <type_traits>
 
-#include "conv_args.h"
+#include "qt_internal.h"
 
 namespace {
 
@@ -92,29 +92,6 @@ template <> struct Raw8<float> {
   }
 };
 
-// two / four transfers 8 KiB apart in LDS (consecutive 64-row passes of a tile), M0 saved once
-__device__ __forceinline__ void blds16x2(const i32x4& rsrc, unsigned v0, unsigned v1, unsigned soff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "s"(rsrc), "s"(soff), "s"(lds_addr)
-      : "memory", "scc");
-}
-__device__ __forceinline__ void blds16x4(const i32x4& rsrc, unsigned v0, unsigned v1, unsigned v2, unsigned v3, unsigned soff,
-                                         unsigned lds_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %5, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %5, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %5, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %5, %6 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(rsrc), "s"(soff), "s"(lds_addr)
-      : "memory", "scc");
-}
-
 // DMA instructions a wave issues in the L segment of tap `tp` (-1: tap 8 of the previous chunk, or the prologue's last
 // weight tile): one patch pass of the next chunk on the first NPASS taps (never in the last chunk) + RW for weight tile
 // t+D (not on the last D taps of the last chunk)
@@ -122,15 +99,6 @@ template <int NPASS, int RW, int D>
 constexpr int issued_in(int tp, bool last) {
   if (tp < 0) return RW;
   return ((!last && tp < NPASS) ? 1 : 0) + ((!last || tp + D < 9) ? RW : 0);
-}
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>): a loop whose counter is a constant expression
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<N, I + 1>(f);
-  }
 }
 
 // patch passes of the NEXT chunk issued in the L segment of tap `tap`: all of them no later than (and, inside their segment,
@@ -880,7 +848,7 @@ static bool pt_merged_shape(const ConvArgs& a, int esz) {
 // the descriptor must be a 3x3 / stride 1 / pad 1 convolution on 28x28, 14x14 or 7x7 images (or 7x7 quadrants of 14x14 maps)
 bool qt_pt_eligible(const ConvArgs& a, int dtype, bool dgrad) {
   if (!pt_enabled()) return false;
-  const int esz = dtype == QT_F32 ? 4 : 2;
+  const int esz = qt_dtype_size(dtype);
   if (a.dst_merge) {
     if (dgrad || !pt_merged_shape(a, esz) || !merged_enabled()) return false;
     if (a.scale || a.shift || a.stats_partial || a.relu) return false;
@@ -925,7 +893,7 @@ int qt_pt_launch(const ConvArgs& a, int dtype, bool dgrad, hipStream_t stream) {
   PtArgs q;
   q.c = a;
   if (a.dst_merge) {
-    const int esz = dtype == QT_F32 ? 4 : 2;
+    const int esz = qt_dtype_size(dtype);
     pt_geometry(a.OH, a.OW, q);
     q.quad = 0;
     q.batch = a.M / (a.OH * a.OW);
@@ -936,12 +904,12 @@ int qt_pt_launch(const ConvArgs& a, int dtype, bool dgrad, hipStream_t stream) {
     q.wgt_bytes = (unsigned)((long long)a.N * 4 * a.KC * esz);
     q.div_hw = make_fastdiv((unsigned)(a.OH * a.OW));
     q.div_w = make_fastdiv((unsigned)a.OW);
-    return dtype == QT_F32 ? dispatch_merged<float>(q, stream) : dispatch_merged<bf16_t>(q, stream);
+    return qt_by_dtype(dtype, [&](auto* t) { return dispatch_merged<QT_T(t)>(q, stream); });
   }
   pt_geometry(a.IH, a.IW, q);
   q.batch = pt_images(a, dgrad, &q.quad);
   q.tiles_m = pt_tiles_m(q, q.batch);
-  const int esz = dtype == QT_F32 ? 4 : 2;
+  const int esz = qt_dtype_size(dtype);
   q.nchunks = a.KC * esz / kKB;
   const long long simgs = q.quad == 1 ? q.batch / 4 : q.batch;
   const int sh = q.quad == 1 ? 14 : a.IH, sw = q.quad == 1 ? 14 : a.IW;
@@ -949,6 +917,7 @@ int qt_pt_launch(const ConvArgs& a, int dtype, bool dgrad, hipStream_t stream) {
   q.src_bytes = (unsigned)(((simgs - 1) * a.src_img_stride + ((long long)sh - 1) * a.src_row_stride +
                             ((long long)sw - 1) * a.src_pix_stride + a.KC + (q.G == 1 ? a.src_row_stride : 0)) * esz);
   q.wgt_bytes = (unsigned)((long long)a.N * 9 * a.KC * esz);
-  if (dtype == QT_F32) return dgrad ? dispatch<float, true>(q, stream) : dispatch<float, false>(q, stream);
-  return dgrad ? dispatch<bf16_t, true>(q, stream) : dispatch<bf16_t, false>(q, stream);
+  return qt_by_dtype(dtype, [&](auto* t) {
+    return dgrad ? dispatch<QT_T(t), true>(q, stream) : dispatch<QT_T(t), false>(q, stream);
+  });
 }

@@ -71,25 +71,6 @@ struct S2Args {
   FastDiv div_pw;
 };
 
-// two / four transfers 8 KiB apart in LDS, M0 saved once (as conv_pt.hip)
-__device__ __forceinline__ void s2_blds16x2(const i32x4& rsrc, unsigned v0, unsigned v1, unsigned soff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\t"
-      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "s"(rsrc), "s"(soff), "s"(lds_addr)
-      : "memory", "scc");
-}
-
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void s2_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    s2_static_for<N, I + 1>(f);
-  }
-}
-
 // K-tile t of a chunk: filter tap (kh * 3 + kw; 9 = the downsample), plane shift rows / columns, stage (plane) it reads
 __device__ constexpr int kTapOf[10] = {0, 2, 6, 8, 3, 5, 1, 7, 4, 9};
 __device__ constexpr int kShR[10] = {0, 0, 1, 1, 1, 1, 0, 1, 1, 1};
@@ -229,11 +210,11 @@ __global__ __launch_bounds__(kNT, 2) void conv_s2_kernel(S2Args q) {
   {
     const unsigned v0 = cur.top ? voff0_top : voff[0];
     const unsigned so = cur.psoff + plane_delta[0];
-    s2_blds16x2(rs_src, v0, voff[1], so, smem_base + wave * 1024);
-    s2_blds16x2(rs_src, voff[2], voff[3], so, smem_base + 2 * 8192 + wave * 1024);
+    blds16x2(rs_src, v0, voff[1], so, smem_base + wave * 1024);
+    blds16x2(rs_src, voff[2], voff[3], so, smem_base + 2 * 8192 + wave * 1024);
 #pragma unroll
     for (int s = 0; s < D; ++s)   // K-tiles 0 .. D-1 of chunk 0 (D <= 3: conv taps)
-      s2_blds16x2(rs_wgt, w_off[0], w_off[1], cur.wsoff + (unsigned)kTapOf[s] * tap_bytes, wring + s * WSLOT + wave * 1024);
+      blds16x2(rs_wgt, w_off[0], w_off[1], cur.wsoff + (unsigned)kTapOf[s] * tap_bytes, wring + s * WSLOT + wave * 1024);
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(RW * (D - 1)) : "memory");   // (lgkmcnt: the affine vectors)
     if (grp == 1) asm volatile("s_barrier" ::: "memory");
   }
@@ -267,7 +248,7 @@ __global__ __launch_bounds__(kNT, 2) void conv_s2_kernel(S2Args q) {
       const int pb1 = pa + 1 >= kNPB ? pa + 1 - kNPB : pa + 1, pb2 = pa + 2 >= kNPB ? pa + 2 - kNPB : pa + 2;
       const bool after_epilogue = D == 2 && cidx == 0 && it != item_begin;
 
-      s2_static_for<10>([&](auto tt) {
+      static_for<10>([&](auto tt) {
         constexpr int t = decltype(tt)::value;
         // ---- L_t: two passes of the stage 1-2 ahead, the weight tile D ahead, this K-tile's fragments ----
         if constexpr (t < 8) {
@@ -277,10 +258,10 @@ __global__ __launch_bounds__(kNT, 2) void conv_s2_kernel(S2Args q) {
           const unsigned lds = smem_base + buf * kPBuf + pp * 8192 + wave * 1024;
           if constexpr (s < 4) {
             unsigned so = c_psoff + plane_delta[s];
-            s2_blds16x2(rs_src, pp == 0 ? v0_c : voff[2], pp == 0 ? voff[1] : voff[3], so, lds);
+            blds16x2(rs_src, pp == 0 ? v0_c : voff[2], pp == 0 ? voff[1] : voff[3], so, lds);
           } else {
             unsigned so = n_psoff + plane_delta[0];
-            s2_blds16x2(rs_src_n, pp == 0 ? v0_n : voff[2], pp == 0 ? voff[1] : voff[3], so, lds);
+            blds16x2(rs_src_n, pp == 0 ? v0_n : voff[2], pp == 0 ? voff[1] : voff[3], so, lds);
           }
         }
         {
@@ -288,10 +269,10 @@ __global__ __launch_bounds__(kNT, 2) void conv_s2_kernel(S2Args q) {
           constexpr bool wrap = t + D >= 10;
           const unsigned sw = wring + wr * WSLOT + wave * 1024;
           if constexpr (u == 9) {
-            s2_blds16x2(wrap ? rs_wds_n : rs_wds, wd_off[0], wd_off[1], wrap ? n_dsoff : c_dsoff, sw);
+            blds16x2(wrap ? rs_wds_n : rs_wds, wd_off[0], wd_off[1], wrap ? n_dsoff : c_dsoff, sw);
           } else {
             unsigned so = (wrap ? n_wsoff : c_wsoff) + (unsigned)kTapOf[u] * tap_bytes;
-            s2_blds16x2(wrap ? rs_wgt_n : rs_wgt, w_off[0], w_off[1], so, sw);
+            blds16x2(wrap ? rs_wgt_n : rs_wgt, w_off[0], w_off[1], so, sw);
           }
           wr = wr + 1 == NBW ? 0 : wr + 1;
         }
@@ -482,7 +463,7 @@ extern "C" void qt_set_conv_s2_max_workgroups(int n) { g_s2_max_wgs = n > 0 ? n 
 extern "C" int qt_conv_s2_pair_supported(const qt_conv_s2_desc* d) {
   if (!d || !s2_enabled()) return 0;
   if (d->dtype != QT_F32 && d->dtype != QT_BF16) return 0;
-  const int esz = d->dtype == QT_F32 ? 4 : 2;
+  const int esz = qt_dtype_size(d->dtype);
   S2Args q;
   if (!s2_geometry(d, q)) return 0;
   if ((d->c_in * esz) % kKB != 0 || d->c_out % 128 != 0 || d->c_out > 512) return 0;
@@ -505,7 +486,7 @@ extern "C" int qt_conv_s2_pair(const qt_conv_s2_desc* d, const qt_conv_s2_io* io
   QT_CHECK_ARG(io->src && io->w_conv && io->w_down && io->y_conv && io->y_down, "qt_conv_s2_pair: null src / weights / outputs");
   for (const void* ptr : {io->src, io->w_conv, io->w_down, (const void*)io->y_conv, (const void*)io->y_down})
     QT_CHECK_ARG(((uintptr_t)ptr % 16) == 0, "qt_conv_s2_pair: pointers must be 16-byte aligned");
-  const int esz = d->dtype == QT_F32 ? 4 : 2;
+  const int esz = qt_dtype_size(d->dtype);
   S2Args q;
   s2_geometry(d, q);
   q.src = io->src; q.wgt = io->w_conv; q.wds = io->w_down;
@@ -533,6 +514,7 @@ extern "C" int qt_conv_s2_pair(const qt_conv_s2_desc* d, const qt_conv_s2_io* io
   q.wgt_bytes = (unsigned)((long long)d->c_out * 9 * d->c_in * esz);
   q.wds_bytes = (unsigned)((long long)d->c_out * d->c_in * esz);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d->dtype == QT_F32) return q.OH == 7 ? s2_launch<float, GEO_STACK>(q, s) : s2_launch<float, GEO_ROWS>(q, s);
-  return q.OH == 7 ? s2_launch<bf16_t, GEO_STACK>(q, s) : s2_launch<bf16_t, GEO_ROWS>(q, s);
+  return qt_by_dtype(d->dtype, [&](auto* t) {
+    return q.OH == 7 ? s2_launch<QT_T(t), GEO_STACK>(q, s) : s2_launch<QT_T(t), GEO_ROWS>(q, s);
+  });
 }

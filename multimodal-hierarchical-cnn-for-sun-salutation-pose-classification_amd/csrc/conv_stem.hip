@@ -18,7 +18,7 @@
 // Bound: the 411 MB output write (HBM), not MFMA.
 #include <stdlib.h>
 
-#include "qt_common.h"
+#include "qt_internal.h"
 
 namespace {
 

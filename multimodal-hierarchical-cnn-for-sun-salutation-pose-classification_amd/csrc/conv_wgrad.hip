@@ -16,7 +16,7 @@
 // accumulated with global_atomic_add_f32 into the zero-initialised f32 gradient.
 #include <string.h>
 
-#include "qt_common.h"
+#include "qt_internal.h"
 
 namespace {
 
@@ -649,12 +649,6 @@ int launch_stem_rows(const void* dy, const void* x, float* dw, int batch, hipStr
 
 }  // namespace
 
-// conv_wgrad_patch.hip: streaming kernel for 3x3 / stride 1 / pad 1 (bf16)
-bool qt_wgrad_patch_eligible(const qt_conv_desc* d);
-size_t qt_wgrad_patch_workspace_bytes(const qt_conv_desc* d);
-int qt_wgrad_patch_launch(const qt_conv_desc* d, const void* dy, const void* x, float* dw, void* workspace,
-                          size_t workspace_bytes, int oihw, void* stream);
-
 // Stem backward in one launch (bf16): max-pool backward + ReLU mask + BatchNorm backward of conv1's output computed tile by
 // tile in LDS and contracted with the packed input at once: dw[64][7][32] += conv1's weight gradient (qt_unpack_stem_wgrad
 // layout).  Inputs as qt_stem_bn_bwd_apply; d(loss)/d(conv1 output) is never materialised.
@@ -700,58 +694,48 @@ extern "C" int qt_stem_bn_bwd_wgrad_ws(int dtype, const void* dpooled, const uns
                            batch, stream);
 }
 
-// conv_wgrad_s2.hip: the stride-2 convolutions of a transition block (3x3 / 2 pad 1, 1x1 / 2) on parity planes (bf16)
-bool qt_wgrad_s2_eligible(const qt_conv_desc* d);
-size_t qt_wgrad_s2_workspace_bytes(const qt_conv_desc* d);
-int qt_wgrad_s2_launch(const qt_conv_desc* d, const void* dy, const void* x, float* grad_oihw, void* workspace,
-                       size_t workspace_bytes, void* stream);
-
 extern "C" size_t qt_conv2d_wgrad_workspace_bytes(const qt_conv_desc* d) {
   if (!d) return 0;
   if (d->mode == QT_CONV_FWD && qt_wgrad_s2_eligible(d)) return qt_wgrad_s2_workspace_bytes(d);
   return qt_wgrad_patch_workspace_bytes(d);
 }
 
-extern "C" int qt_conv2d_wgrad(const qt_conv_desc* d, const void* dy, const void* x, float* dw, void* stream) {
-  return qt_conv2d_wgrad_ws(d, dy, x, dw, nullptr, 0, stream);
-}
-
-extern "C" int qt_conv2d_wgrad_oihw(const qt_conv_desc* d, const void* dy, const void* x, float* grad_oihw, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
+// Streaming kernels with the gradient WRITTEN in OIHW; the fixed-order sum of the partial filters runs on `sum_stream`
+// (nullptr: on `stream`)
+static int wgrad_oihw(const qt_conv_desc* d, const void* dy, const void* x, float* grad_oihw, void* workspace,
+                      size_t workspace_bytes, void* stream, void* sum_stream) {
   QT_CHECK_ARG(d && dy && x && grad_oihw && workspace, "qt_conv2d_wgrad_oihw: null argument");
   QT_CHECK_ARG(((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)grad_oihw % 4) == 0 &&
                    ((uintptr_t)workspace % 16) == 0,
                "qt_conv2d_wgrad_oihw: misaligned pointer");
   if (d->mode == QT_CONV_FWD && qt_wgrad_s2_eligible(d))
-    return qt_wgrad_s2_launch(d, dy, x, grad_oihw, workspace, workspace_bytes, stream);
+    return qt_wgrad_s2_launch(d, dy, x, grad_oihw, workspace, workspace_bytes, stream, sum_stream);
   if (d->mode != QT_CONV_FWD || !qt_wgrad_patch_eligible(d)) {
     qt_set_error("qt_conv2d_wgrad_oihw: only the shapes of the streaming kernels (bf16: 3x3 stride 1; 3x3 / 1x1 stride 2)");
     return QT_ERR_UNSUPPORTED;
   }
-  return qt_wgrad_patch_launch(d, dy, x, grad_oihw, workspace, workspace_bytes, 1, stream);
+  return qt_wgrad_patch_launch(d, dy, x, grad_oihw, workspace, workspace_bytes, 1, stream, sum_stream);
 }
 
-static thread_local int g_wgrad_overwrite = 0;   // set around the one call of qt_linear_wgrad below
-
-// conv_wgrad_patch.hip: stream of the next partial-filter sum of this thread (NULL: the kernel's own)
-void qt_wgrad_set_sum_stream(void* s);
+extern "C" int qt_conv2d_wgrad_oihw(const qt_conv_desc* d, const void* dy, const void* x, float* grad_oihw, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return wgrad_oihw(d, dy, x, grad_oihw, workspace, workspace_bytes, stream, nullptr);
+}
 
 // qt_conv2d_wgrad_oihw with the fixed-order sum of the partial filters on `sum_stream` (ordered behind the kernel by an
 // event): the kernel's stream goes straight on to its next launch.  The caller keeps `workspace` untouched until the sum has
-// run (e.g. two workspaces used in turn, the reuse ordered behind an event on sum_stream) -- csrc/plan.hip does.
+// run (e.g. two workspaces used in turn, the reuse ordered behind an event on sum_stream).
 extern "C" int qt_conv2d_wgrad_oihw_on(const qt_conv_desc* d, const void* dy, const void* x, float* grad_oihw, void* workspace,
                                        size_t workspace_bytes, void* stream, void* sum_stream) {
-  qt_wgrad_set_sum_stream(sum_stream);
-  const int st = qt_conv2d_wgrad_oihw(d, dy, x, grad_oihw, workspace, workspace_bytes, stream);
-  qt_wgrad_set_sum_stream(nullptr);
-  return st;
+  return wgrad_oihw(d, dy, x, grad_oihw, workspace, workspace_bytes, stream, sum_stream);
 }
 
-extern "C" int qt_conv2d_wgrad_ws(const qt_conv_desc* d, const void* dy, const void* x, float* dw, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+// overwrite 1 (qt_linear_wgrad): dw is WRITTEN where every element has one producer, else zeroed and accumulated into
+static int wgrad_generic(const qt_conv_desc* d, const void* dy, const void* x, float* dw, void* workspace,
+                         size_t workspace_bytes, int overwrite, void* stream) {
   QT_CHECK_ARG(d && dy && x && dw, "qt_conv2d_wgrad: null argument");
   QT_CHECK_ARG(((uintptr_t)workspace % 16) == 0, "qt_conv2d_wgrad_ws: misaligned workspace");
-  QT_CHECK_ARG(d->dtype == QT_F32 || d->dtype == QT_BF16, "qt_conv2d_wgrad: bad dtype %d", d->dtype);
+  QT_DT_OK(d->dtype, "qt_conv2d_wgrad");
   QT_CHECK_ARG(d->mode == QT_CONV_FWD, "qt_conv2d_wgrad: describe the FORWARD convolution (mode QT_CONV_FWD)");
   QT_CHECK_ARG(d->n_out > 0 && d->n_out % 8 == 0 && d->k_per_tap > 0 && d->k_per_tap % 8 == 0,
                "qt_conv2d_wgrad: channel counts must be multiples of 8 (n_out=%d k_per_tap=%d)", d->n_out, d->k_per_tap);
@@ -769,12 +753,12 @@ extern "C" int qt_conv2d_wgrad_ws(const qt_conv_desc* d, const void* dy, const v
   a.div_ohw = make_fastdiv((unsigned)(d->out_h * d->out_w));
   a.div_ow = make_fastdiv((unsigned)d->out_w);
   a.tilesN = a.tilesC = a.gtaps = a.ksplit = a.pix_per_split = 0;
-  a.overwrite = g_wgrad_overwrite;
+  a.overwrite = overwrite;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (qt_wgrad_patch_eligible(d)) return qt_wgrad_patch_launch(d, dy, x, dw, workspace, workspace_bytes, 0, stream);
+  if (qt_wgrad_patch_eligible(d)) return qt_wgrad_patch_launch(d, dy, x, dw, workspace, workspace_bytes, 0, stream, nullptr);
   // packed stem: 7 row taps x 32 elements form one 224-wide virtual channel axis
   const bool stem = d->k_per_tap == 32 && d->kw == 1 && d->kh == 7 && d->n_out == 64;
-  if (d->dtype == QT_BF16) {
+  if (d->dtype == QT_BF16) {   // (not qt_by_dtype: bf16 has its own stem kernel and a ladder of four tiles, f32 one tile)
     if (stem) {
       // QTCNN_STEM_WGRAD_ROWS (default 1): the raw-row kernel for the canonical stem geometry; 0: the generic kernel
       static const int rows_on = qt_env_int("QTCNN_STEM_WGRAD_ROWS", 1);
@@ -794,6 +778,15 @@ extern "C" int qt_conv2d_wgrad_ws(const qt_conv_desc* d, const void* dy, const v
   return launch<float, 64, 64, false>(a, s);
 }
 
+extern "C" int qt_conv2d_wgrad_ws(const qt_conv_desc* d, const void* dy, const void* x, float* dw, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  return wgrad_generic(d, dy, x, dw, workspace, workspace_bytes, 0, stream);
+}
+
+extern "C" int qt_conv2d_wgrad(const qt_conv_desc* d, const void* dy, const void* x, float* dw, void* stream) {
+  return qt_conv2d_wgrad_ws(d, dy, x, dw, nullptr, 0, stream);
+}
+
 // dw [out][in] f32 = dy^T x for a Linear layer, WRITTEN (not accumulated): the generic kernel on 1x1 images; when the grid has
 // a single range of rows per tile -- classifier.0 of the reference (Linear 5376 -> 2688 at 256 rows: 882 tiles;
 // /root/reference/Quadtree_from scratch/models.py:264-271) -- every element has one producer and is stored plainly: no
@@ -805,8 +798,5 @@ extern "C" int qt_linear_wgrad(int dtype, const void* dy, const void* x, float* 
   d.dtype = dtype; d.mode = QT_CONV_FWD; d.batch = rows; d.in_h = d.in_w = d.out_h = d.out_w = 1;
   d.kh = d.kw = 1; d.stride = 1; d.pad = 0;
   d.k_per_tap = in; d.n_out = out; d.src_pix_stride = in; d.src_row_stride = in; d.src_img_stride = in;
-  g_wgrad_overwrite = 1;
-  const int st = qt_conv2d_wgrad_ws(&d, dy, x, dw, nullptr, 0, stream);
-  g_wgrad_overwrite = 0;
-  return st;
+  return wgrad_generic(&d, dy, x, dw, nullptr, 0, 1, stream);
 }

@@ -24,7 +24,7 @@
 //     with f32 atomics into the zeroed gradient, as in the generic kernel.
 #include <stdlib.h>
 
-#include "qt_common.h"
+#include "qt_internal.h"
 
 namespace {
 
@@ -77,10 +77,6 @@ struct PosWalk {
     }
   }
 };
-
-__device__ __forceinline__ QT_LDS_AS s16x4* lds_tr_ptr(unsigned lds_byte) {
-  return (QT_LDS_AS s16x4*)(size_t)lds_byte;
-}
 
 constexpr int WP_CH = 32;  // positions per MFMA K-step
 
@@ -700,20 +696,17 @@ __global__ __launch_bounds__(256) void wgrad_partial_sum_light_kernel(const floa
 }
 
 // The sum of a weight gradient's partial filters may run on ANOTHER stream than the kernel that wrote them
-// (qt_conv2d_wgrad_oihw_on): set around that one call, consumed here.
-thread_local hipStream_t g_sum_stream = nullptr;
-
+// (qt_conv2d_wgrad_oihw_on): `sum_stream`, nullptr = the kernel's own.
 // QTCNN_WGRAD_SUM (default 1 = the light form; 0 = the LDS form above, same-box A/B)
-int sum_partials(const float* part, float* dw, int nq, int nsplit, int KC, int layout, hipStream_t stream) {
-  if (g_sum_stream && g_sum_stream != stream) {   // behind the kernel on `stream`, but not in ITS queue
-    hipEvent_t ev;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, stream) != hipSuccess ||
-        hipStreamWaitEvent(g_sum_stream, ev, 0) != hipSuccess) {
+int sum_partials(const float* part, float* dw, int nq, int nsplit, int KC, int layout, hipStream_t stream,
+                 hipStream_t sum_stream) {
+  if (sum_stream && sum_stream != stream) {   // behind the kernel on `stream`, but not in ITS queue
+    hipEvent_t ev = qt_thread_event();
+    if (!ev || hipEventRecord(ev, stream) != hipSuccess || hipStreamWaitEvent(sum_stream, ev, 0) != hipSuccess) {
       qt_set_error("qt_conv2d_wgrad_oihw_on: HIP event error");
       return QT_ERR_LAUNCH;
     }
-    (void)hipEventDestroy(ev);   // (deferred until the event has completed)
-    stream = g_sum_stream;
+    stream = sum_stream;
   }
   static const int light = qt_env_int("QTCNN_WGRAD_SUM", 1);
   if (light && nsplit > 16)   // (few ranges: half of the light form's lanes would idle; r04v trace: 78-83 us against 45-71 in the step)
@@ -749,7 +742,7 @@ void split_ranges(int total, int tiles, int mcr, int* pps_out, int* nsplit_out) 
 constexpr int kGroups = 1;  // wave groups of the default variant (split_ranges depends on it)
 
 template <int G, int D, int NX, int ND>
-int launch_patch(WPArgs a, size_t part_bytes, int oihw, hipStream_t stream) {
+int launch_patch(WPArgs a, size_t part_bytes, int oihw, hipStream_t stream, hipStream_t sum_stream) {
   constexpr int MCR = WP_CH * G;
   constexpr int LDS = (NX + ND) * MCR * 128;
   if (2 * a.halo > a.PP || (2 * a.halo) % MCR != 0 || (2 * a.halo) / MCR + D + 2 > NX || D + 2 > ND) {
@@ -773,7 +766,7 @@ int launch_patch(WPArgs a, size_t part_bytes, int oihw, hipStream_t stream) {
   if (int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(kern), LDS, lds_limit_set)) return rc;
   hipLaunchKernelGGL(kern, dim3(a.tiles * a.nsplit), dim3(256 * G), LDS, stream, a);
   QT_CHECK_LAUNCH();
-  if (a.part) return sum_partials(a.part, a.dw, (int)(filt / 4), real_split, a.KC, oihw, stream);
+  if (a.part) return sum_partials(a.part, a.dw, (int)(filt / 4), real_split, a.KC, oihw, stream, sum_stream);
   return QT_OK;
 }
 
@@ -810,7 +803,7 @@ int launch_tile_nt(const WTArgs& t, unsigned lds, hipStream_t stream) {
 }
 
 // -1: the shape is not for the tile kernel (caller takes the ring kernel), else a status
-int launch_tile(WPArgs a, size_t part_bytes, int oihw, hipStream_t stream) {
+int launch_tile(WPArgs a, size_t part_bytes, int oihw, hipStream_t stream, hipStream_t sum_stream) {
   const TileGeo g = tile_geometry(a.PW, a.PP);
   const unsigned long long xbytes = (unsigned long long)a.B * (unsigned long long)a.x_is * 2ull;
   const unsigned long long ybytes = (unsigned long long)a.B * (unsigned long long)a.dy_is * 2ull;
@@ -832,7 +825,7 @@ int launch_tile(WPArgs a, size_t part_bytes, int oihw, hipStream_t stream) {
   int rc = g.nt == 8 ? launch_tile_nt<8>(t, g.lds, stream)
          : g.nt == 6 ? launch_tile_nt<6>(t, g.lds, stream) : launch_tile_nt<4>(t, g.lds, stream);
   if (rc != QT_OK) return rc;
-  if (a.part) return sum_partials(a.part, a.dw, (int)(filt / 4), real_split, a.KC, oihw, stream);
+  if (a.part) return sum_partials(a.part, a.dw, (int)(filt / 4), real_split, a.KC, oihw, stream, sum_stream);
   return QT_OK;
 }
 
@@ -844,11 +837,10 @@ int wp_variant() {
 
 }  // namespace
 
-// dw = sum over `nsplit` ranges of part[range][filt] in a fixed order (conv_wgrad_s2.hip shares the reduction).  layout 0:
-// added to dw ([O][taps][I]); 1: written to OIHW from [O][9][I]; 2: written as is.
-void qt_wgrad_set_sum_stream(void* s) { g_sum_stream = static_cast<hipStream_t>(s); }
-int qt_wgrad_partial_sum_launch(const float* part, float* dw, size_t filt, int nsplit, int KC, int layout, hipStream_t stream) {
-  return sum_partials(part, dw, (int)(filt / 4), nsplit, KC, layout, stream);
+// (conv_wgrad_s2.hip shares the reduction)
+int qt_wgrad_partial_sum_launch(const float* part, float* dw, size_t filt, int nsplit, int KC, int layout, hipStream_t stream,
+                                hipStream_t sum_stream) {
+  return sum_partials(part, dw, (int)(filt / 4), nsplit, KC, layout, stream, sum_stream);
 }
 
 // Smallest image width whose 3x3 stride-1 weight gradients take the streaming kernel
@@ -898,7 +890,7 @@ size_t qt_wgrad_patch_workspace_bytes(const qt_conv_desc* d) {
 }
 
 int qt_wgrad_patch_launch(const qt_conv_desc* d, const void* dy, const void* x, float* dw, void* workspace,
-                          size_t workspace_bytes, int oihw, void* stream) {
+                          size_t workspace_bytes, int oihw, void* stream, void* sum_stream) {
   WPArgs a;
   a.part = static_cast<float*>(workspace);
   a.dy = static_cast<const bf16_t*>(dy);
@@ -925,7 +917,7 @@ int qt_wgrad_patch_launch(const qt_conv_desc* d, const void* dy, const void* x, 
   const int variant = wp_variant();
   static const int use_ws = qt_env_int("QTCNN_WGRAD_WS", 1);
   if (!use_ws && !oihw) a.part = nullptr;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = static_cast<hipStream_t>(stream), ss = static_cast<hipStream_t>(sum_stream);
   // Alone, two wave groups win (56x56 64->64, atomics: 99 us vs 122 us): a second wave per SIMD
   // covers LDS reads and address arithmetic.  Inside the training step the launch overlaps the
   // main stream's data-gradient / BatchNorm kernels, and two 252-VGPR waves per SIMD leave no room
@@ -933,13 +925,13 @@ int qt_wgrad_patch_launch(const qt_conv_desc* d, const void* dy, const void* x, 
   // workgroup (one wave per SIMD, 96 KB LDS) keeps half of every CU's registers free and measures
   // 1.7 % faster per step (7.43 vs 7.56 ms); 48 KB of LDS with a shallower ring measures slower (7.60).
   if (variant == 3) {
-    const int rc = launch_tile(a, workspace_bytes, oihw, s);
+    const int rc = launch_tile(a, workspace_bytes, oihw, s, ss);
     if (rc >= 0) return rc;
   }
   if (a.reg) {   // (the ring kernels walk plain images only)
     qt_set_error("qt_conv2d_wgrad: region mode needs the tile-resident kernel");
     return QT_ERR_UNSUPPORTED;
   }
-  if (variant == 2) return launch_patch<2, 2, 8, 4>(a, workspace_bytes, oihw, s);
-  return launch_patch<kGroups, 4, 16, 8>(a, workspace_bytes, oihw, s);
+  if (variant == 2) return launch_patch<2, 2, 8, 4>(a, workspace_bytes, oihw, s, ss);
+  return launch_patch<kGroups, 4, 16, 8>(a, workspace_bytes, oihw, s, ss);
 }

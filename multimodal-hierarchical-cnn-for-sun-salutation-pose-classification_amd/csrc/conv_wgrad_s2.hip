@@ -29,11 +29,7 @@
 // deterministic, no atomics, no zero fill.
 #include <stdlib.h>
 
-#include "qt_common.h"
-
-// conv_wgrad_patch.hip: dw = sum over ranges of part[range][...] (fixed order).  layout 1: j = (n*9 + tap)*KC + c ->
-// OIHW element (n*KC + c)*9 + tap;  2: written as is ([N][1][KC] is OIHW already)
-int qt_wgrad_partial_sum_launch(const float* part, float* dw, size_t filt, int nsplit, int KC, int layout, hipStream_t stream);
+#include "qt_internal.h"
 
 namespace {
 
@@ -54,8 +50,6 @@ struct WS2Args {
   FastDiv div_pp, div_pw;
   int tap_plane[9], tap_shift[9];
 };
-
-__device__ __forceinline__ QT_LDS_AS s16x4* lds_tr_ptr(unsigned lds_byte) { return (QT_LDS_AS s16x4*)(size_t)lds_byte; }
 
 // NPL planes staged (4: conv1; 1: the downsample, plane (0,0) only), NTAP taps accumulated (9 / 1).
 // NB tile buffers (2 or 3: NB - 1 tiles of look-ahead -- the kernel is bound by the latency of its LDS-DMA, a tile's MFMAs
@@ -327,7 +321,7 @@ size_t qt_wgrad_s2_workspace_bytes(const qt_conv_desc* d) {
 
 // grad_oihw [n_out][k_per_tap][kh][kw] f32 is WRITTEN (not accumulated)
 int qt_wgrad_s2_launch(const qt_conv_desc* d, const void* dy, const void* x, float* grad_oihw, void* workspace,
-                       size_t workspace_bytes, void* stream) {
+                       size_t workspace_bytes, void* stream, void* sum_stream) {
   const bool k3 = d->kh == 3;
   WS2Args a;
   a.dy = static_cast<const bf16_t*>(dy);
@@ -399,5 +393,6 @@ int qt_wgrad_s2_launch(const qt_conv_desc* d, const void* dy, const void* x, flo
     return QT_ERR_UNSUPPORTED;
   }
   QT_CHECK_LAUNCH();
-  return qt_wgrad_partial_sum_launch(a.part, grad_oihw, filt, real_split, a.KC, k3 ? 1 : 2, s);
+  return qt_wgrad_partial_sum_launch(a.part, grad_oihw, filt, real_split, a.KC, k3 ? 1 : 2, s,
+                                     static_cast<hipStream_t>(sum_stream));
 }

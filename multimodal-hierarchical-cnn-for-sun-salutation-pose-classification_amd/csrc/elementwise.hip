@@ -8,16 +8,9 @@
 // /root/reference/Quadtree_from scratch/models.py:222-243; the quadrant head's
 // ReLU + MaxPool2d(2,2) + flatten + torch.cat at :236-237,284-294; nn.Dropout at
 // :258,269; and their autograd backward.
-#include <type_traits>
-
 #include "qt_common.h"
 
 namespace {
-
-int grid_for(long long total, int block = 256, int cap = 16384) {
-  long long g = (total + block - 1) / block;
-  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
 
 __device__ __forceinline__ void load8f(const float* p, float (&v)[8]) { QtVec8<float>::load(p, v); }
 
@@ -876,8 +869,6 @@ __global__ __launch_bounds__(1024) void col_sum_finish_kernel(const float* __res
 
 }  // namespace
 
-#define QT_DT_OK(dtype, name) QT_CHECK_ARG((dtype) == QT_F32 || (dtype) == QT_BF16, name ": bad dtype %d", (dtype))
-
 // Long row counts are first folded 256:1 into the spare rows behind `rows`.
 static int fold_partial(float*& partial, int& rows, int C, hipStream_t s) {
   if (rows <= 1024) return QT_OK;  // the finalize kernels (16 row groups) cover this directly
@@ -940,13 +931,12 @@ extern "C" int qt_bn_act_mask(int dtype, const void* y, const float* scale, cons
   QT_CHECK_ARG(y && scale && shift && out && M > 0 && C > 0 && C % 8 == 0, "qt_bn_act: bad argument");
   QT_CHECK_ARG((res_scale == nullptr) == (res_shift == nullptr), "qt_bn_act: res_scale/res_shift must come in pairs");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for(M * (C / 8));
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(bn_act_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)y, scale, shift,
-                       (const float*)residual, res_scale, res_shift, relu, (float*)out, mask_bits, M, C);
-  else
-    hipLaunchKernelGGL(bn_act_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift,
-                       (const bf16_t*)residual, res_scale, res_shift, relu, (bf16_t*)out, mask_bits, M, C);
+  const int grid = qt_grid_for(M * (C / 8), 256, 16384);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(bn_act_kernel<T>, dim3(grid), dim3(256), 0, s, qt_as<T>(y), scale, shift, qt_as<T>(residual), res_scale,
+                       res_shift, relu, qt_as<T>(out), mask_bits, M, C);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -981,12 +971,11 @@ extern "C" int qt_bn_bwd_reduce(int dtype, const void* g, const void* mask, cons
   const int RL = 256 / (C / 8);
   const int lds = RL * C * 2 * 4;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(grid), dim3(256), lds, s, (const float*)g, (const float*)mask,
-                       (const float*)y, mean, invstd, partial, M, C, rpb);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(grid), dim3(256), lds, s, (const bf16_t*)g,
-                       (const bf16_t*)mask, (const bf16_t*)y, mean, invstd, partial, M, C, rpb);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(grid), dim3(256), lds, s, qt_as<T>(g), qt_as<T>(mask), qt_as<T>(y), mean,
+                       invstd, partial, M, C, rpb);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -1008,22 +997,22 @@ extern "C" int qt_bn_bwd_apply(int dtype, const void* g, const void* mask, const
   QT_DT_OK(dtype, "qt_bn_bwd_apply");
   QT_CHECK_ARG(g && y && mean && invstd && coef && dy && M > 0 && C > 0 && C % 8 == 0, "qt_bn_bwd_apply: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for(M * (C / 8));
+  const int grid = qt_grid_for(M * (C / 8), 256, 16384);
   static const int light = qt_env_int("QTCNN_BN_APPLY_LIGHT", 1);
   const int cgs = C / 4;   // (4-channel groups per row)
-  const int lgrid = grid_for(M * cgs);
+  const int lgrid = qt_grid_for(M * cgs, 256, 16384);
+  // (a dtype branch: the light kernel exists for bf16 only)
   if (light && dtype == QT_BF16 && !mask && !g_out && ((long long)lgrid * 256) % cgs == 0 && M * cgs < (1ll << 29)) {
     hipLaunchKernelGGL(bn_bwd_apply_light_kernel, dim3(lgrid), dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)y, mean, invstd, coef,
                        (bf16_t*)dy, M * cgs, cgs, C);
     QT_CHECK_LAUNCH();
     return QT_OK;
   }
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)g, (const float*)mask,
-                       (const float*)y, mean, invstd, coef, (float*)dy, (float*)g_out, M, C);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)mask,
-                       (const bf16_t*)y, mean, invstd, coef, (bf16_t*)dy, (bf16_t*)g_out, M, C);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid), dim3(256), 0, s, qt_as<T>(g), qt_as<T>(mask), qt_as<T>(y), mean,
+                       invstd, coef, qt_as<T>(dy), qt_as<T>(g_out), M, C);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -1033,13 +1022,12 @@ extern "C" int qt_stem_pool(int dtype, const void* y, const float* scale, const 
   QT_DT_OK(dtype, "qt_stem_pool");
   QT_CHECK_ARG(y && scale && shift && pooled && batch > 0, "qt_stem_pool: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for((long long)batch * 56 * 56 * 8);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(stem_pool_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)y, scale, shift,
-                       (float*)pooled, argmax, (float*)y_at_max, batch);
-  else
-    hipLaunchKernelGGL(stem_pool_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift,
-                       (bf16_t*)pooled, argmax, (bf16_t*)y_at_max, batch);
+  const int grid = qt_grid_for((long long)batch * 56 * 56 * 8, 256, 16384);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(stem_pool_kernel<T>, dim3(grid), dim3(256), 0, s, qt_as<T>(y), scale, shift, qt_as<T>(pooled), argmax,
+                       qt_as<T>(y_at_max), batch);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -1064,11 +1052,11 @@ extern "C" int qt_stem_pool_bwd(int dtype, const void* dpooled, const unsigned c
   QT_DT_OK(dtype, "qt_stem_pool_bwd");
   QT_CHECK_ARG(dpooled && argmax && y && scale && shift && g && batch > 0, "qt_stem_pool_bwd: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for((long long)batch * 112 * 112 * 8);
-  if (dtype == QT_F32)
-    launch_stem_bwd<float>(0, grid, s, dpooled, argmax, y, scale, shift, nullptr, nullptr, nullptr, nullptr, g, batch);
-  else
-    launch_stem_bwd<bf16_t>(0, grid, s, dpooled, argmax, y, scale, shift, nullptr, nullptr, nullptr, nullptr, g, batch);
+  const int grid = qt_grid_for((long long)batch * 112 * 112 * 8, 256, 16384);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    launch_stem_bwd<T>(0, grid, s, dpooled, argmax, y, scale, shift, nullptr, nullptr, nullptr, nullptr, g, batch);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -1087,10 +1075,10 @@ extern "C" int qt_stem_bn_bwd_reduce(int dtype, const void* dpooled, const unsig
                "qt_stem_bn_bwd_reduce: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int grid = stem_bwd_rows(batch);
-  if (dtype == QT_F32)
-    launch_stem_bwd<float>(1, grid, s, dpooled, argmax, y, scale, shift, mean, invstd, nullptr, partial, nullptr, batch);
-  else
-    launch_stem_bwd<bf16_t>(1, grid, s, dpooled, argmax, y, scale, shift, mean, invstd, nullptr, partial, nullptr, batch);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    launch_stem_bwd<T>(1, grid, s, dpooled, argmax, y, scale, shift, mean, invstd, nullptr, partial, nullptr, batch);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -1180,18 +1168,18 @@ extern "C" int qt_stem_bn_bwd_sums(int dtype, const void* dpooled, const void* y
   const int grid = stem_sums_rows(batch);
   const long long total = (long long)batch * 56 * 56 * 8;
   static const int light = qt_env_int("QTCNN_STEM_SUMS_LIGHT", 1);   // (default 1): 0 = the general kernel (same-box A/B)
+  // (a dtype branch: the light kernel exists for bf16 only)
   if (light && dtype == QT_BF16 && total * 2 < (1ll << 30)) {
     hipLaunchKernelGGL(stem_bn_bwd_sums_light_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)dpooled, (const bf16_t*)y_at_max,
                        scale, shift, mean, invstd, partial, (unsigned)(total * 2));
     QT_CHECK_LAUNCH();
     return QT_OK;
   }
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(stem_bn_bwd_sums_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)dpooled,
-                       (const float*)y_at_max, scale, shift, mean, invstd, partial, total);
-  else
-    hipLaunchKernelGGL(stem_bn_bwd_sums_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)dpooled,
-                       (const bf16_t*)y_at_max, scale, shift, mean, invstd, partial, total);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(stem_bn_bwd_sums_kernel<T>, dim3(grid), dim3(256), 0, s, qt_as<T>(dpooled), qt_as<T>(y_at_max), scale,
+                       shift, mean, invstd, partial, total);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -1203,25 +1191,15 @@ extern "C" int qt_stem_bn_bwd_apply(int dtype, const void* dpooled, const unsign
   QT_CHECK_ARG(dpooled && argmax && y && scale && shift && mean && invstd && coef && dy && batch > 0,
                "qt_stem_bn_bwd_apply: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for((long long)batch * 56 * 56 * 8);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(stem_bn_bwd_apply2x2_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)dpooled, argmax,
-                       (const float*)y, scale, shift, mean, invstd, coef, (float*)dy, batch);
-  else
-    hipLaunchKernelGGL(stem_bn_bwd_apply2x2_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)dpooled, argmax,
-                       (const bf16_t*)y, scale, shift, mean, invstd, coef, (bf16_t*)dy, batch);
+  const int grid = qt_grid_for((long long)batch * 56 * 56 * 8, 256, 16384);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(stem_bn_bwd_apply2x2_kernel<T>, dim3(grid), dim3(256), 0, s, qt_as<T>(dpooled), argmax, qt_as<T>(y),
+                       scale, shift, mean, invstd, coef, qt_as<T>(dy), batch);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
-
-template <typename F>
-static void by_dtype(int dtype, F&& f) {
-  if (dtype == QT_F32)
-    f(static_cast<float*>(nullptr));
-  else
-    f(static_cast<bf16_t*>(nullptr));
-}
-#define QT_T(tag) std::remove_pointer_t<decltype(tag)>
 
 extern "C" int qt_avgpool(int dtype, const void* x, void* dst, int batch, int hw, int C, int ld, int col0,
                           void* stream) {
@@ -1229,10 +1207,10 @@ extern "C" int qt_avgpool(int dtype, const void* x, void* dst, int batch, int hw
   QT_CHECK_ARG(x && dst && batch > 0 && hw > 0 && C > 0 && C % 8 == 0 && ld % 8 == 0 && col0 % 8 == 0 && col0 + C <= ld,
                "qt_avgpool: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(avgpool_kernel<T>, dim3(grid_for((long long)batch * (C / 8), 64)), dim3(64), 0, s,
-                       (const T*)x, (T*)dst, batch, hw, C, ld, col0);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(avgpool_kernel<T>, dim3(qt_grid_for((long long)batch * (C / 8), 64, 16384)), dim3(64), 0, s,
+                       qt_as<T>(x), qt_as<T>(dst), batch, hw, C, ld, col0);
   });
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -1244,10 +1222,10 @@ extern "C" int qt_avgpool_bwd(int dtype, const void* d, const void* x, void* g, 
   QT_CHECK_ARG(d && x && g && batch > 0 && hw > 0 && C > 0 && C % 8 == 0 && ld % 8 == 0 && col0 % 8 == 0 && col0 + C <= ld,
                "qt_avgpool_bwd: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(grid_for((long long)batch * hw * (C / 8))), dim3(256), 0, s,
-                       (const T*)d, (const T*)x, (T*)g, batch, hw, C, ld, col0);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(qt_grid_for((long long)batch * hw * (C / 8), 256, 16384)), dim3(256), 0, s,
+                       qt_as<T>(d), qt_as<T>(x), qt_as<T>(g), batch, hw, C, ld, col0);
   });
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -1257,10 +1235,10 @@ extern "C" int qt_quad_pool(int dtype, const void* q, void* dst, int batch, int 
   QT_DT_OK(dtype, "qt_quad_pool");
   QT_CHECK_ARG(q && dst && batch > 0 && col0 >= 0 && col0 + 4 * 1152 <= ld, "qt_quad_pool: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(quad_pool_kernel<T>, dim3(grid_for((long long)batch * 4 * 9 * 128)), dim3(256), 0, s,
-                       (const T*)q, (T*)dst, batch, ld, col0);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(quad_pool_kernel<T>, dim3(qt_grid_for((long long)batch * 4 * 9 * 128, 256, 16384)), dim3(256), 0, s,
+                       qt_as<T>(q), qt_as<T>(dst), batch, ld, col0);
   });
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -1271,10 +1249,10 @@ extern "C" int qt_quad_pool_bwd(int dtype, const void* d, const void* q, void* d
   QT_DT_OK(dtype, "qt_quad_pool_bwd");
   QT_CHECK_ARG(d && q && dq && batch > 0 && col0 >= 0 && col0 + 4 * 1152 <= ld, "qt_quad_pool_bwd: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(quad_pool_bwd_kernel<T>, dim3(grid_for((long long)batch * 4 * 22 * 16)), dim3(256), 0, s,
-                       (const T*)d, (const T*)q, (T*)dq, batch, ld, col0);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(quad_pool_bwd_kernel<T>, dim3(qt_grid_for((long long)batch * 4 * 22 * 16, 256, 16384)), dim3(256), 0, s,
+                       qt_as<T>(d), qt_as<T>(q), qt_as<T>(dq), batch, ld, col0);
   });
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -1285,9 +1263,9 @@ extern "C" int qt_dropout(int dtype, void* x, long long rows, int cols, int ld, 
   QT_DT_OK(dtype, "qt_dropout");
   QT_CHECK_ARG(x && rows > 0 && cols > 0 && ld >= cols && p >= 0.f && p < 1.f, "qt_dropout: bad argument (p=%f)", p);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(dropout_kernel<T>, dim3(grid_for(rows * cols)), dim3(256), 0, s, (T*)x, rows, cols, ld, seed, p);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(dropout_kernel<T>, dim3(qt_grid_for(rows * cols, 256, 16384)), dim3(256), 0, s, qt_as<T>(x), rows, cols, ld, seed, p);
   });
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -1297,9 +1275,9 @@ extern "C" int qt_relu_mask_scale(int dtype, void* g, const void* act, long long
   QT_DT_OK(dtype, "qt_relu_mask_scale");
   QT_CHECK_ARG(g && act && n > 0, "qt_relu_mask_scale: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(relu_mask_scale_kernel<T>, dim3(grid_for(n)), dim3(256), 0, s, (T*)g, (const T*)act, n, mul);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(relu_mask_scale_kernel<T>, dim3(qt_grid_for(n, 256, 16384)), dim3(256), 0, s, qt_as<T>(g), qt_as<T>(act), n, mul);
   });
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -1315,9 +1293,9 @@ extern "C" int qt_col_sum(int dtype, const void* x, long long rows, int cols, in
     return QT_ERR_LAUNCH;
   }
   const int rpb = 128;
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(col_sum_kernel<T>, dim3(qt_cdiv(cols, 64), qt_cdiv(rows, rpb)), dim3(256), 0, s, (const T*)x,
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(col_sum_kernel<T>, dim3(qt_cdiv(cols, 64), qt_cdiv(rows, rpb)), dim3(256), 0, s, qt_as<T>(x),
                        rows, cols, ld, out, rpb, (float*)nullptr);
   });
   QT_CHECK_LAUNCH();
@@ -1342,9 +1320,9 @@ extern "C" int qt_col_sum_ws(int dtype, const void* x, long long rows, int cols,
   const int nparts = qt_cdiv(rows, 128) < kColSumMaxParts ? qt_cdiv(rows, 128) : kColSumMaxParts;
   const int rpb = qt_cdiv(rows, nparts);
   float* part = static_cast<float*>(workspace);
-  by_dtype(dtype, [&](auto tag) {
-    using T = QT_T(tag);
-    hipLaunchKernelGGL(col_sum_kernel<T>, dim3(qt_cdiv(cols, 64), qt_cdiv(rows, rpb)), dim3(256), 0, s, (const T*)x,
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(col_sum_kernel<T>, dim3(qt_cdiv(cols, 64), qt_cdiv(rows, rpb)), dim3(256), 0, s, qt_as<T>(x),
                        rows, cols, ld, out, rpb, part);
   });
   hipLaunchKernelGGL(col_sum_finish_kernel, dim3(qt_cdiv(cols, 64)), dim3(1024), 0, s, (const float*)part,

@@ -189,7 +189,7 @@ extern "C" int qt_gemm_small(const qt_gemm_small_desc* d, const void* A, const v
   QT_CHECK_ARG(d && A && B && C, "qt_gemm_small: null argument");
   QT_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "qt_gemm_small: bad shape %dx%dx%d", d->M, d->N, d->K);
   for (int t : {d->a_dtype, d->b_dtype, d->c_dtype})
-    QT_CHECK_ARG(t == QT_F32 || t == QT_BF16, "qt_gemm_small: bad dtype %d", t);
+    QT_DT_OK(t, "qt_gemm_small");
   SmallArgs a;
   a.A = A; a.B = B; a.bias = bias; a.C = C;
   a.ars = d->a_row_stride; a.aks = d->a_k_stride; a.brs = d->b_row_stride; a.bks = d->b_k_stride; a.crs = d->c_row_stride;

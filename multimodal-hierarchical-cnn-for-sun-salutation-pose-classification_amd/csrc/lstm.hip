@@ -194,12 +194,11 @@ extern "C" int qt_scale_by_nonzero(float* g, const float* x, long long n, float 
 
 extern "C" int qt_cast_f32(int dtype, const void* src, float* dst, long long n, void* stream) {
   QT_CHECK_ARG((dtype == QT_F32 || dtype == QT_BF16) && src && dst && n > 0, "qt_cast_f32: bad argument");
-  long long blocks = (n + 255) / 256;
-  const dim3 grid((unsigned)(blocks > 8192 ? 8192 : blocks));
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(cast_f32_kernel<float>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), (const float*)src, dst, n);
-  else
-    hipLaunchKernelGGL(cast_f32_kernel<bf16_t>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), (const bf16_t*)src, dst, n);
+  const dim3 grid(qt_grid_for(n, 256, 8192));
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(cast_f32_kernel<T>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), qt_as<T>(src), dst, n);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }

@@ -335,24 +335,17 @@ __global__ void unpack_stem_wgrad_kernel(const float* __restrict__ dw, float* __
   grad[idx] = accumulate ? grad[idx] + v : v;
 }
 
-int grid_for(long long total, int block = 256) {
-  long long g = (total + block - 1) / block;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 }  // namespace
 
 extern "C" int qt_pack_stem_input(int dtype, const float* image_nchw, void* dst, int batch, void* stream) {
   QT_CHECK_ARG(image_nchw && dst && batch > 0, "qt_pack_stem_input: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_stem_input: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_stem_input");
   const long long total = (long long)batch * QT_STEM_PAD_H * QT_STEM_PAD_W;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_stem_input_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, image_nchw,
-                       static_cast<float*>(dst), batch);
-  else
-    hipLaunchKernelGGL(pack_stem_input_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, image_nchw,
-                       static_cast<bf16_t*>(dst), batch);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(pack_stem_input_kernel<T>, dim3(qt_grid_for(total, 256, 8192)), dim3(256), 0, s, image_nchw, qt_as<T>(dst), batch);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -360,15 +353,14 @@ extern "C" int qt_pack_stem_input(int dtype, const float* image_nchw, void* dst,
 extern "C" int qt_pack_conv_weight(int dtype, const float* w_oihw, void* w_fwd, void* w_dgrad, int O, int I, int kh,
                                    int kw, void* stream) {
   QT_CHECK_ARG(w_oihw && (w_fwd || w_dgrad) && O > 0 && I > 0 && kh > 0 && kw > 0, "qt_pack_conv_weight: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_conv_weight: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_conv_weight");
   const long long total = (long long)O * I * kh * kw;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_conv_weight_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw,
-                       static_cast<float*>(w_fwd), static_cast<float*>(w_dgrad), O, I, kh * kw);
-  else
-    hipLaunchKernelGGL(pack_conv_weight_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw,
-                       static_cast<bf16_t*>(w_fwd), static_cast<bf16_t*>(w_dgrad), O, I, kh * kw);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(pack_conv_weight_kernel<T>, dim3(qt_grid_for(total, 256, 8192)), dim3(256), 0, s, w_oihw, qt_as<T>(w_fwd),
+                       qt_as<T>(w_dgrad), O, I, kh * kw);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -443,7 +435,7 @@ extern "C" int qt_adam_multi_scaled(const qt_adam_item* items, int n, const qt_a
 static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item* opt, const qt_adam_desc* adam,
                         const float* grad_scale_dev, int n, void* stream) {
   QT_CHECK_ARG(items && n > 0 && n <= PK_MAX_ITEMS, "qt_pack_weights_batched: 1..%d items", PK_MAX_ITEMS);
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_weights_batched: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_weights_batched");
   PackBatchArgs a;
   memset(&a, 0, sizeof(a));
   if (opt) {
@@ -480,10 +472,10 @@ static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item
   a.first_block[n] = blocks;
   a.n = n;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_weights_batched_kernel<float>, dim3(blocks), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL(pack_weights_batched_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, a);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(pack_weights_batched_kernel<T>, dim3(blocks), dim3(256), 0, s, a);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -491,7 +483,7 @@ static int pack_batched(int dtype, const qt_pack_item* items, const qt_adam_item
 extern "C" int qt_pack_dgrad_s2(int dtype, const float* w_oihw, void* dst, int O, int I, int k, long long* class_offset,
                                 int* class_kh, int* class_kw, void* stream) {
   QT_CHECK_ARG(w_oihw && O > 0 && I > 0 && (k == 1 || k == 3), "qt_pack_dgrad_s2: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_dgrad_s2: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_dgrad_s2");
   long long base = 0;
   for (int cls = 0; cls < 4; ++cls) {
     const int nh = (cls >> 1) ? (k == 3 ? 2 : 0) : 1, nw = (cls & 1) ? (k == 3 ? 2 : 0) : 1;
@@ -503,45 +495,41 @@ extern "C" int qt_pack_dgrad_s2(int dtype, const float* w_oihw, void* dst, int O
   if (!dst) return QT_OK;  // layout query only
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long total = (long long)O * I * k * k;
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_dgrad_s2_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw,
-                       static_cast<float*>(dst), O, I, k);
-  else
-    hipLaunchKernelGGL(pack_dgrad_s2_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw,
-                       static_cast<bf16_t*>(dst), O, I, k);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(pack_dgrad_s2_kernel<T>, dim3(qt_grid_for(total, 256, 8192)), dim3(256), 0, s, w_oihw, qt_as<T>(dst), O, I, k);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
 
 extern "C" int qt_pack_dgrad_s2_merged(int dtype, const float* w_oihw, void* dst, int O, int I, void* stream) {
   QT_CHECK_ARG(w_oihw && dst && O > 0 && I > 0, "qt_pack_dgrad_s2_merged: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_dgrad_s2_merged: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_dgrad_s2_merged");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t esz = dtype == QT_F32 ? 4 : 2;
+  const size_t esz = qt_dtype_size(dtype);
   if (hipMemsetAsync(dst, 0, (size_t)16 * O * I * esz, s) != hipSuccess) {
     qt_set_error("qt_pack_dgrad_s2_merged: memset failed");
     return QT_ERR_LAUNCH;
   }
   const long long total = (long long)O * I * 9;
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_dgrad_s2m_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<float*>(dst), O, I);
-  else
-    hipLaunchKernelGGL(pack_dgrad_s2m_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<bf16_t*>(dst), O, I);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(pack_dgrad_s2m_kernel<T>, dim3(qt_grid_for(total, 256, 8192)), dim3(256), 0, s, w_oihw, qt_as<T>(dst), O, I);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
 
 extern "C" int qt_pack_stem_weight(int dtype, const float* w_oihw, void* dst, int taps, void* stream) {
   QT_CHECK_ARG(w_oihw && dst && (taps == 7 || taps == 8), "qt_pack_stem_weight: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_stem_weight: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_stem_weight");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int total = 64 * taps * 32;
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_stem_weight_kernel<float>, dim3(qt_cdiv(total, 256)), dim3(256), 0, s, w_oihw,
-                       static_cast<float*>(dst), taps);
-  else
-    hipLaunchKernelGGL(pack_stem_weight_kernel<bf16_t>, dim3(qt_cdiv(total, 256)), dim3(256), 0, s, w_oihw,
-                       static_cast<bf16_t*>(dst), taps);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(pack_stem_weight_kernel<T>, dim3(qt_cdiv(total, 256)), dim3(256), 0, s, w_oihw, qt_as<T>(dst), taps);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -550,7 +538,7 @@ extern "C" int qt_unpack_conv_wgrad(const float* dw, float* grad_oihw, int O, in
                                     void* stream) {
   QT_CHECK_ARG(dw && grad_oihw && O > 0 && I > 0 && kh > 0 && kw > 0, "qt_unpack_conv_wgrad: bad argument");
   const long long total = (long long)O * I * kh * kw;
-  hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), dw,
+  hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(qt_grid_for(total, 256, 8192)), dim3(256), 0, static_cast<hipStream_t>(stream), dw,
                      grad_oihw, O, I, kh * kw, accumulate);
   QT_CHECK_LAUNCH();
   return QT_OK;

@@ -684,7 +684,7 @@ struct Exec {
   // implicit GEMM on 1x1 images.  d describes the product like a 1x1 convolution.
   void linear(const qt_conv_desc& d, const void* x, const void* w, void* y, const float* bias, int relu) {
     if (!ok()) return;
-    if (dt == QT_BF16 && B <= 256) {
+    if (dt == QT_BF16 && B <= 256) {   // (a dtype branch: the thin-batch GEMM exists for bf16 only)
       const int slot = begin_timed(conv_flops(d), d.mode == QT_CONV_FWD ? 0 : 1, nullptr,
                                    2.0 * ((double)B * d.k_per_tap + (double)d.k_per_tap * d.n_out + (double)B * d.n_out));
       const int st = qt_linear_bf16(x, w, bias, relu, y, B, d.n_out, d.k_per_tap, at(p->lin_ws), p->lin_ws_bytes, stream);
@@ -711,7 +711,7 @@ struct Exec {
   }
   // algorithmic HBM bytes of a conv launch: source map, weights, destination and every per-pixel epilogue operand, each once
   double conv_bytes(const qt_conv_desc& d, const qt_conv_io& io) const {
-    const double es = d.dtype == QT_F32 ? 4.0 : 2.0;
+    const double es = qt_dtype_size(d.dtype);
     const double imgs = (double)d.batch;
     const bool stem = d.k_per_tap == 32 && d.kw == 1 && d.stride == 2 && d.n_out == 64;
     const double regions = qt_quad_regions(d.quad);
@@ -794,7 +794,7 @@ struct Exec {
       io.stats_conv = at<float>(p->stats);
       io.stats_down = at<float>(p->stats_ds);
     }
-    const double es = dt == QT_F32 ? 4.0 : 2.0;
+    const double es = qt_dtype_size(dt);
     const int slot = begin_timed(conv_flops(conv_desc(c1, QT_CONV_FWD)) + conv_flops(conv_desc(cd, QT_CONV_FWD)), 0, nullptr,
                                  es * ((double)B * c1.hin * c1.hin * c1.cin + 2.0 * B * c1.hout * c1.hout * c1.cout +
                                        10.0 * c1.cin * c1.cout));
@@ -1270,7 +1270,7 @@ struct Bwd : Exec {
     return rows;
   }
   double wgrad_bytes(const ConvL& c, const qt_conv_desc& f) const {
-    const double es = dt == QT_F32 ? 4.0 : 2.0, imgs = (double)f.batch * qt_quad_regions(f.quad);
+    const double es = qt_dtype_size(dt), imgs = (double)f.batch * qt_quad_regions(f.quad);
     return es * imgs * ((double)f.in_h * f.in_w * f.k_per_tap + (double)f.out_h * f.out_w * f.n_out) +
            4.0 * f.kh * f.kw * f.k_per_tap * f.n_out;
   }
@@ -1661,7 +1661,7 @@ int backward(qt_plan* p, void* workspace, void* const* T, float* const* G, const
 // ---------------------------------------------------------------------------------
 extern "C" int qt_plan_create(const qt_plan_desc* desc, qt_plan** out) {
   QT_CHECK_ARG(desc && out, "qt_plan_create: null argument");
-  QT_CHECK_ARG(desc->dtype == QT_F32 || desc->dtype == QT_BF16, "qt_plan_create: bad dtype %d", desc->dtype);
+  QT_DT_OK(desc->dtype, "qt_plan_create");
   QT_CHECK_ARG(desc->batch > 0 && desc->batch <= 4096, "qt_plan_create: batch %d out of range", desc->batch);
   QT_CHECK_ARG(desc->num_classes > 0 && desc->num_classes <= 4096, "qt_plan_create: bad num_classes");
   QT_CHECK_ARG(desc->model == QT_MODEL_QUADTREE || desc->model == QT_MODEL_STANDARD_RESNET ||
@@ -1677,7 +1677,7 @@ extern "C" int qt_plan_create(const qt_plan_desc* desc, qt_plan** out) {
   QT_CHECK_ARG(desc->dropout_p >= 0.f && desc->dropout_p < 1.f, "qt_plan_create: bad dropout_p");
   qt_plan* p = new qt_plan();
   p->d = *desc;
-  p->esz = desc->dtype == QT_F32 ? 4 : 2;
+  p->esz = qt_dtype_size(desc->dtype);
   p->use_side = qt_env_int("QTCNN_SIDE_STREAM", 1) != 0;   // (per plan: read at every qt_plan_create)
   build_graph(p);
   layout_workspace(p);

@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "../../include/qtcnn.h"
 
 typedef __bf16 bf16_t;
@@ -17,6 +20,10 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 // thread-local last-error text (qt_last_error)
 void qt_set_error(const char* fmt, ...);
+// One timing-free event of the calling host thread on the current device, created at first use and kept (nullptr on a HIP
+// error): orders a launch on one stream behind work on another.  A stream's wait holds the record it saw, so the event is
+// free to be recorded again as soon as hipStreamWaitEvent has returned.
+hipEvent_t qt_thread_event();
 
 // value of environment switch `name` (atoi), or `dflt` when unset; each call site caches it in a function-local static
 // (or in the global its qt_set_* setter writes) at first use, so a switch is read once per process
@@ -42,6 +49,22 @@ static inline int qt_env_int(const char* name, int dflt) {
       return QT_ERR_LAUNCH;                                            \
     }                                                                  \
   } while (0)
+
+#define QT_DT_OK(dtype, name) QT_CHECK_ARG((dtype) == QT_F32 || (dtype) == QT_BF16, name ": bad dtype %d", (dtype))
+
+// Element-type dispatch of the launchers (host): calls f with a null float* or bf16_t* as the type tag and returns what f
+// returns.  The dtype is checked beforehand (QT_DT_OK); the launch itself stays at the site:
+//   qt_by_dtype(dtype, [&](auto* t) { using T = QT_T(t); hipLaunchKernelGGL(k<T>, ..., qt_as<T>(x), ...); });
+template <typename F>
+static inline auto qt_by_dtype(int dtype, F&& f) {
+  return dtype == QT_F32 ? f(static_cast<float*>(nullptr)) : f(static_cast<bf16_t*>(nullptr));
+}
+// bytes per element of a checked dtype
+static inline int qt_dtype_size(int dtype) { return dtype == QT_F32 ? 4 : 2; }
+#define QT_T(tag) std::remove_pointer_t<decltype(tag)>
+// an untyped C-ABI pointer as elements of T (constness follows the argument)
+template <typename T> static inline const T* qt_as(const void* p) { return static_cast<const T*>(p); }
+template <typename T> static inline T* qt_as(void* p) { return static_cast<T*>(p); }
 
 template <typename T> struct QtElem;
 template <> struct QtElem<float> { static constexpr int kDtype = QT_F32; };
@@ -176,8 +199,41 @@ __device__ __forceinline__ void blds16(const i32x4& rsrc, unsigned voff, unsigne
       : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_addr)
       : "memory");
 }
+// two / four transfers 8 KiB apart in LDS (consecutive 64-row passes of a tile), M0 saved once
+__device__ __forceinline__ void blds16x2(const i32x4& rsrc, unsigned v0, unsigned v1, unsigned soff, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\t"
+      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(v0), "v"(v1), "s"(rsrc), "s"(soff), "s"(lds_addr)
+      : "memory", "scc");
+}
+__device__ __forceinline__ void blds16x4(const i32x4& rsrc, unsigned v0, unsigned v1, unsigned v2, unsigned v3, unsigned soff,
+                                         unsigned lds_addr) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %5, %6 offen lds\n\t"
+      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %5, %6 offen lds\n\t"
+      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %5, %6 offen lds\n\t"
+      "s_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %5, %6 offen lds\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(rsrc), "s"(soff), "s"(lds_addr)
+      : "memory", "scc");
+}
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
   return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)p);
+}
+// operand of the transposing LDS read (ds_read_b64_tr_b16) at LDS byte address `lds_byte`
+__device__ __forceinline__ QT_LDS_AS s16x4* lds_tr_ptr(unsigned lds_byte) { return (QT_LDS_AS s16x4*)(size_t)lds_byte; }
+
+// f(std::integral_constant<int, I>{}) for I = 0 .. N-1, unrolled at compile time
+template <int N, int I = 0, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<N, I + 1>(f);
+  }
 }
 
 
@@ -217,6 +273,12 @@ static inline int qt_raise_lds_limit(const void* kern, int lds_bytes, std::atomi
 }
 
 static inline int qt_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// workgroups of `block` threads for `total` items, at least 1 and at most `cap`.  The cap is spelled out at every call: the
+// grid-stride reductions sum in an order that follows their grid size, so a call's cap is part of its result.
+static inline int qt_grid_for(long long total, int block, int cap) {
+  const long long g = (total + block - 1) / block;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
 // qt_conv_desc::quad: 0 = whole images, 1 or 2 = 2 x 2 regions per image, 4 = 4 x 4 regions
 static inline int qt_quad_split(int quad) { return quad == 1 ? 2 : quad; }
 static inline int qt_quad_regions(int quad) { return quad ? qt_quad_split(quad) * qt_quad_split(quad) : 1; }

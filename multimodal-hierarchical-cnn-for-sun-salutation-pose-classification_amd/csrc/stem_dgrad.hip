@@ -198,6 +198,5 @@ extern "C" int qt_stem_dgrad(int dtype, const void* dy, const float* w_oihw, flo
     qt_set_error("qt_stem_dgrad: bf16 or f32 dy with 16-byte aligned dy and 8-byte aligned dx only");
     return QT_ERR_UNSUPPORTED;
   }
-  return dtype == QT_BF16 ? launch_stem_dgrad<bf16_t>(dy, w_oihw, dx, batch, stream)
-                          : launch_stem_dgrad<float>(dy, w_oihw, dx, batch, stream);
+  return qt_by_dtype(dtype, [&](auto* t) { return launch_stem_dgrad<QT_T(t)>(dy, w_oihw, dx, batch, stream); });
 }

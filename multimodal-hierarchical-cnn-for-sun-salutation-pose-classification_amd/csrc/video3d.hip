@@ -417,11 +417,6 @@ __global__ void avgpool_tb_bwd_kernel(const float* __restrict__ d, T* __restrict
   }
 }
 
-inline unsigned grid_for(long long n) {
-  const long long b = (n + 255) / 256;
-  return (unsigned)(b > 65536 ? 65536 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 namespace {
@@ -554,28 +549,22 @@ extern "C" int qt_pack_conv3d_block(int dtype, const float* w, void* w_fwd, void
   QT_CHECK_ARG(w && w_fwd && vec_in_dev && vec_out && O > 0 && I > 0 && O_pad >= O && (first || I_pad >= I) &&
                    (!first || 27 * I <= 128),
                "qt_pack_conv3d_block: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_conv3d_block: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_conv3d_block");
   const long long total = (first ? (long long)O_pad * 128 : (long long)O_pad * 27 * I_pad) + 5ll * O_pad;
-  const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+  const int grid = qt_grid_for(total, 256, 4096);
   hipStream_t s = static_cast<hipStream_t>(stream);
   static const bool tiled = qt_env_int("QTCNN_PACK3D_TILED", 1) != 0;
-  if (!first && tiled && O_pad % 64 == 0 && I_pad % 64 == 0 && I % PK3_TI == 0 && ((uintptr_t)w % 16) == 0) {
-    const int blocks = (O_pad / PK3_TO) * (I_pad / PK3_TI) + 1;
-    if (dtype == QT_F32)
-      hipLaunchKernelGGL(pack_conv3d_tile_kernel<float>, dim3(blocks), dim3(256), 0, s, w, static_cast<float*>(w_fwd),
-                         static_cast<float*>(w_dgrad), O, I, O_pad, I_pad, vec_in_dev, vec_out);
-    else
-      hipLaunchKernelGGL(pack_conv3d_tile_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, w, static_cast<bf16_t*>(w_fwd),
-                         static_cast<bf16_t*>(w_dgrad), O, I, O_pad, I_pad, vec_in_dev, vec_out);
-    QT_CHECK_LAUNCH();
-    return QT_OK;
-  }
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_conv3d_block_kernel<float>, dim3(grid), dim3(256), 0, s, w, static_cast<float*>(w_fwd),
-                       static_cast<float*>(w_dgrad), O, I, O_pad, I_pad, first, vec_in_dev, vec_out);
-  else
-    hipLaunchKernelGGL(pack_conv3d_block_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, w, static_cast<bf16_t*>(w_fwd),
-                       static_cast<bf16_t*>(w_dgrad), O, I, O_pad, I_pad, first, vec_in_dev, vec_out);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    if (!first && tiled && O_pad % 64 == 0 && I_pad % 64 == 0 && I % PK3_TI == 0 && ((uintptr_t)w % 16) == 0) {
+      const int blocks = (O_pad / PK3_TO) * (I_pad / PK3_TI) + 1;
+      hipLaunchKernelGGL(pack_conv3d_tile_kernel<T>, dim3(blocks), dim3(256), 0, s, w, qt_as<T>(w_fwd), qt_as<T>(w_dgrad), O, I,
+                         O_pad, I_pad, vec_in_dev, vec_out);
+    } else {
+      hipLaunchKernelGGL(pack_conv3d_block_kernel<T>, dim3(grid), dim3(256), 0, s, w, qt_as<T>(w_fwd), qt_as<T>(w_dgrad), O, I,
+                         O_pad, I_pad, first, vec_in_dev, vec_out);
+    }
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -583,7 +572,7 @@ extern "C" int qt_pack_conv3d_block(int dtype, const float* w, void* w_fwd, void
 extern "C" int qt_unpack_conv3d_wgrad(const float* dw, float* grad, int O, int I, int O_pad, int I_pad, int first, void* stream) {
   QT_CHECK_ARG(dw && grad && O > 0 && I > 0 && O_pad >= O && (first || I_pad >= I), "qt_unpack_conv3d_wgrad: bad argument");
   const long long total = (long long)O * I * 27;
-  const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+  const int grid = qt_grid_for(total, 256, 4096);
   hipLaunchKernelGGL(unpack_conv3d_wgrad_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), dw, grad, O, I,
                      O_pad, I_pad, first);
   QT_CHECK_LAUNCH();
@@ -593,13 +582,14 @@ extern "C" int qt_unpack_conv3d_wgrad(const float* dw, float* grad, int O, int I
 extern "C" int qt_pack_clip27(int dtype, const float* clips, void* dst, int batch, int frames, int h, int w, void* stream) {
   QT_CHECK_ARG(clips && dst && batch > 0 && frames > 0 && h > 0 && w > 0, "qt_pack_clip27: bad argument");
   QT_CHECK_ARG((long long)frames * batch * h * w < (1ll << 31), "qt_pack_clip27: more than 2^31 pixel rows");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pack_clip27: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pack_clip27");
   const long long n = (long long)frames * batch * h * w * 16;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(pack_clip27_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, clips, (float*)dst, batch, frames, h, w);
-  else
-    hipLaunchKernelGGL(pack_clip27_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, s, clips, (bf16_t*)dst, batch, frames, h, w);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(pack_clip27_kernel<T>, dim3(qt_grid_for(n, 256, 65536)), dim3(256), 0, s, clips, qt_as<T>(dst), batch,
+                       frames, h, w);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -607,22 +597,21 @@ extern "C" int qt_pack_clip27(int dtype, const float* clips, void* dst, int batc
 // rows of partial sums qt_bn_stats writes for an [M][C] map (at most 1024 slabs of at least 256 rows)
 extern "C" int qt_bn_stats_rows(long long M, int C) {
   (void)C;
-  const long long slabs = (M + 255) / 256;
-  return (int)(slabs > 1024 ? 1024 : (slabs < 1 ? 1 : slabs));
+  return qt_grid_for(M, 256, 1024);
 }
 
 extern "C" int qt_bn_stats(int dtype, const void* y, long long M, int C, float* partial, void* stream) {
   QT_CHECK_ARG(y && partial && M > 0, "qt_bn_stats: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_bn_stats: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_bn_stats");
   QT_CHECK_ARG(C >= 8 && C % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0,
                "qt_bn_stats: C=%d: C / 8 must divide 256", C);
   const int rows = qt_bn_stats_rows(M, C);
   const int slab = (int)((M + rows - 1) / rows);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(bn_stats_kernel<float>, dim3(rows), dim3(256), 0, s, (const float*)y, M, C, partial, slab);
-  else
-    hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, (const bf16_t*)y, M, C, partial, slab);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(rows), dim3(256), 0, s, qt_as<T>(y), M, C, partial, slab);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -630,15 +619,17 @@ extern "C" int qt_bn_stats(int dtype, const void* y, long long M, int C, float* 
 extern "C" int qt_pool3d_max(int dtype, const void* x, void* out, unsigned char* argmax, int frames, int batch, int h, int w,
                              int C, int pool_t, void* stream) {
   QT_CHECK_ARG(x && out && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C % 8 == 0, "qt_pool3d_max: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pool3d_max: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pool3d_max");
   QT_CHECK_ARG((pool_t == 1 || pool_t == 2) && frames >= pool_t, "qt_pool3d_max: pool_t=%d (1 or 2, <= frames)", pool_t);
   const long long n = (long long)(frames / pool_t) * batch * (h / 2) * (w / 2) * (C / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(grid_for(n)), blk(256);
-#define QT_POOL(TT, PT) hipLaunchKernelGGL((pool3d_max_kernel<TT, PT>), grid, blk, 0, s, (const TT*)x, (TT*)out, argmax, frames, batch, h, w, C)
-  if (dtype == QT_F32) { if (pool_t == 1) QT_POOL(float, 1); else QT_POOL(float, 2); }
-  else { if (pool_t == 1) QT_POOL(bf16_t, 1); else QT_POOL(bf16_t, 2); }
+  const dim3 grid(qt_grid_for(n, 256, 65536)), blk(256);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+#define QT_POOL(PT) hipLaunchKernelGGL((pool3d_max_kernel<T, PT>), grid, blk, 0, s, qt_as<T>(x), qt_as<T>(out), argmax, frames, batch, h, w, C)
+    if (pool_t == 1) QT_POOL(1); else QT_POOL(2);
 #undef QT_POOL
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -646,15 +637,17 @@ extern "C" int qt_pool3d_max(int dtype, const void* x, void* out, unsigned char*
 extern "C" int qt_pool3d_max_bwd(int dtype, const void* dout, const unsigned char* argmax, void* dx, int frames, int batch,
                                  int h, int w, int C, int pool_t, void* stream) {
   QT_CHECK_ARG(dout && argmax && dx && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C % 8 == 0, "qt_pool3d_max_bwd: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pool3d_max_bwd: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pool3d_max_bwd");
   QT_CHECK_ARG((pool_t == 1 || pool_t == 2) && frames >= pool_t, "qt_pool3d_max_bwd: pool_t=%d", pool_t);
   const long long n = (long long)frames * batch * h * w * (C / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(grid_for(n)), blk(256);
-#define QT_POOLB(TT, PT) hipLaunchKernelGGL((pool3d_max_bwd_kernel<TT, PT>), grid, blk, 0, s, (const TT*)dout, argmax, (TT*)dx, frames, batch, h, w, C)
-  if (dtype == QT_F32) { if (pool_t == 1) QT_POOLB(float, 1); else QT_POOLB(float, 2); }
-  else { if (pool_t == 1) QT_POOLB(bf16_t, 1); else QT_POOLB(bf16_t, 2); }
+  const dim3 grid(qt_grid_for(n, 256, 65536)), blk(256);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+#define QT_POOLB(PT) hipLaunchKernelGGL((pool3d_max_bwd_kernel<T, PT>), grid, blk, 0, s, qt_as<T>(dout), argmax, qt_as<T>(dx), frames, batch, h, w, C)
+    if (pool_t == 1) QT_POOLB(1); else QT_POOLB(2);
 #undef QT_POOLB
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -665,15 +658,17 @@ extern "C" int qt_pool3d_bn_relu_max(int dtype, const void* y, const float* scal
   QT_CHECK_ARG(y && scale && shift && out && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C % 8 == 0,
                "qt_pool3d_bn_relu_max: bad argument");
   QT_CHECK_ARG(y_channels > 0 && y_channels <= C && y_channels % 8 == 0, "qt_pool3d_bn_relu_max: y_channels=%d of C=%d", y_channels, C);
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pool3d_bn_relu_max: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pool3d_bn_relu_max");
   QT_CHECK_ARG((pool_t == 1 || pool_t == 2) && frames >= pool_t, "qt_pool3d_bn_relu_max: pool_t=%d", pool_t);
   const long long n = (long long)(frames / pool_t) * batch * (h / 2) * (w / 2) * (C / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(grid_for(n)), blk(256);
-#define QT_POOLF(TT, PT) hipLaunchKernelGGL((pool3d_bn_relu_max_kernel<TT, PT>), grid, blk, 0, s, (const TT*)y, scale, shift, (TT*)out, argmax, (TT*)y_at_max, frames, batch, h, w, C, y_channels)
-  if (dtype == QT_F32) { if (pool_t == 1) QT_POOLF(float, 1); else QT_POOLF(float, 2); }
-  else { if (pool_t == 1) QT_POOLF(bf16_t, 1); else QT_POOLF(bf16_t, 2); }
+  const dim3 grid(qt_grid_for(n, 256, 65536)), blk(256);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+#define QT_POOLF(PT) hipLaunchKernelGGL((pool3d_bn_relu_max_kernel<T, PT>), grid, blk, 0, s, qt_as<T>(y), scale, shift, qt_as<T>(out), argmax, qt_as<T>(y_at_max), frames, batch, h, w, C, y_channels)
+    if (pool_t == 1) QT_POOLF(1); else QT_POOLF(2);
 #undef QT_POOLF
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -690,11 +685,12 @@ extern "C" int qt_pool3d_bn_bwd_apply(int dtype, const void* dout, const unsigne
                "qt_pool3d_bn_bwd_apply: bad argument");
   QT_CHECK_ARG(y_channels > 0 && y_channels <= C && y_channels % 8 == 0 && dy_channels >= y_channels && dy_channels % 8 == 0,
                "qt_pool3d_bn_bwd_apply: y_channels=%d dy_channels=%d of C=%d", y_channels, dy_channels, C);
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_pool3d_bn_bwd_apply: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_pool3d_bn_bwd_apply");
   QT_CHECK_ARG((pool_t == 1 || pool_t == 2) && frames >= pool_t, "qt_pool3d_bn_bwd_apply: pool_t=%d", pool_t);
   const long long n = (long long)frames * batch * h * w * (dy_channels / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);
   static const bool light = qt_env_int("QTCNN_POOL3D_APPLY_LIGHT", 1) != 0;
+  // (a dtype branch: the resident-grid form exists for bf16 only)
   if (light && dtype == QT_BF16 && C == y_channels && C == dy_channels && 256 % (C / 8) == 0 && n >= g_pool3d_light_min.load()) {
     const dim3 lgrid(256 * 5), blk(256);   // (92 VGPRs: five waves per SIMD; a multiple of C / 8 threads: the channel group is loop invariant)
     if (pool_t == 1)
@@ -706,11 +702,13 @@ extern "C" int qt_pool3d_bn_bwd_apply(int dtype, const void* dout, const unsigne
     QT_CHECK_LAUNCH();
     return QT_OK;
   }
-  const dim3 grid(grid_for(n)), blk(256);
-#define QT_POOLA(TT, PT) hipLaunchKernelGGL((pool3d_bn_bwd_apply_kernel<TT, PT>), grid, blk, 0, s, (const TT*)dout, argmax, (const TT*)pooled, (const TT*)y, mean, invstd, coef, (TT*)dy, frames, batch, h, w, C, y_channels, dy_channels)
-  if (dtype == QT_F32) { if (pool_t == 1) QT_POOLA(float, 1); else QT_POOLA(float, 2); }
-  else { if (pool_t == 1) QT_POOLA(bf16_t, 1); else QT_POOLA(bf16_t, 2); }
+  const dim3 grid(qt_grid_for(n, 256, 65536)), blk(256);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+#define QT_POOLA(PT) hipLaunchKernelGGL((pool3d_bn_bwd_apply_kernel<T, PT>), grid, blk, 0, s, qt_as<T>(dout), argmax, qt_as<T>(pooled), qt_as<T>(y), mean, invstd, coef, qt_as<T>(dy), frames, batch, h, w, C, y_channels, dy_channels)
+    if (pool_t == 1) QT_POOLA(1); else QT_POOLA(2);
 #undef QT_POOLA
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -719,12 +717,13 @@ extern "C" int qt_avgpool_tb(int dtype, const void* x, float* dst, int frames, i
                              void* stream) {
   QT_CHECK_ARG(x && dst && frames > 0 && batch > 0 && hw > 0 && C > 0 && C % 8 == 0 && col0 >= 0 && ld >= col0 + C,
                "qt_avgpool_tb: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_avgpool_tb: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_avgpool_tb");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(avgpool_tb_kernel<float>, dim3(batch, (C / 8 + 31) / 32), dim3(256), 0, s, (const float*)x, dst, frames, batch, hw, C, ld, col0);
-  else
-    hipLaunchKernelGGL(avgpool_tb_kernel<bf16_t>, dim3(batch, (C / 8 + 31) / 32), dim3(256), 0, s, (const bf16_t*)x, dst, frames, batch, hw, C, ld, col0);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(avgpool_tb_kernel<T>, dim3(batch, (C / 8 + 31) / 32), dim3(256), 0, s, qt_as<T>(x), dst, frames, batch, hw,
+                       C, ld, col0);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -733,13 +732,14 @@ extern "C" int qt_avgpool_tb_bwd(int dtype, const float* d, void* g, int frames,
                                  void* stream) {
   QT_CHECK_ARG(d && g && frames > 0 && batch > 0 && hw > 0 && C > 0 && C % 8 == 0 && col0 >= 0 && ld >= col0 + C,
                "qt_avgpool_tb_bwd: bad argument");
-  QT_CHECK_ARG(dtype == QT_F32 || dtype == QT_BF16, "qt_avgpool_tb_bwd: bad dtype %d", dtype);
+  QT_DT_OK(dtype, "qt_avgpool_tb_bwd");
   const long long n = (long long)frames * batch * hw * (C / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == QT_F32)
-    hipLaunchKernelGGL(avgpool_tb_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, d, (float*)g, frames, batch, hw, C, ld, col0);
-  else
-    hipLaunchKernelGGL(avgpool_tb_bwd_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, s, d, (bf16_t*)g, frames, batch, hw, C, ld, col0);
+  qt_by_dtype(dtype, [&](auto* t) {
+    using T = QT_T(t);
+    hipLaunchKernelGGL(avgpool_tb_bwd_kernel<T>, dim3(qt_grid_for(n, 256, 65536)), dim3(256), 0, s, d, qt_as<T>(g), frames, batch,
+                       hw, C, ld, col0);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
