@@ -434,6 +434,43 @@ typedef struct qt_augment_desc {
 size_t qt_augment_workspace_bytes(int batch, int use_contrast);
 int qt_augment_f32(const qt_augment_desc* desc, const float* src, const float* params, float* dst, void* workspace,
                    size_t workspace_bytes, void* stream);
+/* Grad-CAM: the heat map of the reference's three Grad-CAM scripts (resnet/grad_cam_analysis.py:306-343,
+ * grad_cam/5_grad_cam_visualizer.py:220-275, Quadtree_from scratch/grad_cam.py:70-96) for a whole batch, from the two hook
+ * tensors to uint8 overlays, without a host read.
+ * qt_gradcam_map.  act, grad: f32, contiguous [batch][C][P], the hooked layer's output and the gradient of the class score
+ * with respect to it; P = the number of positions (h w for base_cnn.layer4, t h w for Quadtree3DCNN.conv3d_final_features).
+ * cam: f32 [batch][P]; peak: f32 [batch].  Per image, on its own:
+ *   w_c = (sum_p grad[c][p]) / P;  s_p = sum_c w_c act[c][p];  r_p = max(s_p, 0);  peak = max_p r_p;
+ *   cam_p = r_p / peak, and cam_p = 0 for every p when peak == 0.
+ * (grad_cam_analysis.py:306-324 image by image.  Quadtree_from scratch/grad_cam.py:84 takes the mean over the channels where
+ * this takes the sum: the normalised map is the same.  That script divides by a zero peak and gets NaN; here such a map
+ * is all zeros, as in the other two scripts.)  Both maxima carry a NaN, and w_c act[c][p] is NaN where either factor is:
+ * an image with a NaN anywhere in its act or grad gets an all-NaN map and a NaN peak; the other images are not touched
+ * by it.  Any C >= 1; 1 <= P <= QT_GRADCAM_MAX_POSITIONS, above that QT_ERR_UNSUPPORTED before any launch.
+ * C <= 32: one launch, no workspace (qt_gradcam_workspace_bytes returns 0, NULL is fine).  Otherwise one workgroup per
+ * image and 32-channel chunk writes its part of s_p to the workspace ([batch][ceil(C / 32)][P] f32, every slot used is
+ * written) and a second launch adds the chunks in ascending order.  Every summation order depends on (C, P) only: no
+ * atomics, no zero fill, no host synchronisation, the same bits on every run and for an image alone or in a batch.
+ * qt_gradcam_overlay_u8.  cam: f32 [batch][h][w]; frames, out: uint8 [batch][H][W][3], contiguous; lut: uint8 [256][3] in
+ * DEVICE memory, in the frames' channel order; heat: f32 [batch][H][W] or NULL; index: uint8 [batch][H][W] or NULL.
+ * Per output pixel (y, x):
+ *   v    = the map sampled bilinearly with pixel centres at half-integers: f_x = (x + 0.5) (w / W) - 0.5, taps floor(f_x) and
+ *          floor(f_x) + 1 with weights 1 - t and t, t = f_x - floor(f_x), a tap outside the map replaced by the nearest one
+ *          inside; rows likewise.  (The rule cv2.resize documents for INTER_LINEAR; bit equality with it is not claimed.)
+ *   idx  = v > 0 ? min(255, int(255 v)) : 0, so a NaN map value gives idx 0 (and NaN in heat);
+ *   out  = uint8(floor(alpha lut[idx][c] + (1 - alpha) frames[c])) per channel: np.uint8(255 * heatmap) and
+ *          np.uint8(heatmap * alpha + image * (1 - alpha)) of visualize_cam; heat = v, index = idx.
+ * One launch, 16-byte accesses wherever frames and out have the same address modulo 16 (any address works); nothing is
+ * read or written outside the stated extents; the same bits on every run.  out may be frames itself; no other overlap.
+ * QT_ERR_INVALID_ARG (before any device call) for non-positive sizes, alpha outside [0, 1], null or misaligned pointers,
+ * a workspace that is too small; QT_ERR_UNSUPPORTED for overlay sizes above 2^22. */
+#define QT_GRADCAM_MAX_POSITIONS 4096
+size_t qt_gradcam_workspace_bytes(int batch, int C, int P);
+int qt_gradcam_map(const float* act, const float* grad, int batch, int C, int P, float* cam, float* peak, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int qt_gradcam_overlay_u8(const float* cam, int h, int w, const unsigned char* frames, int batch, int H, int W,
+                          const unsigned char* lut, float alpha, unsigned char* out, float* heat, unsigned char* index,
+                          void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

@@ -13,7 +13,8 @@ from .optim import FusedAdam, grad_norm  # noqa: F401
 from .preprocess import FramePreprocessor, random_flips, random_resized_crop_boxes  # noqa: F401
 from .quadtree import AttentionHierarchicalCNN, CnnLstm, QuadtreeCNN, StandardResNetCNN  # noqa: F401
 from .video3d import Ji3DCNN, Quadtree3DCNN  # noqa: F401
+from .gradcam import GradCAM, jet_lut  # noqa: F401
 
 __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnLstm", "Quadtree3DCNN", "Ji3DCNN", "FusedAdam", "grad_norm",
            "CrossEntropyLoss", "FocalLoss", "LossMeter", "FramePreprocessor", "random_resized_crop_boxes", "random_flips", "FrameAugmenter",
-           "QtError", "LIB_PATH"]
+           "GradCAM", "jet_lut", "QtError", "LIB_PATH"]

@@ -18,6 +18,8 @@ if os.path.dirname(_PKG_DIR) not in sys.path:
 _v3d = importlib.import_module(_PKG + ".video3d")
 _impl = importlib.import_module(_PKG + ".quadtree")
 QtError = importlib.import_module(_PKG + "._lib").QtError
+GradCAM = importlib.import_module(_PKG + ".gradcam").GradCAM  # batched Grad-CAM maps and overlays on the device
+jet_lut = importlib.import_module(_PKG + ".gradcam").jet_lut
 
 StandardResNetCNN = _impl.StandardResNetCNN
 
