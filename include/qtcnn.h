@@ -701,7 +701,8 @@ int qt_bn_stats_rows(long long M, int C);
 int qt_bn_stats(int dtype, const void* y, long long M, int C, float* partial, void* stream);
 /* nn.MaxPool3d(kernel = stride = (pool_t, 2, 2)), pool_t 1 or 2, floor mode: x [T][B][H][W][C] ->
  * out [T/pool_t][B][H/2][W/2][C]; argmax (u8 per output element, optional) = index of the first maximum in (t,h,w)
- * scan order, which is where torch's backward sends the gradient.  _bwd writes every element of dx. */
+ * scan order, which is where torch's backward sends the gradient.  _bwd writes every element of dx.  C: a positive
+ * multiple of 8 (these two and the two fused entry points below; anything else is QT_ERR_INVALID_ARG). */
 int qt_pool3d_max(int dtype, const void* x, void* out, unsigned char* argmax, int frames, int batch, int h, int w, int C,
                   int pool_t, void* stream);
 int qt_pool3d_max_bwd(int dtype, const void* dout, const unsigned char* argmax, void* dx, int frames, int batch, int h,

@@ -618,7 +618,7 @@ extern "C" int qt_bn_stats(int dtype, const void* y, long long M, int C, float* 
 
 extern "C" int qt_pool3d_max(int dtype, const void* x, void* out, unsigned char* argmax, int frames, int batch, int h, int w,
                              int C, int pool_t, void* stream) {
-  QT_CHECK_ARG(x && out && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C % 8 == 0, "qt_pool3d_max: bad argument");
+  QT_CHECK_ARG(x && out && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C >= 8 && C % 8 == 0, "qt_pool3d_max: bad argument");
   QT_DT_OK(dtype, "qt_pool3d_max");
   QT_CHECK_ARG((pool_t == 1 || pool_t == 2) && frames >= pool_t, "qt_pool3d_max: pool_t=%d (1 or 2, <= frames)", pool_t);
   const long long n = (long long)(frames / pool_t) * batch * (h / 2) * (w / 2) * (C / 8);
@@ -636,7 +636,7 @@ extern "C" int qt_pool3d_max(int dtype, const void* x, void* out, unsigned char*
 
 extern "C" int qt_pool3d_max_bwd(int dtype, const void* dout, const unsigned char* argmax, void* dx, int frames, int batch,
                                  int h, int w, int C, int pool_t, void* stream) {
-  QT_CHECK_ARG(dout && argmax && dx && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C % 8 == 0, "qt_pool3d_max_bwd: bad argument");
+  QT_CHECK_ARG(dout && argmax && dx && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C >= 8 && C % 8 == 0, "qt_pool3d_max_bwd: bad argument");
   QT_DT_OK(dtype, "qt_pool3d_max_bwd");
   QT_CHECK_ARG((pool_t == 1 || pool_t == 2) && frames >= pool_t, "qt_pool3d_max_bwd: pool_t=%d", pool_t);
   const long long n = (long long)frames * batch * h * w * (C / 8);
@@ -655,7 +655,7 @@ extern "C" int qt_pool3d_max_bwd(int dtype, const void* dout, const unsigned cha
 extern "C" int qt_pool3d_bn_relu_max(int dtype, const void* y, const float* scale, const float* shift, void* out,
                                      unsigned char* argmax, void* y_at_max, int frames, int batch, int h, int w, int C,
                                      int y_channels, int pool_t, void* stream) {
-  QT_CHECK_ARG(y && scale && shift && out && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C % 8 == 0,
+  QT_CHECK_ARG(y && scale && shift && out && frames > 0 && batch > 0 && h >= 2 && w >= 2 && C >= 8 && C % 8 == 0,
                "qt_pool3d_bn_relu_max: bad argument");
   QT_CHECK_ARG(y_channels > 0 && y_channels <= C && y_channels % 8 == 0, "qt_pool3d_bn_relu_max: y_channels=%d of C=%d", y_channels, C);
   QT_DT_OK(dtype, "qt_pool3d_bn_relu_max");
@@ -681,7 +681,7 @@ extern "C" int qt_pool3d_bn_bwd_apply(int dtype, const void* dout, const unsigne
                                       const float* mean, const float* invstd, const float* coef, void* dy, int frames, int batch,
                                       int h, int w, int C, int y_channels, int dy_channels, int pool_t, void* stream) {
   QT_CHECK_ARG(dout && argmax && pooled && y && mean && invstd && coef && dy && frames > 0 && batch > 0 && h >= 2 && w >= 2 &&
-                   C % 8 == 0,
+                   C >= 8 && C % 8 == 0,
                "qt_pool3d_bn_bwd_apply: bad argument");
   QT_CHECK_ARG(y_channels > 0 && y_channels <= C && y_channels % 8 == 0 && dy_channels >= y_channels && dy_channels % 8 == 0,
                "qt_pool3d_bn_bwd_apply: y_channels=%d dy_channels=%d of C=%d", y_channels, dy_channels, C);
