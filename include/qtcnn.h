@@ -471,6 +471,56 @@ int qt_gradcam_map(const float* act, const float* grad, int batch, int C, int P,
 int qt_gradcam_overlay_u8(const float* cam, int h, int w, const unsigned char* frames, int batch, int H, int W,
                           const unsigned char* lut, float alpha, unsigned char* out, float* heat, unsigned char* index,
                           void* stream);
+/* The pose vector: the 47 numerical features the models take beside the image, from 33 MediaPipe landmarks (source A; the
+ * rule of experiment/test_on_video_cnn.py:126-202) or from the stored raw vectors (source B), followed by the loaders' NaN
+ * imputation (test_on_video_cnn.py:261, Quadtree_from scratch/dataloader.py:84-88, 3dcnn/dataloaders.py:119-139), in one
+ * launch.  Exactly one of `landmarks` and `raw` is given; out: f32 [rows][47].
+ * Source A.  landmarks: f32 [rows][33][4] = x, y, z, visibility per landmark, 16-byte aligned; detected: uint8 [rows] or
+ * NULL (every row detected).  With p_j = (x, y, z) of landmark j and all arithmetic in f32:
+ *   0-32   visibility of landmark j.
+ *   33-40  the angle at b of (a, b, c) in degrees for (11,13,15) (12,14,16) (23,11,13) (24,12,14) (23,25,27) (24,26,28)
+ *          (11,23,25) (12,24,26): ba = p_a - p_b, bc = p_c - p_b, deg(atan2(|ba x bc|, ba . bc)); NaN when ba or bc is the
+ *          zero vector.
+ *   41     t = (p11 + p12) / 2 - (p23 + p24) / 2 in x, y;  d = |deg(pi/2 - atan2(t.y, t.x))|;  d > 180: d = 360 - d.
+ *   42     d = |deg(atan2(p12 - p11)) - deg(atan2(p24 - p23))| in x, y, folded at 180 likewise.
+ *   43-45  |p15 - p16|, |p27 - p28|, |p15 - p23| (3-D) divided by s:  sw = |p11 - p12|, hw = |p23 - p24|;  s = (sw + hw) / 2
+ *          when sw > 0 and hw > 0, else 1;  s == 0: s = 1;  unless s > 0.05 all three are NaN.
+ *   46     over those of landmarks 11, 12, 23, 24 whose visibility is > 0.65: var(x) / var(y), population variances in
+ *          two passes (the mean, then the squared deviations); NaN with fewer than two of them or when var(y) == 0.
+ * A row with detected == 0 gives 0.0 in columns 0-32 and NaN in 33-46.  A NaN coordinate goes by IEEE rules into the
+ * features that read it (a comparison with it is false: a NaN shoulder gives s = 1); a NaN visibility is not visible.
+ * The reference takes the angle as arccos(ba . bc / (|ba| |bc|)) in float64; in f32 that form loses half its digits near
+ * 0 and 180 degrees, atan2 does not, and it is the same angle.  Two of the reference's behaviours differ: on exactly
+ * collinear points numpy's arccos returns NaN when rounding pushes the cosine past +-1, the rule here gives 0 or 180; a
+ * zero-length limb (0 / 0 there) is NaN in both.
+ * Source B.  raw: f32 [rows][47], NaNs included.  out == raw is allowed (every element is read and written by the same
+ * thread); no other overlap.
+ * Imputation (desc->mode), applied to either source's values v in the same launch; label = labels[row / rows_per_label]
+ * (int64, device; rows_per_label must divide rows: one label per sequence of a [B][T] batch), means, stds: f32
+ * [num_classes][47], device:
+ *   QT_POSE_RAW          v (NaNs stay)
+ *   QT_POSE_ZERO         NaN -> 0
+ *   QT_POSE_CLASS_MEAN   NaN -> means[label][f]
+ *   QT_POSE_STANDARDIZE  NaN -> means[label][f], then (v - means[label][f]) / stds[label][f]; 0 where stds[label][f] < 1e-6f
+ * In the last two modes a label outside [0, num_classes) makes that row all NaN: only the device sees the label, nothing
+ * is indexed with it, the other rows are unaffected.  (The reference's loaders fall back to zeros for an unknown class,
+ * silently; that is not reproduced.)  labels, means, stds are not read in the first two modes.
+ * No atomics, no zero fill, no workspace, no host synchronisation; the same bits on every run and for a row alone or
+ * inside a batch.
+ * QT_ERR_INVALID_ARG (before any device call) for non-positive sizes, both or neither source, `detected` with source B,
+ * null or misaligned pointers, an unknown mode, a mode without the labels / tables it needs, rows_per_label that does not
+ * divide rows; QT_ERR_UNSUPPORTED for more than 2^22 rows. */
+#define QT_POSE_LANDMARKS 33
+#define QT_POSE_FEATURES 47
+enum { QT_POSE_RAW = 0, QT_POSE_ZERO = 1, QT_POSE_CLASS_MEAN = 2, QT_POSE_STANDARDIZE = 3 };
+typedef struct qt_pose_desc {
+  long long rows;
+  int mode;                         /* QT_POSE_* */
+  int rows_per_label;               /* >= 1; read in the two class modes only */
+  int num_classes;                  /* K of means / stds; read in the two class modes only */
+} qt_pose_desc;
+int qt_pose_features(const qt_pose_desc* desc, const float* landmarks, const unsigned char* detected, const float* raw,
+                     const long long* labels, const float* means, const float* stds, float* out, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of
