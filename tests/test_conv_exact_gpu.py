@@ -13,6 +13,7 @@ import torch
 
 import _exact as E
 from _exact import BF, F32
+from _guard import Guard
 from _util import pkg
 from test_conv_gpu import PackItem, nhwc, run_conv, run_wgrad
 from test_conv_pt_gpu import _maxwg, _pt, tiles
@@ -155,15 +156,17 @@ def _forward_27_taps(L, dev, row, dt, c):
     d = _desc(L, dt, L.QT_CONV_FWD, T * B, (H, H), (H, H), Cin, Cout, 3, 1, 1)
     d.kt, d.frames = 3, T
     rows = L.lib().qt_conv2d_stats_rows(ctypes.byref(d))
-    y = torch.full((T * B * H * H, Cout), float("nan"), dtype=dt, device=dev)
-    st = torch.zeros(rows, 2, Cout, device=dev)
+    gd = Guard(dev)
+    xd, wf, resd, sc, sh = (gd.input(n, t) for n, t in (("x", xd), ("w", wf), ("residual", resd), ("scale", sc), ("shift", sh)))
+    y = gd.output("y", (T * B * H * H, Cout), dt)
+    st = gd.output("stats", (rows, 2, Cout), torch.float32)   # (the generic tile stores every partial row)
     io = L.ConvIO(L.ptr(xd), L.ptr(wf), L.ptr(y), None, None, None, None, L.ptr(st))
     L.check(L.lib().qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm kt=3")
     d.relu = 1
-    ya = torch.full((T * B * H * H, Cout), float("nan"), dtype=dt, device=dev)
+    ya = gd.output("y_act", (T * B * H * H, Cout), dt)
     io = L.ConvIO(L.ptr(xd), L.ptr(wf), L.ptr(ya), L.ptr(sc), L.ptr(sh), L.ptr(resd), None, None)
     L.check(L.lib().qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm kt=3")
-    torch.cuda.synchronize()
+    gd.check()
 
     def back(t):
         return t.cpu().view(T, B, H, H, Cout).permute(1, 4, 0, 2, 3)
@@ -233,15 +236,18 @@ def test_packed_stem_is_bit_exact(row):
         lib.qt_set_stem_conv(-1)
     assert rows[1] != rows[0]          # the dedicated kernel keeps its own row count: it was the path taken
     st_ = L.stream_ptr()
-    xpad = torch.empty(B, 230, 232, 4, device=dev, dtype=dt)
+    gd = Guard(dev)
+    imd, wd, sc, sh = gd.input("image", imd), gd.input("w", wd), gd.input("scale", sc), gd.input("shift", sh)
+    xpad = gd.output("xpad", (B, 230, 232, 4), dt)       # the packers write every element, zero borders included
     L.check(lib.qt_pack_stem_input(qdt, L.ptr(imd), L.ptr(xpad), B, st_), "qt_pack_stem_input")
-    wp = torch.empty(64, 8, 32, device=dev, dtype=dt)
+    wp = gd.output("w_packed", (64, 8, 32), dt)
     L.check(lib.qt_pack_stem_weight(qdt, L.ptr(wd), L.ptr(wp), 8, st_), "qt_pack_stem_weight")
+    gd.check()
     for name in ("qt_stem_conv_pool", "qt_stem_conv_pool_nchw"):
-        pooled = torch.full((B, 56, 56, 64), float("nan"), device=dev, dtype=dt)
+        pooled = gd.output(name, (B, 56, 56, 64), dt)
         src = xpad if name == "qt_stem_conv_pool" else imd
         L.check(getattr(lib, name)(qdt, L.ptr(src), L.ptr(wp), 8, L.ptr(sc), L.ptr(sh), L.ptr(pooled), B, st_), name)
-        torch.cuda.synchronize()
+        gd.check()
         _same(pooled.cpu().permute(0, 3, 1, 2), c["pooled"], dt, name)
 
 
@@ -273,11 +279,13 @@ def test_data_gradient_is_bit_exact(row, dt):
             y0, _ = run_conv(L, dt, dyd, wt, B, (Ho, Ho), (H, H), Cout, Cin, k, k, s, p, L.QT_CONV_DGRAD)
             y1, _ = run_conv(L, dt, dyd, wt, B, (Ho, Ho), (H, H), Cout, Cin, k, k, s, p, L.QT_CONV_DGRAD, residual=od,
                              relu_mask=ad)
-            y2 = torch.full((B * H * H, Cin), float("nan"), dtype=dt, device=dev)
-            io = L.ConvIO(L.ptr(dyd), L.ptr(wt), L.ptr(y2), None, None, L.ptr(od), None, None)
-            io.relu_mask_bits = bits.data_ptr()
+            gd = Guard(dev)
+            g_dy, g_w, g_res, g_bits = gd.input("dy", dyd), gd.input("w", wt), gd.input("residual", od), gd.input("mask_bits", bits)
+            y2 = gd.output("y", (B * H * H, Cin), dt)
+            io = L.ConvIO(L.ptr(g_dy), L.ptr(g_w), L.ptr(y2), None, None, L.ptr(g_res), None, None)
+            io.relu_mask_bits = g_bits.data_ptr()
             L.check(L.lib().qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm (mask bits)")
-            torch.cuda.synchronize()
+            gd.check()
         _same(_nchw(y0, B, H, H, Cin), c["dx"], dt, "plain")
         _same(_nchw(y1, B, H, H, Cin), c["out"], dt, "residual + mask")
         _same(_nchw(y2, B, H, H, Cin), c["out"], dt, "residual + packed mask bits")
@@ -312,15 +320,18 @@ def test_stride2_data_gradient_is_bit_exact(row, dt):
     B, Cin, Cout, H, k, _, p = row["cfg"]
     Ho = (H + 2 * p - k) // 2 + 1
     qdt = L.qt_dtype(dt)
-    dyd = nhwc(c["dy"]).to(dev, dt)
-    res = nhwc(c["other"]).to(dev, dt).view(-1, Cin)
-    msk = nhwc(c["act"]).to(dev, dt).view(-1, Cin)
-    wsrc = c["w"].float().to(dev).contiguous()
+    gd = Guard(dev)
+    dyd = gd.input("dy", nhwc(c["dy"]).to(dt))
+    res = gd.input("residual", nhwc(c["other"]).to(dt).view(-1, Cin))
+    msk = gd.input("relu_mask", nhwc(c["act"]).to(dt).view(-1, Cin))
+    wsrc = gd.input("w", c["w"].float().contiguous())
     if row["form"] == "classes":
         offs, khs, kws = (ctypes.c_longlong * 4)(), (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
-        wd = torch.empty(Cout * Cin * k * k, dtype=dt, device=dev)
+        wd = gd.output("w_classes", (Cout * Cin * k * k,), dt)       # the four classes back to back: every element written
         L.check(lib.qt_pack_dgrad_s2(qdt, L.ptr(wsrc), L.ptr(wd), Cout, Cin, k, offs, khs, kws, L.stream_ptr()), "qt_pack_dgrad_s2")
-        out = torch.zeros(B * H * H, Cin, dtype=dt, device=dev)
+        gd.check()
+        # k = 3: the four classes tile the image, every pixel is written.  k = 1: only class (0,0) is, the rest keeps the zeros
+        out = gd.output("dx", (B * H * H, Cin), dt) if k == 3 else gd.output("dx", (B * H * H, Cin), dt, fill=0)
         esz = 2 if dt == BF else 4
         for cls in range(4):
             if khs[cls] * kws[cls] == 0:
@@ -331,26 +342,25 @@ def test_stride2_data_gradient_is_bit_exact(row, dt):
             io = L.ConvIO(L.ptr(dyd), ctypes.c_void_p(wd.data_ptr() + offs[cls] * esz), L.ptr(out), None, None,
                           L.ptr(res), L.ptr(msk), None)
             L.check(lib.qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm")
-        torch.cuda.synchronize()
+        gd.check()
         got, ref = _nchw(out, B, H, H, Cin), c["out"]
         if k == 1:   # pixels no tap reaches were never written: only class (0,0) is defined
             got, ref = got[:, :, ::2, ::2], ref[:, :, ::2, ::2]
         return _same(got, ref, dt, "parity classes")
     extra = row["form"] == "merged5"
     if extra:
-        op = torch.zeros(20 * Cout * Cin, dtype=dt, device=dev)       # [4 Cin][5 slots][Cout]; unused slots stay zero
-        wdsrc = c["wd"].float().to(dev).contiguous()
+        op = gd.output("w_merged5", (20 * Cout * Cin,), dt, fill=0)   # [4 Cin][5 slots][Cout]; unused slots stay zero
+        wdsrc = gd.input("w_down", c["wd"].float().contiguous())
         items = (PackItem * 2)(PackItem(wsrc.data_ptr(), None, op.data_ptr(), Cout, Cin, 3, 3),
                                PackItem(wdsrc.data_ptr(), None, op.data_ptr(), Cout, Cin, 1, 4))
         L.check(lib.qt_pack_weights_batched(qdt, ctypes.cast(items, ctypes.c_void_p), 2, L.stream_ptr()), "qt_pack_weights_batched")
-        maps = torch.empty(2, B, Ho, Ho, Cout, dtype=dt, device=dev)
-        maps[0] = dyd
-        maps[1] = nhwc(c["dyd"]).to(dev, dt)
+        maps = gd.input("dy_maps", torch.stack([nhwc(c["dy"]).to(dt), nhwc(c["dyd"]).to(dt)]))   # both maps in one allocation
         src = maps[0]
     else:
-        op = torch.full((16 * Cout * Cin,), float("nan"), dtype=dt, device=dev)   # the packer zeroes the unused slots
+        op = gd.output("w_merged", (16 * Cout * Cin,), dt)            # NaN: the packer zeroes the unused slots
         L.check(lib.qt_pack_dgrad_s2_merged(qdt, L.ptr(wsrc), L.ptr(op), Cout, Cin, L.stream_ptr()), "qt_pack_dgrad_s2_merged")
         src = dyd
+    gd.check()
     d = _desc(L, dt, L.QT_CONV_FWD, B, (Ho, Ho), (Ho, Ho), Cout, 4 * Cin, 2, 1, 0)
     d.dst_sub, d.dst_h, d.dst_w, d.dst_off_h, d.dst_off_w, d.dst_merge = 2, H, H, 0, 0, Cin
     d.dst_merge_extra = 1 if extra else 0
@@ -361,17 +371,17 @@ def test_stride2_data_gradient_is_bit_exact(row, dt):
     else:
         assert rows == rows_off
     ybn, mean, invstd, xhat = _dyadic_links(c, Cin, row["seed"] + 9000)
-    yb = nhwc(ybn).to(dev, dt).view(-1, Cin)
-    md, isd = mean.float().to(dev), invstd.float().to(dev)
+    yb = gd.input("bn_y", nhwc(ybn).to(dt).view(-1, Cin))
+    md, isd = gd.input("bn_mean", mean.float()), gd.input("bn_invstd", invstd.float())
     for with_ops in (False, True):
-        part = torch.full((rows, 2, Cin), float("nan"), dtype=torch.float32, device=dev)
-        out = torch.full((B * H * H, Cin), float("nan"), dtype=dt, device=dev)   # every pixel belongs to one class
+        part = gd.output(f"bn_partial{int(with_ops)}", (rows, 2, Cin), torch.float32)
+        out = gd.output(f"dx{int(with_ops)}", (B * H * H, Cin), dt)   # every pixel belongs to one class
         io = L.ConvIO(src.data_ptr(), L.ptr(op), L.ptr(out), None, None, L.ptr(res) if with_ops else None,
                       L.ptr(msk) if with_ops else None, None, L.ptr(yb), L.ptr(md), L.ptr(isd), L.ptr(part), None, None, None, None)
         if extra:
             io.extra_src = maps[1].data_ptr()
         L.check(lib.qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm")
-        torch.cuda.synchronize()
+        gd.check()
         ref = c["out"] if with_ops else c["dx"]
         _same(_nchw(out, B, H, H, Cin), ref, dt, ("merged", with_ops))
         assert _links_equal(part, ref, xhat), ("BatchNorm-backward link sums", with_ops)
@@ -413,22 +423,24 @@ def test_weight_gradient_is_bit_exact(row, dt):
         """_oihw into NaN-filled scratch, and _oihw_on twice back to back on alternating workspaces (sum on a side stream)"""
         nbytes = lib.qt_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
         assert nbytes > 0, "the streaming kernel was expected to take this shape"
-        ws = [torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev) for _ in range(2)]
-        gr = [torch.full((Cout, Cin, k, k), float("nan"), dtype=torch.float32, device=dev) for _ in range(3)]
-        L.check(lib.qt_conv2d_wgrad_oihw(ctypes.byref(d), L.ptr(dyd), L.ptr(xd), L.ptr(gr[0]), L.ptr(ws[0]),
+        gd = Guard(dev)
+        g_dy, g_x = gd.input("dy", dyd), gd.input("x", xd)
+        ws = [gd.workspace(f"ws{j}", nbytes) for j in range(2)]       # exactly the queried size
+        gr = [gd.output(f"grad{j}", (Cout, Cin, k, k), torch.float32) for j in range(3)]
+        L.check(lib.qt_conv2d_wgrad_oihw(ctypes.byref(d), L.ptr(g_dy), L.ptr(g_x), L.ptr(gr[0]), L.ptr(ws[0]),
                                          ctypes.c_size_t(nbytes), L.stream_ptr()), "qt_conv2d_wgrad_oihw")
         torch.cuda.synchronize()
         _same(gr[0], c["dw"], F32, (what, "oihw"))
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         for j in (0, 1):
-            ws[j].fill_(float("nan"))
+            ws[j].fill_(0xFF)
         torch.cuda.synchronize()
         for j in (0, 1):
-            L.check(lib.qt_conv2d_wgrad_oihw_on(ctypes.byref(d), L.ptr(dyd), L.ptr(xd), L.ptr(gr[1 + j]), L.ptr(ws[j]),
+            L.check(lib.qt_conv2d_wgrad_oihw_on(ctypes.byref(d), L.ptr(g_dy), L.ptr(g_x), L.ptr(gr[1 + j]), L.ptr(ws[j]),
                                                 ctypes.c_size_t(nbytes), L.stream_ptr(), ctypes.c_void_p(side.cuda_stream)),
                     "qt_conv2d_wgrad_oihw_on")
-        torch.cuda.synchronize()
+        gd.check()
         _same(gr[1], c["dw"], F32, (what, "oihw_on, first"))
         _same(gr[2], c["dw"], F32, (what, "oihw_on, second"))
 
@@ -478,12 +490,13 @@ def test_linear_weight_gradient_is_bit_exact(row, dt):
     c = E.lwgrad_data(row)
     E.lwgrad_conditions(c)
     rows, out, inn = row["cfg"]
-    dw = torch.full((out, inn), float("nan"), dtype=torch.float32, device=dev)
-    dyd, xd = c["dy"].to(dev, dt), c["x"].to(dev, dt)
+    gd = Guard(dev)
+    dw = gd.output("dw", (out, inn), torch.float32)
+    dyd, xd = gd.input("dy", c["dy"].to(dt)), gd.input("x", c["x"].to(dt))
     for _ in range(2):   # (a second call over the first result: nothing is accumulated)
         L.check(L.lib().qt_linear_wgrad(L.qt_dtype(dt), L.ptr(dyd), L.ptr(xd), L.ptr(dw), rows, out, inn, L.stream_ptr()),
                 "qt_linear_wgrad")
-    torch.cuda.synchronize()
+    gd.check()
     _same(dw, c["dw"], F32, "qt_linear_wgrad")
 
 
@@ -497,13 +510,14 @@ def test_linear_splitk_is_bit_exact(row):
     M, N, K = row["cfg"]
     lib.qt_linear_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.qt_linear_workspace_bytes(M, N, K)
-    ws = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev)
-    y = torch.full((M, N), float("nan"), dtype=BF, device=dev)
-    xd, wd = c["x"].to(dev, BF), c["w"].to(dev, BF)
-    bd = c["bias"].float().to(dev) if c["bias"] is not None else None
+    gd = Guard(dev)
+    ws = gd.workspace("ws", nbytes)
+    y = gd.output("y", (M, N), BF)
+    xd, wd = gd.input("x", c["x"].to(BF)), gd.input("w", c["w"].to(BF))
+    bd = gd.input("bias", c["bias"].float() if c["bias"] is not None else None)
     L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), row["relu"], L.ptr(y), M, N, K, L.ptr(ws), ctypes.c_size_t(nbytes),
                                L.stream_ptr()), "qt_linear_bf16")
-    torch.cuda.synchronize()
+    gd.check()
     _same(y, c["out"], BF, "qt_linear_bf16")
 
 
@@ -521,11 +535,12 @@ def test_stem_data_gradient_is_bit_exact(row, dt):
     c = E.dgrad_data(row)
     E.dgrad_conditions(c, F32)
     B = row["cfg"][0]
-    dyd = nhwc(c["dy"]).to(dev, dt)
-    wd = c["w"].float().contiguous().to(dev)
-    dx = torch.full((B, 3, 224, 224), float("nan"), device=dev)
+    gd = Guard(dev)
+    dyd = gd.input("dy", nhwc(c["dy"]).to(dt))
+    wd = gd.input("w", c["w"].float().contiguous())
+    dx = gd.output("dx", (B, 3, 224, 224), torch.float32)
     L.check(L.lib().qt_stem_dgrad(L.qt_dtype(dt), L.ptr(dyd), L.ptr(wd), L.ptr(dx), B, L.stream_ptr()), "qt_stem_dgrad")
-    torch.cuda.synchronize()
+    gd.check()
     _same(dx, c["dx"], F32, "qt_stem_dgrad")
 
 
@@ -542,18 +557,20 @@ def test_stem_weight_gradient_is_bit_exact(row, dt):
     E.wgrad_conditions(c)
     B = row["cfg"][0]
     qdt, st = L.qt_dtype(dt), L.stream_ptr()
-    imd = c["x"].float().to(dev)
-    xpad = torch.empty(B, 230, 232, 4, device=dev, dtype=dt)
+    gd = Guard(dev)
+    imd = gd.input("image", c["x"].float())
+    xpad = gd.output("xpad", (B, 230, 232, 4), dt)
     L.check(lib.qt_pack_stem_input(qdt, L.ptr(imd), L.ptr(xpad), B, st), "qt_pack_stem_input")
-    dyd = nhwc(c["dy"]).to(dev, dt)
+    gd.check()
+    dyd = gd.input("dy", nhwc(c["dy"]).to(dt))
     d = _desc(L, dt, L.QT_CONV_FWD, B, (230, 232), (112, 112), 32, 64, 7, 2, 0)
     d.kw = 1
     d.src_pix_stride, d.src_row_stride, d.src_img_stride = 4, 232 * 4, 230 * 232 * 4
-    dw = torch.zeros(64, 7, 32, device=dev)
+    dw = gd.output("dw", (64, 7, 32), torch.float32, fill=0)          # zeros: qt_conv2d_wgrad accumulates (dw += ...)
     L.check(lib.qt_conv2d_wgrad(ctypes.byref(d), L.ptr(dyd), L.ptr(xpad), L.ptr(dw), st), "qt_conv2d_wgrad")
-    grad = torch.full((64, 3, 7, 7), float("nan"), device=dev)
+    grad = gd.output("grad", (64, 3, 7, 7), torch.float32)
     L.check(lib.qt_unpack_stem_wgrad(L.ptr(dw), L.ptr(grad), 0, st), "qt_unpack_stem_wgrad")
-    torch.cuda.synchronize()
+    gd.check()
     _same(grad, c["dw"], F32, "packed stem weight gradient")
 
 
@@ -586,72 +603,78 @@ def test_first_conv3d_is_bit_exact(row, dt):
     qdt, st = L.qt_dtype(dt), L.stream_ptr()
     if "fwd" in row["only"]:
         E.c3_conditions(c, dt, "fwd")
-        cd = c["x"].permute(0, 2, 1, 3, 4).contiguous().float().to(dev)            # the f32 clip [B][T][3][H][W]
+        gd = Guard(dev)
+        cd = gd.input("clip", c["x"].permute(0, 2, 1, 3, 4).contiguous().float())  # the f32 clip [B][T][3][H][W]
         wp = torch.zeros(64, 128)                                                  # element ((kt*3 + kh)*3 + kw)*3 + c
         wp[:32, :81] = c["w"].permute(0, 2, 3, 4, 1).reshape(32, 81).float()
-        wp = wp.to(dev, dt)
-        sc, sh = c["scale"].float().to(dev), c["shift"].float().to(dev)
+        wp = gd.input("w", wp.to(dt))
+        sc, sh = gd.input("scale", c["scale"].float()), gd.input("shift", c["shift"].float())
         rows = lib.qt_conv3d_first_stats_rows(B, T, H, W)
         assert rows > 0, "conv3d_first.hip was expected to take this shape"
-        y = torch.full((T, B, H, W, 32), float("nan"), dtype=dt, device=dev)
-        y2, y3 = torch.full_like(y, float("nan")), torch.full_like(y, float("nan"))
-        part = torch.full((rows, 2, 64), float("nan"), device=dev)
+        y, y2, y3 = (gd.output(n, (T, B, H, W, 32), dt) for n in ("y_stats", "y_plain", "y_affine"))
+        part = gd.output("stats", (rows, 2, 64), torch.float32)
         L.check(lib.qt_conv3d_first_fwd(qdt, L.ptr(cd), L.ptr(wp), L.ptr(y), None, None, 0, L.ptr(part), B, T, H, W, st), "stats")
         L.check(lib.qt_conv3d_first_fwd(qdt, L.ptr(cd), L.ptr(wp), L.ptr(y2), None, None, 0, None, B, T, H, W, st), "plain")
         L.check(lib.qt_conv3d_first_fwd(qdt, L.ptr(cd), L.ptr(wp), L.ptr(y3), L.ptr(sc), L.ptr(sh), 1, None, B, T, H, W, st), "affine")
-        torch.cuda.synchronize()
+        gd.check()
         _same(_ncthw(y, 32), c["raw"], dt, "raw + statistics")
         _same(_ncthw(y2, 32), c["raw"], dt, "raw")
         _same(_ncthw(y3, 32), c["act"], dt, "scale / shift / ReLU")
         if row["mode"] == "A":
             assert E.stats_equal(part[:, :, :32], c["raw"]) and bool((part[:, :, 32:] == 0).all())
         for pc in (64, 32):
-            pooled = torch.full((T, B, H // 2, W // 2, pc), float("nan"), dtype=dt, device=dev)
+            pooled = gd.output(f"pooled{pc}", (T, B, H // 2, W // 2, pc), dt)
             L.check(lib.qt_conv3d_first_fwd_pool(qdt, L.ptr(cd), L.ptr(wp), L.ptr(pooled), pc, L.ptr(sc), L.ptr(sh), B, T, H, W, st),
                     "qt_conv3d_first_fwd_pool")
-            torch.cuda.synchronize()
+            gd.check()
             _same(_ncthw(pooled, 32), c["pooled"], dt, ("conv + scale / shift / ReLU + max pool", pc))
             assert bool((pooled[..., 32:] == 0).all())
     if "dgrad" in row["only"]:
         E.c3_conditions(c, F32, "dgrad")
-        dyd = _tb(c["dyf"]).to(dev, dt)
-        wd = c["wg"].float().contiguous().to(dev)                                  # nn.Conv3d's [32][3][3][3][3], f32
-        dx = torch.full((B, T, 3, H, W), float("nan"), device=dev)
+        gd = Guard(dev)
+        dyd = gd.input("dy", _tb(c["dyf"]).to(dt))
+        wd = gd.input("w", c["wg"].float().contiguous())                           # nn.Conv3d's [32][3][3][3][3], f32
+        dx = gd.output("dx", (B, T, 3, H, W), torch.float32)
         L.check(lib.qt_conv3d_first_dgrad(qdt, L.ptr(dyd), L.ptr(wd), L.ptr(dx), B, T, H, W, st), "qt_conv3d_first_dgrad")
-        torch.cuda.synchronize()
+        gd.check()
         _same(dx.cpu().permute(0, 2, 1, 3, 4), c["dx"], F32, "qt_conv3d_first_dgrad")
     if "wgrad" in row["only"]:
         E.c3_conditions(c, F32, "wgrad")
         lib.qt_conv3d_first_wgrad_workspace_bytes.restype = ctypes.c_size_t
         nws = int(lib.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W))
         assert nws > 0
-        cd1 = c["x1"].permute(0, 2, 1, 3, 4).contiguous().float().to(dev)
-        dyd = _tb(c["dy"]).to(dev, dt)
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        dw = torch.full((32, 3, 3, 3, 3), float("nan"), device=dev)
+        gd = Guard(dev)
+        cd1 = gd.input("clip", c["x1"].permute(0, 2, 1, 3, 4).contiguous().float())
+        dyd = gd.input("dy", _tb(c["dy"]).to(dt))
+        ws = gd.workspace("ws", nws)
+        dw = gd.output("dw", (32, 3, 3, 3, 3), torch.float32)
         L.check(lib.qt_conv3d_first_wgrad(qdt, L.ptr(cd1), L.ptr(dyd), L.ptr(dw), L.ptr(ws), ctypes.c_size_t(nws), B, T, H, W, st),
                 "qt_conv3d_first_wgrad")
-        torch.cuda.synchronize()
+        gd.check()
         _same(dw, c["dw"], F32, "qt_conv3d_first_wgrad")
     if "fused" in row["only"]:
         for cp in (32, 64):
             f = E.c3_fused_data(c, cp)
             E.c3_fused_conditions(f)
-            yd = _tb(f["y"]).to(dev, dt)
-            dout = _tb(f["dout"]).to(dev, dt)
-            arg = _tb(f["arg"]).to(dev)
-            sc, sh = f["scale"].float().to(dev), f["shift"].float().to(dev)
-            mean, invstd, coef = f["mean"].float().to(dev), f["invstd"].float().to(dev), f["coef"].float().contiguous().to(dev)
-            dwf = torch.full((32, 3, 3, 3, 3), float("nan"), device=dev)
+            gd = Guard(dev)
+            cd1 = gd.input("clip", c["x1"].permute(0, 2, 1, 3, 4).contiguous().float())
+            ws = gd.workspace("ws", nws)                                           # a fresh NaN workspace per pooled width
+            yd = gd.input("y", _tb(f["y"]).to(dt))
+            dout = gd.input("dout", _tb(f["dout"]).to(dt))
+            arg = gd.input("argmax", _tb(f["arg"]))
+            sc, sh = gd.input("scale", f["scale"].float()), gd.input("shift", f["shift"].float())
+            mean, invstd = gd.input("mean", f["mean"].float()), gd.input("invstd", f["invstd"].float())
+            coef = gd.input("coef", f["coef"].float().contiguous())
+            dwf = gd.output("dw_fused", (32, 3, 3, 3, 3), torch.float32)
             L.check(lib.qt_conv3d_first_wgrad_fused(qdt, L.ptr(cd1), L.ptr(yd), L.ptr(dout), L.ptr(arg), cp, L.ptr(mean),
                                                     L.ptr(invstd), L.ptr(sc), L.ptr(sh), L.ptr(coef), L.ptr(dwf), L.ptr(ws),
                                                     ctypes.c_size_t(nws), B, T, H, W, st), "qt_conv3d_first_wgrad_fused")
             # the unfused kernel on the reference's dy: the same contraction
-            dyd = _tb(f["dy"]).to(dev, dt)
-            dwu = torch.full((32, 3, 3, 3, 3), float("nan"), device=dev)
+            dyd = gd.input("dy", _tb(f["dy"]).to(dt))
+            dwu = gd.output("dw_unfused", (32, 3, 3, 3, 3), torch.float32)
             L.check(lib.qt_conv3d_first_wgrad(qdt, L.ptr(cd1), L.ptr(dyd), L.ptr(dwu), L.ptr(ws), ctypes.c_size_t(nws), B, T, H, W, st),
                     "qt_conv3d_first_wgrad")
-            torch.cuda.synchronize()
+            gd.check()
             _same(dwu, f["dw"], F32, ("qt_conv3d_first_wgrad on the formed dy", cp))
             _same(dwf, f["dw"], F32, ("qt_conv3d_first_wgrad_fused", cp))
 
@@ -675,23 +698,23 @@ def test_second_conv3d_is_bit_exact(row, dt):
     def rows_of(x):
         xd = torch.full((T, B, H, W, xc), 3.0, dtype=dt)
         xd[..., :32] = _tb(x).to(dt)
-        return xd.to(dev)
+        return xd
     assert lib.qt_conv3d_c32_stats_rows(B, T, H, W) > 0, "conv3d_slab.hip was expected to take this shape"
     if "fwd" in row["only"]:
         E.c3_conditions(c, dt, "fwd")
-        xd = rows_of(c["x"])
+        gd = Guard(dev)
+        xd = gd.input("x", rows_of(c["x"]))
         wp = torch.full((64, 27, 64), 3.0, dtype=dt)                               # [O][tap][I padded]
         wp[:, :, :32] = c["w"].permute(0, 2, 3, 4, 1).reshape(64, 27, 32).to(dt)
-        wp = wp.to(dev)
-        sc, sh = c["scale"].float().to(dev), c["shift"].float().to(dev)
+        wp = gd.input("w", wp)
+        sc, sh = gd.input("scale", c["scale"].float()), gd.input("shift", c["shift"].float())
         rows = lib.qt_conv3d_c32_stats_rows(B, T, H, W)
-        y = torch.full((T, B, H, W, 64), float("nan"), dtype=dt, device=dev)
-        y2, y3 = torch.full_like(y, float("nan")), torch.full_like(y, float("nan"))
-        part = torch.full((rows, 2, 64), float("nan"), device=dev)
+        y, y2, y3 = (gd.output(n, (T, B, H, W, 64), dt) for n in ("y_stats", "y_plain", "y_affine"))
+        part = gd.output("stats", (rows, 2, 64), torch.float32)
         L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xd), xc, L.ptr(wp), L.ptr(y), None, None, 0, L.ptr(part), B, T, H, W, st), "stats")
         L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xd), xc, L.ptr(wp), L.ptr(y2), None, None, 0, None, B, T, H, W, st), "plain")
         L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xd), xc, L.ptr(wp), L.ptr(y3), L.ptr(sc), L.ptr(sh), 1, None, B, T, H, W, st), "affine")
-        torch.cuda.synchronize()
+        gd.check()
         _same(_ncthw(y, 64), c["raw"], dt, "raw + statistics")
         _same(_ncthw(y2, 64), c["raw"], dt, "raw")
         _same(_ncthw(y3, 64), c["act"], dt, "scale / shift / ReLU")
@@ -699,30 +722,32 @@ def test_second_conv3d_is_bit_exact(row, dt):
             assert E.stats_equal(part, c["raw"])
     if "dgrad" in row["only"]:
         E.c3_conditions(c, dt, "dgrad")
-        dyd = _tb(c["dyf"]).to(dev, dt)
+        gd = Guard(dev)
+        dyd = gd.input("dy", _tb(c["dyf"]).to(dt))
         wdp = torch.full((64, 27, 64), 3.0, dtype=dt)                              # [I padded][tap][O]
         wdp[:32] = c["wg"].permute(1, 2, 3, 4, 0).reshape(32, 27, 64).to(dt)
-        wdp = wdp.to(dev)
+        wdp = gd.input("w", wdp)
         lib.qt_conv3d_c32_dgrad_scratch_bytes.restype = ctypes.c_size_t
         nscr = int(lib.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W))
-        scr = torch.empty(nscr, dtype=torch.uint8, device=dev)
         for dxc in (64, 32):
-            dx = torch.full((T, B, H, W, dxc), float("nan"), dtype=dt, device=dev)
+            scr = gd.workspace(f"scratch{dxc}", nscr)                              # exactly the queried size, NaN
+            dx = gd.output(f"dx{dxc}", (T, B, H, W, dxc), dt)
             L.check(lib.qt_conv3d_c32_dgrad(qdt, L.ptr(dyd), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), ctypes.c_size_t(nscr), B, T, H, W, st),
                     "qt_conv3d_c32_dgrad")
-            torch.cuda.synchronize()
+            gd.check()
             _same(_ncthw(dx, 32), c["dx"], dt, ("qt_conv3d_c32_dgrad", dxc))
             assert bool((dx[..., 32:] == 0).all())
     if "wgrad" in row["only"]:
         E.c3_conditions(c, F32, "wgrad")
-        xd1 = rows_of(c["x1"])
-        dyd = _tb(c["dy"]).to(dev, dt)
+        gd = Guard(dev)
+        xd1 = gd.input("x", rows_of(c["x1"]))
+        dyd = gd.input("dy", _tb(c["dy"]).to(dt))
         lib.qt_conv3d_c32_wgrad_workspace_bytes.restype = ctypes.c_size_t
         nws = int(lib.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W))
         assert nws > 0
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        dwt = torch.full((64, 32, 3, 3, 3), float("nan"), device=dev)
+        ws = gd.workspace("ws", nws)
+        dwt = gd.output("dw", (64, 32, 3, 3, 3), torch.float32)
         L.check(lib.qt_conv3d_c32_wgrad(qdt, L.ptr(xd1), xc, L.ptr(dyd), L.ptr(dwt), L.ptr(ws), ctypes.c_size_t(nws), B, T, H, W, st),
                 "qt_conv3d_c32_wgrad")
-        torch.cuda.synchronize()
+        gd.check()
         _same(dwt, c["dw"], F32, "qt_conv3d_c32_wgrad")

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _guard import Guard
 from _util import pkg, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -46,15 +47,21 @@ def run_conv(L, dt, x_nhwc, w_krsc, B, in_hw, out_hw, k_per_tap, n_out, kh, kw, 
     d.quad, d.relu = quad, relu
     if m_rows is None:
         m_rows = B * (4 if (quad and mode == L.QT_CONV_FWD) else 1) * out_hw[0] * out_hw[1]
-    y = torch.empty(m_rows, n_out, dtype=dt, device=dev)
+    # every buffer the kernel sees sits between two poisoned bands (tests/_guard.py); a view keeps its enclosing tensor
+    gd = Guard(dev)
+    x_nhwc, w_krsc = gd.input("x", x_nhwc), gd.input("w", w_krsc)
+    scale, shift = gd.input("scale", scale), gd.input("shift", shift)
+    residual, relu_mask = gd.input("residual", residual), gd.input("relu_mask", relu_mask)
+    y = gd.output("y", (m_rows, n_out), dt)
     stats = None
     if want_stats:
+        # every kernel behind this entry point stores each partial row (none accumulates): the buffer starts as NaN
         rows = L.lib().qt_conv2d_stats_rows(ctypes.byref(d))
-        stats = torch.zeros(rows, 2, n_out, dtype=torch.float32, device=dev)
+        stats = gd.output("stats", (rows, 2, n_out), torch.float32)
     io = L.ConvIO(L.ptr(x_nhwc), L.ptr(w_krsc), L.ptr(y), L.ptr(scale), L.ptr(shift),
                   L.ptr(residual), L.ptr(relu_mask), L.ptr(stats))
     L.check(L.lib().qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm")
-    torch.cuda.synchronize()
+    gd.check()
     return y, stats
 
 
@@ -213,18 +220,21 @@ def run_wgrad(L, dt, dy_nhwc, x_nhwc, B, in_hw, out_hw, k_per_tap, n_out, kh, kw
         strides = (x_nhwc.shape[1] * x_nhwc.shape[2] * c, x_nhwc.shape[2] * c, c)
     d.src_img_stride, d.src_row_stride, d.src_pix_stride = strides
     d.quad = quad
-    dw = torch.zeros(n_out, kh * kw, k_per_tap, dtype=torch.float32, device=dev)
+    gd = Guard(dev)
+    dy_nhwc, x_nhwc = gd.input("dy", dy_nhwc), gd.input("x", x_nhwc)
+    # zeros, not NaN: include/qtcnn.h has both entry points ACCUMULATE into dw (`dw += ...`)
+    dw = gd.output("dw", (n_out, kh * kw, k_per_tap), torch.float32, fill=0)
     if workspace:
         L.lib().qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
         nbytes = L.lib().qt_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
         assert nbytes > 0, "this shape was expected to use the partial-filter workspace"
-        ws = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev)  # must be fully overwritten
+        ws = gd.workspace("ws", nbytes)  # exactly the queried size, NaN: must be fully overwritten before it is read
         L.check(L.lib().qt_conv2d_wgrad_ws(ctypes.byref(d), L.ptr(dy_nhwc), L.ptr(x_nhwc), L.ptr(dw), L.ptr(ws),
                                            ctypes.c_size_t(nbytes), L.stream_ptr()), "qt_conv2d_wgrad_ws")
     else:
         L.check(L.lib().qt_conv2d_wgrad(ctypes.byref(d), L.ptr(dy_nhwc), L.ptr(x_nhwc), L.ptr(dw), L.stream_ptr()),
                 "qt_conv2d_wgrad")
-    torch.cuda.synchronize()
+    gd.check()
     return dw
 
 

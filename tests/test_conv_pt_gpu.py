@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _guard import Guard
 from _util import pkg, rel_err
 from test_conv_gpu import TOL, nhwc, run_conv
 
@@ -138,18 +139,25 @@ def test_pt_dgrad_with_mask_residual_and_bn_links(dt, cfg):
         d.k_per_tap, d.n_out = Cout, Cin
         d.kh = d.kw = 3; d.stride = 1; d.pad = 1
         d.src_img_stride, d.src_row_stride, d.src_pix_stride = H * H * Cout, H * Cout, Cout
-        y = torch.empty(B * H * H, Cin, dtype=dt, device=dev)
-        io = L.ConvIO(L.ptr(dyd), L.ptr(wt), L.ptr(y), None, None, L.ptr(resd), L.ptr(mskd), None)
+        # guarded buffers (tests/_guard.py): NaN output and partial rows (both kernels store every row of a linked buffer),
+        # operands with NaN around them
+        gd = Guard(dev)
+        gdy, gwt, gres, gmsk = gd.input("dy", dyd), gd.input("w", wt), gd.input("residual", resd), gd.input("mask", mskd)
+        gys = [gd.input(f"bn{k}_y", ysd[k]) for k in range(nlinks)]
+        gmu = [gd.input(f"bn{k}_mean", musd[k]) for k in range(nlinks)]
+        gis = [gd.input(f"bn{k}_invstd", issd[k]) for k in range(nlinks)]
+        y = gd.output("y", (B * H * H, Cin), dt)
+        io = L.ConvIO(L.ptr(gdy), L.ptr(gwt), L.ptr(y), None, None, L.ptr(gres), L.ptr(gmsk), None)
         rows = L.lib().qt_conv2d_stats_rows(ctypes.byref(d))
-        parts = [torch.zeros(rows, 2, Cin, device=dev) for _ in range(2)]
+        parts = [gd.output(f"bn{k}_partial", (rows, 2, Cin), torch.float32) for k in range(nlinks)]
         if nlinks >= 1:
-            io.bn0_y, io.bn0_mean, io.bn0_invstd, io.bn0_partial = (ysd[0].data_ptr(), musd[0].data_ptr(),
-                                                                    issd[0].data_ptr(), parts[0].data_ptr())
+            io.bn0_y, io.bn0_mean, io.bn0_invstd, io.bn0_partial = (gys[0].data_ptr(), gmu[0].data_ptr(),
+                                                                    gis[0].data_ptr(), parts[0].data_ptr())
         if nlinks >= 2:
-            io.bn1_y, io.bn1_mean, io.bn1_invstd, io.bn1_partial = (ysd[1].data_ptr(), musd[1].data_ptr(),
-                                                                    issd[1].data_ptr(), parts[1].data_ptr())
+            io.bn1_y, io.bn1_mean, io.bn1_invstd, io.bn1_partial = (gys[1].data_ptr(), gmu[1].data_ptr(),
+                                                                    gis[1].data_ptr(), parts[1].data_ptr())
         L.check(L.lib().qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm")
-        torch.cuda.synchronize()
+        gd.check()
         return y, [p.sum(0).cpu() for p in parts]
 
     for nlinks in (0, 1, 2):

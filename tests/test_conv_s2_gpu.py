@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _guard import Guard
 from _util import pkg, rel_err
 from test_conv_gpu import TOL, nhwc, run_conv
 
@@ -33,15 +34,18 @@ def run_pair(L, dt, xd, wc, wd_, B, H, Cin, Cout, relu_conv=0, sc=None, sh=None,
     d = L.ConvS2Desc(L.qt_dtype(dt), B, H, H, Cin, Cout, relu_conv, 0)
     assert L.lib().qt_conv_s2_pair_supported(ctypes.byref(d)) == 1
     OH = H // 2
-    y = torch.full((B * OH * OH, Cout), float("nan"), dtype=dt, device=dev)
-    yd = torch.full((B * OH * OH, Cout), float("nan"), dtype=dt, device=dev)
+    gd = Guard(dev)   # NaN outputs between poisoned bands, inputs with NaN around them (tests/_guard.py)
+    xd, wc, wd_ = gd.input("x", xd), gd.input("w_conv", wc), gd.input("w_down", wd_)
+    sc, sh, sd, shd = gd.input("sc", sc), gd.input("sh", sh), gd.input("sd", sd), gd.input("shd", shd)
+    y = gd.output("y", (B * OH * OH, Cout), dt)
+    yd = gd.output("yd", (B * OH * OH, Cout), dt)
     rows = L.lib().qt_conv_s2_pair_stats_rows(ctypes.byref(d))
-    st = torch.full((rows, 2, Cout), float("nan"), device=dev) if want_stats else None
-    std = torch.full((rows, 2, Cout), float("nan"), device=dev) if want_stats else None
+    st = gd.output("stats_conv", (rows, 2, Cout), torch.float32) if want_stats else None
+    std = gd.output("stats_down", (rows, 2, Cout), torch.float32) if want_stats else None
     io = L.ConvS2IO(L.ptr(xd), L.ptr(wc), L.ptr(wd_), L.ptr(y), L.ptr(yd), L.ptr(sc), L.ptr(sh), L.ptr(sd), L.ptr(shd),
                     L.ptr(st), L.ptr(std))
     L.check(L.lib().qt_conv_s2_pair(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv_s2_pair")
-    torch.cuda.synchronize()
+    gd.check()
     return y, yd, st, std
 
 

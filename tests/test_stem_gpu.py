@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _guard import Guard
 from _util import pkg, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -161,24 +162,32 @@ def _stem_conv(L, dt, image, w, taps, want_stats, scale=None, shift=None, relu=0
     B = image.shape[0]
     st = L.stream_ptr()
     qdt = L.qt_dtype(dt)
-    xpad = torch.empty(B, 230, 232, 4, device=dev, dtype=dt)
+    # guarded buffers (tests/_guard.py).  The packers write every element of their destinations, zero borders and the zero
+    # eighth tap included, so those start as NaN too; the packed operands then serve as the conv's inputs, and a load past
+    # the last padded row or tap meets the NaN band behind them.
+    gd = Guard(dev)
+    image, w, scale, shift = gd.input("image", image), gd.input("w", w), gd.input("scale", scale), gd.input("shift", shift)
+    xpad = gd.output("xpad", (B, 230, 232, 4), dt)
     L.check(lib.qt_pack_stem_input(qdt, L.ptr(image), L.ptr(xpad), B, st), "qt_pack_stem_input")
-    wp = torch.empty(64, taps, 32, device=dev, dtype=dt)
+    wp = gd.output("w_packed", (64, taps, 32), dt)
     L.check(lib.qt_pack_stem_weight(qdt, L.ptr(w), L.ptr(wp), taps, st), "qt_pack_stem_weight")
+    gd.check()
+    packed = (xpad.clone(), wp.clone())
     d = L.ConvDesc()
     d.dtype, d.mode, d.batch = qdt, L.QT_CONV_FWD, B
     d.in_h, d.in_w, d.out_h, d.out_w = 230, 232, 112, 112
     d.k_per_tap, d.n_out, d.kh, d.kw, d.stride, d.pad = 32, 64, taps, 1, 2, 0
     d.src_img_stride, d.src_row_stride, d.src_pix_stride = 230 * 232 * 4, 232 * 4, 4
     d.relu = relu
-    y = torch.empty(B, 112, 112, 64, device=dev, dtype=dt)
+    y = gd.output("y", (B, 112, 112, 64), dt)
     stats = None
     if want_stats:
         rows = lib.qt_conv2d_stats_rows(ctypes.byref(d))
-        stats = torch.full((rows, 2, 64), float("nan"), dtype=torch.float32, device=dev)
+        stats = gd.output("stats", (rows, 2, 64), torch.float32)
     io = L.ConvIO(L.ptr(xpad), L.ptr(wp), L.ptr(y), L.ptr(scale), L.ptr(shift), None, None, L.ptr(stats))
     L.check(lib.qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), st), "qt_conv2d_igemm")
-    torch.cuda.synchronize()
+    gd.check()
+    assert torch.equal(xpad, packed[0]) and torch.equal(wp, packed[1]), "the conv changed its packed operands"
     return y, stats
 
 
