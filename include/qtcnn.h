@@ -521,6 +521,62 @@ typedef struct qt_pose_desc {
 } qt_pose_desc;
 int qt_pose_features(const qt_pose_desc* desc, const float* landmarks, const unsigned char* detected, const float* raw,
                      const long long* labels, const float* means, const float* stds, float* out, void* stream);
+/* Evaluation report: the confusion matrix, precision / recall / F1, R^2 and the per-frame softmax confidence that the
+ * reference's scripts end on (comparative analysis/analysis.py:60-109, 3dcnn/train_3D_Quadtree_cnn_model.py:248,
+ * VIT/fact_model_train.py:153, experiment/test_on_video_cnn.py:274-278), without the two host copies per batch and
+ * without scikit-learn.  The data is additive integer counts that stay in device memory for a whole evaluation:
+ *   state   u64 [C*C + 4] = { cm[label * C + pred] ..., rows counted, rows ignored, rows invalid, update calls }
+ * (qt_metrics_state_bytes = 8 (C*C + 4)).  The caller zeroes it once; qt_metrics_update only ever adds to it, so the
+ * states of several streams, devices or ranks add up to the state of their union.  1 <= C <= QT_METRICS_MAX_CLASSES,
+ * 1 <= rows <= 2^22 per call; both size queries return 0 for a C outside the range.
+ * qt_metrics_update, one launch per batch.  Exactly one of `logits` and `pred_in`:
+ *   logits     f32 [rows][C], row stride ld >= C elements.  pred = torch.max(logits, 1)'s index by the total order of the
+ *              loss head (a NaN beats every number, then the larger value, then the lower index): bit-identical to the
+ *              `pred` of qt_loss_forward on the same buffer.  With m = logits[pred], all in f32:
+ *                e_k = expf(z_k - m), s = sum_k e_k, p_k = e_k / s
+ *              probs [rows][ld_probs] receives p (columns >= C untouched), confidence [rows] receives p[pred] (the very
+ *              f32 stored to probs[pred]), pred_out [rows] receives pred (int64); each may be NULL.  A row with a NaN or
+ *              +inf logit (or all -inf) is NaN in every column and in confidence, as torch.softmax gives on the CPU.
+ *              Padding columns of the logits are not read into anything.
+ *   pred_in    int64 [rows], e.g. the `pred` output of qt_loss_forward: counting only (no probs / confidence / pred_out).
+ * Counting, when `labels` (int64 [rows]) and `state` are given (both or neither; without them the call only produces
+ * probs / confidence / pred_out): per row, in this order,
+ *   label == desc->ignore_index                                      -> rows ignored += 1
+ *   label outside [0, C), or a given prediction outside [0, C)        -> rows invalid += 1 (nothing is indexed with it)
+ *   otherwise                                                         -> cm[label * C + pred] += 1, rows counted += 1
+ * and update calls += 1 once per call.  Every add is an integer atomic, so the counts are exact in any order of
+ * execution: C <= 64 counts in a per-workgroup u32 histogram in LDS and adds each non-zero cell to the state with one
+ * 64-bit atomic; above that every counted row is one 64-bit atomic.  No allocation, no host synchronisation.
+ * qt_metrics_finalize, one launch of one workgroup: state -> report, 4 C + 12 doubles (qt_metrics_report_bytes).  Counts
+ * are added as integers, everything else is double arithmetic.  With support_i = sum_j cm[i][j], predicted_j = sum_i
+ * cm[i][j], tp_k = cm[k][k], n = sum_i support_i:
+ *   [0, C)      precision_k = tp_k / predicted_k        [C, 2C)   recall_k = tp_k / support_k
+ *   [2C, 3C)    f1_k = 2 tp_k / (support_k + predicted_k)          [3C, 4C)  support_k
+ *               (a zero denominator gives 0: scikit-learn's zero_division=0)
+ *   4C + 0      accuracy = sum_k tp_k / n
+ *   4C + 1..3   weighted precision / recall / F1: sum_k support_k x_k / n
+ *   4C + 4..6   macro precision / recall / F1: the mean over the classes with support_k + predicted_k > 0 (scikit-learn's
+ *               rule when no labels= is passed)
+ *   4C + 7      R^2 of label index against predicted index (analysis.py:89): 1 - SS_res / SS_tot with
+ *               SS_res = sum_ij cm[i][j] (i - j)^2, SS_tot = sum_i support_i (i - mean)^2, mean = sum_i i support_i / n;
+ *               SS_tot == 0: 1.0 when SS_res == 0, else 0.0; n < 2: NaN
+ *   4C + 8..11  n (samples), rows ignored, rows invalid, the number of classes with support_k + predicted_k > 0
+ * With n == 0 accuracy and the six averages are NaN and the per-class values are 0.
+ * QT_ERR_INVALID_ARG (before any device call) for a null desc, both or neither of logits / pred_in, probs / confidence /
+ * pred_out without logits, labels without a state or a state without labels, a call that would produce nothing, ld < C,
+ * ld_probs < C, rows <= 0, C <= 0, misaligned pointers (4 bytes for f32, 8 for the 64-bit arrays); QT_ERR_UNSUPPORTED for
+ * C > 1024, rows > 2^22 and a dtype other than QT_F32. */
+#define QT_METRICS_MAX_CLASSES 1024
+typedef struct qt_metrics_desc {
+  int dtype;                  /* of the logits: QT_F32 */
+  long long ignore_index;     /* torch's default: -100 */
+} qt_metrics_desc;
+size_t qt_metrics_state_bytes(int C);
+size_t qt_metrics_report_bytes(int C);
+int qt_metrics_update(const qt_metrics_desc* desc, const float* logits, long long ld, const long long* pred_in,
+                      const long long* labels, long long rows, int C, unsigned long long* state, float* probs,
+                      long long ld_probs, float* confidence, long long* pred_out, void* stream);
+int qt_metrics_finalize(const unsigned long long* state, int C, double* report, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

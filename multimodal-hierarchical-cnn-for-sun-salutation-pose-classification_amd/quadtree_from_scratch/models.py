@@ -17,6 +17,7 @@ QtError = importlib.import_module(_PKG + "._lib").QtError
 FusedAdam = importlib.import_module(_PKG + ".optim").FusedAdam  # optional replacement of optim.Adam(...)
 grad_norm = importlib.import_module(_PKG + ".optim").grad_norm  # global gradient norm on the device (logging)
 GradCAM = importlib.import_module(_PKG + ".gradcam").GradCAM  # batched Grad-CAM maps and overlays on the device
+EvalMeter = importlib.import_module(_PKG + ".metrics").EvalMeter  # confusion matrix, P/R/F1, R^2 counted on the device
 jet_lut = importlib.import_module(_PKG + ".gradcam").jet_lut
 
 

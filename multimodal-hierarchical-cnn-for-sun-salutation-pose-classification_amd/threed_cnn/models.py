@@ -19,6 +19,7 @@ _v3d = importlib.import_module(_PKG + ".video3d")
 _impl = importlib.import_module(_PKG + ".quadtree")
 QtError = importlib.import_module(_PKG + "._lib").QtError
 GradCAM = importlib.import_module(_PKG + ".gradcam").GradCAM  # batched Grad-CAM maps and overlays on the device
+EvalMeter = importlib.import_module(_PKG + ".metrics").EvalMeter  # confusion matrix, P/R/F1, R^2 counted on the device
 jet_lut = importlib.import_module(_PKG + ".gradcam").jet_lut
 
 StandardResNetCNN = _impl.StandardResNetCNN
