@@ -577,6 +577,72 @@ int qt_metrics_update(const qt_metrics_desc* desc, const float* logits, long lon
                       const long long* labels, long long rows, int C, unsigned long long* state, float* probs,
                       long long ld_probs, float* confidence, long long* pred_out, void* stream);
 int qt_metrics_finalize(const unsigned long long* state, int C, double* report, void* stream);
+/* Annotated frames: the last step of the reference's video loop (experiment/test_on_video_cnn.py:280-295: draw_landmarks,
+ * putText, then the writer) and the drawing step of sqn process/processing_image_sequence.py:250-318 (draw_enhanced_skeleton),
+ * resnet/grad_cam_analysis.py:437 and grad_cam/5_grad_cam_visualizer.py, for a whole batch of uint8 frames in one launch, from
+ * tensors that are already on the device (the landmarks qt_pose_features takes, the pred / confidence qt_metrics_update
+ * writes): no host read of a prediction, one copy of the finished frames.
+ * frames, out: uint8 [batch][H][W][3], contiguous, any address; out == frames is allowed, no other overlap.  Two groups of
+ * operands, each given whole or not at all, at least one of them:
+ *   skeleton  landmarks f32 [batch][33][4] = x, y, z, visibility (16-byte aligned); segments uint8 [n_segments][3] = landmark
+ *             a, landmark b, major flag, in DEVICE memory, 0 <= n_segments <= QT_ANNOTATE_MAX_SEGMENTS; detected uint8 [batch]
+ *             or NULL (every frame detected).
+ *   caption   pred int64 [batch]; atlas uint8 [num_classes + 14][glyph_h][glyph_w] coverage masks and atlas_widths int32
+ *             [num_classes + 14]: glyph g < num_classes is the pre-rendered caption of class g (whatever string the caller
+ *             rendered, e.g. "Pose: Tadasana"), then '0'..'9', '.', '(', ')', ' '; confidence f32 [batch] or NULL.
+ * The rule per frame, every coordinate an exact integer:
+ *   1. P_j = (trunc(x_j W), trunc(y_j H)): the product in f32, truncated toward zero (Python's int()).  Landmark j is usable
+ *      when both products are finite and lie in [-8192, 16383]; a primitive that needs an unusable landmark is skipped, and so
+ *      is a segment with a landmark index above 32 (nothing is indexed with it).  A frame with detected == 0 gets no skeleton.
+ *   2. Segment (a, b, major): T = major ? thick_major : thick_minor; colour line_hi when both visibilities are
+ *      > min_visibility, else line_lo (a NaN visibility is low).  Pixel q is covered iff 4 dist^2(q, segment) <= T^2, taken
+ *      as: d = P_b - P_a, e = q - P_a, L = d.d, t = e.d;  L == 0 or t <= 0: 4 e.e <= T^2;  t >= L: 4 |q - P_b|^2 <= T^2;
+ *      otherwise cross = e.x d.y - e.y d.x and cross^2 <= floor(T^2 L / 4).  (|cross| < 2^31 and every product fits a signed
+ *      64-bit integer for H, W <= 8192, T <= 15 and usable landmarks.)
+ *   3. Landmark j: the disc |q - P_j|^2 <= r^2 with r = radius_hi and point_hi when its visibility is > min_visibility, else
+ *      radius_lo and point_lo.
+ *   4. Painter's order: the segments in list order, then landmarks 0 .. 32; the last primitive that covers a pixel wins,
+ *      drawing is opaque (draw_enhanced_skeleton's two passes).
+ *   5. The caption, over the skeleton (putText follows draw_landmarks): none when pred[b] is outside [0, num_classes) (only
+ *      the device sees it).  Otherwise the glyphs are pred[b], followed, when confidence is given and not NaN, by
+ *      ' ' '(' d0 '.' d1 d2 ')' with n = clamp((int)rintf(confidence * 100.0f), 0, 100) and the digits n / 100, n / 10 % 10,
+ *      n % 10.  Glyph k occupies columns [pen_k, pen_k + width_k) and rows [oy, oy + glyph_h); pen_0 = ox; a width outside
+ *      [0, glyph_w] counts as 0.  Where its mask m > 0: out_c = (m colour_c + (255 - m) under_c + 127) / 255 in integers.
+ *   6. Everything is clipped to the frame; every other pixel of out equals frames.
+ * Colours are bytes in the frames' channel order.
+ * Against the reference: it multiplies in float64, so a product within one f32 rounding of an integer can land in the
+ * neighbouring pixel; f"{confidence:.2f}" can differ in the last digit where confidence * 100 rounds in f32 to within one
+ * step of a half.  cv2.line draws thick lines as filled polygons with round caps in fixed point and cv2.circle its own
+ * midpoint discs: bit equality with them is not claimed, the rule above is the exact Euclidean one.  MediaPipe's own default
+ * drawing style (test_on_video_cnn.py) is not reproduced, the style is draw_enhanced_skeleton's.  Text is the caller's atlas,
+ * not Hershey strokes.
+ * One launch: a workgroup owns 4096 consecutive pixels of one frame, lists in LDS the primitives whose bounding box meets
+ * them, and each thread owns 16 pixels = three 16-byte stores (16-byte loads where frames and out agree modulo 16, scalar
+ * heads and tails per frame).  With out == frames, pixels no primitive can reach are neither read nor written.  No workspace,
+ * no atomics, no zero fill, no host synchronisation; nothing outside the stated extents is read or written; the same bits on
+ * every run and for a frame alone or inside a batch.
+ * QT_ERR_INVALID_ARG (before any device call) for a null desc, non-positive batch / H / W, n_segments outside
+ * [0, QT_ANNOTATE_MAX_SEGMENTS], a thickness or radius outside [1, 15] or a NaN min_visibility (the three with a skeleton;
+ * a caption alone does not read them), null frames / out, out that overlaps frames without being equal to it, a group given in part (landmarks without segments or the reverse, detected
+ * without landmarks; pred, atlas, atlas_widths not all three; confidence without them), neither group, misaligned
+ * landmarks (16) / pred (8) / confidence and atlas_widths (4), and with a caption num_classes, glyph_h or glyph_w below 1;
+ * QT_ERR_UNSUPPORTED for H or W above 8192, more than 2^31 bytes of frames, glyph_h or glyph_w above 8192, |ox| or |oy|
+ * above 2^20. */
+#define QT_ANNOTATE_MAX_SEGMENTS 64
+typedef struct qt_annotate_desc {
+  int batch, H, W, n_segments;
+  float min_visibility;             /* 0.65 in the reference's call */
+  int thick_major, thick_minor;     /* 5 and 2 */
+  int radius_hi, radius_lo;         /* 3 and 2 */
+  unsigned char line_hi[3], line_lo[3], point_hi[3], point_lo[3];
+  int num_classes, glyph_h, glyph_w;
+  int ox, oy;                       /* top-left of the first glyph */
+  unsigned char caption_colour[3];
+} qt_annotate_desc;
+int qt_annotate_u8(const qt_annotate_desc* desc, const unsigned char* frames, const float* landmarks,
+                   const unsigned char* detected, const unsigned char* segments, const long long* pred,
+                   const float* confidence, const unsigned char* atlas, const int* atlas_widths, unsigned char* out,
+                   void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of
