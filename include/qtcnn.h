@@ -521,6 +521,61 @@ typedef struct qt_pose_desc {
 } qt_pose_desc;
 int qt_pose_features(const qt_pose_desc* desc, const float* landmarks, const unsigned char* detected, const float* raw,
                      const long long* labels, const float* means, const float* stds, float* out, void* stream);
+/* Sequence pose features: the 443 columns per frame that sqn process/processing_image_sequence.py:96-247
+ * (calculate_all_features, driven per clip by the loop at :374-441) writes and create_sequential_dataset.py:179-181 stores as a
+ * sequence's features.npy, followed by the CNN+LSTM loader's NaN -> 0 (cnn+lstm/dataloader.py:64-65), in one launch.  Unlike
+ * the 47-vector a frame depends on earlier frames of its clip.
+ * landmarks: f32 [batch][frames][33][4] = x, y, z, visibility, 16-byte aligned; detected: uint8 [batch][frames] or NULL (a
+ * pose in every frame); sizes: int32 [batch][2] = (W, H) of each clip's frames, device, or NULL for desc->width / height;
+ * out: f32 [batch][frames][443].  All arithmetic is f32.  q_j = (x_j W, y_j H, z_j W) is the pixel position of landmark j.
+ * A landmark is visible iff visibility > 0.65f.  The reference tests `visibility < 0.65` (not visible) in one helper and
+ * `visibility > 0.65` (visible) elsewhere, both against a double; for an f32 v, double(v) < 0.65 <=> v <= 0.65f and
+ * double(v) > 0.65 <=> v > 0.65f (0.65 is no f32: it lies between 0.65f and the next f32 above), so the one predicate
+ * reproduces both.  A NaN
+ * visibility is not visible (the reference's `<` gate lets a NaN through; that is not reproduced).
+ *   4j .. 4j+3  (0-131)    x, y, z, visibility of landmark j as given.
+ *   132-141   the angle at b of (a, b, c) in degrees over q for (11,13,15) (12,14,16) (13,11,23) (14,12,24) (23,25,27)
+ *             (24,26,28) (11,23,25) (12,24,26) (0,11,23) (11,12,23): NaN unless a, b, c are visible, else
+ *             deg(atan2(|ba x bc|, ba . bc)) with ba = q_a - q_b, bc = q_c - q_b, which is 0 when ba or bc is the zero
+ *             vector (the reference returns 0.0 there).  The reference's arccos(clip(ba . bc / (|ba| |bc|))) is the same
+ *             angle; in f32 it loses half its digits near 0 and 180 degrees, atan2 does not (as for qt_pose_features).
+ *   142-144   |q15 - q16|, |q27 - q28|, |q15 - q23| divided by s, NaN unless both landmarks are visible.  sw = |q11 - q12|
+ *             if 11 and 12 are visible, else 0; hw = |q23 - q24| likewise; s = sw if sw > 0.05f W, else hw if
+ *             hw > 0.05f W, else H / 3.
+ *   145+3j .. (145-243)    (x, y, z)_j - m, NaN if landmark j is not visible; m = ((x, y, z)_23 + (x, y, z)_24) * 0.5f if 23
+ *             and 24 are visible, else (0.5, 0.5, 0).
+ *   244+6j .. (244-441)    v = q_j - q'_j, then a = v - (q'_j - q''_j), where ' and '' are the most recent and the second
+ *             most recent DETECTED frames before this one in the clip (undetected frames do not enter the history:
+ *             :375, :410-416).  All six are NaN unless landmark j is visible in all three frames, and when fewer than two
+ *             such frames exist (the reference leaves the velocity NaN too then).  All three positions use this clip's
+ *             (W, H).
+ *   442       over the visible ones of landmarks 11, 12, 23, 24: (var(x) + 1e-6f) / (var(y) + 1e-6f), population variances
+ *             in two passes (the mean, then the squared deviations); NaN with fewer than two.
+ * A frame with detected == 0 is 443 NaNs (the reference's dummy dict has mis-spelt keys and pandas leaves the real columns
+ * NaN); its landmark values are not used.  A non-positive W or H in device `sizes` makes that clip's rows NaN (only the
+ * device sees it); the history is carried as usual.  Then desc->mode: QT_POSE_RAW (NaNs stay) or QT_POSE_ZERO (NaN -> 0);
+ * the two class-table modes do not exist for these columns.
+ * History across calls (a live loop hands frames over in chunks).  hist_in: f32 [batch][2][33][4], the landmarks of the last
+ * two detected frames before this call's first frame, slot 0 the most recent, 16-byte aligned, with hist_count_in: uint8
+ * [batch], how many slots hold a frame (0, 1, 2; more counts as 2); both NULL: every clip starts empty.  hist_out /
+ * hist_count_out (both or neither) receive the same state after the last frame of the call; slots beyond the count are
+ * written as zeros.  hist_out must not overlap hist_in, nor hist_count_out hist_count_in (other workgroups still read them):
+ * a caller swaps two buffers.  A clip processed in any split into consecutive calls gives the same bits as one call.
+ * One launch, no atomics, no zero fill, no workspace, no host synchronisation; the same bits on every run and for a clip
+ * alone or inside a batch.  Inputs are never written.
+ * QT_ERR_INVALID_ARG (before any device call) for non-positive batch or frames, null or misaligned pointers (landmarks and
+ * the histories 16 bytes, out and sizes 4), half a history pair, overlapping histories, a mode other than RAW and ZERO, a
+ * non-positive desc->width / height when sizes is NULL; QT_ERR_UNSUPPORTED for more than 2^22 frames in all. */
+#define QT_POSE_SEQ_FEATURES 443
+typedef struct qt_pose_seq_desc {
+  int batch;                        /* clips */
+  int frames;                       /* frames per clip in this call */
+  int width, height;                /* frame size of every clip; read when `sizes` is NULL */
+  int mode;                         /* QT_POSE_RAW or QT_POSE_ZERO */
+} qt_pose_seq_desc;
+int qt_pose_sequence_features(const qt_pose_seq_desc* desc, const float* landmarks, const unsigned char* detected,
+                              const int* sizes, const float* hist_in, const unsigned char* hist_count_in, float* hist_out,
+                              unsigned char* hist_count_out, float* out, void* stream);
 /* Evaluation report: the confusion matrix, precision / recall / F1, R^2 and the per-frame softmax confidence that the
  * reference's scripts end on (comparative analysis/analysis.py:60-109, 3dcnn/train_3D_Quadtree_cnn_model.py:248,
  * VIT/fact_model_train.py:153, experiment/test_on_video_cnn.py:274-278), without the two host copies per batch and

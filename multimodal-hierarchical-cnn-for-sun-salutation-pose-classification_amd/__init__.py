@@ -15,11 +15,13 @@ from .quadtree import AttentionHierarchicalCNN, CnnLstm, QuadtreeCNN, StandardRe
 from .video3d import Ji3DCNN, Quadtree3DCNN  # noqa: F401
 from .gradcam import GradCAM, jet_lut  # noqa: F401
 from .pose import FEATURE_NAMES, PoseFeatures, load_class_stats  # noqa: F401
+from .pose_sequence import NUM_SEQUENCE_FEATURES, SEQUENCE_FEATURE_NAMES, SequencePoseFeatures  # noqa: F401
 from .metrics import EvalMeter, predict  # noqa: F401
 from .annotate import MAJOR_SEGMENTS, POSE_CONNECTIONS, FrameAnnotator, caption_atlas  # noqa: F401
 
 __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnLstm", "Quadtree3DCNN", "Ji3DCNN", "FusedAdam", "grad_norm",
            "CrossEntropyLoss", "FocalLoss", "LossMeter", "FramePreprocessor", "random_resized_crop_boxes", "random_flips", "FrameAugmenter",
            "GradCAM", "jet_lut", "PoseFeatures", "FEATURE_NAMES", "load_class_stats", "EvalMeter", "predict",
+           "SequencePoseFeatures", "SEQUENCE_FEATURE_NAMES", "NUM_SEQUENCE_FEATURES",
            "FrameAnnotator", "caption_atlas", "POSE_CONNECTIONS", "MAJOR_SEGMENTS",
            "QtError", "LIB_PATH"]
