@@ -576,6 +576,97 @@ typedef struct qt_pose_seq_desc {
 int qt_pose_sequence_features(const qt_pose_seq_desc* desc, const float* landmarks, const unsigned char* detected,
                               const int* sizes, const float* hist_in, const unsigned char* hist_count_in, float* hist_out,
                               unsigned char* hist_count_out, float* out, void* stream);
+/* Sequence windows: the step between labelled clips and the [B][T][...] samples of the sequence models, with every clip held
+ * on the device once instead of one stored copy per window (sqn process/create_sequential_dataset.py:154-205 copies 10 frames
+ * per window at stride 1; cnn+lstm/prepare_sequential_dataset.py:36-112 stores every window as T normalised f32 frames).
+ * Three entry points: which windows there are (qt_seq_windows_plan), a batch of windows of any per-frame array
+ * (qt_seq_gather_rows), a batch of windows of f32 pose rows with the loaders' imputation (qt_seq_gather_features).
+ *
+ * qt_seq_windows_plan.  labels: int64 [frames], device: the frames of all clips one after the other, each clip in temporal
+ * order; clip_offsets: int32 [clips + 1], device, ascending from 0 to frames (clip c is frames clip_offsets[c] ..
+ * clip_offsets[c + 1] - 1; an empty clip is allowed).  Candidate starts are clip_offsets[c] + i for i = 0, stride, 2 stride, ...
+ * while i + seq_len <= the clip's length: a window never crosses a clip boundary, a clip shorter than seq_len gives none.
+ * desc->rule decides which candidates are kept and their label:
+ *   QT_SEQ_LABEL_UNIFORM  (create_sequential_dataset.py:164-171) kept iff the window's seq_len labels are all equal and lie in
+ *                         [0, num_classes); the label is that value.
+ *   QT_SEQ_LABEL_LAST     (prepare_sequential_dataset.py:46-62) the label is the last frame's; kept iff it lies in
+ *                         [0, num_classes).  The other frames' labels are not looked at.
+ * starts: int32 [capacity], the kept starts in ascending frame order (the reference's order: clips in order, i ascending);
+ * window_labels: int64 [capacity], their labels; count: int32 [1], the number of kept windows.  When it exceeds capacity only
+ * the first capacity starts and labels are written and count still holds the total; elements at and behind count are not
+ * written.  (Capacity never needs to exceed the number of candidates, sum over clips of max(0, (n_c - seq_len) / stride + 1).)
+ * The only notion of "no label" is a value outside [0, num_classes).  The reference removes the frames that have no label
+ * from its table BEFORE it windows (create_sequential_dataset.py:125-127), so its windows run over the remaining frames and
+ * may bridge the gap; that filter is the caller's, applied to the labels, the offsets and the per-frame arrays alike before
+ * this call.
+ * Three launches on `stream` (counts per workgroup, an exclusive scan of the counts by one workgroup, the scatter); the
+ * partial counts live in `workspace` (qt_seq_windows_workspace_bytes, 4-byte aligned; every slot used is written, nothing
+ * needs zeroing).  No workgroup waits for another inside a launch, no atomics, no host synchronisation; the same bits on
+ * every run.  clip_offsets is read at indices 0 .. clips and labels at 0 .. frames - 1 only, whatever the offsets hold: a
+ * clip's end is cut at frames, and offsets that do not ascend give fewer windows, never a read outside an array.
+ * QT_ERR_INVALID_ARG (before any device call) for a null desc, non-positive frames, clips, num_classes, capacity or stride,
+ * seq_len outside 1 .. 64, an unknown rule, null or misaligned pointers (8 bytes for the int64 arrays, 4 for the others), a
+ * workspace that is too small; QT_ERR_UNSUPPORTED for more than 2^22 frames.  qt_seq_windows_workspace_bytes returns 0 for
+ * a descriptor the call would refuse.
+ *
+ * qt_seq_gather_rows.  dst[b][t][:] = src[starts[b] + t][:] for b < windows, t < seq_len; rows of row_bytes bytes (any
+ * value >= 1), src of src_rows rows, starts: int32 [windows], device (the loader's plan.starts[idx]; duplicates are fine).
+ * A window is one contiguous run of seq_len * row_bytes bytes; source and destination run need not agree modulo 16: units of
+ * 16 bytes where they do, of 4 bytes where they agree modulo 4, single bytes otherwise, with single bytes up to the
+ * destination's first boundary and behind the last whole unit.  src and dst need no alignment.  A start outside
+ * [0, src_rows - seq_len] makes that window's seq_len * row_bytes bytes 0xFF (NaN as f32 and bf16, 255 as a byte): only the
+ * device sees the value, nothing is read for it, the other windows are unaffected.  One launch, 64-bit byte offsets, no
+ * atomics, no workspace, no host synchronisation; nothing outside src is read, src is not written.
+ * QT_ERR_INVALID_ARG (before any device call) for a null desc, non-positive src_rows, row_bytes or windows, seq_len outside
+ * 1 .. 64, null pointers, misaligned starts, src and dst that overlap; QT_ERR_UNSUPPORTED for src_rows >= 2^31, row_bytes above
+ * 2^34 or more workgroups than one launch takes.
+ *
+ * qt_seq_gather_features.  The same gather for f32 rows of desc->features columns (1 .. 1024; 47 and 443 are in use), out:
+ * f32 [windows][seq_len][features], with the imputation of qt_pose_features applied as an element is stored, by desc->mode
+ * and ONE label per window, label = window_labels[b] (int64 [windows], device; 3dcnn/dataloaders.py:186-207 uses the
+ * sequence's label for every frame); means, stds: f32 [num_classes][features], device:
+ *   QT_POSE_RAW          v (NaNs stay); the same bytes as qt_seq_gather_rows
+ *   QT_POSE_ZERO         NaN -> 0
+ *   QT_POSE_CLASS_MEAN   NaN -> means[label][f]
+ *   QT_POSE_STANDARDIZE  NaN -> means[label][f], then (v - means[label][f]) / stds[label][f] in f32; 0 where
+ *                        stds[label][f] < 1e-6f
+ * which for features == 47 are the bits of qt_pose_features on the gathered rows with rows_per_label = seq_len.  In the last
+ * two modes a label outside [0, num_classes) makes that window NaN (nothing is indexed with it); a start outside
+ * [0, src_rows - seq_len] makes it 0xFF bytes (a NaN) in every mode.  window_labels, means, stds are not read in the first two
+ * modes.  One launch, no atomics, no workspace, no host synchronisation; the same bits on every run.
+ * QT_ERR_INVALID_ARG (before any device call) for a null desc, non-positive src_rows or windows, features outside 1 .. 1024,
+ * seq_len outside 1 .. 64, an unknown mode, a class mode without the labels / tables it needs, null or misaligned pointers (4
+ * bytes for f32 and int32, 8 for window_labels), rows and output that overlap; QT_ERR_UNSUPPORTED for src_rows >= 2^31. */
+enum { QT_SEQ_LABEL_UNIFORM = 0, QT_SEQ_LABEL_LAST = 1 };
+typedef struct qt_seq_windows_desc {
+  int frames;                       /* frames of all clips together, <= 2^22 */
+  int clips;
+  int seq_len;                      /* 1 .. 64 */
+  int stride;                       /* >= 1 */
+  int num_classes;
+  int capacity;                     /* elements of starts / window_labels */
+  int rule;                         /* QT_SEQ_LABEL_* */
+} qt_seq_windows_desc;
+size_t qt_seq_windows_workspace_bytes(const qt_seq_windows_desc* desc);
+int qt_seq_windows_plan(const qt_seq_windows_desc* desc, const long long* labels, const int* clip_offsets, int* starts,
+                        long long* window_labels, int* count, void* workspace, size_t workspace_bytes, void* stream);
+typedef struct qt_seq_gather_desc {
+  long long src_rows;
+  long long row_bytes;
+  int windows;
+  int seq_len;
+} qt_seq_gather_desc;
+int qt_seq_gather_rows(const qt_seq_gather_desc* desc, const void* src, const int* starts, void* dst, void* stream);
+typedef struct qt_seq_features_desc {
+  long long src_rows;
+  int features;                     /* 1 .. 1024 */
+  int windows;
+  int seq_len;
+  int mode;                         /* QT_POSE_* */
+  int num_classes;                  /* K of means / stds; read in the two class modes only */
+} qt_seq_features_desc;
+int qt_seq_gather_features(const qt_seq_features_desc* desc, const float* raw, const int* starts, const long long* window_labels,
+                           const float* means, const float* stds, float* out, void* stream);
 /* Evaluation report: the confusion matrix, precision / recall / F1, R^2 and the per-frame softmax confidence that the
  * reference's scripts end on (comparative analysis/analysis.py:60-109, 3dcnn/train_3D_Quadtree_cnn_model.py:248,
  * VIT/fact_model_train.py:153, experiment/test_on_video_cnn.py:274-278), without the two host copies per batch and

@@ -16,6 +16,7 @@ from .video3d import Ji3DCNN, Quadtree3DCNN  # noqa: F401
 from .gradcam import GradCAM, jet_lut  # noqa: F401
 from .pose import FEATURE_NAMES, PoseFeatures, load_class_stats  # noqa: F401
 from .pose_sequence import NUM_SEQUENCE_FEATURES, SEQUENCE_FEATURE_NAMES, SequencePoseFeatures  # noqa: F401
+from .sequence_windows import SequenceWindows, WindowPlan, fit_class_stats  # noqa: F401
 from .metrics import EvalMeter, predict  # noqa: F401
 from .annotate import MAJOR_SEGMENTS, POSE_CONNECTIONS, FrameAnnotator, caption_atlas  # noqa: F401
 
@@ -23,5 +24,6 @@ __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnL
            "CrossEntropyLoss", "FocalLoss", "LossMeter", "FramePreprocessor", "random_resized_crop_boxes", "random_flips", "FrameAugmenter",
            "GradCAM", "jet_lut", "PoseFeatures", "FEATURE_NAMES", "load_class_stats", "EvalMeter", "predict",
            "SequencePoseFeatures", "SEQUENCE_FEATURE_NAMES", "NUM_SEQUENCE_FEATURES",
+           "SequenceWindows", "WindowPlan", "fit_class_stats",
            "FrameAnnotator", "caption_atlas", "POSE_CONNECTIONS", "MAJOR_SEGMENTS",
            "QtError", "LIB_PATH"]

@@ -102,6 +102,25 @@ def load_class_stats(means_json, stds_json=None, class_names=None):
     return table(means, means_json), (table(stds, stds_json) if stds is not None else None)
 
 
+def class_stats(raw, labels, num_classes):
+    """The rule of PoseFeatures.fit for any column count: raw f32 [N,F], labels int64 [N], both checked by the caller ->
+    (means, stds) f32 [num_classes,F].  Torch float64 on raw's device."""
+    v = raw.double()
+    member = torch.nn.functional.one_hot(labels.clamp(0, num_classes - 1), num_classes).double()
+    member = member * ((labels >= 0) & (labels < num_classes)).double()[:, None]      # [N,K]
+    valid = (~torch.isnan(v)).double()                                                # [N,F]
+    v0 = torch.nan_to_num(v, nan=0.0)
+    count = member.t() @ valid                                                        # [K,F]
+    n = count.clamp_min(1.0)
+    mean = (member.t() @ (v0 * valid)) / n
+    dev2 = (v0 - member @ mean) ** 2 * valid     # each row against its own class's mean
+    std = torch.sqrt((member.t() @ dev2) / n) + 1e-6
+    empty = count == 0
+    mean = torch.where(empty, torch.zeros_like(mean), mean)
+    std = torch.where(empty, torch.ones_like(std), std)
+    return mean.float(), std.float()
+
+
 class PoseFeatures:
     """mode: "zero", "raw", "class_mean" or "standardize"; means (both class modes) and stds ("standardize"): f32 [K,47]
     on the GPU the inputs will be on.  See the module text."""
@@ -137,20 +156,7 @@ class PoseFeatures:
                           f"{list(labels.shape)})")
         if num_classes < 1:
             raise ValueError("PoseFeatures.fit: num_classes must be positive")
-        v = raw.double()
-        member = torch.nn.functional.one_hot(labels.clamp(0, num_classes - 1), num_classes).double()
-        member = member * ((labels >= 0) & (labels < num_classes)).double()[:, None]      # [N,K]
-        valid = (~torch.isnan(v)).double()                                                # [N,F]
-        v0 = torch.nan_to_num(v, nan=0.0)
-        count = member.t() @ valid                                                        # [K,F]
-        n = count.clamp_min(1.0)
-        mean = (member.t() @ (v0 * valid)) / n
-        dev2 = (v0 - member @ mean) ** 2 * valid     # each row against its own class's mean
-        std = torch.sqrt((member.t() @ dev2) / n) + 1e-6
-        empty = count == 0
-        mean = torch.where(empty, torch.zeros_like(mean), mean)
-        std = torch.where(empty, torch.ones_like(std), std)
-        return mean.float(), std.float()
+        return class_stats(raw, labels, num_classes)
 
     def _run(self, landmarks, detected, raw, labels, out, rows, rows_per_label, dev, what):
         if not 1 <= rows <= MAX_ROWS:

@@ -22,9 +22,9 @@ A live loop that gets its frames in chunks carries the two previous detected fra
 
 Against the reference: angles are atan2(|ba x bc|, ba . bc) in f32 where the reference takes arccos of the clipped cosine
 in float64 (the same angle); a NaN visibility is not visible (the reference's `<` gate lets it through); one frame size per
-clip, where the reference reads every image's own shape.  Not built: class-mean and standardize imputation for the 443
-columns, the sliding-window grouping of create_sequential_dataset.py, MediaPipe itself.  There is no torch fallback: CPU
-tensors and other dtypes raise QtError.
+clip, where the reference reads every image's own shape.  Class-mean and standardize imputation for the 443 columns and the
+sliding-window grouping of create_sequential_dataset.py are sequence_windows.py (SequenceWindows.gather_features, .plan).
+Not built: MediaPipe itself.  There is no torch fallback: CPU tensors and other dtypes raise QtError.
 """
 import ctypes
 
