@@ -789,6 +789,94 @@ int qt_annotate_u8(const qt_annotate_desc* desc, const unsigned char* frames, co
                    const unsigned char* detected, const unsigned char* segments, const long long* pred,
                    const float* confidence, const unsigned char* atlas, const int* atlas_widths, unsigned char* out,
                    void* stream);
+/* Pose timeline: what lies between the per-frame probabilities of the video loop (qt_metrics_update's probs) and what a
+ * practitioner is shown or told: a trailing-window mean of the probabilities with its argmax and confidence
+ * (qt_timeline_smooth), then a debounced label per frame and the list of segments "which pose from when to when"
+ * (qt_timeline_decode).  The reference has no such step (experiment/test_on_video_cnn.py:274-292 writes each frame's raw
+ * argmax), so nothing of it is restated here.  batch = streams (videos, or the camera feeds of a live loop), frames = this
+ * call's frames per stream: qt_pose_sequence_features' layout.  Both calls take the one descriptor and read their own fields.
+ *
+ * qt_timeline_smooth (reads batch, frames, num_classes = C, window = W).  probs: f32 [batch][frames][C], row stride ld >= C
+ * elements, a stream's rows `frames * ld` apart; padding columns are neither read into a result nor written.  For frame f of a
+ * stream, with seen = min(hist_count_in, W - 1) the rows its history holds (0 without a history):
+ *   n = min(W, seen + f + 1)
+ *   s_k = p[f-n+1][k]; then s_k = s_k + p[g][k] for g = f-n+2 .. f, one f32 add after the other, oldest row first, formed
+ *         afresh for every frame (no running sum: it would drift, keep a NaN for ever, and depend on where a call starts);
+ *   m_k = s_k / (float)n, the IEEE f32 quotient; a NaN m_k is stored as the quiet NaN 0x7fc00000 (sign and payload of a
+ *         computed NaN differ between processors; a number is never touched)
+ * where p[g] for g < 0 is hist_in slot -1 - g.  NaN and inf go by IEEE rules into the n frames that read them.
+ *   pred        int64 [batch][frames]: argmax_k m_k by the loss head's total order (a NaN beats every number, then the larger
+ *               value, then the lower index), the order of qt_loss_forward and qt_metrics_update
+ *   confidence  f32 [batch][frames]: m[pred]
+ *   smoothed    f32 [batch][frames][C], row stride ld_smoothed >= C, or NULL
+ * pred and confidence are both required (they are what qt_annotate_u8 and qt_timeline_decode take).
+ * History across calls.  hist_in: f32 [batch][W-1][C] dense, the last W - 1 rows before this call, slot 0 the most recent;
+ * hist_count_in: int32 [batch], how many slots hold a row (a value above W - 1 counts as W - 1, a negative one as 0; a zeroed
+ * count is an empty stream); slots at and beyond the count are not read.  hist_out / hist_count_out: the same state after the
+ * call's last frame, rows copied bit for bit, slots beyond the count written as zeros.  Both pairs NULL: every stream starts
+ * empty and nothing is kept.  With W == 1 there is no history: the pointers are not looked at.  hist_out must not overlap
+ * hist_in, nor hist_count_out hist_count_in (other workgroups still read them): a caller swaps two buffers.  A stream
+ * processed in any split into consecutive calls gives the same bits as one call: a predecessor row is the same value from
+ * probs or from the history and goes through the same additions in the same order.
+ * One launch: a workgroup owns QT_TIMELINE_TILE consecutive frames of one stream, stages them and the W - 1 rows in front of
+ * them in LDS (16-byte loads where ld, C and the addresses are multiples of four floats, single floats otherwise), sums with
+ * thread = (frame, class) and takes the argmax across the class lanes (one 16-lane DPP row for C <= 16, a wave above); the
+ * workgroup that owns a stream's last frame writes the history.  No atomics, no zero fill, no workspace, no host
+ * synchronisation; the same bits on every run and for a stream alone or in a batch; inputs are never written; nothing
+ * outside [0, frames) of a stream and the history's counted slots is read.
+ *
+ * qt_timeline_decode (reads batch, frames, num_classes, min_run, min_confidence, capacity, flush).  pred: int64
+ * [batch][frames], confidence: f32 [batch][frames]; state: int64 [batch][QT_TIMELINE_STATE], in device memory for the whole
+ * video, updated in place:
+ *   { frames_seen, stable + 1, cand + 1, run, seg_start, seg_len, seg_conf_sum, segments_total }
+ * Labels are stored plus one, so a zeroed state is the initial state (the caller zeroes it once).  Per stream, frame by frame
+ * in order, t = frames_seen + f:
+ *   c = (confidence >= min_confidence && 0 <= pred < C) ? pred : -1          (a NaN confidence gives -1)
+ *   c == cand: run = min(run + 1, 2^31 - 1); otherwise cand = c, run = 1
+ *   run >= min_run: stable = cand      (so min_run unknown frames in a row make the label unknown again)
+ *   stable[f] = stable, int64 [batch][frames], -1 for none (qt_annotate_u8 draws no caption for it)
+ * A segment is a maximal run of frames with one stable >= 0; a run of -1 is a gap, not a segment.  When stable changes at
+ * frame t, the open segment (if seg_len > 0) is closed, and a stable >= 0 opens one with seg_start = t.  Every frame of an
+ * open segment adds 1 to seg_len and q(confidence) to seg_conf_sum, q(x) = (long long)rintf(min(max(x, 0), 1) * 65536.0f)
+ * and q(NaN) = 0: integer sums, so the mean confidence seg_conf_sum / (65536 seg_len) is the same whatever the split into
+ * calls.  Closing writes { start, length, label, conf_sum } to segments[b][segments_total] (int64 [batch][capacity][4]) if
+ * segments_total < capacity, and adds 1 to segments_total either way; records at and behind it are not written.  Slots are
+ * cumulative across calls: the buffer is the video's list, ascending by start.  With no segment open seg_start, seg_len and
+ * seg_conf_sum are 0.  flush != 0 also closes the segment that is open after the call's last frame (end of the video) and
+ * leaves seg_start = frames_seen, seg_len = seg_conf_sum = 0; the label stays, and a later frame with the same stable label
+ * opens a new segment at its own number.  frames == 0 with flush is allowed (pred, confidence, stable are not looked at).
+ * One launch: one workgroup (one wave) per stream walks its frames in trips of QT_TIMELINE_TRIP, lane = frame; inside a trip
+ * the run length, the stable label and the segment bounds are "last qualifying lane" scans over ballots, the confidence sums
+ * an integer prefix sum (DPP shifts), the slots a ballot rank on segments_total; the carry between trips is read from the
+ * trip's last lane into scalars.  No workgroup waits
+ * for another, no atomics, no zero fill, no workspace, no host synchronisation; the same bits on every run, for any split
+ * into calls and for a stream alone or in a batch.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument) for a null desc, non-positive batch,
+ * negative frames or zero frames (decode: without flush), num_classes outside 1 .. QT_TIMELINE_MAX_CLASSES, smooth: window
+ * outside 1 .. QT_TIMELINE_MAX_WINDOW, ld < C, ld_smoothed < C, half a history pair, histories that overlap, smoothed that
+ * overlaps probs; decode: min_run < 1, a NaN min_confidence, a negative capacity, segments == NULL with capacity > 0; null or
+ * misaligned pointers (4 bytes for f32 and int32, 8 for int64); QT_ERR_UNSUPPORTED for more than 2^22 frames in all. */
+#define QT_TIMELINE_MAX_CLASSES 64
+#define QT_TIMELINE_MAX_WINDOW 64
+#define QT_TIMELINE_TILE 64
+#define QT_TIMELINE_TRIP 64
+#define QT_TIMELINE_STATE 8
+typedef struct qt_timeline_desc {
+  int batch;                        /* streams */
+  int frames;                       /* frames per stream in this call */
+  int num_classes;                  /* C, 1 .. 64 */
+  int window;                       /* W, 1 .. 64: smooth */
+  int min_run;                      /* >= 1: decode */
+  float min_confidence;             /* not NaN: decode */
+  int capacity;                     /* records per stream in `segments`: decode */
+  int flush;                        /* != 0: close the open segment after the last frame: decode */
+} qt_timeline_desc;
+int qt_timeline_smooth(const qt_timeline_desc* desc, const float* probs, long long ld, const float* hist_in,
+                       const int* hist_count_in, float* hist_out, int* hist_count_out, float* smoothed, long long ld_smoothed,
+                       long long* pred, float* confidence, void* stream);
+int qt_timeline_decode(const qt_timeline_desc* desc, const long long* pred, const float* confidence, long long* state,
+                       long long* stable, long long* segments, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

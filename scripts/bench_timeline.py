@@ -1,0 +1,129 @@
+#!/usr/bin/env python
+"""What the pose timeline costs (developer aid, not a test; not part of bench.py).
+
+Three shapes, C = 12 classes, window 15, min_run 5, min_confidence 0.5, timed with device events, the variants alternating inside
+every repeat, microseconds per call:
+
+  offline   one video of 65,536 frames in one call (decode is ONE wave walking 1,024 trips: the shape to watch)
+  live      16 streams x 1 frame, a step of a live loop
+  batch     64 streams x 256 frames
+
+  smooth        qt_timeline_smooth alone, through ctypes into preallocated buffers (history read and written, smoothed rows too)
+  decode        qt_timeline_decode alone, the same way, behind a state.zero_() so that every call walks the same video
+  state_zero    that state.zero_() alone, to subtract
+  update        PoseTimeline.update: both launches, the allocations of its four outputs, the Python around them
+  copy          a device-to-device copy of the probabilities' bytes: every byte read once and written once
+
+and, on one host core, the numpy rule of tests/_timeline_ref.py (the array form of the smoothing, the plain loop of the
+decoding) on the same data, once.  Before timing, the result at every shape is compared with that rule, byte for byte.
+
+    python scripts/bench_timeline.py --out profiles/timeline.json
+
+Prints one JSON line.  No threshold rests on it."""
+import argparse
+import ctypes
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+PKG = "multimodal-hierarchical-cnn-for-sun-salutation-pose-classification_amd"
+SHAPES = (("offline", 1, 1 << 16), ("live", 16, 1), ("batch", 64, 256))
+C, W, MIN_RUN, MIN_CONF, CAPACITY = 12, 15, 5, 0.5, 1 << 14
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50, help="calls per timed window")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_timeline.py measures on the GPU; there is none")
+    import _timeline_ref as R
+    P = importlib.import_module(PKG)
+    M, Lm = importlib.import_module(PKG + ".timeline"), importlib.import_module(PKG + "._lib")
+    L = M.bind(Lm.lib())
+    dev = torch.device("cuda:0")
+
+    def timed(variants, iters):
+        for fn in variants.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in variants}
+        for _ in range(args.repeats):
+            for name, fn in variants.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(iters):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[name].append(e0.elapsed_time(e1) / iters * 1e3)     # microseconds per call
+        return {k: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+                for k, v in times.items()}
+
+    rec = {"device": torch.cuda.get_device_name(0), "classes": C, "window": W, "min_run": MIN_RUN, "min_confidence": MIN_CONF,
+           "iters": args.iters, "repeats": args.repeats, "shapes": {}}
+    for name, S, T in SHAPES:
+        probs_np = R.make_probs(7, S, T, C)
+        probs = torch.from_numpy(probs_np).to(dev)
+        timeline = P.PoseTimeline(C, dev, streams=S, window=W, min_run=MIN_RUN, min_confidence=MIN_CONF, capacity=CAPACITY)
+        pred, conf, stable, rows = timeline.update(probs, smoothed=True)
+        timeline.finish()
+        ref = R.smooth_vectorised(probs_np, W)                 # every shape is compared before it is timed
+        want = R.decode(ref[1], ref[2], C, MIN_RUN, MIN_CONF, np.zeros((S, R.STATE), np.int64),
+                        np.zeros((S, CAPACITY, 4), np.int64), flush=True)
+        for got, r in ((rows, ref[0]), (pred, ref[1]), (conf, ref[2]), (stable, want[0]), (timeline.state, want[1]),
+                       (timeline.records, want[2])):
+            assert R.bits(got.cpu().numpy()) == R.bits(r), f"{name}: the device result differs from the rule"
+        segments = int(timeline.state[:, -1].sum())
+
+        hist = torch.zeros(2, S, W - 1, C, device=dev)
+        counts = torch.zeros(2, S, dtype=torch.int32, device=dev)
+        state = torch.zeros(S, M.STATE, dtype=torch.int64, device=dev)
+        records = torch.zeros(S, CAPACITY, 4, dtype=torch.int64, device=dev)
+        sink = torch.empty_like(probs)
+        desc = M.TimelineDesc(S, T, C, W, MIN_RUN, MIN_CONF, CAPACITY, 0)
+
+        def smooth():
+            Lm.check(L.qt_timeline_smooth(ctypes.byref(desc), Lm.ptr(probs), C, Lm.ptr(hist[0]), Lm.ptr(counts[0]), Lm.ptr(hist[1]),
+                                          Lm.ptr(counts[1]), Lm.ptr(rows), C, Lm.ptr(pred), Lm.ptr(conf), Lm.stream_ptr()),
+                     "qt_timeline_smooth")
+
+        def decode():
+            state.zero_()
+            Lm.check(L.qt_timeline_decode(ctypes.byref(desc), Lm.ptr(pred), Lm.ptr(conf), Lm.ptr(state), Lm.ptr(stable),
+                                          Lm.ptr(records), Lm.stream_ptr()), "qt_timeline_decode")
+
+        us = timed({"smooth": smooth, "decode": decode, "state_zero": lambda: state.zero_(),
+                    "update": lambda: timeline.update(probs), "copy": lambda: sink.copy_(probs)}, args.iters)
+        t0 = time.perf_counter()
+        ref = R.smooth_vectorised(probs_np, W)
+        t1 = time.perf_counter()
+        R.decode(ref[1], ref[2], C, MIN_RUN, MIN_CONF, np.zeros((S, R.STATE), np.int64), np.zeros((S, CAPACITY, 4), np.int64))
+        t2 = time.perf_counter()
+        rec["shapes"][name] = {"streams": S, "frames": T, "probs_bytes": probs.numel() * 4, "segments_closed": segments,
+                               "us_per_call": us,
+                               "host_us_once": {"smooth_array_form": round((t1 - t0) * 1e6), "decode_loop": round((t2 - t1) * 1e6)}}
+        del timeline, probs, sink
+    line = json.dumps(rec)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
