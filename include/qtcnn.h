@@ -877,6 +877,71 @@ int qt_timeline_smooth(const qt_timeline_desc* desc, const float* probs, long lo
                        long long* pred, float* confidence, void* stream);
 int qt_timeline_decode(const qt_timeline_desc* desc, const long long* pred, const float* confidence, long long* state,
                        long long* stable, long long* segments, void* stream);
+/* Pose-order decoding: the best path of a hidden-Markov chain whose STATES are the steps of the pose sequence (the twelve
+ * steps of a Sun Salutation, in their cyclic order), each state emitting one of the C classes, over the probabilities of the
+ * video loop (qt_metrics_update's probs, or qt_timeline_smooth's smoothed rows).  The debounced argmax of qt_timeline_decode
+ * treats the classes as unrelated labels; this decode knows their order, tells the two occurrences of a pose inside one round
+ * apart, and its path is what rounds are counted on.  The reference has no such step.  Every number is an integer from the
+ * emission score on, so every output is the same bits on every run and for any split of a stream into calls.
+ *
+ * probs: f32 [batch][frames][C], row stride ld >= C, a stream's rows `frames * ld` apart; state_class: int32 [S], the class
+ * a state emits; trans: int32 [S][S], trans[i][j] the score of going from state i to state j between two frames, in
+ * [-65536, 0]; init: int32 [S] in the same range, the scores before a stream's first frame, or NULL for zeros.  state_class,
+ * trans and init are in device memory: an entry of trans or init outside the range is clamped into it as it is read, and a
+ * state whose class is outside [0, C) scores the floor -8192 at every frame and indexes nothing.  carry: int64
+ * [batch][S + 2] = { frames_seen, score_offset, delta[S] }, in device memory for the whole video, updated in place; the caller
+ * zeroes it once.
+ * Emission score q(p) of an f32 p with bit pattern b, in units of 1/256 bit:
+ *   p is NaN or p < 2^-32 (negatives, zeros, denormals): q = -8192
+ *   p >= 1 (+inf too):                                    q = 0
+ *   otherwise:  q = 256 ((b >> 23) - 127) + LOG2_TABLE[(b >> 15) & 255],  LOG2_TABLE[i] = rint(256 log2(1 + (2 i + 1) / 512))
+ * (1, 2, 4, 5 ... 254, 255, 256; no entry is closer than 0.0015 to a half; the table is written out in csrc/pose_order.hip).
+ * q stays within 1.25 units of 256 log2 p, and no logf enters the rule.  e[f][s] = q(probs[f][state_class[s]]).
+ * Forward, per stream, frame by frame; d is the previous frame's scores: init for the stream's first frame (frames_seen ==
+ * 0), carry.delta otherwise:
+ *   psi[f][j]   = the LOWEST i that attains max_i (d[i] + trans[i][j])
+ *   delta[f][j] = that maximum + e[f][j]
+ *   filtered[f] = the lowest j that attains max_j delta[f][j]        (causal: usable frame by frame in a live loop)
+ * Backtrace, per call:  path[frames - 1] = filtered[frames - 1],  path[f - 1] = psi[f][path[f]].
+ * Carry out:  frames_seen += frames;  m = max_j delta[last][j];  carry.delta = delta[last] - m;  score_offset += m.
+ *   path        int64 [batch][frames], required
+ *   filtered    int64 [batch][frames], or NULL
+ *   emissions   int32 [batch][frames][S], or NULL
+ * Split contract.  Subtracting a constant changes no argmax, so for a stream handed over in any split into consecutive calls
+ * filtered, emissions and the final carry are the bits of one call, and the LAST call's path is the one-call path on its
+ * frames; the paths of earlier calls are the best paths given what had been seen by then and are not revised.
+ * Routes.  frames <= QT_POSE_ORDER_TILE: one launch, one wave per stream, lane = state, the tile's emissions, the table and
+ * psi in LDS, no workspace (the live loop's route).  Longer calls: with M_f[i][j] = trans[i][j] + e[f][j] a frame is
+ * delta_f = delta_(f-1) (x) M_f in the (max, +) semiring, and integer (max, +) products are exactly associative: (a) a
+ * workgroup per tile forms the tile's product, (b) the start vector is carried through the products in order, on two levels
+ * above 32 tiles (the tile products of a group of 32 multiplied into one, the stream's start carried through the group
+ * products, then every group's start through its own tile products), (c) every tile replays its frames from its start
+ * vector with the vector step, where psi and filtered get the rule's lowest-index ties, and composes its psi into one
+ * back-map, (d) the tiles' end states follow from the last tile's by the back-maps, and every tile backtraces its own
+ * frames.  Five launches (seven above 32 tiles), intermediate scores int32 inside a tile and int64 across tiles; only the
+ * outputs are the contract.  qt_pose_order_workspace_bytes: what the tiled route needs (8-byte
+ * aligned; every slot that is read is written in the same call, nothing is zero-filled), 0 on the short route and for a
+ * descriptor that would be refused.  No workgroup waits for another inside a launch, no atomics, no host synchronisation;
+ * inputs are never written; a stream alone gives the bits of the same stream in a batch.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument) for a null desc, non-positive batch or
+ * frames, num_states or num_classes outside 1 .. 64, ld < C, a null probs, state_class, trans, carry or path, misaligned
+ * pointers (4 bytes for f32 and int32, 8 for int64 and the workspace), a workspace smaller than the query's size, an output
+ * (carry, path, filtered, emissions, workspace) that overlaps an input or another output; QT_ERR_UNSUPPORTED for more than
+ * 2^20 frames in all (batch * frames). */
+#define QT_POSE_ORDER_TILE 64
+#define QT_POSE_ORDER_MAX_STATES 64
+#define QT_POSE_ORDER_MAX_CLASSES 64
+typedef struct qt_pose_order_desc {
+  int batch;                        /* streams */
+  int frames;                       /* frames per stream in this call */
+  int num_classes;                  /* C, 1 .. 64 */
+  int num_states;                   /* S, 1 .. 64 */
+} qt_pose_order_desc;
+long long qt_pose_order_workspace_bytes(const qt_pose_order_desc* desc);
+int qt_pose_order_decode(const qt_pose_order_desc* desc, const float* probs, long long ld, const int* state_class,
+                         const int* trans, const int* init, long long* carry, long long* path, long long* filtered,
+                         int* emissions, void* workspace, long long workspace_bytes, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

@@ -1,0 +1,243 @@
+"""Pose-order decoding on the device: the best path through the steps of the pose sequence, and the rounds it makes
+(csrc/pose_order.hip).  PoseTimeline smooths and debounces, but to it the twelve steps of a Sun Salutation are twelve unrelated
+labels: its label may go from step 3 to step 7 and back, and it cannot tell the first Hasta Uttanasana of a round from the
+second.  Here the STATES of a hidden-Markov chain are the steps, each emitting one class, and a transition table says which
+step may follow which.  The reference has no such step.  In the video loop it sits between the timeline and the annotator:
+
+    state_class, trans = cyclic_prior(step_classes, stay=prob_score(0.9), advance=prob_score(0.1))
+    decoder = PoseOrderDecoder(state_class, trans, device, class_names=class_names)
+    for frames, landmarks, detected in video:                       # chunks of any length
+        probs, _, _ = predict(model(pre(frames), pose(landmarks, detected)))
+        pred, confidence, stable, rows = timeline.update(probs, smoothed=True)
+        path, path_class = decoder.decode(rows)                     # nothing read back
+        rounds += decoder.cycles(path)                              # int64 [streams], on the device
+        out = annotator.draw(frames, landmarks, detected, path_class, confidence)
+
+Scores are integers: an emission is log2 p in units of 1/256 bit, read off the float's bit pattern (`prob_score` is the same
+rule on the host), transitions are int32 in [-65536, 0].  So every output is the same bits on every run, and a stream handed
+over in any split into calls gives the filtered states, emissions and carry of one call; the last call's path is the one-call
+path on its frames, earlier calls' paths are the best given what had been seen by then.  include/qtcnn.h states the rule.
+Calls of up to TILE = 64 frames are one launch of one wave per stream; longer calls are cut into tiles whose (max, +) products
+are formed in parallel (five launches, seven above 32 tiles; a workspace that grows on demand).  Limits: S <= 64 states,
+C <= 64 classes, 2^20 frames per call.
+
+Not built: forward-backward posteriors, learning `trans` from labelled videos, fixed-lag revision of earlier calls' paths, true
+minus-infinity (forbidden) transitions, S > 64, bf16 probabilities.  There is no torch fallback: CPU tensors and other dtypes
+raise QtError.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import QtError
+
+TILE = 64                   # QT_POSE_ORDER_TILE
+GROUP = 32                  # PO_GROUP: tiles per group of the two-level scan
+MAX_STATES = 64             # QT_POSE_ORDER_MAX_STATES
+MAX_CLASSES = 64            # QT_POSE_ORDER_MAX_CLASSES
+MAX_FRAMES = 1 << 20
+SCORE_FLOOR = -8192         # q of NaN and of everything below 2^-32
+TRANS_FLOOR = -65536
+# rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the table of csrc/pose_order.hip
+LOG2_TABLE = (
+      1,   2,   4,   5,   6,   8,   9,  11,  12,  13,  15,  16,  18,  19,  20,  22,
+     23,  24,  26,  27,  28,  30,  31,  32,  34,  35,  36,  38,  39,  40,  42,  43,
+     44,  45,  47,  48,  49,  50,  52,  53,  54,  55,  57,  58,  59,  60,  62,  63,
+     64,  65,  66,  68,  69,  70,  71,  72,  74,  75,  76,  77,  78,  80,  81,  82,
+     83,  84,  85,  86,  88,  89,  90,  91,  92,  93,  94,  95,  97,  98,  99, 100,
+    101, 102, 103, 104, 105, 106, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117,
+    118, 119, 120, 121, 122, 123, 124, 125, 126, 127, 128, 129, 131, 132, 133, 134,
+    135, 136, 137, 138, 139, 140, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149,
+    150, 151, 152, 153, 154, 155, 156, 157, 158, 159, 160, 161, 162, 163, 163, 164,
+    165, 166, 167, 168, 169, 170, 171, 172, 173, 173, 174, 175, 176, 177, 178, 179,
+    180, 181, 182, 182, 183, 184, 185, 186, 187, 188, 189, 189, 190, 191, 192, 193,
+    194, 195, 195, 196, 197, 198, 199, 200, 200, 201, 202, 203, 204, 205, 205, 206,
+    207, 208, 209, 210, 210, 211, 212, 213, 214, 214, 215, 216, 217, 218, 218, 219,
+    220, 221, 222, 222, 223, 224, 225, 226, 226, 227, 228, 229, 229, 230, 231, 232,
+    233, 233, 234, 235, 236, 236, 237, 238, 239, 239, 240, 241, 242, 242, 243, 244,
+    245, 245, 246, 247, 248, 248, 249, 250, 251, 251, 252, 253, 253, 254, 255, 256)
+
+
+class PoseOrderDesc(ctypes.Structure):   # qt_pose_order_desc
+    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int)]
+
+
+def bind(L):
+    """argtypes of the two entry points (idempotent)"""
+    if getattr(L, "_pose_order_bound", False):
+        return L
+    L.qt_pose_order_workspace_bytes.argtypes = [ctypes.POINTER(PoseOrderDesc)]
+    L.qt_pose_order_workspace_bytes.restype = ctypes.c_longlong
+    L.qt_pose_order_decode.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 8 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_order_decode.restype = ctypes.c_int
+    L._pose_order_bound = True
+    return L
+
+
+def scan_trip_tiles(num_states):
+    """products the tiled route's scan stages at a time (16 KB of LDS, at most 16): a call of more than
+    (scan_trip_tiles + 1) * TILE frames makes it stage more than once"""
+    return max(1, min(16, 4096 // (num_states * num_states)))
+
+
+def prob_score(p):
+    """The emission rule q on the host: f32 values (any shape) -> int64 scores, log2 p in units of 1/256 bit from the bit
+    pattern; NaN and everything below 2^-32 give -8192, 1 and above 0.  For a `stay` or `advance` taken from a probability."""
+    a = np.asarray(p, dtype=np.float32)
+    b = np.ascontiguousarray(a).view(np.uint32).astype(np.int64)
+    table = np.array(LOG2_TABLE, np.int64)
+    out = 256 * ((b >> 23) - 127) + table[(b >> 15) & 255]
+    out = np.where(b >= (127 << 23), 0, out)
+    out = np.where((b >> 31 != 0) | (b > 0x7F800000) | (b < ((127 - 32) << 23)), SCORE_FLOOR, out)
+    out = out.astype(np.int64).reshape(a.shape)
+    return int(out) if out.ndim == 0 else out
+
+
+def _score(name, v, optional=False):
+    if v is None and optional:
+        return None
+    if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)) or not TRANS_FLOOR <= int(v) <= 0:
+        raise ValueError(f"cyclic_prior: {name} must be an integer in {TRANS_FLOOR} .. 0 (got {v!r})")
+    return int(v)
+
+
+def cyclic_prior(step_classes, stay, advance, skip=None, other=TRANS_FLOOR, wrap=True):
+    """(state_class int32 [S], trans int32 [S, S]) of a left-to-right cycle over the steps, on the host, integers in and out:
+    trans[s][s] = stay, trans[s][s+1 mod S] = advance, trans[s][s+2 mod S] = skip where given, `other` everywhere else.  Without
+    `wrap` the last steps do not lead back to the first.  Where S is so small that two of them name one entry, stay wins over
+    advance and advance over skip."""
+    classes = [int(c) for c in step_classes]
+    S = len(classes)
+    if not 1 <= S <= MAX_STATES:
+        raise ValueError(f"cyclic_prior: {S} steps; 1 .. {MAX_STATES} are handled")
+    if any(c < 0 for c in classes):
+        raise ValueError("cyclic_prior: a step's class is negative")
+    stay, advance, other = _score("stay", stay), _score("advance", advance), _score("other", other)
+    skip = _score("skip", skip, optional=True)
+    trans = np.full((S, S), other, np.int32)
+    for s in range(S):
+        for step, value in ((2, skip), (1, advance), (0, stay)):
+            if value is None or (s + step >= S and not wrap):
+                continue
+            trans[s, (s + step) % S] = value
+    return np.array(classes, np.int32), trans
+
+
+class PoseOrderDecoder:
+    """The decoder of `streams` videos (or camera feeds): the tables, the carry int64 [streams, S + 2] = (frames_seen,
+    score_offset, delta[S]), each stream's last path state, and a workspace that grows on demand, all in device memory.
+    `decode` and `cycles` launch kernels and read nothing back.  See the module text."""
+
+    def __init__(self, state_class, trans, device, streams=1, init=None, class_names=None):
+        sc = np.asarray(state_class)
+        if sc.ndim != 1 or not 1 <= sc.shape[0] <= MAX_STATES or sc.dtype.kind not in "iu":
+            raise ValueError(f"PoseOrderDecoder: state_class must be 1 .. {MAX_STATES} integers (got shape {sc.shape}, {sc.dtype})")
+        S = int(sc.shape[0])
+        if (sc < 0).any() or (sc >= MAX_CLASSES).any():
+            raise ValueError(f"PoseOrderDecoder: state_class holds a class outside 0 .. {MAX_CLASSES - 1}")
+        tr = np.asarray(trans)
+        if tr.shape != (S, S) or tr.dtype.kind not in "iu":
+            raise ValueError(f"PoseOrderDecoder: trans must be [{S}, {S}] integers (got shape {tr.shape}, {tr.dtype})")
+        if (tr < TRANS_FLOOR).any() or (tr > 0).any():
+            raise ValueError(f"PoseOrderDecoder: trans holds a score outside {TRANS_FLOOR} .. 0")
+        if init is not None:
+            init = np.asarray(init)
+            if init.shape != (S,) or init.dtype.kind not in "iu" or (init < TRANS_FLOOR).any() or (init > 0).any():
+                raise ValueError(f"PoseOrderDecoder: init must be [{S}] integers in {TRANS_FLOOR} .. 0")
+        if isinstance(streams, bool) or not isinstance(streams, int) or not 1 <= streams <= MAX_FRAMES:
+            raise ValueError(f"PoseOrderDecoder: streams must be an integer in 1 .. {MAX_FRAMES} (got {streams!r})")
+        if class_names is not None:
+            class_names = [str(c) for c in class_names]
+            if len(class_names) <= int(sc.max()):
+                raise ValueError(f"PoseOrderDecoder: {len(class_names)} class names, but a state emits class {int(sc.max())}")
+        self.class_names = class_names
+        self.num_states, self.streams = S, streams
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise QtError("PoseOrderDecoder lives on an AMD GPU (device must be cuda:N); no CPU fallback")
+        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
+        self._state_class64 = self.state_class.to(torch.int64)
+        self.trans = torch.from_numpy(np.ascontiguousarray(tr, np.int32)).to(device)
+        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
+        self.carry = torch.zeros(streams, S + 2, dtype=torch.int64, device=device)
+        self._last = torch.full((streams,), -1, dtype=torch.int64, device=device)    # the last decode's last state; -1: none
+        self._before = self._last                                                    # the same of the decode before it
+        self._workspace = None
+        self.device = self.carry.device
+
+    def reset(self):
+        """every stream starts anew (no host sync)"""
+        self.carry.zero_()
+        self._last = torch.full_like(self._last, -1)
+        self._before = self._last
+        return self
+
+    def decode(self, probs, filtered=False, emissions=False):
+        """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on the decoder's device: predict's
+        probabilities or the timeline's smoothed rows.  Returns (path int64, path_class int64), each [streams, frames] (or
+        [frames]): the best state per frame and the class it emits, which is what FrameAnnotator.draw takes as `pred`;
+        with filtered=True the causal states int64 as a third, with emissions=True the scores int32 [..., S] as the last."""
+        what = "PoseOrderDecoder.decode"
+        if not isinstance(probs, torch.Tensor):
+            raise QtError(f"{what}: probs must be a tensor")
+        if probs.device.type != "cuda" or probs.device != self.device:
+            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
+        if probs.dtype != torch.float32:
+            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+        B, S = self.streams, self.num_states
+        flat = probs.dim() == 2
+        if flat and B == 1:
+            probs = probs.unsqueeze(0)
+        if probs.dim() != 3 or probs.shape[0] != B or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
+            raise QtError(f"{what}: probs must be [{B}, frames, C]{' or [frames, C]' if B == 1 else ''} with frames >= 1 and "
+                          f"C <= {MAX_CLASSES} (got {list(probs.shape)})")
+        T, C = probs.shape[1], probs.shape[2]
+        if B * T > MAX_FRAMES:
+            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+        probs = probs.detach()
+        if probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1)):
+            probs = probs.contiguous()
+        lead = (T,) if flat else (B, T)
+        dev = self.device
+        path = torch.empty(lead, dtype=torch.int64, device=dev)
+        filt = torch.empty(lead, dtype=torch.int64, device=dev) if filtered else None
+        emis = torch.empty(lead + (S,), dtype=torch.int32, device=dev) if emissions else None
+        desc = PoseOrderDesc(B, T, C, S)
+        L = bind(_lib.lib())
+        need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(desc)))
+        if need and (self._workspace is None or self._workspace.numel() < need):
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.qt_pose_order_decode(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
+                                              _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.carry), _lib.ptr(path),
+                                              _lib.ptr(filt), _lib.ptr(emis), _lib.ptr(self._workspace) if need else None,
+                                              self._workspace.numel() if need else 0, _lib.stream_ptr()), "qt_pose_order_decode")
+        self._before, self._last = self._last, path.view(B, T)[:, -1].clone()
+        out = (path, self._state_class64[path])
+        if filtered:
+            out += (filt,)
+        if emissions:
+            out += (emis,)
+        return out
+
+    def cycles(self, path, wrap_from=None, wrap_to=0):
+        """int64 [streams], on the device and without a host sync: how often `path` (a decode's, [streams, frames] or [frames])
+        goes from state wrap_from (default S - 1) to state wrap_to between adjacent frames.  `decode` keeps the last state of
+        the call before it, so with the latest decode's path a wrap that falls on the call boundary is counted: call it once
+        per decode.  Plain torch."""
+        S, B = self.num_states, self.streams
+        wrap_from = S - 1 if wrap_from is None else wrap_from
+        for name, v in (("wrap_from", wrap_from), ("wrap_to", wrap_to)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < S:
+                raise ValueError(f"PoseOrderDecoder.cycles: {name} must be a state 0 .. {S - 1} (got {v!r})")
+        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
+            raise QtError(f"PoseOrderDecoder.cycles: path must be an int64 tensor on {self.device}")
+        if path.dim() == 1 and B == 1:
+            path = path.unsqueeze(0)
+        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < 1:
+            raise QtError(f"PoseOrderDecoder.cycles: path must be [{B}, frames] (got {list(path.shape)})")
+        before = torch.cat([self._before[:, None], path[:, :-1]], dim=1)
+        return ((before == wrap_from) & (path == wrap_to)).sum(dim=1)

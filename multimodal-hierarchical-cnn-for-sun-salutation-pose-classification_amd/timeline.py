@@ -21,8 +21,9 @@ unknown frames, which FrameAnnotator draws as no caption.  A stream handed over 
 as one call; the W - 1 previous rows and eight integers per stream are carried in device memory.  include/qtcnn.h states
 both rules.  Limits: C <= 64, window <= 64, 2^22 frames per call.
 
-Not built: EMA or majority-vote smoothing, a centred (look-ahead) window, Viterbi decoding over a pose-order prior, counting
-Sun Salutation cycles, C > 64.  There is no torch fallback: CPU tensors and other dtypes raise QtError.
+Not built: EMA or majority-vote smoothing, a centred (look-ahead) window, C > 64.  Decoding over a pose-order prior and counting
+Sun Salutation rounds are pose_order.py's (PoseOrderDecoder), which takes this module's smoothed rows.  There is no torch
+fallback: CPU tensors and other dtypes raise QtError.
 """
 import ctypes
 

@@ -1,0 +1,150 @@
+#!/usr/bin/env python
+"""What the pose-order decode costs (developer aid, not a test; not part of bench.py).
+
+Three shapes, S = C = 12 (a cycle over the twelve steps), timed with device events, the variants alternating inside every repeat,
+microseconds per call:
+
+  live      16 streams x 1 frame, a step of a live loop (short route)
+  batch     64 streams x 256 frames (tiled route, four tiles per stream)
+  offline   one video of 65,536 frames in one call (tiled route, 1,024 tiles: the shape the tiling is for)
+
+  decode        qt_pose_order_decode alone, through ctypes into preallocated buffers (path, filtered, emissions), behind a
+                carry.zero_() so that every call decodes the same video
+  carry_zero    that carry.zero_() alone, to subtract
+  decoder       PoseOrderDecoder.decode: the launches, the allocations of its outputs, the gather of path_class, the Python
+  copy          a device-to-device copy of the probabilities' bytes: every byte read once and written once
+
+and at the offline and batch shapes the forms behind the QTCNN_POSE_ORDER switch of csrc/pose_order.hip (same bits, compared):
+
+  one_wave      1: the short route's algorithm as ONE wave per stream over all tiles, psi through the workspace
+  walk_in_tiles 2: step (d) as one launch in which every tile walks the back-maps from the stream's end to itself
+  psi_replayed  3: the backtrace launch recomputes psi by a second replay instead of reading it from the workspace
+
+and, on one host core, the numpy loop of tests/_pose_order_ref.py on the same data, once.  Before timing, the result of every
+form at every shape is compared with that loop, byte for byte.
+
+    python scripts/bench_pose_order.py --out profiles/pose_order.json
+
+Prints one JSON line.  No threshold rests on it."""
+import argparse
+import ctypes
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+PKG = "multimodal-hierarchical-cnn-for-sun-salutation-pose-classification_amd"
+SHAPES = (("live", 16, 1), ("batch", 64, 256), ("offline", 1, 1 << 16))
+S = C = 12
+SWITCH = "QTCNN_POSE_ORDER"
+FORMS = (("one_wave", "1"), ("walk_in_tiles", "2"), ("psi_replayed", "3"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50, help="calls per timed window (one_wave: a tenth of it)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--shapes", default="live,batch,offline")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_pose_order.py measures on the GPU; there is none")
+    import _pose_order_ref as R
+    P = importlib.import_module(PKG)
+    M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
+    L = M.bind(Lm.lib())
+    dev = torch.device("cuda:0")
+    os.environ.pop(SWITCH, None)
+
+    def timed(variants):
+        for fn, _ in variants.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in variants}
+        for _ in range(args.repeats):
+            for name, (fn, iters) in variants.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(iters):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[name].append(e0.elapsed_time(e1) / iters * 1e3)     # microseconds per call
+        return {k: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+                for k, v in times.items()}
+
+    sc, tr = M.cyclic_prior(range(S), stay=M.prob_score(0.9), advance=M.prob_score(0.1), skip=M.prob_score(0.01))
+    rec = {"device": torch.cuda.get_device_name(0), "states": S, "classes": C, "iters": args.iters, "repeats": args.repeats,
+           "shapes": {}}
+    for name, B, T in SHAPES:
+        if name not in args.shapes.split(","):
+            continue
+        probs_np = R.make_probs(7, B, T, C)
+        probs = torch.from_numpy(probs_np).to(dev)
+        t0 = time.perf_counter()
+        want = R.decode(probs_np, sc, tr)
+        host_us = round((time.perf_counter() - t0) * 1e6)
+
+        d_sc, d_tr = torch.from_numpy(sc).to(dev), torch.from_numpy(tr).to(dev)
+        carry = torch.zeros(B, S + 2, dtype=torch.int64, device=dev)
+        path = torch.empty(B, T, dtype=torch.int64, device=dev)
+        filt = torch.empty(B, T, dtype=torch.int64, device=dev)
+        emis = torch.empty(B, T, S, dtype=torch.int32, device=dev)
+        sink = torch.empty_like(probs)
+        desc = M.PoseOrderDesc(B, T, C, S)
+        need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(desc)))
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+
+        def decode(form=None):
+            if form is not None:
+                os.environ[SWITCH] = form
+            carry.zero_()
+            rc = L.qt_pose_order_decode(ctypes.byref(desc), Lm.ptr(probs), C, Lm.ptr(d_sc), Lm.ptr(d_tr), None, Lm.ptr(carry),
+                                        Lm.ptr(path), Lm.ptr(filt), Lm.ptr(emis), Lm.ptr(ws) if need else None, need,
+                                        Lm.stream_ptr())
+            if form is not None:
+                del os.environ[SWITCH]
+            Lm.check(rc, "qt_pose_order_decode")
+
+        forms = FORMS if T > M.TILE else ()
+        for label, form in ((("decode", None),) + forms):              # every form is compared before it is timed
+            path.fill_(-1), filt.fill_(-1), emis.fill_(1)
+            decode(form)
+            for got, r in ((path, want[0]), (filt, want[1]), (emis, want[2]), (carry, want[3])):
+                assert R.bits(got.cpu().numpy()) == R.bits(r), f"{name}/{label}: the device result differs from the rule"
+        decoder = P.PoseOrderDecoder(sc, tr, dev, streams=B)
+
+        def through_python():
+            decoder.carry.zero_()
+            decoder.decode(probs, filtered=True, emissions=True)
+
+        variants = {"decode": (decode, args.iters), "carry_zero": (lambda: carry.zero_(), args.iters),
+                    "decoder": (through_python, args.iters), "copy": (lambda: sink.copy_(probs), args.iters)}
+        for label, form in forms:
+            variants[label] = ((lambda form=form: decode(form)), max(args.iters // 10, 2) if label == "one_wave" else args.iters)
+        us = timed(variants)
+        rec["shapes"][name] = {"streams": B, "frames": T, "probs_bytes": probs.numel() * 4, "workspace_bytes": need,
+                               "rounds": int(R.cycles(want[0], S - 1, 0)[0].sum()), "us_per_call": us, "host_us_once": host_us}
+        if "one_wave" in us:
+            rec["shapes"][name]["one_wave_over_tiled"] = round(us["one_wave"]["median"] / us["decode"]["median"], 1)
+        del decoder, probs, sink, ws
+    line = json.dumps(rec)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
