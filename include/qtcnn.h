@@ -723,6 +723,80 @@ int qt_metrics_update(const qt_metrics_desc* desc, const float* logits, long lon
                       const long long* labels, long long rows, int C, unsigned long long* state, float* probs,
                       long long ld_probs, float* confidence, long long* pred_out, void* stream);
 int qt_metrics_finalize(const unsigned long long* state, int C, double* report, void* stream);
+/* Score-based evaluation: what the confusion matrix cannot give because it needs the scores, not counts: top-k accuracy,
+ * one-vs-rest ROC / AUC and average precision per class, and the calibration of the confidence (the value the caption shows
+ * and PoseTimeline(min_confidence=) thresholds), without copying [rows][C] probabilities to the host every batch.  A second
+ * meter in the image of qt_metrics_*: additive integer state in device memory, one launch per batch, one finalize, integers
+ * wherever the result must not depend on order, so the same bits on every run.
+ * Inputs.  scores f32 [rows][C], row stride ld >= C elements (padding columns are never read into a result), labels int64
+ * [rows]; 1 <= C <= QT_SCORES_MAX_CLASSES, 1 <= rows <= 2^22 per call.  desc->kind:
+ *   QT_SCORES_LOGITS   p is qt_metrics_update's softmax (m = z[argmax], e_k = expf(z_k - m), s = sum_k e_k, p_k = e_k / s,
+ *                      same lane mapping and summation order): the bits qt_metrics_update writes to probs
+ *   QT_SCORES_PROBS    p is the row as given (e.g. qt_timeline_smooth's smoothed rows)
+ * Row classes, the first that applies:  ignored (label == desc->ignore_index), invalid (label outside [0, C)), nan (some
+ * p_k is NaN, or, with QT_SCORES_PROBS, outside [0, 1]), counted.  Only counted rows reach the tables.
+ * Score key.  K = 1 << desc->bits, QT_SCORES_MIN_BITS <= bits <= QT_SCORES_MAX_BITS;  q(p) = min(K - 1, (int)(p * (float)K)):
+ * a multiplication by a power of two and a truncation, both exact in f32.
+ * State, u64, zeroed once by the caller and only ever added to; qt_scores_state_bytes(C, bits, M) = 8 (2 C K + C + 3 M + 5):
+ *   hist[C][2][K]   hist[(k * 2 + side) * K + q(p_k)] += 1 for every class k of a counted row; side = 1 when the label is k
+ *   rank[C]         rank[r] += 1 with r = #{k : s_k > s_y, or s_k == s_y and k < y}, y the label, s the scores AS GIVEN (z for
+ *                   logits, p for probs).  rank[0] is torch.max's hit count; top_k = sum_{r < k} rank[r] / counted
+ *   cal[M][3]       1 <= M = desc->cal_bins <= QT_SCORES_MAX_CAL_BINS.  pred = argmax of p in the loss head's total order (the
+ *                   larger value, then the lower index), conf = p[pred], bin = min(M - 1, (int)(conf * (float)M)) with the
+ *                   product rounded to f32;  cal[bin] += { 1, pred == y, rint(clamp(conf, 0, 1) * 65536) }  (the integer
+ *                   confidence of qt_timeline_decode, for the same reason: a sum that does not depend on order)
+ *   counters[5]     rows counted, ignored, invalid, nan; update calls
+ * Every add is an integer atomic: the states of several calls, streams, devices or ranks add up to the state of their
+ * union, and a batch split into calls at any row gives the bits of one call (but for the update counter).
+ * qt_scores_update, one launch, no workspace, no zero fill, no host synchronisation.  desc->route: QT_SCORES_ROUTE_DIRECT (one
+ * 64-bit global atomic per cell of a counted row), QT_SCORES_ROUTE_PRIVATE (a workgroup owns QT_SCORES_SLICE_ROWS rows and one
+ * class, counts in a u32 LDS histogram and adds its non-zero cells), QT_SCORES_ROUTE_AUTO (private from
+ * QT_SCORES_AUTO_PRIVATE_ROWS rows on: a measurement, EXPERIMENTS.md "Score metrics").  The routes give the same state.
+ * qt_scores_finalize: state -> report, 4 C + 3 M + 12 doubles (qt_scores_report_bytes(C, M)); counts are added as integers,
+ * everything else is double arithmetic in a fixed order.  Per class k with pos_b = hist[k][1][b], neg_b = hist[k][0][b],
+ * P = sum_b pos_b, N = sum_b neg_b, negbelow_b = sum_{b' < b} neg_b', tp_b = sum_{b' >= b} pos_b', fp_b likewise:
+ *   [0, C)     auc_k = A2 / (2 P N), A2 = sum_b pos_b (2 negbelow_b + neg_b) in 64-bit integers (exact while 2 P N < 2^64),
+ *              one double division; NaN when P == 0 or N == 0.  The Mann-Whitney statistic of the quantised scores with
+ *              ties at half credit: sklearn.metrics.roc_auc_score(y == k, q / K)
+ *   [C, 2C)    ap_k = sum over the bins with pos_b > 0 of (pos_b / P) (tp_b / (tp_b + fp_b)): a thread sums its K / 256
+ *              consecutive bins from the top down (K < 256: one bin), the 256 partial sums are added by the halving tree
+ *              red[t] += red[t + s], s = 128 .. 1; NaN when P == 0.  sklearn.metrics.average_precision_score(y == k, q / K)
+ *   [2C, 3C)   support_k = P
+ *   [3C, 4C)   top_k for k = 1 .. C (index k - 1): integer partial sums of rank over counted; NaN when nothing was counted
+ *   4C + [0, M) rows of the bin, + [M, 2M) accuracy = hits / rows, + [2M, 3M) mean confidence = sum / (65536 rows); an empty
+ *              bin gives 0
+ *   then 12 scalars: macro AUC, support-weighted AUC (over the classes whose AUC is defined, ascending k), macro AP,
+ *              support-weighted AP (likewise), ece = sum_b (n_b / n) |acc_b - conf_b| over the occupied bins in ascending
+ *              order, mce = the largest such gap (both NaN when n == 0), samples, ignored, invalid, nan rows, classes scored
+ *              (those with a defined AUC), update calls
+ * curves (or NULL): int64 [C][2][K], curves[k][0][b] = tp_b, curves[k][1][b] = fp_b; dividing by P and N gives the ROC and
+ * precision / recall points, no float curve is stored.
+ * Both size queries return 0 for an argument outside its range.  QT_ERR_INVALID_ARG (before any launch; qt_last_error names
+ * the entry point) for a null desc, kind / bits / cal_bins / route outside their ranges, null scores / labels / state /
+ * report, rows <= 0, C <= 0, ld < C, misaligned pointers (4 bytes for f32, 8 for the 64-bit arrays); QT_ERR_UNSUPPORTED for
+ * C > QT_SCORES_MAX_CLASSES, rows > 2^22 and a dtype other than QT_F32. */
+#define QT_SCORES_MAX_CLASSES 64
+#define QT_SCORES_MAX_CAL_BINS 64
+#define QT_SCORES_MIN_BITS 4
+#define QT_SCORES_MAX_BITS 14
+#define QT_SCORES_SLICE_ROWS 1024
+#define QT_SCORES_AUTO_PRIVATE_ROWS 64
+enum { QT_SCORES_LOGITS = 0, QT_SCORES_PROBS = 1 };
+enum { QT_SCORES_ROUTE_AUTO = 0, QT_SCORES_ROUTE_DIRECT = 1, QT_SCORES_ROUTE_PRIVATE = 2 };
+typedef struct qt_scores_desc {
+  int dtype;                  /* of the scores: QT_F32 */
+  int kind;                   /* QT_SCORES_LOGITS | QT_SCORES_PROBS */
+  int bits;                   /* K = 1 << bits score bins */
+  int cal_bins;               /* M calibration bins */
+  int route;                  /* QT_SCORES_ROUTE_* */
+  long long ignore_index;     /* torch's default: -100 */
+} qt_scores_desc;
+size_t qt_scores_state_bytes(int C, int bits, int cal_bins);
+size_t qt_scores_report_bytes(int C, int cal_bins);
+int qt_scores_update(const qt_scores_desc* desc, const float* scores, long long ld, const long long* labels, long long rows,
+                     int C, unsigned long long* state, void* stream);
+int qt_scores_finalize(const unsigned long long* state, int C, int bits, int cal_bins, double* report, long long* curves,
+                       void* stream);
 /* Annotated frames: the last step of the reference's video loop (experiment/test_on_video_cnn.py:280-295: draw_landmarks,
  * putText, then the writer) and the drawing step of sqn process/processing_image_sequence.py:250-318 (draw_enhanced_skeleton),
  * resnet/grad_cam_analysis.py:437 and grad_cam/5_grad_cam_visualizer.py, for a whole batch of uint8 frames in one launch, from

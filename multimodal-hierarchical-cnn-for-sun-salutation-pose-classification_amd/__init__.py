@@ -18,13 +18,14 @@ from .pose import FEATURE_NAMES, PoseFeatures, load_class_stats  # noqa: F401
 from .pose_sequence import NUM_SEQUENCE_FEATURES, SEQUENCE_FEATURE_NAMES, SequencePoseFeatures  # noqa: F401
 from .sequence_windows import SequenceWindows, WindowPlan, fit_class_stats  # noqa: F401
 from .metrics import EvalMeter, predict  # noqa: F401
+from .scores import ScoreMeter  # noqa: F401
 from .annotate import MAJOR_SEGMENTS, POSE_CONNECTIONS, FrameAnnotator, caption_atlas  # noqa: F401
 from .timeline import PoseTimeline  # noqa: F401
 from .pose_order import PoseOrderDecoder, cyclic_prior, prob_score  # noqa: F401
 
 __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnLstm", "Quadtree3DCNN", "Ji3DCNN", "FusedAdam", "grad_norm",
            "CrossEntropyLoss", "FocalLoss", "LossMeter", "FramePreprocessor", "random_resized_crop_boxes", "random_flips", "FrameAugmenter",
-           "GradCAM", "jet_lut", "PoseFeatures", "FEATURE_NAMES", "load_class_stats", "EvalMeter", "predict",
+           "GradCAM", "jet_lut", "PoseFeatures", "FEATURE_NAMES", "load_class_stats", "EvalMeter", "predict", "ScoreMeter",
            "SequencePoseFeatures", "SEQUENCE_FEATURE_NAMES", "NUM_SEQUENCE_FEATURES",
            "SequenceWindows", "WindowPlan", "fit_class_stats",
            "FrameAnnotator", "caption_atlas", "POSE_CONNECTIONS", "MAJOR_SEGMENTS", "PoseTimeline",
