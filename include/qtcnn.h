@@ -1180,6 +1180,33 @@ int qt_transpose_f32(const float* src, float* dst, int rows, int cols, void* str
 int qt_scale_by_nonzero(float* g, const float* x, long long n, float mul, void* stream);
 /* dst[i] = (float)src[i] (src of type `dtype`): f32 copy of the fused per-frame features for the f32 LSTM products */
 int qt_cast_f32(int dtype, const void* src, float* dst, long long n, void* stream);
+/* The same 2-layer LSTM on a video STREAM: one row of h1 per frame instead of one per materialised window.
+ * The rule.  S streams advance together by n >= 1 frames per call; `seen` frames came before the call.  Frame f of the
+ *   call has global index g = seen + f and gets one row: h1 at the last step of the 2-layer LSTM run from a zero state
+ *   over the len = min(T, g + 1) frames ending at g, eval arithmetic (no dropout between the layers).  For g >= T - 1
+ *   that is the model in eval() on the materialised window, for the first T - 1 frames of a stream the model at sequence
+ *   length g + 1: as many rows as have been seen, the rule of qt_timeline_smooth.
+ * qt_lstm_stream_forward: xproj0 [S][T-1+n][4H] = layer 0's input products x W_ih0^T + b_ih0, ONE row per frame: the
+ *   T - 1 carry rows (the frames before the call) first, then the call's n rows; window f reads rows f .. f+T-1, and
+ *   rows of frames in front of the stream's start (row r with seen - (T-1) + r < 0) are never read, whatever they hold.
+ *   whh0_t / wih1_t / whh1_t = W_hh0^T / W_ih1^T / W_hh1^T, each [H][4H] (qt_transpose_f32); bhh0 / bih1 / bhh1 [4H].
+ *   -> hlast [S][n][H], and carry_out [S][T-1][4H] (nullable; must not be xproj0's storage: the caller swaps two
+ *   buffers) = the last T - 1 rows of xproj0, rows in front of the stream's start as zeros.  One launch runs both
+ *   layers, layer 1's input product included; a workgroup owns QT_LSTM_STREAM_TILE consecutive windows of one stream (one
+ *   window when n == 1, the live step) and reads every weight matrix once per step for the tile.  No buffer of size windows x T exists: the workspace
+ *   (qt_lstm_stream_workspace_bytes, the caller's) is 0 bytes today and may be NULL.  f32, no atomics, no host sync.
+ *   Every window is its own k-ordered fmaf chains, so its bits do not depend on its place in a tile, on n or on S: any
+ *   split of a stream into consecutive calls gives the hlast and the final carry of one call, and a stream alone the
+ *   bits it has in a batch.  H in {256, 64}, 1 <= T <= 64, else QT_ERR_UNSUPPORTED before any launch; all operands
+ *   16-byte aligned.
+ * qt_lstm_stream_stage: xproj0 [S][T-1+n][4H] <- carry_in [S][T-1][4H] (NULL when T == 1) in front of xnew [S][n][4H]
+ *   (the dense product of the call's frames); same limits. */
+#define QT_LSTM_STREAM_TILE 8
+size_t qt_lstm_stream_workspace_bytes(int S, int n, int T, int H);
+int qt_lstm_stream_forward(const float* xproj0, const float* whh0_t, const float* bhh0, const float* wih1_t,
+                           const float* bih1, const float* whh1_t, const float* bhh1, float* hlast, float* carry_out,
+                           void* workspace, size_t workspace_bytes, long long seen, int S, int n, int T, int H, void* stream);
+int qt_lstm_stream_stage(const float* carry_in, const float* xnew, float* xproj0, int S, int n, int T, int H, void* stream);
 /* nn.Dropout (Quadtree_from scratch/models.py:258,269), in place, counter-hash RNG */
 int qt_dropout(int dtype, void* x, long long rows, int cols, int ld, unsigned long long seed, float p, void* stream);
 /* g = act > 0 ? g*mul : 0 (ReLU / dropout backward from the forward output) */
@@ -1471,6 +1498,25 @@ int qt_plan_adam_step_clipped(qt_plan* plan, void* workspace, void* const* tenso
                               size_t norm_workspace_bytes, float* out2, void* stream);
 int qt_plan_forward(qt_plan* plan, void* workspace, void* const* tensors, const float* image, const float* numerical,
                     float* logits, int batch, int training, unsigned long long seed, void* stream);
+/* QT_MODEL_CNN_LSTM on a video stream (the rule: qt_lstm_stream_forward): every frame is embedded once, a window is an
+ * addressing rule.  Other models: QT_ERR_UNSUPPORTED with a message.  Eval arithmetic; needs qt_plan_pack_weights.
+ *   qt_plan_features       : the per-frame ResNet-18 and the pose MLP for any batch <= the plan's capacity (it need not be a
+ *                            multiple of seq_len); stops before the LSTM: buffer "fused" holds the [batch][640] rows.
+ *   qt_plan_stream_forward : S streams x n frames, frame-major per stream (image [S*n,3,224,224], numerical [S*n,47],
+ *                            S*n <= capacity) -> logits [S*n][num_classes], one row per frame from the window of the last T
+ *                            frames (T need not be seq_len).  Features, the f32 cast, layer 0's input product on the route
+ *                            of qt_plan_forward, qt_lstm_stream_stage behind carry_in, qt_lstm_stream_forward, the classifier.
+ *                            carry_in / carry_out [S][T-1][4H] f32 (two buffers the caller swaps; unused when T == 1;
+ *                            rows of carry_in in front of the stream's start never reach a result) and
+ *                            stream_workspace (qt_plan_stream_workspace_bytes(plan, S, n, T), 16-byte aligned) are the
+ *                            caller's.  No host synchronisation.
+ * Both overwrite what qt_plan_backward reads: a backward is refused until the next qt_plan_forward. */
+int qt_plan_features(qt_plan* plan, void* workspace, void* const* tensors, const float* image, const float* numerical,
+                     int batch, void* stream);
+size_t qt_plan_stream_workspace_bytes(const qt_plan* plan, int S, int n, int T);
+int qt_plan_stream_forward(qt_plan* plan, void* workspace, void* const* tensors, const float* image, const float* numerical,
+                           float* logits, const float* carry_in, float* carry_out, void* stream_workspace,
+                           size_t stream_workspace_bytes, long long seen, int S, int n, int T, void* stream);
 int qt_plan_backward(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads, const float* numerical,
                      const float* dlogits, int phases, void* stream);
 int qt_plan_backward_dx(qt_plan* plan, void* workspace, void* const* tensors, float* const* grads,

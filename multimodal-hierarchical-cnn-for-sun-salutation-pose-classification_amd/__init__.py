@@ -17,6 +17,7 @@ from .gradcam import GradCAM, jet_lut  # noqa: F401
 from .pose import FEATURE_NAMES, PoseFeatures, load_class_stats  # noqa: F401
 from .pose_sequence import NUM_SEQUENCE_FEATURES, SEQUENCE_FEATURE_NAMES, SequencePoseFeatures  # noqa: F401
 from .sequence_windows import SequenceWindows, WindowPlan, fit_class_stats  # noqa: F401
+from .sequence_stream import CnnLstmStream  # noqa: F401
 from .metrics import EvalMeter, predict  # noqa: F401
 from .scores import ScoreMeter  # noqa: F401
 from .annotate import MAJOR_SEGMENTS, POSE_CONNECTIONS, FrameAnnotator, caption_atlas  # noqa: F401
@@ -27,7 +28,7 @@ __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnL
            "CrossEntropyLoss", "FocalLoss", "LossMeter", "FramePreprocessor", "random_resized_crop_boxes", "random_flips", "FrameAugmenter",
            "GradCAM", "jet_lut", "PoseFeatures", "FEATURE_NAMES", "load_class_stats", "EvalMeter", "predict", "ScoreMeter",
            "SequencePoseFeatures", "SEQUENCE_FEATURE_NAMES", "NUM_SEQUENCE_FEATURES",
-           "SequenceWindows", "WindowPlan", "fit_class_stats",
+           "SequenceWindows", "WindowPlan", "fit_class_stats", "CnnLstmStream",
            "FrameAnnotator", "caption_atlas", "POSE_CONNECTIONS", "MAJOR_SEGMENTS", "PoseTimeline",
            "PoseOrderDecoder", "cyclic_prior", "prob_score",
            "QtError", "LIB_PATH"]

@@ -1160,6 +1160,62 @@ int forward(qt_plan* p, void* workspace, void* const* T, const float* image, con
   return e.status;
 }
 
+// CnnLstm on a video stream (the rule: include/qtcnn.h at qt_lstm_stream_forward).  What a frame needs ONCE -- the
+// backbone, the pose MLP, layer 0's input product -- runs once per frame; only the recurrence belongs to a window.
+// features(): forward() up to the join, eval arithmetic, for any number of frames up to the plan's capacity.
+Fwd stream_exec(qt_plan* p, void* workspace, void* const* T, const float* image, const float* numerical, float* logits,
+                int frames, void* stream) {
+  Fwd e{{p, static_cast<unsigned char*>(workspace), T, stream, frames, p->d.dtype}, image, numerical, logits, 0, 0};
+  e.tr = false;
+  e.unf = false;
+  e.mlp_early = false;
+  return e;
+}
+
+void features(Fwd& e) {
+  qt_plan* p = e.p;
+  e.setup_side();
+  p->tail_ready = false;
+  p->last_batch = 0;  // the buffers a backward would read are overwritten or stale: it is refused until the next forward
+  e.eval_affines(false);
+  e.stem();
+  e.blocks();
+  e.mlp_branch();
+  e.join();
+}
+
+int stream_forward(qt_plan* p, void* workspace, void* const* T, const float* image, const float* numerical, float* logits,
+                   const float* carry_in, float* carry_out, void* stream_ws, size_t stream_ws_bytes, long long seen, int S,
+                   int n, int win, void* stream) {
+  const int B = S * n, H = p->lstm_h;
+  Fwd e = stream_exec(p, workspace, T, image, numerical, logits, B, stream);
+  features(e);
+  const qt_plan::LstmL& L0 = p->lstm_l[0];
+  const qt_plan::LstmL& L1 = p->lstm_l[1];
+  // layer 0's input product of the call's frames, the route of lstm_tail(): f32 copy of the features, f32 MFMA product
+  e.run(qt_cast_f32(e.dt, e.at(p->fused), e.at<float>(p->lstm_x0), (long long)B * L0.in, stream));
+  e.igemm(e.dense_f32(B, L0.in, 4 * H), e.at(p->lstm_x0), e.tf(L0.w_ih), e.at(L0.xproj), nullptr, e.tf(L0.b_ih), nullptr,
+          nullptr, nullptr, 0);
+  // ... into the rows behind the carry: xproj0 [S][win-1+n][4H] is the head of the caller's stream workspace
+  float* xproj0 = static_cast<float*>(stream_ws);
+  const size_t xbytes = (size_t)S * ((size_t)win - 1 + n) * 4 * H * 4;
+  if (e.ok()) e.run(qt_lstm_stream_stage(carry_in, e.at<float>(L0.xproj), xproj0, S, n, win, H, stream));
+  if (e.ok()) e.run(qt_transpose_f32(e.tf(L0.w_hh), e.at<float>(L0.whh_t), 4 * H, H, stream));
+  if (e.ok()) e.run(qt_transpose_f32(e.tf(L1.w_ih), e.at<float>(L1.wih_t), 4 * H, H, stream));
+  if (e.ok()) e.run(qt_transpose_f32(e.tf(L1.w_hh), e.at<float>(L1.whh_t), 4 * H, H, stream));
+  float* hlast = e.at<float>(L1.hout);  // [S*n][H]
+  if (e.ok())
+    e.run(qt_lstm_stream_forward(xproj0, e.at<float>(L0.whh_t), e.tf(L0.b_hh), e.at<float>(L1.wih_t), e.tf(L1.b_ih),
+                                 e.at<float>(L1.whh_t), e.tf(L1.b_hh), hlast, win > 1 ? carry_out : nullptr,
+                                 static_cast<unsigned char*>(stream_ws) + xbytes, stream_ws_bytes - xbytes, seen, S, n, win, H,
+                                 stream));
+  if (!e.ok()) return e.status;
+  e.dense_fwd(hlast, QT_F32, e.tf(p->cls0.w), e.tf(p->cls0.b), e.at(p->lstm_hid), QT_F32, B, H, 128, 1, H, 128, stream);
+  e.dense_fwd(e.at(p->lstm_hid), QT_F32, e.tf(p->cls3.w), e.tf(p->cls3.b), logits, QT_F32, B, 128, p->cls3.out, 0, 128,
+              p->cls3.out, stream);
+  return e.status;
+}
+
 // zero-fill helper (hipMemsetAsync is capture-safe)
 int zero(void* ptr, size_t bytes, void* stream) {
   hipError_t err = hipMemsetAsync(ptr, 0, bytes, static_cast<hipStream_t>(stream));
@@ -1868,6 +1924,54 @@ extern "C" int qt_plan_forward(qt_plan* p, void* workspace, void* const* tensors
   QT_CHECK_ARG(!p->has_numerical || numerical, "qt_plan_forward: numerical input required");
   QT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "qt_plan_forward: workspace must be 256-byte aligned");
   return forward(p, workspace, tensors, image, numerical, logits, batch, training, seed, stream);
+}
+
+extern "C" int qt_plan_features(qt_plan* p, void* workspace, void* const* tensors, const float* image,
+                                const float* numerical, int batch, void* stream) {
+  QT_CHECK_ARG(p, "qt_plan_features: null plan");
+  if (!p->lstm) {
+    qt_set_error("qt_plan_features: the plan is not a CnnLstm (model %d): only the sequence model has per-frame features "
+                 "that a stream shares between windows", p->d.model);
+    return QT_ERR_UNSUPPORTED;
+  }
+  QT_CHECK_ARG(workspace && tensors && image && numerical, "qt_plan_features: null argument");
+  QT_CHECK_ARG(batch > 0 && batch <= p->d.batch, "qt_plan_features: batch %d exceeds the plan's %d", batch, p->d.batch);
+  QT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "qt_plan_features: workspace must be 256-byte aligned");
+  Fwd e = stream_exec(p, workspace, tensors, image, numerical, nullptr, batch, stream);
+  features(e);
+  return e.status;
+}
+
+extern "C" size_t qt_plan_stream_workspace_bytes(const qt_plan* p, int S, int n, int T) {
+  if (!p || !p->lstm || S <= 0 || n <= 0 || T < 1 || T > 64) return 0;
+  return (size_t)S * ((size_t)T - 1 + n) * 4 * p->lstm_h * 4 + qt_lstm_stream_workspace_bytes(S, n, T, p->lstm_h);
+}
+
+extern "C" int qt_plan_stream_forward(qt_plan* p, void* workspace, void* const* tensors, const float* image,
+                                      const float* numerical, float* logits, const float* carry_in, float* carry_out,
+                                      void* stream_workspace, size_t stream_workspace_bytes, long long seen, int S, int n,
+                                      int T, void* stream) {
+  QT_CHECK_ARG(p, "qt_plan_stream_forward: null plan");
+  if (!p->lstm) {
+    qt_set_error("qt_plan_stream_forward: the plan is not a CnnLstm (model %d): the 2-D models classify a frame by itself, "
+                 "use qt_plan_forward", p->d.model);
+    return QT_ERR_UNSUPPORTED;
+  }
+  if (T < 1 || T > 64) {
+    qt_set_error("qt_plan_stream_forward: window of %d frames is outside 1 .. 64", T);
+    return QT_ERR_UNSUPPORTED;
+  }
+  QT_CHECK_ARG(workspace && tensors && image && numerical && logits && stream_workspace, "qt_plan_stream_forward: null argument");
+  QT_CHECK_ARG(T == 1 || (carry_in && carry_out && carry_in != carry_out),
+               "qt_plan_stream_forward: a window of %d frames needs two distinct carry buffers", T);
+  QT_CHECK_ARG(S > 0 && n > 0 && seen >= 0, "qt_plan_stream_forward: streams %d, frames %d, seen %lld", S, n, seen);
+  QT_CHECK_ARG((long long)S * n <= p->d.batch, "qt_plan_stream_forward: %d x %d frames exceed the plan's %d", S, n, p->d.batch);
+  QT_CHECK_ARG(stream_workspace_bytes >= qt_plan_stream_workspace_bytes(p, S, n, T),
+               "qt_plan_stream_forward: stream workspace too small (qt_plan_stream_workspace_bytes)");
+  QT_CHECK_ARG(((uintptr_t)workspace % 256) == 0 && ((uintptr_t)stream_workspace % 16) == 0,
+               "qt_plan_stream_forward: workspace must be 256-byte and stream workspace 16-byte aligned");
+  return stream_forward(p, workspace, tensors, image, numerical, logits, carry_in, carry_out, stream_workspace,
+                        stream_workspace_bytes, seen, S, n, T, stream);
 }
 
 extern "C" int qt_plan_backward(qt_plan* p, void* workspace, void* const* tensors, float* const* grads,
