@@ -1016,6 +1016,53 @@ long long qt_pose_order_workspace_bytes(const qt_pose_order_desc* desc);
 int qt_pose_order_decode(const qt_pose_order_desc* desc, const float* probs, long long ld, const int* state_class,
                          const int* trans, const int* init, long long* carry, long long* path, long long* filtered,
                          int* emissions, void* workspace, long long workspace_bytes, void* stream);
+/* Pose-order posteriors: the marginals of the hidden-Markov chain that qt_pose_order_decode maximises: how sure the chain is
+ * of step j at frame f.  Same inputs, limits and refusals: probs f32 [batch][frames][C] with row stride ld >= C, state_class
+ * int32 [S], trans int32 [S][S] in [-65536, 0] (clamped as read), init int32 [S] or NULL for zeros, S and C <= 64, batch *
+ * frames <= 2^20.  Emissions are the decoder's integers e[f][j] = q(probs[f][state_class[j]]), the same q bit for bit (NaN
+ * and everything below 2^-32 give -8192, and so does a state whose class is outside [0, C)).
+ * Scores are in units of 1/256 bit: T[i][j] = trans[i][j] / 256 and E[f][j] = e[f][j] / 256 are exact in f32, a path weighs
+ * 2^(the sum of its T and E), the quantity the decoder maximises.  Write L_i x[i] = log2 sum_i 2^x[i].
+ * Forward, per stream, frame by frame; a_prev is init / 256 at a stream's first frame (frames_seen == 0), the carry after it:
+ *   A_f[j] = E[f][j] + L_i (a_prev[i] + T[i][j]),   c_f = L_j A_f[j],   a_f = A_f - c_f
+ *   filtered[f][j] = 2^a_f[j]                        (causal; a row sums to 1)
+ * Backward, over the call's n frames:  b_(n-1) = 0,  b_f[i] = L_j (T[i][j] + E[f+1][j] + b_(f+1)[j]), each frame's b less
+ * its maximum (a constant changes no posterior; without it b falls by up to 288 a frame).
+ *   posterior[f][j]       = 2^(a_f[j] + b_f[j] - L_k (a_f[k] + b_f[k]))     P(step j at frame f | every frame up to the call's end)
+ *   class_posterior[f][c] = the sum of posterior[f][j] over the j with state_class[j] == c, in ascending j (0 where there is none)
+ *   log2_evidence[stream] = sum_f c_f over the call, in bits, double
+ * Every L is taken with its maximum out, L x = m + log2 sum_i 2^(x[i] - m) with m = max_i x[i], the sum in ascending i: it is
+ * in [1, S], so no infinity or NaN arises for any table in range (an all -65536 table too: that is why the rule is in log2
+ * and not in scaled probabilities, 2^-256 is no f32); a term more than 126 bits below the maximum may flush to zero.  c_f and
+ * the evidence are accumulated in double.  carry: double [batch][S + 2] = { frames_seen, evidence_total, a_last[S] } in device
+ * memory for the whole video, updated in place; the caller zeroes it once.  a_last holds f32 values, so the next call resumes
+ * from the very a_f the last one ended on.
+ *   posterior        f32 [batch][frames][S], required      filtered       f32 [batch][frames][S], or NULL
+ *   class_posterior  f32 [batch][frames][C], or NULL       log2_evidence  double [batch], or NULL
+ * Routes.  frames <= QT_POSE_ORDER_TILE: one launch, one wave per stream, lane = state, the emissions, the table and the a_f
+ * rows in LDS, forward and then the backward sweep over the same rows, no workspace; at frames == 1 posterior == filtered.
+ * Here filtered, evidence_total and the carry are the bits of one call for any split of a stream into such calls, and the last
+ * call's posterior is the bits of the one-call posterior on its frames.  Longer calls: with M_f[i][j] = T[i][j] + E[f][j] a
+ * frame is a_f = a_(f-1) (x) M_f in the (L, +) semiring and b_f = M_(f+1) (x) b_(f+1), so one set of tile products serves both
+ * directions: (a) a workgroup per tile forms the tile's product, kept row-normalised (row maximum 0, the shifts summed per row
+ * in double), (b) one wave per stream carries the start vector forward and the end vector backward through the products and
+ * leaves every tile's start a, end b and the evidence before it, (c) a wave per tile replays its frames forward from its
+ * start and sweeps backward from its end.  Three launches.  f32 (L, +) products are not exactly associative: this route's
+ * outputs differ from the frame-by-frame rule by rounding, and the split promise in bits holds on the short route only.
+ * qt_pose_posterior_workspace_bytes: what the tiled route needs (8-byte aligned; every slot that is read is written in the
+ * same call, nothing is zero-filled), 0 on the short route and for a descriptor that would be refused.  No workgroup waits for
+ * another inside a launch, no atomics, no host synchronisation; inputs are never written; a stream alone gives the bits of the
+ * same stream in a batch; every run gives the same bits.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument) for a null desc, non-positive batch or
+ * frames, num_states or num_classes outside 1 .. 64, ld < C, a null probs, state_class, trans, carry or posterior, misaligned
+ * pointers (4 bytes for f32 and int32, 8 for double and the workspace), a workspace smaller than the query's size, an output
+ * (carry, posterior, filtered, class_posterior, log2_evidence, workspace) that overlaps an input or another output;
+ * QT_ERR_UNSUPPORTED for more than 2^20 frames in all (batch * frames). */
+long long qt_pose_posterior_workspace_bytes(const qt_pose_order_desc* desc);
+int qt_pose_posterior(const qt_pose_order_desc* desc, const float* probs, long long ld, const int* state_class,
+                      const int* trans, const int* init, double* carry, float* posterior, float* filtered,
+                      float* class_posterior, double* log2_evidence, void* workspace, long long workspace_bytes, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

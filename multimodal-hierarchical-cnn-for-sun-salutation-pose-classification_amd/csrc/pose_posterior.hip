@@ -1,0 +1,733 @@
+// Pose-order posteriors on the device (qt_pose_posterior): the marginals of the hidden-Markov chain that qt_pose_order_decode
+// (pose_order.hip) maximises, by forward-backward in log2.  Emissions are the decoder's integers q (the same rule and table, pinned
+// by tests/test_pose_posterior_gpu.py), scores are in units of 1/256 bit and exact in f32; every L x = log2 sum 2^x[i] is taken
+// with its maximum out and its sum in ascending order, so nothing is infinite for any table in range and every run gives the
+// same bits; whatever grows with the frame count is a double.  include/qtcnn.h states the rule in full.
+//
+// Short route (frames <= PP_TILE): one launch, one wave per stream, lane = state, no workspace.  The table (row stride S | 1: a
+// column for the forward step and a row for the backward one are both free of bank conflicts), the tile's emissions and its a_f
+// rows are in LDS.  A forward step is the decoder's vector step with (L, +) for (max, +): S times { v_readlane of a_prev[i], add
+// the table entry }, a tree of maxima, the sum of v_exp_f32 in ascending i, v_log_f32; for S <= 16 the lane's column (and, for the
+// backward step, its row) is in registers.  Then c_f = L_j A_f[j] over the lanes (S readlanes for the maximum, S for the sum), so
+// that the next frame starts from the a_f of the rule and a split into calls changes no bit.  The backward sweep walks the same
+// LDS rows, one frame per step, overwrites a_f with the posterior and stores it; class_posterior is summed from those rows at the
+// end (thread = (frame, class), ascending j).
+// Tiled route (frames > PP_TILE), three launches, M_f[i][j] = T[i][j] + E[f][j]:
+//   (a) pp_products: a workgroup of 256 per (stream, tile) forms P = M_a (x) ... (x) M_b in the (L, +) semiring in LDS, thread =
+//       (i, j), two buffers in turn, one barrier per frame.  Row i is a forward filter started at state i: every frame takes the
+//       row's maximum out (each thread finds it while it reads the row) and adds it to the row's offset, a double;
+//   (b) pp_scan: a workgroup per stream; wave 0, lane = state, carries the start vector forward through the products of tiles
+//       0 .. tiles - 2 (offsets added in double, the maximum out before going back to f32) and the end vector backward through
+//       those of tiles tiles - 1 .. 1, while all four waves stage the next trip's products (16 KB, at most 16) through registers
+//       into the other LDS buffer.  It leaves every tile's start a, end b and the evidence before the tile in the workspace;
+//   (c) pp_replay: a wave per (stream, tile) replays its frames from its start a with the short route's step (filtered, the a_f
+//       rows in LDS), sweeps backward from its end b and writes the outputs; the stream's last tile writes the carry.
+// f32 (L, +) products are not exactly associative, so (a)-(c) differ from the frame-by-frame rule by rounding.
+// No workgroup waits for another inside a launch, no atomics, no zero fill, no host synchronisation; every order is fixed; the
+// workspace is the caller's and every slot that is read has been written in the same call.
+// QTCNN_POSE_POSTERIOR=1 (consulted per call; measurements only, scripts/bench_pose_posterior.py): the short route's algorithm as
+// ONE wave per stream over all tiles, the a_f rows parked in the posterior output between the two sweeps.
+#include <stdint.h>
+
+#include "qt_common.h"
+
+namespace {
+
+constexpr int PP_TILE = 64;                      // frames per tile; frames <= PP_TILE take the short route
+constexpr int PP_MAX_S = 64;
+constexpr int PP_MAX_C = 64;
+constexpr long long PP_MAX_FRAMES = 1LL << 20;
+constexpr int PP_FLOOR = -8192;                  // q of NaN and of everything below 2^-32
+constexpr int PP_TRANS_FLOOR = -65536;
+constexpr float PP_PAD = -1e30f;                 // a candidate in a slot beyond S: never the maximum, and 2^(it - m) is 0
+constexpr int PP_SCAN_FLOATS = 4096;             // (b): floats of products per trip
+constexpr int PP_SCAN_MAX_TILES = 16;            // (b): products per trip at the most
+constexpr int PP_SCAN_PAD = PP_SCAN_MAX_TILES * 16;   // a trip's tiles * S <= 256 for every S: the rows' padding to S | 1, the offsets
+constexpr int PP_PROD_THREADS = 256;
+constexpr int PP_SCAN_THREADS = 256;
+static_assert(PP_TILE == QT_POSE_ORDER_TILE && PP_MAX_S == QT_POSE_ORDER_MAX_STATES && PP_MAX_C == QT_POSE_ORDER_MAX_CLASSES,
+              "the header states these");
+static_assert(PP_SCAN_FLOATS >= PP_MAX_S * PP_MAX_S && PP_SCAN_FLOATS % PP_SCAN_THREADS == 0, "a trip holds at least one product");
+
+// rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the decoder's table (pose_order.hip, PO_LOG2)
+__device__ const unsigned short PP_LOG2[256] = {
+      1,   2,   4,   5,   6,   8,   9,  11,  12,  13,  15,  16,  18,  19,  20,  22,
+     23,  24,  26,  27,  28,  30,  31,  32,  34,  35,  36,  38,  39,  40,  42,  43,
+     44,  45,  47,  48,  49,  50,  52,  53,  54,  55,  57,  58,  59,  60,  62,  63,
+     64,  65,  66,  68,  69,  70,  71,  72,  74,  75,  76,  77,  78,  80,  81,  82,
+     83,  84,  85,  86,  88,  89,  90,  91,  92,  93,  94,  95,  97,  98,  99, 100,
+    101, 102, 103, 104, 105, 106, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117,
+    118, 119, 120, 121, 122, 123, 124, 125, 126, 127, 128, 129, 131, 132, 133, 134,
+    135, 136, 137, 138, 139, 140, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149,
+    150, 151, 152, 153, 154, 155, 156, 157, 158, 159, 160, 161, 162, 163, 163, 164,
+    165, 166, 167, 168, 169, 170, 171, 172, 173, 173, 174, 175, 176, 177, 178, 179,
+    180, 181, 182, 182, 183, 184, 185, 186, 187, 188, 189, 189, 190, 191, 192, 193,
+    194, 195, 195, 196, 197, 198, 199, 200, 200, 201, 202, 203, 204, 205, 205, 206,
+    207, 208, 209, 210, 210, 211, 212, 213, 214, 214, 215, 216, 217, 218, 218, 219,
+    220, 221, 222, 222, 223, 224, 225, 226, 226, 227, 228, 229, 229, 230, 231, 232,
+    233, 233, 234, 235, 236, 236, 237, 238, 239, 239, 240, 241, 242, 242, 243, 244,
+    245, 245, 246, 247, 248, 248, 249, 250, 251, 251, 252, 253, 253, 254, 255, 256
+};
+
+struct PpArgs {
+  const float* probs;
+  const int* state_class;
+  const int* trans;
+  const int* init;
+  double* carry;
+  float* posterior;
+  float* filtered;
+  float* class_posterior;
+  double* evidence;
+  double* offsets;           // workspace: double [batch][tiles][S], the products' row offsets
+  double* before;            //            double [batch][tiles], the evidence before the tile
+  float* products;           //            f32 [batch][tiles][S][S], row maximum 0
+  float* starts;             //            f32 [batch][tiles][S], a in front of the tile's first frame
+  float* ends;               //            f32 [batch][tiles][S], b at the tile's last frame
+  long long ld;
+  int T, tiles, C, S;
+  FastDiv div_s, div_c;
+};
+
+__device__ __forceinline__ int pp_q(float p) {
+  if (!(p >= 0x1p-32f)) return PP_FLOOR;         // NaN, negatives, zeros, denormals
+  if (p >= 1.0f) return 0;
+  const unsigned b = __float_as_uint(p);
+  return 256 * ((int)(b >> 23) - 127) + (int)PP_LOG2[(b >> 15) & 255u];
+}
+__device__ __forceinline__ float pp_score(int v) { return (float)v * 0x1p-8f; }   // exact: |v| < 2^24
+__device__ __forceinline__ float pp_trans(int v) { return pp_score(min(max(v, PP_TRANS_FLOOR), 0)); }
+
+__device__ __forceinline__ float pp_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32; x <= 0 here
+__device__ __forceinline__ float pp_log2(float x) { return __builtin_amdgcn_logf(x); }    // v_log_f32; x in [1, S] here
+// log2 of a sum s in [1, S] in two parts, s = 2^k t with t in [1, 2): k is exact and log2 t < 1 keeps 2^-24 where log2 s, up to 6,
+// keeps 2^-22.  Where the maximum in front of it is about -log2 s (a normalised vector, a flat table) m + k is exact and the sum
+// keeps the better figure; c_f takes the parts as doubles.
+__device__ __forceinline__ void pp_log2_parts(float s, float& k, float& lt) {
+  const unsigned b = __float_as_uint(s);
+  k = (float)((int)(b >> 23) - 127);
+  lt = pp_log2(__uint_as_float((b & 0x007FFFFFu) | 0x3F800000u));
+}
+__device__ __forceinline__ float pp_m_plus_log2(float m, float s) {
+  float k, lt;
+  pp_log2_parts(s, k, lt);
+  return (m + k) + lt;
+}
+__device__ __forceinline__ float pp_lane(float v, int i) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
+}
+__device__ __forceinline__ double pp_lane(double v, int i) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), i), __builtin_amdgcn_readlane(__double2loint(v), i));
+}
+template <typename V>
+__device__ __forceinline__ V pp_max16(V (&t)[16]) {
+#pragma unroll
+  for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+    for (int i = 0; i < w; ++i) t[i] = t[i + w] > t[i] ? t[i + w] : t[i];
+  return t[0];
+}
+
+// over the states of a per-lane value (one wave, lane = state; lanes >= S hold state S - 1 again), every lane receives the
+// result.  SMALL: S <= 16, sixteen readlanes and a tree, no loop.
+template <bool SMALL, typename V>
+__device__ __forceinline__ V pp_max_states(V v, int S) {
+  if (SMALL) {
+    V t[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t[i] = pp_lane(v, i);
+    return pp_max16(t);
+  }
+  V m = pp_lane(v, 0);
+  for (int i = 1; i < S; ++i) {
+    const V o = pp_lane(v, i);
+    m = o > m ? o : m;
+  }
+  return m;
+}
+// L over the states: the maximum m and lg = log2 of the sum, in ascending state, of 2^(v - m); c = m + lg from lg's parts.
+// live: lane < S.  SMALL: the lanes S .. 15 contribute zeros behind the last state, which changes no bit of the sum.
+template <bool SMALL>
+__device__ __forceinline__ void pp_L_states(float v, int S, bool live, float& m, float& lg, double& c) {
+  m = pp_max_states<SMALL>(v, S);
+  const float p = live ? pp_exp2(v - m) : 0.0f;
+  float s = pp_lane(p, 0);
+  if (SMALL) {
+#pragma unroll
+    for (int i = 1; i < 16; ++i) s += pp_lane(p, i);
+  } else {
+    for (int i = 1; i < S; ++i) s += pp_lane(p, i);
+  }
+  float k, lt;
+  pp_log2_parts(s, k, lt);
+  lg = k + lt;
+  c = ((double)m + (double)k) + (double)lt;
+}
+template <bool SMALL>
+__device__ __forceinline__ void pp_L_states(float v, int S, bool live, float& m, float& lg) {
+  double c;
+  pp_L_states<SMALL>(v, S, live, m, lg, c);
+}
+
+// sixteen table entries of a lane into registers; slots >= S hold PP_PAD, which changes no maximum and adds 0 to a sum
+__device__ __forceinline__ void pp_load16(float (&reg)[16], const float* __restrict__ tab, int stride, int S) {
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const float v = tab[(k < S ? k : 0) * stride];
+    reg[k] = k < S ? v : PP_PAD;
+  }
+}
+
+// L_k (bc[k] + table[k]) for one lane: bc[k] is lane k's value, table[k] the lane's own entry (a column of the table going
+// forward, a row going backward).  SMALL: S <= 16, the entries in `reg`; otherwise tab[k * stride] in LDS.
+template <bool SMALL>
+__device__ __forceinline__ float pp_step(float bc, const float (&reg)[16], const float* __restrict__ tab, int stride, int S) {
+  if (SMALL) {
+    float x[16], t[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t[k] = x[k] = pp_lane(bc, k) + reg[k];   // (lanes S .. 15 hold finite values; reg pads them out)
+    const float m = pp_max16(t);
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += pp_exp2(x[k] - m);
+    return pp_m_plus_log2(m, s);
+  }
+  float m = pp_lane(bc, 0) + tab[0];
+  for (int k = 1; k < S; ++k) m = fmaxf(m, pp_lane(bc, k) + tab[k * stride]);
+  float s = 0.0f;
+  for (int k = 0; k < S; ++k) s += pp_exp2((pp_lane(bc, k) + tab[k * stride]) - m);
+  return pp_m_plus_log2(m, s);
+}
+
+// the emissions of frames [f0, f0 + n) of stream b into e_l [n][S]: as scores, or (where LDS is short) as the integers q
+__device__ __forceinline__ void pp_put(float* e_l, int idx, int e) { e_l[idx] = pp_score(e); }
+__device__ __forceinline__ void pp_put(short* e_l, int idx, int e) { e_l[idx] = (short)e; }
+template <typename E>
+__device__ __forceinline__ void pp_stage_emissions(const PpArgs& a, int b, int f0, int n, E* e_l) {
+  const int S = a.S;
+  const float* __restrict__ p = a.probs + ((long long)b * a.T + f0) * a.ld;
+  for (int idx = threadIdx.x; idx < n * S; idx += blockDim.x) {
+    const int f = (int)fdiv((unsigned)idx, a.div_s), s = idx - f * S;
+    const int k = a.state_class[s];
+    int e = PP_FLOOR;
+    if ((unsigned)k < (unsigned)a.C) e = pp_q(p[(long long)f * a.ld + k]);
+    pp_put(e_l, idx, e);
+  }
+}
+
+// the LDS of the one-wave kernels
+struct PpLds {
+  float* t;              // [S][S | 1]: the table
+  float* a;              // [PP_TILE][S]: a_f, then the posterior
+  float* e;              // [PP_TILE][S]
+  int* sc;               // [S]
+};
+__device__ __forceinline__ PpLds pp_carve(float* lds, int S) {
+  PpLds l;
+  l.t = lds;
+  l.a = l.t + S * (S | 1);
+  l.e = l.a + PP_TILE * S;
+  l.sc = reinterpret_cast<int*>(l.e + PP_TILE * S);
+  return l;
+}
+inline size_t pp_wave_lds_bytes(int S) { return 4 * ((size_t)S * (S | 1) + 2 * PP_TILE * S + S); }
+
+__device__ __forceinline__ void pp_stage_table(const PpArgs& a, const PpLds& l) {
+  const int S = a.S, SP = S | 1;
+  for (int idx = threadIdx.x; idx < S * S; idx += blockDim.x) {
+    const int i = (int)fdiv((unsigned)idx, a.div_s);
+    l.t[i * SP + (idx - i * S)] = pp_trans(a.trans[idx]);
+  }
+  for (int idx = threadIdx.x; idx < S; idx += blockDim.x) l.sc[idx] = a.state_class[idx];
+}
+
+// Forward over the n staged frames, lane = state (one wave; lanes >= S compute on state S - 1 and store nothing).  av: the
+// lane's a in front of the first frame on entry, a of the last frame on exit.  Leaves the a_f rows in LDS, writes filtered when
+// asked, adds every c_f to both sums.
+template <bool SMALL>
+__device__ __forceinline__ void pp_forward(const PpArgs& a, const PpLds& l, const float (&col)[16], int b, int f0, int n, int lane,
+                                           float& av, double& total, double& call) {
+  const int S = a.S, jj = min(lane, S - 1);
+  float* __restrict__ filt = a.filtered ? a.filtered + ((long long)b * a.T + f0) * S : nullptr;
+  float e = l.e[jj];
+  for (int f = 0; f < n; ++f) {
+    const float e_next = f + 1 < n ? l.e[(f + 1) * S + jj] : 0.0f;
+    const float A = e + pp_step<SMALL>(av, col, l.t + jj, S | 1, S);
+    float m, lg;
+    double c;
+    pp_L_states<SMALL>(A, S, lane < S, m, lg, c);
+    av = (A - m) - lg;
+    total += c;
+    call += c;
+    if (lane < S) {
+      l.a[f * S + lane] = av;
+      if (filt) filt[f * S + lane] = pp_exp2(av);
+    }
+    e = e_next;
+  }
+}
+
+// b of a frame from g[j] = E[f + 1][j] + b_(f + 1)[j], its maximum taken out
+template <bool SMALL>
+__device__ __forceinline__ float pp_b_from_g(const PpLds& l, const float (&row)[16], float g, int S, int jj) {
+  const float B = pp_step<SMALL>(g, row, l.t + jj * (S | 1), 1, S);
+  return B - pp_max_states<SMALL>(B, S);
+}
+
+// Backward over the n staged frames whose a_f rows are in LDS.  bv: the lane's b at the tile's last frame on entry.  call_end:
+// that frame is the call's last, where b is 0 and the posterior is the filtered row itself, bit for bit.  Overwrites the rows
+// with the posterior, stores it, and returns g of the tile's first frame for the tile in front.
+template <bool SMALL>
+__device__ __forceinline__ float pp_backward(const PpArgs& a, const PpLds& l, const float (&row)[16], int b, int f0, int n, int lane,
+                                             float bv, bool call_end) {
+  const int S = a.S, jj = min(lane, S - 1);
+  float* __restrict__ out = a.posterior + ((long long)b * a.T + f0) * S;
+  float g = 0.0f;
+  for (int f = n - 1; f >= 0; --f) {
+    if (f < n - 1) bv = pp_b_from_g<SMALL>(l, row, g, S, jj);
+    const float av = l.a[f * S + jj];
+    float post;
+    if (call_end && f == n - 1) {
+      post = pp_exp2(av);
+    } else {
+      const float u = av + bv;
+      float m, lg;
+      pp_L_states<SMALL>(u, S, lane < S, m, lg);
+      post = pp_exp2((u - m) - lg);
+    }
+    if (lane < S) {
+      l.a[f * S + lane] = post;
+      out[f * S + lane] = post;
+    }
+    g = l.e[f * S + jj] + bv;
+  }
+  return g;
+}
+
+// class_posterior of the n frames whose posterior rows are in LDS: thread = (frame, class), ascending j
+__device__ __forceinline__ void pp_classes(const PpArgs& a, const PpLds& l, int b, int f0, int n) {
+  if (!a.class_posterior) return;
+  const int S = a.S, C = a.C;
+  float* __restrict__ out = a.class_posterior + ((long long)b * a.T + f0) * C;
+  for (int idx = threadIdx.x; idx < n * C; idx += blockDim.x) {
+    const int f = (int)fdiv((unsigned)idx, a.div_c), c = idx - f * C;
+    float s = 0.0f;
+    for (int j = 0; j < S; ++j)
+      if (l.sc[j] == c) s += l.a[f * S + j];
+    out[idx] = s;
+  }
+}
+
+// a stream's start vector for lane jj: init before its first frame, the carry after it
+__device__ __forceinline__ float pp_stream_start(const PpArgs& a, int b, int jj) {
+  const double* __restrict__ c = a.carry + (long long)b * (a.S + 2);
+  if (c[0] == 0.0) return a.init ? pp_trans(a.init[jj]) : 0.0f;
+  return (float)c[2 + jj];
+}
+// after a stream's last frame: av = a_last; sum = the c_f of this call
+__device__ __forceinline__ void pp_write_carry(const PpArgs& a, int b, int lane, float av, double seen, double total, double call) {
+  double* __restrict__ c = a.carry + (long long)b * (a.S + 2);
+  if (lane < a.S) c[2 + lane] = (double)av;
+  if (lane == 0) {
+    c[0] = seen + (double)a.T;
+    c[1] = total;
+    if (a.evidence) a.evidence[b] = call;
+  }
+}
+
+// ---- the short route, and (QTCNN_POSE_POSTERIOR=1) the same algorithm over all tiles of a stream -----------------------------
+template <bool SMALL>
+__global__ __launch_bounds__(QT_WAVE) void pp_stream_kernel(PpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float pp_lds[];
+  const PpLds l = pp_carve(pp_lds, a.S);
+  const int lane = threadIdx.x, b = blockIdx.x, S = a.S, SP = S | 1, jj = min(lane, S - 1);
+  pp_stage_table(a, l);
+  const double seen = a.carry[(long long)b * (S + 2)];
+  double total = a.carry[(long long)b * (S + 2) + 1], call = 0.0;
+  float av = pp_stream_start(a, b, jj);
+  __syncthreads();
+  float col[16], row[16];
+  if (SMALL) {
+    pp_load16(col, l.t + jj, SP, S);
+    pp_load16(row, l.t + jj * SP, 1, S);
+  }
+  for (int tile = 0; tile < a.tiles; ++tile) {
+    const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+    __syncthreads();
+    pp_stage_emissions(a, b, f0, n, l.e);
+    __syncthreads();
+    pp_forward<SMALL>(a, l, col, b, f0, n, lane, av, total, call);
+    if (a.tiles > 1) {   // the a_f rows wait in the posterior output for the backward sweep
+      __syncthreads();
+      float* __restrict__ out = a.posterior + ((long long)b * a.T + f0) * S;
+      for (int idx = lane; idx < n * S; idx += QT_WAVE) out[idx] = l.a[idx];
+    }
+  }
+  pp_write_carry(a, b, lane, av, seen, total, call);
+  float g = 0.0f;
+  for (int tile = a.tiles - 1; tile >= 0; --tile) {
+    const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+    const bool last = tile == a.tiles - 1;
+    if (a.tiles > 1) {
+      __syncthreads();
+      pp_stage_emissions(a, b, f0, n, l.e);
+      const float* in = a.posterior + ((long long)b * a.T + f0) * S;
+      for (int idx = lane; idx < n * S; idx += QT_WAVE) l.a[idx] = in[idx];
+    }
+    __syncthreads();
+    const float bv = last ? 0.0f : pp_b_from_g<SMALL>(l, row, g, S, jj);
+    g = pp_backward<SMALL>(a, l, row, b, f0, n, lane, bv, last);
+    __syncthreads();
+    pp_classes(a, l, b, f0, n);
+  }
+}
+
+// ---- (a) tile products ---------------------------------------------------------------------------------------------------------
+// One entry of the next product: row `pr` of the current one (unnormalised: its maximum r is found here and taken out), column
+// `tc` of the table (stride S).  SMALL: S <= 16, the row in registers.
+template <bool SMALL>
+__device__ __forceinline__ float pp_product_entry(const float* __restrict__ pr, const float* __restrict__ tc, int S, float& r) {
+  if (SMALL) {
+    float q[16], x[16], t[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t[k] = q[k] = pr[k < S ? k : 0];
+    r = pp_max16(t);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const float v = (q[k] - r) + tc[(k < S ? k : 0) * S];
+      t[k] = x[k] = k < S ? v : PP_PAD;
+    }
+    const float m = pp_max16(t);
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += pp_exp2(x[k] - m);
+    return pp_m_plus_log2(m, s);
+  }
+  r = pr[0];
+  for (int k = 1; k < S; ++k) r = fmaxf(r, pr[k]);
+  float m = (pr[0] - r) + tc[0];
+  for (int k = 1; k < S; ++k) m = fmaxf(m, (pr[k] - r) + tc[k * S]);
+  float s = 0.0f;
+  for (int k = 0; k < S; ++k) s += pp_exp2(((pr[k] - r) + tc[k * S]) - m);
+  return pp_m_plus_log2(m, s);
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(PP_PROD_THREADS) void pp_products_kernel(PpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float pp_lds[];
+  const int S = a.S, SS = S * S, tid = threadIdx.x;
+  double* off = reinterpret_cast<double*>(pp_lds);   // [S] (64 doubles reserved)
+  float* tr = pp_lds + 2 * PP_MAX_S;
+  float* cur = tr + SS;
+  float* nxt = cur + SS;
+  short* e_l = reinterpret_cast<short*>(nxt + SS);   // q: three products of 64 x 64 leave no room for 16 KB of scores
+  const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
+  const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+  for (int idx = tid; idx < SS; idx += PP_PROD_THREADS) tr[idx] = pp_trans(a.trans[idx]);
+  for (int idx = tid; idx < S; idx += PP_PROD_THREADS) off[idx] = 0.0;
+  pp_stage_emissions(a, b, f0, n, e_l);
+  __syncthreads();
+  for (int idx = tid; idx < SS; idx += PP_PROD_THREADS) {
+    const int i = (int)fdiv((unsigned)idx, a.div_s);
+    cur[idx] = tr[idx] + pp_score(e_l[idx - i * S]);
+  }
+  __syncthreads();
+  for (int f = 1; f < n; ++f) {
+    for (int idx = tid; idx < SS; idx += PP_PROD_THREADS) {
+      const int i = (int)fdiv((unsigned)idx, a.div_s), j = idx - i * S;
+      float r;
+      const float v = pp_product_entry<SMALL>(cur + i * S, tr + j, S, r);
+      nxt[idx] = pp_score(e_l[f * S + j]) + v;
+      if (j == 0) off[i] += (double)r;   // (row i's own thread: nobody else touches off[i])
+    }
+    __syncthreads();
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  float* __restrict__ out = a.products + ((long long)b * a.tiles + tile) * SS;
+  double* __restrict__ out_off = a.offsets + ((long long)b * a.tiles + tile) * S;
+  for (int idx = tid; idx < SS; idx += PP_PROD_THREADS) {
+    const int i = (int)fdiv((unsigned)idx, a.div_s), j = idx - i * S;
+    const float* __restrict__ pr = cur + i * S;
+    float r = pr[0];
+    for (int k = 1; k < S; ++k) r = fmaxf(r, pr[k]);
+    out[idx] = cur[idx] - r;
+    if (j == 0) out_off[i] = off[i] + (double)r;
+  }
+}
+
+// ---- (b) the start vector forward and the end vector backward through the products ------------------------------------------
+__host__ __device__ inline int pp_scan_trip_tiles(int S) {
+  const int k = PP_SCAN_FLOATS / (S * S);
+  return k > PP_SCAN_MAX_TILES ? PP_SCAN_MAX_TILES : k;
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(PP_SCAN_THREADS) void pp_scan_kernel(PpArgs a) {
+  __shared__ __attribute__((aligned(16))) double offs[2][PP_SCAN_PAD];
+  __shared__ __attribute__((aligned(16))) float buf[2][PP_SCAN_FLOATS + PP_SCAN_PAD];
+  constexpr int PER = PP_SCAN_FLOATS / PP_SCAN_THREADS, PER_OFF = PP_SCAN_PAD / PP_SCAN_THREADS;
+  const int S = a.S, SS = S * S, SP = S | 1, tid = threadIdx.x, lane = tid & (QT_WAVE - 1);
+  const bool chain = tid < QT_WAVE;   // wave 0
+  const int K = pp_scan_trip_tiles(S), jj = min(lane, S - 1), b = blockIdx.x, tiles = a.tiles;
+  const float* __restrict__ prod = a.products + (long long)b * tiles * SS;
+  const double* __restrict__ poff = a.offsets + (long long)b * tiles * S;
+  float* __restrict__ starts = a.starts + (long long)b * tiles * S;
+  float* __restrict__ ends = a.ends + (long long)b * tiles * S;
+  double* __restrict__ before = a.before + (long long)b * tiles;
+  float r[PER];
+  double ro[PER_OFF];
+  auto fetch = [&](int t0, int kt) {   // products t0 .. t0 + kt - 1 and their offsets into registers
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int idx = tid + u * PP_SCAN_THREADS;
+      r[u] = idx < kt * SS ? prod[(long long)t0 * SS + idx] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < PER_OFF; ++u) {
+      const int idx = tid + u * PP_SCAN_THREADS;
+      ro[u] = idx < kt * S ? poff[(long long)t0 * S + idx] : 0.0;
+    }
+  };
+  auto put = [&](int which, int kt) {   // rows padded to S | 1
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int idx = tid + u * PP_SCAN_THREADS;
+      if (idx < kt * SS) {
+        const int row = (int)fdiv((unsigned)idx, a.div_s);
+        buf[which][row * SP + (idx - row * S)] = r[u];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PER_OFF; ++u) {
+      const int idx = tid + u * PP_SCAN_THREADS;
+      if (idx < kt * S) offs[which][idx] = ro[u];
+    }
+  };
+  float reg[16];
+
+  // forward: the products of tiles 0 .. tiles - 2 give the starts of tiles 1 .. tiles - 1
+  const int count = tiles - 1;
+  float v = 0.0f;
+  double ev = 0.0;
+  if (chain) {
+    v = pp_stream_start(a, b, jj);
+    if (lane < S) starts[lane] = v;
+    if (lane == 0) before[0] = 0.0;
+  }
+  fetch(0, min(K, count));
+  put(0, min(K, count));
+  __syncthreads();
+  int which = 0;
+  for (int t0 = 0; t0 < count; t0 += K) {
+    const int kt = min(K, count - t0), kn = min(K, count - (t0 + K));
+    if (kn > 0) fetch(t0 + K, kn);
+    if (chain) {
+      for (int u = 0; u < kt; ++u) {
+        const float* __restrict__ P = buf[which] + u * S * SP;
+        const double w = (double)v + offs[which][u * S + jj];
+        const double W = pp_max_states<SMALL>(w, S);
+        const float wf = (float)(w - W);
+        if (SMALL) pp_load16(reg, P + jj, SP, S);
+        const float A = pp_step<SMALL>(wf, reg, P + jj, SP, S);
+        float m, lg;
+        double c;
+        pp_L_states<SMALL>(A, S, lane < S, m, lg, c);
+        v = (A - m) - lg;
+        ev += W + c;
+        if (lane < S) starts[(long long)(t0 + u + 1) * S + lane] = v;
+        if (lane == 0) before[t0 + u + 1] = ev;
+      }
+    }
+    if (kn > 0) put(which ^ 1, kn);
+    __syncthreads();
+    which ^= 1;
+  }
+
+  // backward: the products of tiles tiles - 1 .. 1 give the ends of tiles tiles - 2 .. 0
+  float bv = 0.0f;
+  if (chain && lane < S) ends[(long long)(tiles - 1) * S + lane] = 0.0f;
+  {
+    const int lo = max(tiles - K, 1);
+    fetch(lo, tiles - lo);
+    put(which, tiles - lo);
+  }
+  __syncthreads();
+  for (int hi = tiles - 1; hi >= 1; hi -= K) {   // this trip: tiles lo .. hi
+    const int lo = max(hi - K + 1, 1), nhi = lo - 1, nlo = max(nhi - K + 1, 1);
+    if (nhi >= 1) fetch(nlo, nhi - nlo + 1);
+    if (chain) {
+      for (int t = hi; t >= lo; --t) {
+        const float* __restrict__ P = buf[which] + (t - lo) * S * SP;
+        if (SMALL) pp_load16(reg, P + jj * SP, 1, S);
+        const float B = pp_step<SMALL>(bv, reg, P + jj * SP, 1, S);
+        const double Bd = offs[which][(t - lo) * S + jj] + (double)B;
+        bv = (float)(Bd - pp_max_states<SMALL>(Bd, S));
+        if (lane < S) ends[(long long)(t - 1) * S + lane] = bv;
+      }
+    }
+    if (nhi >= 1) put(which ^ 1, nhi - nlo + 1);
+    __syncthreads();
+    which ^= 1;
+  }
+}
+
+// ---- (c) replay ----------------------------------------------------------------------------------------------------------------
+template <bool SMALL>
+__global__ __launch_bounds__(QT_WAVE) void pp_replay_kernel(PpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float pp_lds[];
+  const PpLds l = pp_carve(pp_lds, a.S);
+  const int lane = threadIdx.x, S = a.S, SP = S | 1, jj = min(lane, S - 1);
+  const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
+  const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+  const bool last = tile == a.tiles - 1;
+  pp_stage_table(a, l);
+  pp_stage_emissions(a, b, f0, n, l.e);
+  float av = a.starts[((long long)b * a.tiles + tile) * S + jj];
+  const float bv = a.ends[((long long)b * a.tiles + tile) * S + jj];
+  __syncthreads();
+  float col[16], row[16];
+  if (SMALL) {
+    pp_load16(col, l.t + jj, SP, S);
+    pp_load16(row, l.t + jj * SP, 1, S);
+  }
+  double call = a.before[(long long)b * a.tiles + tile], unused = 0.0;
+  pp_forward<SMALL>(a, l, col, b, f0, n, lane, av, unused, call);
+  if (last) {
+    const double seen = a.carry[(long long)b * (S + 2)], total = a.carry[(long long)b * (S + 2) + 1];
+    pp_write_carry(a, b, lane, av, seen, total + call, call);
+  }
+  __syncthreads();
+  pp_backward<SMALL>(a, l, row, b, f0, n, lane, bv, last);
+  __syncthreads();
+  pp_classes(a, l, b, f0, n);
+}
+
+inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+inline bool overlap(const void* p, size_t pbytes, const void* q, size_t qbytes) {
+  if (!p || !q || !pbytes || !qbytes) return false;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + qbytes && b < a + pbytes;
+}
+
+int check_desc(const char* who, const qt_pose_order_desc* d) {
+  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  QT_CHECK_ARG(d->batch >= 1, "%s: batch must be positive (got %d)", who, d->batch);
+  QT_CHECK_ARG(d->frames >= 1, "%s: frames must be positive (got %d)", who, d->frames);
+  QT_CHECK_ARG(d->num_classes >= 1 && d->num_classes <= PP_MAX_C, "%s: num_classes = %d; 1 .. %d are handled", who,
+               d->num_classes, PP_MAX_C);
+  QT_CHECK_ARG(d->num_states >= 1 && d->num_states <= PP_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who, d->num_states,
+               PP_MAX_S);
+  const long long frames = (long long)d->batch * d->frames;
+  if (frames > PP_MAX_FRAMES) {
+    qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, frames, PP_MAX_FRAMES);
+    return QT_ERR_UNSUPPORTED;
+  }
+  return QT_OK;
+}
+
+// the workspace of the tiled route, the doubles first
+struct PpLayout {
+  long long offsets, before, products, starts, ends, total;
+};
+PpLayout pp_layout(const qt_pose_order_desc* d) {
+  PpLayout w = {0, 0, 0, 0, 0, 0};
+  if (d->frames <= PP_TILE) return w;
+  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PP_TILE);
+  w.offsets = 0;
+  w.before = w.offsets + B * tiles * S * 8;
+  w.products = w.before + B * tiles * 8;
+  w.starts = w.products + B * tiles * S * S * 4;
+  w.ends = w.starts + B * tiles * S * 4;
+  w.total = w.ends + B * tiles * S * 4;
+  return w;
+}
+
+}  // namespace
+
+extern "C" long long qt_pose_posterior_workspace_bytes(const qt_pose_order_desc* desc) {
+  if (check_desc("qt_pose_posterior_workspace_bytes", desc) != QT_OK) return 0;
+  return pp_layout(desc).total;
+}
+
+extern "C" int qt_pose_posterior(const qt_pose_order_desc* desc, const float* probs, long long ld, const int* state_class,
+                                 const int* trans, const int* init, double* carry, float* posterior, float* filtered,
+                                 float* class_posterior, double* log2_evidence, void* workspace, long long workspace_bytes,
+                                 void* stream) {
+  const char* const who = "qt_pose_posterior";
+  if (const int rc = check_desc(who, desc)) return rc;
+  const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states;
+  QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
+  QT_CHECK_ARG(probs != nullptr && state_class != nullptr && trans != nullptr && carry != nullptr && posterior != nullptr,
+               "%s: null %s", who,
+               !probs ? "probs" : !state_class ? "state_class" : !trans ? "trans" : !carry ? "carry" : "posterior");
+  QT_CHECK_ARG(!misaligned(probs, 3) && !misaligned(state_class, 3) && !misaligned(trans, 3) && !misaligned(init, 3) &&
+                   !misaligned(posterior, 3) && !misaligned(filtered, 3) && !misaligned(class_posterior, 3) &&
+                   !misaligned(carry, 7) && !misaligned(log2_evidence, 7) && !misaligned(workspace, 7),
+               "%s: probs, state_class, trans, init, posterior, filtered and class_posterior must be 4-byte aligned, carry, "
+               "log2_evidence and the workspace 8-byte", who);
+  const PpLayout w = pp_layout(desc);
+  QT_CHECK_ARG(w.total == 0 || (workspace != nullptr && workspace_bytes >= w.total),
+               "%s: workspace of %lld bytes; qt_pose_posterior_workspace_bytes asks for %lld", who,
+               workspace ? workspace_bytes : 0LL, w.total);
+  const long long rows = (long long)B * T;
+  const struct { const void* p; size_t bytes; const char* name; } in[] = {
+      {probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
+      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}},
+    out[] = {{carry, (size_t)B * (S + 2) * 8, "carry"}, {posterior, (size_t)rows * S * 4, "posterior"},
+             {filtered, (size_t)rows * S * 4, "filtered"}, {class_posterior, (size_t)rows * C * 4, "class_posterior"},
+             {log2_evidence, (size_t)B * 8, "log2_evidence"}, {workspace, (size_t)w.total, "workspace"}};
+  for (const auto& o : out) {
+    for (const auto& i : in)
+      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
+    for (const auto& o2 : out)
+      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
+  }
+
+  PpArgs a;
+  a.probs = probs;
+  a.state_class = state_class;
+  a.trans = trans;
+  a.init = init;
+  a.carry = carry;
+  a.posterior = posterior;
+  a.filtered = filtered;
+  a.class_posterior = class_posterior;
+  a.evidence = log2_evidence;
+  char* ws = static_cast<char*>(workspace);
+  a.offsets = reinterpret_cast<double*>(ws + w.offsets);
+  a.before = reinterpret_cast<double*>(ws + w.before);
+  a.products = reinterpret_cast<float*>(ws + w.products);
+  a.starts = reinterpret_cast<float*>(ws + w.starts);
+  a.ends = reinterpret_cast<float*>(ws + w.ends);
+  a.ld = ld;
+  a.T = T;
+  a.tiles = qt_cdiv(T, PP_TILE);
+  a.C = C;
+  a.S = S;
+  a.div_s = make_fastdiv((unsigned)S);
+  a.div_c = make_fastdiv((unsigned)C);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool small = S <= 16;
+  const size_t wave_lds = pp_wave_lds_bytes(S);
+  const bool one_wave = a.tiles > 1 && qt_env_int("QTCNN_POSE_POSTERIOR", 0) == 1;   // per call: see the head of the file
+  if (a.tiles == 1 || one_wave) {
+    if (small) hipLaunchKernelGGL(pp_stream_kernel<true>, dim3((unsigned)B), dim3(QT_WAVE), wave_lds, s, a);
+    else hipLaunchKernelGGL(pp_stream_kernel<false>, dim3((unsigned)B), dim3(QT_WAVE), wave_lds, s, a);
+    QT_CHECK_LAUNCH();
+    return QT_OK;
+  }
+  const unsigned all = (unsigned)((long long)B * a.tiles);
+  const size_t prod_lds = 4 * (2 * PP_MAX_S + 3 * (size_t)S * S) + 2 * PP_TILE * S;
+  if (small) hipLaunchKernelGGL(pp_products_kernel<true>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
+  else hipLaunchKernelGGL(pp_products_kernel<false>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
+  QT_CHECK_LAUNCH();
+  if (small) hipLaunchKernelGGL(pp_scan_kernel<true>, dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(pp_scan_kernel<false>, dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
+  QT_CHECK_LAUNCH();
+  if (small) hipLaunchKernelGGL(pp_replay_kernel<true>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
+  else hipLaunchKernelGGL(pp_replay_kernel<false>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
+  QT_CHECK_LAUNCH();
+  return QT_OK;
+}

@@ -6,11 +6,13 @@ step may follow which.  The reference has no such step.  In the video loop it si
 
     state_class, trans = cyclic_prior(step_classes, stay=prob_score(0.9), advance=prob_score(0.1))
     decoder = PoseOrderDecoder(state_class, trans, device, class_names=class_names)
+    posterior = PosePosterior(state_class, trans, device, class_names=class_names)
     for frames, landmarks, detected in video:                       # chunks of any length
         probs, _, _ = predict(model(pre(frames), pose(landmarks, detected)))
-        pred, confidence, stable, rows = timeline.update(probs, smoothed=True)
+        pred, _, stable, rows = timeline.update(probs, smoothed=True)
         path, path_class = decoder.decode(rows)                     # nothing read back
         rounds += decoder.cycles(path)                              # int64 [streams], on the device
+        confidence = posterior.confidence(posterior.smooth(rows), path)   # how sure the chain is of the step it drew
         out = annotator.draw(frames, landmarks, detected, path_class, confidence)
 
 Scores are integers: an emission is log2 p in units of 1/256 bit, read off the float's bit pattern (`prob_score` is the same
@@ -21,9 +23,16 @@ Calls of up to TILE = 64 frames are one launch of one wave per stream; longer ca
 are formed in parallel (five launches, seven above 32 tiles; a workspace that grows on demand).  Limits: S <= 64 states,
 C <= 64 classes, 2^20 frames per call.
 
-Not built: forward-backward posteriors, learning `trans` from labelled videos, fixed-lag revision of earlier calls' paths, true
-minus-infinity (forbidden) transitions, S > 64, bf16 probabilities.  There is no torch fallback: CPU tensors and other dtypes
-raise QtError.
+PosePosterior (csrc/pose_posterior.hip) gives the marginals of the same chain: posterior[f][j], the probability of step j at
+frame f given every frame up to the end of the call (forward-backward), filtered[f][j] given the frames up to f alone, the
+posterior summed by class on request, and the evidence in bits.  The rule is in log2 (an all -65536 table would underflow any scaled
+probability), every sum runs in a fixed order, and whatever grows with the frame count is a double.  Calls of up to 64 frames are
+one launch, and there a split into calls changes no bit of filtered, of the evidence total or of the carry; longer calls go
+through tile products in the (L, +) semiring (three launches) and differ from the frame-by-frame rule by f32 rounding.
+
+Not built: pairwise posteriors xi and learning `trans` from labelled videos (Baum-Welch), fixed-lag revision of earlier calls'
+paths and fixed-lag smoothing across calls, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second
+level of the posterior's scan.  There is no torch fallback: CPU tensors and other dtypes raise QtError.
 """
 import ctypes
 
@@ -65,7 +74,7 @@ class PoseOrderDesc(ctypes.Structure):   # qt_pose_order_desc
 
 
 def bind(L):
-    """argtypes of the two entry points (idempotent)"""
+    """argtypes of the entry points (idempotent)"""
     if getattr(L, "_pose_order_bound", False):
         return L
     L.qt_pose_order_workspace_bytes.argtypes = [ctypes.POINTER(PoseOrderDesc)]
@@ -73,6 +82,11 @@ def bind(L):
     L.qt_pose_order_decode.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
         [ctypes.c_void_p] * 8 + [ctypes.c_longlong, ctypes.c_void_p]
     L.qt_pose_order_decode.restype = ctypes.c_int
+    L.qt_pose_posterior_workspace_bytes.argtypes = [ctypes.POINTER(PoseOrderDesc)]
+    L.qt_pose_posterior_workspace_bytes.restype = ctypes.c_longlong
+    L.qt_pose_posterior.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 9 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_posterior.restype = ctypes.c_int
     L._pose_order_bound = True
     return L
 
@@ -81,6 +95,13 @@ def scan_trip_tiles(num_states):
     """products the tiled route's scan stages at a time (16 KB of LDS, at most 16): a call of more than
     (scan_trip_tiles + 1) * TILE frames makes it stage more than once"""
     return max(1, min(16, 4096 // (num_states * num_states)))
+
+
+def posterior_scan_trip_tiles(num_states):
+    """products the posterior's scan (csrc/pose_posterior.hip) stages at a time, the decoder's figure: its forward sweep goes
+    through tiles - 1 products and so does its backward sweep, so a call of more than (posterior_scan_trip_tiles + 1) * TILE
+    frames makes both stage more than once"""
+    return scan_trip_tiles(num_states)
 
 
 def prob_score(p):
@@ -132,27 +153,8 @@ class PoseOrderDecoder:
     `decode` and `cycles` launch kernels and read nothing back.  See the module text."""
 
     def __init__(self, state_class, trans, device, streams=1, init=None, class_names=None):
-        sc = np.asarray(state_class)
-        if sc.ndim != 1 or not 1 <= sc.shape[0] <= MAX_STATES or sc.dtype.kind not in "iu":
-            raise ValueError(f"PoseOrderDecoder: state_class must be 1 .. {MAX_STATES} integers (got shape {sc.shape}, {sc.dtype})")
+        sc, tr, init, class_names = _check_tables("PoseOrderDecoder", state_class, trans, init, streams, class_names)
         S = int(sc.shape[0])
-        if (sc < 0).any() or (sc >= MAX_CLASSES).any():
-            raise ValueError(f"PoseOrderDecoder: state_class holds a class outside 0 .. {MAX_CLASSES - 1}")
-        tr = np.asarray(trans)
-        if tr.shape != (S, S) or tr.dtype.kind not in "iu":
-            raise ValueError(f"PoseOrderDecoder: trans must be [{S}, {S}] integers (got shape {tr.shape}, {tr.dtype})")
-        if (tr < TRANS_FLOOR).any() or (tr > 0).any():
-            raise ValueError(f"PoseOrderDecoder: trans holds a score outside {TRANS_FLOOR} .. 0")
-        if init is not None:
-            init = np.asarray(init)
-            if init.shape != (S,) or init.dtype.kind not in "iu" or (init < TRANS_FLOOR).any() or (init > 0).any():
-                raise ValueError(f"PoseOrderDecoder: init must be [{S}] integers in {TRANS_FLOOR} .. 0")
-        if isinstance(streams, bool) or not isinstance(streams, int) or not 1 <= streams <= MAX_FRAMES:
-            raise ValueError(f"PoseOrderDecoder: streams must be an integer in 1 .. {MAX_FRAMES} (got {streams!r})")
-        if class_names is not None:
-            class_names = [str(c) for c in class_names]
-            if len(class_names) <= int(sc.max()):
-                raise ValueError(f"PoseOrderDecoder: {len(class_names)} class names, but a state emits class {int(sc.max())}")
         self.class_names = class_names
         self.num_states, self.streams = S, streams
         device = torch.device(device)
@@ -241,3 +243,110 @@ class PoseOrderDecoder:
             raise QtError(f"PoseOrderDecoder.cycles: path must be [{B}, frames] (got {list(path.shape)})")
         before = torch.cat([self._before[:, None], path[:, :-1]], dim=1)
         return ((before == wrap_from) & (path == wrap_to)).sum(dim=1)
+
+
+def _check_tables(who, state_class, trans, init, streams, class_names):
+    """the argument checks that PoseOrderDecoder makes, for a second owner of the same tables"""
+    sc = np.asarray(state_class)
+    if sc.ndim != 1 or not 1 <= sc.shape[0] <= MAX_STATES or sc.dtype.kind not in "iu":
+        raise ValueError(f"{who}: state_class must be 1 .. {MAX_STATES} integers (got shape {sc.shape}, {sc.dtype})")
+    S = int(sc.shape[0])
+    if (sc < 0).any() or (sc >= MAX_CLASSES).any():
+        raise ValueError(f"{who}: state_class holds a class outside 0 .. {MAX_CLASSES - 1}")
+    tr = np.asarray(trans)
+    if tr.shape != (S, S) or tr.dtype.kind not in "iu":
+        raise ValueError(f"{who}: trans must be [{S}, {S}] integers (got shape {tr.shape}, {tr.dtype})")
+    if (tr < TRANS_FLOOR).any() or (tr > 0).any():
+        raise ValueError(f"{who}: trans holds a score outside {TRANS_FLOOR} .. 0")
+    if init is not None:
+        init = np.asarray(init)
+        if init.shape != (S,) or init.dtype.kind not in "iu" or (init < TRANS_FLOOR).any() or (init > 0).any():
+            raise ValueError(f"{who}: init must be [{S}] integers in {TRANS_FLOOR} .. 0")
+    if isinstance(streams, bool) or not isinstance(streams, int) or not 1 <= streams <= MAX_FRAMES:
+        raise ValueError(f"{who}: streams must be an integer in 1 .. {MAX_FRAMES} (got {streams!r})")
+    if class_names is not None:
+        class_names = [str(c) for c in class_names]
+        if len(class_names) <= int(sc.max()):
+            raise ValueError(f"{who}: {len(class_names)} class names, but a state emits class {int(sc.max())}")
+    return sc, tr, init, class_names
+
+
+class PosePosterior:
+    """The posterior marginals of `streams` videos over the decoder's chain: the tables, the carry float64 [streams, S + 2] =
+    (frames_seen, evidence_total in bits, a_last[S]) and a workspace that grows on demand, all in device memory.  `smooth`
+    launches kernels and reads nothing back.  See the module text."""
+
+    def __init__(self, state_class, trans, device, streams=1, init=None, class_names=None):
+        sc, tr, init, self.class_names = _check_tables("PosePosterior", state_class, trans, init, streams, class_names)
+        self.num_states, self.streams = int(sc.shape[0]), streams
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise QtError("PosePosterior lives on an AMD GPU (device must be cuda:N); no CPU fallback")
+        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
+        self.trans = torch.from_numpy(np.ascontiguousarray(tr, np.int32)).to(device)
+        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
+        self.carry = torch.zeros(streams, self.num_states + 2, dtype=torch.float64, device=device)
+        self._workspace = None
+        self.device = self.carry.device
+
+    def reset(self):
+        """every stream starts anew (no host sync)"""
+        self.carry.zero_()
+        return self
+
+    def smooth(self, probs, filtered=False, by_class=False, evidence=False):
+        """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device: predict's
+        probabilities or the timeline's smoothed rows.  Returns posterior f32 [streams, frames, S] (or [frames, S]): the
+        probability of every step at every frame given all frames up to the end of this call; then, as asked and in this order,
+        filtered f32 of the same shape (given the frames up to each one alone), the class posterior f32 [..., C] and the
+        call's evidence in bits, float64 [streams].  A tuple when anything beyond the posterior is asked for."""
+        what = "PosePosterior.smooth"
+        if not isinstance(probs, torch.Tensor):
+            raise QtError(f"{what}: probs must be a tensor")
+        if probs.device.type != "cuda" or probs.device != self.device:
+            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
+        if probs.dtype != torch.float32:
+            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+        B, S = self.streams, self.num_states
+        flat = probs.dim() == 2
+        if flat and B == 1:
+            probs = probs.unsqueeze(0)
+        if probs.dim() != 3 or probs.shape[0] != B or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
+            raise QtError(f"{what}: probs must be [{B}, frames, C]{' or [frames, C]' if B == 1 else ''} with frames >= 1 and "
+                          f"C <= {MAX_CLASSES} (got {list(probs.shape)})")
+        T, C = probs.shape[1], probs.shape[2]
+        if B * T > MAX_FRAMES:
+            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+        probs = probs.detach()
+        if probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1)):
+            probs = probs.contiguous()
+        lead = (T,) if flat else (B, T)
+        dev = self.device
+        post = torch.empty(lead + (S,), dtype=torch.float32, device=dev)
+        filt = torch.empty(lead + (S,), dtype=torch.float32, device=dev) if filtered else None
+        cls = torch.empty(lead + (C,), dtype=torch.float32, device=dev) if by_class else None
+        ev = torch.empty(B, dtype=torch.float64, device=dev) if evidence else None
+        desc = PoseOrderDesc(B, T, C, S)
+        L = bind(_lib.lib())
+        need = int(L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc)))
+        if need and (self._workspace is None or self._workspace.numel() < need):
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.qt_pose_posterior(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
+                                           _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.carry), _lib.ptr(post),
+                                           _lib.ptr(filt), _lib.ptr(cls), _lib.ptr(ev), _lib.ptr(self._workspace) if need else None,
+                                           self._workspace.numel() if need else 0, _lib.stream_ptr()), "qt_pose_posterior")
+        out = (post,) + tuple(t for t in (filt, cls, ev) if t is not None)
+        return out[0] if len(out) == 1 else out
+
+    def confidence(self, posterior, path):
+        """f32 [streams, frames] (or [frames]): the posterior at the states of `path` (a decode's, int64), which is what
+        FrameAnnotator.draw takes as `confidence` beside the path's class.  Plain torch, nothing read back."""
+        if not isinstance(posterior, torch.Tensor) or posterior.device != self.device or posterior.dtype != torch.float32:
+            raise QtError(f"PosePosterior.confidence: posterior must be an f32 tensor on {self.device}")
+        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
+            raise QtError(f"PosePosterior.confidence: path must be an int64 tensor on {self.device}")
+        if posterior.shape[:-1] != path.shape or posterior.shape[-1] != self.num_states:
+            raise QtError(f"PosePosterior.confidence: posterior {list(posterior.shape)} and path {list(path.shape)} do not "
+                          f"belong together ({self.num_states} states)")
+        return posterior.gather(-1, path.unsqueeze(-1)).squeeze(-1)
