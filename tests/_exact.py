@@ -11,7 +11,15 @@ integer residual give multiples of 0.5 far below 2^24.
   mode A ("representable"): the float64 reference is itself representable in the output type: expected = ref.
   mode B ("rounded", bf16 outputs only): larger magnitudes; the f32 value is still exact and many values sit on a bf16 tie:
   expected = ref.to(bfloat16), one round-to-nearest-even of an exactly known value.
-conditions() asserts all of it on the reference alone, before a kernel result is looked at."""
+conditions() asserts all of it on the reference alone, before a kernel result is looked at.
+
+The rows cover: every 2-D convolution path forward, data gradient and weight gradient (generic tiles, ring, patch-resident,
+stride-2 pair and parity classes, region rows), the packed stem and its gradients, the thin GEMMs, and the 3-D convolutions
+of the clip models.  Rows with a field `walk` = n are shapes at which a persistent kernel's capped grid gives EVERY workgroup
+at least n work items (item, item + grid, ...): the state that survives from one item to the next -- the LDS ring of frame
+slabs, the register prefetch of the next item's first slab or tile, the per-workgroup statistics rows and partial filters --
+is then part of the result.  The GPU test asserts that precondition from the grid the library reports; walk_items() is the
+same walk on the host for the CPU twin."""
 
 import torch
 import torch.nn.functional as F
@@ -349,7 +357,11 @@ LINEAR_ROWS = [
 
 
 # qt_stem_dgrad (f32 image gradient from a bf16 / f32 gradient map) and the packed-stem weight gradient
-STEMD_ROWS = [_r("stem_dgrad", (1, 3, 64, 224, 7, 2, 3), BOTH, "A", 1 / 8, 901)]
+STEMD_ROWS = [
+    _r("stem_dgrad", (1, 3, 64, 224, 7, 2, 3), BOTH, "A", 1 / 8, 901),
+    # 11 images: 539 tiles (bf16) / 1078 tiles (f32) on the persistent grid of 256: 2-3 and 4-5 tiles per workgroup
+    _r("stem_dgrad_walk", (11, 3, 64, 224, 7, 2, 3), BOTH, "A", 1 / 8, 903, walk=2),
+]
 STEMW_ROWS = [_r("stem_wgrad", (1, 3, 64, 224, 7, 2, 3), BOTH, "A", None, 902, keep=0.1)]
 
 # 3-D convolutions of the clip models (bf16 kernels): cfg = (B, T, H, W); `only`: the parts of the row a shape admits
@@ -359,6 +371,9 @@ C3F_ROWS = [   # qt_conv3d_first_*: 3 -> 32 channels from the f32 clip
     _r("first_w32", (2, 2, 8, 32), (BF,), "A", 1 / 2, 913, keep=0.8, only=("fwd", "dgrad", "wgrad", "fused")),
     _r("first_rounded", (2, 3, 8, 32), (BF,), "B", 1.0, 914, xmag=32, xkeep=1.0, zero_block=(2, 6), only=("fwd",)),
     _r("first_dgrad_general", (1, 2, 6, 20), BOTH, "A", 1 / 2, 915, keep=1.0, only=("dgrad",)),   # the direct kernel
+    # 3 x 344 = 1032 (clip, 4-row slab) items on a grid capped at 2 x CUs = 512: every workgroup walks 2 items, eight walk 3,
+    # and consecutive items of a workgroup lie in different clips.  keep: see c32_walk
+    _r("first_walk", (3, 2, 1376, 32), (BF,), "A", 1 / 2, 916, keep=0.004, only=("fwd", "dgrad", "wgrad", "fused"), walk=2),
 ]
 C32_ROWS = [   # qt_conv3d_c32_*: 32 -> 64 channels on frame slabs; xc = channels per input row (32, or 64 with padding)
     _r("c32_t1_w16", (3, 1, 8, 16), (BF,), "A", 1 / 8, 921, keep=1.0, xc=64, only=("fwd", "dgrad")),   # T = 1, smallest w
@@ -366,6 +381,12 @@ C32_ROWS = [   # qt_conv3d_c32_*: 32 -> 64 channels on frame slabs; xc = channel
     _r("c32_w128", (1, 2, 8, 128), (BF,), "A", 1 / 8, 922, keep=0.4, xc=64, only=("fwd", "dgrad", "wgrad")),
     _r("c32_xc32", (1, 5, 12, 64), (BF,), "A", 1 / 8, 923, keep=0.2, xc=32, only=("fwd", "dgrad", "wgrad")),
     _r("c32_rounded", (1, 5, 12, 64), (BF,), "B", 1.0, 924, xc=32, zero_block=(2, 8), only=("fwd",), **B_KW),
+    # (clip, 2-row slab) items on a grid capped at the CU count (256): 516 items = 2-3 per workgroup; 780 items = 3-4 per
+    # workgroup with odd T (the ring slot of an item's last frame is not the one the next item starts in).  The small `keep`:
+    # a weight gradient contracted over 10^5 positions has almost no exact zeros unless dy is thin; every work item still
+    # holds a non-zero dy
+    _r("c32_walk", (3, 2, 344, 16), (BF,), "A", 1 / 8, 925, keep=0.01, xc=32, only=("fwd", "dgrad", "wgrad"), walk=2),
+    _r("c32_walk3", (5, 3, 312, 16), (BF,), "A", 1 / 8, 926, keep=0.01, xc=64, only=("fwd", "dgrad", "wgrad"), walk=2),
 ]
 
 
@@ -458,6 +479,14 @@ def c3_conditions(c, dt, part):
         conditions(c["dx"], c["adx"], dt, "A", w=c["wt"], acts=[c["dyf"]])
     else:
         conditions(c["dw"], c["adw"], F32, "A", acts=[c["x1"], c["dy"]])
+
+
+def walk_items(items, cap):
+    """the walk of a persistent kernel on the host: grid = min(items, cap) workgroups, workgroup k takes items k, k + grid, ...
+    Returns (grid, workgroup of every item, trip of every item: 0 for a workgroup's first item, 1 for its second, ...)"""
+    grid = min(items, cap)
+    i = torch.arange(items)
+    return grid, i % grid, i // grid
 
 
 def ids(rows):

@@ -2,7 +2,8 @@
 (/root/reference/3dcnn/models.py:96-214) and Ji3DCNN (/root/reference/cnn+lstm/models.py:93-142) on the HIP kernels.
 
 * op level through the C ABI: MaxPool3d (1,2,2) / (2,2,2) forward + backward, BatchNorm3d statistics, the 27-tap clip
-  packing, AdaptiveAvgPool3d -- against torch CPU;
+  packing, AdaptiveAvgPool3d -- against torch CPU; the persistent conv kernels at shapes where every workgroup walks several
+  items against the same kernels clip by clip (bit for bit);
 * whole models against the vectors the reference classes produced (tests/golden/clip3d.npz): eval logits + block outputs,
   a dropout-free train step (loss, every gradient, running statistics); f32 build: logits <= 1e-3, head / LSTM gradients
   <= 1e-3, conv gradients by the ReLU-flip-aware rule of tests/test_model_gpu.py; bf16 build: stated loose bounds;
@@ -19,6 +20,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _bounds import sum_bound
 from _util import PKG, ROOT, check_summary, pkg, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -441,6 +443,146 @@ def test_second_conv3d_with_frame_slabs_in_lds(cfg):
     assert lib.qt_conv3d_c32_fwd(L.QT_F32, L.ptr(xd), xc, L.ptr(wp), L.ptr(y), None, None, 0, None, B, T, H, W, L.stream_ptr()) == -3
     assert lib.qt_conv3d_c32_stats_rows(B, T, H, W + 8) == 0 and lib.qt_conv3d_c32_stats_rows(B, T, H + 1, W) == 0
     assert lib.qt_conv3d_c32_stats_rows(B, T, H, 144) == 0
+
+
+def _stats_agree(whole, parts, ref, absref, K, what):
+    """BatchNorm partial rows of one launch over the batch against those of one launch per clip: both add the same f32
+    accumulators v (n per channel), in different orders and groupings.  Each total is within sum_bound(n, sum |v|) of the
+    true sum (sum_bound(n + 1, sum v^2) for the squares: one more rounding for the product), so the two differ by at most
+    twice that.  |v| itself is bounded from the float64 reference: |v| <= |ref| + e, e = sum_bound(K, sum of the K |products|)
+    (ref / absref: the float64 convolution of the operands / of their absolute values).  The whole-batch totals are also held
+    against the reference's, with the movement of v added.  Nothing here comes from what a kernel returns."""
+    e = sum_bound(K, absref)                                                  # [B][C][T][H][W], float64: |v - ref| <= e
+    vmax = ref.abs() + e
+    n = vmax.numel() // vmax.shape[1]
+    dims = (0, 2, 3, 4)
+    one = torch.stack([sum_bound(n, vmax.sum(dims)), sum_bound(n + 1, (vmax * vmax).sum(dims))])   # one launch against sum v
+    a = whole.double().sum(0).cpu()
+    b = sum(p.double().sum(0) for p in parts).cpu()
+    C = one.shape[1]
+    assert bool((a[:, C:] == 0).all()) and bool((b[:, C:] == 0).all())
+    err = (a[:, :C] - b[:, :C]).abs()
+    assert bool((err <= 2 * one).all()), (what, float((err / (2 * one)).max()))
+    # and they are the sums of the map: sum v against the reference's totals moves by sum e, sum v^2 by sum (2 |ref| + e) e
+    want = torch.stack([ref.sum(dims), (ref * ref).sum(dims)])
+    ref_bound = one + torch.stack([e.sum(dims), ((2 * ref.abs() + e) * e).sum(dims)])
+    err = (a[:, :C] - want).abs()
+    assert bool((err <= ref_bound).all()), (what, "against the reference", float((err / ref_bound).max()))
+
+
+@pytest.mark.parametrize("block,cfg", [("first", (3, 2, 1376, 32)), ("c32", (3, 2, 344, 16))], ids=["first", "c32"])
+def test_walking_several_items_per_workgroup_changes_no_result(block, cfg):
+    """The persistent 3-D convolution kernels on thin, tall maps whose (clip, slab) items exceed the capped grid (1032 items on
+    2 x CUs workgroups, 516 on CUs), once over the whole batch -- every workgroup walks two or more items -- and once clip by
+    clip -- 344 / 172 items, one per workgroup; both preconditions are asserted from the grid the library reports.  Per-position
+    arithmetic does not depend on the walk: every output must be the same BIT FOR BIT.  The statistics rows are f32 sums in
+    another grouping: they agree to the derived summation bound (_stats_agree).  Random bf16 operands as in the two tests
+    above (the integer grids of tests/test_conv_exact_gpu.py prove the data movement of the same shapes; weight gradients,
+    where the order of summation is the result, are left to them)."""
+    dev = _dev()
+    L = pkg("_lib")
+    lib = L.lib()
+    B, T, H, W = cfg
+    dt = torch.bfloat16
+    qdt, st = L.qt_dtype(dt), L.stream_ptr()
+    g = torch.Generator().manual_seed(23)
+    first = block == "first"
+    R = 4 if first else 2
+    rows_of = lib.qt_conv3d_first_stats_rows if first else lib.qt_conv3d_c32_stats_rows
+    rows, rows1 = rows_of(B, T, H, W), rows_of(1, T, H, W)
+    # (qt_conv3d_first_dgrad launches by the same rule as the forward -- at most 2 x CUs workgroups over the same items at one
+    # column tile per row, W <= 112 -- so the forward's row count is its grid too)
+    assert rows > 0 and B * (H // R) >= 2 * rows + 1, ("the whole batch does not walk", B * (H // R), rows)
+    assert rows1 == H // R, ("a single clip walks", H // R, rows1)
+    nan = lambda *shape, dtype=dt: torch.full(shape, float("nan"), dtype=dtype, device=dev)
+
+    def both(run):
+        """run(b0, nb) -> tuple of device tensors with the clip axis at `axis`; whole batch, then clip by clip"""
+        whole = run(0, B)
+        torch.cuda.synchronize()
+        clips = [run(b, 1) for b in range(B)]
+        torch.cuda.synchronize()
+        return whole, clips
+
+    def same_bits(whole, clips, axis, what):
+        assert bool(torch.isfinite(whole.float()).all()), what
+        for b, part in enumerate(clips):
+            assert torch.equal(whole.narrow(axis, b, 1), part), (what, "clip", b)
+
+    if first:
+        clip = torch.randn(B, T, 3, H, W, generator=g)
+        w = torch.randn(32, 3, 3, 3, 3, generator=g) * (2.0 / 81) ** 0.5
+        xr, wr = clip.to(dt).double().permute(0, 2, 1, 3, 4), w.to(dt).double()
+        ref, absref = F.conv3d(xr, wr, None, 1, 1), F.conv3d(xr.abs(), wr.abs(), None, 1, 1)
+        wp = torch.zeros(64, 128)
+        wp[:32, :81] = w.permute(0, 2, 3, 4, 1).reshape(32, 81)
+        wp, cd = wp.to(dev, dt), clip.to(dev)
+        sc, sh = (torch.rand(32, generator=g) + 0.5).to(dev), (torch.randn(32, generator=g) * 0.3).to(dev)
+        dyd = torch.randn(T, B, H, W, 32, generator=g).to(dt).to(dev)
+        wd = w.to(dev)
+
+        def fwd(b0, nb):
+            x = cd[b0:b0 + nb].contiguous()
+            y, ya, part = nan(T, nb, H, W, 32), nan(T, nb, H, W, 32), nan(rows_of(nb, T, H, W), 2, 64, dtype=torch.float32)
+            L.check(lib.qt_conv3d_first_fwd(qdt, L.ptr(x), L.ptr(wp), L.ptr(y), None, None, 0, L.ptr(part), nb, T, H, W, st), "stats")
+            L.check(lib.qt_conv3d_first_fwd(qdt, L.ptr(x), L.ptr(wp), L.ptr(ya), L.ptr(sc), L.ptr(sh), 1, None, nb, T, H, W, st), "affine")
+            pooled = [nan(T, nb, H // 2, W // 2, pc) for pc in (64, 32)]
+            for p in pooled:
+                L.check(lib.qt_conv3d_first_fwd_pool(qdt, L.ptr(x), L.ptr(wp), L.ptr(p), p.shape[-1], L.ptr(sc), L.ptr(sh), nb, T, H, W,
+                                                     st), "qt_conv3d_first_fwd_pool")
+            dy = dyd[:, b0:b0 + nb].contiguous()
+            dx = nan(nb, T, 3, H, W, dtype=torch.float32)
+            L.check(lib.qt_conv3d_first_dgrad(qdt, L.ptr(dy), L.ptr(wd), L.ptr(dx), nb, T, H, W, st), "qt_conv3d_first_dgrad")
+            return y, ya, pooled[0], pooled[1], dx, part
+
+        whole, clips = both(fwd)
+        for j, (name, axis) in enumerate([("raw + statistics", 1), ("scale / shift / ReLU", 1), ("pooled, 64-channel rows", 1),
+                                          ("pooled, 32-channel rows", 1), ("qt_conv3d_first_dgrad", 0)]):
+            same_bits(whole[j], [c[j] for c in clips], axis, name)
+        assert rel_err(whole[0].float().cpu(), ref.permute(2, 0, 3, 4, 1)) <= 1e-2
+        _stats_agree(whole[5], [c[5] for c in clips], ref, absref, 81, "qt_conv3d_first_fwd")
+        return
+
+    xc = 64
+    x = torch.randn(B, 32, T, H, W, generator=g).to(dt)
+    w = (torch.randn(64, 32, 3, 3, 3, generator=g) * (2.0 / (32 * 27)) ** 0.5).to(dt)
+    ref, absref = F.conv3d(x.double(), w.double(), None, 1, 1), F.conv3d(x.double().abs(), w.double().abs(), None, 1, 1)
+    xd = torch.full((T, B, H, W, xc), 3.0, dtype=dt)                                  # garbage in the padding channels
+    xd[..., :32] = _to_tb(x)
+    xd = xd.to(dev)
+    wp = torch.full((64, 27, 64), 3.0, dtype=dt)
+    wp[:, :, :32] = w.permute(0, 2, 3, 4, 1).reshape(64, 27, 32)
+    wdp = torch.full((64, 27, 64), 3.0, dtype=dt)
+    wdp[:32] = w.permute(1, 2, 3, 4, 0).reshape(32, 27, 64)
+    wp, wdp = wp.to(dev), wdp.to(dev)
+    sc, sh = (torch.rand(64, generator=g) + 0.5).to(dev), (torch.randn(64, generator=g) * 0.3).to(dev)
+    dyd = torch.randn(T, B, H, W, 64, generator=g).to(dt).to(dev)
+    lib.qt_conv3d_c32_dgrad_scratch_bytes.restype = ctypes.c_size_t
+
+    def run(b0, nb):
+        xs = xd[:, b0:b0 + nb].contiguous()
+        y, yp, ya = (nan(T, nb, H, W, 64) for _ in range(3))
+        part = nan(rows_of(nb, T, H, W), 2, 64, dtype=torch.float32)
+        L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xs), xc, L.ptr(wp), L.ptr(y), None, None, 0, L.ptr(part), nb, T, H, W, st), "stats")
+        L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xs), xc, L.ptr(wp), L.ptr(yp), None, None, 0, None, nb, T, H, W, st), "plain")
+        L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xs), xc, L.ptr(wp), L.ptr(ya), L.ptr(sc), L.ptr(sh), 1, None, nb, T, H, W, st), "affine")
+        dy = dyd[:, b0:b0 + nb].contiguous()
+        nscr = int(lib.qt_conv3d_c32_dgrad_scratch_bytes(nb, T, H, W))
+        dxs = []
+        for dxc in (64, 32):
+            scr = torch.full((nscr // 4,), float("nan"), device=dev)
+            dx = nan(T, nb, H, W, dxc)
+            L.check(lib.qt_conv3d_c32_dgrad(qdt, L.ptr(dy), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), ctypes.c_size_t(nscr), nb, T, H, W, st),
+                    "qt_conv3d_c32_dgrad")
+            dxs.append(dx)
+        return y, yp, ya, dxs[0], dxs[1], part
+
+    whole, clips = both(run)
+    for j, name in enumerate(["raw + statistics", "raw", "scale / shift / ReLU", "dx, 64-channel rows", "dx, 32-channel rows"]):
+        same_bits(whole[j], [c[j] for c in clips], 1, name)
+    assert torch.equal(whole[0], whole[1])
+    assert rel_err(whole[0].float().cpu(), ref.permute(2, 0, 3, 4, 1)) <= 1e-2
+    _stats_agree(whole[5], [c[5] for c in clips], ref, absref, 32 * 27, "qt_conv3d_c32_fwd")
 
 
 CASES = [("q3_t8", 2, 8, 112, "quadtree_3d_fusion", 31), ("q3_t5", 2, 5, 64, "quadtree_3d_fusion", 31),

@@ -2,7 +2,9 @@
 is torch.equal throughout (no tolerance).  conditions() runs on the reference before a kernel result is looked at; the rows
 are the ones tests/test_exact_data_cpu.py checks without a GPU.  The kernels are driven by the launch helpers of the existing
 test files; the path a row names is confirmed the way those files do it (qt_conv2d_stats_rows mirrors the dispatch, the
-workspace size tells the streaming weight-gradient kernels, qt_set_* switches force a path).
+workspace size tells the streaming weight-gradient kernels, qt_set_* switches force a path).  Rows with a field `walk` are
+there for the second and later work items of a persistent kernel's workgroups: that every workgroup takes that many items is
+asserted from the grid the library reports before a result is looked at (a failure, never a skip).
 
 The BatchNorm-backward link sums of the stride-1 data gradients stay with tests/test_conv_pt_gpu.py; the merged stride-2
 forms get a dyadic xhat here and are compared exactly."""
@@ -535,6 +537,11 @@ def test_stem_data_gradient_is_bit_exact(row, dt):
     c = E.dgrad_data(row)
     E.dgrad_conditions(c, F32)
     B = row["cfg"][0]
+    if row.get("walk"):
+        # stem_dgrad.hip: tiles of 16 block rows (bf16) / 8 block rows (f32) x 16 blocks of the 112 x 112 map = 49 / 98 per
+        # image, on a persistent grid of at most 256 workgroups whatever the device
+        ntiles = B * (49 if dt == BF else 98)
+        assert ntiles >= row["walk"] * 256 + 1, ("not every workgroup takes", row["walk"], "tiles:", ntiles, "tiles")
     gd = Guard(dev)
     dyd = gd.input("dy", nhwc(c["dy"]).to(dt))
     wd = gd.input("w", c["w"].float().contiguous())
@@ -587,6 +594,13 @@ def _ncthw(y, C):
     return y.cpu()[..., :C].permute(1, 4, 0, 2, 3)
 
 
+def _walk_precondition(row, items, rows):
+    """a `walk` row is there for the second and later items of a workgroup: with `rows` workgroups (the grid the library
+    reports) every one of them must take at least row["walk"] items.  A failure, not a skip: on a device where this does not
+    hold the row tests nothing it was added for"""
+    assert rows > 0 and items >= row["walk"] * rows + 1, (row["name"], "items", items, "workgroups", rows, "walk", row["walk"])
+
+
 C3F, C3F_IDS = E.expand(E.C3F_ROWS)
 
 
@@ -601,6 +615,12 @@ def test_first_conv3d_is_bit_exact(row, dt):
     c = E.c3_data(row, 3, 32)
     B, T, H, W = row["cfg"]
     qdt, st = L.qt_dtype(dt), L.stream_ptr()
+    if row.get("walk"):
+        # (clip, 4-row slab) items on the grid the library reports (one statistics row per workgroup).  qt_conv3d_first_dgrad
+        # has no query of its own: it launches by the same rule (at most 2 x CUs workgroups) over the same items at one column
+        # tile per row (W <= 112), so the forward's row count is its grid too
+        assert W <= 112
+        _walk_precondition(row, B * (H // 4), lib.qt_conv3d_first_stats_rows(B, T, H, W))
     if "fwd" in row["only"]:
         E.c3_conditions(c, dt, "fwd")
         gd = Guard(dev)
@@ -700,6 +720,8 @@ def test_second_conv3d_is_bit_exact(row, dt):
         xd[..., :32] = _tb(x).to(dt)
         return xd
     assert lib.qt_conv3d_c32_stats_rows(B, T, H, W) > 0, "conv3d_slab.hip was expected to take this shape"
+    if row.get("walk"):   # (clip, 2-row slab) items; forward, data gradient and weight gradient launch the same grid
+        _walk_precondition(row, B * (H // 2), lib.qt_conv3d_c32_stats_rows(B, T, H, W))
     if "fwd" in row["only"]:
         E.c3_conditions(c, dt, "fwd")
         gd = Guard(dev)

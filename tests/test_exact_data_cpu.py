@@ -123,7 +123,7 @@ def test_stem_data_gradient_rows(row, dt):
     c = E.dgrad_data(row)
     E.dgrad_conditions(c, F32)
     for dyf in _formats(c["dy"].float()):
-        assert E.same(torch.nn.grad.conv2d_input((1, 3, 224, 224), c["w"].float(), dyf, 2, 3), c["dx"], F32)
+        assert E.same(torch.nn.grad.conv2d_input((row["cfg"][0], 3, 224, 224), c["w"].float(), dyf, 2, 3), c["dx"], F32)
 
 
 SW, SW_IDS = E.expand(E.STEMW_ROWS)
@@ -228,6 +228,141 @@ def test_a_skipped_tap_a_dropped_k_element_and_a_missing_tile_are_caught(row):
     part = torch.stack([torch.stack([t.sum(0), (t * t).sum(0)]) for t in tiles])
     assert E.stats_equal(part, c["raw"])
     assert tiles[-1].shape[0] <= 128 and not E.stats_equal(part[:-1], c["raw"])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# damage to the walk of a persistent kernel: a stand-in with a capped grid (workgroup k takes items k, k + grid, ...)
+# ----------------------------------------------------------------------------------------------------------------------
+FAULTS = ("stale_slab", "round_skipped", "last_item_only", "frame_slot_left")
+
+
+def _slabs(x, R):
+    """[B][C][T][H][W] -> the input of every (clip, R-row slab) item with its row halo: [items][C][T][R + 2][W]"""
+    B, C, T, H, W = x.shape
+    u = F.pad(x, (0, 0, 1, 1)).unfold(3, R + 2, R)                  # [B][C][T][H / R][W][R + 2]
+    return u.permute(0, 3, 1, 2, 5, 4).reshape(B * (H // R), C, T, R + 2, W)
+
+
+def _walked_conv3d(x, w, R, cap, fault=None, dy=None):
+    """3x3x3 / pad 1 convolution of x [B][C][T][H][W] (f32) the way the slab kernels walk it: item = (clip, R output rows), its
+    input the frame slabs with a row halo and a zero frame on either side of the clip; workgroup k of min(items, cap) takes
+    items k, k + grid, ...  Returns (y [B][O][T][H][W], statistics rows [grid][2][O], the weight gradient for `dy` or None).
+    fault (each is invisible when every workgroup has one item):
+      stale_slab       a workgroup's second item is computed from its first item's slabs (ring not refilled / stale prefetch)
+      round_skipped    the loop runs the full rounds only: the items of the last, partial round are never computed
+      last_item_only   a workgroup's statistics row and partial filter hold its last item alone (overwritten, not accumulated)
+      frame_slot_left  the frame before the clip (t - 1 at t = 0) of a later item is the previous item's last frame slab, not zeros"""
+    B, _, T, H, W = x.shape
+    O = w.shape[0]
+    xi = _slabs(x, R)
+    items = xi.shape[0]
+    grid, wg, trip = E.walk_items(items, cap)
+    i = torch.arange(items)
+    if fault == "stale_slab":
+        xi = xi[torch.where(trip == 1, i - grid, i)]
+    xp = F.pad(xi, (0, 0, 0, 0, 1, 1))                               # a zero frame before and after the clip
+    if fault == "frame_slot_left":
+        later = trip >= 1
+        xp[later, :, 0] = xi[i[later] - grid, :, T - 1]
+    yi = F.conv3d(xp, w, None, 1, (0, 0, 1))                         # [items][O][T][R][W]
+    done = i < (items // grid) * grid if fault == "round_skipped" else torch.ones(items, dtype=torch.bool)
+    yi = yi * done.view(-1, 1, 1, 1, 1)                              # (what a skipped item leaves behind: anything but the result)
+    y = yi.view(B, H // R, O, T, R, W).permute(0, 2, 3, 1, 4, 5).reshape(B, O, T, H, W)
+    counted = done & (i + grid >= items) if fault == "last_item_only" else done
+    per_item = torch.stack([yi.sum((2, 3, 4)), (yi * yi).sum((2, 3, 4))], 1) * counted.view(-1, 1, 1)
+    part = torch.zeros(grid, 2, O).index_add_(0, wg, per_item)
+    dw = None
+    if dy is not None:
+        dyi = dy.view(B, O, T, H // R, R, W).permute(0, 3, 1, 2, 4, 5).reshape(items, O, T, R, W)
+        dw = torch.nn.grad.conv3d_weight(xp[counted], w.shape, dyi[counted], 1, (0, 0, 1))
+    return y, part, dw
+
+
+def _walked_stem_dgrad(dy, w, ty, cap, fault=None):
+    """conv1's data gradient the way stem_dgrad.hip walks it: item = a tile of ty x 16 blocks of 2 x 2 image pixels, its input
+    the dy rows and columns of the tile with a halo of 1 before and 2 after; the same capped grid and the faults of
+    _walked_conv3d that a kernel without frames and partial rows can have"""
+    B = dy.shape[0]
+    u = F.pad(dy, (1, 2, 1, 2)).unfold(2, ty + 3, ty).unfold(3, 19, 16)      # [B][64][112 / ty][7][ty + 3][19]
+    ny = 112 // ty
+    di = u.permute(0, 2, 3, 1, 4, 5).reshape(B * ny * 7, 64, ty + 3, 19)
+    items = di.shape[0]
+    grid, wg, trip = E.walk_items(items, cap)
+    i = torch.arange(items)
+    if fault == "stale_slab":
+        di = di[torch.where(trip == 1, i - grid, i)]
+    # halo pixel j of a tile is conv1 output y0 - 1 + j: it reaches image row 2 (y0 - 1 + j) + k - 3, the transposed
+    # convolution's row 2 j + k: the tile's image rows 2 y0 .. 2 y0 + 2 ty - 1 are its rows 5 .. 5 + 2 ty - 1
+    full = F.conv_transpose2d(di, w, None, 2)
+    out = full[:, :, 5:5 + 2 * ty, 5:5 + 32]
+    if fault == "round_skipped":
+        out = out * (i < (items // grid) * grid).view(-1, 1, 1, 1)
+    return out.reshape(B, ny, 7, 3, 2 * ty, 32).permute(0, 3, 1, 4, 2, 5).reshape(B, 3, 224, 224)
+
+
+def _caught(ok, walking, what):
+    """a fault shows exactly where workgroups take more than one item"""
+    assert ok == (not walking), (what, "caught" if not ok else "not caught", "walking" if walking else "one item per workgroup")
+
+
+WALK3D = [(r, 3, 32, 4, 512) for r in E.C3F_ROWS if r.get("walk")] + [(r, 32, 64, 2, 256) for r in E.C32_ROWS if r.get("walk")]
+
+
+@pytest.mark.parametrize("row,cin,cout,R,cap", WALK3D, ids=[r["name"] for r, *_ in WALK3D])
+def test_a_stale_slab_a_skipped_round_an_overwritten_partial_and_a_left_frame_slot_are_caught(row, cin, cout, R, cap):
+    """R, cap: output rows per item and the grid cap of the kernels of the row (conv3d_first.hip: 4 rows, 2 x 256 CUs;
+    conv3d_slab.hip: 2 rows, 256 CUs).  Every fault fails the GPU test's comparisons on the walk rows at that cap, and none
+    does on the same data when the grid has a workgroup per item -- the state of every earlier row."""
+    dt = BF
+    c = E.c3_data(row, cin, cout)
+    B, T, H, W = row["cfg"]
+    items = B * (H // R)
+    assert items >= row["walk"] * cap + 1
+    x, w = c["x"].float(), c["w"].float()
+    wflip = c["wg"].float().transpose(0, 1).flip(2, 3, 4).contiguous()        # conv3d_input(dy, wg) = conv3d(dy, wflip)
+    ddt = F32 if cin == 3 else dt
+    grads = [("wgrad", c["x1"].float(), c["dy"].float(), c["dw"])]
+    if "fused" in row["only"]:
+        f = E.c3_fused_data(c, 32)
+        grads.append(("fused", f["x1"].float(), f["dy"].float(), f["dw"]))
+    for walking in (True, False):
+        g = cap if walking else items
+        y, part, _ = _walked_conv3d(x, w, R, g)
+        assert part.shape[0] == min(items, g)
+        assert E.same(y.to(dt), c["raw"], dt) and E.stats_equal(part, c["raw"])
+        assert E.same(_walked_conv3d(c["dyf"].float(), wflip, R, g)[0].to(ddt), c["dx"], ddt)
+        for _, x1, dy, dw in grads:
+            assert E.same(_walked_conv3d(x1, w, R, g, dy=dy)[2], dw, F32)
+        for fault in FAULTS:
+            y, part, _ = _walked_conv3d(x, w, R, g, fault)
+            if fault != "last_item_only":                                  # (that one leaves the map alone)
+                _caught(E.same(y.to(dt), c["raw"], dt), walking, (fault, "forward"))
+                dx = _walked_conv3d(c["dyf"].float(), wflip, R, g, fault)[0]
+                _caught(E.same(dx.to(ddt), c["dx"], ddt), walking, (fault, "data gradient"))
+            if fault in ("round_skipped", "last_item_only"):
+                _caught(E.stats_equal(part, c["raw"]), walking, (fault, "statistics"))
+            for name, x1, dy, dw in grads:
+                _caught(E.same(_walked_conv3d(x1, w, R, g, fault, dy=dy)[2], dw, F32), walking, (fault, name))
+
+
+WALK_STEM, WALK_STEM_IDS = E.expand([r for r in E.STEMD_ROWS if r.get("walk")])
+
+
+@pytest.mark.parametrize("row,dt", WALK_STEM, ids=WALK_STEM_IDS)
+def test_a_stale_tile_prefetch_and_a_skipped_round_of_the_stem_data_gradient_are_caught(row, dt):
+    """stem_dgrad.hip: tiles of 16 x 16 blocks (bf16) / 8 x 16 blocks (f32) on a grid of at most 256 workgroups, the next tile's
+    rows loaded into registers under the current tile's MFMAs"""
+    c = E.dgrad_data(row)
+    B = row["cfg"][0]
+    ty, cap = (16 if dt == BF else 8), 256
+    items = B * (112 // ty) * 7
+    assert items >= row["walk"] * cap + 1
+    dy, w = c["dy"].float(), c["w"].float()
+    for walking in (True, False):
+        g = cap if walking else items
+        assert E.same(_walked_stem_dgrad(dy, w, ty, g), c["dx"], F32)
+        for fault in ("stale_slab", "round_skipped"):
+            _caught(E.same(_walked_stem_dgrad(dy, w, ty, g, fault), c["dx"], F32), walking, fault)
 
 
 ROUNDED = [_row(E.FWD_ROWS, "generic_3x3_rounded"), _row(E.FWD_ROWS, "ring_rounded"), _row(E.FWD_ROWS, "pt_14_rounded")]

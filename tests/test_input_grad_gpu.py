@@ -65,7 +65,7 @@ def _oracle_image_grad(kind, mode, sd, x, f, train, dlogits):
 
 # ---- 1. the kernel alone ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B", [2, 3])
+@pytest.mark.parametrize("B", [2, 3, 11])    # 11: 539 / 1078 tiles on the grid of 256 -- every workgroup walks 2 or more
 def test_stem_dgrad_kernel_matches_conv2d_input(dt, B):
     dev = _dev()
     L = pkg("_lib").lib()
