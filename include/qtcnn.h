@@ -1063,6 +1063,61 @@ long long qt_pose_posterior_workspace_bytes(const qt_pose_order_desc* desc);
 int qt_pose_posterior(const qt_pose_order_desc* desc, const float* probs, long long ld, const int* state_class,
                       const int* trans, const int* init, double* carry, float* posterior, float* filtered,
                       float* class_posterior, double* log2_evidence, void* workspace, long long workspace_bytes, void* stream);
+/* Pose-order prior learned on the device (Baum-Welch): the expected transition counts of the chain above under its own
+ * posterior (qt_pose_prior_expect), the hard counts of given state paths (qt_pose_prior_count_paths), and the new tables from
+ * the counts (qt_pose_prior_update).  Inputs, limits and notation are qt_pose_posterior's: E[f][j] = q(probs[f][state_class[j]])
+ * / 256, T[i][j] = clamp(trans[i][j]) / 256, start[i] = clamp(init[i]) / 256 or 0 without init, L x = log2 sum 2^x with its
+ * maximum out and its sum in ascending order.  Every sequence of a call is a WHOLE video: it starts from `start`, no carry is
+ * read or written.
+ * E-step, per sequence of n frames, with a_f and b_f the rows of the posterior rule (a_(-1) = start), for f = 0 .. n - 1:
+ *   g_f[j]     = E[f][j] + b_f[j]
+ *   x_f[i][j]  = a_(f-1)[i] + T[i][j] + g_f[j]
+ *   Z_f        = L_(i,j) x_f[i][j]                   (the maximum out, i ascending, inside it j ascending)
+ *   xi_f[i][j] = 2^(x_f[i][j] - Z_f)                 P(step i at frame f - 1 and step j at frame f | the whole video)
+ *   counts[i][j]    += sum over f = 1 .. n - 1 of xi_f[i][j]
+ *   start_counts[i] += sum over j of xi_0[i][j]      (frame 0's transition is the virtual one out of `start`: not in counts)
+ *   totals[0]       += the sequence's evidence in bits (the posterior rule's log2_evidence);   totals[1] += n
+ * Consequences: Z_f = L_i (a_(f-1)[i] + B_f[i]) with B_f[i] = L_j (T[i][j] + g_f[j]) the un-normalised b_(f-1), which is how
+ * the kernel forms it; sum_j xi_f[i][j] is the posterior of frame f - 1 at i, sum_i xi_f[i][j] that of frame f at j; a
+ * constant added to a_(f-1) or to b_f changes no xi.
+ * counts double [S][S], start_counts double [S], totals double [2], in device memory, are ADDED TO (the caller zeroes them
+ * once per E-step): a training set is one call per video, or one call per batch of videos of equal length.  The order of every
+ * addition is fixed: the frames of a tile of QT_POSE_ORDER_TILE frames go, in the backward sweep's order (descending f), into an
+ * f32 partial per (sequence, tile); a sequence's tiles are added in ascending order, then the sequences in ascending order,
+ * both in double from zero, one thread per entry, and that sum is added onto the accumulator.  No float atomics, no zero
+ * fill of caller memory, the same inputs give the same bits on every run.  frames == 1 adds zeros to counts.
+ * Routes: frames <= QT_POSE_ORDER_TILE: a wave per sequence, then the reduction (two launches); longer calls: the posterior's
+ * tile products and scan as they are, a replay per (sequence, tile) that stores no posterior rows, the reduction (four
+ * launches), and as there the result differs from the frame-by-frame rule by f32 rounding.
+ * Path counts, for path int64 [batch][frames] (a decoder's path for Viterbi training, or labelled steps):
+ *   counts[p[f-1]][p[f]] += 1 for f >= 1;   start_counts[p[0]] += 1;   totals[1] += frames   (totals[0] is left alone)
+ * A transition with an end outside [0, S) is left out, and so is a start outside it.  Per-workgroup integer histograms in
+ * LDS, added in int64: exact integers in double.  num_classes of the descriptor is not used here.
+ * M-step (one launch).  allowed int32 [S][S], non-zero where the transition may be learned (the learner fixes it when it is
+ * made: the entry of the initial table is above -65536).  For row i, in double:
+ *   r[j] = allowed[i][j] ? counts[i][j] + pseudo_count : 0;   R = sum_j r[j], ascending
+ *   R > 0:   trans_out[i][j] = r[j] > 0 ? clamp(rint(256 log2(r[j] / R)), -65536, 0) : -65536
+ *   otherwise the row keeps trans_in's values.
+ * init_out, where not NULL, follows the same rule from start_counts with every entry allowed (old values init_in's, zeros
+ * without one).  trans_out may be trans_in itself and init_out init_in itself.
+ * qt_pose_prior_workspace_bytes: what qt_pose_prior_expect needs (never 0 for a descriptor in range: the partials; 8-byte
+ * aligned; every slot that is read is written in the same call); it serves qt_pose_prior_count_paths too.  0 for a null or
+ * out-of-range descriptor.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument): as qt_pose_posterior for the descriptor, ld,
+ * null and misaligned pointers (8 bytes for double, int64 and the workspace), the workspace's size and overlaps of an output
+ * (counts, start_counts, totals, workspace; trans_out, init_out) with an input or another output; qt_pose_prior_update for
+ * num_states outside 1 .. 64, a pseudo_count that is negative, NaN or infinite, a null counts, allowed, trans_in or trans_out,
+ * an init_out without start_counts.  QT_ERR_UNSUPPORTED for more than 2^20 frames in all. */
+long long qt_pose_prior_workspace_bytes(const qt_pose_order_desc* desc);
+int qt_pose_prior_expect(const qt_pose_order_desc* desc, const float* probs, long long ld, const int* state_class,
+                         const int* trans, const int* init, double* counts, double* start_counts, double* totals,
+                         void* workspace, long long workspace_bytes, void* stream);
+int qt_pose_prior_count_paths(const qt_pose_order_desc* desc, const long long* path, double* counts, double* start_counts,
+                              double* totals, void* workspace, long long workspace_bytes, void* stream);
+int qt_pose_prior_update(int num_states, const double* counts, const double* start_counts, const int* allowed,
+                         double pseudo_count, const int* trans_in, const int* init_in, int* trans_out, int* init_out,
+                         void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

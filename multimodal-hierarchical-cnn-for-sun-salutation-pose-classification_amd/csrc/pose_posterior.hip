@@ -25,6 +25,8 @@
 // f32 (L, +) products are not exactly associative, so (a)-(c) differ from the frame-by-frame rule by rounding.
 // No workgroup waits for another inside a launch, no atomics, no zero fill, no host synchronisation; every order is fixed; the
 // workspace is the caller's and every slot that is read has been written in the same call.
+// qt_pose_prior_expect (the learner's E-step, further down) runs (a) and (b) as they are and a replay of its own that sums the
+// pairwise posteriors instead of storing rows; qt_pose_prior_count_paths and qt_pose_prior_update are in pose_prior.hip.
 // QTCNN_POSE_POSTERIOR=1 (consulted per call; measurements only, scripts/bench_pose_posterior.py): the short route's algorithm as
 // ONE wave per stream over all tiles, the a_f rows parked in the posterior output between the two sweeps.
 #include <stdint.h>
@@ -324,6 +326,8 @@ __device__ __forceinline__ float pp_stream_start(const PpArgs& a, int b, int jj)
   if (c[0] == 0.0) return a.init ? pp_trans(a.init[jj]) : 0.0f;
   return (float)c[2 + jj];
 }
+// the same of a whole video (qt_pose_prior_expect: no carry)
+__device__ __forceinline__ float pp_video_start(const PpArgs& a, int jj) { return a.init ? pp_trans(a.init[jj]) : 0.0f; }
 // after a stream's last frame: av = a_last; sum = the c_f of this call
 __device__ __forceinline__ void pp_write_carry(const PpArgs& a, int b, int lane, float av, double seen, double total, double call) {
   double* __restrict__ c = a.carry + (long long)b * (a.S + 2);
@@ -463,7 +467,8 @@ __host__ __device__ inline int pp_scan_trip_tiles(int S) {
   return k > PP_SCAN_MAX_TILES ? PP_SCAN_MAX_TILES : k;
 }
 
-template <bool SMALL>
+// CARRY: the stream's start is pp_stream_start's; without it (the learner, every call a whole video) init / 256 or 0
+template <bool SMALL, bool CARRY = true>
 __global__ __launch_bounds__(PP_SCAN_THREADS) void pp_scan_kernel(PpArgs a) {
   __shared__ __attribute__((aligned(16))) double offs[2][PP_SCAN_PAD];
   __shared__ __attribute__((aligned(16))) float buf[2][PP_SCAN_FLOATS + PP_SCAN_PAD];
@@ -512,7 +517,7 @@ __global__ __launch_bounds__(PP_SCAN_THREADS) void pp_scan_kernel(PpArgs a) {
   float v = 0.0f;
   double ev = 0.0;
   if (chain) {
-    v = pp_stream_start(a, b, jj);
+    v = CARRY ? pp_stream_start(a, b, jj) : pp_video_start(a, jj);
     if (lane < S) starts[lane] = v;
     if (lane == 0) before[0] = 0.0;
   }
@@ -604,6 +609,154 @@ __global__ __launch_bounds__(QT_WAVE) void pp_replay_kernel(PpArgs a) {
   pp_classes(a, l, b, f0, n);
 }
 
+// ---- the learner's E-step (qt_pose_prior_expect): the pairwise posteriors xi summed over the frames -------------------------
+// A wave per (stream, tile), lane = state i: the replay's forward step (the a_f rows in LDS, nothing stored), then the backward
+// sweep with one more L over the states per frame: the un-normalised B_f[i] = L_j (T[i][j] + g_f[j]) that gives b_(f-1) also
+// gives Z_f = L_i (a_(f-1)[i] + B_f[i]), and the lane adds 2^(((a_(f-1)[i] - Z_f) + T[i][j]) + g_f[j]) into row i of the tile's
+// f32 partial: sixteen registers for S <= 16, its own LDS row (stride S | 1) above.  The emissions stay the integers q in LDS
+// (8 KB at S = 64), so the partial fits beside the table and the a_f rows: 57,856 bytes at S = 64.  A video's frame 0 goes into
+// the start partial (the sum over j in ascending j), every other frame into the partial; the tile's `starts` vector is the
+// a_(f0 - 1) of its first frame.  pr_reduce then adds tiles and streams in ascending order, in double, one thread per entry.
+struct PrArgs {
+  PpArgs p;                  // posterior, filtered, class_posterior, carry: unused; evidence: workspace, double [batch]
+  float* partial;            // workspace: f32 [batch][tiles][S][S]
+  float* start_partial;      //            f32 [batch][S]
+  double* counts;
+  double* start_counts;
+  double* totals;
+};
+inline size_t pr_wave_lds_bytes(int S) {
+  return 4 * ((size_t)S * (S | 1) * (S <= 16 ? 1 : 2) + PP_TILE * S) + 2 * PP_TILE * S;
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(QT_WAVE) void pr_expect_kernel(PrArgs r) {
+  extern __shared__ __attribute__((aligned(16))) float pp_lds[];
+  const PpArgs& a = r.p;
+  const int lane = threadIdx.x, S = a.S, SP = S | 1, jj = min(lane, S - 1);
+  float* t_l = pp_lds;                                  // [S][S | 1]
+  float* a_l = t_l + S * SP;                            // [PP_TILE][S]
+  float* acc_l = a_l + PP_TILE * S;                     // [S][S | 1], S > 16 only
+  short* e_l = reinterpret_cast<short*>(acc_l + (SMALL ? 0 : S * SP));   // [PP_TILE][S]
+  const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
+  const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+  const bool last = tile == a.tiles - 1;
+  const long long slot = (long long)b * a.tiles + tile;
+  for (int idx = lane; idx < S * S; idx += QT_WAVE) {
+    const int i = (int)fdiv((unsigned)idx, a.div_s);
+    t_l[i * SP + (idx - i * S)] = pp_trans(a.trans[idx]);
+    if (!SMALL) acc_l[i * SP + (idx - i * S)] = 0.0f;
+  }
+  pp_stage_emissions(a, b, f0, n, e_l);
+  const float a0 = tile == 0 ? pp_video_start(a, jj) : a.starts[slot * S + jj];   // (the short route runs no scan)
+  float bv = last ? 0.0f : a.ends[slot * S + jj];
+  double call = tile == 0 ? 0.0 : a.before[slot];
+  __syncthreads();
+  float col[16], row[16];
+  if (SMALL) {
+    pp_load16(col, t_l + jj, SP, S);
+    pp_load16(row, t_l + jj * SP, 1, S);
+  }
+  float av = a0;
+  for (int f = 0; f < n; ++f) {   // pp_forward's frames, the emissions from their integers
+    const float A = pp_score(e_l[f * S + jj]) + pp_step<SMALL>(av, col, t_l + jj, SP, S);
+    float m, lg;
+    double c;
+    pp_L_states<SMALL>(A, S, lane < S, m, lg, c);
+    av = (A - m) - lg;
+    call += c;
+    if (lane < S) a_l[f * S + lane] = av;
+  }
+  if (last && lane == 0) a.evidence[b] = call;
+  __syncthreads();
+  float acc[16], sp = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
+  for (int f = n - 1; f >= 0; --f) {
+    const float g = pp_score(e_l[f * S + jj]) + bv;
+    const float B = pp_step<SMALL>(g, row, t_l + jj * SP, 1, S);
+    const float ap = f > 0 ? a_l[(f - 1) * S + jj] : a0;
+    float m, lg;
+    pp_L_states<SMALL>(ap + B, S, lane < S, m, lg);
+    const float w = (ap - m) - lg;                      // a_(f-1)[i] - Z_f
+    const bool first = f == 0 && tile == 0;             // the virtual transition out of the start vector
+    if (SMALL) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {                    // (row pads the slots beyond S out: 2^-1e30 is 0)
+        const float x = pp_exp2((w + row[k]) + pp_lane(g, k));
+        if (first) sp += x;
+        else acc[k] += x;
+      }
+    } else {
+      for (int k = 0; k < S; ++k) {
+        const float x = pp_exp2((w + t_l[jj * SP + k]) + pp_lane(g, k));
+        if (first) sp += x;
+        else if (lane < S) acc_l[lane * SP + k] += x;
+      }
+    }
+    bv = B - pp_max_states<SMALL>(B, S);
+  }
+  float* __restrict__ out = r.partial + slot * S * S;
+  if (SMALL) {
+    if (lane < S) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < S) out[lane * S + k] = acc[k];
+    }
+  } else {
+    __syncthreads();
+    for (int idx = lane; idx < S * S; idx += QT_WAVE) {
+      const int i = (int)fdiv((unsigned)idx, a.div_s);
+      out[idx] = acc_l[i * SP + (idx - i * S)];
+    }
+  }
+  if (tile == 0 && lane < S) r.start_partial[(long long)b * S + lane] = sp;
+}
+
+// thread = one entry of counts, start_counts or totals: a stream's tiles in ascending order, then the streams in ascending
+// order, all in double, then one addition onto the caller's accumulator
+constexpr int PR_REDUCE_THREADS = 256;
+constexpr int PR_REDUCE_AHEAD = 16;
+__global__ __launch_bounds__(PR_REDUCE_THREADS) void pr_reduce_kernel(PrArgs r, int batch) {
+  const PpArgs& a = r.p;
+  const int S = a.S, SS = S * S, idx = blockIdx.x * PR_REDUCE_THREADS + threadIdx.x;
+  if (idx < SS) {
+    // the (stream, tile) slots are one run in memory: PR_REDUCE_AHEAD loads in flight, then their additions in the fixed order
+    const float* __restrict__ p = r.partial + idx;
+    const long long slots = (long long)batch * a.tiles;
+    double s = 0.0, sb = 0.0;
+    int tile = 0;
+    auto add = [&](float v) {
+      sb += (double)v;
+      if (++tile == a.tiles) {   // the stream's last tile
+        s += sb;
+        sb = 0.0;
+        tile = 0;
+      }
+    };
+    long long k = 0;
+    for (; k + PR_REDUCE_AHEAD <= slots; k += PR_REDUCE_AHEAD) {
+      float v[PR_REDUCE_AHEAD];
+#pragma unroll
+      for (int u = 0; u < PR_REDUCE_AHEAD; ++u) v[u] = p[(k + u) * SS];
+#pragma unroll
+      for (int u = 0; u < PR_REDUCE_AHEAD; ++u) add(v[u]);
+    }
+    for (; k < slots; ++k) add(p[k * SS]);
+    r.counts[idx] += s;
+  } else if (idx < SS + S) {
+    double s = 0.0;
+    for (int b = 0; b < batch; ++b) s += (double)r.start_partial[(long long)b * S + (idx - SS)];
+    r.start_counts[idx - SS] += s;
+  } else if (idx == SS + S) {
+    double s = 0.0;
+    for (int b = 0; b < batch; ++b) s += a.evidence[b];
+    r.totals[0] += s;
+  } else if (idx == SS + S + 1) {
+    r.totals[1] += (double)batch * (double)a.T;
+  }
+}
+
 inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 inline bool overlap(const void* p, size_t pbytes, const void* q, size_t qbytes) {
   if (!p || !q || !pbytes || !qbytes) return false;
@@ -644,7 +797,109 @@ PpLayout pp_layout(const qt_pose_order_desc* d) {
   return w;
 }
 
+// the learner's workspace: the tiled route's (none up to PP_TILE frames), then the evidence, the partials, the start partials
+struct PrLayout {
+  PpLayout pp;
+  long long evidence, partial, start_partial, total;
+};
+PrLayout pr_layout(const qt_pose_order_desc* d) {
+  PrLayout w;
+  w.pp = pp_layout(d);
+  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PP_TILE);
+  w.evidence = (w.pp.total + 7) / 8 * 8;
+  w.partial = w.evidence + B * 8;
+  w.start_partial = w.partial + B * tiles * S * S * 4;
+  w.total = (w.start_partial + B * S * 4 + 7) / 8 * 8;
+  return w;
+}
+
 }  // namespace
+
+extern "C" long long qt_pose_prior_workspace_bytes(const qt_pose_order_desc* desc) {
+  if (check_desc("qt_pose_prior_workspace_bytes", desc) != QT_OK) return 0;
+  return pr_layout(desc).total;
+}
+
+extern "C" int qt_pose_prior_expect(const qt_pose_order_desc* desc, const float* probs, long long ld, const int* state_class,
+                                    const int* trans, const int* init, double* counts, double* start_counts, double* totals,
+                                    void* workspace, long long workspace_bytes, void* stream) {
+  const char* const who = "qt_pose_prior_expect";
+  if (const int rc = check_desc(who, desc)) return rc;
+  const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states;
+  QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
+  QT_CHECK_ARG(probs != nullptr && state_class != nullptr && trans != nullptr && counts != nullptr && start_counts != nullptr &&
+                   totals != nullptr,
+               "%s: null %s", who,
+               !probs ? "probs" : !state_class ? "state_class" : !trans ? "trans" : !counts ? "counts" : !start_counts ? "start_counts"
+                                                                                                                        : "totals");
+  QT_CHECK_ARG(!misaligned(probs, 3) && !misaligned(state_class, 3) && !misaligned(trans, 3) && !misaligned(init, 3) &&
+                   !misaligned(counts, 7) && !misaligned(start_counts, 7) && !misaligned(totals, 7) && !misaligned(workspace, 7),
+               "%s: probs, state_class, trans and init must be 4-byte aligned, counts, start_counts, totals and the workspace "
+               "8-byte", who);
+  const PrLayout w = pr_layout(desc);
+  QT_CHECK_ARG(workspace != nullptr && workspace_bytes >= w.total,
+               "%s: workspace of %lld bytes; qt_pose_prior_workspace_bytes asks for %lld", who, workspace ? workspace_bytes : 0LL,
+               w.total);
+  const long long rows = (long long)B * T;
+  const struct { const void* p; size_t bytes; const char* name; } in[] = {
+      {probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
+      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}},
+    out[] = {{counts, (size_t)S * S * 8, "counts"}, {start_counts, (size_t)S * 8, "start_counts"}, {totals, 16, "totals"},
+             {workspace, (size_t)w.total, "workspace"}};
+  for (const auto& o : out) {
+    for (const auto& i : in)
+      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
+    for (const auto& o2 : out)
+      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
+  }
+
+  PrArgs r;
+  PpArgs& a = r.p;
+  a.probs = probs;
+  a.state_class = state_class;
+  a.trans = trans;
+  a.init = init;
+  a.carry = nullptr;
+  a.posterior = a.filtered = a.class_posterior = nullptr;
+  char* ws = static_cast<char*>(workspace);
+  a.evidence = reinterpret_cast<double*>(ws + w.evidence);
+  a.offsets = reinterpret_cast<double*>(ws + w.pp.offsets);
+  a.before = reinterpret_cast<double*>(ws + w.pp.before);
+  a.products = reinterpret_cast<float*>(ws + w.pp.products);
+  a.starts = reinterpret_cast<float*>(ws + w.pp.starts);
+  a.ends = reinterpret_cast<float*>(ws + w.pp.ends);
+  a.ld = ld;
+  a.T = T;
+  a.tiles = qt_cdiv(T, PP_TILE);
+  a.C = C;
+  a.S = S;
+  a.div_s = make_fastdiv((unsigned)S);
+  a.div_c = make_fastdiv((unsigned)C);
+  r.partial = reinterpret_cast<float*>(ws + w.partial);
+  r.start_partial = reinterpret_cast<float*>(ws + w.start_partial);
+  r.counts = counts;
+  r.start_counts = start_counts;
+  r.totals = totals;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool small = S <= 16;
+  const unsigned all = (unsigned)((long long)B * a.tiles);
+  if (a.tiles > 1) {
+    const size_t prod_lds = 4 * (2 * PP_MAX_S + 3 * (size_t)S * S) + 2 * PP_TILE * S;
+    if (small) hipLaunchKernelGGL(pp_products_kernel<true>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
+    else hipLaunchKernelGGL(pp_products_kernel<false>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
+    QT_CHECK_LAUNCH();
+    if (small) hipLaunchKernelGGL((pp_scan_kernel<true, false>), dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((pp_scan_kernel<false, false>), dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
+    QT_CHECK_LAUNCH();
+  }
+  if (small) hipLaunchKernelGGL(pr_expect_kernel<true>, dim3(all), dim3(QT_WAVE), pr_wave_lds_bytes(S), s, r);
+  else hipLaunchKernelGGL(pr_expect_kernel<false>, dim3(all), dim3(QT_WAVE), pr_wave_lds_bytes(S), s, r);
+  QT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pr_reduce_kernel, dim3((unsigned)qt_cdiv(S * S + S + 2, PR_REDUCE_THREADS)), dim3(PR_REDUCE_THREADS), 0, s, r,
+                     B);
+  QT_CHECK_LAUNCH();
+  return QT_OK;
+}
 
 extern "C" long long qt_pose_posterior_workspace_bytes(const qt_pose_order_desc* desc) {
   if (check_desc("qt_pose_posterior_workspace_bytes", desc) != QT_OK) return 0;

@@ -30,9 +30,26 @@ probability), every sum runs in a fixed order, and whatever grows with the frame
 one launch, and there a split into calls changes no bit of filtered, of the evidence total or of the carry; longer calls go
 through tile products in the (L, +) semiring (three launches) and differ from the frame-by-frame rule by f32 rounding.
 
-Not built: pairwise posteriors xi and learning `trans` from labelled videos (Baum-Welch), fixed-lag revision of earlier calls'
-paths and fixed-lag smoothing across calls, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second
-level of the posterior's scan.  There is no torch fallback: CPU tensors and other dtypes raise QtError.
+PoseOrderLearner (csrc/pose_posterior.hip, csrc/pose_prior.hip) fits the table that the two of them take, by Baum-Welch on the
+device: the E-step is the posterior's forward-backward with the pairwise posteriors xi taken out of the backward step and summed
+over the frames into float64 accumulators in a fixed order, the M-step turns the counts into int32 scores.
+
+    learner = PoseOrderLearner(state_class, trans, device, pseudo_count=0.0)    # trans: the shape to start from
+    for it in range(iterations):
+        learner.zero()
+        for probs in videos:                      # f32 [B, n, C] or [n, C], whole videos: predict's or the timeline's rows
+            learner.accumulate(probs)             # E-step, nothing read back
+        learner.update()                          # M-step on the device; learner.trans / learner.init are the new tables
+    bits, frames = learner.totals()               # the one host sync: evidence of the last E-step, frames seen
+    decoder.load_tables(learner.trans, learner.init); posterior.load_tables(learner.trans, learner.init)
+
+`fit(videos, iterations)` is that loop, `accumulate_paths(path)` adds the hard counts of state paths (a decoder's `path` for
+Viterbi training, or labelled steps), `tables()` returns numpy tables for saving.  An entry that starts at -65536 stays there.
+
+Not built: ragged batches (per-sequence lengths) and videos split across calls in the learner, learning emissions (they are the
+network's), tying rows, fixed-lag revision of earlier calls' paths and fixed-lag smoothing across calls, true minus-infinity
+(forbidden) transitions, S > 64, bf16 probabilities, a second level of the posterior's scan.  There is no torch fallback: CPU
+tensors and other dtypes raise QtError.
 """
 import ctypes
 
@@ -87,6 +104,16 @@ def bind(L):
     L.qt_pose_posterior.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
         [ctypes.c_void_p] * 9 + [ctypes.c_longlong, ctypes.c_void_p]
     L.qt_pose_posterior.restype = ctypes.c_int
+    L.qt_pose_prior_workspace_bytes.argtypes = [ctypes.POINTER(PoseOrderDesc)]
+    L.qt_pose_prior_workspace_bytes.restype = ctypes.c_longlong
+    L.qt_pose_prior_expect.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 7 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_prior_expect.restype = ctypes.c_int
+    L.qt_pose_prior_count_paths.argtypes = [ctypes.POINTER(PoseOrderDesc)] + [ctypes.c_void_p] * 5 + \
+        [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_prior_count_paths.restype = ctypes.c_int
+    L.qt_pose_prior_update.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 5
+    L.qt_pose_prior_update.restype = ctypes.c_int
     L._pose_order_bound = True
     return L
 
@@ -176,6 +203,12 @@ class PoseOrderDecoder:
         self._last = torch.full_like(self._last, -1)
         self._before = self._last
         return self
+
+    def load_tables(self, trans, init=None):
+        """a learner's tables (int32 tensors on this device) copied into the decoder's own, device to device and without a host
+        sync; every stream starts anew.  init None: no init from here on."""
+        _load_tables(self, "PoseOrderDecoder.load_tables", trans, init)
+        return self.reset()
 
     def decode(self, probs, filtered=False, emissions=False):
         """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on the decoder's device: predict's
@@ -294,6 +327,12 @@ class PosePosterior:
         self.carry.zero_()
         return self
 
+    def load_tables(self, trans, init=None):
+        """a learner's tables (int32 tensors on this device) copied into this object's own, device to device and without a host
+        sync; every stream starts anew.  init None: no init from here on."""
+        _load_tables(self, "PosePosterior.load_tables", trans, init)
+        return self.reset()
+
     def smooth(self, probs, filtered=False, by_class=False, evidence=False):
         """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device: predict's
         probabilities or the timeline's smoothed rows.  Returns posterior f32 [streams, frames, S] (or [frames, S]): the
@@ -350,3 +389,151 @@ class PosePosterior:
             raise QtError(f"PosePosterior.confidence: posterior {list(posterior.shape)} and path {list(path.shape)} do not "
                           f"belong together ({self.num_states} states)")
         return posterior.gather(-1, path.unsqueeze(-1)).squeeze(-1)
+
+
+def _load_tables(obj, who, trans, init):
+    """trans int32 [S, S] and init int32 [S] or None, tensors on obj.device, into obj's own tensors (values are clamped by the
+    kernels as they are read: checking them here would need a host sync)"""
+    S = obj.num_states
+    for name, t, shape in (("trans", trans, (S, S)), ("init", init, (S,))):
+        if t is None and name == "init":
+            continue
+        if not isinstance(t, torch.Tensor) or t.device != obj.device or t.dtype != torch.int32 or tuple(t.shape) != shape:
+            raise QtError(f"{who}: {name} must be an int32 tensor {list(shape)} on {obj.device}")
+    obj.trans.copy_(trans)
+    if init is None:
+        obj.init = None
+    elif obj.init is None:
+        obj.init = init.detach().clone().contiguous()
+    else:
+        obj.init.copy_(init)
+
+
+class PoseOrderLearner:
+    """Baum-Welch for the decoder's chain, on the device: the transition table (and, with learn_init, the start scores) fitted
+    to videos whose frames carry class probabilities only.  `accumulate` is the E-step of one video or of a batch of videos of
+    equal length (qt_pose_prior_expect adds the expected transition counts onto float64 accumulators in a fixed order),
+    `accumulate_paths` adds the hard counts of given state paths (a decoder's path for Viterbi training, or labelled steps),
+    `update` is the M-step.  An entry of the initial table at -65536 is forbidden and stays there; `pseudo_count` is added to
+    every allowed count.  Nothing is read back but by `totals` and `tables`.  See the module text."""
+
+    def __init__(self, state_class, trans, device, init=None, pseudo_count=0.0, learn_init=False, class_names=None):
+        sc, tr, init, self.class_names = _check_tables("PoseOrderLearner", state_class, trans, init, 1, class_names)
+        if isinstance(pseudo_count, bool) or not isinstance(pseudo_count, (int, float, np.integer, np.floating)) or \
+                not 0.0 <= float(pseudo_count) < float("inf"):
+            raise ValueError(f"PoseOrderLearner: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
+        self.pseudo_count, self.learn_init = float(pseudo_count), bool(learn_init)
+        S = self.num_states = int(sc.shape[0])
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise QtError("PoseOrderLearner lives on an AMD GPU (device must be cuda:N); no CPU fallback")
+        tr = np.ascontiguousarray(tr, np.int32)
+        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
+        self.trans = torch.from_numpy(tr).to(device)
+        self.allowed = torch.from_numpy((tr > TRANS_FLOOR).astype(np.int32)).to(device)
+        if init is None and self.learn_init:
+            init = np.zeros(S, np.int32)                        # the start vector of zeros, written out
+        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
+        self.counts = torch.zeros(S, S, dtype=torch.float64, device=device)
+        self.start_counts = torch.zeros(S, dtype=torch.float64, device=device)
+        self._totals = torch.zeros(2, dtype=torch.float64, device=device)
+        self._workspace = None
+        self.device = self.counts.device
+
+    def zero(self):
+        """the accumulators to zero, before an E-step (no host sync)"""
+        self.counts.zero_(), self.start_counts.zero_(), self._totals.zero_()
+        return self
+
+    def _room(self, L, desc):
+        need = int(L.qt_pose_prior_workspace_bytes(ctypes.byref(desc)))
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._workspace
+
+    def accumulate(self, probs):
+        """E-step of whole videos: probs f32 [B, n, C], or [n, C] for one, on the learner's device (predict's rows or the
+        timeline's smoothed rows).  Adds onto counts, start_counts and the totals; nothing is read back."""
+        what = "PoseOrderLearner.accumulate"
+        if not isinstance(probs, torch.Tensor):
+            raise QtError(f"{what}: probs must be a tensor")
+        if probs.device.type != "cuda" or probs.device != self.device:
+            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
+        if probs.dtype != torch.float32:
+            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+        if probs.dim() == 2:
+            probs = probs.unsqueeze(0)
+        if probs.dim() != 3 or probs.shape[0] < 1 or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
+            raise QtError(f"{what}: probs must be [B, frames, C] or [frames, C] with B, frames >= 1 and C <= {MAX_CLASSES} "
+                          f"(got {list(probs.shape)})")
+        B, T, C = probs.shape
+        if B * T > MAX_FRAMES:
+            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+        probs = probs.detach()
+        if probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1)):
+            probs = probs.contiguous()
+        desc = PoseOrderDesc(B, T, C, self.num_states)
+        L = bind(_lib.lib())
+        ws = self._room(L, desc)
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_prior_expect(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
+                                              _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.counts),
+                                              _lib.ptr(self.start_counts), _lib.ptr(self._totals), _lib.ptr(ws), ws.numel(),
+                                              _lib.stream_ptr()), "qt_pose_prior_expect")
+        return self
+
+    def accumulate_paths(self, path):
+        """hard counts: path int64 [B, n] or [n] on the learner's device, whole videos; a state outside 0 .. S - 1 (a label
+        that is missing) takes its transitions out.  The frames are counted, the evidence is not touched."""
+        what = "PoseOrderLearner.accumulate_paths"
+        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
+            raise QtError(f"{what}: path must be an int64 tensor on {self.device}; there is no CPU or torch fallback")
+        if path.dim() == 1:
+            path = path.unsqueeze(0)
+        if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] < 1:
+            raise QtError(f"{what}: path must be [B, frames] or [frames] with B, frames >= 1 (got {list(path.shape)})")
+        B, T = path.shape
+        if B * T > MAX_FRAMES:
+            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+        path = path.detach().contiguous()
+        desc = PoseOrderDesc(B, T, 1, self.num_states)
+        L = bind(_lib.lib())
+        ws = self._room(L, desc)
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_prior_count_paths(ctypes.byref(desc), _lib.ptr(path), _lib.ptr(self.counts),
+                                                   _lib.ptr(self.start_counts), _lib.ptr(self._totals), _lib.ptr(ws), ws.numel(),
+                                                   _lib.stream_ptr()), "qt_pose_prior_count_paths")
+        return self
+
+    def update(self):
+        """M-step on the device, in place: self.trans (and with learn_init self.init) are the new int32 tables"""
+        L = bind(_lib.lib())
+        init = self.init if self.learn_init else None
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_prior_update(self.num_states, _lib.ptr(self.counts), _lib.ptr(self.start_counts),
+                                              _lib.ptr(self.allowed), self.pseudo_count, _lib.ptr(self.trans), _lib.ptr(init),
+                                              _lib.ptr(self.trans), _lib.ptr(init), _lib.stream_ptr()), "qt_pose_prior_update")
+        return self
+
+    def fit(self, videos, iterations):
+        """`iterations` rounds of zero / accumulate every video / update, with no host synchronisation; `videos` is a sequence
+        (it is walked once per round) of f32 [B, n, C] or [n, C] tensors.  The accumulators are left as the last E-step made
+        them: `totals` gives the evidence under the tables BEFORE the last update."""
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 0:
+            raise ValueError(f"PoseOrderLearner.fit: iterations must be an integer >= 0 (got {iterations!r})")
+        videos = list(videos)
+        for _ in range(iterations):
+            self.zero()
+            for probs in videos:
+                self.accumulate(probs)
+            self.update()
+        return self
+
+    def totals(self):
+        """(evidence in bits, frames) of what has been accumulated since `zero`: the one host sync"""
+        bits, frames = self._totals.cpu().tolist()
+        return bits, int(frames)
+
+    def tables(self):
+        """numpy (state_class int32 [S], trans int32 [S, S], init int32 [S] or None), for saving (a host sync)"""
+        return (self.state_class.cpu().numpy(), self.trans.cpu().numpy(), None if self.init is None else self.init.cpu().numpy())
