@@ -1118,6 +1118,71 @@ int qt_pose_prior_count_paths(const qt_pose_order_desc* desc, const long long* p
 int qt_pose_prior_update(int num_states, const double* counts, const double* start_counts, const int* allowed,
                          double pseudo_count, const int* trans_in, const int* init_in, int* trans_out, int* init_out,
                          void* stream);
+/* Fixed-lag pose-order posteriors and revised paths, for a loop that hands over a few frames (often one) per call: the answer
+ * for the frame `lag` frames ago given everything up to now, a fixed delay behind the camera at a cost per step that does not
+ * grow with the video.  The reference has no such step.  Tables, emissions q, T, E, L, clamping, the limits (S, C <= 64, batch
+ * * frames <= 2^20) are qt_pose_posterior's and qt_pose_order_decode's; new is lag, 0 .. QT_POSE_LAG_MAX = 63, so that lag + 1
+ * <= QT_POSE_ORDER_TILE and every window is a call of the short route.
+ * Frames carry global indices g from the stream's start.  A call covers frames [seen, seen + n), n = desc->frames, its last
+ * frame is last = seen + n - 1, and it EMITS frames [g0, g1):
+ *   g0 = max(0, seen - lag),   g1 = flush ? seen + n : max(0, seen + n - lag),   count = g1 - g0
+ * count is known to the host and may be 0 while the stream warms up; frames == 0 is allowed with flush only.  Output arrays are
+ * [batch][count][...].  seen is host-known: all streams of a batch advance together.
+ * qt_pose_lag_smooth.  Forward a_g, c_g, filtered, evidence_total: qt_pose_posterior's forward rule, frame by frame, the same
+ * arithmetic in the same order (a_prev of frame 0 is init / 256 or zeros).  For each emitted g, with window end w = min(g +
+ * lag, last):  b_w = 0,  b_f[i] = L_j (T[i][j] + E[f+1][j] + b_(f+1)[j]) less its maximum for f = w - 1 .. g,
+ *   lagged[g][j]       = 2^(a_g[j] + b_g[j] - L_k (a_g[k] + b_g[k]));  where w == g the filtered row itself, bit for bit
+ *   lagged_class[g][c] = the sum of lagged[g][j] over the j with state_class[j] == c, in ascending j
+ *   lagged        f32 [batch][count][S], required when count > 0      lagged_class   f32 [batch][count][C], or NULL
+ *   filtered      f32 [batch][n][S] (the new frames), or NULL         log2_evidence  double [batch] (this call's c_f), or NULL
+ * qt_pose_lag_decode.  Forward delta, psi, filtered: the decoder's integer rule.  For each emitted g, with w as above:
+ *   s = filtered[w];  s = psi[f][s] for f = w .. g + 1;  lag_path[g] = s
+ *   lag_path      int64 [batch][count], required when count > 0       filtered       int64 [batch][n], or NULL
+ * Carry.  Caller-owned device memory handed over as two buffers that must not overlap, carry_in (read; not read and may be NULL
+ * with seen == 0) and carry_out (written in full); the caller swaps them between calls.  Per stream, smooth: { double
+ * evidence_total, f32 a_last[S], f32 a[lag][S], int16 q[lag][S] }, decode: { int64 score_offset, int32 delta[S] (maximum 0),
+ * uint8 psi[lag][S] }, each rounded up to 8 bytes; slot k of the history is frame seen + n - lag + k (zeros in front of the
+ * stream's start).  qt_pose_lag_smooth_carry_bytes / qt_pose_lag_decode_carry_bytes give the size of one buffer.  lag, the
+ * tables and batch are fixed for the life of a stream.
+ * Contract.  For any split of a stream into calls, flush on the last, every output and the final carry are the bits of one
+ * call, for both functions: the forward pass is the frame-by-frame rule on every route, and a window's arithmetic depends
+ * neither on where a call boundary falls nor on the route.  Hence: lag == 0 gives filtered; with flush on the last call the
+ * last lag + 1 frames carry the full posterior / path of a call ending there; a one-call flush with n <= lag + 1 is
+ * qt_pose_posterior / qt_pose_order_decode on those frames (from zeroed carries).
+ * Routes, the same bits on both.  Live: one launch, one wave per stream: table, carried history and new emissions in LDS, the
+ * forward pass over the new frames, the count windows one after another, carry_out; no workspace.  Batch (catching up, a
+ * recording): the same forward pass leaves its rows in the workspace (smooth: a and q; decode: psi and filtered), a second
+ * launch runs the windows in parallel (smooth: a wave per emitted frame in groups of 16, decode: a thread per emitted frame).
+ * One new frame goes live, and so do n frames (a flush alone: its pending frames) with n (lag + 1) <= 16 for smooth, <= 4096
+ * for decode, whose walks are cheap; QTCNN_POSE_LAG=1 / 2 forces the live / the batch route (consulted per call, by the
+ * workspace queries too).  qt_pose_lag_*_workspace_bytes: what the call needs (8-byte aligned, every slot that is read is written in the
+ * same call), 0 on the live route and for a descriptor that would be refused.  No atomics, no zero fill of caller memory, no
+ * host synchronisation, no workgroup waits for another inside a launch, inputs are never written, a stream alone gives the
+ * bits it has in a batch.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument): as qt_pose_posterior for the descriptor (but
+ * frames >= 0), ld, null probs (with frames > 0), state_class, trans or carry_out, misaligned pointers (8 bytes for the
+ * carries, double, int64 and the workspace), the workspace's size, an output that overlaps an input or another output; lag
+ * outside 0 .. 63; negative seen or frames; frames == 0 without flush; count > 0 with a null lagged / lag_path; seen > 0 with
+ * a null carry_in; carry_in overlapping carry_out.  QT_ERR_UNSUPPORTED for more than 2^20 frames in all. */
+#define QT_POSE_LAG_MAX 63
+typedef struct qt_pose_lag_desc {
+  int batch, frames, num_classes, num_states;   /* as qt_pose_order_desc; frames = n >= 0 new frames per stream */
+  int lag;                                      /* 0 .. 63 */
+  int flush;                                    /* != 0: also emit the frames still pending after this call's last frame */
+  long long seen;                               /* frames of every stream handed over before this call */
+} qt_pose_lag_desc;
+long long qt_pose_lag_smooth_carry_bytes(const qt_pose_lag_desc* desc);
+long long qt_pose_lag_smooth_workspace_bytes(const qt_pose_lag_desc* desc);
+int qt_pose_lag_smooth(const qt_pose_lag_desc* desc, const float* probs, long long ld, const int* state_class,
+                       const int* trans, const int* init, const void* carry_in, void* carry_out, float* lagged,
+                       float* lagged_class, float* filtered, double* log2_evidence, void* workspace, long long workspace_bytes,
+                       void* stream);
+long long qt_pose_lag_decode_carry_bytes(const qt_pose_lag_desc* desc);
+long long qt_pose_lag_decode_workspace_bytes(const qt_pose_lag_desc* desc);
+int qt_pose_lag_decode(const qt_pose_lag_desc* desc, const float* probs, long long ld, const int* state_class,
+                       const int* trans, const int* init, const void* carry_in, void* carry_out, long long* lag_path,
+                       long long* filtered, void* workspace, long long workspace_bytes, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

@@ -22,6 +22,7 @@ from .metrics import EvalMeter, predict  # noqa: F401
 from .scores import ScoreMeter  # noqa: F401
 from .annotate import MAJOR_SEGMENTS, POSE_CONNECTIONS, FrameAnnotator, caption_atlas  # noqa: F401
 from .timeline import PoseTimeline  # noqa: F401
+from .pose_order import PoseLagDecoder, PoseLagSmoother  # noqa: F401
 from .pose_order import PoseOrderDecoder, PoseOrderLearner, PosePosterior, cyclic_prior, prob_score  # noqa: F401
 
 __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnLstm", "Quadtree3DCNN", "Ji3DCNN", "FusedAdam", "grad_norm",
@@ -30,5 +31,5 @@ __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnL
            "SequencePoseFeatures", "SEQUENCE_FEATURE_NAMES", "NUM_SEQUENCE_FEATURES",
            "SequenceWindows", "WindowPlan", "fit_class_stats", "CnnLstmStream",
            "FrameAnnotator", "caption_atlas", "POSE_CONNECTIONS", "MAJOR_SEGMENTS", "PoseTimeline",
-           "PoseOrderDecoder", "PosePosterior", "PoseOrderLearner", "cyclic_prior", "prob_score",
+           "PoseOrderDecoder", "PosePosterior", "PoseOrderLearner", "PoseLagSmoother", "PoseLagDecoder", "cyclic_prior", "prob_score",
            "QtError", "LIB_PATH"]

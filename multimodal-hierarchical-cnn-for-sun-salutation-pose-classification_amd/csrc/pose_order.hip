@@ -38,6 +38,7 @@
 #include <stdint.h>
 
 #include "qt_common.h"
+#include "qt_internal.h"
 
 namespace {
 
@@ -749,5 +750,256 @@ extern "C" int qt_pose_order_decode(const qt_pose_order_desc* desc, const float*
   if (small) hipLaunchKernelGGL(po_backtrace_kernel<true>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
   else hipLaunchKernelGGL(po_backtrace_kernel<false>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
   QT_CHECK_LAUNCH();
+  return QT_OK;
+}
+
+// ---- fixed-lag paths across calls (qt_pose_lag_decode) ------------------------------------------------------------------------
+// lag_path[g] is the state at frame g of the best path that ends at frame w = min(g + lag, the call's last frame): the forward
+// pass is the integer rule above (po_forward as it is, the scores taken relative to their maximum after every chunk), and every
+// emitted frame walks psi back from filtered[w].  Frames carry global indices; the LDS rings hold psi and filtered of frame g in
+// row g & 127, and the forward pass goes in chunks that end on multiples of PO_TILE so that a chunk's rows are one run.
+// Live route: pld_stream_kernel<LIVE>, one launch, one wave per stream; the walks run with lane = emitted frame, lag byte reads
+// each.  Batch route: the same forward pass leaves psi and filtered of the new frames in the workspace, and pld_walk_kernel
+// walks with one thread per emitted frame, psi from the workspace or from carry_in's history.  Integers: the same bits.
+// The live route's walks cost a chunk of 64 frames about a tenth of its forward pass, the batch route's second launch about
+// 3 us: n (lag + 1) <= PLD_LIVE_STEPS = 4096 goes live (16 streams, lag 16, n = 1 .. 16: 10.2 .. 11.5 us against 13.0 .. 15.0;
+// 64 x 256: 79.7 against 80.3; 1 x 65,536: 21.4 against 19.7 ms; scripts/bench_pose_lag.py), QTCNN_POSE_LAG=1 / 2 forces either.
+namespace {
+
+constexpr int PLD_RING = 128;
+constexpr int PLD_LAG_MAX = 63;
+constexpr int PLD_WALK_THREADS = 256;
+constexpr long long PLD_LIVE_STEPS = 4096;
+static_assert(PLD_LAG_MAX == QT_POSE_LAG_MAX && PLD_LAG_MAX + PO_TILE < PLD_RING && (PLD_RING & (PLD_RING - 1)) == 0,
+              "the ring holds a chunk and its windows");
+
+struct PldArgs {
+  PoArgs p;                  // probs, state_class, trans, init, filtered, ld, T (= n), C, S, div_s; the rest unused
+  const char* carry_in;
+  char* carry_out;
+  long long* lag_path;
+  unsigned char* ws_psi;     // workspace: [batch][n][S]
+  int* ws_filt;              //            int32 [batch][n]
+  long long seen, g0, g1, carry_stride;
+  int lag;
+};
+
+// a stream's carry: { int64 score_offset; int32 delta[S] (maximum 0); uint8 psi[lag][S] }, slot k = frame seen - lag + k
+struct PldCarry {
+  long long* offset;
+  int* delta;
+  unsigned char* psi;
+};
+inline long long pld_carry_stride(int S, int lag) { return (8 + 4LL * S + (long long)lag * S + 7) / 8 * 8; }
+__device__ __forceinline__ PldCarry pld_carry(const char* base, long long stride, int b, int S) {
+  char* p = const_cast<char*>(base) + (long long)b * stride;
+  PldCarry c;
+  c.offset = reinterpret_cast<long long*>(p);
+  c.delta = reinterpret_cast<int*>(p + 8);
+  c.psi = reinterpret_cast<unsigned char*>(c.delta + S);
+  return c;
+}
+inline size_t pld_stream_lds_bytes(int S) {
+  return 4 * ((size_t)S * S + PO_TILE * (S | 1) + PLD_RING) + 2 * PO_TILE * S + PLD_RING * S;
+}
+
+template <bool SMALL, bool LIVE>
+__global__ __launch_bounds__(QT_WAVE) void pld_stream_kernel(PldArgs r) {
+  extern __shared__ __attribute__((aligned(16))) int po_lds[];
+  const PoArgs& a = r.p;
+  const int lane = threadIdx.x, b = blockIdx.x, S = a.S, SP = S | 1, lag = r.lag;
+  PoLds l;
+  l.tk = po_lds;
+  l.dl = l.tk + S * S;                                   // [PO_TILE][S | 1]
+  int* filt_l = l.dl + PO_TILE * SP;                     // [PLD_RING]
+  l.path = filt_l;
+  l.e = reinterpret_cast<short*>(filt_l + PLD_RING);     // [PO_TILE][S]
+  unsigned char* psi_l = reinterpret_cast<unsigned char*>(l.e + PO_TILE * S);   // [PLD_RING][S]
+  l.psi = psi_l;
+  po_stage_keys(a, l.tk);
+  const long long seen = r.seen, end = seen + a.T, last = end - 1, count = r.g1 - r.g0;
+  const PldCarry in = pld_carry(r.carry_in, r.carry_stride, b, S);
+  const PldCarry out = pld_carry(r.carry_out, r.carry_stride, b, S);
+  long long D = LLONG_MIN;
+  if (lane < S) D = seen > 0 ? (long long)in.delta[lane] : (a.init ? (long long)po_clamp_trans(a.init[lane]) : 0);
+  long long base;
+  int d = po_normalise(D, base);
+  long long offset = (seen > 0 ? *in.offset : 0) + base;
+  if (seen > 0) {   // filtered of the frame in front of the call: the lowest state at the carry's maximum
+    const unsigned long long top = __ballot(lane < S && d == 0);
+    if (lane == 0) filt_l[(int)((seen - 1) & (PLD_RING - 1))] = __ffsll((long long)top) - 1;
+    for (long long g = seen > lag ? seen - lag : 0; g < seen; ++g)
+      if (lane < S) psi_l[(int)(g & (PLD_RING - 1)) * S + lane] = in.psi[(g - (seen - lag)) * S + lane];
+  }
+  long long lo = seen;
+  do {
+    const long long nxt = (lo / PO_TILE + 1) * PO_TILE, hi = nxt < end ? nxt : end;
+    const int m = (int)(hi - lo), f0 = (int)(lo - seen), r0 = (int)(lo & (PLD_RING - 1));
+    __syncthreads();
+    if (m > 0) {
+      l.psi = psi_l + r0 * S;
+      po_stage_emissions(a, b, f0, m, l.e, false);
+      __syncthreads();
+      po_forward<SMALL>(l, m, S, lane, d);
+      __syncthreads();
+      const int* __restrict__ row = l.dl + min(lane, m - 1) * SP;   // filtered, lane = frame
+      int bv = row[0], bj = 0;
+      for (int j = 1; j < S; ++j) {
+        const int v = row[j];
+        if (v > bv) bv = v, bj = j;
+      }
+      if (lane < m) {
+        filt_l[r0 + lane] = bj;
+        if (a.filtered) a.filtered[(long long)b * a.T + f0 + lane] = (long long)bj;
+      }
+      const int mx = __builtin_amdgcn_readlane(bv, m - 1);
+      d -= mx;
+      offset += mx;
+      __syncthreads();
+    }
+    if (LIVE) {
+      const long long first = lo > lag ? lo - lag : 0, until = hi == end ? r.g1 : (hi > lag ? hi - lag : 0);
+      for (long long g = first + lane; g < until; g += QT_WAVE) {
+        const long long w = g + lag < last ? g + lag : last;
+        int s = filt_l[(int)(w & (PLD_RING - 1))];
+        for (long long f = w; f > g; --f) s = psi_l[(int)(f & (PLD_RING - 1)) * S + s];
+        r.lag_path[(long long)b * count + (g - r.g0)] = (long long)s;
+      }
+    } else {
+      unsigned char* __restrict__ wp = r.ws_psi + ((long long)b * a.T + f0) * S;
+      for (int idx = lane; idx < m * S; idx += QT_WAVE) wp[idx] = psi_l[r0 * S + idx];
+      if (lane < m) r.ws_filt[(long long)b * a.T + f0 + lane] = filt_l[r0 + lane];
+    }
+    lo = hi;
+  } while (lo < end);
+  if (lane < S) out.delta[lane] = d;
+  if (lane == 0) *out.offset = offset;
+  for (int k = 0; k < lag; ++k) {   // frames end - lag .. end - 1: all in the ring; zeros in front of the stream's start
+    const long long g = end - lag + k;
+    if (lane < S) out.psi[k * S + lane] = g >= 0 ? psi_l[(int)(g & (PLD_RING - 1)) * S + lane] : (unsigned char)0;
+  }
+}
+
+// thread = (stream, emitted frame)
+__global__ __launch_bounds__(PLD_WALK_THREADS) void pld_walk_kernel(PldArgs r, int batch) {
+  const PoArgs& a = r.p;
+  const long long count = r.g1 - r.g0, idx = (long long)blockIdx.x * PLD_WALK_THREADS + threadIdx.x;
+  if (idx >= count * batch) return;
+  const int b = (int)(idx / count), S = a.S, lag = r.lag;
+  const long long g = r.g0 + (idx - (long long)b * count), seen = r.seen, last = seen + a.T - 1;
+  const long long w = g + lag < last ? g + lag : last;
+  const PldCarry in = pld_carry(r.carry_in, r.carry_stride, b, S);
+  int s = 0;
+  if (w >= seen) {
+    s = r.ws_filt[(long long)b * a.T + (w - seen)];
+  } else {   // (a flush without new frames) the frame in front of the call: the lowest state at the carry's maximum
+    int bv = in.delta[0];
+    for (int j = 1; j < S; ++j) {
+      const int v = in.delta[j];
+      if (v > bv) bv = v, s = j;
+    }
+  }
+  for (long long f = w; f > g; --f) {
+    const unsigned char* __restrict__ row =
+        f >= seen ? r.ws_psi + ((long long)b * a.T + (f - seen)) * S : in.psi + (f - (seen - lag)) * S;
+    s = row[s];
+  }
+  r.lag_path[idx] = (long long)s;
+}
+
+}  // namespace
+
+extern "C" long long qt_pose_lag_decode_carry_bytes(const qt_pose_lag_desc* desc) {
+  if (qt_pose_lag_check_desc("qt_pose_lag_decode_carry_bytes", desc) != QT_OK) return 0;
+  return desc->batch * pld_carry_stride(desc->num_states, desc->lag);
+}
+
+extern "C" long long qt_pose_lag_decode_workspace_bytes(const qt_pose_lag_desc* desc) {
+  if (qt_pose_lag_check_desc("qt_pose_lag_decode_workspace_bytes", desc) != QT_OK) return 0;
+  if (qt_pose_lag_live(desc, PLD_LIVE_STEPS)) return 0;
+  const long long rows = (long long)desc->batch * desc->frames;
+  return ((rows * desc->num_states + 7) / 8 * 8) + (rows * 4 + 7) / 8 * 8;
+}
+
+extern "C" int qt_pose_lag_decode(const qt_pose_lag_desc* desc, const float* probs, long long ld, const int* state_class,
+                                  const int* trans, const int* init, const void* carry_in, void* carry_out, long long* lag_path,
+                                  long long* filtered, void* workspace, long long workspace_bytes, void* stream) {
+  const char* const who = "qt_pose_lag_decode";
+  if (const int rc = qt_pose_lag_check_desc(who, desc)) return rc;
+  const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states, lag = desc->lag;
+  const long long end = desc->seen + T, g0 = desc->seen > lag ? desc->seen - lag : 0;
+  const long long g1 = desc->flush ? end : (end > lag ? end - lag : 0), count = g1 - g0;
+  QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
+  QT_CHECK_ARG((probs != nullptr || T == 0) && state_class != nullptr && trans != nullptr && carry_out != nullptr, "%s: null %s",
+               who, !probs && T ? "probs" : !state_class ? "state_class" : !trans ? "trans" : "carry_out");
+  QT_CHECK_ARG(count == 0 || lag_path != nullptr, "%s: null lag_path (the call emits %lld frames)", who, count);
+  QT_CHECK_ARG(desc->seen == 0 || carry_in != nullptr, "%s: null carry_in with seen = %lld", who, desc->seen);
+  QT_CHECK_ARG(!misaligned(probs, 3) && !misaligned(state_class, 3) && !misaligned(trans, 3) && !misaligned(init, 3) &&
+                   !misaligned(lag_path, 7) && !misaligned(filtered, 7) && !misaligned(carry_in, 7) &&
+                   !misaligned(carry_out, 7) && !misaligned(workspace, 7),
+               "%s: probs, state_class, trans and init must be 4-byte aligned, carry_in, carry_out, lag_path, filtered and the "
+               "workspace 8-byte", who);
+  const bool live = qt_pose_lag_live(desc, PLD_LIVE_STEPS);
+  const long long rows = (long long)B * T, psi_bytes = (rows * S + 7) / 8 * 8;
+  const long long ws_bytes = live ? 0 : psi_bytes + (rows * 4 + 7) / 8 * 8;
+  QT_CHECK_ARG(ws_bytes == 0 || (workspace != nullptr && workspace_bytes >= ws_bytes),
+               "%s: workspace of %lld bytes; qt_pose_lag_decode_workspace_bytes asks for %lld", who,
+               workspace ? workspace_bytes : 0LL, ws_bytes);
+  const long long stride = pld_carry_stride(S, lag);
+  const size_t carry_bytes = (size_t)(B * stride);
+  if (desc->seen == 0) carry_in = nullptr;   // not read
+  QT_CHECK_ARG(!overlap(carry_in, carry_bytes, carry_out, carry_bytes), "%s: carry_in must not overlap carry_out", who);
+  const struct { const void* p; size_t bytes; const char* name; } in[] = {
+      {probs, rows ? (size_t)((rows - 1) * ld + C) * 4 : 0, "probs"}, {state_class, (size_t)S * 4, "state_class"},
+      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}, {carry_in, carry_bytes, "carry_in"}},
+    out[] = {{carry_out, carry_bytes, "carry_out"}, {lag_path, (size_t)(B * count) * 8, "lag_path"},
+             {filtered, (size_t)rows * 8, "filtered"}, {workspace, (size_t)ws_bytes, "workspace"}};
+  for (const auto& o : out) {
+    for (const auto& i : in)
+      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
+    for (const auto& o2 : out)
+      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
+  }
+
+  PldArgs r;
+  PoArgs& a = r.p;
+  a.probs = probs;
+  a.state_class = state_class;
+  a.trans = trans;
+  a.init = init;
+  a.carry = nullptr;
+  a.path = nullptr;
+  a.filtered = filtered;
+  a.emissions = nullptr;
+  a.starts = a.gstarts = nullptr;
+  a.products = a.gproducts = a.ends = nullptr;
+  a.psi = a.back = nullptr;
+  a.ld = ld;
+  a.T = T;
+  a.tiles = a.groups = a.mode = 0;
+  a.C = C;
+  a.S = S;
+  a.div_s = make_fastdiv((unsigned)S);
+  r.carry_in = static_cast<const char*>(carry_in);
+  r.carry_out = static_cast<char*>(carry_out);
+  r.lag_path = lag_path;
+  r.ws_psi = static_cast<unsigned char*>(workspace);
+  r.ws_filt = reinterpret_cast<int*>(static_cast<char*>(workspace) + psi_bytes);
+  r.seen = desc->seen;
+  r.g0 = g0;
+  r.g1 = g1;
+  r.carry_stride = stride;
+  r.lag = lag;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool small = S <= 16;
+  auto stream_kernel = small ? (live ? pld_stream_kernel<true, true> : pld_stream_kernel<true, false>)
+                             : (live ? pld_stream_kernel<false, true> : pld_stream_kernel<false, false>);
+  hipLaunchKernelGGL(stream_kernel, dim3((unsigned)B), dim3(QT_WAVE), pld_stream_lds_bytes(S), s, r);
+  QT_CHECK_LAUNCH();
+  if (!live && count > 0) {
+    const unsigned grid = (unsigned)((B * count + PLD_WALK_THREADS - 1) / PLD_WALK_THREADS);
+    hipLaunchKernelGGL(pld_walk_kernel, dim3(grid), dim3(PLD_WALK_THREADS), 0, s, r, B);
+    QT_CHECK_LAUNCH();
+  }
   return QT_OK;
 }

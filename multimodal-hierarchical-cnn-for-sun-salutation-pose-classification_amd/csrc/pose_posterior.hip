@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "qt_common.h"
+#include "qt_internal.h"
 
 namespace {
 
@@ -984,5 +985,357 @@ extern "C" int qt_pose_posterior(const qt_pose_order_desc* desc, const float* pr
   if (small) hipLaunchKernelGGL(pp_replay_kernel<true>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
   else hipLaunchKernelGGL(pp_replay_kernel<false>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
   QT_CHECK_LAUNCH();
+  return QT_OK;
+}
+
+// ---- fixed-lag posteriors across calls (qt_pose_lag_smooth) -------------------------------------------------------------------
+// lagged[g] is the posterior of frame g given the frames up to w = min(g + lag, the call's last frame): the forward pass is the
+// frame-by-frame rule above (pp_forward as it is), and every emitted frame sweeps backward over its own window of at most lag
+// steps with pp_backward's arithmetic (pp_b_from_g, pp_L_states), so a window's bits depend neither on the call boundaries nor on
+// the route.  Frames carry global indices; the LDS rings hold frame g in row g & 127 (lag + PP_TILE <= 127 rows are alive at a
+// time), and the forward pass goes in chunks that end on multiples of PP_TILE so that a chunk's rows are one run.
+// Live route: pl_stream_kernel<LIVE>, one launch, one wave per stream: table, history (from carry_in) and new emissions in LDS,
+// forward over a chunk, then that chunk's windows one after another, then carry_out.  4 (S (S | 1) + 256 S + S) bytes of LDS:
+// 82,432 at S = 64, 26,208 at S = 12.
+// Batch route: pl_stream_kernel<!LIVE> is the same forward pass and carry, and leaves the a rows and the integer emissions of the
+// new frames in the workspace; pl_window_kernel then takes PL_GROUP = 16 emitted frames per workgroup of four waves, a wave per
+// frame in turn, lane = state: table, 16 rows of a and 16 + lag - 1 rows of emissions in LDS (41,472 bytes at S = 64).
+// QTCNN_POSE_LAG (consulted per call): 1 forces the live route, 2 the batch route.  Otherwise one new frame goes live, and so do
+// n frames with n (lag + 1) <= PL_LIVE_STEPS = 16: the live route runs its windows one after another, n lag dependent steps of
+// about 0.5 us at S = 12, the batch route runs them side by side behind a second launch of about 3 us (16 streams, lag 16: 16.5
+// against 19.4 us at n = 1, 25.1 against 20.3 at n = 2, 148.0 against 55.6 at n = 16; lag 5: 13.0 against 13.4 at n = 2, 16.9
+// against 13.8 at n = 3; scripts/bench_pose_lag.py).  A flush without frames counts its pending frames.
+namespace {
+
+constexpr int PL_RING = 128;
+constexpr int PL_LAG_MAX = 63;
+constexpr int PL_GROUP = 16;
+constexpr int PL_WIN_THREADS = 256;
+constexpr int PL_WIN_ROWS = PL_GROUP + PL_LAG_MAX + 1;   // emission rows of a group: frames gs + 1 .. gs + PL_GROUP - 1 + lag
+constexpr long long PL_LIVE_STEPS = 16;
+static_assert(PL_LAG_MAX == QT_POSE_LAG_MAX && PL_LAG_MAX + 1 <= PP_TILE, "a window fits the short route");
+static_assert(PL_LAG_MAX + PP_TILE < PL_RING && PL_WIN_ROWS <= PL_RING && (PL_RING & (PL_RING - 1)) == 0, "the ring holds a chunk and its windows");
+
+struct PlArgs {
+  PpArgs p;                  // probs, state_class, trans, init, filtered, evidence, ld, T (= n), C, S, div_s, div_c; the rest unused
+  const char* carry_in;
+  char* carry_out;
+  float* lagged;
+  float* lagged_class;
+  float* ws_a;               // workspace: f32 [batch][n][S], the a rows of the new frames
+  short* ws_e;               //            int16 [batch][n][S], their emissions q
+  long long seen, g0, g1, carry_stride;
+  int lag;
+};
+
+// a stream's carry: { double evidence_total; f32 a_last[S]; f32 a[lag][S]; int16 q[lag][S] }, slot k = frame seen - lag + k
+struct PlCarry {
+  double* ev;
+  float* a_last;
+  float* a;
+  short* e;
+};
+inline long long pl_carry_stride(int S, int lag) { return (8 + 4LL * S * (1 + lag) + 2LL * S * lag + 7) / 8 * 8; }
+__device__ __forceinline__ PlCarry pl_carry(const char* base, long long stride, int b, int S, int lag) {
+  char* p = const_cast<char*>(base) + (long long)b * stride;
+  PlCarry c;
+  c.ev = reinterpret_cast<double*>(p);
+  c.a_last = reinterpret_cast<float*>(p + 8);
+  c.a = c.a_last + S;
+  c.e = reinterpret_cast<short*>(c.a + (long long)lag * S);
+  return c;
+}
+__device__ __forceinline__ short pl_q(float score) { return (short)(int)(score * 256.0f); }   // exact: the score is q / 256
+
+// The window of emitted frame g, one wave, lane = state: b_w = 0, b_f from g[j] = E[f + 1][j] + b_(f + 1)[j] down to f = g, then
+// pp_backward's posterior of a_g and b_g (the filtered row itself where w == g).  a_row: a_g in LDS; the emissions of frame f
+// are at e_l[((f - ebase) & 127) * S].  Stores lagged and, when asked, lagged_class (lane = class, ascending j).
+template <bool SMALL>
+__device__ __forceinline__ void pl_window(const PlArgs& r, const PpLds& l, const float (&row)[16], const float* __restrict__ a_row,
+                                          const float* __restrict__ e_l, long long ebase, long long g, long long w, int b, int lane) {
+  const int S = r.p.S, C = r.p.C, jj = min(lane, S - 1);
+  float bv = 0.0f;
+  for (long long f = w - 1; f >= g; --f) {
+    const float gv = e_l[(int)((f + 1 - ebase) & (PL_RING - 1)) * S + jj] + bv;
+    bv = pp_b_from_g<SMALL>(l, row, gv, S, jj);
+  }
+  const float av = a_row[jj];
+  float post;
+  if (w == g) {
+    post = pp_exp2(av);
+  } else {
+    const float u = av + bv;
+    float m, lg;
+    pp_L_states<SMALL>(u, S, lane < S, m, lg);
+    post = pp_exp2((u - m) - lg);
+  }
+  const long long slot = (long long)b * (r.g1 - r.g0) + (g - r.g0);
+  if (lane < S) r.lagged[slot * S + lane] = post;
+  if (r.lagged_class) {
+    float s = 0.0f;
+    for (int j = 0; j < S; ++j) {
+      const float pj = pp_lane(post, j);
+      if (l.sc[j] == lane) s += pj;
+    }
+    if (lane < C) r.lagged_class[slot * C + lane] = s;
+  }
+}
+
+template <bool SMALL, bool LIVE>
+__global__ __launch_bounds__(QT_WAVE) void pl_stream_kernel(PlArgs r) {
+  extern __shared__ __attribute__((aligned(16))) float pp_lds[];
+  const PpArgs& a = r.p;
+  const int lane = threadIdx.x, b = blockIdx.x, S = a.S, SP = S | 1, jj = min(lane, S - 1), lag = r.lag;
+  float* a_l = pp_lds + S * SP;                         // [PL_RING][S]
+  float* e_l = a_l + PL_RING * S;                       // [PL_RING][S]
+  PpLds l;
+  l.t = pp_lds;
+  l.a = a_l;
+  l.e = e_l;
+  l.sc = reinterpret_cast<int*>(e_l + PL_RING * S);
+  pp_stage_table(a, l);
+  const long long seen = r.seen, end = seen + a.T, last = end - 1;
+  const PlCarry in = pl_carry(r.carry_in, r.carry_stride, b, S, lag);
+  const PlCarry out = pl_carry(r.carry_out, r.carry_stride, b, S, lag);
+  double total = seen > 0 ? *in.ev : 0.0, call = 0.0;
+  float av = seen > 0 ? in.a_last[jj] : pp_video_start(a, jj);
+  for (long long g = seen > lag ? seen - lag : 0; g < seen; ++g) {   // the history: frames seen - lag .. seen - 1 that exist
+    const long long k = g - (seen - lag);
+    if (lane < S) {
+      a_l[(int)(g & (PL_RING - 1)) * S + lane] = in.a[k * S + lane];
+      e_l[(int)(g & (PL_RING - 1)) * S + lane] = pp_score(in.e[k * S + lane]);
+    }
+  }
+  __syncthreads();
+  float col[16], row[16];
+  if (SMALL) {
+    pp_load16(col, l.t + jj, SP, S);
+    pp_load16(row, l.t + jj * SP, 1, S);
+  }
+  long long lo = seen;
+  do {
+    const long long nxt = (lo / PP_TILE + 1) * PP_TILE, hi = nxt < end ? nxt : end;
+    const int m = (int)(hi - lo), f0 = (int)(lo - seen), r0 = (int)(lo & (PL_RING - 1)) * S;
+    if (m > 0) {
+      l.a = a_l + r0;
+      l.e = e_l + r0;
+      pp_stage_emissions(a, b, f0, m, l.e);
+      __syncthreads();
+      pp_forward<SMALL>(a, l, col, b, f0, m, lane, av, total, call);
+      __syncthreads();
+    }
+    if (LIVE) {
+      const long long first = lo > lag ? lo - lag : 0, until = hi == end ? r.g1 : (hi > lag ? hi - lag : 0);
+      for (long long g = first; g < until; ++g) {
+        const long long w = g + lag < last ? g + lag : last;
+        pl_window<SMALL>(r, l, row, a_l + (int)(g & (PL_RING - 1)) * S, e_l, 0, g, w, b, lane);
+      }
+    } else {
+      float* __restrict__ wa = r.ws_a + ((long long)b * a.T + f0) * S;
+      short* __restrict__ we = r.ws_e + ((long long)b * a.T + f0) * S;
+      for (int idx = lane; idx < m * S; idx += QT_WAVE) {
+        wa[idx] = a_l[r0 + idx];
+        we[idx] = pl_q(e_l[r0 + idx]);
+      }
+    }
+    lo = hi;
+  } while (lo < end);
+  if (lane < S) out.a_last[lane] = av;
+  if (lane == 0) {
+    *out.ev = total;
+    if (a.evidence) a.evidence[b] = call;
+  }
+  for (int k = 0; k < lag; ++k) {   // frames end - lag .. end - 1: all in the rings; zeros in front of the stream's start
+    const long long g = end - lag + k;
+    if (lane < S) {
+      out.a[k * S + lane] = g >= 0 ? a_l[(int)(g & (PL_RING - 1)) * S + lane] : 0.0f;
+      out.e[k * S + lane] = g >= 0 ? pl_q(e_l[(int)(g & (PL_RING - 1)) * S + lane]) : (short)0;
+    }
+  }
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(PL_WIN_THREADS) void pl_window_kernel(PlArgs r) {
+  extern __shared__ __attribute__((aligned(16))) float pp_lds[];
+  const PpArgs& a = r.p;
+  const int tid = threadIdx.x, lane = tid & (QT_WAVE - 1), wave = tid / QT_WAVE, S = a.S, SP = S | 1, jj = min(lane, S - 1);
+  const int lag = r.lag;
+  PpLds l;
+  l.t = pp_lds;
+  l.a = l.t + S * SP;                                   // [PL_GROUP][S]: a of frames gs ..
+  l.e = l.a + PL_GROUP * S;                             // [PL_WIN_ROWS][S]: row f - gs
+  l.sc = reinterpret_cast<int*>(l.e + PL_WIN_ROWS * S);
+  const long long count = r.g1 - r.g0, seen = r.seen, last = seen + a.T - 1;
+  const int groups = (int)((count + PL_GROUP - 1) / PL_GROUP), b = blockIdx.x / groups, grp = blockIdx.x - b * groups;
+  const long long gs = r.g0 + (long long)grp * PL_GROUP, ge = gs + PL_GROUP < r.g1 ? gs + PL_GROUP : r.g1;
+  const long long we = ge - 1 + lag < last ? ge - 1 + lag : last;   // the last frame any window of the group reaches
+  const PlCarry in = pl_carry(r.carry_in, r.carry_stride, b, S, lag);
+  pp_stage_table(a, l);
+  for (int idx = tid; idx < (int)(ge - gs) * S; idx += PL_WIN_THREADS) {
+    const int fr = (int)fdiv((unsigned)idx, a.div_s), s = idx - fr * S;
+    const long long f = gs + fr;
+    l.a[idx] = f >= seen ? r.ws_a[((long long)b * a.T + (f - seen)) * S + s] : in.a[(f - (seen - lag)) * S + s];
+  }
+  for (int idx = tid; idx < (int)(we - gs) * S; idx += PL_WIN_THREADS) {   // frames gs + 1 .. we
+    const int fr = (int)fdiv((unsigned)idx, a.div_s) + 1, s = idx - (fr - 1) * S;
+    const long long f = gs + fr;
+    const short q = f >= seen ? r.ws_e[((long long)b * a.T + (f - seen)) * S + s] : in.e[(f - (seen - lag)) * S + s];
+    l.e[fr * S + s] = pp_score(q);
+  }
+  __syncthreads();
+  float row[16];
+  if (SMALL) pp_load16(row, l.t + jj * SP, 1, S);
+  for (long long g = gs + wave; g < ge; g += PL_WIN_THREADS / QT_WAVE) {
+    const long long w = g + lag < last ? g + lag : last;
+    pl_window<SMALL>(r, l, row, l.a + (int)(g - gs) * S, l.e, gs, g, w, b, lane);
+  }
+}
+
+inline size_t pl_stream_lds_bytes(int S) { return 4 * ((size_t)S * (S | 1) + 2 * PL_RING * S + S); }
+inline size_t pl_window_lds_bytes(int S) { return 4 * ((size_t)S * (S | 1) + (PL_GROUP + PL_WIN_ROWS) * S + S); }
+
+// the frames a call emits
+struct PlSpan {
+  long long g0, g1;
+};
+inline PlSpan pl_span(const qt_pose_lag_desc* d) {
+  const long long end = d->seen + d->frames;
+  PlSpan s;
+  s.g0 = d->seen > d->lag ? d->seen - d->lag : 0;
+  s.g1 = d->flush ? end : (end > d->lag ? end - d->lag : 0);
+  return s;
+}
+
+}  // namespace
+
+// (pose_order.hip uses them too)
+int qt_pose_lag_check_desc(const char* who, const qt_pose_lag_desc* d) {
+  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  QT_CHECK_ARG(d->batch >= 1, "%s: batch must be positive (got %d)", who, d->batch);
+  QT_CHECK_ARG(d->frames >= 0, "%s: frames must not be negative (got %d)", who, d->frames);
+  QT_CHECK_ARG(d->frames >= 1 || d->flush, "%s: frames == 0 is a flush only (flush is 0)", who);
+  QT_CHECK_ARG(d->num_classes >= 1 && d->num_classes <= PP_MAX_C, "%s: num_classes = %d; 1 .. %d are handled", who,
+               d->num_classes, PP_MAX_C);
+  QT_CHECK_ARG(d->num_states >= 1 && d->num_states <= PP_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who, d->num_states,
+               PP_MAX_S);
+  QT_CHECK_ARG(d->lag >= 0 && d->lag <= PL_LAG_MAX, "%s: lag = %d; 0 .. %d are handled", who, d->lag, PL_LAG_MAX);
+  QT_CHECK_ARG(d->seen >= 0, "%s: seen must not be negative (got %lld)", who, d->seen);
+  const long long frames = (long long)d->batch * d->frames;
+  if (frames > PP_MAX_FRAMES) {
+    qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, frames, PP_MAX_FRAMES);
+    return QT_ERR_UNSUPPORTED;
+  }
+  return QT_OK;
+}
+// true: the live route.  QTCNN_POSE_LAG = 1 / 2 forces the live / the batch route (per call); otherwise one new frame, or n
+// frames (a flush alone: its pending frames) with n (lag + 1) <= live_steps
+bool qt_pose_lag_live(const qt_pose_lag_desc* d, long long live_steps) {
+  const int mode = qt_env_int("QTCNN_POSE_LAG", 0);
+  if (mode == 1 || mode == 2) return mode == 1;
+  const long long n = d->frames ? d->frames : d->lag;
+  return d->frames == 1 || n * (d->lag + 1) <= live_steps;
+}
+
+extern "C" long long qt_pose_lag_smooth_carry_bytes(const qt_pose_lag_desc* desc) {
+  if (qt_pose_lag_check_desc("qt_pose_lag_smooth_carry_bytes", desc) != QT_OK) return 0;
+  return desc->batch * pl_carry_stride(desc->num_states, desc->lag);
+}
+
+extern "C" long long qt_pose_lag_smooth_workspace_bytes(const qt_pose_lag_desc* desc) {
+  if (qt_pose_lag_check_desc("qt_pose_lag_smooth_workspace_bytes", desc) != QT_OK) return 0;
+  if (qt_pose_lag_live(desc, PL_LIVE_STEPS)) return 0;
+  return ((long long)desc->batch * desc->frames * desc->num_states * 6 + 7) / 8 * 8;
+}
+
+extern "C" int qt_pose_lag_smooth(const qt_pose_lag_desc* desc, const float* probs, long long ld, const int* state_class,
+                                  const int* trans, const int* init, const void* carry_in, void* carry_out, float* lagged,
+                                  float* lagged_class, float* filtered, double* log2_evidence, void* workspace,
+                                  long long workspace_bytes, void* stream) {
+  const char* const who = "qt_pose_lag_smooth";
+  if (const int rc = qt_pose_lag_check_desc(who, desc)) return rc;
+  const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states, lag = desc->lag;
+  const PlSpan span = pl_span(desc);
+  const long long count = span.g1 - span.g0;
+  QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
+  QT_CHECK_ARG((probs != nullptr || T == 0) && state_class != nullptr && trans != nullptr && carry_out != nullptr, "%s: null %s",
+               who, !probs && T ? "probs" : !state_class ? "state_class" : !trans ? "trans" : "carry_out");
+  QT_CHECK_ARG(count == 0 || lagged != nullptr, "%s: null lagged (the call emits %lld frames)", who, count);
+  QT_CHECK_ARG(desc->seen == 0 || carry_in != nullptr, "%s: null carry_in with seen = %lld", who, desc->seen);
+  QT_CHECK_ARG(!misaligned(probs, 3) && !misaligned(state_class, 3) && !misaligned(trans, 3) && !misaligned(init, 3) &&
+                   !misaligned(lagged, 3) && !misaligned(lagged_class, 3) && !misaligned(filtered, 3) &&
+                   !misaligned(carry_in, 7) && !misaligned(carry_out, 7) && !misaligned(log2_evidence, 7) &&
+                   !misaligned(workspace, 7),
+               "%s: probs, state_class, trans, init, lagged, lagged_class and filtered must be 4-byte aligned, carry_in, "
+               "carry_out, log2_evidence and the workspace 8-byte", who);
+  const bool live = qt_pose_lag_live(desc, PL_LIVE_STEPS);
+  const long long ws_bytes = live ? 0 : ((long long)B * T * S * 6 + 7) / 8 * 8;
+  QT_CHECK_ARG(ws_bytes == 0 || (workspace != nullptr && workspace_bytes >= ws_bytes),
+               "%s: workspace of %lld bytes; qt_pose_lag_smooth_workspace_bytes asks for %lld", who,
+               workspace ? workspace_bytes : 0LL, ws_bytes);
+  const long long stride = pl_carry_stride(S, lag), rows = (long long)B * T;
+  const size_t carry_bytes = (size_t)(B * stride);
+  if (desc->seen == 0) carry_in = nullptr;   // not read
+  QT_CHECK_ARG(!overlap(carry_in, carry_bytes, carry_out, carry_bytes), "%s: carry_in must not overlap carry_out", who);
+  const struct { const void* p; size_t bytes; const char* name; } in[] = {
+      {probs, rows ? (size_t)((rows - 1) * ld + C) * 4 : 0, "probs"}, {state_class, (size_t)S * 4, "state_class"},
+      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}, {carry_in, carry_bytes, "carry_in"}},
+    out[] = {{carry_out, carry_bytes, "carry_out"}, {lagged, (size_t)(B * count * S) * 4, "lagged"},
+             {lagged_class, (size_t)(B * count * C) * 4, "lagged_class"}, {filtered, (size_t)rows * S * 4, "filtered"},
+             {log2_evidence, (size_t)B * 8, "log2_evidence"}, {workspace, (size_t)ws_bytes, "workspace"}};
+  for (const auto& o : out) {
+    for (const auto& i : in)
+      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
+    for (const auto& o2 : out)
+      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
+  }
+
+  PlArgs r;
+  PpArgs& a = r.p;
+  a.probs = probs;
+  a.state_class = state_class;
+  a.trans = trans;
+  a.init = init;
+  a.carry = nullptr;
+  a.posterior = a.class_posterior = nullptr;
+  a.filtered = filtered;
+  a.evidence = log2_evidence;
+  a.offsets = a.before = nullptr;
+  a.products = a.starts = a.ends = nullptr;
+  a.ld = ld;
+  a.T = T;
+  a.tiles = 0;
+  a.C = C;
+  a.S = S;
+  a.div_s = make_fastdiv((unsigned)S);
+  a.div_c = make_fastdiv((unsigned)C);
+  r.carry_in = static_cast<const char*>(carry_in);
+  r.carry_out = static_cast<char*>(carry_out);
+  r.lagged = lagged;
+  r.lagged_class = lagged_class;
+  r.ws_a = static_cast<float*>(workspace);
+  r.ws_e = reinterpret_cast<short*>(static_cast<char*>(workspace) + rows * S * 4);
+  r.seen = desc->seen;
+  r.g0 = span.g0;
+  r.g1 = span.g1;
+  r.carry_stride = stride;
+  r.lag = lag;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool small = S <= 16;
+  const size_t lds = pl_stream_lds_bytes(S);
+  static std::atomic<unsigned long long> raised[4] = {{0}, {0}, {0}, {0}};
+  auto stream_kernel = small ? (live ? pl_stream_kernel<true, true> : pl_stream_kernel<true, false>)
+                             : (live ? pl_stream_kernel<false, true> : pl_stream_kernel<false, false>);
+  if (lds > 64 * 1024)
+    if (int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(stream_kernel), (int)pl_stream_lds_bytes(PP_MAX_S),
+                                    raised[(small ? 2 : 0) + (live ? 1 : 0)]))
+      return rc;
+  hipLaunchKernelGGL(stream_kernel, dim3((unsigned)B), dim3(QT_WAVE), lds, s, r);
+  QT_CHECK_LAUNCH();
+  if (!live && count > 0) {
+    const unsigned grid = (unsigned)(B * ((count + PL_GROUP - 1) / PL_GROUP));
+    if (small) hipLaunchKernelGGL(pl_window_kernel<true>, dim3(grid), dim3(PL_WIN_THREADS), pl_window_lds_bytes(S), s, r);
+    else hipLaunchKernelGGL(pl_window_kernel<false>, dim3(grid), dim3(PL_WIN_THREADS), pl_window_lds_bytes(S), s, r);
+    QT_CHECK_LAUNCH();
+  }
   return QT_OK;
 }

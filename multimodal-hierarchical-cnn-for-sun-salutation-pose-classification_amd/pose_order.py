@@ -46,10 +46,26 @@ over the frames into float64 accumulators in a fixed order, the M-step turns the
 `fit(videos, iterations)` is that loop, `accumulate_paths(path)` adds the hard counts of state paths (a decoder's `path` for
 Viterbi training, or labelled steps), `tables()` returns numpy tables for saving.  An entry that starts at -65536 stays there.
 
+PoseLagSmoother and PoseLagDecoder (qt_pose_lag_smooth in csrc/pose_posterior.hip, qt_pose_lag_decode in csrc/pose_order.hip)
+are the two above for a loop that hands over a frame or a few per call: `push` returns the answer for the frames `lag` frames
+ago given everything up to now (the posterior over a window of lag + 1 frames, the path walked back from the filtered state lag
+frames later), a fixed delay behind the camera whose cost per step does not grow with the video.  The history of the last `lag`
+frames travels between calls in two carry buffers that the object swaps; for any split of a stream into pushes, flush on the
+last, the outputs are the bits of one push.
+
+    smoother = PoseLagSmoother(state_class, trans, device, lag=16, streams=16)
+    lagdec = PoseLagDecoder(state_class, trans, device, lag=16, streams=16)
+    for rows in live:                                               # f32 [streams, 1, C]: one frame per stream
+        first, lagged = smoother.push(rows)                         # frames first .. first + lagged.shape[1] - 1 (none while warming up)
+        _, lag_path = lagdec.push(rows)
+        confidence = smoother.confidence(lagged, lag_path)          # draw frame `first` from the ring of delayed frames
+    first, lagged = smoother.push(rows[:, :0], flush=True)          # the last lag frames, at the end of the video
+
 Not built: ragged batches (per-sequence lengths) and videos split across calls in the learner, learning emissions (they are the
-network's), tying rows, fixed-lag revision of earlier calls' paths and fixed-lag smoothing across calls, true minus-infinity
-(forbidden) transitions, S > 64, bf16 probabilities, a second level of the posterior's scan.  There is no torch fallback: CPU
-tensors and other dtypes raise QtError.
+network's), tying rows, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second level of the
+posterior's scan; for the fixed-lag pair: sliding-window products that share work between neighbouring windows (f32 (L, +) is
+not associative: the split contract would break), a tiled forward pass, streams that advance by different counts.  There is no
+torch fallback: CPU tensors and other dtypes raise QtError.
 """
 import ctypes
 
@@ -64,6 +80,7 @@ GROUP = 32                  # PO_GROUP: tiles per group of the two-level scan
 MAX_STATES = 64             # QT_POSE_ORDER_MAX_STATES
 MAX_CLASSES = 64            # QT_POSE_ORDER_MAX_CLASSES
 MAX_FRAMES = 1 << 20
+LAG_MAX = 63                # QT_POSE_LAG_MAX
 SCORE_FLOOR = -8192         # q of NaN and of everything below 2^-32
 TRANS_FLOOR = -65536
 # rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the table of csrc/pose_order.hip
@@ -90,6 +107,11 @@ class PoseOrderDesc(ctypes.Structure):   # qt_pose_order_desc
     _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int)]
 
 
+class PoseLagDesc(ctypes.Structure):     # qt_pose_lag_desc
+    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
+                ("lag", ctypes.c_int), ("flush", ctypes.c_int), ("seen", ctypes.c_longlong)]
+
+
 def bind(L):
     """argtypes of the entry points (idempotent)"""
     if getattr(L, "_pose_order_bound", False):
@@ -114,6 +136,16 @@ def bind(L):
     L.qt_pose_prior_count_paths.restype = ctypes.c_int
     L.qt_pose_prior_update.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 5
     L.qt_pose_prior_update.restype = ctypes.c_int
+    for name in ("qt_pose_lag_smooth_carry_bytes", "qt_pose_lag_smooth_workspace_bytes", "qt_pose_lag_decode_carry_bytes",
+                 "qt_pose_lag_decode_workspace_bytes"):
+        getattr(L, name).argtypes = [ctypes.POINTER(PoseLagDesc)]
+        getattr(L, name).restype = ctypes.c_longlong
+    L.qt_pose_lag_smooth.argtypes = [ctypes.POINTER(PoseLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 10 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_lag_smooth.restype = ctypes.c_int
+    L.qt_pose_lag_decode.argtypes = [ctypes.POINTER(PoseLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 8 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_lag_decode.restype = ctypes.c_int
     L._pose_order_bound = True
     return L
 
@@ -407,6 +439,144 @@ def _load_tables(obj, who, trans, init):
         obj.init = init.detach().clone().contiguous()
     else:
         obj.init.copy_(init)
+
+
+class _PoseLag:
+    """what PoseLagSmoother and PoseLagDecoder share: the tables, the count of frames seen (on the host: all streams advance
+    together), the two carry buffers that are swapped after every push, and a workspace that grows on demand"""
+    _carry_query = None
+
+    def __init__(self, state_class, trans, device, lag, streams=1, init=None, class_names=None):
+        who = type(self).__name__
+        sc, tr, init, self.class_names = _check_tables(who, state_class, trans, init, streams, class_names)
+        if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
+            raise ValueError(f"{who}: lag must be an integer in 0 .. {LAG_MAX} (got {lag!r})")
+        self.lag, self.num_states, self.streams = int(lag), int(sc.shape[0]), streams
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise QtError(f"{who} lives on an AMD GPU (device must be cuda:N); no CPU fallback")
+        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
+        self.trans = torch.from_numpy(np.ascontiguousarray(tr, np.int32)).to(device)
+        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
+        self.device = self.trans.device
+        self.seen = 0
+        desc = PoseLagDesc(streams, 1, 1, self.num_states, self.lag, 0, 0)
+        nbytes = int(getattr(bind(_lib.lib()), self._carry_query)(ctypes.byref(desc)))
+        self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=device) for _ in range(2)]    # [0]: the next call's carry_in
+        self._workspace = None
+
+    def reset(self):
+        """every stream starts anew (no host sync; the carry is not read at a stream's first frame)"""
+        self.seen = 0
+        return self
+
+    def load_tables(self, trans, init=None):
+        """a learner's tables (int32 tensors on this device) copied into this object's own, device to device and without a host
+        sync; every stream starts anew.  init None: no init from here on."""
+        _load_tables(self, f"{type(self).__name__}.load_tables", trans, init)
+        return self.reset()
+
+    def _probs(self, what, probs, flush):
+        if not isinstance(probs, torch.Tensor):
+            raise QtError(f"{what}: probs must be a tensor")
+        if probs.device.type != "cuda" or probs.device != self.device:
+            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
+        if probs.dtype != torch.float32:
+            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+        B = self.streams
+        flat = probs.dim() == 2
+        if flat and B == 1:
+            probs = probs.unsqueeze(0)
+        if probs.dim() != 3 or probs.shape[0] != B or not 1 <= probs.shape[2] <= MAX_CLASSES or (probs.shape[1] < 1 and not flush):
+            raise QtError(f"{what}: probs must be [{B}, frames, C]{' or [frames, C]' if B == 1 else ''} with C <= {MAX_CLASSES} "
+                          f"and frames >= 1, or 0 with flush (got {list(probs.shape)})")
+        T, C = probs.shape[1], probs.shape[2]
+        if B * T > MAX_FRAMES:
+            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+        probs = probs.detach()
+        if T and (probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1))):
+            probs = probs.contiguous()
+        first = max(0, self.seen - self.lag)
+        count = (self.seen + T if flush else max(0, self.seen + T - self.lag)) - first
+        return probs, flat, T, C, first, count, PoseLagDesc(B, T, C, self.num_states, self.lag, int(bool(flush)), self.seen)
+
+    def _room(self, query, desc):
+        need = int(query(ctypes.byref(desc)))
+        if need and (self._workspace is None or self._workspace.numel() < need):
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return (_lib.ptr(self._workspace), self._workspace.numel()) if need else (None, 0)
+
+    def _advance(self, T):
+        self.seen += T
+        self._carry.reverse()
+
+
+class PoseLagSmoother(_PoseLag):
+    """Fixed-lag posteriors of `streams` live videos over the decoder's chain: `push` takes the new frames and returns the
+    posterior of the frames `lag` frames ago given everything up to now.  Nothing is read back.  See the module text."""
+    _carry_query = "qt_pose_lag_smooth_carry_bytes"
+
+    def push(self, probs, flush=False, by_class=False, filtered=False):
+        """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device; frames may be 0
+        with flush.  Returns (first_frame, lagged f32 [streams, count, S] (or [count, S])), then as asked the class posterior
+        f32 [..., count, C] and the causal rows of the new frames f32 [..., frames, S]: lagged[:, k] belongs to frame
+        first_frame + k of the stream, count is frames once the stream is `lag` frames old, 0 before, and with flush also the
+        frames still pending."""
+        probs, flat, T, C, first, count, desc = self._probs("PoseLagSmoother.push", probs, flush)
+        B, S, dev = self.streams, self.num_states, self.device
+        lead = (lambda n: (n,)) if flat else (lambda n: (B, n))
+        lagged = torch.empty(lead(count) + (S,), dtype=torch.float32, device=dev)
+        cls = torch.empty(lead(count) + (C,), dtype=torch.float32, device=dev) if by_class else None
+        filt = torch.empty(lead(T) + (S,), dtype=torch.float32, device=dev) if filtered else None
+        L = bind(_lib.lib())
+        ws, ws_bytes = self._room(L.qt_pose_lag_smooth_workspace_bytes, desc)
+        with torch.cuda.device(dev):
+            _lib.check(L.qt_pose_lag_smooth(ctypes.byref(desc), _lib.ptr(probs) if T else None, probs.stride(1) if T else C,
+                                            _lib.ptr(self.state_class), _lib.ptr(self.trans), _lib.ptr(self.init),
+                                            _lib.ptr(self._carry[0]) if self.seen else None, _lib.ptr(self._carry[1]),
+                                            _lib.ptr(lagged) if count else None, _lib.ptr(cls) if count else None,
+                                            _lib.ptr(filt) if T else None, None, ws, ws_bytes, _lib.stream_ptr()),
+                       "qt_pose_lag_smooth")
+        self._advance(T)
+        return (first, lagged) + tuple(t for t in (cls, filt) if t is not None)
+
+    def confidence(self, lagged, lag_path):
+        """f32 [streams, count] (or [count]): the lagged posterior at the states of `lag_path` (a PoseLagDecoder's push of the
+        same frames, int64).  Plain torch, nothing read back."""
+        if not isinstance(lagged, torch.Tensor) or lagged.device != self.device or lagged.dtype != torch.float32:
+            raise QtError(f"PoseLagSmoother.confidence: lagged must be an f32 tensor on {self.device}")
+        if not isinstance(lag_path, torch.Tensor) or lag_path.device != self.device or lag_path.dtype != torch.int64:
+            raise QtError(f"PoseLagSmoother.confidence: lag_path must be an int64 tensor on {self.device}")
+        if lagged.shape[:-1] != lag_path.shape or lagged.shape[-1] != self.num_states:
+            raise QtError(f"PoseLagSmoother.confidence: lagged {list(lagged.shape)} and lag_path {list(lag_path.shape)} do not "
+                          f"belong together ({self.num_states} states)")
+        return lagged.gather(-1, lag_path.unsqueeze(-1)).squeeze(-1)
+
+
+class PoseLagDecoder(_PoseLag):
+    """Fixed-lag paths of `streams` live videos: `push` takes the new frames and returns, for the frames `lag` frames ago, the
+    state on the best path that ends at the newest frame.  The joined lag_path is what PoseOrderDecoder.cycles counts rounds
+    on.  Nothing is read back.  See the module text."""
+    _carry_query = "qt_pose_lag_decode_carry_bytes"
+
+    def push(self, probs, flush=False, filtered=False):
+        """probs as PoseLagSmoother.push.  Returns (first_frame, lag_path int64 [streams, count] (or [count])), then with
+        filtered=True the causal states of the new frames int64 [..., frames]."""
+        probs, flat, T, C, first, count, desc = self._probs("PoseLagDecoder.push", probs, flush)
+        B, dev = self.streams, self.device
+        lead = (lambda n: (n,)) if flat else (lambda n: (B, n))
+        path = torch.empty(lead(count), dtype=torch.int64, device=dev)
+        filt = torch.empty(lead(T), dtype=torch.int64, device=dev) if filtered else None
+        L = bind(_lib.lib())
+        ws, ws_bytes = self._room(L.qt_pose_lag_decode_workspace_bytes, desc)
+        with torch.cuda.device(dev):
+            _lib.check(L.qt_pose_lag_decode(ctypes.byref(desc), _lib.ptr(probs) if T else None, probs.stride(1) if T else C,
+                                            _lib.ptr(self.state_class), _lib.ptr(self.trans), _lib.ptr(self.init),
+                                            _lib.ptr(self._carry[0]) if self.seen else None, _lib.ptr(self._carry[1]),
+                                            _lib.ptr(path) if count else None, _lib.ptr(filt) if T else None, ws, ws_bytes,
+                                            _lib.stream_ptr()), "qt_pose_lag_decode")
+        self._advance(T)
+        return (first, path) + ((filt,) if filtered else ())
 
 
 class PoseOrderLearner:
