@@ -969,7 +969,7 @@ int qt_timeline_decode(const qt_timeline_desc* desc, const long long* pred, cons
  *   p is NaN or p < 2^-32 (negatives, zeros, denormals): q = -8192
  *   p >= 1 (+inf too):                                    q = 0
  *   otherwise:  q = 256 ((b >> 23) - 127) + LOG2_TABLE[(b >> 15) & 255],  LOG2_TABLE[i] = rint(256 log2(1 + (2 i + 1) / 512))
- * (1, 2, 4, 5 ... 254, 255, 256; no entry is closer than 0.0015 to a half; the table is written out in csrc/pose_order.hip).
+ * (1, 2, 4, 5 ... 254, 255, 256; no entry is closer than 0.0015 to a half; the table is written out in csrc/pose_chain.h).
  * q stays within 1.25 units of 256 log2 p, and no logf enters the rule.  e[f][s] = q(probs[f][state_class[s]]).
  * Forward, per stream, frame by frame; d is the previous frame's scores: init for the stream's first frame (frames_seen ==
  * 0), carry.delta otherwise:

@@ -331,7 +331,6 @@ __global__ __launch_bounds__(MET_THREADS) void metrics_finalize_kernel(const uns
 }
 
 inline int met_lanes(int C) { return C <= 16 ? 1 : C <= 64 ? 16 : 64; }
-inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 }  // namespace
 

@@ -3,15 +3,18 @@
 // (an emission is log2 p in units of 1/256 bit, taken from the float's bit pattern; transitions are int32), so (max, +)
 // products are exactly associative and a chain of `frames` dependent steps can be cut into tiles that run in parallel and
 // still give the bits of the frame-by-frame rule.  include/qtcnn.h states the rule in full; the reference has no such step.
+// pose_chain.h holds what this file shares with pose_posterior.hip and pose_prior.hip: the limits PC_*, the emission rule
+// (pc_q, its table, pc_stage_emissions), the chain's inputs PcChain at the head of every argument struct, and the host's
+// descriptor checks, fixed-lag route and span, overlap check and S <= 16 launch switch.  Here: the integer kernels.
 //
-// Short route (frames <= PO_TILE): one launch, one wave per stream, no workspace.  The tile's emissions, the transition
+// Short route (frames <= PC_TILE): one launch, one wave per stream, no workspace.  The tile's emissions, the transition
 // table, psi and delta are in LDS.  Forward with lane = state j: a step is S times { v_readlane of d[i], add the table entry,
 // max }, where value and predecessor travel in one integer, key = 64 (d[i] + trans[i][j]) + (63 - i): the maximum key is the
 // maximum value at the lowest i.  For S <= 16 lane j keeps its table column in registers, the sixteen candidates (slots beyond
 // S repeat candidate 0, which changes no maximum and needs no branch) are formed independently and meet in a tree of maxima: a
 // frame is five dependent steps deep; above that four maxima run side by side over the table in LDS.
 // Then filtered (lane = frame, the delta rows padded to an odd stride), the backtrace through psi, the carry.
-// Tiled route (frames > PO_TILE), five launches (seven above 32 tiles), M_f[i][j] = trans[i][j] + e[f][j]:
+// Tiled route (frames > PC_TILE), five launches (seven above 32 tiles), M_f[i][j] = trans[i][j] + e[f][j]:
 //   (a) po_products: a workgroup of 256 per (stream, tile but the last) forms P = M_a (x) ... (x) M_b in LDS, thread = (i, j),
 //       two buffers in turn, one barrier per frame, and writes it to the workspace;
 //   (b) po_scan carries a start vector through products in order: wave 0 with lane = j in int32 against an int64 offset, all
@@ -37,17 +40,10 @@
 #include <limits.h>
 #include <stdint.h>
 
-#include "qt_common.h"
-#include "qt_internal.h"
+#include "pose_chain.h"
 
 namespace {
 
-constexpr int PO_TILE = 64;                      // frames per tile; frames <= PO_TILE take the short route
-constexpr int PO_MAX_S = 64;
-constexpr int PO_MAX_C = 64;
-constexpr long long PO_MAX_FRAMES = 1LL << 20;
-constexpr int PO_FLOOR = -8192;                  // q of NaN and of everything below 2^-32
-constexpr int PO_TRANS_FLOOR = -65536;
 constexpr int PO_LOW = -(1 << 24);               // a start vector is taken relative to its maximum and not below this (a carry
                                                  // written by this kernel spreads over 73,728 at the most): 64 frames further
                                                  // down the key 64 v + r still fits 32 bits
@@ -57,36 +53,9 @@ constexpr int PO_GROUP = 32;                     // (b): tiles per group: the sc
 constexpr int PO_WALK_TILES = 256;               // (d): back-maps staged at a time
 constexpr int PO_PROD_THREADS = 256;
 constexpr int PO_SCAN_THREADS = 256;
-static_assert(PO_TILE == QT_POSE_ORDER_TILE && PO_MAX_S == QT_POSE_ORDER_MAX_STATES && PO_MAX_C == QT_POSE_ORDER_MAX_CLASSES,
-              "the header states these");
-static_assert(PO_TILE == QT_WAVE, "lane = frame where a tile's frames are spread over a wave");
-static_assert(PO_SCAN_INTS >= PO_MAX_S * PO_MAX_S && PO_SCAN_INTS % PO_SCAN_THREADS == 0, "a trip holds at least one product");
+static_assert(PO_SCAN_INTS >= PC_MAX_S * PC_MAX_S && PO_SCAN_INTS % PO_SCAN_THREADS == 0, "a trip holds at least one product");
 
-// rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255 (no entry closer than 0.0015 to a half)
-__device__ const unsigned short PO_LOG2[256] = {
-      1,   2,   4,   5,   6,   8,   9,  11,  12,  13,  15,  16,  18,  19,  20,  22,
-     23,  24,  26,  27,  28,  30,  31,  32,  34,  35,  36,  38,  39,  40,  42,  43,
-     44,  45,  47,  48,  49,  50,  52,  53,  54,  55,  57,  58,  59,  60,  62,  63,
-     64,  65,  66,  68,  69,  70,  71,  72,  74,  75,  76,  77,  78,  80,  81,  82,
-     83,  84,  85,  86,  88,  89,  90,  91,  92,  93,  94,  95,  97,  98,  99, 100,
-    101, 102, 103, 104, 105, 106, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117,
-    118, 119, 120, 121, 122, 123, 124, 125, 126, 127, 128, 129, 131, 132, 133, 134,
-    135, 136, 137, 138, 139, 140, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149,
-    150, 151, 152, 153, 154, 155, 156, 157, 158, 159, 160, 161, 162, 163, 163, 164,
-    165, 166, 167, 168, 169, 170, 171, 172, 173, 173, 174, 175, 176, 177, 178, 179,
-    180, 181, 182, 182, 183, 184, 185, 186, 187, 188, 189, 189, 190, 191, 192, 193,
-    194, 195, 195, 196, 197, 198, 199, 200, 200, 201, 202, 203, 204, 205, 205, 206,
-    207, 208, 209, 210, 210, 211, 212, 213, 214, 214, 215, 216, 217, 218, 218, 219,
-    220, 221, 222, 222, 223, 224, 225, 226, 226, 227, 228, 229, 229, 230, 231, 232,
-    233, 233, 234, 235, 236, 236, 237, 238, 239, 239, 240, 241, 242, 242, 243, 244,
-    245, 245, 246, 247, 248, 248, 249, 250, 251, 251, 252, 253, 253, 254, 255, 256
-};
-
-struct PoArgs {
-  const float* probs;
-  const int* state_class;
-  const int* trans;
-  const int* init;
+struct PoArgs : PcChain {
   long long* carry;
   long long* path;
   long long* filtered;
@@ -98,33 +67,8 @@ struct PoArgs {
   int* ends;                 //            int32 [batch][tiles]
   unsigned char* psi;        //            [batch][T][S]
   unsigned char* back;       //            [batch][tiles][S]
-  long long ld;
-  int T, tiles, groups, C, S, mode;
-  FastDiv div_s;
+  int groups, mode;
 };
-
-__device__ __forceinline__ int po_q(float p) {
-  if (!(p >= 0x1p-32f)) return PO_FLOOR;         // NaN, negatives, zeros, denormals
-  if (p >= 1.0f) return 0;
-  const unsigned b = __float_as_uint(p);
-  return 256 * ((int)(b >> 23) - 127) + (int)PO_LOG2[(b >> 15) & 255u];
-}
-__device__ __forceinline__ int po_clamp_trans(int v) { return min(max(v, PO_TRANS_FLOOR), 0); }
-
-// the emissions of frames [f0, f0 + n) of stream b into e_l [n][S] (and to the emissions output when asked)
-__device__ __forceinline__ void po_stage_emissions(const PoArgs& a, int b, int f0, int n, short* e_l, bool write_out) {
-  const int S = a.S;
-  const float* __restrict__ p = a.probs + ((long long)b * a.T + f0) * a.ld;
-  int* __restrict__ out = write_out && a.emissions ? a.emissions + ((long long)b * a.T + f0) * S : nullptr;
-  for (int idx = threadIdx.x; idx < n * S; idx += blockDim.x) {
-    const int f = (int)fdiv((unsigned)idx, a.div_s), s = idx - f * S;
-    const int k = a.state_class[s];
-    int e = PO_FLOOR;
-    if ((unsigned)k < (unsigned)a.C) e = po_q(p[(long long)f * a.ld + k]);
-    e_l[idx] = (short)e;
-    if (out) out[idx] = e;
-  }
-}
 
 __device__ __forceinline__ int po_max16(int (&t)[16]) {
 #pragma unroll
@@ -153,7 +97,7 @@ __device__ __forceinline__ int po_wave_max(int v) {
 __device__ __forceinline__ long long po_stream_start(const PoArgs& a, int b, int lane) {
   if (lane >= a.S) return LLONG_MIN;
   const long long* __restrict__ c = a.carry + (long long)b * (a.S + 2);
-  if (c[0] == 0) return a.init ? (long long)po_clamp_trans(a.init[lane]) : 0;
+  if (c[0] == 0) return a.init ? (long long)pc_clamp_trans(a.init[lane]) : 0;
   return c[2 + lane];
 }
 // D relative to its maximum over the states, as the int32 the tile works in; lanes >= S hold LLONG_MIN and get PO_LOW
@@ -166,27 +110,27 @@ __device__ __forceinline__ int po_normalise(long long D, long long& mx) {
 // the LDS of the one-wave kernels
 struct PoLds {
   int* tk;               // [S][S]: 64 trans[i][j] + (63 - i)
-  int* dl;               // [PO_TILE][S | 1]: delta
-  int* path;             // [PO_TILE]
-  short* e;              // [PO_TILE][S]
-  unsigned char* psi;    // [PO_TILE][S]
+  int* dl;               // [PC_TILE][S | 1]: delta
+  int* path;             // [PC_TILE]
+  short* e;              // [PC_TILE][S]
+  unsigned char* psi;    // [PC_TILE][S]
 };
 __device__ __forceinline__ PoLds po_carve(int* lds, int S) {
   PoLds l;
   l.tk = lds;
   l.dl = l.tk + S * S;
-  l.path = l.dl + PO_TILE * (S | 1);
-  l.e = reinterpret_cast<short*>(l.path + PO_TILE);
-  l.psi = reinterpret_cast<unsigned char*>(l.e + PO_TILE * S);
+  l.path = l.dl + PC_TILE * (S | 1);
+  l.e = reinterpret_cast<short*>(l.path + PC_TILE);
+  l.psi = reinterpret_cast<unsigned char*>(l.e + PC_TILE * S);
   return l;
 }
-inline size_t po_wave_lds_bytes(int S) { return 4 * ((size_t)S * S + PO_TILE * (S | 1) + PO_TILE) + 2 * PO_TILE * S + PO_TILE * S; }
+inline size_t po_wave_lds_bytes(int S) { return 4 * ((size_t)S * S + PC_TILE * (S | 1) + PC_TILE) + 2 * PC_TILE * S + PC_TILE * S; }
 
-__device__ __forceinline__ void po_stage_keys(const PoArgs& a, int* tk) {
+__device__ __forceinline__ void po_stage_keys(const PcChain& a, int* tk) {
   const int S = a.S;
   for (int idx = threadIdx.x; idx < S * S; idx += blockDim.x) {
     const int i = (int)fdiv((unsigned)idx, a.div_s);
-    tk[idx] = po_clamp_trans(a.trans[idx]) * 64 + (63 - i);
+    tk[idx] = pc_clamp_trans(a.trans[idx]) * 64 + (63 - i);
   }
 }
 
@@ -232,16 +176,21 @@ __device__ __forceinline__ void po_forward(const PoLds& l, int n, int S, int lan
   }
 }
 
-// filtered of the n frames whose delta is in LDS, lane = frame; writes the output when asked.  end / m: the last frame's
-// state and score (wave-uniform).
-__device__ __forceinline__ void po_filtered(const PoArgs& a, const PoLds& l, int b, int f0, int n, int lane, int& end, int& m) {
-  const int S = a.S, SP = S | 1;
+// the filtered state bj of the lane's frame and its score bv (lane = frame; lanes >= n take frame n - 1) among the n frames
+// whose delta is in LDS, rows SP = S | 1 apart: the lowest state at the row's maximum.  The caller broadcasts what it needs.
+__device__ __forceinline__ void po_row_argmax(const PoLds& l, int S, int SP, int n, int lane, int& bv, int& bj) {
   const int* __restrict__ row = l.dl + min(lane, n - 1) * SP;
-  int bv = row[0], bj = 0;
+  bv = row[0], bj = 0;
   for (int j = 1; j < S; ++j) {
     const int v = row[j];
     if (v > bv) bv = v, bj = j;
   }
+}
+// filtered of those n frames to the output when asked.  end / m: the last frame's state and score (wave-uniform).
+__device__ __forceinline__ void po_filtered(const PoArgs& a, const PoLds& l, int b, int f0, int n, int lane, int& end, int& m) {
+  const int S = a.S, SP = S | 1;
+  int bv, bj;
+  po_row_argmax(l, S, SP, n, lane, bv, bj);
   if (a.filtered && lane < n) a.filtered[(long long)b * a.T + f0 + lane] = (long long)bj;
   end = __builtin_amdgcn_readlane(bj, n - 1);
   m = __builtin_amdgcn_readlane(bv, n - 1);
@@ -281,9 +230,9 @@ __global__ __launch_bounds__(QT_WAVE) void po_stream_kernel(PoArgs a) {
   int d = po_normalise(po_stream_start(a, b, lane), base);
   int end = 0, m = 0;
   for (int tile = 0; tile < a.tiles; ++tile) {
-    const int f0 = tile * PO_TILE, n = min(PO_TILE, a.T - f0);
+    const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
     __syncthreads();
-    po_stage_emissions(a, b, f0, n, l.e, true);
+    pc_stage_emissions(a, b, f0, n, l.e, a.emissions);
     __syncthreads();
     po_forward<SMALL>(l, n, S, lane, d);
     __syncthreads();
@@ -301,7 +250,7 @@ __global__ __launch_bounds__(QT_WAVE) void po_stream_kernel(PoArgs a) {
   po_write_carry(a, b, lane, d, m, base);
   int s = end;
   for (int tile = a.tiles - 1; tile >= 0; --tile) {
-    const int f0 = tile * PO_TILE, n = min(PO_TILE, a.T - f0);
+    const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
     if (a.tiles > 1) {
       __syncthreads();
       const unsigned char* __restrict__ in = a.psi + ((long long)b * a.T + f0) * S;
@@ -315,18 +264,21 @@ __global__ __launch_bounds__(QT_WAVE) void po_stream_kernel(PoArgs a) {
 // ---- (a) tile products ------------------------------------------------------------------------------------------------------
 // SMALL: S <= 16, so a thread owns one (i, j) for the whole tile: its column of trans stays in registers, and a frame is sixteen
 // independent candidates (slots beyond S repeat candidate 0) and a tree of maxima.
+// `tiles` (= a.tiles) is an argument of its own on purpose: read out of the struct it rides in the load of T, C and S, the
+// prologue is one s_load shorter, the frame loop sits 8 bytes lower in the code object, and the kernel takes 20.4 instead of
+// 19.3 us at 64 x 256 frames (EXPERIMENTS.md, "Pose-chain refactor"); with it the loop is where it has been measured.
 template <bool SMALL>
-__global__ __launch_bounds__(PO_PROD_THREADS) void po_products_kernel(PoArgs a) {
+__global__ __launch_bounds__(PO_PROD_THREADS) void po_products_kernel(PoArgs a, int tiles) {
   extern __shared__ __attribute__((aligned(16))) int po_lds[];
   const int S = a.S, SS = S * S, tid = threadIdx.x;
   int* tr = po_lds;
   int* cur = tr + SS;
   int* nxt = cur + SS;
   short* e_l = reinterpret_cast<short*>(nxt + SS);
-  const int per = a.tiles - 1;
+  const int per = tiles - 1;
   const int b = blockIdx.x / per, tile = blockIdx.x - b * per;
-  for (int idx = tid; idx < SS; idx += PO_PROD_THREADS) tr[idx] = po_clamp_trans(a.trans[idx]);
-  po_stage_emissions(a, b, tile * PO_TILE, PO_TILE, e_l, false);   // (never a stream's last tile: PO_TILE frames)
+  for (int idx = tid; idx < SS; idx += PO_PROD_THREADS) tr[idx] = pc_clamp_trans(a.trans[idx]);
+  pc_stage_emissions(a, b, tile * PC_TILE, PC_TILE, e_l);   // (never a stream's last tile: PC_TILE frames)
   __syncthreads();
   for (int idx = tid; idx < SS; idx += PO_PROD_THREADS) {
     const int i = (int)fdiv((unsigned)idx, a.div_s);
@@ -339,7 +291,7 @@ __global__ __launch_bounds__(PO_PROD_THREADS) void po_products_kernel(PoArgs a) 
 #pragma unroll
     for (int k = 0; k < 16; ++k) col[k] = tr[(k < S ? k : 0) * S + own_j];
   }
-  for (int f = 1; f < PO_TILE; ++f) {
+  for (int f = 1; f < PC_TILE; ++f) {
     if (SMALL) {
       int t[16];
 #pragma unroll
@@ -530,9 +482,9 @@ __global__ __launch_bounds__(QT_WAVE) void po_replay_kernel(PoArgs a) {
   const PoLds l = po_carve(po_lds, a.S);
   const int lane = threadIdx.x, S = a.S;
   const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-  const int f0 = tile * PO_TILE, n = min(PO_TILE, a.T - f0);
+  const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
   po_stage_keys(a, l.tk);
-  po_stage_emissions(a, b, f0, n, l.e, true);
+  pc_stage_emissions(a, b, f0, n, l.e, a.emissions);
   long long base;
   int d = po_normalise(lane < S ? a.starts[((long long)b * a.tiles + tile) * S + lane] : LLONG_MIN, base);
   __syncthreads();
@@ -556,7 +508,7 @@ __global__ __launch_bounds__(QT_WAVE) void po_replay_kernel(PoArgs a) {
 
 // ---- (d) end states, then every tile's path -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(QT_WAVE) void po_walk_kernel(PoArgs a) {
-  __shared__ unsigned char maps[PO_WALK_TILES * PO_MAX_S];
+  __shared__ unsigned char maps[PO_WALK_TILES * PC_MAX_S];
   __shared__ int ends_l[PO_WALK_TILES];
   const int lane = threadIdx.x, b = blockIdx.x, S = a.S;
   int* __restrict__ ends = a.ends + (long long)b * a.tiles;
@@ -582,7 +534,7 @@ __global__ __launch_bounds__(QT_WAVE) void po_backtrace_kernel(PoArgs a) {
   const PoLds l = po_carve(po_lds, a.S);
   const int lane = threadIdx.x, S = a.S;
   const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-  const int f0 = tile * PO_TILE, n = min(PO_TILE, a.T - f0);
+  const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
   int s;
   if (a.mode == 2) {   // every tile walks from the stream's end to itself
     s = a.ends[(long long)b * a.tiles + a.tiles - 1];
@@ -593,7 +545,7 @@ __global__ __launch_bounds__(QT_WAVE) void po_backtrace_kernel(PoArgs a) {
   }
   if (a.mode == 3) {   // psi by a second replay
     po_stage_keys(a, l.tk);
-    po_stage_emissions(a, b, f0, n, l.e, false);
+    pc_stage_emissions(a, b, f0, n, l.e);
     long long base;
     int d = po_normalise(lane < S ? a.starts[((long long)b * a.tiles + tile) * S + lane] : LLONG_MIN, base);
     __syncthreads();
@@ -606,37 +558,14 @@ __global__ __launch_bounds__(QT_WAVE) void po_backtrace_kernel(PoArgs a) {
   po_backtrace(a, l, b, f0, n, lane, s);
 }
 
-inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-inline bool overlap(const void* p, size_t pbytes, const void* q, size_t qbytes) {
-  if (!p || !q || !pbytes || !qbytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + qbytes && b < a + pbytes;
-}
-
-int check_desc(const char* who, const qt_pose_order_desc* d) {
-  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  QT_CHECK_ARG(d->batch >= 1, "%s: batch must be positive (got %d)", who, d->batch);
-  QT_CHECK_ARG(d->frames >= 1, "%s: frames must be positive (got %d)", who, d->frames);
-  QT_CHECK_ARG(d->num_classes >= 1 && d->num_classes <= PO_MAX_C, "%s: num_classes = %d; 1 .. %d are handled", who,
-               d->num_classes, PO_MAX_C);
-  QT_CHECK_ARG(d->num_states >= 1 && d->num_states <= PO_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who, d->num_states,
-               PO_MAX_S);
-  const long long frames = (long long)d->batch * d->frames;
-  if (frames > PO_MAX_FRAMES) {
-    qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, frames, PO_MAX_FRAMES);
-    return QT_ERR_UNSUPPORTED;
-  }
-  return QT_OK;
-}
-
 // the workspace of the tiled route, sections in the order of their alignment
 struct PoLayout {
   long long starts, gstarts, products, gproducts, ends, psi, back, total;
 };
 PoLayout po_layout(const qt_pose_order_desc* d) {
   PoLayout w = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (d->frames <= PO_TILE) return w;
-  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PO_TILE);
+  if (d->frames <= PC_TILE) return w;
+  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PC_TILE);
   const long long groups = qt_cdiv(tiles, PO_GROUP);
   w.starts = 0;
   w.gstarts = w.starts + B * tiles * S * 8;
@@ -652,7 +581,7 @@ PoLayout po_layout(const qt_pose_order_desc* d) {
 }  // namespace
 
 extern "C" long long qt_pose_order_workspace_bytes(const qt_pose_order_desc* desc) {
-  if (check_desc("qt_pose_order_workspace_bytes", desc) != QT_OK) return 0;
+  if (pc_check_desc("qt_pose_order_workspace_bytes", desc) != QT_OK) return 0;
   return po_layout(desc).total;
 }
 
@@ -660,7 +589,7 @@ extern "C" int qt_pose_order_decode(const qt_pose_order_desc* desc, const float*
                                     const int* trans, const int* init, long long* carry, long long* path, long long* filtered,
                                     int* emissions, void* workspace, long long workspace_bytes, void* stream) {
   const char* const who = "qt_pose_order_decode";
-  if (const int rc = check_desc(who, desc)) return rc;
+  if (const int rc = pc_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
   QT_CHECK_ARG(probs != nullptr && state_class != nullptr && trans != nullptr && carry != nullptr && path != nullptr,
@@ -675,24 +604,16 @@ extern "C" int qt_pose_order_decode(const qt_pose_order_desc* desc, const float*
                "%s: workspace of %lld bytes; qt_pose_order_workspace_bytes asks for %lld", who, workspace ? workspace_bytes : 0LL,
                w.total);
   const long long rows = (long long)B * T;
-  const struct { const void* p; size_t bytes; const char* name; } in[] = {
-      {probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
-      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}},
-    out[] = {{carry, (size_t)B * (S + 2) * 8, "carry"}, {path, (size_t)rows * 8, "path"}, {filtered, (size_t)rows * 8, "filtered"},
-             {emissions, (size_t)rows * S * 4, "emissions"}, {workspace, (size_t)w.total, "workspace"}};
-  for (const auto& o : out) {
-    for (const auto& i : in)
-      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
-    for (const auto& o2 : out)
-      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
-  }
+  const PcBuf in[] = {{probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
+                      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}};
+  const PcBuf out[] = {{carry, (size_t)B * (S + 2) * 8, "carry"}, {path, (size_t)rows * 8, "path"},
+                       {filtered, (size_t)rows * 8, "filtered"}, {emissions, (size_t)rows * S * 4, "emissions"},
+                       {workspace, (size_t)w.total, "workspace"}};
+  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
 
-  const int env_mode = desc->frames > PO_TILE ? qt_env_int("QTCNN_POSE_ORDER", 0) : 0;   // per call: see the head of the file
+  const int env_mode = desc->frames > PC_TILE ? qt_env_int("QTCNN_POSE_ORDER", 0) : 0;   // per call: see the head of the file
   PoArgs a;
-  a.probs = probs;
-  a.state_class = state_class;
-  a.trans = trans;
-  a.init = init;
+  pc_fill(a, probs, ld, state_class, trans, init, T, C, S);
   a.carry = carry;
   a.path = path;
   a.filtered = filtered;
@@ -705,50 +626,40 @@ extern "C" int qt_pose_order_decode(const qt_pose_order_desc* desc, const float*
   a.ends = reinterpret_cast<int*>(ws + w.ends);
   a.psi = reinterpret_cast<unsigned char*>(ws + w.psi);
   a.back = reinterpret_cast<unsigned char*>(ws + w.back);
-  a.ld = ld;
-  a.T = T;
-  a.tiles = qt_cdiv(T, PO_TILE);
   a.groups = qt_cdiv(a.tiles, PO_GROUP);
-  a.C = C;
-  a.S = S;
   a.mode = a.tiles > 1 && env_mode >= 1 && env_mode <= 3 ? env_mode : 0;
-  a.div_s = make_fastdiv((unsigned)S);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = S <= 16;
   const size_t wave_lds = po_wave_lds_bytes(S);
+  const dim3 wave(QT_WAVE), prod(PO_PROD_THREADS), scan(PO_SCAN_THREADS);
   if (a.tiles == 1 || a.mode == 1) {
-    if (small) hipLaunchKernelGGL(po_stream_kernel<true>, dim3((unsigned)B), dim3(QT_WAVE), wave_lds, s, a);
-    else hipLaunchKernelGGL(po_stream_kernel<false>, dim3((unsigned)B), dim3(QT_WAVE), wave_lds, s, a);
+    const dim3 streams((unsigned)B);
+    pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(po_stream_kernel<PC_SMALL(sm)>, streams, wave, wave_lds, s, a); });
     QT_CHECK_LAUNCH();
     return QT_OK;
   }
-  const unsigned all = (unsigned)((long long)B * a.tiles), inner = (unsigned)((long long)B * (a.tiles - 1));
-  const size_t prod_lds = 4 * 3 * (size_t)S * S + 2 * PO_TILE * S;
-  if (small) hipLaunchKernelGGL(po_products_kernel<true>, dim3(inner), dim3(PO_PROD_THREADS), prod_lds, s, a);
-  else hipLaunchKernelGGL(po_products_kernel<false>, dim3(inner), dim3(PO_PROD_THREADS), prod_lds, s, a);
+  const dim3 all((unsigned)((long long)B * a.tiles)), inner((unsigned)((long long)B * (a.tiles - 1)));
+  const size_t prod_lds = 4 * 3 * (size_t)S * S + 2 * PC_TILE * S;
+  pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(po_products_kernel<PC_SMALL(sm)>, inner, prod, prod_lds, s, a, a.tiles); });
   QT_CHECK_LAUNCH();
   if (a.groups > 1) {
     const dim3 full((unsigned)((long long)B * (a.groups - 1)));
-    if (small) hipLaunchKernelGGL(po_group_products_kernel<true>, full, dim3(PO_PROD_THREADS), 4 * 3 * (size_t)S * S, s, a);
-    else hipLaunchKernelGGL(po_group_products_kernel<false>, full, dim3(PO_PROD_THREADS), 4 * 3 * (size_t)S * S, s, a);
+    pc_by_small(S, [&](auto sm) {
+      hipLaunchKernelGGL(po_group_products_kernel<PC_SMALL(sm)>, full, prod, 4 * 3 * (size_t)S * S, s, a);
+    });
     QT_CHECK_LAUNCH();
-    if (small) hipLaunchKernelGGL(po_scan_kernel<true>, dim3((unsigned)B), dim3(PO_SCAN_THREADS), 0, s, a, 2);
-    else hipLaunchKernelGGL(po_scan_kernel<false>, dim3((unsigned)B), dim3(PO_SCAN_THREADS), 0, s, a, 2);
+    pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(po_scan_kernel<PC_SMALL(sm)>, dim3((unsigned)B), scan, 0, s, a, 2); });
     QT_CHECK_LAUNCH();
   }
-  const unsigned scans = (unsigned)((long long)B * a.groups);
-  if (small) hipLaunchKernelGGL(po_scan_kernel<true>, dim3(scans), dim3(PO_SCAN_THREADS), 0, s, a, 1);
-  else hipLaunchKernelGGL(po_scan_kernel<false>, dim3(scans), dim3(PO_SCAN_THREADS), 0, s, a, 1);
+  const dim3 scans((unsigned)((long long)B * a.groups));
+  pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(po_scan_kernel<PC_SMALL(sm)>, scans, scan, 0, s, a, 1); });
   QT_CHECK_LAUNCH();
-  if (small) hipLaunchKernelGGL(po_replay_kernel<true>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
-  else hipLaunchKernelGGL(po_replay_kernel<false>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
+  pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(po_replay_kernel<PC_SMALL(sm)>, all, wave, wave_lds, s, a); });
   QT_CHECK_LAUNCH();
   if (a.mode != 2) {
-    hipLaunchKernelGGL(po_walk_kernel, dim3((unsigned)B), dim3(QT_WAVE), 0, s, a);
+    hipLaunchKernelGGL(po_walk_kernel, dim3((unsigned)B), wave, 0, s, a);
     QT_CHECK_LAUNCH();
   }
-  if (small) hipLaunchKernelGGL(po_backtrace_kernel<true>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
-  else hipLaunchKernelGGL(po_backtrace_kernel<false>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
+  pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(po_backtrace_kernel<PC_SMALL(sm)>, all, wave, wave_lds, s, a); });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -757,7 +668,7 @@ extern "C" int qt_pose_order_decode(const qt_pose_order_desc* desc, const float*
 // lag_path[g] is the state at frame g of the best path that ends at frame w = min(g + lag, the call's last frame): the forward
 // pass is the integer rule above (po_forward as it is, the scores taken relative to their maximum after every chunk), and every
 // emitted frame walks psi back from filtered[w].  Frames carry global indices; the LDS rings hold psi and filtered of frame g in
-// row g & 127, and the forward pass goes in chunks that end on multiples of PO_TILE so that a chunk's rows are one run.
+// row g & 127, and the forward pass goes in chunks that end on multiples of PC_TILE so that a chunk's rows are one run.
 // Live route: pld_stream_kernel<LIVE>, one launch, one wave per stream; the walks run with lane = emitted frame, lag byte reads
 // each.  Batch route: the same forward pass leaves psi and filtered of the new frames in the workspace, and pld_walk_kernel
 // walks with one thread per emitted frame, psi from the workspace or from carry_in's history.  Integers: the same bits.
@@ -767,14 +678,13 @@ extern "C" int qt_pose_order_decode(const qt_pose_order_desc* desc, const float*
 namespace {
 
 constexpr int PLD_RING = 128;
-constexpr int PLD_LAG_MAX = 63;
 constexpr int PLD_WALK_THREADS = 256;
 constexpr long long PLD_LIVE_STEPS = 4096;
-static_assert(PLD_LAG_MAX == QT_POSE_LAG_MAX && PLD_LAG_MAX + PO_TILE < PLD_RING && (PLD_RING & (PLD_RING - 1)) == 0,
+static_assert(PC_LAG_MAX + PC_TILE < PLD_RING && (PLD_RING & (PLD_RING - 1)) == 0,
               "the ring holds a chunk and its windows");
 
-struct PldArgs {
-  PoArgs p;                  // probs, state_class, trans, init, filtered, ld, T (= n), C, S, div_s; the rest unused
+struct PldArgs : PcChain {   // T: the new frames of the call (tiles: not read)
+  long long* filtered;
   const char* carry_in;
   char* carry_out;
   long long* lag_path;
@@ -800,28 +710,28 @@ __device__ __forceinline__ PldCarry pld_carry(const char* base, long long stride
   return c;
 }
 inline size_t pld_stream_lds_bytes(int S) {
-  return 4 * ((size_t)S * S + PO_TILE * (S | 1) + PLD_RING) + 2 * PO_TILE * S + PLD_RING * S;
+  return 4 * ((size_t)S * S + PC_TILE * (S | 1) + PLD_RING) + 2 * PC_TILE * S + PLD_RING * S;
 }
 
 template <bool SMALL, bool LIVE>
 __global__ __launch_bounds__(QT_WAVE) void pld_stream_kernel(PldArgs r) {
   extern __shared__ __attribute__((aligned(16))) int po_lds[];
-  const PoArgs& a = r.p;
+  const PcChain& a = r;
   const int lane = threadIdx.x, b = blockIdx.x, S = a.S, SP = S | 1, lag = r.lag;
   PoLds l;
   l.tk = po_lds;
-  l.dl = l.tk + S * S;                                   // [PO_TILE][S | 1]
-  int* filt_l = l.dl + PO_TILE * SP;                     // [PLD_RING]
+  l.dl = l.tk + S * S;                                   // [PC_TILE][S | 1]
+  int* filt_l = l.dl + PC_TILE * SP;                     // [PLD_RING]
   l.path = filt_l;
-  l.e = reinterpret_cast<short*>(filt_l + PLD_RING);     // [PO_TILE][S]
-  unsigned char* psi_l = reinterpret_cast<unsigned char*>(l.e + PO_TILE * S);   // [PLD_RING][S]
+  l.e = reinterpret_cast<short*>(filt_l + PLD_RING);     // [PC_TILE][S]
+  unsigned char* psi_l = reinterpret_cast<unsigned char*>(l.e + PC_TILE * S);   // [PLD_RING][S]
   l.psi = psi_l;
   po_stage_keys(a, l.tk);
   const long long seen = r.seen, end = seen + a.T, last = end - 1, count = r.g1 - r.g0;
   const PldCarry in = pld_carry(r.carry_in, r.carry_stride, b, S);
   const PldCarry out = pld_carry(r.carry_out, r.carry_stride, b, S);
   long long D = LLONG_MIN;
-  if (lane < S) D = seen > 0 ? (long long)in.delta[lane] : (a.init ? (long long)po_clamp_trans(a.init[lane]) : 0);
+  if (lane < S) D = seen > 0 ? (long long)in.delta[lane] : (a.init ? (long long)pc_clamp_trans(a.init[lane]) : 0);
   long long base;
   int d = po_normalise(D, base);
   long long offset = (seen > 0 ? *in.offset : 0) + base;
@@ -833,24 +743,20 @@ __global__ __launch_bounds__(QT_WAVE) void pld_stream_kernel(PldArgs r) {
   }
   long long lo = seen;
   do {
-    const long long nxt = (lo / PO_TILE + 1) * PO_TILE, hi = nxt < end ? nxt : end;
+    const long long nxt = (lo / PC_TILE + 1) * PC_TILE, hi = nxt < end ? nxt : end;
     const int m = (int)(hi - lo), f0 = (int)(lo - seen), r0 = (int)(lo & (PLD_RING - 1));
     __syncthreads();
     if (m > 0) {
       l.psi = psi_l + r0 * S;
-      po_stage_emissions(a, b, f0, m, l.e, false);
+      pc_stage_emissions(a, b, f0, m, l.e);
       __syncthreads();
       po_forward<SMALL>(l, m, S, lane, d);
       __syncthreads();
-      const int* __restrict__ row = l.dl + min(lane, m - 1) * SP;   // filtered, lane = frame
-      int bv = row[0], bj = 0;
-      for (int j = 1; j < S; ++j) {
-        const int v = row[j];
-        if (v > bv) bv = v, bj = j;
-      }
+      int bv, bj;
+      po_row_argmax(l, S, SP, m, lane, bv, bj);   // filtered, lane = frame
       if (lane < m) {
         filt_l[r0 + lane] = bj;
-        if (a.filtered) a.filtered[(long long)b * a.T + f0 + lane] = (long long)bj;
+        if (r.filtered) r.filtered[(long long)b * a.T + f0 + lane] = (long long)bj;
       }
       const int mx = __builtin_amdgcn_readlane(bv, m - 1);
       d -= mx;
@@ -882,7 +788,7 @@ __global__ __launch_bounds__(QT_WAVE) void pld_stream_kernel(PldArgs r) {
 
 // thread = (stream, emitted frame)
 __global__ __launch_bounds__(PLD_WALK_THREADS) void pld_walk_kernel(PldArgs r, int batch) {
-  const PoArgs& a = r.p;
+  const PcChain& a = r;
   const long long count = r.g1 - r.g0, idx = (long long)blockIdx.x * PLD_WALK_THREADS + threadIdx.x;
   if (idx >= count * batch) return;
   const int b = (int)(idx / count), S = a.S, lag = r.lag;
@@ -910,13 +816,13 @@ __global__ __launch_bounds__(PLD_WALK_THREADS) void pld_walk_kernel(PldArgs r, i
 }  // namespace
 
 extern "C" long long qt_pose_lag_decode_carry_bytes(const qt_pose_lag_desc* desc) {
-  if (qt_pose_lag_check_desc("qt_pose_lag_decode_carry_bytes", desc) != QT_OK) return 0;
+  if (pc_lag_check_desc("qt_pose_lag_decode_carry_bytes", desc) != QT_OK) return 0;
   return desc->batch * pld_carry_stride(desc->num_states, desc->lag);
 }
 
 extern "C" long long qt_pose_lag_decode_workspace_bytes(const qt_pose_lag_desc* desc) {
-  if (qt_pose_lag_check_desc("qt_pose_lag_decode_workspace_bytes", desc) != QT_OK) return 0;
-  if (qt_pose_lag_live(desc, PLD_LIVE_STEPS)) return 0;
+  if (pc_lag_check_desc("qt_pose_lag_decode_workspace_bytes", desc) != QT_OK) return 0;
+  if (pc_lag_live(desc, PLD_LIVE_STEPS)) return 0;
   const long long rows = (long long)desc->batch * desc->frames;
   return ((rows * desc->num_states + 7) / 8 * 8) + (rows * 4 + 7) / 8 * 8;
 }
@@ -925,10 +831,10 @@ extern "C" int qt_pose_lag_decode(const qt_pose_lag_desc* desc, const float* pro
                                   const int* trans, const int* init, const void* carry_in, void* carry_out, long long* lag_path,
                                   long long* filtered, void* workspace, long long workspace_bytes, void* stream) {
   const char* const who = "qt_pose_lag_decode";
-  if (const int rc = qt_pose_lag_check_desc(who, desc)) return rc;
+  if (const int rc = pc_lag_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states, lag = desc->lag;
-  const long long end = desc->seen + T, g0 = desc->seen > lag ? desc->seen - lag : 0;
-  const long long g1 = desc->flush ? end : (end > lag ? end - lag : 0), count = g1 - g0;
+  const PcSpan span = pc_lag_span(desc);
+  const long long count = span.count;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
   QT_CHECK_ARG((probs != nullptr || T == 0) && state_class != nullptr && trans != nullptr && carry_out != nullptr, "%s: null %s",
                who, !probs && T ? "probs" : !state_class ? "state_class" : !trans ? "trans" : "carry_out");
@@ -939,7 +845,7 @@ extern "C" int qt_pose_lag_decode(const qt_pose_lag_desc* desc, const float* pro
                    !misaligned(carry_out, 7) && !misaligned(workspace, 7),
                "%s: probs, state_class, trans and init must be 4-byte aligned, carry_in, carry_out, lag_path, filtered and the "
                "workspace 8-byte", who);
-  const bool live = qt_pose_lag_live(desc, PLD_LIVE_STEPS);
+  const bool live = pc_lag_live(desc, PLD_LIVE_STEPS);
   const long long rows = (long long)B * T, psi_bytes = (rows * S + 7) / 8 * 8;
   const long long ws_bytes = live ? 0 : psi_bytes + (rows * 4 + 7) / 8 * 8;
   QT_CHECK_ARG(ws_bytes == 0 || (workspace != nullptr && workspace_bytes >= ws_bytes),
@@ -949,45 +855,24 @@ extern "C" int qt_pose_lag_decode(const qt_pose_lag_desc* desc, const float* pro
   const size_t carry_bytes = (size_t)(B * stride);
   if (desc->seen == 0) carry_in = nullptr;   // not read
   QT_CHECK_ARG(!overlap(carry_in, carry_bytes, carry_out, carry_bytes), "%s: carry_in must not overlap carry_out", who);
-  const struct { const void* p; size_t bytes; const char* name; } in[] = {
-      {probs, rows ? (size_t)((rows - 1) * ld + C) * 4 : 0, "probs"}, {state_class, (size_t)S * 4, "state_class"},
-      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}, {carry_in, carry_bytes, "carry_in"}},
-    out[] = {{carry_out, carry_bytes, "carry_out"}, {lag_path, (size_t)(B * count) * 8, "lag_path"},
-             {filtered, (size_t)rows * 8, "filtered"}, {workspace, (size_t)ws_bytes, "workspace"}};
-  for (const auto& o : out) {
-    for (const auto& i : in)
-      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
-    for (const auto& o2 : out)
-      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
-  }
+  const PcBuf in[] = {{probs, rows ? (size_t)((rows - 1) * ld + C) * 4 : 0, "probs"},
+                      {state_class, (size_t)S * 4, "state_class"}, {trans, (size_t)S * S * 4, "trans"},
+                      {init, (size_t)S * 4, "init"}, {carry_in, carry_bytes, "carry_in"}};
+  const PcBuf out[] = {{carry_out, carry_bytes, "carry_out"}, {lag_path, (size_t)(B * count) * 8, "lag_path"},
+                       {filtered, (size_t)rows * 8, "filtered"}, {workspace, (size_t)ws_bytes, "workspace"}};
+  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
 
   PldArgs r;
-  PoArgs& a = r.p;
-  a.probs = probs;
-  a.state_class = state_class;
-  a.trans = trans;
-  a.init = init;
-  a.carry = nullptr;
-  a.path = nullptr;
-  a.filtered = filtered;
-  a.emissions = nullptr;
-  a.starts = a.gstarts = nullptr;
-  a.products = a.gproducts = a.ends = nullptr;
-  a.psi = a.back = nullptr;
-  a.ld = ld;
-  a.T = T;
-  a.tiles = a.groups = a.mode = 0;
-  a.C = C;
-  a.S = S;
-  a.div_s = make_fastdiv((unsigned)S);
+  pc_fill(r, probs, ld, state_class, trans, init, T, C, S);
+  r.filtered = filtered;
   r.carry_in = static_cast<const char*>(carry_in);
   r.carry_out = static_cast<char*>(carry_out);
   r.lag_path = lag_path;
   r.ws_psi = static_cast<unsigned char*>(workspace);
   r.ws_filt = reinterpret_cast<int*>(static_cast<char*>(workspace) + psi_bytes);
   r.seen = desc->seen;
-  r.g0 = g0;
-  r.g1 = g1;
+  r.g0 = span.g0;
+  r.g1 = span.g1;
   r.carry_stride = stride;
   r.lag = lag;
   hipStream_t s = static_cast<hipStream_t>(stream);

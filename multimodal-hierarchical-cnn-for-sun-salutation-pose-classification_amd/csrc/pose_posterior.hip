@@ -3,8 +3,10 @@
 // by tests/test_pose_posterior_gpu.py), scores are in units of 1/256 bit and exact in f32; every L x = log2 sum 2^x[i] is taken
 // with its maximum out and its sum in ascending order, so nothing is infinite for any table in range and every run gives the
 // same bits; whatever grows with the frame count is a double.  include/qtcnn.h states the rule in full.
+// The rule q, its table, the loop that stages a tile's emissions, the limits PC_*, the chain's inputs PcChain and the host's
+// shared checks are in pose_chain.h, once for the decoder and for this file: the posterior's bits rest on that q.
 //
-// Short route (frames <= PP_TILE): one launch, one wave per stream, lane = state, no workspace.  The table (row stride S | 1: a
+// Short route (frames <= PC_TILE): one launch, one wave per stream, lane = state, no workspace.  The table (row stride S | 1: a
 // column for the forward step and a row for the backward one are both free of bank conflicts), the tile's emissions and its a_f
 // rows are in LDS.  A forward step is the decoder's vector step with (L, +) for (max, +): S times { v_readlane of a_prev[i], add
 // the table entry }, a tree of maxima, the sum of v_exp_f32 in ascending i, v_log_f32; for S <= 16 the lane's column (and, for the
@@ -12,7 +14,7 @@
 // that the next frame starts from the a_f of the rule and a split into calls changes no bit.  The backward sweep walks the same
 // LDS rows, one frame per step, overwrites a_f with the posterior and stores it; class_posterior is summed from those rows at the
 // end (thread = (frame, class), ascending j).
-// Tiled route (frames > PP_TILE), three launches, M_f[i][j] = T[i][j] + E[f][j]:
+// Tiled route (frames > PC_TILE), three launches, M_f[i][j] = T[i][j] + E[f][j]:
 //   (a) pp_products: a workgroup of 256 per (stream, tile) forms P = M_a (x) ... (x) M_b in the (L, +) semiring in LDS, thread =
 //       (i, j), two buffers in turn, one barrier per frame.  Row i is a forward filter started at state i: every frame takes the
 //       row's maximum out (each thread finds it while it reads the row) and adds it to the row's offset, a double;
@@ -31,75 +33,35 @@
 // ONE wave per stream over all tiles, the a_f rows parked in the posterior output between the two sweeps.
 #include <stdint.h>
 
-#include "qt_common.h"
-#include "qt_internal.h"
+#include "pose_chain.h"
 
 namespace {
 
-constexpr int PP_TILE = 64;                      // frames per tile; frames <= PP_TILE take the short route
-constexpr int PP_MAX_S = 64;
-constexpr int PP_MAX_C = 64;
-constexpr long long PP_MAX_FRAMES = 1LL << 20;
-constexpr int PP_FLOOR = -8192;                  // q of NaN and of everything below 2^-32
-constexpr int PP_TRANS_FLOOR = -65536;
 constexpr float PP_PAD = -1e30f;                 // a candidate in a slot beyond S: never the maximum, and 2^(it - m) is 0
 constexpr int PP_SCAN_FLOATS = 4096;             // (b): floats of products per trip
 constexpr int PP_SCAN_MAX_TILES = 16;            // (b): products per trip at the most
 constexpr int PP_SCAN_PAD = PP_SCAN_MAX_TILES * 16;   // a trip's tiles * S <= 256 for every S: the rows' padding to S | 1, the offsets
 constexpr int PP_PROD_THREADS = 256;
 constexpr int PP_SCAN_THREADS = 256;
-static_assert(PP_TILE == QT_POSE_ORDER_TILE && PP_MAX_S == QT_POSE_ORDER_MAX_STATES && PP_MAX_C == QT_POSE_ORDER_MAX_CLASSES,
-              "the header states these");
-static_assert(PP_SCAN_FLOATS >= PP_MAX_S * PP_MAX_S && PP_SCAN_FLOATS % PP_SCAN_THREADS == 0, "a trip holds at least one product");
+static_assert(PP_SCAN_FLOATS >= PC_MAX_S * PC_MAX_S && PP_SCAN_FLOATS % PP_SCAN_THREADS == 0, "a trip holds at least one product");
 
-// rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the decoder's table (pose_order.hip, PO_LOG2)
-__device__ const unsigned short PP_LOG2[256] = {
-      1,   2,   4,   5,   6,   8,   9,  11,  12,  13,  15,  16,  18,  19,  20,  22,
-     23,  24,  26,  27,  28,  30,  31,  32,  34,  35,  36,  38,  39,  40,  42,  43,
-     44,  45,  47,  48,  49,  50,  52,  53,  54,  55,  57,  58,  59,  60,  62,  63,
-     64,  65,  66,  68,  69,  70,  71,  72,  74,  75,  76,  77,  78,  80,  81,  82,
-     83,  84,  85,  86,  88,  89,  90,  91,  92,  93,  94,  95,  97,  98,  99, 100,
-    101, 102, 103, 104, 105, 106, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117,
-    118, 119, 120, 121, 122, 123, 124, 125, 126, 127, 128, 129, 131, 132, 133, 134,
-    135, 136, 137, 138, 139, 140, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149,
-    150, 151, 152, 153, 154, 155, 156, 157, 158, 159, 160, 161, 162, 163, 163, 164,
-    165, 166, 167, 168, 169, 170, 171, 172, 173, 173, 174, 175, 176, 177, 178, 179,
-    180, 181, 182, 182, 183, 184, 185, 186, 187, 188, 189, 189, 190, 191, 192, 193,
-    194, 195, 195, 196, 197, 198, 199, 200, 200, 201, 202, 203, 204, 205, 205, 206,
-    207, 208, 209, 210, 210, 211, 212, 213, 214, 214, 215, 216, 217, 218, 218, 219,
-    220, 221, 222, 222, 223, 224, 225, 226, 226, 227, 228, 229, 229, 230, 231, 232,
-    233, 233, 234, 235, 236, 236, 237, 238, 239, 239, 240, 241, 242, 242, 243, 244,
-    245, 245, 246, 247, 248, 248, 249, 250, 251, 251, 252, 253, 253, 254, 255, 256
-};
-
-struct PpArgs {
-  const float* probs;
-  const int* state_class;
-  const int* trans;
-  const int* init;
-  double* carry;
-  float* posterior;
-  float* filtered;
-  float* class_posterior;
-  double* evidence;
+// what the tiled route's products and scan read and leave, and the learner's replay as well as the posterior's
+struct PpTiles : PcChain {
   double* offsets;           // workspace: double [batch][tiles][S], the products' row offsets
   double* before;            //            double [batch][tiles], the evidence before the tile
   float* products;           //            f32 [batch][tiles][S][S], row maximum 0
   float* starts;             //            f32 [batch][tiles][S], a in front of the tile's first frame
   float* ends;               //            f32 [batch][tiles][S], b at the tile's last frame
-  long long ld;
-  int T, tiles, C, S;
-  FastDiv div_s, div_c;
+};
+struct PpArgs : PpTiles {
+  double* carry;
+  float* posterior;
+  float* filtered;
+  float* class_posterior;
+  double* evidence;
 };
 
-__device__ __forceinline__ int pp_q(float p) {
-  if (!(p >= 0x1p-32f)) return PP_FLOOR;         // NaN, negatives, zeros, denormals
-  if (p >= 1.0f) return 0;
-  const unsigned b = __float_as_uint(p);
-  return 256 * ((int)(b >> 23) - 127) + (int)PP_LOG2[(b >> 15) & 255u];
-}
-__device__ __forceinline__ float pp_score(int v) { return (float)v * 0x1p-8f; }   // exact: |v| < 2^24
-__device__ __forceinline__ float pp_trans(int v) { return pp_score(min(max(v, PP_TRANS_FLOOR), 0)); }
+__device__ __forceinline__ float pp_trans(int v) { return pc_score(pc_clamp_trans(v)); }
 
 __device__ __forceinline__ float pp_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32; x <= 0 here
 __device__ __forceinline__ float pp_log2(float x) { return __builtin_amdgcn_logf(x); }    // v_log_f32; x in [1, S] here
@@ -202,40 +164,24 @@ __device__ __forceinline__ float pp_step(float bc, const float (&reg)[16], const
   return pp_m_plus_log2(m, s);
 }
 
-// the emissions of frames [f0, f0 + n) of stream b into e_l [n][S]: as scores, or (where LDS is short) as the integers q
-__device__ __forceinline__ void pp_put(float* e_l, int idx, int e) { e_l[idx] = pp_score(e); }
-__device__ __forceinline__ void pp_put(short* e_l, int idx, int e) { e_l[idx] = (short)e; }
-template <typename E>
-__device__ __forceinline__ void pp_stage_emissions(const PpArgs& a, int b, int f0, int n, E* e_l) {
-  const int S = a.S;
-  const float* __restrict__ p = a.probs + ((long long)b * a.T + f0) * a.ld;
-  for (int idx = threadIdx.x; idx < n * S; idx += blockDim.x) {
-    const int f = (int)fdiv((unsigned)idx, a.div_s), s = idx - f * S;
-    const int k = a.state_class[s];
-    int e = PP_FLOOR;
-    if ((unsigned)k < (unsigned)a.C) e = pp_q(p[(long long)f * a.ld + k]);
-    pp_put(e_l, idx, e);
-  }
-}
-
 // the LDS of the one-wave kernels
 struct PpLds {
   float* t;              // [S][S | 1]: the table
-  float* a;              // [PP_TILE][S]: a_f, then the posterior
-  float* e;              // [PP_TILE][S]
+  float* a;              // [PC_TILE][S]: a_f, then the posterior
+  float* e;              // [PC_TILE][S]
   int* sc;               // [S]
 };
 __device__ __forceinline__ PpLds pp_carve(float* lds, int S) {
   PpLds l;
   l.t = lds;
   l.a = l.t + S * (S | 1);
-  l.e = l.a + PP_TILE * S;
-  l.sc = reinterpret_cast<int*>(l.e + PP_TILE * S);
+  l.e = l.a + PC_TILE * S;
+  l.sc = reinterpret_cast<int*>(l.e + PC_TILE * S);
   return l;
 }
-inline size_t pp_wave_lds_bytes(int S) { return 4 * ((size_t)S * (S | 1) + 2 * PP_TILE * S + S); }
+inline size_t pp_wave_lds_bytes(int S) { return 4 * ((size_t)S * (S | 1) + 2 * PC_TILE * S + S); }
 
-__device__ __forceinline__ void pp_stage_table(const PpArgs& a, const PpLds& l) {
+__device__ __forceinline__ void pp_stage_table(const PcChain& a, const PpLds& l) {
   const int S = a.S, SP = S | 1;
   for (int idx = threadIdx.x; idx < S * S; idx += blockDim.x) {
     const int i = (int)fdiv((unsigned)idx, a.div_s);
@@ -245,13 +191,13 @@ __device__ __forceinline__ void pp_stage_table(const PpArgs& a, const PpLds& l) 
 }
 
 // Forward over the n staged frames, lane = state (one wave; lanes >= S compute on state S - 1 and store nothing).  av: the
-// lane's a in front of the first frame on entry, a of the last frame on exit.  Leaves the a_f rows in LDS, writes filtered when
-// asked, adds every c_f to both sums.
+// lane's a in front of the first frame on entry, a of the last frame on exit.  Leaves the a_f rows in LDS, writes `filtered`
+// ([batch][T][S]) when there is one, adds every c_f to both sums.
 template <bool SMALL>
-__device__ __forceinline__ void pp_forward(const PpArgs& a, const PpLds& l, const float (&col)[16], int b, int f0, int n, int lane,
-                                           float& av, double& total, double& call) {
+__device__ __forceinline__ void pp_forward(const PcChain& a, float* filtered, const PpLds& l, const float (&col)[16], int b,
+                                           int f0, int n, int lane, float& av, double& total, double& call) {
   const int S = a.S, jj = min(lane, S - 1);
-  float* __restrict__ filt = a.filtered ? a.filtered + ((long long)b * a.T + f0) * S : nullptr;
+  float* __restrict__ filt = filtered ? filtered + ((long long)b * a.T + f0) * S : nullptr;
   float e = l.e[jj];
   for (int f = 0; f < n; ++f) {
     const float e_next = f + 1 < n ? l.e[(f + 1) * S + jj] : 0.0f;
@@ -322,13 +268,13 @@ __device__ __forceinline__ void pp_classes(const PpArgs& a, const PpLds& l, int 
 }
 
 // a stream's start vector for lane jj: init before its first frame, the carry after it
-__device__ __forceinline__ float pp_stream_start(const PpArgs& a, int b, int jj) {
-  const double* __restrict__ c = a.carry + (long long)b * (a.S + 2);
+__device__ __forceinline__ float pp_stream_start(const PcChain& a, const double* carry, int b, int jj) {
+  const double* __restrict__ c = carry + (long long)b * (a.S + 2);
   if (c[0] == 0.0) return a.init ? pp_trans(a.init[jj]) : 0.0f;
   return (float)c[2 + jj];
 }
 // the same of a whole video (qt_pose_prior_expect: no carry)
-__device__ __forceinline__ float pp_video_start(const PpArgs& a, int jj) { return a.init ? pp_trans(a.init[jj]) : 0.0f; }
+__device__ __forceinline__ float pp_video_start(const PcChain& a, int jj) { return a.init ? pp_trans(a.init[jj]) : 0.0f; }
 // after a stream's last frame: av = a_last; sum = the c_f of this call
 __device__ __forceinline__ void pp_write_carry(const PpArgs& a, int b, int lane, float av, double seen, double total, double call) {
   double* __restrict__ c = a.carry + (long long)b * (a.S + 2);
@@ -349,7 +295,7 @@ __global__ __launch_bounds__(QT_WAVE) void pp_stream_kernel(PpArgs a) {
   pp_stage_table(a, l);
   const double seen = a.carry[(long long)b * (S + 2)];
   double total = a.carry[(long long)b * (S + 2) + 1], call = 0.0;
-  float av = pp_stream_start(a, b, jj);
+  float av = pp_stream_start(a, a.carry, b, jj);
   __syncthreads();
   float col[16], row[16];
   if (SMALL) {
@@ -357,11 +303,11 @@ __global__ __launch_bounds__(QT_WAVE) void pp_stream_kernel(PpArgs a) {
     pp_load16(row, l.t + jj * SP, 1, S);
   }
   for (int tile = 0; tile < a.tiles; ++tile) {
-    const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+    const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
     __syncthreads();
-    pp_stage_emissions(a, b, f0, n, l.e);
+    pc_stage_emissions(a, b, f0, n, l.e);
     __syncthreads();
-    pp_forward<SMALL>(a, l, col, b, f0, n, lane, av, total, call);
+    pp_forward<SMALL>(a, a.filtered, l, col, b, f0, n, lane, av, total, call);
     if (a.tiles > 1) {   // the a_f rows wait in the posterior output for the backward sweep
       __syncthreads();
       float* __restrict__ out = a.posterior + ((long long)b * a.T + f0) * S;
@@ -371,11 +317,11 @@ __global__ __launch_bounds__(QT_WAVE) void pp_stream_kernel(PpArgs a) {
   pp_write_carry(a, b, lane, av, seen, total, call);
   float g = 0.0f;
   for (int tile = a.tiles - 1; tile >= 0; --tile) {
-    const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+    const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
     const bool last = tile == a.tiles - 1;
     if (a.tiles > 1) {
       __syncthreads();
-      pp_stage_emissions(a, b, f0, n, l.e);
+      pc_stage_emissions(a, b, f0, n, l.e);
       const float* in = a.posterior + ((long long)b * a.T + f0) * S;
       for (int idx = lane; idx < n * S; idx += QT_WAVE) l.a[idx] = in[idx];
     }
@@ -418,23 +364,23 @@ __device__ __forceinline__ float pp_product_entry(const float* __restrict__ pr, 
 }
 
 template <bool SMALL>
-__global__ __launch_bounds__(PP_PROD_THREADS) void pp_products_kernel(PpArgs a) {
+__global__ __launch_bounds__(PP_PROD_THREADS) void pp_products_kernel(PpTiles a) {
   extern __shared__ __attribute__((aligned(16))) float pp_lds[];
   const int S = a.S, SS = S * S, tid = threadIdx.x;
   double* off = reinterpret_cast<double*>(pp_lds);   // [S] (64 doubles reserved)
-  float* tr = pp_lds + 2 * PP_MAX_S;
+  float* tr = pp_lds + 2 * PC_MAX_S;
   float* cur = tr + SS;
   float* nxt = cur + SS;
   short* e_l = reinterpret_cast<short*>(nxt + SS);   // q: three products of 64 x 64 leave no room for 16 KB of scores
   const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-  const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+  const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
   for (int idx = tid; idx < SS; idx += PP_PROD_THREADS) tr[idx] = pp_trans(a.trans[idx]);
   for (int idx = tid; idx < S; idx += PP_PROD_THREADS) off[idx] = 0.0;
-  pp_stage_emissions(a, b, f0, n, e_l);
+  pc_stage_emissions(a, b, f0, n, e_l);
   __syncthreads();
   for (int idx = tid; idx < SS; idx += PP_PROD_THREADS) {
     const int i = (int)fdiv((unsigned)idx, a.div_s);
-    cur[idx] = tr[idx] + pp_score(e_l[idx - i * S]);
+    cur[idx] = tr[idx] + pc_score(e_l[idx - i * S]);
   }
   __syncthreads();
   for (int f = 1; f < n; ++f) {
@@ -442,7 +388,7 @@ __global__ __launch_bounds__(PP_PROD_THREADS) void pp_products_kernel(PpArgs a) 
       const int i = (int)fdiv((unsigned)idx, a.div_s), j = idx - i * S;
       float r;
       const float v = pp_product_entry<SMALL>(cur + i * S, tr + j, S, r);
-      nxt[idx] = pp_score(e_l[f * S + j]) + v;
+      nxt[idx] = pc_score(e_l[f * S + j]) + v;
       if (j == 0) off[i] += (double)r;   // (row i's own thread: nobody else touches off[i])
     }
     __syncthreads();
@@ -470,7 +416,7 @@ __host__ __device__ inline int pp_scan_trip_tiles(int S) {
 
 // CARRY: the stream's start is pp_stream_start's; without it (the learner, every call a whole video) init / 256 or 0
 template <bool SMALL, bool CARRY = true>
-__global__ __launch_bounds__(PP_SCAN_THREADS) void pp_scan_kernel(PpArgs a) {
+__global__ __launch_bounds__(PP_SCAN_THREADS) void pp_scan_kernel(const double* carry, PpTiles a) {
   __shared__ __attribute__((aligned(16))) double offs[2][PP_SCAN_PAD];
   __shared__ __attribute__((aligned(16))) float buf[2][PP_SCAN_FLOATS + PP_SCAN_PAD];
   constexpr int PER = PP_SCAN_FLOATS / PP_SCAN_THREADS, PER_OFF = PP_SCAN_PAD / PP_SCAN_THREADS;
@@ -518,7 +464,7 @@ __global__ __launch_bounds__(PP_SCAN_THREADS) void pp_scan_kernel(PpArgs a) {
   float v = 0.0f;
   double ev = 0.0;
   if (chain) {
-    v = CARRY ? pp_stream_start(a, b, jj) : pp_video_start(a, jj);
+    v = CARRY ? pp_stream_start(a, carry, b, jj) : pp_video_start(a, jj);
     if (lane < S) starts[lane] = v;
     if (lane == 0) before[0] = 0.0;
   }
@@ -586,10 +532,10 @@ __global__ __launch_bounds__(QT_WAVE) void pp_replay_kernel(PpArgs a) {
   const PpLds l = pp_carve(pp_lds, a.S);
   const int lane = threadIdx.x, S = a.S, SP = S | 1, jj = min(lane, S - 1);
   const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-  const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+  const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
   const bool last = tile == a.tiles - 1;
   pp_stage_table(a, l);
-  pp_stage_emissions(a, b, f0, n, l.e);
+  pc_stage_emissions(a, b, f0, n, l.e);
   float av = a.starts[((long long)b * a.tiles + tile) * S + jj];
   const float bv = a.ends[((long long)b * a.tiles + tile) * S + jj];
   __syncthreads();
@@ -599,7 +545,7 @@ __global__ __launch_bounds__(QT_WAVE) void pp_replay_kernel(PpArgs a) {
     pp_load16(row, l.t + jj * SP, 1, S);
   }
   double call = a.before[(long long)b * a.tiles + tile], unused = 0.0;
-  pp_forward<SMALL>(a, l, col, b, f0, n, lane, av, unused, call);
+  pp_forward<SMALL>(a, a.filtered, l, col, b, f0, n, lane, av, unused, call);
   if (last) {
     const double seen = a.carry[(long long)b * (S + 2)], total = a.carry[(long long)b * (S + 2) + 1];
     pp_write_carry(a, b, lane, av, seen, total + call, call);
@@ -618,29 +564,29 @@ __global__ __launch_bounds__(QT_WAVE) void pp_replay_kernel(PpArgs a) {
 // (8 KB at S = 64), so the partial fits beside the table and the a_f rows: 57,856 bytes at S = 64.  A video's frame 0 goes into
 // the start partial (the sum over j in ascending j), every other frame into the partial; the tile's `starts` vector is the
 // a_(f0 - 1) of its first frame.  pr_reduce then adds tiles and streams in ascending order, in double, one thread per entry.
-struct PrArgs {
-  PpArgs p;                  // posterior, filtered, class_posterior, carry: unused; evidence: workspace, double [batch]
-  float* partial;            // workspace: f32 [batch][tiles][S][S]
+struct PrArgs : PpTiles {
+  double* evidence;          // workspace: double [batch]
+  float* partial;            //            f32 [batch][tiles][S][S]
   float* start_partial;      //            f32 [batch][S]
   double* counts;
   double* start_counts;
   double* totals;
 };
 inline size_t pr_wave_lds_bytes(int S) {
-  return 4 * ((size_t)S * (S | 1) * (S <= 16 ? 1 : 2) + PP_TILE * S) + 2 * PP_TILE * S;
+  return 4 * ((size_t)S * (S | 1) * (S <= 16 ? 1 : 2) + PC_TILE * S) + 2 * PC_TILE * S;
 }
 
 template <bool SMALL>
 __global__ __launch_bounds__(QT_WAVE) void pr_expect_kernel(PrArgs r) {
   extern __shared__ __attribute__((aligned(16))) float pp_lds[];
-  const PpArgs& a = r.p;
+  const PrArgs& a = r;
   const int lane = threadIdx.x, S = a.S, SP = S | 1, jj = min(lane, S - 1);
   float* t_l = pp_lds;                                  // [S][S | 1]
-  float* a_l = t_l + S * SP;                            // [PP_TILE][S]
-  float* acc_l = a_l + PP_TILE * S;                     // [S][S | 1], S > 16 only
-  short* e_l = reinterpret_cast<short*>(acc_l + (SMALL ? 0 : S * SP));   // [PP_TILE][S]
+  float* a_l = t_l + S * SP;                            // [PC_TILE][S]
+  float* acc_l = a_l + PC_TILE * S;                     // [S][S | 1], S > 16 only
+  short* e_l = reinterpret_cast<short*>(acc_l + (SMALL ? 0 : S * SP));   // [PC_TILE][S]
   const int b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
-  const int f0 = tile * PP_TILE, n = min(PP_TILE, a.T - f0);
+  const int f0 = tile * PC_TILE, n = min(PC_TILE, a.T - f0);
   const bool last = tile == a.tiles - 1;
   const long long slot = (long long)b * a.tiles + tile;
   for (int idx = lane; idx < S * S; idx += QT_WAVE) {
@@ -648,7 +594,7 @@ __global__ __launch_bounds__(QT_WAVE) void pr_expect_kernel(PrArgs r) {
     t_l[i * SP + (idx - i * S)] = pp_trans(a.trans[idx]);
     if (!SMALL) acc_l[i * SP + (idx - i * S)] = 0.0f;
   }
-  pp_stage_emissions(a, b, f0, n, e_l);
+  pc_stage_emissions(a, b, f0, n, e_l);
   const float a0 = tile == 0 ? pp_video_start(a, jj) : a.starts[slot * S + jj];   // (the short route runs no scan)
   float bv = last ? 0.0f : a.ends[slot * S + jj];
   double call = tile == 0 ? 0.0 : a.before[slot];
@@ -660,7 +606,7 @@ __global__ __launch_bounds__(QT_WAVE) void pr_expect_kernel(PrArgs r) {
   }
   float av = a0;
   for (int f = 0; f < n; ++f) {   // pp_forward's frames, the emissions from their integers
-    const float A = pp_score(e_l[f * S + jj]) + pp_step<SMALL>(av, col, t_l + jj, SP, S);
+    const float A = pc_score(e_l[f * S + jj]) + pp_step<SMALL>(av, col, t_l + jj, SP, S);
     float m, lg;
     double c;
     pp_L_states<SMALL>(A, S, lane < S, m, lg, c);
@@ -674,7 +620,7 @@ __global__ __launch_bounds__(QT_WAVE) void pr_expect_kernel(PrArgs r) {
 #pragma unroll
   for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
   for (int f = n - 1; f >= 0; --f) {
-    const float g = pp_score(e_l[f * S + jj]) + bv;
+    const float g = pc_score(e_l[f * S + jj]) + bv;
     const float B = pp_step<SMALL>(g, row, t_l + jj * SP, 1, S);
     const float ap = f > 0 ? a_l[(f - 1) * S + jj] : a0;
     float m, lg;
@@ -719,7 +665,7 @@ __global__ __launch_bounds__(QT_WAVE) void pr_expect_kernel(PrArgs r) {
 constexpr int PR_REDUCE_THREADS = 256;
 constexpr int PR_REDUCE_AHEAD = 16;
 __global__ __launch_bounds__(PR_REDUCE_THREADS) void pr_reduce_kernel(PrArgs r, int batch) {
-  const PpArgs& a = r.p;
+  const PrArgs& a = r;
   const int S = a.S, SS = S * S, idx = blockIdx.x * PR_REDUCE_THREADS + threadIdx.x;
   if (idx < SS) {
     // the (stream, tile) slots are one run in memory: PR_REDUCE_AHEAD loads in flight, then their additions in the fixed order
@@ -758,37 +704,14 @@ __global__ __launch_bounds__(PR_REDUCE_THREADS) void pr_reduce_kernel(PrArgs r, 
   }
 }
 
-inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-inline bool overlap(const void* p, size_t pbytes, const void* q, size_t qbytes) {
-  if (!p || !q || !pbytes || !qbytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + qbytes && b < a + pbytes;
-}
-
-int check_desc(const char* who, const qt_pose_order_desc* d) {
-  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  QT_CHECK_ARG(d->batch >= 1, "%s: batch must be positive (got %d)", who, d->batch);
-  QT_CHECK_ARG(d->frames >= 1, "%s: frames must be positive (got %d)", who, d->frames);
-  QT_CHECK_ARG(d->num_classes >= 1 && d->num_classes <= PP_MAX_C, "%s: num_classes = %d; 1 .. %d are handled", who,
-               d->num_classes, PP_MAX_C);
-  QT_CHECK_ARG(d->num_states >= 1 && d->num_states <= PP_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who, d->num_states,
-               PP_MAX_S);
-  const long long frames = (long long)d->batch * d->frames;
-  if (frames > PP_MAX_FRAMES) {
-    qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, frames, PP_MAX_FRAMES);
-    return QT_ERR_UNSUPPORTED;
-  }
-  return QT_OK;
-}
-
 // the workspace of the tiled route, the doubles first
 struct PpLayout {
   long long offsets, before, products, starts, ends, total;
 };
 PpLayout pp_layout(const qt_pose_order_desc* d) {
   PpLayout w = {0, 0, 0, 0, 0, 0};
-  if (d->frames <= PP_TILE) return w;
-  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PP_TILE);
+  if (d->frames <= PC_TILE) return w;
+  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PC_TILE);
   w.offsets = 0;
   w.before = w.offsets + B * tiles * S * 8;
   w.products = w.before + B * tiles * 8;
@@ -797,8 +720,17 @@ PpLayout pp_layout(const qt_pose_order_desc* d) {
   w.total = w.ends + B * tiles * S * 4;
   return w;
 }
+void pp_fill_tiles(PpTiles& a, void* workspace, const PpLayout& w) {
+  char* ws = static_cast<char*>(workspace);
+  a.offsets = reinterpret_cast<double*>(ws + w.offsets);
+  a.before = reinterpret_cast<double*>(ws + w.before);
+  a.products = reinterpret_cast<float*>(ws + w.products);
+  a.starts = reinterpret_cast<float*>(ws + w.starts);
+  a.ends = reinterpret_cast<float*>(ws + w.ends);
+}
+inline size_t pp_prod_lds_bytes(int S) { return 4 * (2 * PC_MAX_S + 3 * (size_t)S * S) + 2 * PC_TILE * S; }
 
-// the learner's workspace: the tiled route's (none up to PP_TILE frames), then the evidence, the partials, the start partials
+// the learner's workspace: the tiled route's (none up to PC_TILE frames), then the evidence, the partials, the start partials
 struct PrLayout {
   PpLayout pp;
   long long evidence, partial, start_partial, total;
@@ -806,7 +738,7 @@ struct PrLayout {
 PrLayout pr_layout(const qt_pose_order_desc* d) {
   PrLayout w;
   w.pp = pp_layout(d);
-  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PP_TILE);
+  const long long B = d->batch, S = d->num_states, tiles = qt_cdiv(d->frames, PC_TILE);
   w.evidence = (w.pp.total + 7) / 8 * 8;
   w.partial = w.evidence + B * 8;
   w.start_partial = w.partial + B * tiles * S * S * 4;
@@ -817,7 +749,7 @@ PrLayout pr_layout(const qt_pose_order_desc* d) {
 }  // namespace
 
 extern "C" long long qt_pose_prior_workspace_bytes(const qt_pose_order_desc* desc) {
-  if (check_desc("qt_pose_prior_workspace_bytes", desc) != QT_OK) return 0;
+  if (pc_check_desc("qt_pose_prior_workspace_bytes", desc) != QT_OK) return 0;
   return pr_layout(desc).total;
 }
 
@@ -825,7 +757,7 @@ extern "C" int qt_pose_prior_expect(const qt_pose_order_desc* desc, const float*
                                     const int* trans, const int* init, double* counts, double* start_counts, double* totals,
                                     void* workspace, long long workspace_bytes, void* stream) {
   const char* const who = "qt_pose_prior_expect";
-  if (const int rc = check_desc(who, desc)) return rc;
+  if (const int rc = pc_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
   QT_CHECK_ARG(probs != nullptr && state_class != nullptr && trans != nullptr && counts != nullptr && start_counts != nullptr &&
@@ -842,59 +774,36 @@ extern "C" int qt_pose_prior_expect(const qt_pose_order_desc* desc, const float*
                "%s: workspace of %lld bytes; qt_pose_prior_workspace_bytes asks for %lld", who, workspace ? workspace_bytes : 0LL,
                w.total);
   const long long rows = (long long)B * T;
-  const struct { const void* p; size_t bytes; const char* name; } in[] = {
-      {probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
-      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}},
-    out[] = {{counts, (size_t)S * S * 8, "counts"}, {start_counts, (size_t)S * 8, "start_counts"}, {totals, 16, "totals"},
-             {workspace, (size_t)w.total, "workspace"}};
-  for (const auto& o : out) {
-    for (const auto& i : in)
-      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
-    for (const auto& o2 : out)
-      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
-  }
+  const PcBuf in[] = {{probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
+                      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}};
+  const PcBuf out[] = {{counts, (size_t)S * S * 8, "counts"}, {start_counts, (size_t)S * 8, "start_counts"},
+                       {totals, 16, "totals"}, {workspace, (size_t)w.total, "workspace"}};
+  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
 
   PrArgs r;
-  PpArgs& a = r.p;
-  a.probs = probs;
-  a.state_class = state_class;
-  a.trans = trans;
-  a.init = init;
-  a.carry = nullptr;
-  a.posterior = a.filtered = a.class_posterior = nullptr;
+  pc_fill(r, probs, ld, state_class, trans, init, T, C, S);
+  pp_fill_tiles(r, workspace, w.pp);
   char* ws = static_cast<char*>(workspace);
-  a.evidence = reinterpret_cast<double*>(ws + w.evidence);
-  a.offsets = reinterpret_cast<double*>(ws + w.pp.offsets);
-  a.before = reinterpret_cast<double*>(ws + w.pp.before);
-  a.products = reinterpret_cast<float*>(ws + w.pp.products);
-  a.starts = reinterpret_cast<float*>(ws + w.pp.starts);
-  a.ends = reinterpret_cast<float*>(ws + w.pp.ends);
-  a.ld = ld;
-  a.T = T;
-  a.tiles = qt_cdiv(T, PP_TILE);
-  a.C = C;
-  a.S = S;
-  a.div_s = make_fastdiv((unsigned)S);
-  a.div_c = make_fastdiv((unsigned)C);
+  r.evidence = reinterpret_cast<double*>(ws + w.evidence);
   r.partial = reinterpret_cast<float*>(ws + w.partial);
   r.start_partial = reinterpret_cast<float*>(ws + w.start_partial);
   r.counts = counts;
   r.start_counts = start_counts;
   r.totals = totals;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = S <= 16;
-  const unsigned all = (unsigned)((long long)B * a.tiles);
-  if (a.tiles > 1) {
-    const size_t prod_lds = 4 * (2 * PP_MAX_S + 3 * (size_t)S * S) + 2 * PP_TILE * S;
-    if (small) hipLaunchKernelGGL(pp_products_kernel<true>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
-    else hipLaunchKernelGGL(pp_products_kernel<false>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
+  const dim3 all((unsigned)((long long)B * r.tiles)), streams((unsigned)B);
+  const dim3 wave(QT_WAVE), prod(PP_PROD_THREADS), scan(PP_SCAN_THREADS);
+  const PpTiles& tiles = r;
+  if (r.tiles > 1) {
+    const size_t prod_lds = pp_prod_lds_bytes(S);
+    pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(pp_products_kernel<PC_SMALL(sm)>, all, prod, prod_lds, s, tiles); });
     QT_CHECK_LAUNCH();
-    if (small) hipLaunchKernelGGL((pp_scan_kernel<true, false>), dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((pp_scan_kernel<false, false>), dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
+    pc_by_small(S, [&](auto sm) {
+      hipLaunchKernelGGL((pp_scan_kernel<PC_SMALL(sm), false>), streams, scan, 0, s, (const double*)nullptr, tiles);
+    });
     QT_CHECK_LAUNCH();
   }
-  if (small) hipLaunchKernelGGL(pr_expect_kernel<true>, dim3(all), dim3(QT_WAVE), pr_wave_lds_bytes(S), s, r);
-  else hipLaunchKernelGGL(pr_expect_kernel<false>, dim3(all), dim3(QT_WAVE), pr_wave_lds_bytes(S), s, r);
+  pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(pr_expect_kernel<PC_SMALL(sm)>, all, wave, pr_wave_lds_bytes(S), s, r); });
   QT_CHECK_LAUNCH();
   hipLaunchKernelGGL(pr_reduce_kernel, dim3((unsigned)qt_cdiv(S * S + S + 2, PR_REDUCE_THREADS)), dim3(PR_REDUCE_THREADS), 0, s, r,
                      B);
@@ -903,7 +812,7 @@ extern "C" int qt_pose_prior_expect(const qt_pose_order_desc* desc, const float*
 }
 
 extern "C" long long qt_pose_posterior_workspace_bytes(const qt_pose_order_desc* desc) {
-  if (check_desc("qt_pose_posterior_workspace_bytes", desc) != QT_OK) return 0;
+  if (pc_check_desc("qt_pose_posterior_workspace_bytes", desc) != QT_OK) return 0;
   return pp_layout(desc).total;
 }
 
@@ -912,7 +821,7 @@ extern "C" int qt_pose_posterior(const qt_pose_order_desc* desc, const float* pr
                                  float* class_posterior, double* log2_evidence, void* workspace, long long workspace_bytes,
                                  void* stream) {
   const char* const who = "qt_pose_posterior";
-  if (const int rc = check_desc(who, desc)) return rc;
+  if (const int rc = pc_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
   QT_CHECK_ARG(probs != nullptr && state_class != nullptr && trans != nullptr && carry != nullptr && posterior != nullptr,
@@ -928,62 +837,40 @@ extern "C" int qt_pose_posterior(const qt_pose_order_desc* desc, const float* pr
                "%s: workspace of %lld bytes; qt_pose_posterior_workspace_bytes asks for %lld", who,
                workspace ? workspace_bytes : 0LL, w.total);
   const long long rows = (long long)B * T;
-  const struct { const void* p; size_t bytes; const char* name; } in[] = {
-      {probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
-      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}},
-    out[] = {{carry, (size_t)B * (S + 2) * 8, "carry"}, {posterior, (size_t)rows * S * 4, "posterior"},
-             {filtered, (size_t)rows * S * 4, "filtered"}, {class_posterior, (size_t)rows * C * 4, "class_posterior"},
-             {log2_evidence, (size_t)B * 8, "log2_evidence"}, {workspace, (size_t)w.total, "workspace"}};
-  for (const auto& o : out) {
-    for (const auto& i : in)
-      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
-    for (const auto& o2 : out)
-      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
-  }
+  const PcBuf in[] = {{probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
+                      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}};
+  const PcBuf out[] = {{carry, (size_t)B * (S + 2) * 8, "carry"}, {posterior, (size_t)rows * S * 4, "posterior"},
+                       {filtered, (size_t)rows * S * 4, "filtered"}, {class_posterior, (size_t)rows * C * 4, "class_posterior"},
+                       {log2_evidence, (size_t)B * 8, "log2_evidence"}, {workspace, (size_t)w.total, "workspace"}};
+  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
 
   PpArgs a;
-  a.probs = probs;
-  a.state_class = state_class;
-  a.trans = trans;
-  a.init = init;
+  pc_fill(a, probs, ld, state_class, trans, init, T, C, S);
+  pp_fill_tiles(a, workspace, w);
   a.carry = carry;
   a.posterior = posterior;
   a.filtered = filtered;
   a.class_posterior = class_posterior;
   a.evidence = log2_evidence;
-  char* ws = static_cast<char*>(workspace);
-  a.offsets = reinterpret_cast<double*>(ws + w.offsets);
-  a.before = reinterpret_cast<double*>(ws + w.before);
-  a.products = reinterpret_cast<float*>(ws + w.products);
-  a.starts = reinterpret_cast<float*>(ws + w.starts);
-  a.ends = reinterpret_cast<float*>(ws + w.ends);
-  a.ld = ld;
-  a.T = T;
-  a.tiles = qt_cdiv(T, PP_TILE);
-  a.C = C;
-  a.S = S;
-  a.div_s = make_fastdiv((unsigned)S);
-  a.div_c = make_fastdiv((unsigned)C);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = S <= 16;
   const size_t wave_lds = pp_wave_lds_bytes(S);
+  const dim3 all((unsigned)((long long)B * a.tiles)), streams((unsigned)B);
+  const dim3 wave(QT_WAVE), prod(PP_PROD_THREADS), scan(PP_SCAN_THREADS);
   const bool one_wave = a.tiles > 1 && qt_env_int("QTCNN_POSE_POSTERIOR", 0) == 1;   // per call: see the head of the file
   if (a.tiles == 1 || one_wave) {
-    if (small) hipLaunchKernelGGL(pp_stream_kernel<true>, dim3((unsigned)B), dim3(QT_WAVE), wave_lds, s, a);
-    else hipLaunchKernelGGL(pp_stream_kernel<false>, dim3((unsigned)B), dim3(QT_WAVE), wave_lds, s, a);
+    pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(pp_stream_kernel<PC_SMALL(sm)>, streams, wave, wave_lds, s, a); });
     QT_CHECK_LAUNCH();
     return QT_OK;
   }
-  const unsigned all = (unsigned)((long long)B * a.tiles);
-  const size_t prod_lds = 4 * (2 * PP_MAX_S + 3 * (size_t)S * S) + 2 * PP_TILE * S;
-  if (small) hipLaunchKernelGGL(pp_products_kernel<true>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
-  else hipLaunchKernelGGL(pp_products_kernel<false>, dim3(all), dim3(PP_PROD_THREADS), prod_lds, s, a);
+  const PpTiles& tiles = a;
+  const size_t prod_lds = pp_prod_lds_bytes(S);
+  pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(pp_products_kernel<PC_SMALL(sm)>, all, prod, prod_lds, s, tiles); });
   QT_CHECK_LAUNCH();
-  if (small) hipLaunchKernelGGL(pp_scan_kernel<true>, dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
-  else hipLaunchKernelGGL(pp_scan_kernel<false>, dim3((unsigned)B), dim3(PP_SCAN_THREADS), 0, s, a);
+  pc_by_small(S, [&](auto sm) {
+    hipLaunchKernelGGL((pp_scan_kernel<PC_SMALL(sm), true>), streams, scan, 0, s, (const double*)a.carry, tiles);
+  });
   QT_CHECK_LAUNCH();
-  if (small) hipLaunchKernelGGL(pp_replay_kernel<true>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
-  else hipLaunchKernelGGL(pp_replay_kernel<false>, dim3(all), dim3(QT_WAVE), wave_lds, s, a);
+  pc_by_small(S, [&](auto sm) { hipLaunchKernelGGL(pp_replay_kernel<PC_SMALL(sm)>, all, wave, wave_lds, s, a); });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -992,8 +879,8 @@ extern "C" int qt_pose_posterior(const qt_pose_order_desc* desc, const float* pr
 // lagged[g] is the posterior of frame g given the frames up to w = min(g + lag, the call's last frame): the forward pass is the
 // frame-by-frame rule above (pp_forward as it is), and every emitted frame sweeps backward over its own window of at most lag
 // steps with pp_backward's arithmetic (pp_b_from_g, pp_L_states), so a window's bits depend neither on the call boundaries nor on
-// the route.  Frames carry global indices; the LDS rings hold frame g in row g & 127 (lag + PP_TILE <= 127 rows are alive at a
-// time), and the forward pass goes in chunks that end on multiples of PP_TILE so that a chunk's rows are one run.
+// the route.  Frames carry global indices; the LDS rings hold frame g in row g & 127 (lag + PC_TILE <= 127 rows are alive at a
+// time), and the forward pass goes in chunks that end on multiples of PC_TILE so that a chunk's rows are one run.
 // Live route: pl_stream_kernel<LIVE>, one launch, one wave per stream: table, history (from carry_in) and new emissions in LDS,
 // forward over a chunk, then that chunk's windows one after another, then carry_out.  4 (S (S | 1) + 256 S + S) bytes of LDS:
 // 82,432 at S = 64, 26,208 at S = 12.
@@ -1008,16 +895,16 @@ extern "C" int qt_pose_posterior(const qt_pose_order_desc* desc, const float* pr
 namespace {
 
 constexpr int PL_RING = 128;
-constexpr int PL_LAG_MAX = 63;
 constexpr int PL_GROUP = 16;
 constexpr int PL_WIN_THREADS = 256;
-constexpr int PL_WIN_ROWS = PL_GROUP + PL_LAG_MAX + 1;   // emission rows of a group: frames gs + 1 .. gs + PL_GROUP - 1 + lag
+constexpr int PL_WIN_ROWS = PL_GROUP + PC_LAG_MAX + 1;   // emission rows of a group: frames gs + 1 .. gs + PL_GROUP - 1 + lag
 constexpr long long PL_LIVE_STEPS = 16;
-static_assert(PL_LAG_MAX == QT_POSE_LAG_MAX && PL_LAG_MAX + 1 <= PP_TILE, "a window fits the short route");
-static_assert(PL_LAG_MAX + PP_TILE < PL_RING && PL_WIN_ROWS <= PL_RING && (PL_RING & (PL_RING - 1)) == 0, "the ring holds a chunk and its windows");
+static_assert(PC_LAG_MAX + 1 <= PC_TILE, "a window fits the short route");
+static_assert(PC_LAG_MAX + PC_TILE < PL_RING && PL_WIN_ROWS <= PL_RING && (PL_RING & (PL_RING - 1)) == 0, "the ring holds a chunk and its windows");
 
-struct PlArgs {
-  PpArgs p;                  // probs, state_class, trans, init, filtered, evidence, ld, T (= n), C, S, div_s, div_c; the rest unused
+struct PlArgs : PcChain {    // T: the new frames of the call (tiles: not read)
+  float* filtered;
+  double* evidence;
   const char* carry_in;
   char* carry_out;
   float* lagged;
@@ -1053,7 +940,7 @@ __device__ __forceinline__ short pl_q(float score) { return (short)(int)(score *
 template <bool SMALL>
 __device__ __forceinline__ void pl_window(const PlArgs& r, const PpLds& l, const float (&row)[16], const float* __restrict__ a_row,
                                           const float* __restrict__ e_l, long long ebase, long long g, long long w, int b, int lane) {
-  const int S = r.p.S, C = r.p.C, jj = min(lane, S - 1);
+  const int S = r.S, C = r.C, jj = min(lane, S - 1);
   float bv = 0.0f;
   for (long long f = w - 1; f >= g; --f) {
     const float gv = e_l[(int)((f + 1 - ebase) & (PL_RING - 1)) * S + jj] + bv;
@@ -1084,7 +971,7 @@ __device__ __forceinline__ void pl_window(const PlArgs& r, const PpLds& l, const
 template <bool SMALL, bool LIVE>
 __global__ __launch_bounds__(QT_WAVE) void pl_stream_kernel(PlArgs r) {
   extern __shared__ __attribute__((aligned(16))) float pp_lds[];
-  const PpArgs& a = r.p;
+  const PcChain& a = r;
   const int lane = threadIdx.x, b = blockIdx.x, S = a.S, SP = S | 1, jj = min(lane, S - 1), lag = r.lag;
   float* a_l = pp_lds + S * SP;                         // [PL_RING][S]
   float* e_l = a_l + PL_RING * S;                       // [PL_RING][S]
@@ -1103,7 +990,7 @@ __global__ __launch_bounds__(QT_WAVE) void pl_stream_kernel(PlArgs r) {
     const long long k = g - (seen - lag);
     if (lane < S) {
       a_l[(int)(g & (PL_RING - 1)) * S + lane] = in.a[k * S + lane];
-      e_l[(int)(g & (PL_RING - 1)) * S + lane] = pp_score(in.e[k * S + lane]);
+      e_l[(int)(g & (PL_RING - 1)) * S + lane] = pc_score(in.e[k * S + lane]);
     }
   }
   __syncthreads();
@@ -1114,14 +1001,14 @@ __global__ __launch_bounds__(QT_WAVE) void pl_stream_kernel(PlArgs r) {
   }
   long long lo = seen;
   do {
-    const long long nxt = (lo / PP_TILE + 1) * PP_TILE, hi = nxt < end ? nxt : end;
+    const long long nxt = (lo / PC_TILE + 1) * PC_TILE, hi = nxt < end ? nxt : end;
     const int m = (int)(hi - lo), f0 = (int)(lo - seen), r0 = (int)(lo & (PL_RING - 1)) * S;
     if (m > 0) {
       l.a = a_l + r0;
       l.e = e_l + r0;
-      pp_stage_emissions(a, b, f0, m, l.e);
+      pc_stage_emissions(a, b, f0, m, l.e);
       __syncthreads();
-      pp_forward<SMALL>(a, l, col, b, f0, m, lane, av, total, call);
+      pp_forward<SMALL>(a, r.filtered, l, col, b, f0, m, lane, av, total, call);
       __syncthreads();
     }
     if (LIVE) {
@@ -1143,7 +1030,7 @@ __global__ __launch_bounds__(QT_WAVE) void pl_stream_kernel(PlArgs r) {
   if (lane < S) out.a_last[lane] = av;
   if (lane == 0) {
     *out.ev = total;
-    if (a.evidence) a.evidence[b] = call;
+    if (r.evidence) r.evidence[b] = call;
   }
   for (int k = 0; k < lag; ++k) {   // frames end - lag .. end - 1: all in the rings; zeros in front of the stream's start
     const long long g = end - lag + k;
@@ -1157,7 +1044,7 @@ __global__ __launch_bounds__(QT_WAVE) void pl_stream_kernel(PlArgs r) {
 template <bool SMALL>
 __global__ __launch_bounds__(PL_WIN_THREADS) void pl_window_kernel(PlArgs r) {
   extern __shared__ __attribute__((aligned(16))) float pp_lds[];
-  const PpArgs& a = r.p;
+  const PcChain& a = r;
   const int tid = threadIdx.x, lane = tid & (QT_WAVE - 1), wave = tid / QT_WAVE, S = a.S, SP = S | 1, jj = min(lane, S - 1);
   const int lag = r.lag;
   PpLds l;
@@ -1180,7 +1067,7 @@ __global__ __launch_bounds__(PL_WIN_THREADS) void pl_window_kernel(PlArgs r) {
     const int fr = (int)fdiv((unsigned)idx, a.div_s) + 1, s = idx - (fr - 1) * S;
     const long long f = gs + fr;
     const short q = f >= seen ? r.ws_e[((long long)b * a.T + (f - seen)) * S + s] : in.e[(f - (seen - lag)) * S + s];
-    l.e[fr * S + s] = pp_score(q);
+    l.e[fr * S + s] = pc_score(q);
   }
   __syncthreads();
   float row[16];
@@ -1194,56 +1081,16 @@ __global__ __launch_bounds__(PL_WIN_THREADS) void pl_window_kernel(PlArgs r) {
 inline size_t pl_stream_lds_bytes(int S) { return 4 * ((size_t)S * (S | 1) + 2 * PL_RING * S + S); }
 inline size_t pl_window_lds_bytes(int S) { return 4 * ((size_t)S * (S | 1) + (PL_GROUP + PL_WIN_ROWS) * S + S); }
 
-// the frames a call emits
-struct PlSpan {
-  long long g0, g1;
-};
-inline PlSpan pl_span(const qt_pose_lag_desc* d) {
-  const long long end = d->seen + d->frames;
-  PlSpan s;
-  s.g0 = d->seen > d->lag ? d->seen - d->lag : 0;
-  s.g1 = d->flush ? end : (end > d->lag ? end - d->lag : 0);
-  return s;
-}
-
 }  // namespace
 
-// (pose_order.hip uses them too)
-int qt_pose_lag_check_desc(const char* who, const qt_pose_lag_desc* d) {
-  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  QT_CHECK_ARG(d->batch >= 1, "%s: batch must be positive (got %d)", who, d->batch);
-  QT_CHECK_ARG(d->frames >= 0, "%s: frames must not be negative (got %d)", who, d->frames);
-  QT_CHECK_ARG(d->frames >= 1 || d->flush, "%s: frames == 0 is a flush only (flush is 0)", who);
-  QT_CHECK_ARG(d->num_classes >= 1 && d->num_classes <= PP_MAX_C, "%s: num_classes = %d; 1 .. %d are handled", who,
-               d->num_classes, PP_MAX_C);
-  QT_CHECK_ARG(d->num_states >= 1 && d->num_states <= PP_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who, d->num_states,
-               PP_MAX_S);
-  QT_CHECK_ARG(d->lag >= 0 && d->lag <= PL_LAG_MAX, "%s: lag = %d; 0 .. %d are handled", who, d->lag, PL_LAG_MAX);
-  QT_CHECK_ARG(d->seen >= 0, "%s: seen must not be negative (got %lld)", who, d->seen);
-  const long long frames = (long long)d->batch * d->frames;
-  if (frames > PP_MAX_FRAMES) {
-    qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, frames, PP_MAX_FRAMES);
-    return QT_ERR_UNSUPPORTED;
-  }
-  return QT_OK;
-}
-// true: the live route.  QTCNN_POSE_LAG = 1 / 2 forces the live / the batch route (per call); otherwise one new frame, or n
-// frames (a flush alone: its pending frames) with n (lag + 1) <= live_steps
-bool qt_pose_lag_live(const qt_pose_lag_desc* d, long long live_steps) {
-  const int mode = qt_env_int("QTCNN_POSE_LAG", 0);
-  if (mode == 1 || mode == 2) return mode == 1;
-  const long long n = d->frames ? d->frames : d->lag;
-  return d->frames == 1 || n * (d->lag + 1) <= live_steps;
-}
-
 extern "C" long long qt_pose_lag_smooth_carry_bytes(const qt_pose_lag_desc* desc) {
-  if (qt_pose_lag_check_desc("qt_pose_lag_smooth_carry_bytes", desc) != QT_OK) return 0;
+  if (pc_lag_check_desc("qt_pose_lag_smooth_carry_bytes", desc) != QT_OK) return 0;
   return desc->batch * pl_carry_stride(desc->num_states, desc->lag);
 }
 
 extern "C" long long qt_pose_lag_smooth_workspace_bytes(const qt_pose_lag_desc* desc) {
-  if (qt_pose_lag_check_desc("qt_pose_lag_smooth_workspace_bytes", desc) != QT_OK) return 0;
-  if (qt_pose_lag_live(desc, PL_LIVE_STEPS)) return 0;
+  if (pc_lag_check_desc("qt_pose_lag_smooth_workspace_bytes", desc) != QT_OK) return 0;
+  if (pc_lag_live(desc, PL_LIVE_STEPS)) return 0;
   return ((long long)desc->batch * desc->frames * desc->num_states * 6 + 7) / 8 * 8;
 }
 
@@ -1252,10 +1099,10 @@ extern "C" int qt_pose_lag_smooth(const qt_pose_lag_desc* desc, const float* pro
                                   float* lagged_class, float* filtered, double* log2_evidence, void* workspace,
                                   long long workspace_bytes, void* stream) {
   const char* const who = "qt_pose_lag_smooth";
-  if (const int rc = qt_pose_lag_check_desc(who, desc)) return rc;
+  if (const int rc = pc_lag_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states, lag = desc->lag;
-  const PlSpan span = pl_span(desc);
-  const long long count = span.g1 - span.g0;
+  const PcSpan span = pc_lag_span(desc);
+  const long long count = span.count;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
   QT_CHECK_ARG((probs != nullptr || T == 0) && state_class != nullptr && trans != nullptr && carry_out != nullptr, "%s: null %s",
                who, !probs && T ? "probs" : !state_class ? "state_class" : !trans ? "trans" : "carry_out");
@@ -1267,7 +1114,7 @@ extern "C" int qt_pose_lag_smooth(const qt_pose_lag_desc* desc, const float* pro
                    !misaligned(workspace, 7),
                "%s: probs, state_class, trans, init, lagged, lagged_class and filtered must be 4-byte aligned, carry_in, "
                "carry_out, log2_evidence and the workspace 8-byte", who);
-  const bool live = qt_pose_lag_live(desc, PL_LIVE_STEPS);
+  const bool live = pc_lag_live(desc, PL_LIVE_STEPS);
   const long long ws_bytes = live ? 0 : ((long long)B * T * S * 6 + 7) / 8 * 8;
   QT_CHECK_ARG(ws_bytes == 0 || (workspace != nullptr && workspace_bytes >= ws_bytes),
                "%s: workspace of %lld bytes; qt_pose_lag_smooth_workspace_bytes asks for %lld", who,
@@ -1276,38 +1123,19 @@ extern "C" int qt_pose_lag_smooth(const qt_pose_lag_desc* desc, const float* pro
   const size_t carry_bytes = (size_t)(B * stride);
   if (desc->seen == 0) carry_in = nullptr;   // not read
   QT_CHECK_ARG(!overlap(carry_in, carry_bytes, carry_out, carry_bytes), "%s: carry_in must not overlap carry_out", who);
-  const struct { const void* p; size_t bytes; const char* name; } in[] = {
-      {probs, rows ? (size_t)((rows - 1) * ld + C) * 4 : 0, "probs"}, {state_class, (size_t)S * 4, "state_class"},
-      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}, {carry_in, carry_bytes, "carry_in"}},
-    out[] = {{carry_out, carry_bytes, "carry_out"}, {lagged, (size_t)(B * count * S) * 4, "lagged"},
-             {lagged_class, (size_t)(B * count * C) * 4, "lagged_class"}, {filtered, (size_t)rows * S * 4, "filtered"},
-             {log2_evidence, (size_t)B * 8, "log2_evidence"}, {workspace, (size_t)ws_bytes, "workspace"}};
-  for (const auto& o : out) {
-    for (const auto& i : in)
-      QT_CHECK_ARG(!overlap(o.p, o.bytes, i.p, i.bytes), "%s: %s must not overlap %s", who, o.name, i.name);
-    for (const auto& o2 : out)
-      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
-  }
+  const PcBuf in[] = {{probs, rows ? (size_t)((rows - 1) * ld + C) * 4 : 0, "probs"},
+                      {state_class, (size_t)S * 4, "state_class"}, {trans, (size_t)S * S * 4, "trans"},
+                      {init, (size_t)S * 4, "init"}, {carry_in, carry_bytes, "carry_in"}};
+  const PcBuf out[] = {{carry_out, carry_bytes, "carry_out"}, {lagged, (size_t)(B * count * S) * 4, "lagged"},
+                       {lagged_class, (size_t)(B * count * C) * 4, "lagged_class"},
+                       {filtered, (size_t)rows * S * 4, "filtered"}, {log2_evidence, (size_t)B * 8, "log2_evidence"},
+                       {workspace, (size_t)ws_bytes, "workspace"}};
+  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
 
   PlArgs r;
-  PpArgs& a = r.p;
-  a.probs = probs;
-  a.state_class = state_class;
-  a.trans = trans;
-  a.init = init;
-  a.carry = nullptr;
-  a.posterior = a.class_posterior = nullptr;
-  a.filtered = filtered;
-  a.evidence = log2_evidence;
-  a.offsets = a.before = nullptr;
-  a.products = a.starts = a.ends = nullptr;
-  a.ld = ld;
-  a.T = T;
-  a.tiles = 0;
-  a.C = C;
-  a.S = S;
-  a.div_s = make_fastdiv((unsigned)S);
-  a.div_c = make_fastdiv((unsigned)C);
+  pc_fill(r, probs, ld, state_class, trans, init, T, C, S);
+  r.filtered = filtered;
+  r.evidence = log2_evidence;
   r.carry_in = static_cast<const char*>(carry_in);
   r.carry_out = static_cast<char*>(carry_out);
   r.lagged = lagged;
@@ -1326,15 +1154,16 @@ extern "C" int qt_pose_lag_smooth(const qt_pose_lag_desc* desc, const float* pro
   auto stream_kernel = small ? (live ? pl_stream_kernel<true, true> : pl_stream_kernel<true, false>)
                              : (live ? pl_stream_kernel<false, true> : pl_stream_kernel<false, false>);
   if (lds > 64 * 1024)
-    if (int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(stream_kernel), (int)pl_stream_lds_bytes(PP_MAX_S),
+    if (int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(stream_kernel), (int)pl_stream_lds_bytes(PC_MAX_S),
                                     raised[(small ? 2 : 0) + (live ? 1 : 0)]))
       return rc;
   hipLaunchKernelGGL(stream_kernel, dim3((unsigned)B), dim3(QT_WAVE), lds, s, r);
   QT_CHECK_LAUNCH();
   if (!live && count > 0) {
     const unsigned grid = (unsigned)(B * ((count + PL_GROUP - 1) / PL_GROUP));
-    if (small) hipLaunchKernelGGL(pl_window_kernel<true>, dim3(grid), dim3(PL_WIN_THREADS), pl_window_lds_bytes(S), s, r);
-    else hipLaunchKernelGGL(pl_window_kernel<false>, dim3(grid), dim3(PL_WIN_THREADS), pl_window_lds_bytes(S), s, r);
+    pc_by_small(S, [&](auto sm) {
+      hipLaunchKernelGGL(pl_window_kernel<PC_SMALL(sm)>, dim3(grid), dim3(PL_WIN_THREADS), pl_window_lds_bytes(S), s, r);
+    });
     QT_CHECK_LAUNCH();
   }
   return QT_OK;

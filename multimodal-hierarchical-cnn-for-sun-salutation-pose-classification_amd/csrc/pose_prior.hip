@@ -1,6 +1,7 @@
 // Learning the pose-order prior on the device, the parts that are not forward-backward: the hard counts of state paths
 // (qt_pose_prior_count_paths) and the M-step (qt_pose_prior_update).  The E-step, qt_pose_prior_expect, extends the posterior's
-// kernels and lives beside them in pose_posterior.hip; include/qtcnn.h states the rule in full.
+// kernels and lives beside them in pose_posterior.hip; include/qtcnn.h states the rule in full.  The limits and the floor of a
+// transition score (PC_MAX_S, PC_MAX_FRAMES, PC_TRANS_FLOOR) and the overlap check are pose_chain.h's.
 // count_paths, two launches: (a) a workgroup of 256 per (stream, chunk of PR_CHUNK frames) counts its transitions
 // path[f - 1] -> path[f] into an int histogram [S][S] in LDS (integer atomics on LDS: the result does not depend on their
 // order) and writes it to the workspace; (b) one thread per entry adds the chunks of every stream in int64 and adds the sum, an
@@ -10,19 +11,16 @@
 // the new init.
 #include <stdint.h>
 
-#include "qt_common.h"
+#include "pose_chain.h"
 
 namespace {
 
 constexpr int PR_CHUNK = 1024;                   // frames per workgroup of (a); a histogram entry stays below 2^10
 constexpr int PR_THREADS = 256;
-constexpr int PR_MAX_S = QT_POSE_ORDER_MAX_STATES;
-constexpr long long PR_MAX_FRAMES = 1LL << 20;
-constexpr int PR_TRANS_FLOOR = -65536;
 
 __global__ __launch_bounds__(PR_THREADS) void pr_count_kernel(const long long* __restrict__ path, int* __restrict__ partial, int T,
                                                               int chunks, int S) {
-  __shared__ int hist[PR_MAX_S * PR_MAX_S];
+  __shared__ int hist[PC_MAX_S * PC_MAX_S];
   const int SS = S * S, tid = threadIdx.x;
   const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
   const int f0 = chunk * PR_CHUNK, f1 = min(f0 + PR_CHUNK, T);
@@ -67,8 +65,8 @@ __device__ void pr_row(const double* __restrict__ src, const int* __restrict__ a
     const double rj = (!allowed || allowed[j]) ? src[j] + pseudo : 0.0;
     int v;
     if (R > 0.0) {
-      v = PR_TRANS_FLOOR;
-      if (rj > 0.0) v = (int)fmin(fmax(rint(256.0 * log2(rj / R)), (double)PR_TRANS_FLOOR), 0.0);
+      v = PC_TRANS_FLOOR;
+      if (rj > 0.0) v = (int)fmin(fmax(rint(256.0 * log2(rj / R)), (double)PC_TRANS_FLOOR), 0.0);
     } else {
       v = old ? old[j] : 0;
     }
@@ -76,20 +74,13 @@ __device__ void pr_row(const double* __restrict__ src, const int* __restrict__ a
   }
 }
 
-__global__ __launch_bounds__(2 * PR_MAX_S) void pr_update_kernel(const double* __restrict__ counts,
+__global__ __launch_bounds__(2 * PC_MAX_S) void pr_update_kernel(const double* __restrict__ counts,
                                                                  const double* __restrict__ start_counts,
                                                                  const int* __restrict__ allowed, double pseudo, const int* trans_in,
                                                                  const int* init_in, int* trans_out, int* init_out, int S) {
   const int i = threadIdx.x;   // (a row is read and written by its own thread alone: trans_out may be trans_in)
   if (i < S) pr_row(counts + i * S, allowed + i * S, pseudo, trans_in + i * S, trans_out + i * S, S);
   else if (i == S && init_out) pr_row(start_counts, nullptr, pseudo, init_in, init_out, S);
-}
-
-inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-inline bool overlap(const void* p, size_t pbytes, const void* q, size_t qbytes) {
-  if (!p || !q || !pbytes || !qbytes) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + qbytes && b < a + pbytes;
 }
 
 }  // namespace
@@ -101,11 +92,11 @@ extern "C" int qt_pose_prior_count_paths(const qt_pose_order_desc* desc, const l
   QT_CHECK_ARG(desc != nullptr, "%s: null descriptor", who);
   QT_CHECK_ARG(desc->batch >= 1, "%s: batch must be positive (got %d)", who, desc->batch);
   QT_CHECK_ARG(desc->frames >= 1, "%s: frames must be positive (got %d)", who, desc->frames);
-  QT_CHECK_ARG(desc->num_states >= 1 && desc->num_states <= PR_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who,
-               desc->num_states, PR_MAX_S);
+  QT_CHECK_ARG(desc->num_states >= 1 && desc->num_states <= PC_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who,
+               desc->num_states, PC_MAX_S);
   const long long rows = (long long)desc->batch * desc->frames;
-  if (rows > PR_MAX_FRAMES) {
-    qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, rows, PR_MAX_FRAMES);
+  if (rows > PC_MAX_FRAMES) {
+    qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, rows, PC_MAX_FRAMES);
     return QT_ERR_UNSUPPORTED;
   }
   const int B = desc->batch, T = desc->frames, S = desc->num_states, chunks = qt_cdiv(T, PR_CHUNK);
@@ -121,14 +112,10 @@ extern "C" int qt_pose_prior_count_paths(const qt_pose_order_desc* desc, const l
   QT_CHECK_ARG(workspace != nullptr && workspace_bytes >= need,
                "%s: workspace of %lld bytes; qt_pose_prior_workspace_bytes asks for %lld", who, workspace ? workspace_bytes : 0LL,
                need);
-  const struct { const void* p; size_t bytes; const char* name; } out[] = {
-      {counts, (size_t)S * S * 8, "counts"}, {start_counts, (size_t)S * 8, "start_counts"}, {totals, 16, "totals"},
-      {workspace, (size_t)need, "workspace"}};
-  for (const auto& o : out) {
-    QT_CHECK_ARG(!overlap(o.p, o.bytes, path, (size_t)rows * 8), "%s: %s must not overlap path", who, o.name);
-    for (const auto& o2 : out)
-      QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
-  }
+  const PcBuf in[] = {{path, (size_t)rows * 8, "path"}};
+  const PcBuf out[] = {{counts, (size_t)S * S * 8, "counts"}, {start_counts, (size_t)S * 8, "start_counts"},
+                       {totals, 16, "totals"}, {workspace, (size_t)need, "workspace"}};
+  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int* partial = static_cast<int*>(workspace);
   hipLaunchKernelGGL(pr_count_kernel, dim3((unsigned)(B * chunks)), dim3(PR_THREADS), 0, s, path, partial, T, chunks, S);
@@ -144,7 +131,7 @@ extern "C" int qt_pose_prior_update(int num_states, const double* counts, const 
                                     void* stream) {
   const char* const who = "qt_pose_prior_update";
   const int S = num_states;
-  QT_CHECK_ARG(S >= 1 && S <= PR_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who, S, PR_MAX_S);
+  QT_CHECK_ARG(S >= 1 && S <= PC_MAX_S, "%s: num_states = %d; 1 .. %d are handled", who, S, PC_MAX_S);
   QT_CHECK_ARG(pseudo_count >= 0.0 && pseudo_count <= 1.7976931348623157e308,
                "%s: pseudo_count must be a finite number that is not negative (got %g)", who, pseudo_count);
   QT_CHECK_ARG(counts != nullptr && allowed != nullptr && trans_in != nullptr && trans_out != nullptr, "%s: null %s", who,
@@ -154,7 +141,7 @@ extern "C" int qt_pose_prior_update(int num_states, const double* counts, const 
                    !misaligned(init_in, 3) && !misaligned(trans_out, 3) && !misaligned(init_out, 3),
                "%s: counts and start_counts must be 8-byte aligned, allowed, trans_in, init_in, trans_out and init_out 4-byte", who);
   const size_t tb = (size_t)S * S * 4, ib = (size_t)S * 4;
-  const struct { const void* p; size_t bytes; const char* name; } in[] = {
+  const PcBuf in[] = {
       {counts, 2 * tb, "counts"}, {start_counts, 2 * ib, "start_counts"}, {allowed, tb, "allowed"},
       {trans_in, tb, "trans_in"}, {init_in, ib, "init_in"}},
     out[] = {{trans_out, tb, "trans_out"}, {init_out, ib, "init_out"}};
@@ -166,7 +153,7 @@ extern "C" int qt_pose_prior_update(int num_states, const double* counts, const 
                    "%s: %s must not overlap %s (trans_out may be trans_in itself, init_out init_in itself)", who, o.name, i.name);
     }
   QT_CHECK_ARG(!overlap(trans_out, tb, init_out, ib), "%s: trans_out must not overlap init_out", who);
-  hipLaunchKernelGGL(pr_update_kernel, dim3(1), dim3(2 * PR_MAX_S), 0, static_cast<hipStream_t>(stream), counts, start_counts,
+  hipLaunchKernelGGL(pr_update_kernel, dim3(1), dim3(2 * PC_MAX_S), 0, static_cast<hipStream_t>(stream), counts, start_counts,
                      allowed, pseudo_count, trans_in, init_in, trans_out, init_out, S);
   QT_CHECK_LAUNCH();
   return QT_OK;

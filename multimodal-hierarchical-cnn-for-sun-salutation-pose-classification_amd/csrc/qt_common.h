@@ -272,6 +272,15 @@ static inline int qt_raise_lds_limit(const void* kern, int lds_bytes, std::atomi
   return QT_OK;
 }
 
+// argument checks of the entry points: p (may be null) is not a multiple of mask + 1; two byte ranges share a byte (a null
+// pointer or an empty range overlaps nothing)
+static inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+static inline bool overlap(const void* p, size_t pbytes, const void* q, size_t qbytes) {
+  if (!p || !q || !pbytes || !qbytes) return false;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + qbytes && b < a + pbytes;
+}
+
 static inline int qt_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 // workgroups of `block` threads for `total` items, at least 1 and at most `cap`.  The cap is spelled out at every call: the
 // grid-stride reductions sum in an order that follows their grid size, so a call's cap is part of its result.

@@ -37,8 +37,3 @@ bool qt_wgrad_s2_eligible(const qt_conv_desc* d);
 size_t qt_wgrad_s2_workspace_bytes(const qt_conv_desc* d);
 int qt_wgrad_s2_launch(const qt_conv_desc* d, const void* dy, const void* x, float* grad_oihw, void* workspace,
                        size_t workspace_bytes, void* stream, void* sum_stream);
-
-// pose_posterior.hip: the descriptor checks and the route (true: live) that qt_pose_lag_smooth and qt_pose_lag_decode
-// (pose_order.hip) share
-int qt_pose_lag_check_desc(const char* who, const qt_pose_lag_desc* d);
-bool qt_pose_lag_live(const qt_pose_lag_desc* d, long long live_steps);

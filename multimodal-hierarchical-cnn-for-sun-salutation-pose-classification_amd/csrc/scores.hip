@@ -439,7 +439,6 @@ __global__ __launch_bounds__(64) void scores_average_kernel(int C, int M, double
   scal[10] = na;
 }
 
-inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 inline bool sizes_ok(int C, int bits, int M) {
   return C >= 1 && C <= SC_MAX_C && bits >= SC_MIN_BITS && bits <= SC_MAX_BITS && M >= 1 && M <= SC_MAX_M;
 }

@@ -338,7 +338,6 @@ bool overlap(const void* p, long long p_bytes, const void* q, long long q_bytes)
   const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
   return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
 }
-bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
 // descriptor checks shared by the size query and the call; leaves the error text
 int plan_desc_status(const qt_seq_windows_desc* desc, const char* who) {
@@ -374,9 +373,9 @@ extern "C" int qt_seq_windows_plan(const qt_seq_windows_desc* desc, const long l
   QT_CHECK_ARG(labels != nullptr && clip_offsets != nullptr && starts != nullptr && window_labels != nullptr &&
                    count != nullptr && workspace != nullptr,
                "%s: null labels, clip_offsets, starts, window_labels, count or workspace", who);
-  QT_CHECK_ARG(!misaligned(labels, 8) && !misaligned(window_labels, 8),
+  QT_CHECK_ARG(!misaligned(labels, 7) && !misaligned(window_labels, 7),
                "%s: labels and window_labels must be 8-byte aligned", who);
-  QT_CHECK_ARG(!misaligned(clip_offsets, 4) && !misaligned(starts, 4) && !misaligned(count, 4) && !misaligned(workspace, 4),
+  QT_CHECK_ARG(!misaligned(clip_offsets, 3) && !misaligned(starts, 3) && !misaligned(count, 3) && !misaligned(workspace, 3),
                "%s: clip_offsets, starts, count and workspace must be 4-byte aligned", who);
   const int spans = qt_cdiv(desc->frames, SW_SPAN);
   QT_CHECK_ARG(workspace_bytes >= sizeof(int) * (size_t)spans, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
@@ -418,7 +417,7 @@ extern "C" int qt_seq_gather_rows(const qt_seq_gather_desc* desc, const void* sr
     return QT_ERR_UNSUPPORTED;
   }
   QT_CHECK_ARG(src != nullptr && starts != nullptr && dst != nullptr, "%s: null source, starts or destination", who);
-  QT_CHECK_ARG(!misaligned(starts, 4), "%s: starts must be 4-byte aligned", who);
+  QT_CHECK_ARG(!misaligned(starts, 3), "%s: starts must be 4-byte aligned", who);
   RowsArgs a;
   a.run_bytes = desc->seq_len * desc->row_bytes;
   QT_CHECK_ARG(!overlap(src, desc->src_rows * desc->row_bytes, dst, desc->windows * a.run_bytes),
@@ -461,8 +460,8 @@ extern "C" int qt_seq_gather_features(const qt_seq_features_desc* desc, const fl
     return QT_ERR_UNSUPPORTED;
   }
   QT_CHECK_ARG(raw != nullptr && starts != nullptr && out != nullptr, "%s: null rows, starts or output", who);
-  QT_CHECK_ARG(!misaligned(raw, 4) && !misaligned(starts, 4) && !misaligned(out, 4) && !misaligned(means, 4) &&
-                   !misaligned(stds, 4) && !misaligned(window_labels, 8),
+  QT_CHECK_ARG(!misaligned(raw, 3) && !misaligned(starts, 3) && !misaligned(out, 3) && !misaligned(means, 3) &&
+                   !misaligned(stds, 3) && !misaligned(window_labels, 7),
                "%s: rows, starts, output, means and stds must be 4-byte aligned, window_labels 8-byte aligned", who);
   const bool by_class = desc->mode == QT_POSE_CLASS_MEAN || desc->mode == QT_POSE_STANDARDIZE;
   if (by_class) {

@@ -342,12 +342,6 @@ __global__ __launch_bounds__(TL_TRIP) void timeline_decode_kernel(DecodeArgs a) 
   }
 }
 
-inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-inline bool overlap(const void* p, size_t pbytes, const void* q, size_t qbytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + qbytes && b < a + pbytes;
-}
-
 // what both entry points ask of batch, frames and num_classes
 int check_shape(const char* who, const qt_timeline_desc* d, bool zero_frames_ok) {
   QT_CHECK_ARG(d->batch >= 1, "%s: batch must be positive (got %d)", who, d->batch);

@@ -83,7 +83,7 @@ MAX_FRAMES = 1 << 20
 LAG_MAX = 63                # QT_POSE_LAG_MAX
 SCORE_FLOOR = -8192         # q of NaN and of everything below 2^-32
 TRANS_FLOOR = -65536
-# rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the table of csrc/pose_order.hip
+# rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the table of csrc/pose_chain.h
 LOG2_TABLE = (
       1,   2,   4,   5,   6,   8,   9,  11,  12,  13,  15,  16,  18,  19,  20,  22,
      23,  24,  26,  27,  28,  30,  31,  32,  34,  35,  36,  38,  39,  40,  42,  43,
@@ -206,28 +206,109 @@ def cyclic_prior(step_classes, stay, advance, skip=None, other=TRANS_FLOOR, wrap
     return np.array(classes, np.int32), trans
 
 
-class PoseOrderDecoder:
+class _PoseTables:
+    """what every owner of the chain's tables shares: the checked tables in device memory (state_class, trans, init or None),
+    a workspace that grows on demand, and the checks of a `probs` argument"""
+    _empty_with_flush = False                    # the fixed-lag pair: a push may bring no frames
+
+    def __init__(self, state_class, trans, device, streams=1, init=None, class_names=None, **own):
+        who = type(self).__name__
+        sc, tr, init, self.class_names = _check_tables(who, state_class, trans, init, streams, class_names)
+        self.num_states, self.streams = int(sc.shape[0]), streams
+        init = self._check_own(who, init, **own)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise QtError(f"{who} lives on an AMD GPU (device must be cuda:N); no CPU fallback")
+        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
+        self.trans = torch.from_numpy(np.ascontiguousarray(tr, np.int32)).to(device)
+        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
+        self.device = self.trans.device
+        self._workspace = None
+
+    def _check_own(self, who, init):
+        """a subclass's own constructor arguments (`own`), checked before anything goes to the device; returns init (numpy or
+        None)"""
+        return init
+
+    def _room(self, query, desc):
+        """(pointer, bytes) of a workspace of at least what `query` asks for `desc`; (None, 0) where it asks for none"""
+        need = int(query(ctypes.byref(desc)))
+        if need and (self._workspace is None or self._workspace.numel() < need):
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return (_lib.ptr(self._workspace), self._workspace.numel()) if need else (None, 0)
+
+    def _check_probs(self, what, probs, allow_empty=False):
+        """probs f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device -> (probs as
+        [streams, frames, C] with rows the kernels can walk, flat, frames, C)"""
+        _check_probs_tensor(what, probs, self.device)
+        B = self.streams
+        flat = probs.dim() == 2
+        if flat and B == 1:
+            probs = probs.unsqueeze(0)
+        if probs.dim() != 3 or probs.shape[0] != B or not 1 <= probs.shape[2] <= MAX_CLASSES or \
+                (probs.shape[1] < 1 and not allow_empty):
+            want = f"C <= {MAX_CLASSES} and frames >= 1, or 0 with flush" if self._empty_with_flush else \
+                f"frames >= 1 and C <= {MAX_CLASSES}"
+            raise QtError(f"{what}: probs must be [{B}, frames, C]{' or [frames, C]' if B == 1 else ''} with {want} "
+                          f"(got {list(probs.shape)})")
+        return (_check_probs_rows(what, probs), flat) + tuple(probs.shape[1:])
+
+
+class _PoseStreams(_PoseTables):
+    """the owners of streams (each has a `reset`): they take a learner's tables"""
+
+    def load_tables(self, trans, init=None):
+        """a learner's tables (int32 tensors on this device) copied into this object's own, device to device and without a host
+        sync; every stream starts anew.  init None: no init from here on.  (Values are clamped by the kernels as they are read:
+        checking them here would need a host sync.)"""
+        who, S = f"{type(self).__name__}.load_tables", self.num_states
+        for name, t, shape in (("trans", trans, (S, S)), ("init", init, (S,))):
+            if t is None and name == "init":
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32 or tuple(t.shape) != shape:
+                raise QtError(f"{who}: {name} must be an int32 tensor {list(shape)} on {self.device}")
+        self.trans.copy_(trans)
+        if init is None:
+            self.init = None
+        elif self.init is None:
+            self.init = init.detach().clone().contiguous()
+        else:
+            self.init.copy_(init)
+        return self.reset()
+
+
+def _check_probs_tensor(what, probs, device):
+    if not isinstance(probs, torch.Tensor):
+        raise QtError(f"{what}: probs must be a tensor")
+    if probs.device.type != "cuda" or probs.device != device:
+        raise QtError(f"{what}: probs must be on {device} (got {probs.device}); there is no CPU or torch fallback")
+    if probs.dtype != torch.float32:
+        raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+
+
+def _check_probs_rows(what, probs):
+    """probs [B, frames, C] of a checked shape: the frame limit, then unit stride within a row and one stride between rows"""
+    B, T, C = probs.shape
+    if B * T > MAX_FRAMES:
+        raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+    probs = probs.detach()
+    if T and (probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1))):
+        probs = probs.contiguous()
+    return probs
+
+
+class PoseOrderDecoder(_PoseStreams):
     """The decoder of `streams` videos (or camera feeds): the tables, the carry int64 [streams, S + 2] = (frames_seen,
     score_offset, delta[S]), each stream's last path state, and a workspace that grows on demand, all in device memory.
     `decode` and `cycles` launch kernels and read nothing back.  See the module text."""
 
     def __init__(self, state_class, trans, device, streams=1, init=None, class_names=None):
-        sc, tr, init, class_names = _check_tables("PoseOrderDecoder", state_class, trans, init, streams, class_names)
-        S = int(sc.shape[0])
-        self.class_names = class_names
-        self.num_states, self.streams = S, streams
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise QtError("PoseOrderDecoder lives on an AMD GPU (device must be cuda:N); no CPU fallback")
-        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
+        super().__init__(state_class, trans, device, streams, init, class_names)
+        device = self.device
         self._state_class64 = self.state_class.to(torch.int64)
-        self.trans = torch.from_numpy(np.ascontiguousarray(tr, np.int32)).to(device)
-        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
-        self.carry = torch.zeros(streams, S + 2, dtype=torch.int64, device=device)
+        self.carry = torch.zeros(streams, self.num_states + 2, dtype=torch.int64, device=device)
         self._last = torch.full((streams,), -1, dtype=torch.int64, device=device)    # the last decode's last state; -1: none
         self._before = self._last                                                    # the same of the decode before it
-        self._workspace = None
-        self.device = self.carry.device
 
     def reset(self):
         """every stream starts anew (no host sync)"""
@@ -236,37 +317,13 @@ class PoseOrderDecoder:
         self._before = self._last
         return self
 
-    def load_tables(self, trans, init=None):
-        """a learner's tables (int32 tensors on this device) copied into the decoder's own, device to device and without a host
-        sync; every stream starts anew.  init None: no init from here on."""
-        _load_tables(self, "PoseOrderDecoder.load_tables", trans, init)
-        return self.reset()
-
     def decode(self, probs, filtered=False, emissions=False):
         """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on the decoder's device: predict's
         probabilities or the timeline's smoothed rows.  Returns (path int64, path_class int64), each [streams, frames] (or
         [frames]): the best state per frame and the class it emits, which is what FrameAnnotator.draw takes as `pred`;
         with filtered=True the causal states int64 as a third, with emissions=True the scores int32 [..., S] as the last."""
-        what = "PoseOrderDecoder.decode"
-        if not isinstance(probs, torch.Tensor):
-            raise QtError(f"{what}: probs must be a tensor")
-        if probs.device.type != "cuda" or probs.device != self.device:
-            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
-        if probs.dtype != torch.float32:
-            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+        probs, flat, T, C = self._check_probs("PoseOrderDecoder.decode", probs)
         B, S = self.streams, self.num_states
-        flat = probs.dim() == 2
-        if flat and B == 1:
-            probs = probs.unsqueeze(0)
-        if probs.dim() != 3 or probs.shape[0] != B or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
-            raise QtError(f"{what}: probs must be [{B}, frames, C]{' or [frames, C]' if B == 1 else ''} with frames >= 1 and "
-                          f"C <= {MAX_CLASSES} (got {list(probs.shape)})")
-        T, C = probs.shape[1], probs.shape[2]
-        if B * T > MAX_FRAMES:
-            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
-        probs = probs.detach()
-        if probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1)):
-            probs = probs.contiguous()
         lead = (T,) if flat else (B, T)
         dev = self.device
         path = torch.empty(lead, dtype=torch.int64, device=dev)
@@ -274,14 +331,12 @@ class PoseOrderDecoder:
         emis = torch.empty(lead + (S,), dtype=torch.int32, device=dev) if emissions else None
         desc = PoseOrderDesc(B, T, C, S)
         L = bind(_lib.lib())
-        need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(desc)))
-        if need and (self._workspace is None or self._workspace.numel() < need):
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = self._room(L.qt_pose_order_workspace_bytes, desc)
         with torch.cuda.device(dev):
             _lib.check(L.qt_pose_order_decode(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
                                               _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.carry), _lib.ptr(path),
-                                              _lib.ptr(filt), _lib.ptr(emis), _lib.ptr(self._workspace) if need else None,
-                                              self._workspace.numel() if need else 0, _lib.stream_ptr()), "qt_pose_order_decode")
+                                              _lib.ptr(filt), _lib.ptr(emis), ws, ws_bytes, _lib.stream_ptr()),
+                       "qt_pose_order_decode")
         self._before, self._last = self._last, path.view(B, T)[:, -1].clone()
         out = (path, self._state_class64[path])
         if filtered:
@@ -336,34 +391,19 @@ def _check_tables(who, state_class, trans, init, streams, class_names):
     return sc, tr, init, class_names
 
 
-class PosePosterior:
+class PosePosterior(_PoseStreams):
     """The posterior marginals of `streams` videos over the decoder's chain: the tables, the carry float64 [streams, S + 2] =
     (frames_seen, evidence_total in bits, a_last[S]) and a workspace that grows on demand, all in device memory.  `smooth`
     launches kernels and reads nothing back.  See the module text."""
 
     def __init__(self, state_class, trans, device, streams=1, init=None, class_names=None):
-        sc, tr, init, self.class_names = _check_tables("PosePosterior", state_class, trans, init, streams, class_names)
-        self.num_states, self.streams = int(sc.shape[0]), streams
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise QtError("PosePosterior lives on an AMD GPU (device must be cuda:N); no CPU fallback")
-        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
-        self.trans = torch.from_numpy(np.ascontiguousarray(tr, np.int32)).to(device)
-        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
-        self.carry = torch.zeros(streams, self.num_states + 2, dtype=torch.float64, device=device)
-        self._workspace = None
-        self.device = self.carry.device
+        super().__init__(state_class, trans, device, streams, init, class_names)
+        self.carry = torch.zeros(streams, self.num_states + 2, dtype=torch.float64, device=self.device)
 
     def reset(self):
         """every stream starts anew (no host sync)"""
         self.carry.zero_()
         return self
-
-    def load_tables(self, trans, init=None):
-        """a learner's tables (int32 tensors on this device) copied into this object's own, device to device and without a host
-        sync; every stream starts anew.  init None: no init from here on."""
-        _load_tables(self, "PosePosterior.load_tables", trans, init)
-        return self.reset()
 
     def smooth(self, probs, filtered=False, by_class=False, evidence=False):
         """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device: predict's
@@ -371,26 +411,8 @@ class PosePosterior:
         probability of every step at every frame given all frames up to the end of this call; then, as asked and in this order,
         filtered f32 of the same shape (given the frames up to each one alone), the class posterior f32 [..., C] and the
         call's evidence in bits, float64 [streams].  A tuple when anything beyond the posterior is asked for."""
-        what = "PosePosterior.smooth"
-        if not isinstance(probs, torch.Tensor):
-            raise QtError(f"{what}: probs must be a tensor")
-        if probs.device.type != "cuda" or probs.device != self.device:
-            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
-        if probs.dtype != torch.float32:
-            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+        probs, flat, T, C = self._check_probs("PosePosterior.smooth", probs)
         B, S = self.streams, self.num_states
-        flat = probs.dim() == 2
-        if flat and B == 1:
-            probs = probs.unsqueeze(0)
-        if probs.dim() != 3 or probs.shape[0] != B or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
-            raise QtError(f"{what}: probs must be [{B}, frames, C]{' or [frames, C]' if B == 1 else ''} with frames >= 1 and "
-                          f"C <= {MAX_CLASSES} (got {list(probs.shape)})")
-        T, C = probs.shape[1], probs.shape[2]
-        if B * T > MAX_FRAMES:
-            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
-        probs = probs.detach()
-        if probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1)):
-            probs = probs.contiguous()
         lead = (T,) if flat else (B, T)
         dev = self.device
         post = torch.empty(lead + (S,), dtype=torch.float32, device=dev)
@@ -399,14 +421,12 @@ class PosePosterior:
         ev = torch.empty(B, dtype=torch.float64, device=dev) if evidence else None
         desc = PoseOrderDesc(B, T, C, S)
         L = bind(_lib.lib())
-        need = int(L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc)))
-        if need and (self._workspace is None or self._workspace.numel() < need):
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = self._room(L.qt_pose_posterior_workspace_bytes, desc)
         with torch.cuda.device(dev):
             _lib.check(L.qt_pose_posterior(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
                                            _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.carry), _lib.ptr(post),
-                                           _lib.ptr(filt), _lib.ptr(cls), _lib.ptr(ev), _lib.ptr(self._workspace) if need else None,
-                                           self._workspace.numel() if need else 0, _lib.stream_ptr()), "qt_pose_posterior")
+                                           _lib.ptr(filt), _lib.ptr(cls), _lib.ptr(ev), ws, ws_bytes, _lib.stream_ptr()),
+                       "qt_pose_posterior")
         out = (post,) + tuple(t for t in (filt, cls, ev) if t is not None)
         return out[0] if len(out) == 1 else out
 
@@ -423,88 +443,35 @@ class PosePosterior:
         return posterior.gather(-1, path.unsqueeze(-1)).squeeze(-1)
 
 
-def _load_tables(obj, who, trans, init):
-    """trans int32 [S, S] and init int32 [S] or None, tensors on obj.device, into obj's own tensors (values are clamped by the
-    kernels as they are read: checking them here would need a host sync)"""
-    S = obj.num_states
-    for name, t, shape in (("trans", trans, (S, S)), ("init", init, (S,))):
-        if t is None and name == "init":
-            continue
-        if not isinstance(t, torch.Tensor) or t.device != obj.device or t.dtype != torch.int32 or tuple(t.shape) != shape:
-            raise QtError(f"{who}: {name} must be an int32 tensor {list(shape)} on {obj.device}")
-    obj.trans.copy_(trans)
-    if init is None:
-        obj.init = None
-    elif obj.init is None:
-        obj.init = init.detach().clone().contiguous()
-    else:
-        obj.init.copy_(init)
-
-
-class _PoseLag:
+class _PoseLag(_PoseStreams):
     """what PoseLagSmoother and PoseLagDecoder share: the tables, the count of frames seen (on the host: all streams advance
     together), the two carry buffers that are swapped after every push, and a workspace that grows on demand"""
     _carry_query = None
+    _empty_with_flush = True
 
     def __init__(self, state_class, trans, device, lag, streams=1, init=None, class_names=None):
-        who = type(self).__name__
-        sc, tr, init, self.class_names = _check_tables(who, state_class, trans, init, streams, class_names)
-        if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
-            raise ValueError(f"{who}: lag must be an integer in 0 .. {LAG_MAX} (got {lag!r})")
-        self.lag, self.num_states, self.streams = int(lag), int(sc.shape[0]), streams
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise QtError(f"{who} lives on an AMD GPU (device must be cuda:N); no CPU fallback")
-        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
-        self.trans = torch.from_numpy(np.ascontiguousarray(tr, np.int32)).to(device)
-        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
-        self.device = self.trans.device
-        self.seen = 0
+        super().__init__(state_class, trans, device, streams, init, class_names, lag=lag)
+        self.lag, self.seen = int(lag), 0
         desc = PoseLagDesc(streams, 1, 1, self.num_states, self.lag, 0, 0)
         nbytes = int(getattr(bind(_lib.lib()), self._carry_query)(ctypes.byref(desc)))
-        self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=device) for _ in range(2)]    # [0]: the next call's carry_in
-        self._workspace = None
+        self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]  # [0]: the next call's carry_in
+
+    def _check_own(self, who, init, lag):
+        if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
+            raise ValueError(f"{who}: lag must be an integer in 0 .. {LAG_MAX} (got {lag!r})")
+        return init
 
     def reset(self):
         """every stream starts anew (no host sync; the carry is not read at a stream's first frame)"""
         self.seen = 0
         return self
 
-    def load_tables(self, trans, init=None):
-        """a learner's tables (int32 tensors on this device) copied into this object's own, device to device and without a host
-        sync; every stream starts anew.  init None: no init from here on."""
-        _load_tables(self, f"{type(self).__name__}.load_tables", trans, init)
-        return self.reset()
-
     def _probs(self, what, probs, flush):
-        if not isinstance(probs, torch.Tensor):
-            raise QtError(f"{what}: probs must be a tensor")
-        if probs.device.type != "cuda" or probs.device != self.device:
-            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
-        if probs.dtype != torch.float32:
-            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
-        B = self.streams
-        flat = probs.dim() == 2
-        if flat and B == 1:
-            probs = probs.unsqueeze(0)
-        if probs.dim() != 3 or probs.shape[0] != B or not 1 <= probs.shape[2] <= MAX_CLASSES or (probs.shape[1] < 1 and not flush):
-            raise QtError(f"{what}: probs must be [{B}, frames, C]{' or [frames, C]' if B == 1 else ''} with C <= {MAX_CLASSES} "
-                          f"and frames >= 1, or 0 with flush (got {list(probs.shape)})")
-        T, C = probs.shape[1], probs.shape[2]
-        if B * T > MAX_FRAMES:
-            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
-        probs = probs.detach()
-        if T and (probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1))):
-            probs = probs.contiguous()
+        probs, flat, T, C = self._check_probs(what, probs, allow_empty=flush)
         first = max(0, self.seen - self.lag)
         count = (self.seen + T if flush else max(0, self.seen + T - self.lag)) - first
-        return probs, flat, T, C, first, count, PoseLagDesc(B, T, C, self.num_states, self.lag, int(bool(flush)), self.seen)
-
-    def _room(self, query, desc):
-        need = int(query(ctypes.byref(desc)))
-        if need and (self._workspace is None or self._workspace.numel() < need):
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return (_lib.ptr(self._workspace), self._workspace.numel()) if need else (None, 0)
+        desc = PoseLagDesc(self.streams, T, C, self.num_states, self.lag, int(bool(flush)), self.seen)
+        return probs, flat, T, C, first, count, desc
 
     def _advance(self, T):
         self.seen += T
@@ -579,7 +546,7 @@ class PoseLagDecoder(_PoseLag):
         return (first, path) + ((filt,) if filtered else ())
 
 
-class PoseOrderLearner:
+class PoseOrderLearner(_PoseTables):
     """Baum-Welch for the decoder's chain, on the device: the transition table (and, with learn_init, the start scores) fitted
     to videos whose frames carry class probabilities only.  `accumulate` is the E-step of one video or of a batch of videos of
     equal length (qt_pose_prior_expect adds the expected transition counts onto float64 accumulators in a fixed order),
@@ -588,67 +555,47 @@ class PoseOrderLearner:
     every allowed count.  Nothing is read back but by `totals` and `tables`.  See the module text."""
 
     def __init__(self, state_class, trans, device, init=None, pseudo_count=0.0, learn_init=False, class_names=None):
-        sc, tr, init, self.class_names = _check_tables("PoseOrderLearner", state_class, trans, init, 1, class_names)
-        if isinstance(pseudo_count, bool) or not isinstance(pseudo_count, (int, float, np.integer, np.floating)) or \
-                not 0.0 <= float(pseudo_count) < float("inf"):
-            raise ValueError(f"PoseOrderLearner: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
-        self.pseudo_count, self.learn_init = float(pseudo_count), bool(learn_init)
-        S = self.num_states = int(sc.shape[0])
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise QtError("PoseOrderLearner lives on an AMD GPU (device must be cuda:N); no CPU fallback")
-        tr = np.ascontiguousarray(tr, np.int32)
-        self.state_class = torch.from_numpy(sc.astype(np.int32)).to(device)
-        self.trans = torch.from_numpy(tr).to(device)
-        self.allowed = torch.from_numpy((tr > TRANS_FLOOR).astype(np.int32)).to(device)
-        if init is None and self.learn_init:
-            init = np.zeros(S, np.int32)                        # the start vector of zeros, written out
-        self.init = None if init is None else torch.from_numpy(init.astype(np.int32)).to(device)
+        self.learn_init = bool(learn_init)
+        super().__init__(state_class, trans, device, 1, init, class_names, pseudo_count=pseudo_count)
+        S, device = self.num_states, self.device
+        self.pseudo_count = float(pseudo_count)
+        self.allowed = (self.trans > TRANS_FLOOR).to(torch.int32)
         self.counts = torch.zeros(S, S, dtype=torch.float64, device=device)
         self.start_counts = torch.zeros(S, dtype=torch.float64, device=device)
         self._totals = torch.zeros(2, dtype=torch.float64, device=device)
-        self._workspace = None
-        self.device = self.counts.device
+
+    def _check_own(self, who, init, pseudo_count):
+        if isinstance(pseudo_count, bool) or not isinstance(pseudo_count, (int, float, np.integer, np.floating)) or \
+                not 0.0 <= float(pseudo_count) < float("inf"):
+            raise ValueError(f"{who}: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
+        if init is None and self.learn_init:
+            init = np.zeros(self.num_states, np.int32)          # the start vector of zeros, written out
+        return init
 
     def zero(self):
         """the accumulators to zero, before an E-step (no host sync)"""
         self.counts.zero_(), self.start_counts.zero_(), self._totals.zero_()
         return self
 
-    def _room(self, L, desc):
-        need = int(L.qt_pose_prior_workspace_bytes(ctypes.byref(desc)))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._workspace
-
     def accumulate(self, probs):
         """E-step of whole videos: probs f32 [B, n, C], or [n, C] for one, on the learner's device (predict's rows or the
         timeline's smoothed rows).  Adds onto counts, start_counts and the totals; nothing is read back."""
         what = "PoseOrderLearner.accumulate"
-        if not isinstance(probs, torch.Tensor):
-            raise QtError(f"{what}: probs must be a tensor")
-        if probs.device.type != "cuda" or probs.device != self.device:
-            raise QtError(f"{what}: probs must be on {self.device} (got {probs.device}); there is no CPU or torch fallback")
-        if probs.dtype != torch.float32:
-            raise QtError(f"{what}: f32 probabilities only (got {probs.dtype})")
+        _check_probs_tensor(what, probs, self.device)
         if probs.dim() == 2:
             probs = probs.unsqueeze(0)
         if probs.dim() != 3 or probs.shape[0] < 1 or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
             raise QtError(f"{what}: probs must be [B, frames, C] or [frames, C] with B, frames >= 1 and C <= {MAX_CLASSES} "
                           f"(got {list(probs.shape)})")
+        probs = _check_probs_rows(what, probs)
         B, T, C = probs.shape
-        if B * T > MAX_FRAMES:
-            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
-        probs = probs.detach()
-        if probs.stride(2) != 1 or probs.stride(1) < C or (B > 1 and probs.stride(0) != T * probs.stride(1)):
-            probs = probs.contiguous()
         desc = PoseOrderDesc(B, T, C, self.num_states)
         L = bind(_lib.lib())
-        ws = self._room(L, desc)
+        ws, ws_bytes = self._room(L.qt_pose_prior_workspace_bytes, desc)
         with torch.cuda.device(self.device):
             _lib.check(L.qt_pose_prior_expect(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
                                               _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.counts),
-                                              _lib.ptr(self.start_counts), _lib.ptr(self._totals), _lib.ptr(ws), ws.numel(),
+                                              _lib.ptr(self.start_counts), _lib.ptr(self._totals), ws, ws_bytes,
                                               _lib.stream_ptr()), "qt_pose_prior_expect")
         return self
 
@@ -668,10 +615,10 @@ class PoseOrderLearner:
         path = path.detach().contiguous()
         desc = PoseOrderDesc(B, T, 1, self.num_states)
         L = bind(_lib.lib())
-        ws = self._room(L, desc)
+        ws, ws_bytes = self._room(L.qt_pose_prior_workspace_bytes, desc)
         with torch.cuda.device(self.device):
             _lib.check(L.qt_pose_prior_count_paths(ctypes.byref(desc), _lib.ptr(path), _lib.ptr(self.counts),
-                                                   _lib.ptr(self.start_counts), _lib.ptr(self._totals), _lib.ptr(ws), ws.numel(),
+                                                   _lib.ptr(self.start_counts), _lib.ptr(self._totals), ws, ws_bytes,
                                                    _lib.stream_ptr()), "qt_pose_prior_count_paths")
         return self
 

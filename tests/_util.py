@@ -1,6 +1,7 @@
 """Shared helpers for the test-suite (imports the hyphenated package by name)."""
 import importlib
 import os
+import re
 import sys
 
 import numpy as np
@@ -14,6 +15,19 @@ PKG = "multimodal-hierarchical-cnn-for-sun-salutation-pose-classification_amd"
 
 def pkg(sub=None):
     return importlib.import_module(PKG if sub is None else f"{PKG}.{sub}")
+
+
+def pose_chain_header():
+    """the text of csrc/pose_chain.h, the one place of the pose-order chain's table, limits and floors: pose_order.hip,
+    pose_posterior.hip and pose_prior.hip include it and define no log2 table, no *_FLOOR and no *_TRANS_FLOOR of
+    their own"""
+    csrc = os.path.join(ROOT, PKG, "csrc")
+    for name in ("pose_order.hip", "pose_posterior.hip", "pose_prior.hip"):
+        src = open(os.path.join(csrc, name)).read()
+        assert '#include "pose_chain.h"' in src, name
+        code = re.sub(r"//[^\n]*", "", src)
+        assert not re.search(r"_LOG2\[256\]\s*=|\b\w*_FLOOR\s*=(?!=)", code), name
+    return open(os.path.join(csrc, "pose_chain.h")).read()
 
 
 def rel_err(a, b):

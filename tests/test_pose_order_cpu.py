@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import _pose_order_ref as R
-from _util import PKG, ROOT, pkg
+from _util import PKG, ROOT, pkg, pose_chain_header
 
 QT_ERR_INVALID_ARG, QT_ERR_UNSUPPORTED = -1, -3
 F32 = np.float32
@@ -25,8 +25,7 @@ def test_log2_table_is_its_formula():
     assert R.LOG2_TABLE[:4] == (1, 2, 4, 5) and R.LOG2_TABLE[-4:] == (253, 254, 255, 256)
     M = pkg("pose_order")
     assert tuple(M.LOG2_TABLE) == R.LOG2_TABLE
-    src = open(os.path.join(ROOT, PKG, "csrc", "pose_order.hip")).read()
-    body = re.search(r"PO_LOG2\[256\] = \{(.*?)\};", src, re.S).group(1)
+    body = re.search(r"PC_LOG2\[256\] = \{(.*?)\};", pose_chain_header(), re.S).group(1)
     assert [int(v) for v in re.findall(r"\d+", body)] == list(R.LOG2_TABLE)
 
 
@@ -173,9 +172,9 @@ def test_constants_are_the_kernels_and_the_modules():
     M = pkg("pose_order")
     assert (M.TILE, M.MAX_STATES, M.MAX_CLASSES, M.MAX_FRAMES, M.SCORE_FLOOR, M.TRANS_FLOOR) == \
         (R.TILE, R.MAX_STATES, R.MAX_CLASSES, R.MAX_FRAMES, R.SCORE_FLOOR, R.TRANS_FLOOR)
-    src = open(os.path.join(ROOT, PKG, "csrc", "pose_order.hip")).read()
+    src = pose_chain_header() + open(os.path.join(ROOT, PKG, "csrc", "pose_order.hip")).read()
     const = lambda name: int(re.search(rf"constexpr int {name} = (-?\d+);", src).group(1))
-    assert (const("PO_TILE"), const("PO_MAX_S"), const("PO_MAX_C"), const("PO_FLOOR"), const("PO_TRANS_FLOOR")) == \
+    assert (const("PC_TILE"), const("PC_MAX_S"), const("PC_MAX_C"), const("PC_FLOOR"), const("PC_TRANS_FLOOR")) == \
         (R.TILE, R.MAX_STATES, R.MAX_CLASSES, R.SCORE_FLOOR, R.TRANS_FLOOR)
     assert M.GROUP == const("PO_GROUP") == R.GROUP
     for S in (1, 2, 3, 11, 12, 13, 16, 17, 45, 46, 63, 64):

@@ -11,7 +11,7 @@ import pytest
 
 import _pose_order_ref as O
 import _pose_posterior_ref as R
-from _util import PKG, ROOT, pkg
+from _util import PKG, ROOT, pkg, pose_chain_header
 
 QT_ERR_INVALID_ARG, QT_ERR_UNSUPPORTED = -1, -3
 F32 = np.float32
@@ -109,11 +109,11 @@ def test_new_symbols_are_declared_and_exported():
         assert symbol in declared and hasattr(lib, symbol), symbol
     P, M = pkg(), pkg("pose_order")
     assert P.PosePosterior is M.PosePosterior and "PosePosterior" in P.__all__
-    src = open(os.path.join(ROOT, PKG, "csrc", "pose_posterior.hip")).read()
-    body = re.search(r"PP_LOG2\[256\] = \{(.*?)\};", src, re.S).group(1)
+    src = pose_chain_header() + open(os.path.join(ROOT, PKG, "csrc", "pose_posterior.hip")).read()
+    body = re.search(r"PC_LOG2\[256\] = \{(.*?)\};", src, re.S).group(1)
     assert [int(v) for v in re.findall(r"\d+", body)] == list(O.LOG2_TABLE)
     const = lambda name: int(re.search(rf"constexpr int {name} = (-?\d+);", src).group(1))
-    assert (const("PP_TILE"), const("PP_MAX_S"), const("PP_MAX_C"), const("PP_FLOOR"), const("PP_TRANS_FLOOR")) == \
+    assert (const("PC_TILE"), const("PC_MAX_S"), const("PC_MAX_C"), const("PC_FLOOR"), const("PC_TRANS_FLOOR")) == \
         (O.TILE, O.MAX_STATES, O.MAX_CLASSES, O.SCORE_FLOOR, O.TRANS_FLOOR)
     for S in (1, 2, 3, 11, 12, 13, 16, 17, 45, 46, 63, 64):
         assert M.posterior_scan_trip_tiles(S) == max(1, min(const("PP_SCAN_MAX_TILES"), const("PP_SCAN_FLOATS") // (S * S)))

@@ -13,7 +13,7 @@ import pytest
 import _pose_order_ref as O
 import _pose_posterior_ref as P
 import _pose_prior_ref as R
-from _util import PKG, ROOT, pkg
+from _util import PKG, ROOT, pkg, pose_chain_header
 
 QT_ERR_INVALID_ARG, QT_ERR_UNSUPPORTED = -1, -3
 F32 = np.float32
@@ -158,8 +158,7 @@ def test_new_symbols_are_declared_and_exported():
     Pk, M = pkg(), pkg("pose_order")
     assert Pk.PoseOrderLearner is M.PoseOrderLearner and "PoseOrderLearner" in Pk.__all__
     assert callable(Pk.PoseOrderDecoder.load_tables) and callable(Pk.PosePosterior.load_tables)
-    src = open(os.path.join(ROOT, PKG, "csrc", "pose_prior.hip")).read()
-    assert int(re.search(r"constexpr int PR_TRANS_FLOOR = (-?\d+);", src).group(1)) == O.TRANS_FLOOR
+    assert int(re.search(r"constexpr int PC_TRANS_FLOOR = (-?\d+);", pose_chain_header()).group(1)) == O.TRANS_FLOOR
 
 
 def _lib():
