@@ -951,6 +951,88 @@ int qt_timeline_smooth(const qt_timeline_desc* desc, const float* probs, long lo
                        long long* pred, float* confidence, void* stream);
 int qt_timeline_decode(const qt_timeline_desc* desc, const long long* pred, const float* confidence, long long* state,
                        long long* stable, long long* segments, void* stream);
+/* Segment-level evaluation: the segmental edit score and the segmental F1 at IoU thresholds (Lea et al., CVPR 2017; the MS-TCN
+ * evaluation: Edit, F1@10/25/50) of a per-frame labelling against the ground truth, counted in integers on the device and added
+ * to a state in device memory.  qt_metrics_update and qt_scores_update count frames: a prediction that splits every pose hold
+ * into five fragments scores there almost as a clean one.  These counts see runs: what qt_timeline_decode's stable labels,
+ * qt_pose_order_decode's path classes and a raw argmax differ in.  The reference has no such step (comparative analysis/
+ * analysis.py:60-109 counts frames), so nothing of it is restated here.
+ *
+ * Inputs.  Per call `batch` WHOLE videos.  pred, label: int64 [batch][frames], row strides ld_pred, ld_label >= frames
+ * elements; padding columns are never read.  lengths: int32 [batch] or NULL: video b has len_b = clamp(lengths[b], 0, frames)
+ * frames, NULL means frames; frames at and beyond len_b are never read.
+ * Runs.  A frame's value v is KNOWN when 0 <= v < C.  A run is a maximal stretch of consecutive frames of one video that hold
+ * the same known value; unknown frames belong to no run and are a gap, as in qt_timeline_decode, so two runs of one class with
+ * a gap between them are two runs.  A run is { start, length, class }.  P = the runs of pred (m of them), Y = the runs of label
+ * (n of them), both in order of start.
+ * Per video, all in integers:
+ *   frames_labelled  frames whose label is known;  frames_correct  those of them with pred == label
+ *   overflow         m > QT_SEGMENTS_MAX or n > QT_SEGMENTS_MAX: the record holds the true m and n, D = -1 and every tp_k = -1;
+ *                    the frame counts still count; the video adds to videos_overflow and to nothing else below
+ *   D                the Levenshtein distance of the class sequences of P and Y, insertion, deletion and substitution 1 each:
+ *                    D[i][j] = min(D[i-1][j] + 1, D[i][j-1] + 1, D[i-1][j-1] + (p_i != y_j)), D[i][0] = i, D[0][j] = j
+ *   edit_q           with M = max(m, n) > 0: ((M - D) * 2^32) / M, a division of int64; M == 0: the video is EMPTY and adds
+ *                    nothing to the edit sums
+ *   partner          of a predicted run p among the true runs y of p's class, end = start + length:
+ *                      inter = max(0, min(p_end, y_end) - max(p_start, y_start)),  union = max(p_end, y_end) - min(p_start, y_start)
+ *                    the y with the largest inter / union, fractions compared by cross-multiplication in int64, ties to the lowest
+ *                    index; none when Y has no run of that class
+ *   tp_k             p PASSES threshold k (pct_k in 1 .. 100, 1 <= K <= 8) when it has a partner and 100 inter >= pct_k union;
+ *                    tp_k = the number of DISTINCT true runs that are the partner of at least one passing predicted run;
+ *                    fp_k = m - tp_k, fn_k = n - tp_k
+ * (In the published loop each predicted run in turn claims its best partner and is a false positive if that one is taken.  For
+ * thresholds above zero both forms count the same: tests/_segments_ref.py holds both.)
+ *   records  int64 [batch][QT_SEGMENTS_RECORD + K] or NULL:  { m, n, D, frames_labelled, frames_correct, tp_0 .. tp_{K-1} }
+ *   state    int64 [QT_SEGMENTS_STATE + K], zeroed once by the caller, added to by every call:
+ *            { videos, videos_overflow, videos_empty, seg_pred, seg_true, edit_dist, edit_max, edit_q, frames_labelled,
+ *              frames_correct, tp_0 .. }
+ *            seg_pred = sum m, seg_true = sum n, edit_dist = sum D, edit_max = sum M, edit_q and tp_k over the videos that do
+ *            not overflow; the frame counts over all.  The state is additive: any split of the videos into calls, any order and
+ *            a sum of per-rank states give the same bits.
+ * The report is the caller's arithmetic on one copy of the state (no kernel), a zero denominator giving 0:
+ *   edit = 100 edit_q / (2^32 (videos - videos_overflow - videos_empty)),  edit_micro = 100 (1 - edit_dist / edit_max)
+ *   precision_k = 100 tp_k / seg_pred,  recall_k = 100 tp_k / seg_true,  f1_k = 100 * 2 tp_k / (seg_pred + seg_true)
+ *   frame_accuracy = frames_correct / frames_labelled,  over_segmentation = seg_pred / seg_true
+ * workspace: qt_segments_workspace_bytes(desc) bytes (batch records), 8-byte aligned, always required.
+ * Two launches.  One workgroup of 256 threads per video: (a) frames in trips of 256, thread = frame; the thread at a run's last
+ * frame writes the run, its slot the ballot rank (64-bit ballots) of its end plus the ends of the waves and trips before, its
+ * start the last start flag at or before it; runs go to LDS up to QT_SEGMENTS_MAX, m and n go on counting; (b) the frame
+ * counts; (c) the Levenshtein table by anti-diagonals, three rotating diagonals of QT_SEGMENTS_MAX + 1 int32 in LDS, one
+ * barrier per diagonal; (d) thread = predicted run, a plain scan of the true runs, an LDS flag per (partner, threshold),
+ * counted by ballot; (e) the record goes to the workspace.  Then ONE workgroup adds the records of the workspace to the state
+ * (integer atomics) and copies them to `records`.  40 KiB of static LDS.  No workgroup waits for another inside a launch, no
+ * zero fill, no host synchronisation; inputs are never written; nothing outside [0, len_b) of a row is read.
+ *
+ * qt_segments_encode (reads batch, frames, num_classes, capacity) is the run extraction alone, the same device function: the
+ * first `capacity` runs of values (int64 [batch][frames], row stride ld) go to runs: int32 [batch][capacity][3] = { start,
+ * length, class }, the true number of runs to counts: int32 [batch], as qt_timeline_decode does with segments_total; records
+ * at and behind the count are not written.  One launch, one workgroup per video.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument) for a null desc, batch < 1, frames < 0,
+ * num_classes outside 1 .. QT_SEGMENTS_MAX_CLASSES, update: num_thresholds outside 1 .. QT_SEGMENTS_MAX_THRESHOLDS, a pct outside
+ * 1 .. 100, ld_pred or ld_label < frames, a null state or workspace, a workspace that is too small; encode: ld < frames, a
+ * negative capacity, runs == NULL with capacity > 0, null counts; null (with frames > 0) or misaligned pointers (8 bytes for
+ * int64, 4 for int32).  QT_ERR_UNSUPPORTED for more than 2^22 frames (or videos) in all.  frames == 0 is allowed: every video
+ * is then empty, and pred, label and values are not looked at. */
+#define QT_SEGMENTS_MAX 1024
+#define QT_SEGMENTS_MAX_CLASSES 1024
+#define QT_SEGMENTS_MAX_THRESHOLDS 8
+#define QT_SEGMENTS_RECORD 5
+#define QT_SEGMENTS_STATE 10
+typedef struct qt_segments_desc {
+  int batch;                        /* videos in this call */
+  int frames;                       /* columns per video; a video's own length is lengths[b] */
+  int num_classes;                  /* C, 1 .. 1024 */
+  int num_thresholds;               /* K, 1 .. 8: update */
+  int pct[8];                       /* IoU thresholds in per cent, 1 .. 100, the first K are read: update */
+  int capacity;                     /* runs per video in `runs`: encode */
+} qt_segments_desc;
+size_t qt_segments_workspace_bytes(const qt_segments_desc* desc);
+int qt_segments_update(const qt_segments_desc* desc, const long long* pred, long long ld_pred, const long long* label,
+                       long long ld_label, const int* lengths, long long* state, long long* records, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int qt_segments_encode(const qt_segments_desc* desc, const long long* values, long long ld, const int* lengths, int* runs,
+                       int* counts, void* stream);
 /* Pose-order decoding: the best path of a hidden-Markov chain whose STATES are the steps of the pose sequence (the twelve
  * steps of a Sun Salutation, in their cyclic order), each state emitting one of the C classes, over the probabilities of the
  * video loop (qt_metrics_update's probs, or qt_timeline_smooth's smoothed rows).  The debounced argmax of qt_timeline_decode

@@ -22,6 +22,7 @@ from .metrics import EvalMeter, predict  # noqa: F401
 from .scores import ScoreMeter  # noqa: F401
 from .annotate import MAJOR_SEGMENTS, POSE_CONNECTIONS, FrameAnnotator, caption_atlas  # noqa: F401
 from .timeline import PoseTimeline  # noqa: F401
+from .segments import SegmentMeter, segment_runs  # noqa: F401
 from .pose_order import PoseLagDecoder, PoseLagSmoother  # noqa: F401
 from .pose_order import PoseOrderDecoder, PoseOrderLearner, PosePosterior, cyclic_prior, prob_score  # noqa: F401
 
@@ -32,4 +33,5 @@ __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnL
            "SequenceWindows", "WindowPlan", "fit_class_stats", "CnnLstmStream",
            "FrameAnnotator", "caption_atlas", "POSE_CONNECTIONS", "MAJOR_SEGMENTS", "PoseTimeline",
            "PoseOrderDecoder", "PosePosterior", "PoseOrderLearner", "PoseLagSmoother", "PoseLagDecoder", "cyclic_prior", "prob_score",
+           "SegmentMeter", "segment_runs",
            "QtError", "LIB_PATH"]
