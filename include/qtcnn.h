@@ -1265,6 +1265,71 @@ long long qt_pose_lag_decode_workspace_bytes(const qt_pose_lag_desc* desc);
 int qt_pose_lag_decode(const qt_pose_lag_desc* desc, const float* probs, long long ld, const int* state_class,
                        const int* trans, const int* init, const void* carry_in, void* carry_out, long long* lag_path,
                        long long* filtered, void* workspace, long long workspace_bytes, void* stream);
+/* Pose-order decoding with hold durations: the best SEGMENTATION of a whole video under an explicit-duration (semi-Markov)
+ * chain.  qt_pose_order_decode knows of a hold only one `stay` score per state, so every hold length is geometric and its
+ * most likely length is one frame; here a segment is a pair (state, length), a table scores every length per state, and the
+ * best sequence of segments is found jointly with the step order.  The reference has no such step.  Every number is an integer
+ * from the emission score on, so every output is the same bits on every run.
+ *
+ * probs, ld, state_class, trans, init, the emission score q and e[f][j] = q(probs[f][state_class[j]]) (the floor -8192 for a
+ * class outside [0, C)) are qt_pose_order_decode's; trans and init are clamped to [-65536, 0] as read.  New:
+ *   dur       int32 [S][D], D = desc->max_duration in 1 .. QT_POSE_DUR_MAX = 128: dur[j][d - 1] is the score of a segment of
+ *             d frames in state j, clamped to [-65536, 0] as read
+ *   dur_open  int32 [S][D], or NULL for dur itself: the score of a segment that the video cuts off, which are a stream's
+ *             first and last segment (a caller fills it with the suffix maximum of dur, so that a hold whose start or end lies
+ *             outside the video is not charged for being short)
+ *   lengths   int32 [batch] in device memory, or NULL: stream b has T_b = lengths[b] frames, clamped into 1 .. frames as
+ *             read and never used as an unchecked index; NULL: every stream has `frames`
+ * Forward, per stream of T frames, in exact integers (int64); cum[f][j] = the sum of e[g][j] over g < f:
+ *   beta[0][j]  = max_i (init[i] + trans[i][j])        (init all zeros when NULL: the decoder's scores before the first frame)
+ *   alpha[f][j] = max over d = 1 .. min(D, f) of  beta[f - d][j] + len(j, d, f) + cum[f][j] - cum[f - d][j],   f = 1 .. T
+ *                 len(j, d, f) = dur_open[j][d - 1] where the segment touches a cut (f - d == 0 or f == T), else dur[j][d - 1]
+ *   dlen[f][j]  = the LOWEST d that attains it
+ *   beta[f][j]  = max_i (alpha[f][i] + trans[i][j]),   from[f][j] = the LOWEST i that attains it,              f = 1 .. T - 1
+ * The diagonal of trans is read like any other entry: a hold of more than D frames is several segments of one state joined by
+ * trans[j][j].  End: last = the lowest j that attains max_j alpha[T][j]; score[b] = that maximum.
+ * Backtrace: f = T, j = last; repeat { d = dlen[f][j]; frames f - d .. f - 1 get path = j and start = f - d; f -= d; stop at
+ * f == 0; j = from[f][j] }.
+ *   path    int64 [batch][frames], required        start   int64 [batch][frames], or NULL: the first frame of the segment a
+ *   score   int64 [batch], or NULL                         frame lies in (f - start[f]: "held for n frames")
+ * Frames at and beyond T_b get path = -1 and start = -1.  A stream alone gives the bits of the same stream in a batch, and a
+ * stream with lengths[b] = L the bits of a call on its first L frames.  Nothing is carried between calls: whole videos only.
+ * With D = 1 and dur all zero, path is qt_pose_order_decode's path; with dur[j][d - 1] = (d - 1) stay, trans[j][j] = stay and
+ * dur_open NULL, score is the decoder's best score for every D.
+ * One launch, one workgroup per stream walking its frames in order: the last D rows of g[f][j] = beta[f][j] - cum[f][j] are a
+ * ring of int64 in LDS (alpha[f][j] = cum[f][j] + max_d (g[f - d][j] + len)), the candidates of both maxima are spread over
+ * the workgroup, and (dlen - 1) | from << 7 goes to the workspace as 16 bits per (f, j); the same workgroup then walks the
+ * segments back and writes each one's frames across its lanes.  qt_pose_duration_workspace_bytes: batch * frames * S * 2,
+ * rounded up to 8 bytes (every slot that is read is written in the same call), 0 for a descriptor that would be refused.  No
+ * workgroup waits for another, no atomics, no host synchronisation; inputs are never written.
+ *
+ * qt_pose_duration_count gathers the run lengths of state paths (this decoder's, qt_pose_order_decode's, or labelled steps) for
+ * fitting dur: path int64 [batch][frames] with row stride ld_path >= frames, lengths as above.  A run is a maximal stretch of
+ * one state j in [0, S) over frames [s, e) of a stream's first T_b frames; an entry outside [0, S) ends a run and counts
+ * nowhere.  Every run with s > 0 and e < T_b (the first and the last are cut by the video) adds 1 to
+ * counts[j][min(e - s, D) - 1]; counts int64 [S][D] is added to, the caller zeroes it once.  Integer atomics: the same bits in
+ * any order.  desc->num_classes is not read beyond its range check.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument) for a null desc, non-positive batch or frames,
+ * num_states or num_classes outside 1 .. 64, max_duration outside 1 .. 128, ld < C, ld_path < frames, a null probs,
+ * state_class, trans, dur or path (count: path or counts), misaligned pointers (4 bytes for f32 and int32, 8 for int64 and
+ * the workspace), a workspace smaller than the query's size, an output (path, start, score, workspace; counts) that overlaps
+ * an input or another output; QT_ERR_UNSUPPORTED for more than 2^20 frames in all (batch * frames). */
+#define QT_POSE_DUR_MAX 128
+typedef struct qt_pose_duration_desc {
+  int batch;                        /* streams */
+  int frames;                       /* frames per stream (the longest; see lengths) */
+  int num_classes;                  /* C, 1 .. 64 */
+  int num_states;                   /* S, 1 .. 64 */
+  int max_duration;                 /* D, 1 .. QT_POSE_DUR_MAX */
+} qt_pose_duration_desc;
+long long qt_pose_duration_workspace_bytes(const qt_pose_duration_desc* desc);
+int qt_pose_duration_decode(const qt_pose_duration_desc* desc, const float* probs, long long ld, const int* state_class,
+                            const int* trans, const int* init, const int* dur, const int* dur_open, const int* lengths,
+                            long long* path, long long* start, long long* score, void* workspace, long long workspace_bytes,
+                            void* stream);
+int qt_pose_duration_count(const qt_pose_duration_desc* desc, const long long* path, long long ld_path, const int* lengths,
+                           long long* counts, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

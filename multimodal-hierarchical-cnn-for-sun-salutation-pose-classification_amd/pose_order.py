@@ -61,6 +61,30 @@ last, the outputs are the bits of one push.
         confidence = smoother.confidence(lagged, lag_path)          # draw frame `first` from the ring of delayed frames
     first, lagged = smoother.push(rows[:, :0], flush=True)          # the last lag frames, at the end of the video
 
+PoseDurationDecoder (csrc/pose_duration.hip) is the decoder with hold durations, for a whole video in hand.  The chain above
+knows of a hold only one `stay` score per state, so every hold length is geometric and its most likely length is one frame: a
+two-frame visit to the next step and back, or a step skipped because its three frames scored no better than staying, cost it
+little, and they are what SegmentMeter's Edit and F1@IoU punish.  Here a segment is a pair (step, length), a table dur int32
+[S, D] scores every length 1 .. D <= 128 per step (a longer hold is several segments joined by trans[j][j]), and the best
+segmentation is found jointly with the step order (explicit-duration, semi-Markov Viterbi).  dur_open scores the first and the
+last segment of a video, which the video cuts off: by default the suffix maximum of dur, so that a hold whose start or end lies
+outside the video is not charged for being short.  Videos of different lengths go in one call (`lengths`); frames beyond a
+video's end get path -1.  Integers throughout: the same bits on every run.  In the evaluation loop it takes the place of
+`decoder.decode`:
+
+    dur = hold_prior(S, D=64, shortest=4, longest=48)               # or duration_prior(counts) from labelled tracks, below
+    durdec = PoseDurationDecoder(state_class, trans, dur, device, streams=B, class_names=class_names)
+    for rows, labels, lengths in videos:                            # f32 [B, frames, C], int64 [B, frames], int32 [B]
+        path, path_class, start = durdec.decode(rows, lengths=lengths, start=True)    # nothing read back
+        rounds += durdec.cycles(path)
+        meter.update(path_class, labels, lengths=lengths)           # SegmentMeter
+        held = torch.arange(rows.shape[1], device=device) - start   # "held for n frames", for the caption
+    counts = durdec.count_durations(step_labels, lengths)           # int64 [S, D] on the device: run lengths of labelled steps
+    dur = duration_prior(counts.cpu().numpy())                      # the table fitted to them
+
+Not built for the duration decoder: streaming, fixed-lag and split calls (the carry would be the last D frames of beta),
+posteriors and Baum-Welch over durations, D > 128, true minus infinity (a forbidden length is -65536).
+
 Not built: ragged batches (per-sequence lengths) and videos split across calls in the learner, learning emissions (they are the
 network's), tying rows, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second level of the
 posterior's scan; for the fixed-lag pair: sliding-window products that share work between neighbouring windows (f32 (L, +) is
@@ -81,6 +105,7 @@ MAX_STATES = 64             # QT_POSE_ORDER_MAX_STATES
 MAX_CLASSES = 64            # QT_POSE_ORDER_MAX_CLASSES
 MAX_FRAMES = 1 << 20
 LAG_MAX = 63                # QT_POSE_LAG_MAX
+DUR_MAX = 128               # QT_POSE_DUR_MAX
 SCORE_FLOOR = -8192         # q of NaN and of everything below 2^-32
 TRANS_FLOOR = -65536
 # rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the table of csrc/pose_chain.h
@@ -110,6 +135,11 @@ class PoseOrderDesc(ctypes.Structure):   # qt_pose_order_desc
 class PoseLagDesc(ctypes.Structure):     # qt_pose_lag_desc
     _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
                 ("lag", ctypes.c_int), ("flush", ctypes.c_int), ("seen", ctypes.c_longlong)]
+
+
+class PoseDurationDesc(ctypes.Structure):   # qt_pose_duration_desc
+    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
+                ("max_duration", ctypes.c_int)]
 
 
 def bind(L):
@@ -146,6 +176,14 @@ def bind(L):
     L.qt_pose_lag_decode.argtypes = [ctypes.POINTER(PoseLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
         [ctypes.c_void_p] * 8 + [ctypes.c_longlong, ctypes.c_void_p]
     L.qt_pose_lag_decode.restype = ctypes.c_int
+    L.qt_pose_duration_workspace_bytes.argtypes = [ctypes.POINTER(PoseDurationDesc)]
+    L.qt_pose_duration_workspace_bytes.restype = ctypes.c_longlong
+    L.qt_pose_duration_decode.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 10 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_duration_decode.restype = ctypes.c_int
+    L.qt_pose_duration_count.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 3
+    L.qt_pose_duration_count.restype = ctypes.c_int
     L._pose_order_bound = True
     return L
 
@@ -204,6 +242,56 @@ def cyclic_prior(step_classes, stay, advance, skip=None, other=TRANS_FLOOR, wrap
                 continue
             trans[s, (s + step) % S] = value
     return np.array(classes, np.int32), trans
+
+
+def _dur_shape(who, S, D):
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) <= MAX_STATES:
+        raise ValueError(f"{who}: S must be an integer in 1 .. {MAX_STATES} (got {S!r})")
+    if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 1 <= int(D) <= DUR_MAX:
+        raise ValueError(f"{who}: D must be an integer in 1 .. {DUR_MAX} (got {D!r})")
+    return int(S), int(D)
+
+
+def duration_prior(counts, pseudo_count=1.0):
+    """dur int32 [S, D] from run-length counts [S, D] (PoseDurationDecoder.count_durations, integers), on the host:
+    prob_score of (counts + pseudo_count) / the row's sum of them, as f32.  A row without any count and without a pseudo-count
+    scores the floor -8192 everywhere."""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.dtype.kind not in "iu" or not 1 <= c.shape[0] <= MAX_STATES or not 1 <= c.shape[1] <= DUR_MAX or \
+            (c < 0).any():
+        raise ValueError(f"duration_prior: counts must be [S <= {MAX_STATES}, D <= {DUR_MAX}] integers >= 0 (got shape "
+                         f"{c.shape}, {c.dtype})")
+    if isinstance(pseudo_count, bool) or not isinstance(pseudo_count, (int, float, np.integer, np.floating)) or \
+            not 0.0 <= float(pseudo_count) < float("inf"):
+        raise ValueError(f"duration_prior: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
+    r = c.astype(np.float64) + float(pseudo_count)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = (r / r.sum(axis=1, keepdims=True)).astype(np.float32)
+    return prob_score(p).astype(np.int32)
+
+
+def hold_prior(S, D, shortest, longest, inside=0, outside=TRANS_FLOOR):
+    """dur int32 [S, D] of the simple box: `inside` for shortest <= d <= longest, `outside` for every other length"""
+    S, D = _dur_shape("hold_prior", S, D)
+    for name, v in (("shortest", shortest), ("longest", longest)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError(f"hold_prior: {name} must be an integer >= 1 (got {v!r})")
+    if shortest > longest:
+        raise ValueError(f"hold_prior: shortest = {shortest} > longest = {longest}")
+    inside, outside = _score("inside", inside), _score("outside", outside)
+    d = np.arange(1, D + 1)
+    row = np.where((d >= shortest) & (d <= longest), inside, outside).astype(np.int32)
+    return np.tile(row, (S, 1))
+
+
+def geometric_durations(stay, S, D):
+    """dur int32 [S, D] with dur[j][d - 1] = (d - 1) * stay: with trans[j][j] = stay the plain chain's implied durations (a hold
+    split into segments costs what it costs inside one)"""
+    S, D = _dur_shape("geometric_durations", S, D)
+    stay = _score("stay", stay)
+    if (D - 1) * stay < TRANS_FLOOR:
+        raise ValueError(f"geometric_durations: (D - 1) * stay = {(D - 1) * stay} is below {TRANS_FLOOR}")
+    return np.tile((np.arange(D, dtype=np.int64) * stay).astype(np.int32), (S, 1))
 
 
 class _PoseTables:
@@ -363,6 +451,125 @@ class PoseOrderDecoder(_PoseStreams):
             raise QtError(f"PoseOrderDecoder.cycles: path must be [{B}, frames] (got {list(path.shape)})")
         before = torch.cat([self._before[:, None], path[:, :-1]], dim=1)
         return ((before == wrap_from) & (path == wrap_to)).sum(dim=1)
+
+
+class PoseDurationDecoder(_PoseTables):
+    """The decoder with hold durations of `streams` whole videos: the chain's tables, dur and dur_open int32 [S, D] and a
+    workspace that grows on demand, all in device memory.  dur_open: "suffix_max" (built here, on the host), a table of its
+    own, or None for dur itself.  Nothing is carried between calls; `decode`, `cycles` and `count_durations` launch kernels
+    and read nothing back.  See the module text."""
+
+    def __init__(self, state_class, trans, dur, device, streams=1, init=None, dur_open="suffix_max", class_names=None):
+        super().__init__(state_class, trans, device, streams, init, class_names, dur=dur, dur_open=dur_open)
+        dur, dur_open = self._dur_host
+        del self._dur_host
+        self.max_duration = int(dur.shape[1])
+        self.dur = torch.from_numpy(np.ascontiguousarray(dur, np.int32)).to(self.device)
+        self.dur_open = None if dur_open is None else torch.from_numpy(np.ascontiguousarray(dur_open, np.int32)).to(self.device)
+        self._state_class64 = self.state_class.to(torch.int64)
+
+    def _check_own(self, who, init, dur, dur_open):
+        S = self.num_states
+
+        def table(name, t):
+            t = np.asarray(t)
+            if t.ndim != 2 or t.shape[0] != S or not 1 <= t.shape[1] <= DUR_MAX or t.dtype.kind not in "iu":
+                raise ValueError(f"{who}: {name} must be [{S}, D] integers with D in 1 .. {DUR_MAX} (got shape {t.shape}, "
+                                 f"{t.dtype})")
+            if (t < TRANS_FLOOR).any() or (t > 0).any():
+                raise ValueError(f"{who}: {name} holds a score outside {TRANS_FLOOR} .. 0")
+            return t
+
+        dur = table("dur", dur)
+        if isinstance(dur_open, str):
+            if dur_open != "suffix_max":
+                raise ValueError(f"{who}: dur_open must be 'suffix_max', a table or None (got {dur_open!r})")
+            dur_open = np.maximum.accumulate(dur[:, ::-1], axis=1)[:, ::-1].copy()     # (a copy: no negative stride, at D = 1 either)
+        elif dur_open is not None:
+            dur_open = table("dur_open", dur_open)
+            if dur_open.shape != dur.shape:
+                raise ValueError(f"{who}: dur_open is {list(dur_open.shape)}, dur {list(dur.shape)}")
+        self._dur_host = (dur, dur_open)
+        return init
+
+    def _check_lengths(self, what, lengths, B):
+        if lengths is None:
+            return None
+        if not isinstance(lengths, torch.Tensor) or lengths.device != self.device or lengths.dtype != torch.int32 or \
+                tuple(lengths.shape) != (B,):
+            raise QtError(f"{what}: lengths must be an int32 tensor [{B}] on {self.device}")
+        return lengths.detach().contiguous()
+
+    def decode(self, probs, lengths=None, start=False, score=False):
+        """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on the decoder's device, whole videos;
+        lengths: int32 [streams] on the device, or None when every video has `frames` frames (a value outside 1 .. frames is
+        clamped into it).  Returns (path int64, path_class int64), each [streams, frames] (or [frames]): the step per frame and
+        the class it emits, -1 for both beyond a video's end; with start=True the first frame of the segment a frame lies in,
+        int64 of the same shape, with score=True the best score int64 [streams] as the last."""
+        what = "PoseDurationDecoder.decode"
+        probs, flat, T, C = self._check_probs(what, probs)
+        B, S = self.streams, self.num_states
+        lengths = self._check_lengths(what, lengths, B)
+        lead = (T,) if flat else (B, T)
+        dev = self.device
+        path = torch.empty(lead, dtype=torch.int64, device=dev)
+        first = torch.empty(lead, dtype=torch.int64, device=dev) if start else None
+        best = torch.empty(B, dtype=torch.int64, device=dev) if score else None
+        desc = PoseDurationDesc(B, T, C, S, self.max_duration)
+        L = bind(_lib.lib())
+        ws, ws_bytes = self._room(L.qt_pose_duration_workspace_bytes, desc)
+        with torch.cuda.device(dev):
+            _lib.check(L.qt_pose_duration_decode(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
+                                                 _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.dur),
+                                                 _lib.ptr(self.dur_open), _lib.ptr(lengths), _lib.ptr(path), _lib.ptr(first),
+                                                 _lib.ptr(best), ws, ws_bytes, _lib.stream_ptr()), "qt_pose_duration_decode")
+        path_class = torch.where(path >= 0, self._state_class64[path.clamp_min(0)], path)
+        return (path, path_class) + tuple(t for t in (first, best) if t is not None)
+
+    def cycles(self, path, wrap_from=None, wrap_to=0):
+        """int64 [streams], on the device and without a host sync: how often `path` (a decode's, [streams, frames] or [frames])
+        goes from state wrap_from (default S - 1) to state wrap_to between adjacent frames; whole videos, so nothing is kept
+        between calls.  Plain torch."""
+        S, B = self.num_states, self.streams
+        wrap_from = S - 1 if wrap_from is None else wrap_from
+        for name, v in (("wrap_from", wrap_from), ("wrap_to", wrap_to)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < S:
+                raise ValueError(f"PoseDurationDecoder.cycles: {name} must be a state 0 .. {S - 1} (got {v!r})")
+        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
+            raise QtError(f"PoseDurationDecoder.cycles: path must be an int64 tensor on {self.device}")
+        if path.dim() == 1 and B == 1:
+            path = path.unsqueeze(0)
+        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < 1:
+            raise QtError(f"PoseDurationDecoder.cycles: path must be [{B}, frames] (got {list(path.shape)})")
+        return ((path[:, :-1] == wrap_from) & (path[:, 1:] == wrap_to)).sum(dim=1)
+
+    def count_durations(self, path, lengths=None):
+        """int64 [S, D] on the device: the run lengths of state paths, for `duration_prior`.  path: int64 [B, n] or [n] on the
+        decoder's device (any B): a decode's path, a PoseOrderDecoder's, or labelled steps; lengths: int32 [B] or None.  A run
+        longer than D counts in column D - 1, a video's first and last run are cut by the video and not counted, an entry
+        outside 0 .. S - 1 ends a run and counts nowhere.  Counts of further batches add up (integers)."""
+        what = "PoseDurationDecoder.count_durations"
+        S, D = self.num_states, self.max_duration
+        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
+            raise QtError(f"{what}: path must be an int64 tensor on {self.device}; there is no CPU or torch fallback")
+        if path.dim() == 1:
+            path = path.unsqueeze(0)
+        if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] < 1:
+            raise QtError(f"{what}: path must be [B, frames] or [frames] with B, frames >= 1 (got {list(path.shape)})")
+        B, T = path.shape
+        if B * T > MAX_FRAMES:
+            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+        lengths = self._check_lengths(what, lengths, B)
+        path = path.detach()
+        if path.stride(1) != 1 or (B > 1 and path.stride(0) < T):
+            path = path.contiguous()
+        out = torch.zeros(S, D, dtype=torch.int64, device=self.device)
+        desc = PoseDurationDesc(B, T, 1, S, D)
+        L = bind(_lib.lib())
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_duration_count(ctypes.byref(desc), _lib.ptr(path), path.stride(0) if B > 1 else T,
+                                                _lib.ptr(lengths), _lib.ptr(out), _lib.stream_ptr()), "qt_pose_duration_count")
+        return out
 
 
 def _check_tables(who, state_class, trans, init, streams, class_names):

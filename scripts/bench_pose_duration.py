@@ -1,0 +1,146 @@
+#!/usr/bin/env python
+"""What the pose-order decode with hold durations costs (developer aid, not a test; not part of bench.py).
+
+Whole videos of 9,000 frames (five minutes at 30 frames a second), timed with device events, the variants alternating inside
+every repeat, microseconds per call:
+
+  one        S = C = 12, D = 64, one stream
+  sixteen    S = C = 12, D = 64, sixteen streams, ragged lengths
+  wide       S = C = 64, D = 128, one stream (the limits)
+
+  duration      qt_pose_duration_decode alone, through ctypes into preallocated buffers (path, start, score)
+  decoder       PoseDurationDecoder.decode(start=True, score=True): the launch, the allocations of its outputs, the gather of
+                path_class, the Python
+  plain         qt_pose_order_decode on the same tracks with the same chain (path only), behind the carry.zero_() that makes
+                every call decode the same video; carry_zero is that alone, to subtract
+  copy          a device-to-device copy of the probabilities' bytes
+
+and per shape `us_per_frame` (the duration call over the frames of its longest stream: one workgroup walks each stream's
+frames in order, the streams side by side) and `over_plain` (the duration call over the plain call less carry_zero).  Before
+timing, the device results are compared byte for byte with the loops of tests/_pose_duration_ref.py and tests/
+_pose_order_ref.py on the same data (a minute of numpy at these sizes; --no-check skips it).
+
+    python scripts/bench_pose_duration.py --out profiles/pose_duration.json
+
+Prints one JSON line.  No threshold rests on it."""
+import argparse
+import ctypes
+import importlib
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+PKG = "multimodal-hierarchical-cnn-for-sun-salutation-pose-classification_amd"
+SHAPES = (("one", 1, 12, 64), ("sixteen", 16, 12, 64), ("wide", 1, 64, 128))      # name, streams, S = C, D
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=9000)
+    ap.add_argument("--iters", type=int, default=10, help="calls per timed window")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--shapes", default="one,sixteen,wide")
+    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_pose_duration.py measures on the GPU; there is none")
+    import _pose_duration_ref as Q
+    import _pose_order_ref as R
+    P = importlib.import_module(PKG)
+    M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
+    L = M.bind(Lm.lib())
+    dev = torch.device("cuda:0")
+
+    def timed(variants):
+        for fn in variants.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in variants}
+        for _ in range(args.repeats):
+            for name, fn in variants.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(args.iters):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[name].append(e0.elapsed_time(e1) / args.iters * 1e3)     # microseconds per call
+        return {k: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+                for k, v in times.items()}
+
+    T = args.frames
+    rec = {"device": torch.cuda.get_device_name(0), "frames": T, "iters": args.iters, "repeats": args.repeats, "shapes": {}}
+    for name, B, S, D in SHAPES:
+        if name not in args.shapes.split(","):
+            continue
+        C = S
+        sc, tr = M.cyclic_prior(range(S), stay=M.prob_score(0.9), advance=M.prob_score(0.1), skip=M.prob_score(0.01))
+        dur = M.hold_prior(S, D, 4, min(D, 48), inside=M.prob_score(0.05), outside=M.prob_score(0.0005))
+        dur_open = np.maximum.accumulate(dur[:, ::-1], axis=1)[:, ::-1].copy()
+        probs_np = R.make_probs(7, B, T, C)
+        lengths_np = None if B == 1 else np.maximum(T - 137 * np.arange(B), 1).astype(np.int32)
+        probs = torch.from_numpy(probs_np).to(dev)
+        t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_sc, d_tr, d_dur, d_open, d_len = t(sc), t(tr), t(dur), t(dur_open), t(lengths_np)
+        path = torch.empty(B, T, dtype=torch.int64, device=dev)
+        start = torch.empty(B, T, dtype=torch.int64, device=dev)
+        score = torch.empty(B, dtype=torch.int64, device=dev)
+        plain_path = torch.empty(B, T, dtype=torch.int64, device=dev)
+        carry = torch.zeros(B, S + 2, dtype=torch.int64, device=dev)
+        sink = torch.empty_like(probs)
+        desc = M.PoseDurationDesc(B, T, C, S, D)
+        need = int(L.qt_pose_duration_workspace_bytes(ctypes.byref(desc)))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        plain_desc = M.PoseOrderDesc(B, T, C, S)
+        plain_need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(plain_desc)))
+        plain_ws = torch.empty(max(plain_need, 8), dtype=torch.uint8, device=dev)
+
+        def duration():
+            Lm.check(L.qt_pose_duration_decode(ctypes.byref(desc), Lm.ptr(probs), C, Lm.ptr(d_sc), Lm.ptr(d_tr), None,
+                                               Lm.ptr(d_dur), Lm.ptr(d_open), Lm.ptr(d_len), Lm.ptr(path), Lm.ptr(start),
+                                               Lm.ptr(score), Lm.ptr(ws), need, Lm.stream_ptr()), "qt_pose_duration_decode")
+
+        def plain():
+            carry.zero_()
+            Lm.check(L.qt_pose_order_decode(ctypes.byref(plain_desc), Lm.ptr(probs), C, Lm.ptr(d_sc), Lm.ptr(d_tr), None,
+                                            Lm.ptr(carry), Lm.ptr(plain_path), None, None, Lm.ptr(plain_ws) if plain_need else None,
+                                            plain_need, Lm.stream_ptr()), "qt_pose_order_decode")
+
+        decoder = P.PoseDurationDecoder(sc, tr, dur, dev, streams=B)
+        duration(), plain()
+        got = decoder.decode(probs, lengths=d_len, start=True, score=True)
+        assert torch.equal(got[0], path) and torch.equal(got[2], start) and torch.equal(got[3], score)
+        if not args.no_check:
+            want = Q.decode(probs_np, sc, tr, dur, None, dur_open, lengths_np)
+            for g, w in zip((path, start, score), want):
+                assert R.bits(g.cpu().numpy()) == R.bits(w), f"{name}: the device result differs from the rule"
+            assert R.bits(plain_path.cpu().numpy()) == R.bits(R.decode(probs_np, sc, tr)[0]), f"{name}: plain"
+        us = timed({"duration": duration, "decoder": lambda: decoder.decode(probs, lengths=d_len, start=True, score=True),
+                    "plain": plain, "carry_zero": lambda: carry.zero_(), "copy": lambda: sink.copy_(probs)})
+        short = lambda p: int(sum(1 for row in p.cpu().numpy() for r in Q.runs_of(row[row >= 0])[1:-1] if r[1] < 4))
+        rec["shapes"][name] = {"streams": B, "states": S, "max_duration": D, "workspace_bytes": need,
+                               "plain_workspace_bytes": plain_need, "us_per_call": us,
+                               "us_per_frame": round(us["duration"]["median"] / T, 4),
+                               "over_plain": round(us["duration"]["median"] / (us["plain"]["median"] - us["carry_zero"]["median"]), 1),
+                               "interior_runs_shorter_than_4": {"duration": short(path), "plain": short(plain_path)}}
+        del decoder, probs, sink, ws, plain_ws
+    line = json.dumps(rec)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
