@@ -19,7 +19,10 @@ of the clip models.  Rows with a field `walk` = n are shapes at which a persiste
 at least n work items (item, item + grid, ...): the state that survives from one item to the next -- the LDS ring of frame
 slabs, the register prefetch of the next item's first slab or tile, the per-workgroup statistics rows and partial filters --
 is then part of the result.  The GPU test asserts that precondition from the grid the library reports; walk_items() is the
-same walk on the host for the CPU twin."""
+same walk on the host for the CPU twin.  The stem and layer-1 ring kernels split their tiles into CONTIGUOUS shares instead
+(share_items(), share_facts(); the rows stem_walk, stem_pool_walk, stem_wgrad_walk, ring_walk): what their state holds from
+tile to tile -- two input buffers, a sliding window of 640 rows with a 48-row mirror, the conv tile of the fused pool --
+depends on a tile's place in its workgroup's share and in its image, and WALKS records what each row reaches."""
 
 import torch
 import torch.nn.functional as F
@@ -124,7 +127,7 @@ def channel_sums(ref):
 # ----------------------------------------------------------------------------------------------------------------------
 def _mags(row):
     if row["mode"] == "A":
-        return 1, 1.0, 1
+        return 1, row.get("xkeep", 1.0), 1
     return row.get("xmag", 8), row.get("xkeep", 0.5), 8
 
 
@@ -273,6 +276,11 @@ FWD_ROWS = [
     _r("ring_b1", (1, 64, 64, 56, 3, 1, 1), (BF,), "A", 1 / 8, 110, path="ring"),
     _r("ring_b3_ragged", (3, 64, 64, 56, 3, 1, 1), (BF,), "A", 1 / 8, 111, path="ring"),
     _r("ring_rounded", (1, 64, 64, 56, 3, 1, 1), (BF,), "B", 1.0, 112, path="ring", xmag=16, zero_block=(20, 30), **B_KW),
+    # 80 images: 1052 tiles of 256 padded positions in contiguous shares of 4-5 on the ring kernel's 256 workgroups: the
+    # 640-row window wraps twice (window indices 640 and 1280), the mirror is refreshed, all five phases (256 k) mod 640 run
+    _r("ring_walk", (80, 64, 64, 56, 3, 1, 1), (BF,), "A", 1 / 16, 121, path="ring", walk=4),
+    _r("ring_walk_rounded", (80, 64, 64, 56, 3, 1, 1), (BF,), "B", 1.0, 122, path="ring", xmag=16, zero_block=(20, 30), walk=4,
+       **B_KW),
     _r("pt_28", (16, 128, 128, 28, 3, 1, 1), BOTH, "A", 1 / 8, 113, path="pt"),
     _r("pt_14_bn256", (16, 128, 256, 14, 3, 1, 1), BOTH, "A", 1 / 8, 114, path="pt"),
     _r("pt_7_ragged", (18, 128, 128, 7, 3, 1, 1), BOTH, "A", 1 / 8, 115, path="pt"),
@@ -294,6 +302,14 @@ S2_ROWS = [
 STEM_ROWS = [
     _r("stem_b1", (1, 3, 64, 224, 7, 2, 3), (BF,), "A", 1 / 2, 301),
     _r("stem_b1_rounded", (1, 3, 64, 224, 7, 2, 3), (BF,), "B", 1.0, 302, xmag=16, xkeep=1.0, zero_block=(60, 100)),
+    # contiguous tile shares (STEM_WALKS, share_facts): the smallest batches at which a workgroup of conv_stem_kernel (39) /
+    # of the fused stem (21) takes three tiles, reuses its first input buffer, and meets the first and the last tile of an
+    # image as its second and as its third tile.  `only`: the kernels the batch was chosen for.  stem_walk thins the image
+    # to 1/2: the forced weight entries alone would put a channel's sum of squares over 2^24 at 39 images
+    _r("stem_walk", (39, 3, 64, 224, 7, 2, 3), (BF,), "A", 1 / 8, 303, xkeep=1 / 2, only=("conv",), walk=2),
+    _r("stem_pool_walk", (21, 3, 64, 224, 7, 2, 3), (BF,), "A", 1 / 4, 304, only=("pool",), walk=2),
+    _r("stem_pool_walk_rounded", (21, 3, 64, 224, 7, 2, 3), (BF,), "B", 1.0, 305, xmag=16, xkeep=1.0, zero_block=(60, 100),
+       only=("pool",), walk=2),
 ]
 
 DGRAD_ROWS = [
@@ -301,6 +317,7 @@ DGRAD_ROWS = [
     _r("generic_3x3_s2", (1, 64, 128, 28, 3, 2, 1), BOTH, "A", 1 / 4, 402, path="generic"),
     _r("generic_rounded", (2, 128, 128, 14, 3, 1, 1), (BF,), "B", 1.0, 403, path="generic", **B_KW),
     _r("ring", (1, 64, 64, 56, 3, 1, 1), (BF,), "A", 1 / 8, 404, path="ring"),
+    _r("ring_walk", (80, 64, 64, 56, 3, 1, 1), (BF,), "A", 1 / 16, 408, path="ring", walk=4),   # see FWD_ROWS
     _r("pt_28", (16, 128, 128, 28, 3, 1, 1), BOTH, "A", 1 / 8, 405, path="pt"),
     _r("pt_7_ragged", (18, 128, 128, 7, 3, 1, 1), BOTH, "A", 1 / 8, 406, path="pt"),
     _r("pt_14_rounded", (16, 128, 256, 14, 3, 1, 1), (BF,), "B", 1.0, 407, path="pt", **B_KW),
@@ -362,7 +379,12 @@ STEMD_ROWS = [
     # 11 images: 539 tiles (bf16) / 1078 tiles (f32) on the persistent grid of 256: 2-3 and 4-5 tiles per workgroup
     _r("stem_dgrad_walk", (11, 3, 64, 224, 7, 2, 3), BOTH, "A", 1 / 8, 903, walk=2),
 ]
-STEMW_ROWS = [_r("stem_wgrad", (1, 3, 64, 224, 7, 2, 3), BOTH, "A", None, 902, keep=0.1)]
+STEMW_ROWS = [
+    _r("stem_wgrad", (1, 3, 64, 224, 7, 2, 3), BOTH, "A", None, 902, keep=0.1),
+    # 11 images: 616 two-row tiles in contiguous shares of 2-3 on the 256 workgroups of stem_wgrad_rows_kernel (bf16); dy is
+    # thin enough for exact zeros among 9408 sums over 138 k positions, and every tile still holds a non-zero dy
+    _r("stem_wgrad_walk", (11, 3, 64, 224, 7, 2, 3), BOTH, "A", None, 904, keep=0.003, walk=2),
+]
 
 # 3-D convolutions of the clip models (bf16 kernels): cfg = (B, T, H, W); `only`: the parts of the row a shape admits
 C3F_ROWS = [   # qt_conv3d_first_*: 3 -> 32 channels from the f32 clip
@@ -487,6 +509,75 @@ def walk_items(items, cap):
     grid = min(items, cap)
     i = torch.arange(items)
     return grid, i % grid, i // grid
+
+
+def share_items(items, cap):
+    """the other walk: grid = min(items, cap) workgroups, workgroup b takes the CONTIGUOUS share b * items / grid ..
+    (b + 1) * items / grid - 1 (conv_stem.hip, stem_wgrad_rows_kernel, conv_l1_ring_kernel).  Returns (grid, workgroup of
+    every item, trip of every item: 0 for the first item of its workgroup's share, 1 for the second, ...)"""
+    grid = min(items, cap)
+    beg = torch.arange(grid + 1) * items // grid
+    i = torch.arange(items)
+    wg = torch.bucketize(i, beg[1:], right=True)
+    return grid, wg, i - beg[wg]
+
+
+def share_facts(items, cap, per_image=0):
+    """what a contiguous-share walk reaches.  least / most: items per workgroup, with_most: workgroups that take `most`.
+    per_image = n (items are image * n + k): crossing = workgroups whose share goes on behind the last item of an image;
+    first_as[t] / last_as[t] = workgroups that take the first (k = 0) / last (k = n - 1) item of an image on trip t"""
+    grid, wg, trip = share_items(items, cap)
+    n = torch.bincount(wg, minlength=grid)
+    f = dict(items=items, grid=grid, least=int(n.min()), most=int(n.max()), with_most=int((n == n.max()).sum()))
+    if per_image:
+        k = torch.arange(items) % per_image
+        f["crossing"] = int(((k == per_image - 1) & (trip < n[wg] - 1)).sum())
+        f["first_as"] = {t: int(((k == 0) & (trip == t)).sum()) for t in (1, 2)}
+        f["last_as"] = {t: int(((k == per_image - 1) & (trip == t)).sum()) for t in (1, 2)}
+    return f
+
+
+def stem_walk_reaches(f):
+    """the state the stem walk rows are there for: a workgroup with three tiles (its first input buffer is reused), a share
+    that crosses an image boundary, the first tile of an image (k = 0: rows skipped, a shorter fetch, no conv row -1) as a
+    workgroup's second and as its third tile, the last tile of an image as its third"""
+    return f["least"] >= 2 and f["most"] >= 3 and f["crossing"] > 0 and min(f["first_as"].values()) > 0 and f["last_as"][2] > 0
+
+
+# (items per image, grid cap) of the kernels behind the walk rows, and the facts of their walks -- computed from the split
+# above, asserted by tests/test_exact_data_cpu.py; the GPU test asserts what it needs of them again before it reads a result
+WALKS = {
+    "stem_walk": (28, 512, dict(items=1092, grid=512, least=2, most=3, with_most=68, crossing=20, first_as={1: 18, 2: 2},
+                                last_as={1: 18, 2: 3})),
+    "stem_pool_walk": (28, 256, dict(items=588, grid=256, least=2, most=3, with_most=76, crossing=11, first_as={1: 9, 2: 2},
+                                     last_as={1: 9, 2: 3})),
+    "stem_wgrad_walk": (56, 256, dict(items=616, grid=256, least=2, most=3, with_most=104)),
+    "ring_walk": (0, 256, dict(items=1052, grid=256, least=4, most=5, with_most=28)),
+}
+WALKS["stem_pool_walk_rounded"], WALKS["ring_walk_rounded"] = WALKS["stem_pool_walk"], WALKS["ring_walk"]
+
+
+def ring_tiles(B, H):
+    """256-position tiles of the padded grid [B][H + 2][H + 2] the layer-1 ring kernel walks"""
+    return -(-(B * (H + 2) * (H + 2)) // 256)
+
+
+def locate(row, index):
+    """where output element (n, c, h, w) of a walk row lies in the walk, for a failure message: its tile, the workgroup that
+    takes it, the trip of that workgroup (0 = first tile of its share) and, for the stem, the tile's place k in its image.
+    stem_walk: 4 conv rows per tile; the fused stem: 2 pooled rows per tile; ring: 256 positions of the padded grid"""
+    per, cap, _ = WALKS[row["name"]]
+    n, _, h, w = index
+    B, H = row["cfg"][0], row["cfg"][3]
+    if per == 0:
+        items, tile = ring_tiles(B, H), (n * (H + 2) * (H + 2) + (h + 1) * (H + 2) + (w + 1)) // 256
+    else:
+        items, tile = per * B, n * per + h // (4 if "conv" in row["only"] else 2)
+    grid, wg, trip = share_items(items, cap)
+    where = dict(tile=tile, workgroup=int(wg[tile]), trip=int(trip[tile]))
+    if per:
+        where["k"] = tile % per
+    return where
 
 
 def ids(rows):

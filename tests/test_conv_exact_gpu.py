@@ -4,10 +4,13 @@ are the ones tests/test_exact_data_cpu.py checks without a GPU.  The kernels are
 test files; the path a row names is confirmed the way those files do it (qt_conv2d_stats_rows mirrors the dispatch, the
 workspace size tells the streaming weight-gradient kernels, qt_set_* switches force a path).  Rows with a field `walk` are
 there for the second and later work items of a persistent kernel's workgroups: that every workgroup takes that many items is
-asserted from the grid the library reports before a result is looked at (a failure, never a skip).
+asserted from the grid the library reports before a result is looked at (a failure, never a skip).  The stem and layer-1
+ring kernels walk contiguous shares of their tiles: their walk rows assert what E.WALKS records of the share table (a third
+tile, first and last tiles of an image on later trips, four tiles and two window wraps on the ring), from the reported grid
+or, for the fused stem and the stem weight gradient, which have no query, from the launch code's min(tiles, 256).
 
-The BatchNorm-backward link sums of the stride-1 data gradients stay with tests/test_conv_pt_gpu.py; the merged stride-2
-forms get a dyadic xhat here and are compared exactly."""
+The BatchNorm-backward link sums of the patch-resident stride-1 data gradients stay with tests/test_conv_pt_gpu.py; the
+ring kernel's and the merged stride-2 forms' get a dyadic xhat here and are compared exactly."""
 import ctypes
 
 import pytest
@@ -16,6 +19,7 @@ import torch
 import _exact as E
 from _exact import BF, F32
 from _guard import Guard
+from _stem_bounds import tile_ranges
 from _util import pkg
 from test_conv_gpu import PackItem, nhwc, run_conv, run_wgrad
 from test_conv_pt_gpu import _maxwg, _pt, tiles
@@ -32,10 +36,14 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _same(got, ref, dt, what):
-    """torch.equal against the reference in the output type; the message names the first differing element"""
+def _same(got, ref, dt, what, walk=None):
+    """torch.equal against the reference in the output type; the message names the first differing element and, for a map
+    [N][C][H][W] of the walk row `walk`, the tile, workgroup and trip it belongs to (E.locate)"""
     got = got.cpu()
-    assert E.same(got, ref, dt), (what, "first mismatch (index, got, want, count):", E.first_mismatch(got, ref, dt))
+    if not E.same(got, ref, dt):
+        bad = E.first_mismatch(got, ref, dt)
+        where = E.locate(walk, bad[0]) if walk and walk.get("walk") and walk["name"] in E.WALKS else None
+        assert False, (what, "first mismatch (index, got, want, count):", bad, where)
 
 
 def _nchw(y, n, h, w, c):
@@ -73,8 +81,14 @@ def _check_path(L, row, d, B, H, M):
     if row["path"] == "generic":
         assert off == -(-M // (256 if row.get("tile256") else 128)), (off, M)
         assert on == off or row.get("pt_off"), (on, off)
-    elif row["path"] == "ring":   # one row per workgroup of the persistent kernel: a 256-position tile of the padded grid each
-        assert on == min(-(-(B * (H + 2) * (H + 2)) // 256), 256) and on != off and off == -(-M // 128), (on, off)
+    elif row["path"] == "ring":
+        # one row per workgroup of the persistent kernel: min(tiles, 256) workgroups take contiguous shares of the 256-position
+        # tiles of the padded grid.  A `walk` row is there for a share's third and later tiles (the window wraps with the third)
+        assert on == min(E.ring_tiles(B, H), 256) and on != off and off == -(-M // 128), (on, off)
+        if row.get("walk"):
+            _walk_precondition(row, E.ring_tiles(B, H), on)
+            f = E.share_facts(E.ring_tiles(B, H), on)
+            assert f["least"] >= row["walk"] >= 3 and f["most"] > f["least"], f
     else:
         assert row["path"] == "pt" and on == 2 * (B if row.get("quad") else tiles(B, H)) and on != off, (on, off)
         assert off == -(-M // 128)
@@ -141,8 +155,8 @@ def test_forward_is_bit_exact(row, dt):
                              want_stats=True, strides=strides, m_rows=mr)
             ya, _ = run_conv(L, dt, xd, wd, B, (H, H), (Ho, Ho), Cin, Cout, k, k, s, p, L.QT_CONV_FWD, quad=quad, relu=1,
                              scale=sc, shift=sh, residual=resd, strides=strides, m_rows=mr)
-        _same(_nchw(y, n_img, Ho, Ho, Cout), c["raw"], dt, "raw output")
-        _same(_nchw(ya, n_img, Ho, Ho, Cout), c["act"], dt, "scale / shift / residual / ReLU epilogue")
+        _same(_nchw(y, n_img, Ho, Ho, Cout), c["raw"], dt, "raw output", row)
+        _same(_nchw(ya, n_img, Ho, Ho, Cout), c["act"], dt, "scale / shift / residual / ReLU epilogue", row)
         if mode == "A":
             assert E.stats_equal(st, c["raw"]), "statistics rows"
 
@@ -207,6 +221,50 @@ def test_stride2_pair_is_bit_exact(row, dt):
         assert E.stats_equal(st, c["raw"]) and E.stats_equal(std, c["rawd"])
 
 
+def _stem_walk_precondition(row, B, grid):
+    """the stem walk rows are there for what E.stem_walk_reaches() names, on `grid` workgroups (the count the library
+    reports, or the launch code's where there is no query).  A failure, not a skip"""
+    per, cap, want = E.WALKS[row["name"]]
+    assert grid == min(per * B, cap), (row["name"], "workgroups", grid, "expected", min(per * B, cap))
+    f = E.share_facts(per * B, grid, per)
+    assert f["items"] >= row["walk"] * grid + 1 and E.stem_walk_reaches(f), (row["name"], f)
+
+
+def _packed_stem_conv(L, row, c, imd, wd, sc, sh):
+    """qt_conv2d_igemm on the packed descriptor: conv_stem_kernel (qt_set_stem_conv(1)) raw + statistics and scale / shift /
+    ReLU, on a walk row its two other instantiations as well (raw alone; scale / shift / ReLU with the statistics, which
+    are those of the raw accumulators); the generic half-K-step tile behind the same descriptor (qt_set_stem_conv(0))"""
+    lib = L.lib()
+    dt, mode = BF, row["mode"]
+    rows = {}
+    try:
+        for on in (1, 0):
+            lib.qt_set_stem_conv(on)
+            y, st = _stem_conv(L, dt, imd, wd, 8, True)
+            rows[on] = st.shape[0]
+            if on and row.get("walk"):   # (the statistics rows of conv_stem_kernel are its workgroups)
+                _stem_walk_precondition(row, row["cfg"][0], rows[on])
+            _same(y.cpu().permute(0, 3, 1, 2), c["raw"], dt, ("raw + statistics", on), row)
+            if mode == "A":
+                assert E.stats_equal(st, c["raw"]), on
+            del y
+            ya, _ = _stem_conv(L, dt, imd, wd, 8, False, sc, sh, relu=1)
+            _same(ya.cpu().permute(0, 3, 1, 2), c["act"], dt, ("scale / shift / ReLU", on), row)
+            del ya
+            if on and row.get("walk"):
+                y, _ = _stem_conv(L, dt, imd, wd, 8, False)
+                _same(y.cpu().permute(0, 3, 1, 2), c["raw"], dt, "raw", row)
+                del y
+                ya, st = _stem_conv(L, dt, imd, wd, 8, True, sc, sh, relu=1)
+                assert st.shape[0] == rows[on]
+                _same(ya.cpu().permute(0, 3, 1, 2), c["act"], dt, "scale / shift / ReLU + statistics", row)
+                assert E.stats_equal(st, c["raw"]), "statistics beside scale / shift / ReLU"
+                del ya
+    finally:
+        lib.qt_set_stem_conv(-1)
+    assert rows[1] != rows[0]          # the dedicated kernel keeps its own row count: it was the path taken
+
+
 @pytest.mark.parametrize("row", E.STEM_ROWS, ids=E.ids(E.STEM_ROWS))
 def test_packed_stem_is_bit_exact(row):
     """conv_stem.hip (qt_set_stem_conv(1)) and the generic half-K-step tile behind the same packed descriptor
@@ -221,22 +279,17 @@ def test_packed_stem_is_bit_exact(row):
     E.conditions(c["raw"], c["araw"], dt, mode, w=c["w"], acts=[c["x"]], stats=(mode == "A"))
     E.conditions(c["pre"], c["apre"], dt, mode, zeros=False)
     B = row["cfg"][0]
+    only = row.get("only", ("conv", "pool"))
     imd, wd = c["x"].float().to(dev), c["w"].float().to(dev)
     sc, sh = c["scale"].float().to(dev), c["shift"].float().to(dev)
-    rows = {}
-    try:
-        for on in (1, 0):
-            lib.qt_set_stem_conv(on)
-            y, st = _stem_conv(L, dt, imd, wd, 8, True)
-            ya, _ = _stem_conv(L, dt, imd, wd, 8, False, sc, sh, relu=1)
-            rows[on] = st.shape[0]
-            _same(y.cpu().permute(0, 3, 1, 2), c["raw"], dt, ("raw", on))
-            _same(ya.cpu().permute(0, 3, 1, 2), c["act"], dt, ("scale / shift / ReLU", on))
-            if mode == "A":
-                assert E.stats_equal(st, c["raw"]), on
-    finally:
-        lib.qt_set_stem_conv(-1)
-    assert rows[1] != rows[0]          # the dedicated kernel keeps its own row count: it was the path taken
+    if "conv" in only:
+        _packed_stem_conv(L, row, c, imd, wd, sc, sh)
+    if "pool" not in only:
+        return
+    if row.get("walk"):
+        # qt_stem_conv_pool and qt_stem_conv_pool_nchw have no query: both launch min(28 B, 256) workgroups on contiguous
+        # shares of the B * 28 tiles (two pooled rows each) -- conv_stem.hip
+        _stem_walk_precondition(row, B, 256)
     st_ = L.stream_ptr()
     gd = Guard(dev)
     imd, wd, sc, sh = gd.input("image", imd), gd.input("w", wd), gd.input("scale", sc), gd.input("shift", sh)
@@ -250,7 +303,7 @@ def test_packed_stem_is_bit_exact(row):
         src = xpad if name == "qt_stem_conv_pool" else imd
         L.check(getattr(lib, name)(qdt, L.ptr(src), L.ptr(wp), 8, L.ptr(sc), L.ptr(sh), L.ptr(pooled), B, st_), name)
         gd.check()
-        _same(pooled.cpu().permute(0, 3, 1, 2), c["pooled"], dt, name)
+        _same(pooled.cpu().permute(0, 3, 1, 2), c["pooled"], dt, name, row)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -288,9 +341,41 @@ def test_data_gradient_is_bit_exact(row, dt):
             io.relu_mask_bits = g_bits.data_ptr()
             L.check(L.lib().qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm (mask bits)")
             gd.check()
-        _same(_nchw(y0, B, H, H, Cin), c["dx"], dt, "plain")
-        _same(_nchw(y1, B, H, H, Cin), c["out"], dt, "residual + mask")
-        _same(_nchw(y2, B, H, H, Cin), c["out"], dt, "residual + packed mask bits")
+        _same(_nchw(y0, B, H, H, Cin), c["dx"], dt, "plain", row)
+        _same(_nchw(y1, B, H, H, Cin), c["out"], dt, "residual + mask", row)
+        _same(_nchw(y2, B, H, H, Cin), c["out"], dt, "residual + packed mask bits", row)
+    if row["path"] == "ring":
+        _ring_links(L, dev, row, dt, c, d, dyd, wt, od, ad)
+
+
+def _ring_links(L, dev, row, dt, c, d, dyd, wt, od, ad):
+    """the BatchNorm-backward link sums of the ring kernel (sum g, sum g * xhat of the value it writes): ONE partial row per
+    workgroup, accumulated in registers over every tile of its share.  One link on the plain gradient, two links behind
+    residual + ReLU mask; dyadic xhat, so that every sum is exact"""
+    B, Cin, _, H = row["cfg"][:4]
+    rows = L.lib().qt_conv2d_stats_rows(ctypes.byref(d))
+    links = [_dyadic_links(c, Cin, row["seed"] + 9000 + j) for j in range(2)]
+    gd = Guard(dev)
+    g_dy, g_w, g_res, g_msk = gd.input("dy", dyd), gd.input("w", wt), gd.input("residual", od), gd.input("relu_mask", ad)
+    dev_links = [(gd.input(f"bn{j}_y", nhwc(ybn).to(dt).view(-1, Cin)), gd.input(f"bn{j}_mean", mean.float()),
+                  gd.input(f"bn{j}_invstd", invstd.float())) for j, (ybn, mean, invstd, _) in enumerate(links)]
+    for with_ops in (False, True):
+        n = 2 if with_ops else 1
+        parts = [gd.output(f"bn{j}_partial{n}", (rows, 2, Cin), torch.float32) for j in range(n)]
+        out = gd.output(f"dx{n}", (B * H * H, Cin), dt)
+        io = L.ConvIO(L.ptr(g_dy), L.ptr(g_w), L.ptr(out), None, None, L.ptr(g_res) if with_ops else None,
+                      L.ptr(g_msk) if with_ops else None, None)
+        io.bn0_y, io.bn0_mean, io.bn0_invstd = (t.data_ptr() for t in dev_links[0])
+        io.bn0_partial = parts[0].data_ptr()
+        if n == 2:
+            io.bn1_y, io.bn1_mean, io.bn1_invstd = (t.data_ptr() for t in dev_links[1])
+            io.bn1_partial = parts[1].data_ptr()
+        L.check(L.lib().qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()), "qt_conv2d_igemm (links)")
+        gd.check()
+        ref = c["out"] if with_ops else c["dx"]
+        _same(_nchw(out, B, H, H, Cin), ref, dt, ("links", n), row)
+        for j in range(n):
+            assert _links_equal(parts[j], ref, links[j][3]), ("BatchNorm-backward link sums", n, j)
 
 
 S2D, S2D_IDS = E.expand(E.S2D_ROWS)
@@ -563,6 +648,14 @@ def test_stem_weight_gradient_is_bit_exact(row, dt):
     c = E.wgrad_data(row)
     E.wgrad_conditions(c)
     B = row["cfg"][0]
+    if row.get("walk"):
+        # stem_wgrad_rows_kernel<false> (bf16) has no query: min(56 B, 256) workgroups on contiguous shares of the B * 56
+        # two-row tiles, the split tests/_stem_bounds.py restates; a partial filter per workgroup, summed over its share
+        shares = tile_ranges(B)
+        per, cap, want = E.WALKS[row["name"]]
+        assert len(shares) == min(per * B, cap) and min(e - b for b, e in shares) >= row["walk"], (B, len(shares))
+        assert any(e - b >= 3 for b, e in shares) and per * B >= row["walk"] * len(shares) + 1
+        assert bool((c["dy"].view(B, 64, 56, 2, 112) != 0).any(4).any(3).any(1).all()), "a two-row tile without a gradient"
     qdt, st = L.qt_dtype(dt), L.stream_ptr()
     gd = Guard(dev)
     imd = gd.input("image", c["x"].float())

@@ -183,12 +183,13 @@ def test_patch_kernel_matches_generic_path(dt):
     lib = L.lib()
     lib.qt_set_patch_conv(1)
     try:
-        # (26, 64, 64, 56): 342 tiles > 256 workgroups, so the persistent ring kernel (bf16) walks
-        # several tiles per workgroup and its sliding window wraps
-        for cfg in [(2, 64, 64, 56, 3, 1, 1), (26, 64, 64, 56, 3, 1, 1), (3, 128, 128, 28, 3, 1, 1),
+        # (26, 64, 64, 56): 342 tiles > 256 workgroups, so the persistent ring kernel (bf16) walks one or two tiles per
+        # workgroup: two at the most, its 640-row sliding window does not wrap.  (80, 64, 64, 56): 1052 tiles, four or five
+        # per workgroup; the window wraps with a workgroup's third tile and again with its fifth
+        for cfg in [(2, 64, 64, 56, 3, 1, 1), (26, 64, 64, 56, 3, 1, 1), (80, 64, 64, 56, 3, 1, 1), (3, 128, 128, 28, 3, 1, 1),
                     (1, 64, 128, 56, 3, 1, 1), (5, 128, 64, 28, 3, 1, 1)]:
             test_conv_fwd_epilogue(dt, cfg)
-        for cfg in [(2, 64, 64, 56, 3, 1, 1), (26, 64, 64, 56, 3, 1, 1), (3, 128, 128, 28, 3, 1, 1)]:
+        for cfg in [(2, 64, 64, 56, 3, 1, 1), (26, 64, 64, 56, 3, 1, 1), (80, 64, 64, 56, 3, 1, 1), (3, 128, 128, 28, 3, 1, 1)]:
             test_conv_dgrad(dt, cfg)
     finally:
         lib.qt_set_patch_conv(2)

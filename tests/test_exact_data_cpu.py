@@ -365,6 +365,196 @@ def test_a_stale_tile_prefetch_and_a_skipped_round_of_the_stem_data_gradient_are
             _caught(E.same(_walked_stem_dgrad(dy, w, ty, g, fault), c["dx"], F32), walking, fault)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# damage to the walk of the stem and layer-1 ring kernels: a capped grid of CONTIGUOUS shares (E.share_items)
+# ----------------------------------------------------------------------------------------------------------------------
+def test_the_walk_rows_reach_what_they_are_there_for():
+    """the recorded facts are those of the split, and 39 / 21 are the smallest batches at which conv_stem_kernel (512
+    workgroups) / the fused stem (256) reach all of E.stem_walk_reaches()"""
+    rows = {r["name"]: r for r in E.FWD_ROWS + E.STEM_ROWS + E.STEMW_ROWS}
+    for name, (per, cap, want) in E.WALKS.items():
+        B, H = rows[name]["cfg"][0], rows[name]["cfg"][3]
+        items = per * B if per else E.ring_tiles(B, H)
+        f = E.share_facts(items, cap, per)
+        assert {k: f[k] for k in want} == want, (name, f)
+        assert f["least"] >= rows[name]["walk"] and items >= rows[name]["walk"] * f["grid"] + 1
+    for cap, smallest in ((512, 39), (256, 21)):
+        assert [B for B in range(1, smallest + 1) if E.stem_walk_reaches(E.share_facts(28 * B, cap, 28))] == [smallest]
+    # the ring kernel's window: a share of n tiles reads window indices up to 256 n - 1 + 2 * 58 + 2.  Two tiles stay inside
+    # the 640 rows; the fifth tile of a share reads past 1280, the second wrap
+    last_index = lambda n: 256 * n - 1 + 2 * 58 + 2
+    assert last_index(2) == 629 < 640 <= last_index(3) and last_index(E.WALKS["ring_walk"][2]["most"]) >= 1280
+
+
+def _share(items, cap):
+    grid, wg, trip = E.share_items(items, cap)
+    return grid, wg, trip, torch.bincount(wg, minlength=grid)[wg]      # (.. and the length of the share an item lies in)
+
+
+def _stem_slabs(x, top, rows, step):
+    """[B][3][224][224] -> per tile the `rows` packed input rows from packed row step * k - top on: [B * 28 or 56][3][rows][230]"""
+    u = F.pad(x, (3, 3, 3 + top, 3)).unfold(2, rows, step)               # [B][3][tiles][230][rows]
+    return u.permute(0, 2, 1, 4, 3).reshape(-1, 3, rows, 230)
+
+
+def _stale(slabs, trip):
+    """a workgroup's third tile is computed from the input rows of its first: the buffer was reused without a refill"""
+    i = torch.arange(slabs.shape[0])
+    return slabs[torch.where(trip == 2, i - 2, i)]
+
+
+def _walked_stem_conv(x, w, cap, fault=None):
+    """conv1 the way conv_stem_kernel walks it: tile = (image, 4 output rows) from 13 packed rows, contiguous shares on
+    min(tiles, cap) workgroups, one statistics row per workgroup.  Returns (y [B][64][112][112], rows [grid][2][64])"""
+    B = x.shape[0]
+    xi = _stem_slabs(x, 0, 13, 8)
+    grid, wg, trip, n = _share(xi.shape[0], cap)
+    if fault == "stale_input":
+        xi = _stale(xi, trip)
+    yi = F.conv2d(xi, w, None, 2)                                        # [tiles][64][4][112]
+    counted = trip == n - 1 if fault == "last_item_only" else torch.ones_like(trip, dtype=torch.bool)
+    per_item = torch.stack([yi.sum((2, 3)), (yi * yi).sum((2, 3))], 1) * counted.view(-1, 1, 1)
+    part = torch.zeros(grid, 2, 64).index_add_(0, wg, per_item)
+    return yi.view(B, 28, 64, 4, 112).permute(0, 2, 1, 3, 4).reshape(B, 64, 112, 112), part
+
+
+def _walked_stem_pool(x, w, scale, shift, cap, fault=None):
+    """the fused eval stem the way conv_stem_pool_kernel walks it: tile = (image, k), conv rows 4k - 1 .. 4k + 3 from 15 packed
+    rows as a bf16 ReLU tile of five rows, two pooled rows from it; conv row -1 of a first tile (k = 0) is not computed and
+    not read (0 never beats a ReLU output).  fault top_row_left: a first tile that is not its workgroup's first reads the row
+    the previous tile left in that place"""
+    B = x.shape[0]
+    xi = _stem_slabs(x, 2, 15, 8)
+    grid, wg, trip, n = _share(xi.shape[0], cap)
+    if fault == "stale_input":
+        xi = _stale(xi, trip)
+    raw = F.conv2d(xi, w, None, 2)                                       # [tiles][64][5][112]
+    tile = F.relu(raw * E.bcast(scale, raw) + E.bcast(shift, raw)).to(BF).float()
+    first = torch.arange(xi.shape[0]) % 28 == 0
+    top = torch.zeros_like(tile[:, :, 0])
+    if fault == "top_row_left":
+        later = first & (trip >= 1)
+        top[later] = tile[later.nonzero().flatten() - 1, :, 0]
+    tile[first, :, 0] = top[first]
+    pooled = F.max_pool2d(F.pad(tile, (1, 0)), 3, 2)                     # [tiles][64][2][56]
+    return pooled.view(B, 28, 64, 2, 56).permute(0, 2, 1, 3, 4).reshape(B, 64, 56, 56)
+
+
+@pytest.mark.parametrize("row", E.STEM_ROWS, ids=E.ids(E.STEM_ROWS))
+def test_a_stale_input_buffer_a_left_top_row_and_overwritten_statistics_of_the_stem_are_caught(row):
+    """Every fault fails the GPU test's comparisons on the walk rows and none does on the one-image rows, where a workgroup
+    has one tile: those rows could not see them"""
+    c = E.stem_data(row)
+    only = row.get("only", ("conv", "pool"))
+    walking = bool(row.get("walk"))
+    x, w, sc, sh = (c[n].float() for n in ("x", "w", "scale", "shift"))
+    if "conv" in only:
+        y, part = _walked_stem_conv(x, w, 512)
+        assert E.same(y.to(BF), c["raw"], BF)
+        assert row["mode"] == "B" or E.stats_equal(part, c["raw"])
+        y, _ = _walked_stem_conv(x, w, 512, "stale_input")
+        _caught(E.same(y.to(BF), c["raw"], BF), walking, "stale_input")
+        if row["mode"] == "A":
+            _, part = _walked_stem_conv(x, w, 512, "last_item_only")
+            _caught(E.stats_equal(part, c["raw"]), walking, "last_item_only")
+    if "pool" in only:
+        assert E.same(_walked_stem_pool(x, w, sc, sh, 256).to(BF), c["pooled"], BF)
+        for fault in ("stale_input", "top_row_left"):
+            _caught(E.same(_walked_stem_pool(x, w, sc, sh, 256, fault).to(BF), c["pooled"], BF), walking, fault)
+
+
+@pytest.mark.parametrize("row", E.STEMW_ROWS, ids=E.ids(E.STEMW_ROWS))
+def test_a_stale_input_buffer_and_an_overwritten_partial_filter_of_the_stem_weight_gradient_are_caught(row):
+    """stem_wgrad_rows_kernel: tile = (image, 2 rows of dy) with 9 packed input rows, contiguous shares on min(tiles, 256)
+    workgroups, a partial filter per workgroup summed over its share"""
+    c = E.wgrad_data(row)
+    B = row["cfg"][0]
+    walking = bool(row.get("walk"))
+    xi = _stem_slabs(c["x"].float(), 0, 9, 4)
+    dyi = c["dy"].float().view(B, 64, 56, 2, 112).permute(0, 2, 1, 3, 4).reshape(B * 56, 64, 2, 112)
+    grid, wg, trip, n = _share(B * 56, 256)
+    assert (n.min() >= 2 and n.max() >= 3) == walking
+    assert bool((dyi != 0).flatten(1).any(1).all())                      # every tile holds a non-zero dy
+    every = torch.ones_like(trip, dtype=torch.bool)
+    for fault, xs, counted in ((None, xi, every), ("stale_input", _stale(xi, trip), every), ("last_item_only", xi, trip == n - 1)):
+        dw = torch.nn.grad.conv2d_weight(xs[counted], (64, 3, 7, 7), dyi[counted], 2, 0)
+        if fault is None:
+            assert E.same(dw, c["dw"], F32)
+        else:
+            _caught(E.same(dw, c["dw"], F32), walking, fault)
+
+
+def _walked_ring(x, w, cap, fault=None):
+    """3x3 / pad 1 convolution of x [B][C][H][H] (f32) the way conv_l1_ring_kernel walks it: the padded grid [B][H + 2][H + 2]
+    as one sequence of positions, tiles of 256 of them in contiguous shares on min(tiles, cap) workgroups; a workgroup
+    reads position q + (kh - 1)(H + 2) + (kw - 1) at window index u = (q - first position of its share) + kh (H + 2) + kw,
+    kept in ring row u mod 640; a lane reads its four 16-row fragments of a tap at rr0, rr0 + 16, rr0 + 32, rr0 + 48 with
+    rr0 = (256 k + 64 wm + frow + shift) mod 640, so rows 640 .. 687 are a mirror of rows 0 .. 47.
+    Returns (y [B][O][H][H], statistics rows [grid][2][O]).  fault:
+      unfolded_row     window indices >= 640 are not folded: the data of the position 640 earlier is read
+      mirror_left      the mirror keeps the first window: a read through it gets window index u mod 640 of the share's start
+      last_item_only   the workgroup's statistics row holds its last tile alone"""
+    B, C, H, _ = x.shape
+    O = w.shape[0]
+    PW = H + 2
+    Q, M = B * PW * PW, PW + 1
+    tiles = E.ring_tiles(B, H)
+    grid, wg, trip, n = _share(tiles, cap)
+    src = torch.zeros(M + tiles * 256 + M, C)
+    src[M:M + Q] = F.pad(x, (1, 1, 1, 1)).permute(0, 2, 3, 1).reshape(Q, C)
+    i = torch.arange(256).view(1, -1)
+    q = torch.arange(tiles).view(-1, 1) * 256 + i
+    start = (torch.arange(tiles) - trip).view(-1, 1) * 256              # first position of the share a tile lies in
+    u0 = trip.view(-1, 1) * 256 + i
+    j16 = (i % 64) // 16 * 16
+    out = torch.zeros(tiles * 256, O)
+    for kh in range(3):
+        for kw in range(3):
+            shift = kh * PW + kw
+            u, pos = u0 + shift, q - M + shift
+            if fault == "unfolded_row":
+                pos = torch.where(u >= 640, pos - 640, pos)
+            if fault == "mirror_left":
+                through_mirror = (u0 - j16 + shift) % 640 + j16 >= 640
+                pos = torch.where(through_mirror, start - M + u % 640, pos)
+            out += src[(pos + M).flatten()] @ w[:, :, kh, kw].t()
+    qq = q.flatten()
+    hp, wp = qq % (PW * PW) // PW, qq % PW
+    live = (qq < Q) & (hp >= 1) & (hp <= H) & (wp >= 1) & (wp <= H)
+    counted = (trip == n - 1) if fault == "last_item_only" else torch.ones_like(trip, dtype=torch.bool)
+    lv = out * (live & counted.repeat_interleave(256)).view(-1, 1)
+    part = torch.zeros(grid, 2, O).index_add_(0, wg, torch.stack([lv.view(tiles, 256, O).sum(1), (lv * lv).view(tiles, 256, O).sum(1)], 1))
+    y = out[:Q].view(B, PW, PW, O)[:, 1:-1, 1:-1].permute(0, 3, 1, 2)
+    return y, part
+
+
+RING_FWD = [r for r in E.FWD_ROWS if r.get("path") == "ring" and r["name"] != "ring_walk_rounded"]
+RING_DG = [r for r in E.DGRAD_ROWS if r.get("path") == "ring"]
+RING = [("fwd", r) for r in RING_FWD] + [("dgrad", r) for r in RING_DG]
+
+
+@pytest.mark.parametrize("kind,row", RING, ids=[f"{k}-{r['name']}" for k, r in RING])
+def test_an_unfolded_ring_row_a_left_mirror_and_overwritten_statistics_of_the_ring_kernel_are_caught(kind, row):
+    """An unfolded row and a mirror that is not refreshed show only from a share's third tile on (window index 640): caught on
+    ring_walk (4-5 tiles per workgroup), invisible on every other ring row (two tiles at the most)"""
+    walking = bool(row.get("walk"))
+    B, H = row["cfg"][0], row["cfg"][3]
+    assert (E.share_facts(E.ring_tiles(B, H), 256)["least"] >= 3) == walking
+    if kind == "fwd":
+        c = E.fwd_data(row)
+        x, w, ref = c["x"].float(), c["w"].float(), c["raw"]
+    else:
+        c = E.dgrad_data(row)
+        x, w, ref = c["dy"].float(), c["w"].float().transpose(0, 1).flip(2, 3).contiguous(), c["dx"]   # conv2d_input as a conv
+    y, part = _walked_ring(x, w, 256)
+    assert E.same(y.to(BF), ref, BF)
+    for fault in ("unfolded_row", "mirror_left"):
+        _caught(E.same(_walked_ring(x, w, 256, fault)[0].to(BF), ref, BF), walking, fault)
+    if kind == "fwd" and row["mode"] == "A":
+        assert E.stats_equal(part, ref)
+        _caught(E.stats_equal(_walked_ring(x, w, 256, "last_item_only")[1], ref), walking, "last_item_only")
+
+
 ROUNDED = [_row(E.FWD_ROWS, "generic_3x3_rounded"), _row(E.FWD_ROWS, "ring_rounded"), _row(E.FWD_ROWS, "pt_14_rounded")]
 
 

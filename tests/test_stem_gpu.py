@@ -191,7 +191,7 @@ def _stem_conv(L, dt, image, w, taps, want_stats, scale=None, shift=None, relu=0
     return y, stats
 
 
-@pytest.mark.parametrize("B", [1, 3, 20])   # 28, 84, 560 tiles: fewer / more tiles than workgroups
+@pytest.mark.parametrize("B", [1, 3, 20, 39])   # 28, 84, 560, 1092 tiles on <= 512 workgroups: one, two, up to three each
 def test_stem_conv_dedicated_kernel(B):
     """csrc/conv_stem.hip (bf16) against F.conv2d and against the generic implicit GEMM."""
     dev = _dev()
@@ -225,7 +225,7 @@ def test_stem_conv_dedicated_kernel(B):
     assert rel_err(y_act.float().cpu().permute(0, 3, 1, 2), act) <= 4e-3
 
 
-@pytest.mark.parametrize("B", [1, 3, 11])   # 28 / 84 / 308 tiles: fewer and more tiles than workgroups
+@pytest.mark.parametrize("B", [1, 3, 11, 21])   # 28 / 84 / 308 / 588 tiles on <= 256 workgroups: one, two, up to three each
 def test_stem_conv_pool_fused_eval_kernel(B):
     """qt_stem_conv_pool (conv1 + folded BatchNorm + ReLU + MaxPool2d(3,2,1), eval forward) against torch on the CPU and
     against the two-kernel form (qt_conv2d_igemm with the affine epilogue + qt_stem_pool)."""
@@ -302,7 +302,7 @@ def test_stem_conv_pool_negative_zero_is_not_a_maximum():
     assert (pooled.view(torch.int16) >= 0).all()               # no sign bit in the result: +0, not -0
 
 
-@pytest.mark.parametrize("B", [1, 3, 9])   # 56 / 168 / 504 tiles: fewer and more tiles than workgroups
+@pytest.mark.parametrize("B", [1, 3, 9, 11])   # 56 / 168 / 504 / 616 tiles on <= 256 workgroups: one, two, up to three each
 def test_stem_weight_gradient_from_raw_rows(B):
     """conv1's weight gradient (conv2d backward-weight inside loss.backward(), /root/reference/Quadtree_from
     scratch/Quadtree_train.py:65, layer built at models.py:222-223) through qt_conv2d_wgrad on the packed stem descriptor
