@@ -59,6 +59,16 @@ const char* qt_last_error(void);
  * epilogue(v) = relu_mask( relu( v*scale[n] + shift[n] + residual[m][n] ) ),
  * each part optional; stats_partial (optional) receives per-128-row-tile sums and
  * sums of squares of the raw v per channel: [qt_conv2d_stats_rows][2][n_out] f32.
+ * Non-finite values (every forward entry point of this header, not only this one): dst
+ * holds NaN, +inf and -inf where IEEE arithmetic on the same operands gives them, in any
+ * order of summation; relu is the NaN-propagating maximum (relu(NaN) = NaN as torch.relu,
+ * relu(-0.0) = +0.0), never fmaxf.  The max pools (qt_stem_pool, qt_stem_conv_pool*,
+ * qt_quad_pool, qt_pool3d_max, qt_pool3d_bn_relu_max, qt_conv3d_first_fwd_pool) follow
+ * ATen: a NaN wins every comparison, so a window that holds one pools to NaN and its
+ * argmax is the LAST NaN in scan order.  The backward ReLU gates (relu_mask,
+ * relu_mask_bits as qt_bn_act_mask writes them, the gates the fused backward kernels
+ * recompute) are torch's threshold_backward: the gradient is dropped where act <= 0
+ * (+0.0 and -0.0 alike) and kept otherwise, at a NaN activation too.
  * ------------------------------------------------------------------------ */
 enum { QT_CONV_FWD = 0, QT_CONV_DGRAD = 1 };
 

@@ -78,7 +78,7 @@ __global__ void region_avgpool_bwd_kernel(const D* __restrict__ d, const T* __re
     load8<D>(d + (long long)b * ld + col0 + region_slot(r, S) * C + c0, dv);
     QtVec8<T>::load(x + i * 8, xv);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) dv[e] = xv[e] > 0.f ? dv[e] * inv : 0.f;
+    for (int e = 0; e < 8; ++e) dv[e] = qt_relu_gate(xv[e]) ? dv[e] * inv : 0.f;
     QtVec8<T>::store(g + i * 8, dv);
   }
 }
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(64) void attention_fwd_kernel(const float* __restri
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float r = fmaxf(a[j], 0.f);
+      const float r = qt_relu(a[j]);
       sa[(j0 + j) * (DH + 1) + h] = r;
       act[((long long)b * NV + j0 + j) * DH + h] = r;
     }
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(const T* __restrict__
 #pragma unroll
       for (int q = 0; q < NV; ++q) dj = (j0 + j) == q ? dsj[q] : dj;
       const long long idx = ((long long)b * NV + j0 + j) * DH + h;
-      const float p = act[idx] > 0.f ? dj * w : 0.f;
+      const float p = qt_relu_gate(act[idx]) ? dj * w : 0.f;
       sp[(j0 + j) * (DH + 1) + h] = p;
       dpre[idx] = p;
     }
@@ -225,7 +225,7 @@ __global__ void relu_mask_cols_kernel(const T* __restrict__ d, const T* __restri
        i += (long long)gridDim.x * blockDim.x) {
     const int c = (int)(i % cols);
     const long long r = i / cols, src = r * ld + col0 + c;
-    out[i] = qt_to_f32<T>(act[src]) > 0.f ? qt_to_f32<T>(d[src]) * mul : 0.f;
+    out[i] = qt_relu_gate(qt_to_f32<T>(act[src])) ? qt_to_f32<T>(d[src]) * mul : 0.f;
   }
 }
 

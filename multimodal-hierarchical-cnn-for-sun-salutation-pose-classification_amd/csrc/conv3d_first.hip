@@ -78,6 +78,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_first_kernel(C3Args p) {
                              e[6] | ((unsigned)e[7] << 16));
     }
 
+  // odd k-groups hold pixels 2 and 3 of a tap row's four; the fourth meets zero weights only and is read as zero, so that an
+  // inf or a NaN NEXT to the 3-pixel window cannot become a NaN of this output
+  const unsigned keep4 = (lg & 1) ? 0u : 0xffffffffu;
   float sc[8], sh[8], s1[8], s2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_first_kernel(C3Args p) {
               const unsigned char* q = a[s] - back + r * rowb + blk * 128;
               const uint2 lo = *reinterpret_cast<const uint2*>(q);
               const uint2 hi = *reinterpret_cast<const uint2*>(q + 8);
-              xf[s] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+              xf[s] = make_uint4(lo.x, lo.y, hi.x & keep4, hi.y & keep4);
             }
             acc[r][0] = acc[r][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -173,11 +176,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_first_kernel(C3Args p) {
           float v[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            const float v0 = fmaxf(acc[0][j >> 2][j & 3] * sc[j] + sh[j], 0.f);
-            const float v1 = fmaxf(acc[1][j >> 2][j & 3] * sc[j] + sh[j], 0.f);
-            const float m = fmaxf(v0, v1);
+            const float v0 = qt_relu(acc[0][j >> 2][j & 3] * sc[j] + sh[j]);
+            const float v1 = qt_relu(acc[1][j >> 2][j & 3] * sc[j] + sh[j]);
+            const float m = qt_max_nan(v0, v1);
             const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0xb1, 0xf, 0xf, false));
-            v[j] = (li & 1) ? 0.f : fmaxf(m, o);   // odd lanes write the zero half of their left neighbour's pooled row
+            v[j] = (li & 1) ? 0.f : qt_max_nan(m, o);   // odd lanes write the zero half of their left neighbour's pooled row
           }
           if (writes)
             *reinterpret_cast<uint4*>(orow + (size_t)blk * 8 * pc) =
@@ -193,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_first_kernel(C3Args p) {
         for (int s = 0; s < 5; ++s) {
           const uint2 lo = *reinterpret_cast<const uint2*>(a[s] + blk * 128);
           const uint2 hi = *reinterpret_cast<const uint2*>(a[s] + blk * 128 + 8);
-          xf[s] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+          xf[s] = make_uint4(lo.x, lo.y, hi.x & keep4, hi.y & keep4);
         }
         f32x4 acc[2];
         acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -214,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_first_kernel(C3Args p) {
           v[j] = acv;
           if (AFF) {
             v[j] = acv * sc[j] + sh[j];
-            if (p.relu) v[j] = fmaxf(v[j], 0.f);
+            if (p.relu) v[j] = qt_relu(v[j]);
           }
         }
         *reinterpret_cast<uint4*>(yrow + (size_t)blk * 16 * 32) =
@@ -406,7 +409,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_first_wgrad_kernel(C3WArgs p) {
         const float yf = __builtin_bit_cast(float, u ? (yw[q] & 0xffff0000u) : (yw[q] << 16));
         const float df = __builtin_bit_cast(float, u ? (dw[q] & 0xffff0000u) : (dw[q] << 16));
         const unsigned a = ((j < 4 ? av.x : av.y) >> (8 * (j & 3))) & 0xffu;
-        const float g = (a == me && yf * ksc[j] + ksh[j] > 0.f) ? df : 0.f;
+        const float g = (a == me && qt_relu_gate(yf * ksc[j] + ksh[j])) ? df : 0.f;
         r[u] = ka[j] * g + kb[j] - yf * kc[j];
       }
       o[q] = pack_bf16x2(r[0], r[1]);

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(512 / CPW) void conv3d_c32_kernel(S3Args p) {
               v[r] = a;
               if (AFF) {
                 v[r] = a * sc[cb][r] + sh[cb][r];
-                if (p.relu) v[r] = fmaxf(v[r], 0.f);
+                if (p.relu) v[r] = qt_relu(v[r]);
               }
             }
             if (OUT == 1) {

@@ -47,6 +47,10 @@ struct ConvArgs {
   // frame exists; ntaps = KT * KH * KW <= 32.  KT <= 1: plain 2-D.
   int KT, frames, imgs_per_frame;
   long long frame_stride;   // elements between consecutive frames of the source
+  // The packed stem (kw == 1, a tap row of 8 packed pixels = k_per_tap, stride 2): the 7-wide window uses 7 of the 8 pixels
+  // and 7 of kh == 8 tap rows; the rest lies under zero weights but holds REAL neighbouring pixels.  pad_pix: the generic
+  // tile reads the eighth pixel and the eighth tap row as zero, so that 0 * inf / 0 * NaN cannot reach the output.
+  int pad_pix;
 };
 
 }  // namespace qtc

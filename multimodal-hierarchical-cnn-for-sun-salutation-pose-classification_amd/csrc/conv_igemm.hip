@@ -32,7 +32,7 @@ constexpr bool kPrio = true;
 // NSTAGE == 1: single-buffered tiles (every fragment of a K-step is read into registers, a second
 // barrier, then the next K-step's DMA is issued under the MFMAs) + EH == 2: the f32 epilogue staging
 // holds half of the rows at a time -> 32 KB of LDS, three workgroups per CU.
-template <typename T, int BM, int BN, int WM, int WN, int NSTAGE, bool DGRAD, int EH = 1>
+template <typename T, int BM, int BN, int WM, int WN, int NSTAGE, bool DGRAD, int EH = 1, bool PADPIX = false>
 __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 3 : 1) void conv_igemm_kernel(ConvArgs p) {
   static_assert(EH == 1 || (EH == 2 && WM == 2), "the split epilogue takes one wave row per pass");
   constexpr int NT = 64 * WM * WN;   // threads
@@ -167,6 +167,7 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 3 : 1) void conv_igemm_
         mask = m3;
         f0 = (DGRAD ? pt : -pt) * p.frame_stride;
       }
+      if (PADPIX) mask &= 0x7fu;   // the packed stem's eighth tap row: zero weights over a real row
       if (p.dst_merge && p.ntaps == 5) mask |= (mask & 1u) << 4;   // the fifth slot reads the window's first pixel (of the second map)
       a_mask[i] = mask;
       const long long h0 = DGRAD ? (oh + p.pad) : (oh * p.stride - p.pad);
@@ -271,6 +272,21 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 3 : 1) void conv_igemm_
     for (int j = 0; j < TM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int frow = lane & 15, fk = lane >> 4;
+  // PADPIX (ConvArgs::pad_pix, an instantiation of its own: the packed stem only): the eighth pixel of a tap row, 4 elements,
+  // is read as zero.  bf16: a tap row is 64 bytes = chunks 4 kk .. 4 kk + 3, the pixel is the upper half of chunk 4 kk + 3;
+  // f32: a tap row is the whole 128-byte K-step, the pixel is chunk 7
+  const unsigned keep8 = fk == 3 ? 0u : 0xffffffffu;
+  auto pad_fix = [&](uint4& f, int kk) {
+    if (sizeof(T) == 2) {
+      f.z &= keep8;
+      f.w &= keep8;
+    } else if (kk == 1) {
+      f.x &= keep8;
+      f.y &= keep8;
+      f.z &= keep8;
+      f.w &= keep8;
+    }
+  };
 
   // NSTAGE-deep LDS ring.  Stage s lives in buffer s % NSTAGE; NSTAGE-1 stages are in
   // flight.  Per K-step: wait until this wave's DMAs of stage ks have landed (counted
@@ -300,6 +316,12 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 3 : 1) void conv_igemm_
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // every wave holds its fragments: the tiles are free
+      if constexpr (PADPIX) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int j = 0; j < TM; ++j) pad_fix(fa[kk][j], kk);
+      }
       if (ks + 1 < nk) dma_stage(ks + 1, 0);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
@@ -334,6 +356,10 @@ __global__ __launch_bounds__(64 * WM * WN, NSTAGE == 1 ? 3 : 1) void conv_igemm_
         for (int j = 0; j < TM; ++j) {
           const int r = wm * (BM / WM) + j * 16 + frow;
           fa[j] = *reinterpret_cast<const uint4*>(sa + r * kRowBytes + (((kk * 4 + fk) ^ (r & 7)) << 4));
+        }
+        if constexpr (PADPIX) {
+#pragma unroll
+          for (int j = 0; j < TM; ++j) pad_fix(fa[j], kk);
         }
         if (kPrio) __builtin_amdgcn_s_setprio(1);
   #pragma unroll
@@ -478,13 +504,13 @@ if (p.scale || p.shift) {  // (uniform)
       }
       if (p.relu) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+        for (int e = 0; e < 8; ++e) v[e] = qt_relu(v[e]);
       }
       if (msk) {
         float mv[8];
         operand(msk, raw_msk[u], off, mv);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = mv[e] > 0.f ? v[e] : 0.f;
+        for (int e = 0; e < 8; ++e) v[e] = qt_relu_gate(mv[e]) ? v[e] : 0.f;
       }
       if (mbits) qt_apply_mask_bits(PB > 1 ? raw_bits[u] : (unsigned)mbits[off >> 3], v);
       QtVec8<T>::store(dst + off, v);
@@ -547,13 +573,13 @@ if (p.scale || p.shift) {  // (uniform)
       }
       if (p.relu) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+        for (int e = 0; e < 8; ++e) v[e] = qt_relu(v[e]);
       }
       if (msk) {
         float mv[8];
         QtVec8<T>::load(msk + off, mv);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = mv[e] > 0.f ? v[e] : 0.f;
+        for (int e = 0; e < 8; ++e) v[e] = qt_relu_gate(mv[e]) ? v[e] : 0.f;
       }
       if (mbits) qt_apply_mask_bits(mbits[off >> 3], v);
       QtVec8<T>::store(dst + off, v);
@@ -612,7 +638,7 @@ if (p.scale || p.shift) {  // (uniform)
   stamp(3);   // epilogue done
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NSTAGE, bool DGRAD, int EH = 1>
+template <typename T, int BM, int BN, int WM, int WN, int NSTAGE, bool DGRAD, int EH = 1, bool PADPIX = false>
 int launch(const ConvArgs& a, hipStream_t stream) {
   constexpr int STAGE = (BM + BN) * kRowBytes;
   constexpr int EPI = BM * BN * 4 / EH;
@@ -620,7 +646,7 @@ int launch(const ConvArgs& a, hipStream_t stream) {
   constexpr int LDS0 = (NSTAGE * STAGE > EPI) ? NSTAGE * STAGE : EPI;
   constexpr int LDS = LDS0 > RED ? LDS0 : RED;
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  auto kern = conv_igemm_kernel<T, BM, BN, WM, WN, NSTAGE, DGRAD, EH>;
+  auto kern = conv_igemm_kernel<T, BM, BN, WM, WN, NSTAGE, DGRAD, EH, PADPIX>;
   static std::atomic<unsigned long long> lds_limit_set{0};  // per device
   if (int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(kern), LDS, lds_limit_set)) return rc;
   ConvArgs args = a;
@@ -663,6 +689,7 @@ inline int tile_m(long long M, int N, int ksteps) { return (M >= 256 * 256 && ks
 template <typename T, bool DGRAD>
 int dispatch2(const ConvArgs& a, hipStream_t stream) {
   const int bm = tile_m(a.M, a.N, a.ntaps * a.KC * (int)sizeof(T) / kRowBytes);
+  if (a.N <= 64 && a.pad_pix) return launch<T, 128, 64, 2, 2, 2, DGRAD, 1, true>(a, stream);
   if (a.N <= 64) return launch<T, 128, 64, 2, 2, 2, DGRAD>(a, stream);
   if (bm == 256) return launch<T, 256, 128, 4, 2, 3, DGRAD>(a, stream);
   return launch<T, 128, 128, 2, 2, 2, DGRAD>(a, stream);
@@ -773,6 +800,8 @@ extern "C" int qt_conv2d_igemm(const qt_conv_desc* d, const qt_conv_io* io, void
   a.gridM = a.gridN = 0;
   a.dst_sub = d->dst_sub; a.dst_h = d->dst_h; a.dst_w = d->dst_w; a.dst_oh = d->dst_off_h; a.dst_ow = d->dst_off_w;
   a.dst_merge = d->dst_merge; a.dst_merge_res0 = d->dst_merge_res0;
+  a.pad_pix = KT == 1 && d->mode == QT_CONV_FWD && d->kw == 1 && d->stride == 2 && (d->kh == 7 || d->kh == 8) &&
+              d->k_per_tap == 32 && d->src_pix_stride == 4 && d->n_out <= 64;
   a.extra_off = 0;
   if (d->dst_merge_extra) {
     QT_CHECK_ARG(d->dst_merge > 0 && io->extra_src && ((uintptr_t)io->extra_src % 16) == 0,

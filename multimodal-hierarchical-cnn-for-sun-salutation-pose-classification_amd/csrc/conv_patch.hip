@@ -284,13 +284,13 @@ if (p.scale || p.shift) {  // (uniform)
         }
         if (p.relu) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+          for (int r = 0; r < 4; ++r) v[r] = qt_relu(v[r]);
         }
         if (OPS && msk) {
           float mv[4];
           bf4(i ? pre_msk[j].z : pre_msk[j].x, i ? pre_msk[j].w : pre_msk[j].y, mv);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = mv[r] > 0.f ? v[r] : 0.f;
+          for (int r = 0; r < 4; ++r) v[r] = qt_relu_gate(mv[r]) ? v[r] : 0.f;
         }
         if (OPS && mbits) {
 #pragma unroll

@@ -616,14 +616,14 @@ __global__ __launch_bounds__(kNT, 2) void conv_pt_kernel(PtArgs q) {
           if constexpr (!BWD) {
             if (p.relu) {
 #pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+              for (int e = 0; e < 8; ++e) v[e] = qt_relu(v[e]);
             }
           } else {
             if (msk) {
               float mv[8];
               rmsk[u].get(mv);
 #pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = mv[e] > 0.f ? v[e] : 0.f;
+              for (int e = 0; e < 8; ++e) v[e] = qt_relu_gate(mv[e]) ? v[e] : 0.f;
             }
             if (mbits) qt_apply_mask_bits(rbits[u], v);
           }

@@ -388,7 +388,7 @@ __global__ __launch_bounds__(kNT, 2) void conv_s2_kernel(S2Args q) {
           }
           if (o.relu) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+            for (int e = 0; e < 8; ++e) v[e] = qt_relu(v[e]);
           }
           QtVec8<T>::store(dst + (long long)drow[j] * q.N + c0, v);
         }

@@ -91,6 +91,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(StemArgs p) {
   };
 
   unsigned char* stg = smem + 2 * ST_BUF + wave * ST_STG;
+  const unsigned keep8 = lg == 3 ? 0u : 0xffffffffu;   // k-group 3 holds window pixels 6 and 7; 7 is the padding of K = 28 to 32
   if (t_beg < t_end) dma_tile(t_beg, 0);
   for (int t = t_beg; t < t_end; ++t) {
     const int buf = (t - t_beg) & 1;
@@ -105,7 +106,11 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(StemArgs p) {
       const unsigned char* a0 = in + (2 * orow) * ST_ROWB + 16 * (ob * 16 + li + lg);
       uint4 xf[7];
 #pragma unroll
-      for (int kh = 0; kh < 7; ++kh) xf[kh] = *reinterpret_cast<const uint4*>(a0 + kh * ST_ROWB);
+      for (int kh = 0; kh < 7; ++kh) {
+        xf[kh] = *reinterpret_cast<const uint4*>(a0 + kh * ST_ROWB);
+        xf[kh].z &= keep8;   // the eighth pixel of the window meets zero weights only: as zero it cannot turn an inf or a
+        xf[kh].w &= keep8;   // NaN NEXT to the 7x7 window into a NaN of this output
+      }
       f32x4 acc[4];
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) acc[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -131,7 +136,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(StemArgs p) {
           v[r] = a;
           if (AFF) {
             v[r] = a * sc[cb][r] + sh[cb][r];
-            if (p.relu) v[r] = fmaxf(v[r], 0.f);
+            if (p.relu) v[r] = qt_relu(v[r]);
           }
         }
         bf16x4 o;
@@ -214,6 +219,7 @@ __global__ __launch_bounds__(512) void conv_stem_pool_kernel(StemPoolArgs p) {
   const int li = lane & 15, lg = lane >> 4;
   const unsigned smem_base = lds_addr_of(smem);
   unsigned char* ctile = smem + (RAW ? SP_BUF + SP_RAW_STG : 2 * SP_BUF);
+  const unsigned keep8 = lg == 3 ? 0u : 0xffffffffu;   // (as in conv_stem_kernel)
 
   const int t_beg = (int)((long long)blockIdx.x * p.ntiles / gridDim.x);
   const int t_end = (int)((long long)(blockIdx.x + 1) * p.ntiles / gridDim.x);
@@ -331,7 +337,11 @@ __global__ __launch_bounds__(512) void conv_stem_pool_kernel(StemPoolArgs p) {
       const unsigned char* a0 = in + (2 * tr) * ST_ROWB + 16 * (ob * 16 + li + lg);
       uint4 xf[7];
 #pragma unroll
-      for (int kh = 0; kh < 7; ++kh) xf[kh] = *reinterpret_cast<const uint4*>(a0 + kh * ST_ROWB);
+      for (int kh = 0; kh < 7; ++kh) {
+        xf[kh] = *reinterpret_cast<const uint4*>(a0 + kh * ST_ROWB);
+        xf[kh].z &= keep8;   // the eighth pixel of the window meets zero weights only: as zero it cannot turn an inf or a
+        xf[kh].w &= keep8;   // NaN NEXT to the 7x7 window into a NaN of this output
+      }
       f32x4 acc[4];
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) acc[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -347,8 +357,13 @@ __global__ __launch_bounds__(512) void conv_stem_pool_kernel(StemPoolArgs p) {
       for (int cb = 0; cb < 4; ++cb) {
         bf16x4 o;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fmaxf(acc[cb][r] * sc[cb][r] + sh[cb][r], 0.f);
-        *reinterpret_cast<bf16x4*>(ctile + ((tr * 112 + ob * 16 + li) * SP_PXB) + cb * 32 + lg * 8) = o;
+        for (int r = 0; r < 4; ++r) o[r] = (bf16_t)qt_relu(acc[cb][r] * sc[cb][r] + sh[cb][r]);
+        // qt_relu keeps a NaN; its sign bit is cleared so that the signed 16-bit maximum of the pool phase orders every NaN
+        // pattern (0x7f81 .. 0x7fff) above +inf (0x7f80): the pooled value of a window that holds a NaN is a NaN, as in ATen
+        uint2 ow = __builtin_bit_cast(uint2, o);
+        ow.x &= 0x7fff7fffu;
+        ow.y &= 0x7fff7fffu;
+        *reinterpret_cast<uint2*>(ctile + ((tr * 112 + ob * 16 + li) * SP_PXB) + cb * 32 + lg * 8) = ow;
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the conv tile is complete
@@ -358,9 +373,9 @@ __global__ __launch_bounds__(512) void conv_stem_pool_kernel(StemPoolArgs p) {
     if (tid < 448) {
       const int cg = tid & 7, pw = tid >> 3;
       // The tile holds ReLU outputs: non-negative bf16 values order like their bit patterns, so the 3x3 maximum is a
-      // packed SIGNED 16-bit maximum on the raw words (a -0 the ReLU may have let through is then the smallest value,
-      // as it is for the float maximum against the +0 start): 4 instructions per 8 channels and window cell instead of
-      // 8 unpacks + 8 float maxima, and the result is the same bf16 value, bit for bit.
+      // packed SIGNED 16-bit maximum on the raw words (the sign bit is clear in every word of the tile: qt_relu returns
+      // +0 for -0, and a NaN was stored without its sign, so a NaN beats every number): 4 instructions per 8 channels and
+      // window cell instead of 8 unpacks + 8 float maxima, and the result is the same bf16 value, bit for bit.
       typedef short us2 __attribute__((ext_vector_type(2)));
       auto pkmax = [](unsigned a, unsigned b) -> unsigned {
         return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));

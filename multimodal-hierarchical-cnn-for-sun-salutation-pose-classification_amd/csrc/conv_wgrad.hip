@@ -528,7 +528,7 @@ __global__ __launch_bounds__(512) void stem_wgrad_rows_kernel(StemWgArgs p) {
         g[3] += (i11 == 0 ? d[3][e] : 0.f);
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
-          const float gm = (y[q4][e] * sc[e] + sh[e] > 0.f) ? g[q4] : 0.f;
+          const float gm = qt_relu_gate(y[q4][e] * sc[e] + sh[e]) ? g[q4] : 0.f;
           o[q4][e] = __builtin_fmaf(k1[e], gm, __builtin_fmaf(-k3[e], y[q4][e], k4[e]));
         }
       }

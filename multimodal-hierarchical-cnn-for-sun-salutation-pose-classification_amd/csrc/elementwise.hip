@@ -185,13 +185,13 @@ __global__ void bn_act_kernel(const T* __restrict__ y, const float* __restrict__
     }
     if (relu) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+      for (int e = 0; e < 8; ++e) v[e] = qt_relu(v[e]);
     }
     QtVec8<T>::store(out + off, v);
     if (bits) {  // the ReLU mask of the data-gradient epilogues, one bit per element (qt_conv_io.relu_mask_bits)
       unsigned b = 0;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) b |= (v[e] > 0.f ? 1u : 0u) << e;
+      for (int e = 0; e < 8; ++e) b |= (qt_relu_gate(v[e]) ? 1u : 0u) << e;
       bits[i] = (unsigned char)b;
     }
   }
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
         float mv[8];
         QtVec8<T>::load(mask + off, mv);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) gv[e] = mv[e] > 0.f ? gv[e] : 0.f;
+        for (int e = 0; e < 8; ++e) gv[e] = qt_relu_gate(mv[e]) ? gv[e] : 0.f;
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -304,7 +304,7 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ g, const T* __restrict
       float mv[8];
       QtVec8<T>::load(mask + off, mv);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) gv[e] = mv[e] > 0.f ? gv[e] : 0.f;
+      for (int e = 0; e < 8; ++e) gv[e] = qt_relu_gate(mv[e]) ? gv[e] : 0.f;
     }
     if (g_out) QtVec8<T>::store(g_out + off, gv);
     load8f(mean + c0, mu);
@@ -408,8 +408,8 @@ __global__ void stem_pool_kernel(const T* __restrict__ y, const float* __restric
         QtVec8<T>::load(y + (((long long)n * H + h) * W + w) * C + c0, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float a = fmaxf(v[e] * sc[e] + sh[e], 0.f);
-          if (a > best[e]) {
+          const float a = qt_relu(v[e] * sc[e] + sh[e]);
+          if (qt_pool_wins(a, best[e])) {
             best[e] = a;
             braw[e] = v[e];
             bidx[e] = kh * 3 + kw;
@@ -494,10 +494,10 @@ __global__ __launch_bounds__(256) void stem_bn_bwd_apply2x2_kernel(
       g11 += (i01 == 6 ? d01[e] : 0.f);
       g11 += (i10 == 2 ? d10[e] : 0.f);
       g11 += (i11 == 0 ? d11[e] : 0.f);
-      g00 = (y00[e] * sc[e] + sh[e] > 0.f) ? g00 : 0.f;
-      g01 = (y01[e] * sc[e] + sh[e] > 0.f) ? g01 : 0.f;
-      g10 = (y10[e] * sc[e] + sh[e] > 0.f) ? g10 : 0.f;
-      g11 = (y11[e] * sc[e] + sh[e] > 0.f) ? g11 : 0.f;
+      g00 = qt_relu_gate(y00[e] * sc[e] + sh[e]) ? g00 : 0.f;
+      g01 = qt_relu_gate(y01[e] * sc[e] + sh[e]) ? g01 : 0.f;
+      g10 = qt_relu_gate(y10[e] * sc[e] + sh[e]) ? g10 : 0.f;
+      g11 = qt_relu_gate(y11[e] * sc[e] + sh[e]) ? g11 : 0.f;
       o00[e] = ca[e] * (g00 - cb[e] - (y00[e] - mu[e]) * is[e] * cc[e]);
       o01[e] = ca[e] * (g01 - cb[e] - (y01[e] - mu[e]) * is[e] * cc[e]);
       o10[e] = ca[e] * (g10 - cb[e] - (y10[e] - mu[e]) * is[e] * cc[e]);
@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256) void stem_bn_bwd_sums_kernel(const T* __restri
     QtVec8<T>::load(y_at_max + i * 8, v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float g = (v[e] * sc[e] + sh[e] > 0.f) ? d[e] : 0.f;
+      const float g = qt_relu_gate(v[e] * sc[e] + sh[e]) ? d[e] : 0.f;
       s1[e] += g;
       s2[e] += g * (v[e] - mu[e]) * is[e];
     }
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_kernel(
     float v[8];
     QtVec8<T>::load(y + off, v);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = (v[e] * sc[e] + sh[e] > 0.f) ? acc[e] : 0.f;
+    for (int e = 0; e < 8; ++e) acc[e] = qt_relu_gate(v[e] * sc[e] + sh[e]) ? acc[e] : 0.f;
     if (MODE == 0) {
       QtVec8<T>::store(out + off, acc);
     } else if (MODE == 1) {
@@ -701,7 +701,7 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ d, const T* __restrict_
     QtVec8<T>::load(d + (long long)b * ld + col0 + c0, dv);
     QtVec8<T>::load(x + i * 8, xv);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) dv[e] = xv[e] > 0.f ? dv[e] * inv : 0.f;
+    for (int e = 0; e < 8; ++e) dv[e] = qt_relu_gate(xv[e]) ? dv[e] * inv : 0.f;
     QtVec8<T>::store(g + i * 8, dv);
   }
 }
@@ -722,9 +722,9 @@ __global__ void quad_pool_kernel(const T* __restrict__ q, T* __restrict__ dst, i
     const int ph = cell / 3, pw = cell % 3;
     const T* s = q + (((long long)img * 7 + ph * 2) * 7 + pw * 2) * C + c;
     float m = qt_to_f32<T>(s[0]);
-    m = fmaxf(m, qt_to_f32<T>(s[C]));
-    m = fmaxf(m, qt_to_f32<T>(s[7 * C]));
-    m = fmaxf(m, qt_to_f32<T>(s[8 * C]));
+    m = qt_max_nan(m, qt_to_f32<T>(s[C]));
+    m = qt_max_nan(m, qt_to_f32<T>(s[7 * C]));
+    m = qt_max_nan(m, qt_to_f32<T>(s[8 * C]));
     const int b = img >> 2, quad = img & 3;
     if constexpr (sizeof(T) == 4)
       dst[(long long)b * ld + col0 + quad * 1152 + c * 9 + cell] = m;
@@ -766,10 +766,10 @@ __global__ void quad_pool_bwd_kernel(const T* __restrict__ d, const T* __restric
     for (int e = 0; e < 8; ++e) {
       int am = 0;
       float best = v[0][e];
-      if (v[1][e] > best) { best = v[1][e]; am = 1; }
-      if (v[2][e] > best) { best = v[2][e]; am = 2; }
-      if (v[3][e] > best) { best = v[3][e]; am = 3; }
-      const float gd = best > 0.f ? qt_to_f32<T>(dp[(c0 + e) * 9]) : 0.f;   // best > 0: ReLU passes gradient
+      if (qt_pool_wins(v[1][e], best)) { best = v[1][e]; am = 1; }
+      if (qt_pool_wins(v[2][e], best)) { best = v[2][e]; am = 2; }
+      if (qt_pool_wins(v[3][e], best)) { best = v[3][e]; am = 3; }
+      const float gd = qt_relu_gate(best) ? qt_to_f32<T>(dp[(c0 + e) * 9]) : 0.f;   // the ReLU in front of the pool
 #pragma unroll
       for (int m = 0; m < 4; ++m) o[m][e] = m == am ? gd : 0.f;
     }
@@ -817,7 +817,7 @@ template <typename T>
 __global__ void relu_mask_scale_kernel(T* __restrict__ g, const T* __restrict__ act, long long n, float mul) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
-    const float v = qt_to_f32<T>(act[i]) > 0.f ? qt_to_f32<T>(g[i]) * mul : 0.f;
+    const float v = qt_relu_gate(qt_to_f32<T>(act[i])) ? qt_to_f32<T>(g[i]) * mul : 0.f;
     if constexpr (sizeof(T) == 4)
       g[i] = v;
     else
@@ -1112,7 +1112,7 @@ static __global__ __launch_bounds__(256) void stem_bn_bwd_sums_light_kernel(cons
                         __uint_as_float(vu.y & 0xffff0000u)};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float g = (v[e] * sc[e] + sh[e] > 0.f) ? d[e] : 0.f;
+      const float g = qt_relu_gate(v[e] * sc[e] + sh[e]) ? d[e] : 0.f;
       s1[e] += g;
       s2[e] += g * v[e];
     }

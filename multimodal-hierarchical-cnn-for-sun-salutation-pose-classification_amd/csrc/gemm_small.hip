@@ -27,7 +27,7 @@ __device__ __forceinline__ void finish(const SmallArgs& a, int m, int n, float a
   if (a.bias) acc += a.bias[n];
   const long long ci = (long long)m * a.crs + n;
   if (a.accumulate) acc += ld(a.C, ci, a.c_bf16);
-  if (a.relu) acc = fmaxf(acc, 0.f);
+  if (a.relu) acc = qt_relu(acc);
   if (a.c_bf16)
     static_cast<bf16_t*>(a.C)[ci] = (bf16_t)acc;
   else

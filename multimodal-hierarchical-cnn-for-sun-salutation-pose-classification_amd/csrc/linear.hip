@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void linear_finish_kernel(const float* __restr
   }
   if (relu) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+    for (int e = 0; e < 8; ++e) v[e] = qt_relu(v[e]);
   }
   QtVec8<bf16_t>::store(y + i, v);
 }

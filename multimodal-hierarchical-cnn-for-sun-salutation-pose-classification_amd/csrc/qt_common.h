@@ -112,6 +112,21 @@ __device__ __forceinline__ void qt_apply_mask_bits(unsigned byte, float (&v)[8])
   for (int e = 0; e < 8; ++e) v[e] = (byte >> e) & 1u ? v[e] : 0.f;
 }
 
+// The ReLU of every forward epilogue: max(v, 0) that KEEPS a NaN (fmaxf returns the other operand: a NaN pre-activation
+// would be stored as 0, where torch.relu gives NaN) and returns +0.0 for -0.0 (`-0.0 <= 0` holds; `v < 0 ? 0 : v` would
+// let it through).  v_cmp_le + v_cndmask, both full rate: __builtin_elementwise_maximum is one v_maximum3_f32 on gfx950,
+// but the train step measured 1 % slower with it than with this pair.  qt_max_nan: the two-operand maximum with the same
+// NaN rule (a NaN on either side is the result), for pools that keep no argmax.
+__device__ __forceinline__ float qt_relu(float v) { return v <= 0.f ? 0.f : v; }
+__device__ __forceinline__ float qt_max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
+// The ReLU gate of every backward kernel, torch's threshold_backward: the gradient is dropped where act <= 0 and kept
+// otherwise -- at a NaN activation too (`act > 0` would send it to 0 and leave bias and BatchNorm gradients of a diverged
+// step at a finite 0).  +0.0 and -0.0 both close the gate.  v_cmp_nle instead of v_cmp_gt: the same instruction count.
+__device__ __forceinline__ bool qt_relu_gate(float act) { return !(act <= 0.f); }
+// The comparison of a max pool that keeps an argmax, ATen's `(val > maxval) || isnan(val)`: a NaN always wins, so the
+// index ends on the LAST NaN of the window in scan order, and a NaN maximum is never replaced by a finite value.
+__device__ __forceinline__ bool qt_pool_wins(float v, float best) { return v > best || v != v; }
+
 // Sum over the 16 lanes of a DPP row (lanes 16r .. 16r+15), every lane receives the total; four DPP adds in a fixed
 // order (row mirror, half-row mirror, quad reversal, neighbour swap) -> deterministic, no LDS crossbar traffic
 // (__shfl_xor compiles to ds_bpermute_b32).

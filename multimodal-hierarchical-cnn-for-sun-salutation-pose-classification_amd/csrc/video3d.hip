@@ -119,7 +119,7 @@ __global__ void pool3d_max_kernel(const T* __restrict__ x, T* __restrict__ out, 
           QtVec8<T>::load(x + src, v);
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            if (v[e] > best[e]) { best[e] = v[e]; idx[e] = (unsigned char)((dt * 2 + dh) * 2 + dw); }
+            if (qt_pool_wins(v[e], best[e])) { best[e] = v[e]; idx[e] = (unsigned char)((dt * 2 + dh) * 2 + dw); }
         }
     const long long o = ((((long long)to * B + b) * Ho + ho) * Wo + wo) * C + g * 8;
     QtVec8<T>::store(out + o, best);
@@ -210,8 +210,8 @@ __global__ void pool3d_bn_relu_max_kernel(const T* __restrict__ y, const float* 
           QtVec8<T>::load(y + src, v);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            const float a = (float)(T)fmaxf(v[e] * sc[e] + sh[e], 0.f);   // (the stored activation's value)
-            if (a > best[e]) { best[e] = a; braw[e] = v[e]; idx[e] = (unsigned char)((dt * 2 + dh) * 2 + dw); }
+            const float a = (float)(T)qt_relu(v[e] * sc[e] + sh[e]);   // (the stored activation's value)
+            if (qt_pool_wins(a, best[e])) { best[e] = a; braw[e] = v[e]; idx[e] = (unsigned char)((dt * 2 + dh) * 2 + dw); }
           }
         }
     QtVec8<T>::store(out + o, best);
@@ -265,7 +265,7 @@ __global__ void pool3d_bn_bwd_apply_kernel(const T* __restrict__ dout, const uns
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const unsigned a = ((e < 4 ? pk.x : pk.y) >> (8 * (e & 3))) & 0xffu;
-        gv[e] = (a == me && pv[e] > 0.f) ? d[e] : 0.f;
+        gv[e] = (a == me && qt_relu_gate(pv[e])) ? d[e] : 0.f;
       }
     }
     QtVec8<T>::load(y + row * Cy + g * 8, yv);
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void pool3d_bn_bwd_apply_light_kernel(const T*
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const unsigned a = ((e < 4 ? pk.x : pk.y) >> (8 * (e & 3))) & 0xffu;
-          gv[u][e] = (a == me && pv[e] > 0.f) ? d[e] : 0.f;
+          gv[u][e] = (a == me && qt_relu_gate(pv[e])) ? d[e] : 0.f;
         }
       }
     }

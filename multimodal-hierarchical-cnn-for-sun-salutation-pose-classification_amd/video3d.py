@@ -594,7 +594,7 @@ class _ConvBlock:
         # cb = cc = 0 and it is gamma invstd sum g = gamma invstd dbeta.
         nv = dbeta.shape[0]   # (cout_p, or cout where the pooled side has no padding channels)
         if s.training:
-            db = torch.zeros(nv, dtype=torch.float32, device=x.device)
+            db = dbeta.float() * 0.0    # zero -- and NaN where the step has diverged (dbeta NaN), as autograd's is
         else:
             db = self.gamma_p.detach().float()[:nv] * s.stats[1][:nv] * dbeta
         slab = r.kernel == SLAB and dy.data_ptr() % 16 == 0
