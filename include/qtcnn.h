@@ -1340,6 +1340,62 @@ int qt_pose_duration_decode(const qt_pose_duration_desc* desc, const float* prob
                             void* stream);
 int qt_pose_duration_count(const qt_pose_duration_desc* desc, const long long* path, long long ld_path, const int* lengths,
                            long long* counts, void* stream);
+/* Pose-order posteriors with hold durations: the MARGINALS of the very chain that qt_pose_duration_decode maximises, by an
+ * explicit-duration (semi-Markov) forward-backward over whole videos, and the expected duration counts that fit dur.  The
+ * reference has no such step.  probs, ld, state_class, trans, init, dur, dur_open and lengths, their clamping, the limits
+ * (S, C <= 64, D <= QT_POSE_DUR_MAX, batch * frames <= 2^20), lengths clamped into 1 .. frames, the emission integers
+ * e[f][j] = q(probs[f][state_class[j]]) and the descriptor are qt_pose_duration_decode's, bit for bit.
+ *
+ * Scores are in bits: T[i][j] = trans / 256, Dur and DurOpen = dur / 256 and dur_open / 256 (DurOpen = Dur when dur_open is
+ * NULL), start = init / 256 or zeros without init.  cum[f][j] = the sum of e[g][j] over g < f, an exact int64;
+ * seg(f, d, j) = (cum[f][j] - cum[f - d][j]) / 256, exact; len(j, d, f) = DurOpen[j][d - 1] where the segment [f - d, f) touches
+ * a cut (f - d == 0 or f == T), else Dur[j][d - 1]; L x = log2 of the sum of 2^x.  Per stream of T frames:
+ *   Bt[0][j] = L_i (start[i] + T[i][j])
+ *   Al[f][j] = L_{d = 1 .. min(D, f)} (Bt[f - d][j] + len(j, d, f) + seg(f, d, j))          f = 1 .. T   (segmentations of
+ *                                                                                          [0, f) that end with a hold of j)
+ *   Bt[f][j] = L_i (Al[f][i] + T[i][j])                                                    f = 1 .. T - 1
+ *   Z        = L_j Al[T][j]                                                                log2_evidence[stream]
+ *   Be[T][j] = 0;   Be[f][i] = L_j (T[i][j] + Bs[f][j])                                    f = T - 1 .. 1
+ *   Bs[f][j] = L_{d = 1 .. min(D, T - f)} (len(j, d, f + d) + seg(f + d, d, j) + Be[f + d][j])      f = T - 1 .. 0
+ *   begin[f][j] = 2^(Bt[f][j] + Bs[f][j] - Z)    f = 0 .. T - 1     the probability that a hold of j begins at frame f
+ *   endp[f][j]  = 2^(Al[f][j] + Be[f][j] - Z)    f = 1 .. T         the probability that a hold of j ends before frame f
+ *   occ[T - 1][j] = endp[T][j];   occ[t][j] = (occ[t + 1][j] + endp[t + 1][j]) - begin[t + 1][j]     (double, descending t)
+ *   posterior[t][j] = r[j] / R,   r = max(occ[t], 0),   R = the sum of r[j] in ascending j (double);   R <= 0: 1 / S
+ *   class_posterior[t][c] = the sum of posterior[t][j] over state_class[j] == c, in ascending j (f32)
+ *   dur_counts[j][d - 1] += the sum over f = 2 .. T - 1 and d <= min(D, f - 1) of
+ *                           2^(Bt[f - d][j] + Dur[j][d - 1] + seg(f, d, j) + Be[f][j] - Z)
+ * dur_counts counts the segments that the video does not cut, as qt_pose_duration_count does for hard paths; it is a double
+ * [S][D] that is ADDED TO (the caller zeroes it once), a stream's terms summed in descending f and the streams' sums in ascending
+ * stream order from zero.  The sum of begin[f][j] over f is the expected number of holds of step j.
+ * Precision: a level (Bt, Al, Be, Bs, Z) is a double (it falls by up to 288 bits a frame, and two levels that a term combines
+ * lie up to D frames apart, so no per-frame normalisation applies).  Inside an L the maximum m is taken out in double; the terms
+ * 2^(x - m), their sum and log2 of the sum are f32, added to m in double.  The exponent of begin, endp and of a count's term is
+ * formed in double, rounded to f32, and 2^ taken in f32; occ and dur_counts are sums in double.  The order of the additions
+ * inside an L depends on S and D only, never on the batch, on other streams or on the run.  Every table in range gives finite
+ * outputs: the floors -8192 and -65536 are finite, so no L is empty.
+ *   posterior        f32 [batch][frames][S], or NULL      class_posterior  f32 [batch][frames][C], or NULL
+ *   begin            f32 [batch][frames][S], or NULL      log2_evidence    double [batch], or NULL
+ *   dur_counts       double [S][D], or NULL               (posterior and dur_counts must not both be NULL)
+ * Rows at and beyond T_b are zeros.  A stream alone gives the bits of the same stream in a batch, a stream with lengths[b] = L
+ * the bits of a call on its first L frames, and every run the same bits.  Nothing is carried between calls: whole videos only.
+ * One launch of qt_pose_duration_decode's walk, one workgroup per stream: a forward sweep with the last D rows of
+ * Bt[f][j] - cum[f][j] / 256 as a ring of doubles in LDS, Al and that row going to the workspace, then the same workgroup's
+ * backward sweep with the ring reused for Be[f][j] + cum[f][j] / 256, writing begin, posterior and class_posterior of a frame
+ * as it passes; with dur_counts every lane also sums the terms of its own (j, d) slots, a stream's [S][D] partial goes to the
+ * workspace and a second small launch adds the partials onto dur_counts.  qt_pose_duration_posterior_workspace_bytes:
+ * 8 * (2 * batch * frames * S + batch * S * D) (every slot that is read is written in the same call), 0 for a descriptor that
+ * would be refused.  No workgroup waits for another, no atomics, no host synchronisation; inputs are never written.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument) for what qt_pose_duration_decode refuses of
+ * the descriptor, ld and the inputs, a null posterior together with a null dur_counts, misaligned pointers (4 bytes for f32
+ * and int32, 8 for log2_evidence, dur_counts and the workspace), a workspace smaller than the query's size, an output
+ * (posterior, class_posterior, begin, log2_evidence, dur_counts, workspace) that overlaps an input or another output;
+ * QT_ERR_UNSUPPORTED for more than 2^20 frames in all (batch * frames). */
+long long qt_pose_duration_posterior_workspace_bytes(const qt_pose_duration_desc* desc);
+int qt_pose_duration_posterior(const qt_pose_duration_desc* desc, const float* probs, long long ld, const int* state_class,
+                               const int* trans, const int* init, const int* dur, const int* dur_open, const int* lengths,
+                               float* posterior, float* class_posterior, float* begin, double* log2_evidence,
+                               double* dur_counts, void* workspace, long long workspace_bytes, void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

@@ -1,5 +1,6 @@
 // What the kernels of the pose-order chain share (pose_order.hip: the decoder and fixed-lag paths; pose_posterior.hip: the
-// posteriors, the learner's E-step and fixed-lag posteriors; pose_prior.hip: path counts and the M-step): the limits, the
+// posteriors, the learner's E-step and fixed-lag posteriors; pose_prior.hip: path counts and the M-step; pose_duration.hip and
+// pose_duration_posterior.hip: the best path and the marginals of the chain with hold durations): the limits, the
 // emission rule q with its table and the loop that stages a tile's emissions, the chain's inputs as one kernel-argument struct,
 // and on the host the descriptor checks, the fixed-lag route and span, the overlap check and the S <= 16 template switch.
 // The build is not relocatable: every .hip that uses pc_q (pose_order.hip, pose_posterior.hip) has the table in its own code
@@ -106,6 +107,18 @@ inline int pc_check_desc(const char* who, const qt_pose_order_desc* d) {
     qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, frames, PC_MAX_FRAMES);
     return QT_ERR_UNSUPPORTED;
   }
+  return QT_OK;
+}
+
+// the chain with hold durations (pose_duration.hip, pose_duration_posterior.hip): the chain's checks and the table's width
+constexpr int PC_MAX_D = 128;
+static_assert(PC_MAX_D == QT_POSE_DUR_MAX, "the header states this");
+inline int pc_duration_check_desc(const char* who, const qt_pose_duration_desc* d) {
+  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  const qt_pose_order_desc chain = {d->batch, d->frames, d->num_classes, d->num_states};
+  if (const int rc = pc_check_desc(who, &chain)) return rc;
+  QT_CHECK_ARG(d->max_duration >= 1 && d->max_duration <= PC_MAX_D, "%s: max_duration = %d; 1 .. %d are handled", who,
+               d->max_duration, PC_MAX_D);
   return QT_OK;
 }
 

@@ -32,7 +32,7 @@ namespace {
 constexpr int PD_THREADS = 256;
 constexpr int PD_CHUNK = 64;                     // frames of emissions staged at a time
 constexpr int PD_MAX_D = 128;
-static_assert(PD_MAX_D == QT_POSE_DUR_MAX, "the header states this");
+static_assert(PD_MAX_D == PC_MAX_D, "pose_chain.h checks the descriptor against this");
 static_assert(PD_MAX_D <= PD_THREADS && PD_MAX_D <= 128 && PC_MAX_S <= 64, "a segment's frames go across the lanes; 7 + 6 bits");
 
 struct PdArgs : PcChain {    // T: the frames of the descriptor (tiles: not read)
@@ -183,14 +183,6 @@ __global__ __launch_bounds__(PD_THREADS) void pd_count_kernel(const long long* _
   atomicAdd(&counts[(int)v * D + min(f - s + 1, D) - 1], 1ull);
 }
 
-int pd_check_desc(const char* who, const qt_pose_duration_desc* d) {
-  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  const qt_pose_order_desc chain = {d->batch, d->frames, d->num_classes, d->num_states};
-  if (const int rc = pc_check_desc(who, &chain)) return rc;
-  QT_CHECK_ARG(d->max_duration >= 1 && d->max_duration <= PD_MAX_D, "%s: max_duration = %d; 1 .. %d are handled", who,
-               d->max_duration, PD_MAX_D);
-  return QT_OK;
-}
 inline long long pd_workspace_bytes(const qt_pose_duration_desc* d) {
   return ((long long)d->batch * d->frames * d->num_states * 2 + 7) / 8 * 8;
 }
@@ -198,7 +190,7 @@ inline long long pd_workspace_bytes(const qt_pose_duration_desc* d) {
 }  // namespace
 
 extern "C" long long qt_pose_duration_workspace_bytes(const qt_pose_duration_desc* desc) {
-  if (pd_check_desc("qt_pose_duration_workspace_bytes", desc) != QT_OK) return 0;
+  if (pc_duration_check_desc("qt_pose_duration_workspace_bytes", desc) != QT_OK) return 0;
   return pd_workspace_bytes(desc);
 }
 
@@ -207,7 +199,7 @@ extern "C" int qt_pose_duration_decode(const qt_pose_duration_desc* desc, const 
                                        const int* dur_open, const int* lengths, long long* path, long long* start,
                                        long long* score, void* workspace, long long workspace_bytes, void* stream) {
   const char* const who = "qt_pose_duration_decode";
-  if (const int rc = pd_check_desc(who, desc)) return rc;
+  if (const int rc = pc_duration_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states, D = desc->max_duration;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
   QT_CHECK_ARG(probs != nullptr && state_class != nullptr && trans != nullptr && dur != nullptr && path != nullptr,
@@ -257,7 +249,7 @@ extern "C" int qt_pose_duration_decode(const qt_pose_duration_desc* desc, const 
 extern "C" int qt_pose_duration_count(const qt_pose_duration_desc* desc, const long long* path, long long ld_path,
                                       const int* lengths, long long* counts, void* stream) {
   const char* const who = "qt_pose_duration_count";
-  if (const int rc = pd_check_desc(who, desc)) return rc;
+  if (const int rc = pc_duration_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, S = desc->num_states, D = desc->max_duration;
   QT_CHECK_ARG(ld_path >= T, "%s: row stride ld_path = %lld < frames = %d", who, ld_path, T);
   QT_CHECK_ARG(path != nullptr && counts != nullptr, "%s: null %s", who, !path ? "path" : "counts");

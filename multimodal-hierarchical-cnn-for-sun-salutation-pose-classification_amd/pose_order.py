@@ -82,8 +82,25 @@ video's end get path -1.  Integers throughout: the same bits on every run.  In t
     counts = durdec.count_durations(step_labels, lengths)           # int64 [S, D] on the device: run lengths of labelled steps
     dur = duration_prior(counts.cpu().numpy())                      # the table fitted to them
 
-Not built for the duration decoder: streaming, fixed-lag and split calls (the carry would be the last D frames of beta),
-posteriors and Baum-Welch over durations, D > 128, true minus infinity (a forbidden length is -65536).
+PoseDurationPosterior (csrc/pose_duration_posterior.hip) gives the marginals of that chain, what PosePosterior gives under the
+plain one: the probability of every step at every frame given the whole video (explicit-duration forward-backward), the same
+summed by class, begin[f][j], the probability that a hold of step j begins at frame f (its sum over the frames is the expected
+number of holds, and so of rounds), the evidence in bits, and the expected duration counts that fit `dur` softly.  It takes the
+decoder's tables, emissions and `lengths`.  A level is a double (it falls by up to 288 bits a frame), the terms inside a log2-sum
+are f32, every sum runs in a fixed order: the same bits on every run, alone or in a batch.
+
+    durpost = PoseDurationPosterior(state_class, trans, dur, device, streams=B, class_names=class_names)
+    for rows, lengths in videos:
+        path, path_class = durdec.decode(rows, lengths=lengths)
+        posterior, begin, bits = durpost.smooth(rows, lengths=lengths, begin=True, evidence=True)    # nothing read back
+        confidence = durpost.confidence(posterior, path)            # 0 beyond a video's end
+        holds = durpost.holds(begin)                                # float64 [B, S]: expected holds per step
+        durpost.expected_durations(rows, lengths)                   # adds into durpost.counts, float64 [S, D]
+    dur = expected_duration_prior(durpost.counts.cpu().numpy())     # the soft counterpart of duration_prior; durpost.zero()
+
+Not built for the chain with durations: streaming, fixed-lag and split calls (the carry would be the last D frames of beta),
+expected transition counts and a full Baum-Welch learner over durations, D > 128, true minus infinity (a forbidden length is
+-65536).
 
 Not built: ragged batches (per-sequence lengths) and videos split across calls in the learner, learning emissions (they are the
 network's), tying rows, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second level of the
@@ -184,6 +201,11 @@ def bind(L):
     L.qt_pose_duration_count.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
         [ctypes.c_void_p] * 3
     L.qt_pose_duration_count.restype = ctypes.c_int
+    L.qt_pose_duration_posterior_workspace_bytes.argtypes = [ctypes.POINTER(PoseDurationDesc)]
+    L.qt_pose_duration_posterior_workspace_bytes.restype = ctypes.c_longlong
+    L.qt_pose_duration_posterior.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 12 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_duration_posterior.restype = ctypes.c_int
     L._pose_order_bound = True
     return L
 
@@ -261,13 +283,32 @@ def duration_prior(counts, pseudo_count=1.0):
             (c < 0).any():
         raise ValueError(f"duration_prior: counts must be [S <= {MAX_STATES}, D <= {DUR_MAX}] integers >= 0 (got shape "
                          f"{c.shape}, {c.dtype})")
+    return _counts_to_scores("duration_prior", c.astype(np.float64), pseudo_count)
+
+
+def _counts_to_scores(who, counts, pseudo_count):
+    """the rule both duration priors share: checked float64 counts [S, D] -> int32 scores"""
     if isinstance(pseudo_count, bool) or not isinstance(pseudo_count, (int, float, np.integer, np.floating)) or \
             not 0.0 <= float(pseudo_count) < float("inf"):
-        raise ValueError(f"duration_prior: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
-    r = c.astype(np.float64) + float(pseudo_count)
+        raise ValueError(f"{who}: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
+    r = counts + float(pseudo_count)
     with np.errstate(divide="ignore", invalid="ignore"):
         p = (r / r.sum(axis=1, keepdims=True)).astype(np.float32)
     return prob_score(p).astype(np.int32)
+
+
+def expected_duration_prior(counts, pseudo_count=1.0):
+    """dur int32 [S, D] from expected duration counts [S, D] (PoseDurationPosterior.expected_durations, float64), on the host:
+    `duration_prior`'s rule for counts that are not integers.  Refused: anything but a real floating or integer array
+    [S <= 64, D <= 128], a negative, NaN or infinite count, a pseudo_count that is not a finite number >= 0."""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.dtype.kind not in "fiu" or not 1 <= c.shape[0] <= MAX_STATES or not 1 <= c.shape[1] <= DUR_MAX:
+        raise ValueError(f"expected_duration_prior: counts must be [S <= {MAX_STATES}, D <= {DUR_MAX}] real numbers (got shape "
+                         f"{c.shape}, {c.dtype})")
+    c = c.astype(np.float64)
+    if not np.isfinite(c).all() or (c < 0).any():
+        raise ValueError("expected_duration_prior: counts must be finite and >= 0")
+    return _counts_to_scores("expected_duration_prior", c, pseudo_count)
 
 
 def hold_prior(S, D, shortest, longest, inside=0, outside=TRANS_FLOOR):
@@ -453,11 +494,10 @@ class PoseOrderDecoder(_PoseStreams):
         return ((before == wrap_from) & (path == wrap_to)).sum(dim=1)
 
 
-class PoseDurationDecoder(_PoseTables):
-    """The decoder with hold durations of `streams` whole videos: the chain's tables, dur and dur_open int32 [S, D] and a
-    workspace that grows on demand, all in device memory.  dur_open: "suffix_max" (built here, on the host), a table of its
-    own, or None for dur itself.  Nothing is carried between calls; `decode`, `cycles` and `count_durations` launch kernels
-    and read nothing back.  See the module text."""
+class _PoseDurationTables(_PoseTables):
+    """what the owners of a duration table share: the chain's tables, dur and dur_open int32 [S, D] checked and in device
+    memory (dur_open: "suffix_max", built here on the host, a table of its own, or None for dur itself), and the check of a
+    `lengths` argument"""
 
     def __init__(self, state_class, trans, dur, device, streams=1, init=None, dur_open="suffix_max", class_names=None):
         super().__init__(state_class, trans, device, streams, init, class_names, dur=dur, dur_open=dur_open)
@@ -466,7 +506,6 @@ class PoseDurationDecoder(_PoseTables):
         self.max_duration = int(dur.shape[1])
         self.dur = torch.from_numpy(np.ascontiguousarray(dur, np.int32)).to(self.device)
         self.dur_open = None if dur_open is None else torch.from_numpy(np.ascontiguousarray(dur_open, np.int32)).to(self.device)
-        self._state_class64 = self.state_class.to(torch.int64)
 
     def _check_own(self, who, init, dur, dur_open):
         S = self.num_states
@@ -499,6 +538,17 @@ class PoseDurationDecoder(_PoseTables):
                 tuple(lengths.shape) != (B,):
             raise QtError(f"{what}: lengths must be an int32 tensor [{B}] on {self.device}")
         return lengths.detach().contiguous()
+
+
+class PoseDurationDecoder(_PoseDurationTables):
+    """The decoder with hold durations of `streams` whole videos: the chain's tables, dur and dur_open int32 [S, D] and a
+    workspace that grows on demand, all in device memory.  dur_open: "suffix_max" (built here, on the host), a table of its
+    own, or None for dur itself.  Nothing is carried between calls; `decode`, `cycles` and `count_durations` launch kernels
+    and read nothing back.  See the module text."""
+
+    def __init__(self, state_class, trans, dur, device, streams=1, init=None, dur_open="suffix_max", class_names=None):
+        super().__init__(state_class, trans, dur, device, streams, init, dur_open, class_names)
+        self._state_class64 = self.state_class.to(torch.int64)
 
     def decode(self, probs, lengths=None, start=False, score=False):
         """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on the decoder's device, whole videos;
@@ -648,6 +698,91 @@ class PosePosterior(_PoseStreams):
             raise QtError(f"PosePosterior.confidence: posterior {list(posterior.shape)} and path {list(path.shape)} do not "
                           f"belong together ({self.num_states} states)")
         return posterior.gather(-1, path.unsqueeze(-1)).squeeze(-1)
+
+
+class PoseDurationPosterior(_PoseDurationTables):
+    """The posterior marginals of `streams` whole videos over PoseDurationDecoder's chain (csrc/pose_duration_posterior.hip):
+    the same checked tables, a float64 [S, D] accumulator of expected duration counts and a workspace that grows on demand, all
+    in device memory.  Nothing is carried between calls; no call reads anything back or synchronises.  See the module text."""
+
+    def __init__(self, state_class, trans, dur, device, streams=1, init=None, dur_open="suffix_max", class_names=None):
+        super().__init__(state_class, trans, dur, device, streams, init, dur_open, class_names)
+        self.counts = torch.zeros(self.num_states, self.max_duration, dtype=torch.float64, device=self.device)
+
+    def zero(self):
+        """clears the accumulator of `expected_durations` (no host sync)"""
+        self.counts.zero_()
+        return self
+
+    def _run(self, what, probs, lengths, post, cls, begin, ev, counts):
+        B, T, C = probs.shape
+        desc = PoseDurationDesc(B, T, C, self.num_states, self.max_duration)
+        L = bind(_lib.lib())
+        ws, ws_bytes = self._room(L.qt_pose_duration_posterior_workspace_bytes, desc)
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_duration_posterior(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1),
+                                                    _lib.ptr(self.state_class), _lib.ptr(self.trans), _lib.ptr(self.init),
+                                                    _lib.ptr(self.dur), _lib.ptr(self.dur_open), _lib.ptr(lengths),
+                                                    _lib.ptr(post), _lib.ptr(cls), _lib.ptr(begin), _lib.ptr(ev),
+                                                    _lib.ptr(counts), ws, ws_bytes, _lib.stream_ptr()),
+                       "qt_pose_duration_posterior")
+
+    def smooth(self, probs, lengths=None, by_class=False, begin=False, evidence=False):
+        """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device, whole videos;
+        lengths: int32 [streams] on the device, or None (a value outside 1 .. frames is clamped into it).  Returns posterior f32
+        [streams, frames, S] (or [frames, S]): the probability of every step at every frame given the whole video; then, as
+        asked and in this order, the class posterior f32 [..., C], begin f32 [..., S] (the probability that a hold of step j
+        begins at frame f) and the evidence in bits, float64 [streams].  Rows beyond a video's end are zeros.  A tuple when
+        anything beyond the posterior is asked for."""
+        what = "PoseDurationPosterior.smooth"
+        probs, flat, T, C = self._check_probs(what, probs)
+        B, S = self.streams, self.num_states
+        lengths = self._check_lengths(what, lengths, B)
+        lead = (T,) if flat else (B, T)
+        dev = self.device
+        post = torch.empty(lead + (S,), dtype=torch.float32, device=dev)
+        cls = torch.empty(lead + (C,), dtype=torch.float32, device=dev) if by_class else None
+        beg = torch.empty(lead + (S,), dtype=torch.float32, device=dev) if begin else None
+        ev = torch.empty(B, dtype=torch.float64, device=dev) if evidence else None
+        self._run(what, probs, lengths, post, cls, beg, ev, None)
+        out = (post,) + tuple(t for t in (cls, beg, ev) if t is not None)
+        return out[0] if len(out) == 1 else out
+
+    def confidence(self, posterior, path):
+        """f32 [streams, frames] (or [frames]): the posterior at the states of `path` (PoseDurationDecoder.decode's, int64),
+        0 where path is -1 (beyond a video's end).  Plain torch, nothing read back."""
+        who = "PoseDurationPosterior.confidence"
+        if not isinstance(posterior, torch.Tensor) or posterior.device != self.device or posterior.dtype != torch.float32:
+            raise QtError(f"{who}: posterior must be an f32 tensor on {self.device}")
+        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
+            raise QtError(f"{who}: path must be an int64 tensor on {self.device}")
+        if posterior.shape[:-1] != path.shape or posterior.shape[-1] != self.num_states:
+            raise QtError(f"{who}: posterior {list(posterior.shape)} and path {list(path.shape)} do not belong together "
+                          f"({self.num_states} states)")
+        at = posterior.gather(-1, path.clamp_min(0).unsqueeze(-1)).squeeze(-1)
+        return torch.where(path >= 0, at, torch.zeros_like(at))
+
+    def holds(self, begin):
+        """float64 [streams, S]: the sum of `begin` (a smooth's, [streams, frames, S] or [frames, S]) over the frames, the
+        expected number of holds of every step, and so of rounds.  Plain torch, nothing read back."""
+        who = "PoseDurationPosterior.holds"
+        if not isinstance(begin, torch.Tensor) or begin.device != self.device or begin.dtype != torch.float32:
+            raise QtError(f"{who}: begin must be an f32 tensor on {self.device}")
+        if begin.dim() == 2 and self.streams == 1:
+            begin = begin.unsqueeze(0)
+        if begin.dim() != 3 or begin.shape[0] != self.streams or begin.shape[2] != self.num_states:
+            raise QtError(f"{who}: begin must be [{self.streams}, frames, {self.num_states}] (got {list(begin.shape)})")
+        return begin.sum(dim=1, dtype=torch.float64)
+
+    def expected_durations(self, probs, lengths=None):
+        """adds the expected duration counts of these videos (probs and lengths as for `smooth`) into the float64 [S, D]
+        accumulator on the device and returns it: the soft counterpart of PoseDurationDecoder.count_durations, for
+        `expected_duration_prior`.  Only the segments that the video does not cut count.  `zero()` clears it."""
+        what = "PoseDurationPosterior.expected_durations"
+        probs, _, _, _ = self._check_probs(what, probs)
+        lengths = self._check_lengths(what, lengths, self.streams)
+        self._run(what, probs, lengths, None, None, None, None, self.counts)
+        return self.counts
 
 
 class _PoseLag(_PoseStreams):
