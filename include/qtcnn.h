@@ -1396,6 +1396,71 @@ int qt_pose_duration_posterior(const qt_pose_duration_desc* desc, const float* p
                                const int* trans, const int* init, const int* dur, const int* dur_open, const int* lengths,
                                float* posterior, float* class_posterior, float* begin, double* log2_evidence,
                                double* dur_counts, void* workspace, long long workspace_bytes, void* stream);
+/* Fixed-lag pose-order decoding with hold durations, for a loop that hands over a frame or a few per call: for the frame `lag`
+ * frames ago, the state and the segment start that qt_pose_duration_decode would give on the stream up to now, at a cost per
+ * step that does not grow with the video.  The reference has no such step.  probs, ld, state_class, trans, init, dur, dur_open
+ * (NULL: dur), the emission integers e[f][j], the clamps to [-65536, 0] and the limits (S, C <= 64, D <= QT_POSE_DUR_MAX) are
+ * qt_pose_duration_decode's, bit for bit; lag in 0 .. QT_POSE_LAG_MAX, seen, flush, frames = n >= 0 (0 with flush only),
+ * batch * frames <= 2^20 per call and the emitted span are the fixed-lag pair's:
+ *   g0 = max(0, seen - lag),   g1 = flush ? seen + n : max(0, seen + n - lag),   count = g1 - g0
+ * There is no lengths argument: all streams of a batch advance together.
+ * Forward, per stream, f = the count of frames consumed since the stream's start, in exact integers (int64); cum and beta[0] as
+ * in qt_pose_duration_decode:
+ *   alpha[f][j]      = max over d = 1 .. min(D, f) of  beta[f - d][j] + len + cum[f][j] - cum[f - d][j],   len = dur_open[j][d - 1]
+ *                      where f - d == 0 (the segment touches the stream's start), else dur[j][d - 1];   dlen[f][j] = the LOWEST
+ *                      d that attains it
+ *   alpha_open[f][j] = the same maximum with len = dur_open[j][d - 1] for every d, as if the stream were cut after frame f, and
+ *                      dlen_open[f][j] its lowest d (dur_open NULL: alpha and dlen themselves)
+ *   beta[f][j]       = max_i (alpha[f][i] + trans[i][j]),   from[f][j] = the LOWEST i: built from the closed alpha, as the
+ *                      whole-video decoder does for f < T
+ *   end[f]           = the LOWEST j that attains best[f] = max_j alpha_open[f][j]
+ * Window of an emitted frame g (0-based), with last = seen + n - 1, w = min(g + lag, last), F = w + 1:
+ *   j = end[F], d = dlen_open[F][j], f = F;  repeat { if f - d <= g: lag_path[g] = j, lag_start[g] = f - d, stop;
+ *   f -= d;  j = from[f][j];  d = dlen[f][j] }
+ * which reads from and dlen at g < f <= w only: at most lag rows.
+ *   lag_path   int64 [batch][count], required when count > 0    lag_start  int64 [batch][count], or NULL: the global index of
+ *   filtered   int64 [batch][n], or NULL: end[f] of each                   the first frame of the segment frame g lies in
+ *              new frame                                        score      int64 [batch][n], or NULL: best[f] of each new frame
+ * Carry.  Caller-owned device memory as two buffers that must not overlap, carry_in (read; not read and may be NULL with seen
+ * == 0) and carry_out (written in full); the caller swaps them between calls.  Per stream { int64 cum[S]; int64 g[D][S]:
+ * g[f][j] = beta[f][j] - cum[f][j] at row f mod D for the last D values of f, rows never written zero; uint16 hist[lag][S]:
+ * (dlen - 1) | from << 7 of f = seen + n - lag + 1 + k in slot k, zeros for f <= 0; uint16 tail = (dlen_open[F][end[F]] - 1) |
+ * end[F] << 7 of the newest F = seen + n (0 at F == 0; a flush with frames == 0 starts its walks there) }, rounded up to 8
+ * bytes.  qt_pose_duration_lag_carry_bytes gives the size of one buffer.  lag, the tables, D and batch are fixed for the life
+ * of a stream.  The scores are absolute: no offset, no saturation; seen + frames may be at most 2^36 (|beta| < 2^54).
+ * Contract.  For any split of a stream into calls, flush on the last, every output and the final carry are the bits of one
+ * call (one route, no environment switch).  lag_path[g] and lag_start[g] are path[g] and start[g] of qt_pose_duration_decode
+ * on the stream's first min(g + lag, last) + 1 frames, score of frame f is its score on the first f + 1 frames; hence a
+ * one-call flush with n <= lag + 1 is qt_pose_duration_decode on those frames.  With D == 1 and dur all zero lag_path is
+ * qt_pose_lag_decode's.  A stream alone gives the bits it has in a batch.
+ * One launch, one workgroup of 256 per stream, qt_pose_duration_decode's frame step with both maxima: the ring g comes from
+ * carry_in into LDS (beta[0] at seen == 0), every new frame's hist row and tail word go to the workspace (uint16 [batch][n][S]
+ * and [batch][n], each rounded up to 8 bytes; 0 bytes at n == 0), filtered and score are written per frame, and behind a
+ * barrier one thread per emitted frame walks its window through the workspace (the workgroup's own stores) and carry_in's
+ * hist; then carry_out.  qt_pose_duration_lag_workspace_bytes: what the call needs, 0 for a descriptor that would be refused
+ * (as the carry query).  No atomics, no host synchronisation, no workgroup waits for another; inputs, carry_in included, are
+ * never written; every workspace slot that is read is written in the same call.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument): the descriptor's ranges (batch >= 1, frames
+ * >= 0, num_classes and num_states in 1 .. 64, max_duration in 1 .. 128, lag in 0 .. 63, seen >= 0), ld < C, a null probs
+ * (with frames > 0), state_class, trans, dur or carry_out, count > 0 with a null lag_path, seen > 0 with a null carry_in,
+ * frames == 0 without flush, misaligned pointers (4 bytes for f32 and int32; 8 for int64, the carries and the workspace), a
+ * workspace smaller than the query's size, an output that overlaps an input or another output (carry_in overlapping
+ * carry_out included).  QT_ERR_UNSUPPORTED for more than 2^20 frames in a call (batch * frames) and for seen + frames > 2^36. */
+typedef struct qt_pose_duration_lag_desc {
+  int batch, frames, num_classes, num_states;   /* as qt_pose_lag_desc; frames = n >= 0 new frames per stream */
+  int max_duration;                             /* D, 1 .. QT_POSE_DUR_MAX */
+  int lag;                                      /* 0 .. QT_POSE_LAG_MAX */
+  int flush;                                    /* != 0: also emit the frames still pending after this call's last frame */
+  long long seen;                               /* frames of every stream handed over before this call */
+} qt_pose_duration_lag_desc;
+long long qt_pose_duration_lag_carry_bytes(const qt_pose_duration_lag_desc* desc);
+long long qt_pose_duration_lag_workspace_bytes(const qt_pose_duration_lag_desc* desc);
+int qt_pose_duration_lag_decode(const qt_pose_duration_lag_desc* desc, const float* probs, long long ld,
+                                const int* state_class, const int* trans, const int* init, const int* dur, const int* dur_open,
+                                const void* carry_in, void* carry_out, long long* lag_path, long long* lag_start,
+                                long long* filtered, long long* score, void* workspace, long long workspace_bytes,
+                                void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

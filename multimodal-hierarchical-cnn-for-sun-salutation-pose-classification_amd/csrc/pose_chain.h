@@ -1,8 +1,9 @@
 // What the kernels of the pose-order chain share (pose_order.hip: the decoder and fixed-lag paths; pose_posterior.hip: the
-// posteriors, the learner's E-step and fixed-lag posteriors; pose_prior.hip: path counts and the M-step; pose_duration.hip and
-// pose_duration_posterior.hip: the best path and the marginals of the chain with hold durations): the limits, the
-// emission rule q with its table and the loop that stages a tile's emissions, the chain's inputs as one kernel-argument struct,
-// and on the host the descriptor checks, the fixed-lag route and span, the overlap check and the S <= 16 template switch.
+// posteriors, the learner's E-step and fixed-lag posteriors; pose_prior.hip: path counts and the M-step; pose_duration.hip,
+// pose_duration_lag.hip and pose_duration_posterior.hip: the best path, its fixed-lag form and the marginals of the chain with
+// hold durations): the limits, the emission rule q with its table and the loop that stages a tile's emissions, the chain's
+// inputs as one kernel-argument struct, the lane-group maximum, and on the host the descriptor checks, the fixed-lag route and
+// span, the overlap check and the S <= 16 template switch.
 // The build is not relocatable: every .hip that uses pc_q (pose_order.hip, pose_posterior.hip) has the table in its own code
 // object.
 #pragma once
@@ -93,6 +94,18 @@ __device__ __forceinline__ void pc_stage_emissions(const PcChain& a, int b, int 
   }
 }
 
+// (value, index) of the maximum over a group of LPS adjacent lanes, the lower index at equal values; every lane receives it
+// (pose_duration.hip, pose_duration_lag.hip)
+template <int LPS>
+__device__ __forceinline__ void pc_group_max(long long& v, int& k) {
+#pragma unroll
+  for (int s = 1; s < LPS; s <<= 1) {
+    const long long ov = __shfl_xor(v, s, QT_WAVE);
+    const int ok = __shfl_xor(k, s, QT_WAVE);
+    if (ov > v || (ov == v && ok < k)) v = ov, k = ok;
+  }
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 inline int pc_check_desc(const char* who, const qt_pose_order_desc* d) {
   QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
@@ -160,6 +173,28 @@ inline PcSpan pc_lag_span(const qt_pose_lag_desc* d) {
   s.g1 = d->flush ? end : (end > d->lag ? end - d->lag : 0);
   s.count = s.g1 - s.g0;
   return s;
+}
+
+// the fixed-lag decoder with hold durations (pose_duration_lag.hip): the fixed-lag pair's descriptor with the table's width;
+// the scores are absolute int64, which bounds the frames of a stream
+constexpr long long PC_DUR_LAG_MAX_SEEN = 1LL << 36;
+inline qt_pose_lag_desc pc_duration_lag_as_lag(const qt_pose_duration_lag_desc* d) {
+  return {d->batch, d->frames, d->num_classes, d->num_states, d->lag, d->flush, d->seen};
+}
+inline int pc_duration_lag_check_desc(const char* who, const qt_pose_duration_lag_desc* d) {
+  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  const qt_pose_lag_desc lag = pc_duration_lag_as_lag(d);
+  const int rc = pc_lag_check_desc(who, &lag);
+  if (rc != QT_OK && rc != QT_ERR_UNSUPPORTED) return rc;
+  QT_CHECK_ARG(d->max_duration >= 1 && d->max_duration <= PC_MAX_D, "%s: max_duration = %d; 1 .. %d are handled", who,
+               d->max_duration, PC_MAX_D);
+  if (rc != QT_OK) return rc;
+  if (d->seen > PC_DUR_LAG_MAX_SEEN - d->frames) {
+    qt_set_error("%s: seen + frames = %lld + %d; a stream of at most %lld frames is handled", who, d->seen, d->frames,
+                 PC_DUR_LAG_MAX_SEEN);
+    return QT_ERR_UNSUPPORTED;
+  }
+  return QT_OK;
 }
 
 // no output may overlap an input or another output

@@ -1,7 +1,8 @@
 // Pose-order decoding with hold durations (qt_pose_duration_decode): the best segmentation of a whole video under an explicit-
 // duration (semi-Markov) chain over the steps of the pose sequence, and the run-length counts that fit its duration table
 // (qt_pose_duration_count).  include/qtcnn.h states the rule in full; the reference has no such step.  pose_chain.h supplies the
-// limits PC_*, the emission rule (pc_q, pc_stage_emissions), the chain's inputs PcChain, the overlap check and the S <= 16 switch.
+// limits PC_*, the emission rule (pc_q, pc_stage_emissions), the chain's inputs PcChain, the lane-group maximum pc_group_max,
+// the overlap check and the S <= 16 switch.
 //
 // The recurrence has order D in the frame index, so the (max, +) tile products of pose_order.hip do not apply (the semiring
 // state would be S * D wide).  One workgroup of 256 per stream walks the frames in order.  With cum[f][j] the prefix sum of the
@@ -48,17 +49,6 @@ struct PdArgs : PcChain {    // T: the frames of the descriptor (tiles: not read
 
 inline size_t pd_lds_bytes(int S, int D) { return 8 * ((size_t)D * S + S + 1) + 4 * (size_t)S * S + 2 * (size_t)PD_CHUNK * S; }
 
-// (value, index) of the maximum over the LPS lanes of a group, the lower index at equal values; every lane receives it
-template <int LPS>
-__device__ __forceinline__ void pd_group_max(long long& v, int& k) {
-#pragma unroll
-  for (int s = 1; s < LPS; s <<= 1) {
-    const long long ov = __shfl_xor(v, s, QT_WAVE);
-    const int ok = __shfl_xor(k, s, QT_WAVE);
-    if (ov > v || (ov == v && ok < k)) v = ov, k = ok;
-  }
-}
-
 template <bool SMALL>
 __global__ __launch_bounds__(PD_THREADS) void pd_stream_kernel(PdArgs a) {
   constexpr int LPS = SMALL ? 16 : 4;            // lanes per state
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(PD_THREADS) void pd_stream_kernel(PdArgs a) {
       const long long v = alpha[i] + tr[i * S + jj];
       if (v > best) best = v, from = i;
     }
-    pd_group_max<LPS>(best, from);
+    pc_group_max<LPS>(best, from);
   };
 
   long long cum = 0, beta;
@@ -124,7 +114,7 @@ __global__ __launch_bounds__(PD_THREADS) void pd_stream_kernel(PdArgs a) {
         if (v > best) best = v, bd = d;
       }
     }
-    pd_group_max<LPS>(best, bd);
+    pc_group_max<LPS>(best, bd);
     if (own) alpha[j] = cum + best;
     __syncthreads();
     if (f < T) {

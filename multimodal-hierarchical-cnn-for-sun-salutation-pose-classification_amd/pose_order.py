@@ -98,9 +98,22 @@ are f32, every sum runs in a fixed order: the same bits on every run, alone or i
         durpost.expected_durations(rows, lengths)                   # adds into durpost.counts, float64 [S, D]
     dur = expected_duration_prior(durpost.counts.cpu().numpy())     # the soft counterpart of duration_prior; durpost.zero()
 
-Not built for the chain with durations: streaming, fixed-lag and split calls (the carry would be the last D frames of beta),
-expected transition counts and a full Baum-Welch learner over durations, D > 128, true minus infinity (a forbidden length is
--65536).
+PoseDurationLagDecoder (csrc/pose_duration_lag.hip) is PoseDurationDecoder for a loop that hands over a frame or a few per call,
+as PoseLagDecoder is PoseOrderDecoder's: `push` returns, for the frames `lag` frames ago, the step and (start=True) the first frame
+of its hold that PoseDurationDecoder would give on the stream up to now, a fixed delay behind the camera at a cost per step that
+does not grow with the video.  The forward pass takes two maxima per frame, the closed one that the recurrence goes on from and
+the open one that scores the stream as if it were cut here (dur_open); the last D rows of the forward pass and the last `lag` rows
+of back-pointers travel between calls in two carry buffers that the object swaps.  Integers throughout, absolute int64 scores (a
+stream may run for 2^36 frames); for any split of a stream into pushes, flush on the last, the outputs are the bits of one push.
+
+    livedur = PoseDurationLagDecoder(state_class, trans, dur, device, lag=16, streams=16)
+    for rows in live:                                               # f32 [streams, 1, C]: one frame per stream
+        first, lag_path, lag_start = livedur.push(rows, start=True)     # frames first .. first + lag_path.shape[1] - 1
+        held = first + torch.arange(lag_path.shape[1], device=device) - lag_start      # "held for n frames"
+    first, lag_path, lag_start = livedur.push(rows[:, :0], flush=True, start=True)     # the last lag frames
+
+Not built for the chain with durations: fixed-lag posteriors with durations, expected transition counts and a full Baum-Welch
+learner over durations, D > 128, true minus infinity (a forbidden length is -65536).
 
 Not built: ragged batches (per-sequence lengths) and videos split across calls in the learner, learning emissions (they are the
 network's), tying rows, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second level of the
@@ -123,6 +136,7 @@ MAX_CLASSES = 64            # QT_POSE_ORDER_MAX_CLASSES
 MAX_FRAMES = 1 << 20
 LAG_MAX = 63                # QT_POSE_LAG_MAX
 DUR_MAX = 128               # QT_POSE_DUR_MAX
+MAX_STREAM_FRAMES = 1 << 36  # qt_pose_duration_lag_decode: seen + frames (absolute int64 scores)
 SCORE_FLOOR = -8192         # q of NaN and of everything below 2^-32
 TRANS_FLOOR = -65536
 # rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the table of csrc/pose_chain.h
@@ -157,6 +171,11 @@ class PoseLagDesc(ctypes.Structure):     # qt_pose_lag_desc
 class PoseDurationDesc(ctypes.Structure):   # qt_pose_duration_desc
     _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
                 ("max_duration", ctypes.c_int)]
+
+
+class PoseDurationLagDesc(ctypes.Structure):   # qt_pose_duration_lag_desc
+    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
+                ("max_duration", ctypes.c_int), ("lag", ctypes.c_int), ("flush", ctypes.c_int), ("seen", ctypes.c_longlong)]
 
 
 def bind(L):
@@ -206,6 +225,12 @@ def bind(L):
     L.qt_pose_duration_posterior.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
         [ctypes.c_void_p] * 12 + [ctypes.c_longlong, ctypes.c_void_p]
     L.qt_pose_duration_posterior.restype = ctypes.c_int
+    for name in ("qt_pose_duration_lag_carry_bytes", "qt_pose_duration_lag_workspace_bytes"):
+        getattr(L, name).argtypes = [ctypes.POINTER(PoseDurationLagDesc)]
+        getattr(L, name).restype = ctypes.c_longlong
+    L.qt_pose_duration_lag_decode.argtypes = [ctypes.POINTER(PoseDurationLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 12 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_duration_lag_decode.restype = ctypes.c_int
     L._pose_order_bound = True
     return L
 
@@ -785,6 +810,11 @@ class PoseDurationPosterior(_PoseDurationTables):
         return self.counts
 
 
+def _check_lag(who, lag):
+    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
+        raise ValueError(f"{who}: lag must be an integer in 0 .. {LAG_MAX} (got {lag!r})")
+
+
 class _PoseLag(_PoseStreams):
     """what PoseLagSmoother and PoseLagDecoder share: the tables, the count of frames seen (on the host: all streams advance
     together), the two carry buffers that are swapped after every push, and a workspace that grows on demand"""
@@ -799,8 +829,7 @@ class _PoseLag(_PoseStreams):
         self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]  # [0]: the next call's carry_in
 
     def _check_own(self, who, init, lag):
-        if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
-            raise ValueError(f"{who}: lag must be an integer in 0 .. {LAG_MAX} (got {lag!r})")
+        _check_lag(who, lag)
         return init
 
     def reset(self):
@@ -886,6 +915,60 @@ class PoseLagDecoder(_PoseLag):
                                             _lib.stream_ptr()), "qt_pose_lag_decode")
         self._advance(T)
         return (first, path) + ((filt,) if filtered else ())
+
+
+class PoseDurationLagDecoder(_PoseDurationTables):
+    """Fixed-lag paths with hold durations of `streams` live videos (csrc/pose_duration_lag.hip): `push` takes the new frames
+    and returns, for the frames `lag` frames ago, the step and the start of its hold that PoseDurationDecoder would give on the
+    stream up to now.  The tables are PoseDurationDecoder's; the count of frames seen lives on the host (all streams advance
+    together), the two carry buffers are swapped after every push.  Nothing is read back.  See the module text."""
+    _empty_with_flush = True
+
+    def __init__(self, state_class, trans, dur, device, lag, streams=1, init=None, dur_open="suffix_max", class_names=None):
+        _check_lag(type(self).__name__, lag)
+        super().__init__(state_class, trans, dur, device, streams, init, dur_open, class_names)
+        self.lag, self.seen = int(lag), 0
+        desc = PoseDurationLagDesc(streams, 1, 1, self.num_states, self.max_duration, self.lag, 0, 0)
+        nbytes = int(bind(_lib.lib()).qt_pose_duration_lag_carry_bytes(ctypes.byref(desc)))
+        self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]  # [0]: the next call's carry_in
+
+    def reset(self):
+        """every stream starts anew (no host sync; the carry is not read at a stream's first frame)"""
+        self.seen = 0
+        return self
+
+    def push(self, probs, flush=False, start=False, filtered=False, score=False):
+        """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device; frames may be 0
+        with flush.  Returns (first_frame, lag_path int64 [streams, count] (or [count])), then as asked and in this order
+        lag_start int64 of the same shape (the first frame of the hold a frame lies in, counted from the stream's start), the
+        causal end states of the new frames int64 [..., frames] and the best score of the stream cut after each new frame,
+        int64 [..., frames]: lag_path[:, k] belongs to frame first_frame + k of the stream, count is frames once the stream is
+        `lag` frames old, 0 before, and with flush also the frames still pending."""
+        what = "PoseDurationLagDecoder.push"
+        probs, flat, T, C = self._check_probs(what, probs, allow_empty=flush)
+        B, dev = self.streams, self.device
+        if self.seen + T > MAX_STREAM_FRAMES:
+            raise QtError(f"{what}: frame {self.seen + T} of a stream; at most {MAX_STREAM_FRAMES} are handled")
+        first = max(0, self.seen - self.lag)
+        count = (self.seen + T if flush else max(0, self.seen + T - self.lag)) - first
+        desc = PoseDurationLagDesc(B, T, C, self.num_states, self.max_duration, self.lag, int(bool(flush)), self.seen)
+        lead = (lambda n: (n,)) if flat else (lambda n: (B, n))
+        path = torch.empty(lead(count), dtype=torch.int64, device=dev)
+        begin = torch.empty(lead(count), dtype=torch.int64, device=dev) if start else None
+        filt = torch.empty(lead(T), dtype=torch.int64, device=dev) if filtered else None
+        best = torch.empty(lead(T), dtype=torch.int64, device=dev) if score else None
+        L = bind(_lib.lib())
+        ws, ws_bytes = self._room(L.qt_pose_duration_lag_workspace_bytes, desc)
+        with torch.cuda.device(dev):
+            _lib.check(L.qt_pose_duration_lag_decode(
+                ctypes.byref(desc), _lib.ptr(probs) if T else None, probs.stride(1) if T else C, _lib.ptr(self.state_class),
+                _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.dur), _lib.ptr(self.dur_open),
+                _lib.ptr(self._carry[0]) if self.seen else None, _lib.ptr(self._carry[1]), _lib.ptr(path) if count else None,
+                _lib.ptr(begin) if count else None, _lib.ptr(filt) if T else None, _lib.ptr(best) if T else None, ws, ws_bytes,
+                _lib.stream_ptr()), "qt_pose_duration_lag_decode")
+        self.seen += T
+        self._carry.reverse()
+        return (first, path) + tuple(t for t in (begin, filt, best) if t is not None)
 
 
 class PoseOrderLearner(_PoseTables):
