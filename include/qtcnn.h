@@ -1396,6 +1396,75 @@ int qt_pose_duration_posterior(const qt_pose_duration_desc* desc, const float* p
                                const int* trans, const int* init, const int* dur, const int* dur_open, const int* lengths,
                                float* posterior, float* class_posterior, float* begin, double* log2_evidence,
                                double* dur_counts, void* workspace, long long workspace_bytes, void* stream);
+/* The chain with hold durations learned on the device (semi-Markov Baum-Welch): trans, init and dur fitted jointly to whole
+ * videos whose frames carry class probabilities only.  The expected counts under the chain's own posterior
+ * (qt_pose_duration_prior_expect), the hard counts of given segmentations (qt_pose_duration_prior_count_paths) and the new
+ * tables from the counts (qt_pose_duration_prior_update) are to the chain with durations what qt_pose_prior_expect /
+ * _count_paths / _update are to the plain one, whose tables do not fit here: there trans[j][j] means "stay one more frame",
+ * here it joins two segments of one step.  The reference has no such step.
+ * E-step.  The descriptor, probs, ld, state_class, trans, init, dur, dur_open (NULL: dur), lengths, their clamping, the limits,
+ * the emission integers and the levels Bt, Al, Be, Bs, Z are qt_pose_duration_posterior's, the same arithmetic in the same
+ * order.  Per stream of T frames (T = T_b):
+ *   xi_f[i][j]      = 2^(Al[f][i] + T[i][j] + Bs[f][j] - Z)         f = 1 .. T - 1
+ *                     P(a hold of i ends before frame f and a hold of j begins at f | the video)
+ *   trans_counts[i][j] += the sum over f = 1 .. T - 1 of xi_f[i][j]  (i == j included: two joined segments of one step)
+ *   xi_0[i][j]      = 2^(start[i] + T[i][j] + Bs[0][j] - Z)
+ *   start_counts[i] += the sum over j (ascending) of xi_0[i][j]
+ *   dur_counts[j][d - 1] += qt_pose_duration_posterior's rule, unchanged (the segments that the video does not cut)
+ *   totals[0] += Z;   totals[1] += T_b
+ * Consequences: sum_i xi_f[i][j] = begin[f][j] for f >= 1; sum_j xi_f[i][j] = endp[f][i]; sum_i start_counts[i] = 1 per
+ * stream; T = 1 adds zeros to trans_counts, T <= 2 adds zeros to dur_counts.
+ *   trans_counts double [S][S], required     start_counts double [S], or NULL
+ *   dur_counts   double [S][D], required     totals       double [2], required
+ * All are ADDED TO (the caller zeroes them once per E-step).  Precision follows the posterior's rule: the exponent of a term,
+ * (T[i][j] + Bs[f][j]) + (Al[f][i] - Z), is formed in double, rounded to f32, and 2^ taken in f32; every sum is a double.  The
+ * order of the additions is fixed: a stream's terms are added in descending f, every (i, j) and (j, d) slot by one lane of
+ * its own; the streams' partials are added in ascending stream order from zero by a second small launch, and that sum is added
+ * onto the accumulator.  No float atomics, no zero fill of caller memory, no host synchronisation; a stream alone gives the
+ * bits of that stream's partial in a batch, and every run the same bits.
+ * Contract with qt_pose_duration_posterior: on the same inputs dur_counts and every stream's Z are the BITS that it returns:
+ * both are one kernel, which here writes no posterior, begin or class rows and in its backward step also adds the xi of the
+ * candidates it visits anyway, with Al[f][i] from the workspace row of the forward sweep.
+ * qt_pose_duration_prior_workspace_bytes: 8 * (2 * batch * frames * S + batch * (S * S + S + S * D + 1)): the two level
+ * arrays and the streams' partials (8-byte aligned; every slot that is read is written in the same call); 0 for a descriptor
+ * that would be refused.  It serves qt_pose_duration_prior_count_paths too, which needs less.
+ * Hard counts, for path int64 [batch][frames] with row stride ld_path >= frames and start int64 in the same layout or NULL
+ * (qt_pose_duration_decode's two outputs, or labelled steps without start), lengths as above.  A segment begins at frame 0 and
+ * at every boundary f in 1 .. T_b - 1: with start the frames with start[f] == f (the decoder's segments: a join of one step
+ * with itself counts on the diagonal), without it the frames with path[f] != path[f - 1] (runs of labelled steps).
+ *   at a boundary with path[f - 1] and path[f] in [0, S):   trans_counts[path[f - 1]][path[f]] += 1
+ *   a segment [s, e) with s > 0 and e < T_b whose step j = path[s] is in [0, S):   dur_counts[j][min(e - s, D) - 1] += 1
+ *   start_counts[path[0]] += 1 where path[0] is in [0, S) (start_counts may be NULL);   totals[1] += T_b;   totals[0] is left alone
+ * An entry outside [0, S) ends a segment and counts nowhere; without start dur_counts is qt_pose_duration_count's.  Integer
+ * histograms per workgroup in LDS, added in int64 and then onto the doubles: exact, the same bits in any order.
+ * desc->num_classes is not read beyond its range check.
+ * M-step (one launch).  trans_out and init_out: qt_pose_prior_update's rule and code from trans_counts, start_counts, allowed
+ * and pseudo_count, bit for bit.  dur_allowed int32 [S][D], non-zero where a length may be learned.  For row j, in double:
+ *   r[d] = dur_allowed[j][d] ? dur_counts[j][d] + dur_pseudo_count : 0;   R = sum_d r[d], ascending
+ *   R > 0:   dur_out[j][d] = dur_allowed[j][d] ? q((float)(r[d] / R)) : -65536    (q: the emission score rule; a zero scores -8192)
+ *   otherwise the row keeps dur_in's values.
+ *   dur_open_out[j][d], where not NULL = max over d' >= d of dur_out[j][d']
+ * trans_out may be trans_in itself, init_out init_in itself, dur_out dur_in itself.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument): everything qt_pose_duration_posterior refuses
+ * of the descriptor, ld and the inputs (count_paths: ld_path < frames, a null path); a null trans_counts, dur_counts or
+ * totals; misaligned pointers (4 bytes for f32 and int32; 8 for double, int64 and the workspace); a workspace that is too
+ * small; an output that overlaps an input or another output.  qt_pose_duration_prior_update: what qt_pose_prior_update
+ * refuses, max_duration outside 1 .. 128, a dur_pseudo_count that is negative, NaN or infinite, a null dur_counts, dur_allowed,
+ * dur_in or dur_out.  QT_ERR_UNSUPPORTED for more than 2^20 frames in all. */
+long long qt_pose_duration_prior_workspace_bytes(const qt_pose_duration_desc* desc);
+int qt_pose_duration_prior_expect(const qt_pose_duration_desc* desc, const float* probs, long long ld, const int* state_class,
+                                  const int* trans, const int* init, const int* dur, const int* dur_open, const int* lengths,
+                                  double* trans_counts, double* start_counts, double* dur_counts, double* totals,
+                                  void* workspace, long long workspace_bytes, void* stream);
+int qt_pose_duration_prior_count_paths(const qt_pose_duration_desc* desc, const long long* path, const long long* start,
+                                       long long ld_path, const int* lengths, double* trans_counts, double* start_counts,
+                                       double* dur_counts, double* totals, void* workspace, long long workspace_bytes,
+                                       void* stream);
+int qt_pose_duration_prior_update(int num_states, int max_duration, const double* trans_counts, const double* start_counts,
+                                  const double* dur_counts, const int* allowed, const int* dur_allowed, double pseudo_count,
+                                  double dur_pseudo_count, const int* trans_in, const int* init_in, const int* dur_in,
+                                  int* trans_out, int* init_out, int* dur_out, int* dur_open_out, void* stream);
 /* Fixed-lag pose-order decoding with hold durations, for a loop that hands over a frame or a few per call: for the frame `lag`
  * frames ago, the state and the segment start that qt_pose_duration_decode would give on the stream up to now, at a cost per
  * step that does not grow with the video.  The reference has no such step.  probs, ld, state_class, trans, init, dur, dur_open

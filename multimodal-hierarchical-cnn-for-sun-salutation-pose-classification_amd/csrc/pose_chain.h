@@ -1,9 +1,10 @@
 // What the kernels of the pose-order chain share (pose_order.hip: the decoder and fixed-lag paths; pose_posterior.hip: the
 // posteriors, the learner's E-step and fixed-lag posteriors; pose_prior.hip: path counts and the M-step; pose_duration.hip,
-// pose_duration_lag.hip and pose_duration_posterior.hip: the best path, its fixed-lag form and the marginals of the chain with
-// hold durations): the limits, the emission rule q with its table and the loop that stages a tile's emissions, the chain's
-// inputs as one kernel-argument struct, the lane-group maximum, and on the host the descriptor checks, the fixed-lag route and
-// span, the overlap check and the S <= 16 template switch.
+// pose_duration_lag.hip, pose_duration_posterior.hip and pose_duration_prior.hip: the best path, its fixed-lag form, the
+// marginals and the learner of the chain with hold durations, the last two sharing pose_duration_sweep.h): the limits, the
+// emission rule q with its table and the loop that stages a tile's emissions, the chain's inputs as one kernel-argument struct,
+// the M-step of a row, the lane-group maximum, and on the host the descriptor checks, the fixed-lag route and span, the overlap
+// check and the S <= 16 template switch.
 // The build is not relocatable: every .hip that uses pc_q (pose_order.hip, pose_posterior.hip) has the table in its own code
 // object.
 #pragma once
@@ -91,6 +92,26 @@ __device__ __forceinline__ void pc_stage_emissions(const PcChain& a, int b, int 
     if ((unsigned)k < (unsigned)a.C) e = pc_q(p[(long long)f * a.ld + k]);
     pc_put(e_l, idx, e);
     if (out) out[idx] = e;
+  }
+}
+
+// the M-step of a row of transition (or start) scores (pose_prior.hip, pose_duration_prior.hip).  Row `src` of counts -> `dst`:
+// r[j] = allowed ? count + pseudo : 0, R = sum in ascending j; R > 0: rint(256 log2(r / R)) clamped to [-65536, 0] where r > 0
+// and -65536 elsewhere; otherwise the old values (zeros where there are none)
+__device__ __forceinline__ void pc_update_row(const double* __restrict__ src, const int* __restrict__ allowed, double pseudo,
+                                              const int* old, int* dst, int S) {
+  double R = 0.0;
+  for (int j = 0; j < S; ++j) R += (!allowed || allowed[j]) ? src[j] + pseudo : 0.0;
+  for (int j = 0; j < S; ++j) {
+    const double rj = (!allowed || allowed[j]) ? src[j] + pseudo : 0.0;
+    int v;
+    if (R > 0.0) {
+      v = PC_TRANS_FLOOR;
+      if (rj > 0.0) v = (int)fmin(fmax(rint(256.0 * log2(rj / R)), (double)PC_TRANS_FLOOR), 0.0);
+    } else {
+      v = old ? old[j] : 0;
+    }
+    dst[j] = v;
   }
 }
 

@@ -3,262 +3,15 @@
 // its table.  include/qtcnn.h states the rule in full; the reference has no such step.  pose_chain.h supplies the limits, the
 // emission rule, the chain's inputs PcChain, the descriptor and overlap checks and the S <= 16 switch.
 //
-// The walk is pose_duration.hip's: one workgroup of 256 per stream, a group of LPS lanes per state (16 for S <= 16, 4 above)
-// with the state's slices of dur and dur_open in registers (lane l the lengths d = 1 + l + k LPS), the emissions staged
-// PP_CHUNK frames at a time, the last D frames of history as a ring [D][S] in dynamic LDS.  A level (Bt, Al, Be, Bs, Z) is a
-// double: it falls by up to 288 bits a frame.  An L = log2 sum 2^x is a group maximum in double and then a group sum of the f32
-// terms 2^(x - m) over the same candidates, each lane its own in ascending order and the lanes by a butterfly, so the order
-// depends on S and D alone.  With cum[f][j] the exact int64 prefix sum of the emissions:
-//   forward, f = 1 .. T: the ring holds g[f][j] = Bt[f][j] - cum[f][j] / 256;
-//     (A) Al[f][j] = cum[f][j] / 256 + L_d (g[f - d][j] + len(j, d, f))                                             barrier
-//     (B) Bt[f][j] = L_i (Al[f][i] + T[i][j]); g[f] goes to ring row f mod D (row f - D was last read in (A))        barrier
-//     Al[f] and g[f] also go to the workspace as doubles; after f = T every thread forms Z = L_j Al[T][j] in ascending j.
-//   backward, f = T - 1 .. 0, after a barrier: the ring is reused for h[f][j] = Be[f][j] + cum[f][j] / 256, cum steps back
-//     through the emissions staged in descending chunks;
-//     (A') Lh = L_d (h[f + d][j] + len(j, d, f + d)), Bs[f][j] = Lh - cum[f][j] / 256; the state's owner lane forms
-//          begin[f][j] = 2^(g[f][j] + Lh - Z), endp[f + 1][j] from the workspace's Al row and the Be it kept, and steps occ;   barrier
-//     (B') Be[f][i] = L_j (T[i][j] + Bs[f][j]), h[f] to ring row f mod D (row f + D was last read in (A')); the owner sums
-//          R in ascending j and writes the posterior row; each lane adds the count terms of its own (j, d) slots at this f,
-//          2^(g[f - d][j] + Dur[j][d - 1] + h[f][j] - Z) with g from the workspace, into double registers;             barrier
-//     the class posterior of frame f + 1 is summed in (A') from the row that (B') left in LDS, the one of frame 0 after the walk.
-// A stream's [S][D] partial counts go to the workspace; pp_counts_kernel adds the streams' partials in ascending stream order,
-// from zero, onto dur_counts.  No workgroup waits for another, no atomics, no host synchronisation; every workspace slot that is
-// read has been written in the same call (a workgroup reads its own stores behind barriers).
-#include <float.h>
-#include <stdint.h>
-
+// The stream kernel, one workgroup per stream walking a forward and a backward sweep, is pose_duration_sweep.h's, which states
+// the walk; the learner's E-step (pose_duration_prior.hip) runs the same kernel in its second mode.  A stream's [S][D] partial
+// counts go to the workspace; pp_counts_kernel adds the streams' partials in ascending stream order, from zero, onto dur_counts.
+// No workgroup waits for another, no atomics, no host synchronisation; every workspace slot that is read has been written in
+// the same call (a workgroup reads its own stores behind barriers).
 #include "pose_chain.h"
+#include "pose_duration_sweep.h"
 
 namespace {
-
-constexpr int PP_THREADS = 256;
-constexpr int PP_CHUNK = 64;                     // frames of emissions staged at a time
-constexpr int PP_MAX_D = PC_MAX_D;
-static_assert((PP_CHUNK & (PP_CHUNK - 1)) == 0 && PP_MAX_D % 16 == 0, "chunk masks; lengths per lane");
-
-struct PpArgs : PcChain {    // T: the frames of the descriptor (tiles: not read)
-  const int* dur;
-  const int* dur_open;       // never null: dur where the caller gave none
-  const int* lengths;
-  float* posterior;
-  float* class_posterior;
-  float* begin;
-  double* evidence;
-  double* g;                 // workspace [batch][T][S]: g[f][j], f = 0 .. T - 1
-  double* al;                // workspace [batch][T][S]: Al[f][j] in row f - 1
-  double* part;              // workspace [batch][S][D]: a stream's expected counts; null without dur_counts
-  int D;
-};
-
-// the ring, two rows of doubles (a level; Bs), trans, state_class, a posterior row, the staged emissions
-inline size_t pp_lds_bytes(int S, int D) {
-  return 8 * ((size_t)D * S + 2 * S) + 4 * ((size_t)S * S + 2 * S) + 2 * (size_t)PP_CHUNK * S;
-}
-inline long long pp_level_elems(const qt_pose_duration_desc* d) { return (long long)d->batch * d->frames * d->num_states; }
-inline long long pp_workspace_bytes(const qt_pose_duration_desc* d) {
-  return 8 * (2 * pp_level_elems(d) + (long long)d->batch * d->num_states * d->max_duration);
-}
-
-template <int LPS>
-__device__ __forceinline__ double pp_group_max(double v) {
-#pragma unroll
-  for (int s = 1; s < LPS; s <<= 1) v = fmax(v, __shfl_xor(v, s, QT_WAVE));
-  return v;
-}
-// the butterfly: every lane of the group receives the same bits (a + b == b + a)
-template <int LPS>
-__device__ __forceinline__ float pp_group_sum(float v) {
-#pragma unroll
-  for (int s = 1; s < LPS; s <<= 1) v += __shfl_xor(v, s, QT_WAVE);
-  return v;
-}
-__device__ __forceinline__ double pp_bits(long long v) { return (double)v * 0x1p-8; }   // exact: |v| < 2^53
-__device__ __forceinline__ float pp_term(double x) { return exp2f((float)x); }
-
-template <bool SMALL>
-__global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
-  constexpr int LPS = SMALL ? 16 : 4;            // lanes per state
-  constexpr int KMAX = PP_MAX_D / LPS;           // lengths per lane
-  extern __shared__ __attribute__((aligned(16))) double pp_lds[];
-  const int S = a.S, C = a.C, D = a.D, tid = threadIdx.x, b = blockIdx.x;
-  double* ring = pp_lds;                                     // [D][S]: g, then h, of the last D frames, row f mod D
-  double* lev = ring + D * S;                                // [S]: start, Al[f]; backward: r = max(occ, 0)
-  double* vec = lev + S;                                     // [S]: Bs[f]
-  int* tr = reinterpret_cast<int*>(vec + S);                 // [S][S]
-  int* sc = tr + S * S;                                      // [S]
-  float* pst = reinterpret_cast<float*>(sc + S);             // [S]: the posterior row of the frame (B') last passed
-  short* e_l = reinterpret_cast<short*>(pst + S);            // [PP_CHUNK][S]
-  const int j = tid / LPS, l = tid - j * LPS, jj = min(j, S - 1);
-  const bool own = l == 0 && j < S;              // (groups beyond S compute on state S - 1 and store nothing)
-  int T = a.T;
-  if (a.lengths) T = min(max(a.lengths[b], 1), a.T);
-
-  int du[KMAX], dop[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    const int d0 = l + k * LPS;
-    du[k] = d0 < D ? pc_clamp_trans(a.dur[jj * D + d0]) : 0;
-    dop[k] = d0 < D ? pc_clamp_trans(a.dur_open[jj * D + d0]) : 0;
-  }
-  for (int idx = tid; idx < S * S; idx += PP_THREADS) tr[idx] = pc_clamp_trans(a.trans[idx]);
-  if (tid < S) {
-    lev[tid] = a.init ? pp_bits(pc_clamp_trans(a.init[tid])) : 0.0;
-    sc[tid] = a.state_class[tid];
-  }
-  __syncthreads();
-
-  // L over the group's share of `n` candidates x(i), i = l, l + LPS, ..: the maximum out in double, the terms and their sum f32
-  auto group_L = [&](int n, auto x) -> double {
-    double m = -DBL_MAX;
-    for (int i = l; i < n; i += LPS) m = fmax(m, x(i));
-    m = pp_group_max<LPS>(m);
-    float s = 0.0f;
-    for (int i = l; i < n; i += LPS) s += pp_term(x(i) - m);
-    return m + (double)log2f(pp_group_sum<LPS>(s));
-  };
-  // L over the state's lengths d = 1 .. dmax, the ring row of length d being row0 - d (forward) or row0 + d (backward)
-  auto length_L = [&](int dmax, int row0, bool forward, int d_cut, bool cut) -> double {
-    double x[KMAX];
-    double m = -DBL_MAX;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k * LPS >= dmax) break;                // (uniform)
-      const int d = 1 + l + k * LPS;
-      x[k] = -DBL_MAX;
-      if (d <= dmax) {
-        int r = forward ? row0 - d : row0 + d;
-        r += r < 0 ? D : (r >= D ? -D : 0);
-        x[k] = ring[r * S + jj] + pp_bits((cut || d == d_cut) ? dop[k] : du[k]);
-        m = fmax(m, x[k]);
-      }
-    }
-    m = pp_group_max<LPS>(m);
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k * LPS >= dmax) break;
-      if (1 + l + k * LPS <= dmax) s += pp_term(x[k] - m);
-    }
-    return m + (double)log2f(pp_group_sum<LPS>(s));
-  };
-
-  // ---- forward ---------------------------------------------------------------------------------------------------------------
-  const long long base = (long long)b * a.T * S;
-  double* __restrict__ gw = a.g + base;
-  double* __restrict__ alw = a.al + base;
-  long long cum = 0;
-  double bt = group_L(S, [&](int i) { return lev[i] + pp_bits(tr[i * S + jj]); });       // Bt[0]; cum[0] = 0
-  if (own) ring[j] = bt, gw[j] = bt;
-  int row = 0;
-  double Z = 0.0;
-  for (int f = 1; f <= T; ++f) {
-    const int g = f - 1;
-    if ((g & (PP_CHUNK - 1)) == 0) {             // (the chunk before was last read two barriers ago)
-      pc_stage_emissions(a, b, g, min(PP_CHUNK, T - g), e_l);
-      __syncthreads();
-    }
-    cum += e_l[(g & (PP_CHUNK - 1)) * S + jj];
-    row = row + 1 == D ? 0 : row + 1;            // f mod D
-    const double alv = length_L(min(D, f), row, true, f, f == T) + pp_bits(cum);
-    if (own) lev[j] = alv, alw[(long long)g * S + j] = alv;
-    __syncthreads();
-    if (f < T) {
-      bt = group_L(S, [&](int i) { return lev[i] + pp_bits(tr[i * S + jj]); });
-      if (own) {
-        const double gv = bt - pp_bits(cum);
-        ring[row * S + j] = gv;
-        gw[(long long)f * S + j] = gv;
-      }
-    } else {                                     // Z, by every thread, in ascending j
-      double m = lev[0];
-      for (int s = 1; s < S; ++s) m = fmax(m, lev[s]);
-      float sum = 0.0f;
-      for (int s = 0; s < S; ++s) sum += pp_term(lev[s] - m);
-      Z = m + (double)log2f(sum);
-      if (tid == 0 && a.evidence) a.evidence[b] = Z;
-    }
-    __syncthreads();
-  }
-
-  // ---- backward --------------------------------------------------------------------------------------------------------------
-  const bool rows_out = a.posterior || a.class_posterior;
-  const long long out_row = (long long)b * a.T;
-  // the class posterior of frame t from the posterior row in pst: ascending j, f32
-  auto class_row = [&](int t) {
-    if (a.class_posterior && tid < C) {
-      float s = 0.0f;
-      for (int i = 0; i < S; ++i)
-        if (sc[i] == tid) s += pst[i];
-      a.class_posterior[(out_row + t) * C + tid] = s;
-    }
-  };
-  double acc[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
-  if (own) ring[row * S + j] = pp_bits(cum);     // h[T] = cum[T] / 256: Be[T] = 0
-  double be_next = 0.0, occ = 0.0;               // Be[f + 1][j], occ[f + 1][j]
-  float begin_next = 0.0f;                       // begin[f + 1][j]
-  __syncthreads();
-  for (int f = T - 1; f >= 0; --f) {
-    if ((f & (PP_CHUNK - 1)) == PP_CHUNK - 1 || f == T - 1) {
-      const int f0 = f & ~(PP_CHUNK - 1);
-      pc_stage_emissions(a, b, f0, min(PP_CHUNK, T - f0), e_l);
-      __syncthreads();
-    }
-    if (f < T - 1) class_row(f + 1);
-    cum -= e_l[(f & (PP_CHUNK - 1)) * S + jj];   // cum[f]
-    row = row == 0 ? D - 1 : row - 1;            // f mod D
-    const double lh = length_L(min(D, T - f), row, false, T - f, f == 0);
-    if (own) {
-      const float bg = pp_term(gw[(long long)f * S + j] + lh - Z);            // Bt[f] + Bs[f] - Z: the cum terms cancel
-      const float ep = pp_term(alw[(long long)f * S + j] + be_next - Z);      // endp[f + 1]
-      occ = f == T - 1 ? (double)ep : occ + (double)ep - (double)begin_next;
-      begin_next = bg;
-      if (a.begin) a.begin[(out_row + f) * S + j] = bg;
-      vec[j] = lh - pp_bits(cum);
-      lev[j] = fmax(occ, 0.0);
-    }
-    __syncthreads();
-    double hv = 0.0;
-    if (f >= 1) {
-      be_next = group_L(S, [&](int i) { return pp_bits(tr[jj * S + i]) + vec[i]; });
-      hv = be_next + pp_bits(cum);
-      if (a.part && f >= 2) {                    // the uncut segments [f - d, f) of this state: f - d >= 1, f <= T - 1
-        const int dmax = min(D, f - 1);
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-          if (k * LPS >= dmax) break;
-          const int d = 1 + l + k * LPS;
-          if (d <= dmax) acc[k] += (double)pp_term(gw[(long long)(f - d) * S + jj] + pp_bits(du[k]) + hv - Z);
-        }
-      }
-      if (own) ring[row * S + j] = hv;
-    }
-    if (own && rows_out) {
-      double R = 0.0;
-      for (int i = 0; i < S; ++i) R += lev[i];
-      const float p = R > 0.0 ? (float)(lev[j] / R) : (float)(1.0 / S);
-      pst[j] = p;
-      if (a.posterior) a.posterior[(out_row + f) * S + j] = p;
-    }
-    __syncthreads();
-  }
-  class_row(0);
-
-  if (a.part && j < S) {
-    double* __restrict__ part = a.part + ((long long)b * S + j) * D;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (l + k * LPS < D) part[l + k * LPS] = acc[k];
-  }
-  // rows at and beyond the stream's length are zeros
-  for (int idx = T * S + tid; idx < a.T * S; idx += PP_THREADS) {
-    if (a.posterior) a.posterior[out_row * S + idx] = 0.0f;
-    if (a.begin) a.begin[out_row * S + idx] = 0.0f;
-  }
-  if (a.class_posterior)
-    for (int idx = T * C + tid; idx < a.T * C; idx += PP_THREADS) a.class_posterior[out_row * C + idx] = 0.0f;
-}
 
 // dur_counts[idx] += the streams' partials in ascending stream order, from zero
 __global__ __launch_bounds__(PP_THREADS) void pp_counts_kernel(const double* __restrict__ part, double* counts, int batch, int n) {
@@ -320,17 +73,18 @@ extern "C" int qt_pose_duration_posterior(const qt_pose_duration_desc* desc, con
   a.g = static_cast<double*>(workspace);
   a.al = a.g + pp_level_elems(desc);
   a.part = dur_counts ? a.al + pp_level_elems(desc) : nullptr;
+  a.xi_part = a.start_part = a.z_part = nullptr;
   a.D = D;
   const size_t lds = pp_lds_bytes(S, D);
   const bool small = S <= 16;
   static std::atomic<unsigned long long> raised[2] = {{0}, {0}};
   if (lds > 64 * 1024)
-    if (const int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(small ? pp_stream_kernel<true> : pp_stream_kernel<false>),
+    if (const int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(small ? pp_stream_kernel<true, false> : pp_stream_kernel<false, false>),
                                           (int)pp_lds_bytes(PC_MAX_S, PP_MAX_D), raised[small]))
       return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   pc_by_small(S, [&](auto sm) {
-    hipLaunchKernelGGL(pp_stream_kernel<PC_SMALL(sm)>, dim3((unsigned)B), dim3(PP_THREADS), lds, s, a);
+    hipLaunchKernelGGL((pp_stream_kernel<PC_SMALL(sm), false>), dim3((unsigned)B), dim3(PP_THREADS), lds, s, a);
   });
   QT_CHECK_LAUNCH();
   if (dur_counts) {

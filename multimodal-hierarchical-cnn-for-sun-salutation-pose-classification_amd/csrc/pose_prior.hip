@@ -8,7 +8,7 @@
 // exact integer, onto the double accumulator; the start counts are read off path[b][0] there.  No float atomics, no zero fill
 // of caller memory, no workgroup waits for another; every slot of the workspace that is read has been written in the same call.
 // update, one launch of one workgroup: thread i forms row i of the new table in double (log2 of the double library), thread S
-// the new init.
+// the new init, both by pose_chain.h's pc_update_row, which the learner of the chain with durations shares.
 #include <stdint.h>
 
 #include "pose_chain.h"
@@ -55,32 +55,13 @@ __global__ __launch_bounds__(PR_THREADS) void pr_count_reduce_kernel(const long 
   }
 }
 
-// row `src` of counts -> `dst`: r[j] = allowed ? count + pseudo : 0, R = sum in ascending j; R > 0: rint(256 log2(r / R)) clamped
-// to [-65536, 0] where r > 0 and -65536 elsewhere; otherwise the old values (zeros where there are none)
-__device__ void pr_row(const double* __restrict__ src, const int* __restrict__ allowed, double pseudo, const int* old, int* dst,
-                       int S) {
-  double R = 0.0;
-  for (int j = 0; j < S; ++j) R += (!allowed || allowed[j]) ? src[j] + pseudo : 0.0;
-  for (int j = 0; j < S; ++j) {
-    const double rj = (!allowed || allowed[j]) ? src[j] + pseudo : 0.0;
-    int v;
-    if (R > 0.0) {
-      v = PC_TRANS_FLOOR;
-      if (rj > 0.0) v = (int)fmin(fmax(rint(256.0 * log2(rj / R)), (double)PC_TRANS_FLOOR), 0.0);
-    } else {
-      v = old ? old[j] : 0;
-    }
-    dst[j] = v;
-  }
-}
-
 __global__ __launch_bounds__(2 * PC_MAX_S) void pr_update_kernel(const double* __restrict__ counts,
                                                                  const double* __restrict__ start_counts,
                                                                  const int* __restrict__ allowed, double pseudo, const int* trans_in,
                                                                  const int* init_in, int* trans_out, int* init_out, int S) {
   const int i = threadIdx.x;   // (a row is read and written by its own thread alone: trans_out may be trans_in)
-  if (i < S) pr_row(counts + i * S, allowed + i * S, pseudo, trans_in + i * S, trans_out + i * S, S);
-  else if (i == S && init_out) pr_row(start_counts, nullptr, pseudo, init_in, init_out, S);
+  if (i < S) pc_update_row(counts + i * S, allowed + i * S, pseudo, trans_in + i * S, trans_out + i * S, S);
+  else if (i == S && init_out) pc_update_row(start_counts, nullptr, pseudo, init_in, init_out, S);
 }
 
 }  // namespace

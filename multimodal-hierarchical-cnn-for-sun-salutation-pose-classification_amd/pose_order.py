@@ -112,10 +112,38 @@ stream may run for 2^36 frames); for any split of a stream into pushes, flush on
         held = first + torch.arange(lag_path.shape[1], device=device) - lag_start      # "held for n frames"
     first, lag_path, lag_start = livedur.push(rows[:, :0], flush=True, start=True)     # the last lag frames
 
-Not built for the chain with durations: fixed-lag posteriors with durations, expected transition counts and a full Baum-Welch
-learner over durations, D > 128, true minus infinity (a forbidden length is -65536).
+PoseDurationLearner (csrc/pose_duration_prior.hip) fits the tables that these three take, trans, init and dur jointly, to whole
+videos whose frames carry class probabilities only: Baum-Welch for the explicit-duration chain, on the device.  PoseOrderLearner's
+tables do not fit here: it learns the plain chain, where trans[j][j] means "stay one more frame", while here that entry joins two
+segments of one step.  The E-step is PoseDurationPosterior's kernel in a second mode (the same sweeps: its evidence and its
+expected duration counts are that kernel's bits), which in its backward step also sums xi_f[i][j], the probability that a hold of
+i ends and a hold of j begins at frame f, into float64 registers, one lane per entry, in a fixed order; a second small launch adds
+the videos' partials in order.  The M-step turns the three counts into int32 scores on the device (trans and init by
+PoseOrderLearner's rule, dur by `expected_duration_prior`'s, dur_open as the suffix maximum) and nothing is read back:
 
-Not built: ragged batches (per-sequence lengths) and videos split across calls in the learner, learning emissions (they are the
+    learner = PoseDurationLearner(state_class, trans, dur, device, dur_pseudo_count=0.01)    # the shapes to start from
+    for it in range(iterations):
+        learner.zero()
+        for probs, lengths in videos:             # f32 [B, n, C] and int32 [B] or None: ragged batches of whole videos
+            learner.accumulate(probs, lengths)    # E-step, nothing read back
+        learner.update()                          # M-step; learner.trans / .init / .dur / .dur_open are the new tables
+    bits, frames = learner.totals()               # the one host sync: evidence of the last E-step, frames seen
+    for user in (durdec, durpost, livedur):
+        user.load_tables(learner.trans, learner.init, learner.dur, learner.dur_open)    # device to device, no host sync
+
+`fit(videos, iterations)` is that loop, `accumulate_paths(path, start)` adds hard counts (PoseDurationDecoder.decode's path and
+start for Viterbi training: its segments, a join of one step with itself counting on the diagonal; or labelled steps without
+start: their runs), `tables()` returns numpy tables for saving.  An entry of trans or dur that starts at -65536 stays there.
+Start from a normalised dur (every row's 2^(dur / 256) summing to one, e.g. uniform at rint(-256 log2 D)): the evidence then
+compares across iterations from the first on.  If self-joins are not wanted, start with trans[j][j] = -65536: with an allowed
+diagonal a hold decomposes into one-frame segments joined by trans[j][j], which is the plain chain again, and the fitted dur says
+nothing.  On seeded tracks with holds of 9 frames (tests/test_pose_duration_prior_cpu.py) four iterations from a uniform dur
+raise the evidence at every step and move every step's most likely length to 9.
+
+Not built for the chain with durations: fixed-lag posteriors with durations, D > 128, true minus infinity (a forbidden length is
+-65536), videos split across calls in the learner.
+
+Not built: ragged batches (per-sequence lengths) and videos split across calls in PoseOrderLearner, learning emissions (they are the
 network's), tying rows, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second level of the
 posterior's scan; for the fixed-lag pair: sliding-window products that share work between neighbouring windows (f32 (L, +) is
 not associative: the split contract would break), a tiled forward pass, streams that advance by different counts.  There is no
@@ -231,6 +259,18 @@ def bind(L):
     L.qt_pose_duration_lag_decode.argtypes = [ctypes.POINTER(PoseDurationLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
         [ctypes.c_void_p] * 12 + [ctypes.c_longlong, ctypes.c_void_p]
     L.qt_pose_duration_lag_decode.restype = ctypes.c_int
+    L.qt_pose_duration_prior_workspace_bytes.argtypes = [ctypes.POINTER(PoseDurationDesc)]
+    L.qt_pose_duration_prior_workspace_bytes.restype = ctypes.c_longlong
+    L.qt_pose_duration_prior_expect.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 11 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_duration_prior_expect.restype = ctypes.c_int
+    L.qt_pose_duration_prior_count_paths.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_longlong] + [ctypes.c_void_p] * 6 + \
+        [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_duration_prior_count_paths.restype = ctypes.c_int
+    L.qt_pose_duration_prior_update.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + \
+        [ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 8
+    L.qt_pose_duration_prior_update.restype = ctypes.c_int
     L._pose_order_bound = True
     return L
 
@@ -563,6 +603,37 @@ class _PoseDurationTables(_PoseTables):
                 tuple(lengths.shape) != (B,):
             raise QtError(f"{what}: lengths must be an int32 tensor [{B}] on {self.device}")
         return lengths.detach().contiguous()
+
+    def load_tables(self, trans, init=None, dur=None, dur_open=None):
+        """a PoseDurationLearner's tables (int32 tensors on this device) copied into this object's own, device to device and
+        without a host sync.  init None: no init from here on; dur None: the current dur and dur_open stay; dur_open None with a
+        dur: dur itself scores the cut segments from here on.  An owner of streams starts them anew.  (Values are clamped by the
+        kernels as they are read: checking them here would need a host sync.)"""
+        who, S, D = f"{type(self).__name__}.load_tables", self.num_states, self.max_duration
+        if dur is None and dur_open is not None:
+            raise QtError(f"{who}: a dur_open without a dur")
+        for name, t, shape in (("trans", trans, (S, S)), ("init", init, (S,)), ("dur", dur, (S, D)), ("dur_open", dur_open, (S, D))):
+            if t is None and name != "trans":
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32 or tuple(t.shape) != shape:
+                raise QtError(f"{who}: {name} must be an int32 tensor {list(shape)} on {self.device}")
+        self.trans.copy_(trans)
+        if init is None:
+            self.init = None
+        elif self.init is None:
+            self.init = init.detach().clone().contiguous()
+        else:
+            self.init.copy_(init)
+        if dur is not None:
+            self.dur.copy_(dur)
+            if dur_open is None:
+                self.dur_open = None
+            elif self.dur_open is None:
+                self.dur_open = dur_open.detach().clone().contiguous()
+            else:
+                self.dur_open.copy_(dur_open)
+        reset = getattr(self, "reset", None)
+        return reset() if reset else self
 
 
 class PoseDurationDecoder(_PoseDurationTables):
@@ -1079,3 +1150,146 @@ class PoseOrderLearner(_PoseTables):
     def tables(self):
         """numpy (state_class int32 [S], trans int32 [S, S], init int32 [S] or None), for saving (a host sync)"""
         return (self.state_class.cpu().numpy(), self.trans.cpu().numpy(), None if self.init is None else self.init.cpu().numpy())
+
+
+def _check_pseudo(who, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) < float("inf"):
+        raise ValueError(f"{who}: {name} must be a finite number >= 0 (got {v!r})")
+    return float(v)
+
+
+class PoseDurationLearner(_PoseDurationTables):
+    """Baum-Welch for the chain with hold durations, on the device (csrc/pose_duration_prior.hip): trans, dur and, with
+    learn_init, the start scores fitted jointly to whole videos whose frames carry class probabilities only.  `accumulate` is the
+    E-step of one video or of a ragged batch (qt_pose_duration_prior_expect adds the expected transition, start and duration
+    counts onto float64 accumulators in a fixed order), `accumulate_paths` adds the hard counts of given segmentations, `update`
+    is the M-step.  Entries of the initial trans and dur at -65536 are forbidden and stay there; `pseudo_count` is added to
+    every allowed transition count, `dur_pseudo_count` to every allowed duration count.  dur_open "suffix_max": the M-step
+    rewrites dur_open on the device; a table of its own or None is left as given.  Nothing is read back but by `totals` and
+    `tables`.  See the module text."""
+
+    def __init__(self, state_class, trans, dur, device, init=None, dur_open="suffix_max", pseudo_count=0.0, dur_pseudo_count=1.0,
+                 learn_init=False, class_names=None):
+        who = type(self).__name__
+        self.learn_init = bool(learn_init)
+        self.pseudo_count = _check_pseudo(who, "pseudo_count", pseudo_count)
+        self.dur_pseudo_count = _check_pseudo(who, "dur_pseudo_count", dur_pseudo_count)
+        self._learn_open = isinstance(dur_open, str)
+        super().__init__(state_class, trans, dur, device, 1, init, dur_open, class_names)
+        S, D, device = self.num_states, self.max_duration, self.device
+        self.allowed = (self.trans > TRANS_FLOOR).to(torch.int32)
+        self.dur_allowed = (self.dur > TRANS_FLOOR).to(torch.int32)
+        self.counts = torch.zeros(S, S, dtype=torch.float64, device=device)
+        self.start_counts = torch.zeros(S, dtype=torch.float64, device=device)
+        self.dur_counts = torch.zeros(S, D, dtype=torch.float64, device=device)
+        self._totals = torch.zeros(2, dtype=torch.float64, device=device)
+
+    def _check_own(self, who, init, dur, dur_open):
+        init = super()._check_own(who, init, dur, dur_open)
+        if init is None and self.learn_init:
+            init = np.zeros(self.num_states, np.int32)          # the start vector of zeros, written out
+        return init
+
+    def zero(self):
+        """the accumulators to zero, before an E-step (no host sync)"""
+        self.counts.zero_(), self.start_counts.zero_(), self.dur_counts.zero_(), self._totals.zero_()
+        return self
+
+    def accumulate(self, probs, lengths=None):
+        """E-step of whole videos: probs f32 [B, n, C], or [n, C] for one, on the learner's device (predict's rows or the
+        timeline's smoothed rows); lengths int32 [B] on the device, or None when every video has n frames (a value outside
+        1 .. n is clamped into it).  Adds onto counts, start_counts, dur_counts and the totals; nothing is read back."""
+        what = "PoseDurationLearner.accumulate"
+        _check_probs_tensor(what, probs, self.device)
+        if probs.dim() == 2:
+            probs = probs.unsqueeze(0)
+        if probs.dim() != 3 or probs.shape[0] < 1 or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
+            raise QtError(f"{what}: probs must be [B, frames, C] or [frames, C] with B, frames >= 1 and C <= {MAX_CLASSES} "
+                          f"(got {list(probs.shape)})")
+        probs = _check_probs_rows(what, probs)
+        B, T, C = probs.shape
+        lengths = self._check_lengths(what, lengths, B)
+        desc = PoseDurationDesc(B, T, C, self.num_states, self.max_duration)
+        L = bind(_lib.lib())
+        ws, ws_bytes = self._room(L.qt_pose_duration_prior_workspace_bytes, desc)
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_duration_prior_expect(
+                ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class), _lib.ptr(self.trans),
+                _lib.ptr(self.init), _lib.ptr(self.dur), _lib.ptr(self.dur_open), _lib.ptr(lengths), _lib.ptr(self.counts),
+                _lib.ptr(self.start_counts), _lib.ptr(self.dur_counts), _lib.ptr(self._totals), ws, ws_bytes, _lib.stream_ptr()),
+                "qt_pose_duration_prior_expect")
+        return self
+
+    def accumulate_paths(self, path, start=None, lengths=None):
+        """hard counts: path int64 [B, n] or [n] on the learner's device, whole videos, and start int64 of the same shape or
+        None, lengths int32 [B] or None.  With start (PoseDurationDecoder.decode's) the segments are the decoder's, and two
+        segments of one step count on the diagonal of trans; without it they are the runs of path (labelled steps).  A step
+        outside 0 .. S - 1 (a label that is missing) counts nowhere.  The frames are counted, the evidence is not touched."""
+        what = "PoseDurationLearner.accumulate_paths"
+        for name, t in (("path", path), ("start", start)):
+            if t is None and name == "start":
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int64:
+                raise QtError(f"{what}: {name} must be an int64 tensor on {self.device}; there is no CPU or torch fallback")
+        if start is not None and start.shape != path.shape:
+            raise QtError(f"{what}: start {list(start.shape)} and path {list(path.shape)} do not belong together")
+        if path.dim() == 1:
+            path = path.unsqueeze(0)
+            start = None if start is None else start.unsqueeze(0)
+        if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] < 1:
+            raise QtError(f"{what}: path must be [B, frames] or [frames] with B, frames >= 1 (got {list(path.shape)})")
+        B, T = path.shape
+        if B * T > MAX_FRAMES:
+            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
+        lengths = self._check_lengths(what, lengths, B)
+        path = path.detach().contiguous()
+        start = None if start is None else start.detach().contiguous()
+        desc = PoseDurationDesc(B, T, 1, self.num_states, self.max_duration)
+        L = bind(_lib.lib())
+        ws, ws_bytes = self._room(L.qt_pose_duration_prior_workspace_bytes, desc)
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_duration_prior_count_paths(
+                ctypes.byref(desc), _lib.ptr(path), _lib.ptr(start), T, _lib.ptr(lengths), _lib.ptr(self.counts),
+                _lib.ptr(self.start_counts), _lib.ptr(self.dur_counts), _lib.ptr(self._totals), ws, ws_bytes, _lib.stream_ptr()),
+                "qt_pose_duration_prior_count_paths")
+        return self
+
+    def update(self):
+        """M-step on the device, in place: self.trans, self.dur (with learn_init self.init, with dur_open "suffix_max"
+        self.dur_open) are the new int32 tables"""
+        L = bind(_lib.lib())
+        init = self.init if self.learn_init else None
+        dur_open = self.dur_open if self._learn_open else None
+        with torch.cuda.device(self.device):
+            _lib.check(L.qt_pose_duration_prior_update(
+                self.num_states, self.max_duration, _lib.ptr(self.counts), _lib.ptr(self.start_counts), _lib.ptr(self.dur_counts),
+                _lib.ptr(self.allowed), _lib.ptr(self.dur_allowed), self.pseudo_count, self.dur_pseudo_count, _lib.ptr(self.trans),
+                _lib.ptr(init), _lib.ptr(self.dur), _lib.ptr(self.trans), _lib.ptr(init), _lib.ptr(self.dur), _lib.ptr(dur_open),
+                _lib.stream_ptr()), "qt_pose_duration_prior_update")
+        return self
+
+    def fit(self, videos, iterations):
+        """`iterations` rounds of zero / accumulate every video / update, with no host synchronisation; `videos` is a sequence
+        (it is walked once per round) whose items are probs (f32 [B, n, C] or [n, C]) or pairs (probs, lengths).  The
+        accumulators are left as the last E-step made them: `totals` gives the evidence under the tables BEFORE the last
+        update."""
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 0:
+            raise ValueError(f"PoseDurationLearner.fit: iterations must be an integer >= 0 (got {iterations!r})")
+        videos = [v if isinstance(v, (tuple, list)) else (v, None) for v in videos]
+        for _ in range(iterations):
+            self.zero()
+            for probs, lengths in videos:
+                self.accumulate(probs, lengths)
+            self.update()
+        return self
+
+    def totals(self):
+        """(evidence in bits, frames) of what has been accumulated since `zero`: the one host sync"""
+        bits, frames = self._totals.cpu().tolist()
+        return bits, int(frames)
+
+    def tables(self):
+        """numpy (state_class int32 [S], trans int32 [S, S], init int32 [S] or None, dur int32 [S, D], dur_open int32 [S, D] or
+        None), for saving (a host sync)"""
+        host = lambda t: None if t is None else t.cpu().numpy()
+        return (host(self.state_class), host(self.trans), host(self.init), host(self.dur), host(self.dur_open))
