@@ -1,10 +1,9 @@
 // What the kernels of the pose-order chain share (pose_order.hip: the decoder and fixed-lag paths; pose_posterior.hip: the
-// posteriors, the learner's E-step and fixed-lag posteriors; pose_prior.hip: path counts and the M-step; pose_duration.hip,
-// pose_duration_lag.hip, pose_duration_posterior.hip and pose_duration_prior.hip: the best path, its fixed-lag form, the
-// marginals and the learner of the chain with hold durations, the last two sharing pose_duration_sweep.h): the limits, the
-// emission rule q with its table and the loop that stages a tile's emissions, the chain's inputs as one kernel-argument struct,
-// the M-step of a row, the lane-group maximum, and on the host the descriptor checks, the fixed-lag route and span, the overlap
-// check and the S <= 16 template switch.
+// posteriors, the learner's E-step and fixed-lag posteriors; pose_prior.hip: path counts and the M-step; and, through
+// pose_duration_chain.h, which adds what the chain with hold durations alone needs, the pose_duration*.hip files): the limits,
+// the emission rule q with its table and the loop that stages a tile's emissions, the chain's inputs as one kernel-argument
+// struct, the M-step of a row, and on the host the descriptor checks, the fixed-lag route and span, the checks of an entry
+// point's buffers (nulls, alignment, workspace size, overlap) from one list and the S <= 16 template switch.
 // The build is not relocatable: every .hip that uses pc_q (pose_order.hip, pose_posterior.hip) has the table in its own code
 // object.
 #pragma once
@@ -115,18 +114,6 @@ __device__ __forceinline__ void pc_update_row(const double* __restrict__ src, co
   }
 }
 
-// (value, index) of the maximum over a group of LPS adjacent lanes, the lower index at equal values; every lane receives it
-// (pose_duration.hip, pose_duration_lag.hip)
-template <int LPS>
-__device__ __forceinline__ void pc_group_max(long long& v, int& k) {
-#pragma unroll
-  for (int s = 1; s < LPS; s <<= 1) {
-    const long long ov = __shfl_xor(v, s, QT_WAVE);
-    const int ok = __shfl_xor(k, s, QT_WAVE);
-    if (ov > v || (ov == v && ok < k)) v = ov, k = ok;
-  }
-}
-
 // ---- host -------------------------------------------------------------------------------------------------------------------
 inline int pc_check_desc(const char* who, const qt_pose_order_desc* d) {
   QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
@@ -141,18 +128,6 @@ inline int pc_check_desc(const char* who, const qt_pose_order_desc* d) {
     qt_set_error("%s: %lld frames in one call; at most %lld are handled", who, frames, PC_MAX_FRAMES);
     return QT_ERR_UNSUPPORTED;
   }
-  return QT_OK;
-}
-
-// the chain with hold durations (pose_duration.hip, pose_duration_posterior.hip): the chain's checks and the table's width
-constexpr int PC_MAX_D = 128;
-static_assert(PC_MAX_D == QT_POSE_DUR_MAX, "the header states this");
-inline int pc_duration_check_desc(const char* who, const qt_pose_duration_desc* d) {
-  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  const qt_pose_order_desc chain = {d->batch, d->frames, d->num_classes, d->num_states};
-  if (const int rc = pc_check_desc(who, &chain)) return rc;
-  QT_CHECK_ARG(d->max_duration >= 1 && d->max_duration <= PC_MAX_D, "%s: max_duration = %d; 1 .. %d are handled", who,
-               d->max_duration, PC_MAX_D);
   return QT_OK;
 }
 
@@ -196,34 +171,16 @@ inline PcSpan pc_lag_span(const qt_pose_lag_desc* d) {
   return s;
 }
 
-// the fixed-lag decoder with hold durations (pose_duration_lag.hip): the fixed-lag pair's descriptor with the table's width;
-// the scores are absolute int64, which bounds the frames of a stream
-constexpr long long PC_DUR_LAG_MAX_SEEN = 1LL << 36;
-inline qt_pose_lag_desc pc_duration_lag_as_lag(const qt_pose_duration_lag_desc* d) {
-  return {d->batch, d->frames, d->num_classes, d->num_states, d->lag, d->flush, d->seen};
-}
-inline int pc_duration_lag_check_desc(const char* who, const qt_pose_duration_lag_desc* d) {
-  QT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  const qt_pose_lag_desc lag = pc_duration_lag_as_lag(d);
-  const int rc = pc_lag_check_desc(who, &lag);
-  if (rc != QT_OK && rc != QT_ERR_UNSUPPORTED) return rc;
-  QT_CHECK_ARG(d->max_duration >= 1 && d->max_duration <= PC_MAX_D, "%s: max_duration = %d; 1 .. %d are handled", who,
-               d->max_duration, PC_MAX_D);
-  if (rc != QT_OK) return rc;
-  if (d->seen > PC_DUR_LAG_MAX_SEEN - d->frames) {
-    qt_set_error("%s: seen + frames = %lld + %d; a stream of at most %lld frames is handled", who, d->seen, d->frames,
-                 PC_DUR_LAG_MAX_SEEN);
-    return QT_ERR_UNSUPPORTED;
-  }
-  return QT_OK;
-}
-
-// no output may overlap an input or another output
+// a buffer of an entry point: its extent and name, the alignment its address must have (mask + 1 bytes) and whether it may
+// be null
 struct PcBuf {
   const void* p;
   size_t bytes;
   const char* name;
+  unsigned mask = 0;
+  bool required = false;
 };
+// no output may overlap an input or another output
 template <int N_IN, int N_OUT>
 inline int pc_check_disjoint(const char* who, const PcBuf (&in)[N_IN], const PcBuf (&out)[N_OUT]) {
   for (const PcBuf& o : out) {
@@ -233,6 +190,46 @@ inline int pc_check_disjoint(const char* who, const PcBuf (&in)[N_IN], const PcB
       QT_CHECK_ARG(&o == &o2 || !overlap(o.p, o.bytes, o2.p, o2.bytes), "%s: %s must not overlap %s", who, o.name, o2.name);
   }
   return QT_OK;
+}
+
+// The checks of an entry point's buffers from its two lists, in the order every entry point keeps: pc_check_present, the first
+// required buffer that is null (inputs, then outputs); then the entry's own conditions, spelled out at the site; then
+// pc_check_layout: the first misaligned buffer, the workspace's size, the overlaps (the pieces stand alone for an entry with a
+// condition of its own between them).  pc_check_bufs is the two in a row.
+struct PcRoom {                // the workspace: what the caller gave, what the call needs, and how the message states the need
+  const void* p;
+  long long bytes, need;
+  const char* asks;            // a format for `need`, e.g. "qt_..._workspace_bytes asks for %lld"
+};
+template <int N_IN, int N_OUT>
+inline int pc_check_present(const char* who, const PcBuf (&in)[N_IN], const PcBuf (&out)[N_OUT]) {
+  for (const PcBuf& i : in) QT_CHECK_ARG(i.p != nullptr || !i.required, "%s: null %s", who, i.name);
+  for (const PcBuf& o : out) QT_CHECK_ARG(o.p != nullptr || !o.required, "%s: null %s", who, o.name);
+  return QT_OK;
+}
+template <int N_IN, int N_OUT>
+inline int pc_check_aligned(const char* who, const PcBuf (&in)[N_IN], const PcBuf (&out)[N_OUT]) {
+  for (const PcBuf& i : in) QT_CHECK_ARG(!misaligned(i.p, i.mask), "%s: %s must be %u-byte aligned", who, i.name, i.mask + 1);
+  for (const PcBuf& o : out) QT_CHECK_ARG(!misaligned(o.p, o.mask), "%s: %s must be %u-byte aligned", who, o.name, o.mask + 1);
+  return QT_OK;
+}
+inline int pc_check_room(const char* who, const PcRoom& room) {
+  if (room.need == 0 || (room.p != nullptr && room.bytes >= room.need)) return QT_OK;
+  char asks[128];
+  snprintf(asks, sizeof asks, room.asks, room.need);
+  qt_set_error("%s: workspace of %lld bytes; %s", who, room.p ? room.bytes : 0LL, asks);
+  return QT_ERR_INVALID_ARG;
+}
+template <int N_IN, int N_OUT>
+inline int pc_check_layout(const char* who, const PcBuf (&in)[N_IN], const PcBuf (&out)[N_OUT], const PcRoom& room = {}) {
+  if (const int rc = pc_check_aligned(who, in, out)) return rc;
+  if (const int rc = pc_check_room(who, room)) return rc;
+  return pc_check_disjoint(who, in, out);
+}
+template <int N_IN, int N_OUT>
+inline int pc_check_bufs(const char* who, const PcBuf (&in)[N_IN], const PcBuf (&out)[N_OUT], const PcRoom& room = {}) {
+  if (const int rc = pc_check_present(who, in, out)) return rc;
+  return pc_check_layout(who, in, out, room);
 }
 
 // The kernels' SMALL switch (S <= 16: a lane's table entries in registers): calls f with std::true_type or std::false_type; the

@@ -1,11 +1,12 @@
 // Fixed-lag pose-order decoding with hold durations (qt_pose_duration_lag_decode): qt_pose_duration_decode's semi-Markov Viterbi
 // for a loop that hands over a frame or a few per call.  include/qtcnn.h states the rule in full; the reference has no such
-// step.  pose_chain.h supplies the limits PC_*, the emission rule, the chain's inputs PcChain, the lane-group maximum, the
-// descriptor check, the emitted span, the overlap check and the S <= 16 switch.
+// step.  pose_chain.h supplies the limits PC_*, the emission rule, the emitted span and the buffer checks;
+// pose_duration_chain.h the chain's inputs PcDurChain, the lane map with its register tables, the pieces of the walk, the
+// lane-group maximum, the descriptor check and the stream kernel's launch.
 //
 // The frame step is pd_stream_kernel's (pose_duration.hip): one workgroup of 256 per stream, a group of LPS lanes per state
 // with the state's slices of dur and dur_open in registers, the ring g[f][j] = beta[f][j] - cum[f][j] of the last D frames in
-// LDS (row f mod D), two barriers a frame, emissions staged PDL_CHUNK frames at a time.  What differs:
+// LDS (row f mod D), two barriers a frame, emissions staged PC_DUR_CHUNK frames at a time.  What differs:
 //   - the ring and cum come from carry_in (beta[0] at seen == 0) and leave through carry_out; f counts from the stream's start;
 //   - any frame may be the last one seen so far, so (A) takes two maxima over the same ring reads: the closed one (dur; dur_open
 //     only where the segment touches the stream's start), which feeds beta as for f < T of the whole-video decoder, and the
@@ -18,21 +19,16 @@
 // hist rows, from the workspace (the workgroup's own stores) at f > seen and from carry_in's hist at f <= seen; then the
 // workgroup writes carry_out in full.  One launch, one route: no workgroup waits for another, no atomics, no host
 // synchronisation; inputs, carry_in included, are never written; every workspace slot that is read is written in the same call.
-#include <limits.h>
 #include <stdint.h>
 
 #include "pose_chain.h"
+#include "pose_duration_chain.h"
 
 namespace {
 
-constexpr int PDL_THREADS = 256;
-constexpr int PDL_CHUNK = 64;                    // frames of emissions staged at a time
-static_assert(PC_MAX_D <= 128 && PC_MAX_S <= 64, "a hist or tail word is 7 + 6 bits");
 static_assert(PC_MAX_S <= QT_WAVE, "wave 0 takes the end state, lane = state");
 
-struct PdlArgs : PcChain {   // T: the new frames of the call (tiles: not read)
-  const int* dur;
-  const int* dur_open;       // never null: dur where the caller gave none
+struct PdlArgs : PcDurChain {   // T: the new frames of the call; lengths: null
   const char* carry_in;
   char* carry_out;
   long long* lag_path;
@@ -42,7 +38,7 @@ struct PdlArgs : PcChain {   // T: the new frames of the call (tiles: not read)
   unsigned short* ws_hist;   // workspace: [batch][n][S], row i: the hist word of frame f = seen + i + 1
   unsigned short* ws_tail;   //            [batch][n]: its tail word
   long long seen, g0, g1, carry_stride;
-  int D, lag, row0;          // row0: seen mod D
+  int lag, row0;             // row0: seen mod D
 };
 
 // a stream's carry: { int64 cum[S]; int64 g[D][S]; uint16 hist[lag][S]; uint16 tail }, rounded up to 8 bytes
@@ -65,7 +61,7 @@ __device__ __forceinline__ PdlCarry pdl_carry(const char* base, long long stride
 }
 
 inline size_t pdl_lds_bytes(int S, int D) {
-  return 8 * ((size_t)D * S + 2 * S) + 4 * ((size_t)S * S + S) + 2 * (size_t)PDL_CHUNK * S;
+  return 8 * ((size_t)D * S + 2 * S) + 4 * ((size_t)S * S + S) + 2 * (size_t)PC_DUR_CHUNK * S;
 }
 inline long long pdl_hist_bytes(const qt_pose_duration_lag_desc* d) {
   return ((long long)d->batch * d->frames * d->num_states * 2 + 7) / 8 * 8;
@@ -75,9 +71,8 @@ inline long long pdl_workspace_bytes(const qt_pose_duration_lag_desc* d) {
 }
 
 template <bool SMALL>
-__global__ __launch_bounds__(PDL_THREADS) void pdl_stream_kernel(PdlArgs a) {
-  constexpr int LPS = SMALL ? 16 : 4;            // lanes per state
-  constexpr int KMAX = PC_MAX_D / LPS;           // lengths per lane
+__global__ __launch_bounds__(PC_DUR_THREADS) void pdl_stream_kernel(PdlArgs a) {
+  constexpr int LPS = PC_DUR_LPS<SMALL>;
   extern __shared__ __attribute__((aligned(16))) long long pdl_lds[];
   const int S = a.S, D = a.D, lag = a.lag, n = a.T, tid = threadIdx.x, b = blockIdx.x;
   long long* ring = pdl_lds;                                 // [D][S]: g of the last D frames, row f mod D
@@ -85,43 +80,27 @@ __global__ __launch_bounds__(PDL_THREADS) void pdl_stream_kernel(PdlArgs a) {
   long long* alpha_o = alpha + S;                            // [S]: the open one
   int* tr = reinterpret_cast<int*>(alpha_o + S);             // [S][S]
   int* dlo = tr + S * S;                                     // [S]: dlen_open of the frame
-  short* e_l = reinterpret_cast<short*>(dlo + S);            // [PDL_CHUNK][S]
-  const int j = tid / LPS, l = tid - j * LPS, jj = min(j, S - 1);
-  const bool own = l == 0 && j < S;              // (groups beyond S compute on state S - 1 and store nothing)
+  short* e_l = reinterpret_cast<short*>(dlo + S);            // [PC_DUR_CHUNK][S]
+  const PcDurLane<LPS> ln(tid, S, D, a.dur, a.dur_open);
+  const int j = ln.j, l = ln.l, jj = ln.jj;
+  const bool own = ln.own;
   const bool two = a.dur_open != a.dur;          // (uniform)
   const long long seen = a.seen;
   const PdlCarry in = pdl_carry(a.carry_in, a.carry_stride, b, S, D, lag);
   const PdlCarry out = pdl_carry(a.carry_out, a.carry_stride, b, S, D, lag);
 
-  int du[KMAX], dop[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    const int d0 = l + k * LPS;
-    du[k] = d0 < D ? pc_clamp_trans(a.dur[jj * D + d0]) : 0;
-    dop[k] = d0 < D ? pc_clamp_trans(a.dur_open[jj * D + d0]) : 0;
-  }
-  for (int idx = tid; idx < S * S; idx += PDL_THREADS) tr[idx] = pc_clamp_trans(a.trans[idx]);
-
-  // (B): max_i (alpha[i] + trans[i][j]) and the lowest i that attains it
-  auto step_in = [&](long long& best, int& from) {
-    best = LLONG_MIN, from = INT_MAX;
-    for (int i = l; i < S; i += LPS) {
-      const long long v = alpha[i] + tr[i * S + jj];
-      if (v > best) best = v, from = i;
-    }
-    pc_group_max<LPS>(best, from);
-  };
+  pc_stage_trans(a.trans, tr, S);
 
   long long cum = 0, beta;
   int from;
   if (seen == 0) {                               // beta[0]: the scores before the first frame; cum[0] = 0; the other rows zero
-    for (int idx = tid; idx < D * S; idx += PDL_THREADS) ring[idx] = 0;
-    if (tid < S) alpha[tid] = a.init ? (long long)pc_clamp_trans(a.init[tid]) : 0;
+    for (int idx = tid; idx < D * S; idx += PC_DUR_THREADS) ring[idx] = 0;
+    if (tid < S) alpha[tid] = pc_init_score(a.init, tid);
     __syncthreads();
-    step_in(beta, from);
+    beta = pc_dur_step_in<LPS>(alpha, tr, S, l, jj, from);
     if (own) ring[j] = beta;
   } else {
-    for (int idx = tid; idx < D * S; idx += PDL_THREADS) ring[idx] = in.g[idx];
+    for (int idx = tid; idx < D * S; idx += PC_DUR_THREADS) ring[idx] = in.g[idx];
     cum = in.cum[jj];
   }
   __syncthreads();
@@ -132,31 +111,19 @@ __global__ __launch_bounds__(PDL_THREADS) void pdl_stream_kernel(PdlArgs a) {
   long long f = seen;
   for (int i = 0; i < n; ++i) {
     ++f;
-    if ((i & (PDL_CHUNK - 1)) == 0) {            // (the chunk before was last read two barriers ago)
-      pc_stage_emissions(a, b, i, min(PDL_CHUNK, n - i), e_l);
-      __syncthreads();
-    }
-    cum += e_l[(i & (PDL_CHUNK - 1)) * S + jj];
-    row = row + 1 == D ? 0 : row + 1;            // f mod D
-    const int dmax = (int)min((long long)D, f);
+    cum += pc_chunk_row(a, b, i, n, e_l, pc_chunk_start(i))[jj];
+    row = pc_ring_next(row, D);                  // f mod D
     long long best = LLONG_MIN, best_o = LLONG_MIN;
     int bd = INT_MAX, bd_o = INT_MAX;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k * LPS >= dmax) break;                // (uniform)
-      const int d = 1 + l + k * LPS;
-      if (d <= dmax) {
-        int r = row - d;
-        r += r < 0 ? D : 0;
-        const long long g = ring[r * S + jj];
-        const long long v = g + (d == f ? dop[k] : du[k]);
-        if (v > best) best = v, bd = d;
-        if (two) {
-          const long long vo = g + dop[k];
-          if (vo > best_o) best_o = vo, bd_o = d;
-        }
+    pc_for_lengths<LPS>((int)min((long long)D, f), l, [&](int k, int d) {
+      const long long g = ring[pc_ring_behind(row, d, D) * S + jj];
+      const long long v = g + (d == f ? ln.dop[k] : ln.du[k]);
+      if (v > best) best = v, bd = d;
+      if (two) {
+        const long long vo = g + ln.dop[k];
+        if (vo > best_o) best_o = vo, bd_o = d;
       }
-    }
+    });
     pc_group_max<LPS>(best, bd);
     if (two) pc_group_max<LPS>(best_o, bd_o);
     else best_o = best, bd_o = bd;
@@ -166,7 +133,7 @@ __global__ __launch_bounds__(PDL_THREADS) void pdl_stream_kernel(PdlArgs a) {
       dlo[j] = bd_o;
     }
     __syncthreads();
-    step_in(beta, from);
+    beta = pc_dur_step_in<LPS>(alpha, tr, S, l, jj, from);
     if (own) {
       ring[row * S + j] = beta - cum;            // (row f - D was last read in (A))
       hist[(long long)i * S + j] = (unsigned short)((bd - 1) | (from << 7));
@@ -186,7 +153,7 @@ __global__ __launch_bounds__(PDL_THREADS) void pdl_stream_kernel(PdlArgs a) {
 
   // the windows: thread = emitted frame.  The walk stays at g < f <= w whatever the words hold, and a state is clamped.
   const long long end = seen + n, last = end - 1, count = a.g1 - a.g0;
-  for (long long g = a.g0 + tid; g < a.g1; g += PDL_THREADS) {
+  for (long long g = a.g0 + tid; g < a.g1; g += PC_DUR_THREADS) {
     const long long w = g + lag < last ? g + lag : last;
     long long ff = w + 1;
     const unsigned t = ff > seen ? tail[ff - seen - 1] : *in.tail;
@@ -203,8 +170,8 @@ __global__ __launch_bounds__(PDL_THREADS) void pdl_stream_kernel(PdlArgs a) {
 
   // carry_out, in full: cum, the ring as it stands, hist of f = end - lag + 1 .. end (zeros for f <= 0), the tail, the padding
   if (own) out.cum[j] = cum;
-  for (int idx = tid; idx < D * S; idx += PDL_THREADS) out.g[idx] = ring[idx];
-  for (int idx = tid; idx < lag * S; idx += PDL_THREADS) {
+  for (int idx = tid; idx < D * S; idx += PC_DUR_THREADS) out.g[idx] = ring[idx];
+  for (int idx = tid; idx < lag * S; idx += PC_DUR_THREADS) {
     const int k = (int)fdiv((unsigned)idx, a.div_s);
     const long long fk = end - lag + 1 + k;
     unsigned short v = 0;
@@ -244,40 +211,26 @@ extern "C" int qt_pose_duration_lag_decode(const qt_pose_duration_lag_desc* desc
   const PcSpan span = pc_lag_span(&as_lag);
   const long long count = span.count;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
-  QT_CHECK_ARG((probs != nullptr || T == 0) && state_class != nullptr && trans != nullptr && dur != nullptr &&
-                   carry_out != nullptr,
-               "%s: null %s", who,
-               !probs && T ? "probs" : !state_class ? "state_class" : !trans ? "trans" : !dur ? "dur" : "carry_out");
+  const long long need = pdl_workspace_bytes(desc), stride = pdl_carry_stride(S, D, lag), rows = (long long)B * T;
+  const size_t carry_bytes = (size_t)(B * stride);
+  // carry_in is not read at seen == 0: it may be null there and overlaps nothing
+  const PcDurInputs in = pc_dur_inputs(probs, rows, ld, C, S, D, state_class, trans, init, dur, dur_open,
+                                       {carry_in, desc->seen ? carry_bytes : 0, "carry_in", 7});
+  const PcBuf out[] = {{carry_out, carry_bytes, "carry_out", 7, true}, {lag_path, (size_t)(B * count) * 8, "lag_path", 7},
+                       {lag_start, (size_t)(B * count) * 8, "lag_start", 7}, {filtered, (size_t)rows * 8, "filtered", 7},
+                       {score, (size_t)rows * 8, "score", 7}, {workspace, (size_t)need, "workspace", 7}};
+  if (const int rc = pc_check_present(who, in.v, out)) return rc;
   QT_CHECK_ARG(count == 0 || lag_path != nullptr, "%s: null lag_path (the call emits %lld frames)", who, count);
   QT_CHECK_ARG(desc->seen == 0 || carry_in != nullptr, "%s: null carry_in with seen = %lld", who, desc->seen);
-  QT_CHECK_ARG(!misaligned(probs, 3) && !misaligned(state_class, 3) && !misaligned(trans, 3) && !misaligned(init, 3) &&
-                   !misaligned(dur, 3) && !misaligned(dur_open, 3) && !misaligned(carry_in, 7) && !misaligned(carry_out, 7) &&
-                   !misaligned(lag_path, 7) && !misaligned(lag_start, 7) && !misaligned(filtered, 7) && !misaligned(score, 7) &&
-                   !misaligned(workspace, 7),
-               "%s: probs, state_class, trans, init, dur and dur_open must be 4-byte aligned, carry_in, carry_out, lag_path, "
-               "lag_start, filtered, score and the workspace 8-byte", who);
-  const long long need = pdl_workspace_bytes(desc);
-  QT_CHECK_ARG(need == 0 || (workspace != nullptr && workspace_bytes >= need),
-               "%s: workspace of %lld bytes; qt_pose_duration_lag_workspace_bytes asks for %lld", who,
-               workspace ? workspace_bytes : 0LL, need);
-  const long long stride = pdl_carry_stride(S, D, lag), rows = (long long)B * T;
-  const size_t carry_bytes = (size_t)(B * stride);
-  if (desc->seen == 0) carry_in = nullptr;   // not read
-  QT_CHECK_ARG(!overlap(carry_in, carry_bytes, carry_out, carry_bytes), "%s: carry_in must not overlap carry_out", who);
-  const PcBuf in[] = {{probs, rows ? (size_t)((rows - 1) * ld + C) * 4 : 0, "probs"},
-                      {state_class, (size_t)S * 4, "state_class"}, {trans, (size_t)S * S * 4, "trans"},
-                      {init, (size_t)S * 4, "init"}, {dur, (size_t)S * D * 4, "dur"},
-                      {dur_open, (size_t)S * D * 4, "dur_open"}, {carry_in, carry_bytes, "carry_in"}};
-  const PcBuf out[] = {{carry_out, carry_bytes, "carry_out"}, {lag_path, (size_t)(B * count) * 8, "lag_path"},
-                       {lag_start, (size_t)(B * count) * 8, "lag_start"}, {filtered, (size_t)rows * 8, "filtered"},
-                       {score, (size_t)rows * 8, "score"}, {workspace, (size_t)need, "workspace"}};
-  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
+  if (const int rc = pc_check_aligned(who, in.v, out)) return rc;
+  if (const int rc = pc_check_room(who, {workspace, workspace_bytes, need, "qt_pose_duration_lag_workspace_bytes asks for %lld"}))
+    return rc;
+  QT_CHECK_ARG(!overlap(carry_in, in.v[6].bytes, carry_out, carry_bytes), "%s: carry_in must not overlap carry_out", who);
+  if (const int rc = pc_check_disjoint(who, in.v, out)) return rc;
 
   PdlArgs a;
-  pc_fill(a, probs, ld, state_class, trans, init, T, C, S);
-  a.dur = dur;
-  a.dur_open = dur_open ? dur_open : dur;
-  a.carry_in = static_cast<const char*>(carry_in);
+  pc_dur_fill(a, probs, ld, state_class, trans, init, dur, dur_open, nullptr, T, C, S, D);
+  a.carry_in = desc->seen ? static_cast<const char*>(carry_in) : nullptr;
   a.carry_out = static_cast<char*>(carry_out);
   a.lag_path = lag_path;
   a.lag_start = lag_start;
@@ -289,20 +242,8 @@ extern "C" int qt_pose_duration_lag_decode(const qt_pose_duration_lag_desc* desc
   a.g0 = span.g0;
   a.g1 = span.g1;
   a.carry_stride = stride;
-  a.D = D;
   a.lag = lag;
   a.row0 = (int)(desc->seen % D);
-  const size_t lds = pdl_lds_bytes(S, D);
-  const bool small = S <= 16;
-  static std::atomic<unsigned long long> raised[2] = {{0}, {0}};
-  if (lds > 64 * 1024)
-    if (const int rc = qt_raise_lds_limit(reinterpret_cast<const void*>(small ? pdl_stream_kernel<true> : pdl_stream_kernel<false>),
-                                          (int)pdl_lds_bytes(PC_MAX_S, PC_MAX_D), raised[small]))
-      return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  pc_by_small(S, [&](auto sm) {
-    hipLaunchKernelGGL(pdl_stream_kernel<PC_SMALL(sm)>, dim3((unsigned)B), dim3(PDL_THREADS), lds, s, a);
-  });
-  QT_CHECK_LAUNCH();
-  return QT_OK;
+  return pc_launch_stream<pdl_stream_kernel<true>, pdl_stream_kernel<false>>(S, pdl_lds_bytes(S, D),
+                                                                            pdl_lds_bytes(PC_MAX_S, PC_MAX_D), B, stream, a);
 }

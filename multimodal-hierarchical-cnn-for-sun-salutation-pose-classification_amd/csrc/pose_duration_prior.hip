@@ -6,7 +6,8 @@
 // qt_pose_duration_posterior, so that Z and the duration counts are that function's bits; every (i, j) and (j, d) slot is owned
 // by one lane, a stream's terms are added in descending f into double registers and go to the workspace as the stream's
 // partials; (b) pq_reduce_kernel, one thread per slot, adds the streams' partials in ascending stream order from zero and adds
-// that sum onto the accumulator.  No float atomics, no zero fill of caller memory, no host synchronisation.
+// that sum onto the accumulator.  pose_chain.h supplies the buffer checks, pose_duration_chain.h the descriptor check, the
+// seven inputs as a list, a stream's length and the stream kernel's launch.  No float atomics, no zero fill of caller memory, no host synchronisation.
 // count_paths, two launches: (a) a workgroup of 256 per (stream, chunk of PQ_CHUNK frames) counts the boundaries and the uncut
 // segments that END in its chunk into int histograms [S][S] and [S][D] in LDS (integer atomics on LDS: the result does not
 // depend on their order) and writes them to the workspace; (b) one thread per slot adds the chunks of every stream in int64 and
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_reduce_kernel(const double* __r
     totals[0] += s;
   } else if (idx == SS + SD + S + 1) {
     long long n = 0;
-    for (int b = 0; b < batch; ++b) n += lengths ? min(max(lengths[b], 1), frames) : frames;
+    for (int b = 0; b < batch; ++b) n += pc_stream_length(lengths, b, frames);
     totals[1] += (double)n;
   }
 }
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_count_kernel(const long long* _
   extern __shared__ int pq_hist[];               // [S][S] transitions, then [S][D] durations
   const int n = S * S + S * D, tid = threadIdx.x;
   const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
-  const int T = lengths ? min(max(lengths[b], 1), frames) : frames;
+  const int T = pc_stream_length(lengths, b, frames);
   const int f0 = max(chunk * PQ_CHUNK, 1), f1 = min((chunk + 1) * PQ_CHUNK, T);
   for (int idx = tid; idx < n; idx += PQ_THREADS) pq_hist[idx] = 0;
   __syncthreads();
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_count_reduce_kernel(const long 
     for (int b = 0; b < batch; ++b) s += path[(long long)b * ld] == idx - n;
     start_counts[idx - n] += (double)s;
   } else if (idx == n + S) {
-    for (int b = 0; b < batch; ++b) s += lengths ? min(max(lengths[b], 1), frames) : frames;
+    for (int b = 0; b < batch; ++b) s += pc_stream_length(lengths, b, frames);
     totals[1] += (double)s;
   }
 }
@@ -168,34 +169,18 @@ extern "C" int qt_pose_duration_prior_expect(const qt_pose_duration_desc* desc, 
   if (const int rc = pc_duration_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, C = desc->num_classes, S = desc->num_states, D = desc->max_duration;
   QT_CHECK_ARG(ld >= C, "%s: row stride ld = %lld < C = %d", who, ld, C);
-  QT_CHECK_ARG(probs != nullptr && state_class != nullptr && trans != nullptr && dur != nullptr, "%s: null %s", who,
-               !probs ? "probs" : !state_class ? "state_class" : !trans ? "trans" : "dur");
-  QT_CHECK_ARG(trans_counts != nullptr && dur_counts != nullptr && totals != nullptr, "%s: null %s", who,
-               !trans_counts ? "trans_counts" : !dur_counts ? "dur_counts" : "totals");
-  QT_CHECK_ARG(!misaligned(probs, 3) && !misaligned(state_class, 3) && !misaligned(trans, 3) && !misaligned(init, 3) &&
-                   !misaligned(dur, 3) && !misaligned(dur_open, 3) && !misaligned(lengths, 3) && !misaligned(trans_counts, 7) &&
-                   !misaligned(start_counts, 7) && !misaligned(dur_counts, 7) && !misaligned(totals, 7) &&
-                   !misaligned(workspace, 7),
-               "%s: probs, state_class, trans, init, dur, dur_open and lengths must be 4-byte aligned, trans_counts, "
-               "start_counts, dur_counts, totals and the workspace 8-byte", who);
-  const long long need = pq_workspace_bytes(desc);
-  QT_CHECK_ARG(workspace != nullptr && workspace_bytes >= need,
-               "%s: workspace of %lld bytes; qt_pose_duration_prior_workspace_bytes asks for %lld", who,
-               workspace ? workspace_bytes : 0LL, need);
-  const long long rows = (long long)B * T;
-  const PcBuf in[] = {{probs, (size_t)((rows - 1) * ld + C) * 4, "probs"}, {state_class, (size_t)S * 4, "state_class"},
-                      {trans, (size_t)S * S * 4, "trans"}, {init, (size_t)S * 4, "init"}, {dur, (size_t)S * D * 4, "dur"},
-                      {dur_open, (size_t)S * D * 4, "dur_open"}, {lengths, (size_t)B * 4, "lengths"}};
-  const PcBuf out[] = {{trans_counts, (size_t)S * S * 8, "trans_counts"}, {start_counts, (size_t)S * 8, "start_counts"},
-                       {dur_counts, (size_t)S * D * 8, "dur_counts"}, {totals, 16, "totals"},
-                       {workspace, (size_t)need, "workspace"}};
-  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
+  const long long need = pq_workspace_bytes(desc), rows = (long long)B * T;
+  const PcDurInputs in =
+      pc_dur_inputs(probs, rows, ld, C, S, D, state_class, trans, init, dur, dur_open, {lengths, (size_t)B * 4, "lengths", 3});
+  const PcBuf out[] = {{trans_counts, (size_t)S * S * 8, "trans_counts", 7, true}, {start_counts, (size_t)S * 8, "start_counts", 7},
+                       {dur_counts, (size_t)S * D * 8, "dur_counts", 7, true}, {totals, 16, "totals", 7, true},
+                       {workspace, (size_t)need, "workspace", 7}};
+  if (const int rc = pc_check_bufs(who, in.v, out,
+                                   {workspace, workspace_bytes, need, "qt_pose_duration_prior_workspace_bytes asks for %lld"}))
+    return rc;
 
   PpArgs a;
-  pc_fill(a, probs, ld, state_class, trans, init, T, C, S);
-  a.dur = dur;
-  a.dur_open = dur_open ? dur_open : dur;
-  a.lengths = lengths;
+  pc_dur_fill(a, probs, ld, state_class, trans, init, dur, dur_open, lengths, T, C, S, D);
   a.posterior = a.class_posterior = a.begin = nullptr;
   a.evidence = nullptr;
   a.g = static_cast<double*>(workspace);
@@ -206,23 +191,12 @@ extern "C" int qt_pose_duration_prior_expect(const qt_pose_duration_desc* desc, 
   a.z_part = a.start_part + (long long)B * S;
   double* const start_part = a.start_part;
   if (!start_counts) a.start_part = nullptr;
-  a.D = D;
-  const size_t lds = pp_lds_bytes(S, D);
-  const bool small = S <= 16;
-  static std::atomic<unsigned long long> raised[2] = {{0}, {0}};
-  if (lds > 64 * 1024)
-    if (const int rc = qt_raise_lds_limit(
-            reinterpret_cast<const void*>(small ? pp_stream_kernel<true, true> : pp_stream_kernel<false, true>),
-            (int)pp_lds_bytes(PC_MAX_S, PP_MAX_D), raised[small]))
-      return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  pc_by_small(S, [&](auto sm) {
-    hipLaunchKernelGGL((pp_stream_kernel<PC_SMALL(sm), true>), dim3((unsigned)B), dim3(PP_THREADS), lds, s, a);
-  });
-  QT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(pq_reduce_kernel, dim3((unsigned)qt_cdiv(pq_part_elems(desc) + 1, PQ_THREADS)), dim3(PQ_THREADS), 0, s,
-                     (const double*)a.xi_part, (const double*)start_part, (const double*)a.part, (const double*)a.z_part, lengths,
-                     trans_counts, start_counts, dur_counts, totals, B, T, S, D);
+  if (const int rc = pc_launch_stream<pp_stream_kernel<true, true>, pp_stream_kernel<false, true>>(
+          S, pp_lds_bytes(S, D), pp_lds_bytes(PC_MAX_S, PC_MAX_D), B, stream, a))
+    return rc;
+  hipLaunchKernelGGL(pq_reduce_kernel, dim3((unsigned)qt_cdiv(pq_part_elems(desc) + 1, PQ_THREADS)), dim3(PQ_THREADS), 0,
+                     static_cast<hipStream_t>(stream), (const double*)a.xi_part, (const double*)start_part, (const double*)a.part,
+                     (const double*)a.z_part, lengths, trans_counts, start_counts, dur_counts, totals, B, T, S, D);
   QT_CHECK_LAUNCH();
   return QT_OK;
 }
@@ -235,23 +209,16 @@ extern "C" int qt_pose_duration_prior_count_paths(const qt_pose_duration_desc* d
   if (const int rc = pc_duration_check_desc(who, desc)) return rc;
   const int B = desc->batch, T = desc->frames, S = desc->num_states, D = desc->max_duration, chunks = qt_cdiv(T, PQ_CHUNK);
   QT_CHECK_ARG(ld_path >= T, "%s: row stride ld_path = %lld < frames = %d", who, ld_path, T);
-  QT_CHECK_ARG(path != nullptr && trans_counts != nullptr && dur_counts != nullptr && totals != nullptr, "%s: null %s", who,
-               !path ? "path" : !trans_counts ? "trans_counts" : !dur_counts ? "dur_counts" : "totals");
-  QT_CHECK_ARG(!misaligned(path, 7) && !misaligned(start, 7) && !misaligned(lengths, 3) && !misaligned(trans_counts, 7) &&
-                   !misaligned(start_counts, 7) && !misaligned(dur_counts, 7) && !misaligned(totals, 7) &&
-                   !misaligned(workspace, 7),
-               "%s: path, start, trans_counts, start_counts, dur_counts, totals and the workspace must be 8-byte aligned, "
-               "lengths 4-byte", who);
   const long long need = pq_count_workspace_bytes(desc);
-  QT_CHECK_ARG(workspace != nullptr && workspace_bytes >= need,
-               "%s: workspace of %lld bytes; %lld are needed (qt_pose_duration_prior_workspace_bytes asks for no less)", who,
-               workspace ? workspace_bytes : 0LL, need);
   const size_t pb = (size_t)((B - 1) * ld_path + T) * 8;
-  const PcBuf in[] = {{path, pb, "path"}, {start, pb, "start"}, {lengths, (size_t)B * 4, "lengths"}};
-  const PcBuf out[] = {{trans_counts, (size_t)S * S * 8, "trans_counts"}, {start_counts, (size_t)S * 8, "start_counts"},
-                       {dur_counts, (size_t)S * D * 8, "dur_counts"}, {totals, 16, "totals"},
-                       {workspace, (size_t)need, "workspace"}};
-  if (const int rc = pc_check_disjoint(who, in, out)) return rc;
+  const PcBuf in[] = {{path, pb, "path", 7, true}, {start, pb, "start", 7}, {lengths, (size_t)B * 4, "lengths", 3}};
+  const PcBuf out[] = {{trans_counts, (size_t)S * S * 8, "trans_counts", 7, true}, {start_counts, (size_t)S * 8, "start_counts", 7},
+                       {dur_counts, (size_t)S * D * 8, "dur_counts", 7, true}, {totals, 16, "totals", 7, true},
+                       {workspace, (size_t)need, "workspace", 7}};
+  if (const int rc = pc_check_bufs(who, in, out,
+                                   {workspace, workspace_bytes, need,
+                                    "%lld are needed (qt_pose_duration_prior_workspace_bytes asks for no less)"}))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int* partial = static_cast<int*>(workspace);
   const int n = S * S + S * D;

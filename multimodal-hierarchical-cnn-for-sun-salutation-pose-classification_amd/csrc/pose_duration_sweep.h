@@ -2,9 +2,10 @@
 // LEARN = false) and the learner's E-step (pose_duration_prior.hip, LEARN = true), so that both walk the very same forward and
 // backward sweeps: Z and the expected duration counts of the two are the same bits.  include/qtcnn.h states the rules in full.
 //
-// The walk is pose_duration.hip's: one workgroup of 256 per stream, a group of LPS lanes per state (16 for S <= 16, 4 above)
-// with the state's slices of dur and dur_open in registers (lane l the lengths d = 1 + l + k LPS), the emissions staged
-// PP_CHUNK frames at a time, the last D frames of history as a ring [D][S] in dynamic LDS.  A level (Bt, Al, Be, Bs, Z) is a
+// The walk is pose_duration.hip's, from the pieces of pose_duration_chain.h: one workgroup of 256 per stream, a group of LPS
+// lanes per state (16 for S <= 16, 4 above) with the state's slices of dur and dur_open in registers (lane l the lengths
+// d = 1 + l + k LPS), the emissions staged PC_DUR_CHUNK frames at a time, the last D frames of history as a ring [D][S] in
+// dynamic LDS.  A level (Bt, Al, Be, Bs, Z) is a
 // double: it falls by up to 288 bits a frame.  An L = log2 sum 2^x is a group maximum in double and then a group sum of the f32
 // terms 2^(x - m) over the same candidates, each lane its own in ascending order and the lanes by a butterfly, so the order
 // depends on S and D alone.  With cum[f][j] the exact int64 prefix sum of the emissions:
@@ -33,18 +34,11 @@
 #include <stdint.h>
 
 #include "pose_chain.h"
+#include "pose_duration_chain.h"
 
 namespace {
 
-constexpr int PP_THREADS = 256;
-constexpr int PP_CHUNK = 64;                     // frames of emissions staged at a time
-constexpr int PP_MAX_D = PC_MAX_D;
-static_assert((PP_CHUNK & (PP_CHUNK - 1)) == 0 && PP_MAX_D % 16 == 0, "chunk masks; lengths per lane");
-
-struct PpArgs : PcChain {    // T: the frames of the descriptor (tiles: not read)
-  const int* dur;
-  const int* dur_open;       // never null: dur where the caller gave none
-  const int* lengths;
+struct PpArgs : PcDurChain {   // T: the frames of the descriptor
   float* posterior;
   float* class_posterior;
   float* begin;
@@ -55,12 +49,11 @@ struct PpArgs : PcChain {    // T: the frames of the descriptor (tiles: not read
   double* xi_part;           // LEARN: workspace [batch][S][S], a stream's expected transition counts
   double* start_part;        // LEARN: workspace [batch][S], a stream's xi_0 row sums; null without start_counts
   double* z_part;            // LEARN: workspace [batch], a stream's Z
-  int D;
 };
 
 // the ring, two rows of doubles (a level; Bs), trans, state_class, a posterior row, the staged emissions
 inline size_t pp_lds_bytes(int S, int D) {
-  return 8 * ((size_t)D * S + 2 * S) + 4 * ((size_t)S * S + 2 * S) + 2 * (size_t)PP_CHUNK * S;
+  return 8 * ((size_t)D * S + 2 * S) + 4 * ((size_t)S * S + 2 * S) + 2 * (size_t)PC_DUR_CHUNK * S;
 }
 inline long long pp_level_elems(const qt_pose_duration_desc* d) { return (long long)d->batch * d->frames * d->num_states; }
 inline long long pp_workspace_bytes(const qt_pose_duration_desc* d) {
@@ -84,9 +77,9 @@ __device__ __forceinline__ double pp_bits(long long v) { return (double)v * 0x1p
 __device__ __forceinline__ float pp_term(double x) { return exp2f((float)x); }
 
 template <bool SMALL, bool LEARN>
-__global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
-  constexpr int LPS = SMALL ? 16 : 4;            // lanes per state
-  constexpr int KMAX = PP_MAX_D / LPS;           // lengths per lane
+__global__ __launch_bounds__(PC_DUR_THREADS) void pp_stream_kernel(PpArgs a) {
+  constexpr int LPS = PC_DUR_LPS<SMALL>;
+  constexpr int KMAX = PcDurLane<LPS>::KMAX;     // lengths per lane
   constexpr int XMAX = SMALL ? 1 : PC_MAX_S / LPS;   // LEARN: (i, j) slots per lane, j = l + k LPS
   extern __shared__ __attribute__((aligned(16))) double pp_lds[];
   const int S = a.S, C = a.C, D = a.D, tid = threadIdx.x, b = blockIdx.x;
@@ -96,22 +89,14 @@ __global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
   int* tr = reinterpret_cast<int*>(vec + S);                 // [S][S]
   int* sc = tr + S * S;                                      // [S]
   float* pst = reinterpret_cast<float*>(sc + S);             // [S]: the posterior row of the frame (B') last passed
-  short* e_l = reinterpret_cast<short*>(pst + S);            // [PP_CHUNK][S]
-  const int j = tid / LPS, l = tid - j * LPS, jj = min(j, S - 1);
-  const bool own = l == 0 && j < S;              // (groups beyond S compute on state S - 1 and store nothing)
-  int T = a.T;
-  if (a.lengths) T = min(max(a.lengths[b], 1), a.T);
-
-  int du[KMAX], dop[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    const int d0 = l + k * LPS;
-    du[k] = d0 < D ? pc_clamp_trans(a.dur[jj * D + d0]) : 0;
-    dop[k] = d0 < D ? pc_clamp_trans(a.dur_open[jj * D + d0]) : 0;
-  }
-  for (int idx = tid; idx < S * S; idx += PP_THREADS) tr[idx] = pc_clamp_trans(a.trans[idx]);
+  short* e_l = reinterpret_cast<short*>(pst + S);            // [PC_DUR_CHUNK][S]
+  const PcDurLane<LPS> ln(tid, S, D, a.dur, a.dur_open);
+  const int j = ln.j, l = ln.l, jj = ln.jj;
+  const bool own = ln.own;
+  const int T = pc_stream_length(a.lengths, b, a.T);
+  pc_stage_trans(a.trans, tr, S);
   if (tid < S) {
-    lev[tid] = a.init ? pp_bits(pc_clamp_trans(a.init[tid])) : 0.0;
+    lev[tid] = pp_bits(pc_init_score(a.init, tid));
     sc[tid] = a.state_class[tid];
   }
   __syncthreads();
@@ -129,25 +114,14 @@ __global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
   auto length_L = [&](int dmax, int row0, bool forward, int d_cut, bool cut) -> double {
     double x[KMAX];
     double m = -DBL_MAX;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k * LPS >= dmax) break;                // (uniform)
-      const int d = 1 + l + k * LPS;
-      x[k] = -DBL_MAX;
-      if (d <= dmax) {
-        int r = forward ? row0 - d : row0 + d;
-        r += r < 0 ? D : (r >= D ? -D : 0);
-        x[k] = ring[r * S + jj] + pp_bits((cut || d == d_cut) ? dop[k] : du[k]);
-        m = fmax(m, x[k]);
-      }
-    }
+    pc_for_lengths<LPS>(dmax, l, [&](int k, int d) {
+      const int r = pc_ring_wrap(forward ? row0 - d : row0 + d, D);
+      x[k] = ring[r * S + jj] + pp_bits((cut || d == d_cut) ? ln.dop[k] : ln.du[k]);
+      m = fmax(m, x[k]);
+    });
     m = pp_group_max<LPS>(m);
     float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k * LPS >= dmax) break;
-      if (1 + l + k * LPS <= dmax) s += pp_term(x[k] - m);
-    }
+    pc_for_lengths<LPS>(dmax, l, [&](int k, int) { s += pp_term(x[k] - m); });
     return m + (double)log2f(pp_group_sum<LPS>(s));
   };
 
@@ -162,12 +136,8 @@ __global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
   double Z = 0.0;
   for (int f = 1; f <= T; ++f) {
     const int g = f - 1;
-    if ((g & (PP_CHUNK - 1)) == 0) {             // (the chunk before was last read two barriers ago)
-      pc_stage_emissions(a, b, g, min(PP_CHUNK, T - g), e_l);
-      __syncthreads();
-    }
-    cum += e_l[(g & (PP_CHUNK - 1)) * S + jj];
-    row = row + 1 == D ? 0 : row + 1;            // f mod D
+    cum += pc_chunk_row(a, b, g, T, e_l, pc_chunk_start(g))[jj];
+    row = pc_ring_next(row, D);                  // f mod D
     const double alv = length_L(min(D, f), row, true, f, f == T) + pp_bits(cum);
     if (own) lev[j] = alv, alw[(long long)g * S + j] = alv;
     __syncthreads();
@@ -212,14 +182,10 @@ __global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
   float begin_next = 0.0f;                       // begin[f + 1][j]
   __syncthreads();
   for (int f = T - 1; f >= 0; --f) {
-    if ((f & (PP_CHUNK - 1)) == PP_CHUNK - 1 || f == T - 1) {
-      const int f0 = f & ~(PP_CHUNK - 1);
-      pc_stage_emissions(a, b, f0, min(PP_CHUNK, T - f0), e_l);
-      __syncthreads();
-    }
+    const short* e_f = pc_chunk_row(a, b, f, T, e_l, pc_chunk_start(f + 1) || f == T - 1);   // (descending: a chunk's last frame)
     if (f < T - 1) class_row(f + 1);
-    cum -= e_l[(f & (PP_CHUNK - 1)) * S + jj];   // cum[f]
-    row = row == 0 ? D - 1 : row - 1;            // f mod D
+    cum -= e_f[jj];                              // cum[f]
+    row = pc_ring_prev(row, D);                  // f mod D
     const double lh = length_L(min(D, T - f), row, false, T - f, f == 0);
     if constexpr (LEARN) {
       if (own) vec[j] = lh - pp_bits(cum);
@@ -238,12 +204,12 @@ __global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
       be_next = group_L(S, [&](int i) { return pp_bits(tr[jj * S + i]) + vec[i]; });
       hv = be_next + pp_bits(cum);
       if (a.part && f >= 2) {                    // the uncut segments [f - d, f) of this state: f - d >= 1, f <= T - 1
-        const int dmax = min(D, f - 1);
+        const int dmax = min(D, f - 1);          // (written out: through pc_for_lengths this loop costs two VGPRs at S <= 16)
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
           if (k * LPS >= dmax) break;
           const int d = 1 + l + k * LPS;
-          if (d <= dmax) acc[k] += (double)pp_term(gw[(long long)(f - d) * S + jj] + pp_bits(du[k]) + hv - Z);
+          if (d <= dmax) acc[k] += (double)pp_term(gw[(long long)(f - d) * S + jj] + pp_bits(ln.du[k]) + hv - Z);
         }
       }
       if (own) ring[row * S + j] = hv;
@@ -290,12 +256,12 @@ __global__ __launch_bounds__(PP_THREADS) void pp_stream_kernel(PpArgs a) {
       if (l + k * LPS < D) part[l + k * LPS] = acc[k];
   }
   // rows at and beyond the stream's length are zeros
-  for (int idx = T * S + tid; idx < a.T * S; idx += PP_THREADS) {
+  for (int idx = T * S + tid; idx < a.T * S; idx += PC_DUR_THREADS) {
     if (a.posterior) a.posterior[out_row * S + idx] = 0.0f;
     if (a.begin) a.begin[out_row * S + idx] = 0.0f;
   }
   if (a.class_posterior)
-    for (int idx = T * C + tid; idx < a.T * C; idx += PP_THREADS) a.class_posterior[out_row * C + idx] = 0.0f;
+    for (int idx = T * C + tid; idx < a.T * C; idx += PC_DUR_THREADS) a.class_posterior[out_row * C + idx] = 0.0f;
 }
 
 }  // namespace

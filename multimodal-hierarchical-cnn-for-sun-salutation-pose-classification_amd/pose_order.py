@@ -301,12 +301,39 @@ def prob_score(p):
     return int(out) if out.ndim == 0 else out
 
 
+def _int_in(who, name, v, lo, hi=None, numpy=True, what=None):
+    """v as an int where it is an integer (no bool; numpy's too where `numpy`) in lo .. hi (hi None: no upper bound); `what`
+    words the range where "an integer in lo .. hi" does not"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer) if numpy else int) or int(v) < lo or \
+            (hi is not None and int(v) > hi):
+        what = what or (f"an integer >= {lo}" if hi is None else f"an integer in {lo} .. {hi}")
+        raise ValueError(f"{who}: {name} must be {what} (got {v!r})")
+    return int(v)
+
+
+_DTYPE_NAMES = {torch.float32: "f32", torch.int32: "int32", torch.int64: "int64"}
+_NO_FALLBACK = "; there is no CPU or torch fallback"
+_NUMBERS = (int, float)
+
+
+def _check_device_tensor(what, name, t, device, dtype, shape=None, tail=""):
+    """t must be a tensor of `dtype` on `device` (and of `shape` where one is given)"""
+    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or \
+            (shape is not None and tuple(t.shape) != tuple(shape)):
+        dims = "" if shape is None else f" {list(shape)}"
+        raise QtError(f"{what}: {name} must be an {_DTYPE_NAMES[dtype]} tensor{dims} on {device}{tail}")
+
+
+def _check_pseudo(who, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) < float("inf"):
+        raise ValueError(f"{who}: {name} must be a finite number >= 0 (got {v!r})")
+    return float(v)
+
+
 def _score(name, v, optional=False):
     if v is None and optional:
         return None
-    if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)) or not TRANS_FLOOR <= int(v) <= 0:
-        raise ValueError(f"cyclic_prior: {name} must be an integer in {TRANS_FLOOR} .. 0 (got {v!r})")
-    return int(v)
+    return _int_in("cyclic_prior", name, v, TRANS_FLOOR, 0)
 
 
 def cyclic_prior(step_classes, stay, advance, skip=None, other=TRANS_FLOOR, wrap=True):
@@ -332,11 +359,7 @@ def cyclic_prior(step_classes, stay, advance, skip=None, other=TRANS_FLOOR, wrap
 
 
 def _dur_shape(who, S, D):
-    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) <= MAX_STATES:
-        raise ValueError(f"{who}: S must be an integer in 1 .. {MAX_STATES} (got {S!r})")
-    if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 1 <= int(D) <= DUR_MAX:
-        raise ValueError(f"{who}: D must be an integer in 1 .. {DUR_MAX} (got {D!r})")
-    return int(S), int(D)
+    return _int_in(who, "S", S, 1, MAX_STATES), _int_in(who, "D", D, 1, DUR_MAX)
 
 
 def duration_prior(counts, pseudo_count=1.0):
@@ -353,10 +376,7 @@ def duration_prior(counts, pseudo_count=1.0):
 
 def _counts_to_scores(who, counts, pseudo_count):
     """the rule both duration priors share: checked float64 counts [S, D] -> int32 scores"""
-    if isinstance(pseudo_count, bool) or not isinstance(pseudo_count, (int, float, np.integer, np.floating)) or \
-            not 0.0 <= float(pseudo_count) < float("inf"):
-        raise ValueError(f"{who}: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
-    r = counts + float(pseudo_count)
+    r = counts + _check_pseudo(who, "pseudo_count", pseudo_count)
     with np.errstate(divide="ignore", invalid="ignore"):
         p = (r / r.sum(axis=1, keepdims=True)).astype(np.float32)
     return prob_score(p).astype(np.int32)
@@ -379,9 +399,7 @@ def expected_duration_prior(counts, pseudo_count=1.0):
 def hold_prior(S, D, shortest, longest, inside=0, outside=TRANS_FLOOR):
     """dur int32 [S, D] of the simple box: `inside` for shortest <= d <= longest, `outside` for every other length"""
     S, D = _dur_shape("hold_prior", S, D)
-    for name, v in (("shortest", shortest), ("longest", longest)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
-            raise ValueError(f"hold_prior: {name} must be an integer >= 1 (got {v!r})")
+    shortest, longest = _int_in("hold_prior", "shortest", shortest, 1), _int_in("hold_prior", "longest", longest, 1)
     if shortest > longest:
         raise ValueError(f"hold_prior: shortest = {shortest} > longest = {longest}")
     inside, outside = _score("inside", inside), _score("outside", outside)
@@ -431,6 +449,17 @@ class _PoseTables:
             self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
         return (_lib.ptr(self._workspace), self._workspace.numel()) if need else (None, 0)
 
+    def _call(self, name, desc, *args, workspace=None):
+        """the entry point `name` on this object's device and torch's current stream: `desc` (a descriptor, passed by
+        reference, or the leading number of an entry point without one), then `args` (tensors as their addresses, None and
+        numbers as they are), then, where `workspace` names the size query, the workspace and its size, then the stream"""
+        L = bind(_lib.lib())
+        room = self._room(getattr(L, workspace), desc) if workspace else ()
+        args = [a if a is None or a.__class__ in _NUMBERS else a.data_ptr() for a in args]   # (this runs once per live frame)
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(L, name)(desc if desc.__class__ is int else ctypes.byref(desc), *args, *room, _lib.stream_ptr()),
+                       name)
+
     def _check_probs(self, what, probs, allow_empty=False):
         """probs f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device -> (probs as
         [streams, frames, C] with rows the kernels can walk, flat, frames, C)"""
@@ -455,20 +484,69 @@ class _PoseStreams(_PoseTables):
         """a learner's tables (int32 tensors on this device) copied into this object's own, device to device and without a host
         sync; every stream starts anew.  init None: no init from here on.  (Values are clamped by the kernels as they are read:
         checking them here would need a host sync.)"""
-        who, S = f"{type(self).__name__}.load_tables", self.num_states
-        for name, t, shape in (("trans", trans, (S, S)), ("init", init, (S,))):
-            if t is None and name == "init":
-                continue
-            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32 or tuple(t.shape) != shape:
-                raise QtError(f"{who}: {name} must be an int32 tensor {list(shape)} on {self.device}")
-        self.trans.copy_(trans)
-        if init is None:
-            self.init = None
-        elif self.init is None:
-            self.init = init.detach().clone().contiguous()
-        else:
-            self.init.copy_(init)
+        S = self.num_states
+        _load_tables(self, f"{type(self).__name__}.load_tables", (("trans", trans, (S, S)), ("init", init, (S,))))
         return self.reset()
+
+
+def _replace_optional(current, new):
+    """an optional table after a load: None for `new` None, a copy of its own where there was none, else copied in place"""
+    if new is None:
+        return None
+    if current is None:
+        return new.detach().clone().contiguous()
+    current.copy_(new)
+    return current
+
+
+def _load_tables(self, who, specs):
+    """checks `specs`, (name, int32 tensor on this device or None, shape) with trans first (required) and init second, and
+    copies those two into the object's own"""
+    for name, t, shape in specs:
+        if t is not None or name == "trans":
+            _check_device_tensor(who, name, t, self.device, torch.int32, shape)
+    self.trans.copy_(specs[0][1])
+    self.init = _replace_optional(self.init, specs[1][1])
+
+
+def _cycles(who, self, path, wrap_from, wrap_to, before=None):
+    """how often `path` goes from wrap_from to wrap_to between adjacent frames, `before` [streams] standing in front of it"""
+    S, B = self.num_states, self.streams
+    wrap_from = S - 1 if wrap_from is None else wrap_from
+    for name, v in (("wrap_from", wrap_from), ("wrap_to", wrap_to)):
+        _int_in(who, name, v, 0, S - 1, numpy=False, what=f"a state 0 .. {S - 1}")
+    _check_device_tensor(who, "path", path, self.device, torch.int64)
+    if path.dim() == 1 and B == 1:
+        path = path.unsqueeze(0)
+    if path.dim() != 2 or path.shape[0] != B or path.shape[1] < 1:
+        raise QtError(f"{who}: path must be [{B}, frames] (got {list(path.shape)})")
+    if before is None:
+        return ((path[:, :-1] == wrap_from) & (path[:, 1:] == wrap_to)).sum(dim=1)
+    return ((torch.cat([before[:, None], path[:, :-1]], dim=1) == wrap_from) & (path == wrap_to)).sum(dim=1)
+
+
+def _confidence(who, self, rows, path, rows_name, path_name, pad=False):
+    """`rows` f32 [..., S] at the states of `path` int64 [...]; pad: 0 where path is -1"""
+    _check_device_tensor(who, rows_name, rows, self.device, torch.float32)
+    _check_device_tensor(who, path_name, path, self.device, torch.int64)
+    if rows.shape[:-1] != path.shape or rows.shape[-1] != self.num_states:
+        raise QtError(f"{who}: {rows_name} {list(rows.shape)} and {path_name} {list(path.shape)} do not belong together "
+                      f"({self.num_states} states)")
+    if not pad:
+        return rows.gather(-1, path.unsqueeze(-1)).squeeze(-1)
+    at = rows.gather(-1, path.clamp_min(0).unsqueeze(-1)).squeeze(-1)
+    return torch.where(path >= 0, at, torch.zeros_like(at))
+
+
+def _path_batch(what, path):
+    """a checked int64 tensor as [B, frames] with B, frames >= 1, within the frame limit"""
+    if path.dim() == 1:
+        path = path.unsqueeze(0)
+    if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] < 1:
+        raise QtError(f"{what}: path must be [B, frames] or [frames] with B, frames >= 1 (got {list(path.shape)})")
+    if path.shape[0] * path.shape[1] > MAX_FRAMES:
+        raise QtError(f"{what}: {path.shape[0] * path.shape[1]} frames; at most {MAX_FRAMES} are handled in one call")
+    return path
 
 
 def _check_probs_tensor(what, probs, device):
@@ -523,14 +601,8 @@ class PoseOrderDecoder(_PoseStreams):
         path = torch.empty(lead, dtype=torch.int64, device=dev)
         filt = torch.empty(lead, dtype=torch.int64, device=dev) if filtered else None
         emis = torch.empty(lead + (S,), dtype=torch.int32, device=dev) if emissions else None
-        desc = PoseOrderDesc(B, T, C, S)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_order_workspace_bytes, desc)
-        with torch.cuda.device(dev):
-            _lib.check(L.qt_pose_order_decode(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
-                                              _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.carry), _lib.ptr(path),
-                                              _lib.ptr(filt), _lib.ptr(emis), ws, ws_bytes, _lib.stream_ptr()),
-                       "qt_pose_order_decode")
+        self._call("qt_pose_order_decode", PoseOrderDesc(B, T, C, S), probs, probs.stride(1), self.state_class, self.trans,
+                   self.init, self.carry, path, filt, emis, workspace="qt_pose_order_workspace_bytes")
         self._before, self._last = self._last, path.view(B, T)[:, -1].clone()
         out = (path, self._state_class64[path])
         if filtered:
@@ -544,19 +616,7 @@ class PoseOrderDecoder(_PoseStreams):
         goes from state wrap_from (default S - 1) to state wrap_to between adjacent frames.  `decode` keeps the last state of
         the call before it, so with the latest decode's path a wrap that falls on the call boundary is counted: call it once
         per decode.  Plain torch."""
-        S, B = self.num_states, self.streams
-        wrap_from = S - 1 if wrap_from is None else wrap_from
-        for name, v in (("wrap_from", wrap_from), ("wrap_to", wrap_to)):
-            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < S:
-                raise ValueError(f"PoseOrderDecoder.cycles: {name} must be a state 0 .. {S - 1} (got {v!r})")
-        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
-            raise QtError(f"PoseOrderDecoder.cycles: path must be an int64 tensor on {self.device}")
-        if path.dim() == 1 and B == 1:
-            path = path.unsqueeze(0)
-        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < 1:
-            raise QtError(f"PoseOrderDecoder.cycles: path must be [{B}, frames] (got {list(path.shape)})")
-        before = torch.cat([self._before[:, None], path[:, :-1]], dim=1)
-        return ((before == wrap_from) & (path == wrap_to)).sum(dim=1)
+        return _cycles("PoseOrderDecoder.cycles", self, path, wrap_from, wrap_to, self._before)
 
 
 class _PoseDurationTables(_PoseTables):
@@ -596,12 +656,14 @@ class _PoseDurationTables(_PoseTables):
         self._dur_host = (dur, dur_open)
         return init
 
+    def _tables(self):
+        """the five tables in the order every stream entry point takes them"""
+        return self.state_class, self.trans, self.init, self.dur, self.dur_open
+
     def _check_lengths(self, what, lengths, B):
         if lengths is None:
             return None
-        if not isinstance(lengths, torch.Tensor) or lengths.device != self.device or lengths.dtype != torch.int32 or \
-                tuple(lengths.shape) != (B,):
-            raise QtError(f"{what}: lengths must be an int32 tensor [{B}] on {self.device}")
+        _check_device_tensor(what, "lengths", lengths, self.device, torch.int32, (B,))
         return lengths.detach().contiguous()
 
     def load_tables(self, trans, init=None, dur=None, dur_open=None):
@@ -612,26 +674,10 @@ class _PoseDurationTables(_PoseTables):
         who, S, D = f"{type(self).__name__}.load_tables", self.num_states, self.max_duration
         if dur is None and dur_open is not None:
             raise QtError(f"{who}: a dur_open without a dur")
-        for name, t, shape in (("trans", trans, (S, S)), ("init", init, (S,)), ("dur", dur, (S, D)), ("dur_open", dur_open, (S, D))):
-            if t is None and name != "trans":
-                continue
-            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32 or tuple(t.shape) != shape:
-                raise QtError(f"{who}: {name} must be an int32 tensor {list(shape)} on {self.device}")
-        self.trans.copy_(trans)
-        if init is None:
-            self.init = None
-        elif self.init is None:
-            self.init = init.detach().clone().contiguous()
-        else:
-            self.init.copy_(init)
+        _load_tables(self, who, (("trans", trans, (S, S)), ("init", init, (S,)), ("dur", dur, (S, D)), ("dur_open", dur_open, (S, D))))
         if dur is not None:
             self.dur.copy_(dur)
-            if dur_open is None:
-                self.dur_open = None
-            elif self.dur_open is None:
-                self.dur_open = dur_open.detach().clone().contiguous()
-            else:
-                self.dur_open.copy_(dur_open)
+            self.dur_open = _replace_optional(self.dur_open, dur_open)
         reset = getattr(self, "reset", None)
         return reset() if reset else self
 
@@ -661,14 +707,8 @@ class PoseDurationDecoder(_PoseDurationTables):
         path = torch.empty(lead, dtype=torch.int64, device=dev)
         first = torch.empty(lead, dtype=torch.int64, device=dev) if start else None
         best = torch.empty(B, dtype=torch.int64, device=dev) if score else None
-        desc = PoseDurationDesc(B, T, C, S, self.max_duration)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_duration_workspace_bytes, desc)
-        with torch.cuda.device(dev):
-            _lib.check(L.qt_pose_duration_decode(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
-                                                 _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.dur),
-                                                 _lib.ptr(self.dur_open), _lib.ptr(lengths), _lib.ptr(path), _lib.ptr(first),
-                                                 _lib.ptr(best), ws, ws_bytes, _lib.stream_ptr()), "qt_pose_duration_decode")
+        self._call("qt_pose_duration_decode", PoseDurationDesc(B, T, C, S, self.max_duration), probs, probs.stride(1),
+                   *self._tables(), lengths, path, first, best, workspace="qt_pose_duration_workspace_bytes")
         path_class = torch.where(path >= 0, self._state_class64[path.clamp_min(0)], path)
         return (path, path_class) + tuple(t for t in (first, best) if t is not None)
 
@@ -676,18 +716,7 @@ class PoseDurationDecoder(_PoseDurationTables):
         """int64 [streams], on the device and without a host sync: how often `path` (a decode's, [streams, frames] or [frames])
         goes from state wrap_from (default S - 1) to state wrap_to between adjacent frames; whole videos, so nothing is kept
         between calls.  Plain torch."""
-        S, B = self.num_states, self.streams
-        wrap_from = S - 1 if wrap_from is None else wrap_from
-        for name, v in (("wrap_from", wrap_from), ("wrap_to", wrap_to)):
-            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < S:
-                raise ValueError(f"PoseDurationDecoder.cycles: {name} must be a state 0 .. {S - 1} (got {v!r})")
-        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
-            raise QtError(f"PoseDurationDecoder.cycles: path must be an int64 tensor on {self.device}")
-        if path.dim() == 1 and B == 1:
-            path = path.unsqueeze(0)
-        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < 1:
-            raise QtError(f"PoseDurationDecoder.cycles: path must be [{B}, frames] (got {list(path.shape)})")
-        return ((path[:, :-1] == wrap_from) & (path[:, 1:] == wrap_to)).sum(dim=1)
+        return _cycles("PoseDurationDecoder.cycles", self, path, wrap_from, wrap_to)
 
     def count_durations(self, path, lengths=None):
         """int64 [S, D] on the device: the run lengths of state paths, for `duration_prior`.  path: int64 [B, n] or [n] on the
@@ -696,25 +725,15 @@ class PoseDurationDecoder(_PoseDurationTables):
         outside 0 .. S - 1 ends a run and counts nowhere.  Counts of further batches add up (integers)."""
         what = "PoseDurationDecoder.count_durations"
         S, D = self.num_states, self.max_duration
-        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
-            raise QtError(f"{what}: path must be an int64 tensor on {self.device}; there is no CPU or torch fallback")
-        if path.dim() == 1:
-            path = path.unsqueeze(0)
-        if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] < 1:
-            raise QtError(f"{what}: path must be [B, frames] or [frames] with B, frames >= 1 (got {list(path.shape)})")
+        _check_device_tensor(what, "path", path, self.device, torch.int64, tail=_NO_FALLBACK)
+        path = _path_batch(what, path)
         B, T = path.shape
-        if B * T > MAX_FRAMES:
-            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
         lengths = self._check_lengths(what, lengths, B)
         path = path.detach()
         if path.stride(1) != 1 or (B > 1 and path.stride(0) < T):
             path = path.contiguous()
         out = torch.zeros(S, D, dtype=torch.int64, device=self.device)
-        desc = PoseDurationDesc(B, T, 1, S, D)
-        L = bind(_lib.lib())
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_duration_count(ctypes.byref(desc), _lib.ptr(path), path.stride(0) if B > 1 else T,
-                                                _lib.ptr(lengths), _lib.ptr(out), _lib.stream_ptr()), "qt_pose_duration_count")
+        self._call("qt_pose_duration_count", PoseDurationDesc(B, T, 1, S, D), path, path.stride(0) if B > 1 else T, lengths, out)
         return out
 
 
@@ -735,8 +754,7 @@ def _check_tables(who, state_class, trans, init, streams, class_names):
         init = np.asarray(init)
         if init.shape != (S,) or init.dtype.kind not in "iu" or (init < TRANS_FLOOR).any() or (init > 0).any():
             raise ValueError(f"{who}: init must be [{S}] integers in {TRANS_FLOOR} .. 0")
-    if isinstance(streams, bool) or not isinstance(streams, int) or not 1 <= streams <= MAX_FRAMES:
-        raise ValueError(f"{who}: streams must be an integer in 1 .. {MAX_FRAMES} (got {streams!r})")
+    _int_in(who, "streams", streams, 1, MAX_FRAMES, numpy=False)
     if class_names is not None:
         class_names = [str(c) for c in class_names]
         if len(class_names) <= int(sc.max()):
@@ -772,28 +790,15 @@ class PosePosterior(_PoseStreams):
         filt = torch.empty(lead + (S,), dtype=torch.float32, device=dev) if filtered else None
         cls = torch.empty(lead + (C,), dtype=torch.float32, device=dev) if by_class else None
         ev = torch.empty(B, dtype=torch.float64, device=dev) if evidence else None
-        desc = PoseOrderDesc(B, T, C, S)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_posterior_workspace_bytes, desc)
-        with torch.cuda.device(dev):
-            _lib.check(L.qt_pose_posterior(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
-                                           _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.carry), _lib.ptr(post),
-                                           _lib.ptr(filt), _lib.ptr(cls), _lib.ptr(ev), ws, ws_bytes, _lib.stream_ptr()),
-                       "qt_pose_posterior")
+        self._call("qt_pose_posterior", PoseOrderDesc(B, T, C, S), probs, probs.stride(1), self.state_class, self.trans, self.init,
+                   self.carry, post, filt, cls, ev, workspace="qt_pose_posterior_workspace_bytes")
         out = (post,) + tuple(t for t in (filt, cls, ev) if t is not None)
         return out[0] if len(out) == 1 else out
 
     def confidence(self, posterior, path):
         """f32 [streams, frames] (or [frames]): the posterior at the states of `path` (a decode's, int64), which is what
         FrameAnnotator.draw takes as `confidence` beside the path's class.  Plain torch, nothing read back."""
-        if not isinstance(posterior, torch.Tensor) or posterior.device != self.device or posterior.dtype != torch.float32:
-            raise QtError(f"PosePosterior.confidence: posterior must be an f32 tensor on {self.device}")
-        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
-            raise QtError(f"PosePosterior.confidence: path must be an int64 tensor on {self.device}")
-        if posterior.shape[:-1] != path.shape or posterior.shape[-1] != self.num_states:
-            raise QtError(f"PosePosterior.confidence: posterior {list(posterior.shape)} and path {list(path.shape)} do not "
-                          f"belong together ({self.num_states} states)")
-        return posterior.gather(-1, path.unsqueeze(-1)).squeeze(-1)
+        return _confidence("PosePosterior.confidence", self, posterior, path, "posterior", "path")
 
 
 class PoseDurationPosterior(_PoseDurationTables):
@@ -812,16 +817,9 @@ class PoseDurationPosterior(_PoseDurationTables):
 
     def _run(self, what, probs, lengths, post, cls, begin, ev, counts):
         B, T, C = probs.shape
-        desc = PoseDurationDesc(B, T, C, self.num_states, self.max_duration)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_duration_posterior_workspace_bytes, desc)
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_duration_posterior(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1),
-                                                    _lib.ptr(self.state_class), _lib.ptr(self.trans), _lib.ptr(self.init),
-                                                    _lib.ptr(self.dur), _lib.ptr(self.dur_open), _lib.ptr(lengths),
-                                                    _lib.ptr(post), _lib.ptr(cls), _lib.ptr(begin), _lib.ptr(ev),
-                                                    _lib.ptr(counts), ws, ws_bytes, _lib.stream_ptr()),
-                       "qt_pose_duration_posterior")
+        self._call("qt_pose_duration_posterior", PoseDurationDesc(B, T, C, self.num_states, self.max_duration), probs,
+                   probs.stride(1), *self._tables(), lengths, post, cls, begin, ev, counts,
+                   workspace="qt_pose_duration_posterior_workspace_bytes")
 
     def smooth(self, probs, lengths=None, by_class=False, begin=False, evidence=False):
         """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device, whole videos;
@@ -847,23 +845,13 @@ class PoseDurationPosterior(_PoseDurationTables):
     def confidence(self, posterior, path):
         """f32 [streams, frames] (or [frames]): the posterior at the states of `path` (PoseDurationDecoder.decode's, int64),
         0 where path is -1 (beyond a video's end).  Plain torch, nothing read back."""
-        who = "PoseDurationPosterior.confidence"
-        if not isinstance(posterior, torch.Tensor) or posterior.device != self.device or posterior.dtype != torch.float32:
-            raise QtError(f"{who}: posterior must be an f32 tensor on {self.device}")
-        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
-            raise QtError(f"{who}: path must be an int64 tensor on {self.device}")
-        if posterior.shape[:-1] != path.shape or posterior.shape[-1] != self.num_states:
-            raise QtError(f"{who}: posterior {list(posterior.shape)} and path {list(path.shape)} do not belong together "
-                          f"({self.num_states} states)")
-        at = posterior.gather(-1, path.clamp_min(0).unsqueeze(-1)).squeeze(-1)
-        return torch.where(path >= 0, at, torch.zeros_like(at))
+        return _confidence("PoseDurationPosterior.confidence", self, posterior, path, "posterior", "path", pad=True)
 
     def holds(self, begin):
         """float64 [streams, S]: the sum of `begin` (a smooth's, [streams, frames, S] or [frames, S]) over the frames, the
         expected number of holds of every step, and so of rounds.  Plain torch, nothing read back."""
         who = "PoseDurationPosterior.holds"
-        if not isinstance(begin, torch.Tensor) or begin.device != self.device or begin.dtype != torch.float32:
-            raise QtError(f"{who}: begin must be an f32 tensor on {self.device}")
+        _check_device_tensor(who, "begin", begin, self.device, torch.float32)
         if begin.dim() == 2 and self.streams == 1:
             begin = begin.unsqueeze(0)
         if begin.dim() != 3 or begin.shape[0] != self.streams or begin.shape[2] != self.num_states:
@@ -882,42 +870,56 @@ class PoseDurationPosterior(_PoseDurationTables):
 
 
 def _check_lag(who, lag):
-    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
-        raise ValueError(f"{who}: lag must be an integer in 0 .. {LAG_MAX} (got {lag!r})")
+    _int_in(who, "lag", lag, 0, LAG_MAX)
 
 
-class _PoseLag(_PoseStreams):
-    """what PoseLagSmoother and PoseLagDecoder share: the tables, the count of frames seen (on the host: all streams advance
-    together), the two carry buffers that are swapped after every push, and a workspace that grows on demand"""
-    _carry_query = None
+class _LagState:
+    """what the fixed-lag objects share beside their tables: the lag, the count of frames seen (on the host: all streams advance
+    together) and the two carry buffers that are swapped after every push"""
     _empty_with_flush = True
 
-    def __init__(self, state_class, trans, device, lag, streams=1, init=None, class_names=None):
-        super().__init__(state_class, trans, device, streams, init, class_names, lag=lag)
+    def _lag_init(self, lag, carry_query, desc):
+        """desc: the descriptor of one frame, which `carry_query` takes"""
         self.lag, self.seen = int(lag), 0
-        desc = PoseLagDesc(streams, 1, 1, self.num_states, self.lag, 0, 0)
-        nbytes = int(getattr(bind(_lib.lib()), self._carry_query)(ctypes.byref(desc)))
+        nbytes = int(getattr(bind(_lib.lib()), carry_query)(ctypes.byref(desc)))
         self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]  # [0]: the next call's carry_in
-
-    def _check_own(self, who, init, lag):
-        _check_lag(who, lag)
-        return init
 
     def reset(self):
         """every stream starts anew (no host sync; the carry is not read at a stream's first frame)"""
         self.seen = 0
         return self
 
-    def _probs(self, what, probs, flush):
-        probs, flat, T, C = self._check_probs(what, probs, allow_empty=flush)
+    def _span(self, T, flush):
+        """(first, count) of the frames that a push of T frames emits"""
         first = max(0, self.seen - self.lag)
-        count = (self.seen + T if flush else max(0, self.seen + T - self.lag)) - first
-        desc = PoseLagDesc(self.streams, T, C, self.num_states, self.lag, int(bool(flush)), self.seen)
-        return probs, flat, T, C, first, count, desc
+        return first, (self.seen + T if flush else max(0, self.seen + T - self.lag)) - first
+
+    def _carries(self):
+        """(carry_in or None at a stream's start, carry_out)"""
+        return (self._carry[0] if self.seen else None), self._carry[1]
 
     def _advance(self, T):
         self.seen += T
         self._carry.reverse()
+
+
+class _PoseLag(_LagState, _PoseStreams):
+    """what PoseLagSmoother and PoseLagDecoder share: the tables, the fixed-lag state and a workspace that grows on demand"""
+    _carry_query = None
+
+    def __init__(self, state_class, trans, device, lag, streams=1, init=None, class_names=None):
+        super().__init__(state_class, trans, device, streams, init, class_names, lag=lag)
+        self._lag_init(lag, self._carry_query, PoseLagDesc(streams, 1, 1, self.num_states, int(lag), 0, 0))
+
+    def _check_own(self, who, init, lag):
+        _check_lag(who, lag)
+        return init
+
+    def _probs(self, what, probs, flush):
+        probs, flat, T, C = self._check_probs(what, probs, allow_empty=flush)
+        first, count = self._span(T, flush)
+        desc = PoseLagDesc(self.streams, T, C, self.num_states, self.lag, int(bool(flush)), self.seen)
+        return probs, flat, T, C, first, count, desc
 
 
 class PoseLagSmoother(_PoseLag):
@@ -937,29 +939,16 @@ class PoseLagSmoother(_PoseLag):
         lagged = torch.empty(lead(count) + (S,), dtype=torch.float32, device=dev)
         cls = torch.empty(lead(count) + (C,), dtype=torch.float32, device=dev) if by_class else None
         filt = torch.empty(lead(T) + (S,), dtype=torch.float32, device=dev) if filtered else None
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_lag_smooth_workspace_bytes, desc)
-        with torch.cuda.device(dev):
-            _lib.check(L.qt_pose_lag_smooth(ctypes.byref(desc), _lib.ptr(probs) if T else None, probs.stride(1) if T else C,
-                                            _lib.ptr(self.state_class), _lib.ptr(self.trans), _lib.ptr(self.init),
-                                            _lib.ptr(self._carry[0]) if self.seen else None, _lib.ptr(self._carry[1]),
-                                            _lib.ptr(lagged) if count else None, _lib.ptr(cls) if count else None,
-                                            _lib.ptr(filt) if T else None, None, ws, ws_bytes, _lib.stream_ptr()),
-                       "qt_pose_lag_smooth")
+        self._call("qt_pose_lag_smooth", desc, probs if T else None, probs.stride(1) if T else C, self.state_class, self.trans,
+                   self.init, *self._carries(), lagged if count else None, cls if count else None, filt if T else None, None,
+                   workspace="qt_pose_lag_smooth_workspace_bytes")
         self._advance(T)
         return (first, lagged) + tuple(t for t in (cls, filt) if t is not None)
 
     def confidence(self, lagged, lag_path):
         """f32 [streams, count] (or [count]): the lagged posterior at the states of `lag_path` (a PoseLagDecoder's push of the
         same frames, int64).  Plain torch, nothing read back."""
-        if not isinstance(lagged, torch.Tensor) or lagged.device != self.device or lagged.dtype != torch.float32:
-            raise QtError(f"PoseLagSmoother.confidence: lagged must be an f32 tensor on {self.device}")
-        if not isinstance(lag_path, torch.Tensor) or lag_path.device != self.device or lag_path.dtype != torch.int64:
-            raise QtError(f"PoseLagSmoother.confidence: lag_path must be an int64 tensor on {self.device}")
-        if lagged.shape[:-1] != lag_path.shape or lagged.shape[-1] != self.num_states:
-            raise QtError(f"PoseLagSmoother.confidence: lagged {list(lagged.shape)} and lag_path {list(lag_path.shape)} do not "
-                          f"belong together ({self.num_states} states)")
-        return lagged.gather(-1, lag_path.unsqueeze(-1)).squeeze(-1)
+        return _confidence("PoseLagSmoother.confidence", self, lagged, lag_path, "lagged", "lag_path")
 
 
 class PoseLagDecoder(_PoseLag):
@@ -976,37 +965,24 @@ class PoseLagDecoder(_PoseLag):
         lead = (lambda n: (n,)) if flat else (lambda n: (B, n))
         path = torch.empty(lead(count), dtype=torch.int64, device=dev)
         filt = torch.empty(lead(T), dtype=torch.int64, device=dev) if filtered else None
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_lag_decode_workspace_bytes, desc)
-        with torch.cuda.device(dev):
-            _lib.check(L.qt_pose_lag_decode(ctypes.byref(desc), _lib.ptr(probs) if T else None, probs.stride(1) if T else C,
-                                            _lib.ptr(self.state_class), _lib.ptr(self.trans), _lib.ptr(self.init),
-                                            _lib.ptr(self._carry[0]) if self.seen else None, _lib.ptr(self._carry[1]),
-                                            _lib.ptr(path) if count else None, _lib.ptr(filt) if T else None, ws, ws_bytes,
-                                            _lib.stream_ptr()), "qt_pose_lag_decode")
+        self._call("qt_pose_lag_decode", desc, probs if T else None, probs.stride(1) if T else C, self.state_class, self.trans,
+                   self.init, *self._carries(), path if count else None, filt if T else None,
+                   workspace="qt_pose_lag_decode_workspace_bytes")
         self._advance(T)
         return (first, path) + ((filt,) if filtered else ())
 
 
-class PoseDurationLagDecoder(_PoseDurationTables):
+class PoseDurationLagDecoder(_LagState, _PoseDurationTables):
     """Fixed-lag paths with hold durations of `streams` live videos (csrc/pose_duration_lag.hip): `push` takes the new frames
     and returns, for the frames `lag` frames ago, the step and the start of its hold that PoseDurationDecoder would give on the
     stream up to now.  The tables are PoseDurationDecoder's; the count of frames seen lives on the host (all streams advance
     together), the two carry buffers are swapped after every push.  Nothing is read back.  See the module text."""
-    _empty_with_flush = True
 
     def __init__(self, state_class, trans, dur, device, lag, streams=1, init=None, dur_open="suffix_max", class_names=None):
         _check_lag(type(self).__name__, lag)
         super().__init__(state_class, trans, dur, device, streams, init, dur_open, class_names)
-        self.lag, self.seen = int(lag), 0
-        desc = PoseDurationLagDesc(streams, 1, 1, self.num_states, self.max_duration, self.lag, 0, 0)
-        nbytes = int(bind(_lib.lib()).qt_pose_duration_lag_carry_bytes(ctypes.byref(desc)))
-        self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]  # [0]: the next call's carry_in
-
-    def reset(self):
-        """every stream starts anew (no host sync; the carry is not read at a stream's first frame)"""
-        self.seen = 0
-        return self
+        self._lag_init(lag, "qt_pose_duration_lag_carry_bytes",
+                       PoseDurationLagDesc(streams, 1, 1, self.num_states, self.max_duration, int(lag), 0, 0))
 
     def push(self, probs, flush=False, start=False, filtered=False, score=False):
         """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device; frames may be 0
@@ -1020,29 +996,63 @@ class PoseDurationLagDecoder(_PoseDurationTables):
         B, dev = self.streams, self.device
         if self.seen + T > MAX_STREAM_FRAMES:
             raise QtError(f"{what}: frame {self.seen + T} of a stream; at most {MAX_STREAM_FRAMES} are handled")
-        first = max(0, self.seen - self.lag)
-        count = (self.seen + T if flush else max(0, self.seen + T - self.lag)) - first
+        first, count = self._span(T, flush)
         desc = PoseDurationLagDesc(B, T, C, self.num_states, self.max_duration, self.lag, int(bool(flush)), self.seen)
         lead = (lambda n: (n,)) if flat else (lambda n: (B, n))
         path = torch.empty(lead(count), dtype=torch.int64, device=dev)
         begin = torch.empty(lead(count), dtype=torch.int64, device=dev) if start else None
         filt = torch.empty(lead(T), dtype=torch.int64, device=dev) if filtered else None
         best = torch.empty(lead(T), dtype=torch.int64, device=dev) if score else None
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_duration_lag_workspace_bytes, desc)
-        with torch.cuda.device(dev):
-            _lib.check(L.qt_pose_duration_lag_decode(
-                ctypes.byref(desc), _lib.ptr(probs) if T else None, probs.stride(1) if T else C, _lib.ptr(self.state_class),
-                _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.dur), _lib.ptr(self.dur_open),
-                _lib.ptr(self._carry[0]) if self.seen else None, _lib.ptr(self._carry[1]), _lib.ptr(path) if count else None,
-                _lib.ptr(begin) if count else None, _lib.ptr(filt) if T else None, _lib.ptr(best) if T else None, ws, ws_bytes,
-                _lib.stream_ptr()), "qt_pose_duration_lag_decode")
-        self.seen += T
-        self._carry.reverse()
+        self._call("qt_pose_duration_lag_decode", desc, probs if T else None, probs.stride(1) if T else C, *self._tables(),
+                   *self._carries(), path if count else None, begin if count else None, filt if T else None,
+                   best if T else None, workspace="qt_pose_duration_lag_workspace_bytes")
+        self._advance(T)
         return (first, path) + tuple(t for t in (begin, filt, best) if t is not None)
 
 
-class PoseOrderLearner(_PoseTables):
+class _Learner:
+    """what the two learners share: the loop of `fit`, `totals`, the checks of whole videos and of state paths, and the start
+    vector that learn_init writes out"""
+    def _learned_init(self, init):
+        if init is None and self.learn_init:
+            init = np.zeros(self.num_states, np.int32)          # the start vector of zeros, written out
+        return init
+
+    def _videos(self, what, probs):
+        """probs f32 [B, n, C] or [n, C] on this device -> [B, n, C] with rows the kernels can walk"""
+        _check_probs_tensor(what, probs, self.device)
+        if probs.dim() == 2:
+            probs = probs.unsqueeze(0)
+        if probs.dim() != 3 or probs.shape[0] < 1 or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
+            raise QtError(f"{what}: probs must be [B, frames, C] or [frames, C] with B, frames >= 1 and C <= {MAX_CLASSES} "
+                          f"(got {list(probs.shape)})")
+        return _check_probs_rows(what, probs)
+
+    def _fit_args(self, video):
+        """an item of `fit`'s videos as the arguments of `accumulate`"""
+        return (video,)
+
+    def fit(self, videos, iterations):
+        """`iterations` rounds of zero / accumulate every video / update, with no host synchronisation; `videos` is a sequence
+        (it is walked once per round) of what `accumulate` takes: probs f32 [B, n, C] or [n, C] and, for the learner with hold
+        durations, also pairs (probs, lengths).  The accumulators are left as the last E-step made them: `totals` gives the
+        evidence under the tables BEFORE the last update."""
+        _int_in(f"{type(self).__name__}.fit", "iterations", iterations, 0, numpy=False)
+        videos = [self._fit_args(v) for v in videos]
+        for _ in range(iterations):
+            self.zero()
+            for args in videos:
+                self.accumulate(*args)
+            self.update()
+        return self
+
+    def totals(self):
+        """(evidence in bits, frames) of what has been accumulated since `zero`: the one host sync"""
+        bits, frames = self._totals.cpu().tolist()
+        return bits, int(frames)
+
+
+class PoseOrderLearner(_Learner, _PoseTables):
     """Baum-Welch for the decoder's chain, on the device: the transition table (and, with learn_init, the start scores) fitted
     to videos whose frames carry class probabilities only.  `accumulate` is the E-step of one video or of a batch of videos of
     equal length (qt_pose_prior_expect adds the expected transition counts onto float64 accumulators in a fixed order),
@@ -1061,12 +1071,8 @@ class PoseOrderLearner(_PoseTables):
         self._totals = torch.zeros(2, dtype=torch.float64, device=device)
 
     def _check_own(self, who, init, pseudo_count):
-        if isinstance(pseudo_count, bool) or not isinstance(pseudo_count, (int, float, np.integer, np.floating)) or \
-                not 0.0 <= float(pseudo_count) < float("inf"):
-            raise ValueError(f"{who}: pseudo_count must be a finite number >= 0 (got {pseudo_count!r})")
-        if init is None and self.learn_init:
-            init = np.zeros(self.num_states, np.int32)          # the start vector of zeros, written out
-        return init
+        _check_pseudo(who, "pseudo_count", pseudo_count)
+        return self._learned_init(init)
 
     def zero(self):
         """the accumulators to zero, before an E-step (no host sync)"""
@@ -1076,89 +1082,36 @@ class PoseOrderLearner(_PoseTables):
     def accumulate(self, probs):
         """E-step of whole videos: probs f32 [B, n, C], or [n, C] for one, on the learner's device (predict's rows or the
         timeline's smoothed rows).  Adds onto counts, start_counts and the totals; nothing is read back."""
-        what = "PoseOrderLearner.accumulate"
-        _check_probs_tensor(what, probs, self.device)
-        if probs.dim() == 2:
-            probs = probs.unsqueeze(0)
-        if probs.dim() != 3 or probs.shape[0] < 1 or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
-            raise QtError(f"{what}: probs must be [B, frames, C] or [frames, C] with B, frames >= 1 and C <= {MAX_CLASSES} "
-                          f"(got {list(probs.shape)})")
-        probs = _check_probs_rows(what, probs)
+        probs = self._videos("PoseOrderLearner.accumulate", probs)
         B, T, C = probs.shape
-        desc = PoseOrderDesc(B, T, C, self.num_states)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_prior_workspace_bytes, desc)
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_prior_expect(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class),
-                                              _lib.ptr(self.trans), _lib.ptr(self.init), _lib.ptr(self.counts),
-                                              _lib.ptr(self.start_counts), _lib.ptr(self._totals), ws, ws_bytes,
-                                              _lib.stream_ptr()), "qt_pose_prior_expect")
+        self._call("qt_pose_prior_expect", PoseOrderDesc(B, T, C, self.num_states), probs, probs.stride(1), self.state_class,
+                   self.trans, self.init, self.counts, self.start_counts, self._totals, workspace="qt_pose_prior_workspace_bytes")
         return self
 
     def accumulate_paths(self, path):
         """hard counts: path int64 [B, n] or [n] on the learner's device, whole videos; a state outside 0 .. S - 1 (a label
         that is missing) takes its transitions out.  The frames are counted, the evidence is not touched."""
         what = "PoseOrderLearner.accumulate_paths"
-        if not isinstance(path, torch.Tensor) or path.device != self.device or path.dtype != torch.int64:
-            raise QtError(f"{what}: path must be an int64 tensor on {self.device}; there is no CPU or torch fallback")
-        if path.dim() == 1:
-            path = path.unsqueeze(0)
-        if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] < 1:
-            raise QtError(f"{what}: path must be [B, frames] or [frames] with B, frames >= 1 (got {list(path.shape)})")
+        _check_device_tensor(what, "path", path, self.device, torch.int64, tail=_NO_FALLBACK)
+        path = _path_batch(what, path).detach().contiguous()
         B, T = path.shape
-        if B * T > MAX_FRAMES:
-            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
-        path = path.detach().contiguous()
-        desc = PoseOrderDesc(B, T, 1, self.num_states)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_prior_workspace_bytes, desc)
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_prior_count_paths(ctypes.byref(desc), _lib.ptr(path), _lib.ptr(self.counts),
-                                                   _lib.ptr(self.start_counts), _lib.ptr(self._totals), ws, ws_bytes,
-                                                   _lib.stream_ptr()), "qt_pose_prior_count_paths")
+        self._call("qt_pose_prior_count_paths", PoseOrderDesc(B, T, 1, self.num_states), path, self.counts, self.start_counts,
+                   self._totals, workspace="qt_pose_prior_workspace_bytes")
         return self
 
     def update(self):
         """M-step on the device, in place: self.trans (and with learn_init self.init) are the new int32 tables"""
-        L = bind(_lib.lib())
         init = self.init if self.learn_init else None
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_prior_update(self.num_states, _lib.ptr(self.counts), _lib.ptr(self.start_counts),
-                                              _lib.ptr(self.allowed), self.pseudo_count, _lib.ptr(self.trans), _lib.ptr(init),
-                                              _lib.ptr(self.trans), _lib.ptr(init), _lib.stream_ptr()), "qt_pose_prior_update")
+        self._call("qt_pose_prior_update", self.num_states, self.counts, self.start_counts, self.allowed, self.pseudo_count,
+                   self.trans, init, self.trans, init)
         return self
-
-    def fit(self, videos, iterations):
-        """`iterations` rounds of zero / accumulate every video / update, with no host synchronisation; `videos` is a sequence
-        (it is walked once per round) of f32 [B, n, C] or [n, C] tensors.  The accumulators are left as the last E-step made
-        them: `totals` gives the evidence under the tables BEFORE the last update."""
-        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 0:
-            raise ValueError(f"PoseOrderLearner.fit: iterations must be an integer >= 0 (got {iterations!r})")
-        videos = list(videos)
-        for _ in range(iterations):
-            self.zero()
-            for probs in videos:
-                self.accumulate(probs)
-            self.update()
-        return self
-
-    def totals(self):
-        """(evidence in bits, frames) of what has been accumulated since `zero`: the one host sync"""
-        bits, frames = self._totals.cpu().tolist()
-        return bits, int(frames)
 
     def tables(self):
         """numpy (state_class int32 [S], trans int32 [S, S], init int32 [S] or None), for saving (a host sync)"""
         return (self.state_class.cpu().numpy(), self.trans.cpu().numpy(), None if self.init is None else self.init.cpu().numpy())
 
 
-def _check_pseudo(who, name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) < float("inf"):
-        raise ValueError(f"{who}: {name} must be a finite number >= 0 (got {v!r})")
-    return float(v)
-
-
-class PoseDurationLearner(_PoseDurationTables):
+class PoseDurationLearner(_Learner, _PoseDurationTables):
     """Baum-Welch for the chain with hold durations, on the device (csrc/pose_duration_prior.hip): trans, dur and, with
     learn_init, the start scores fitted jointly to whole videos whose frames carry class probabilities only.  `accumulate` is the
     E-step of one video or of a ragged batch (qt_pose_duration_prior_expect adds the expected transition, start and duration
@@ -1185,10 +1138,7 @@ class PoseDurationLearner(_PoseDurationTables):
         self._totals = torch.zeros(2, dtype=torch.float64, device=device)
 
     def _check_own(self, who, init, dur, dur_open):
-        init = super()._check_own(who, init, dur, dur_open)
-        if init is None and self.learn_init:
-            init = np.zeros(self.num_states, np.int32)          # the start vector of zeros, written out
-        return init
+        return self._learned_init(super()._check_own(who, init, dur, dur_open))
 
     def zero(self):
         """the accumulators to zero, before an E-step (no host sync)"""
@@ -1200,24 +1150,12 @@ class PoseDurationLearner(_PoseDurationTables):
         timeline's smoothed rows); lengths int32 [B] on the device, or None when every video has n frames (a value outside
         1 .. n is clamped into it).  Adds onto counts, start_counts, dur_counts and the totals; nothing is read back."""
         what = "PoseDurationLearner.accumulate"
-        _check_probs_tensor(what, probs, self.device)
-        if probs.dim() == 2:
-            probs = probs.unsqueeze(0)
-        if probs.dim() != 3 or probs.shape[0] < 1 or probs.shape[1] < 1 or not 1 <= probs.shape[2] <= MAX_CLASSES:
-            raise QtError(f"{what}: probs must be [B, frames, C] or [frames, C] with B, frames >= 1 and C <= {MAX_CLASSES} "
-                          f"(got {list(probs.shape)})")
-        probs = _check_probs_rows(what, probs)
+        probs = self._videos(what, probs)
         B, T, C = probs.shape
         lengths = self._check_lengths(what, lengths, B)
-        desc = PoseDurationDesc(B, T, C, self.num_states, self.max_duration)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_duration_prior_workspace_bytes, desc)
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_duration_prior_expect(
-                ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), _lib.ptr(self.state_class), _lib.ptr(self.trans),
-                _lib.ptr(self.init), _lib.ptr(self.dur), _lib.ptr(self.dur_open), _lib.ptr(lengths), _lib.ptr(self.counts),
-                _lib.ptr(self.start_counts), _lib.ptr(self.dur_counts), _lib.ptr(self._totals), ws, ws_bytes, _lib.stream_ptr()),
-                "qt_pose_duration_prior_expect")
+        self._call("qt_pose_duration_prior_expect", PoseDurationDesc(B, T, C, self.num_states, self.max_duration), probs,
+                   probs.stride(1), *self._tables(), lengths, self.counts, self.start_counts, self.dur_counts, self._totals,
+                   workspace="qt_pose_duration_prior_workspace_bytes")
         return self
 
     def accumulate_paths(self, path, start=None, lengths=None):
@@ -1226,67 +1164,34 @@ class PoseDurationLearner(_PoseDurationTables):
         segments of one step count on the diagonal of trans; without it they are the runs of path (labelled steps).  A step
         outside 0 .. S - 1 (a label that is missing) counts nowhere.  The frames are counted, the evidence is not touched."""
         what = "PoseDurationLearner.accumulate_paths"
-        for name, t in (("path", path), ("start", start)):
-            if t is None and name == "start":
-                continue
-            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int64:
-                raise QtError(f"{what}: {name} must be an int64 tensor on {self.device}; there is no CPU or torch fallback")
-        if start is not None and start.shape != path.shape:
-            raise QtError(f"{what}: start {list(start.shape)} and path {list(path.shape)} do not belong together")
-        if path.dim() == 1:
-            path = path.unsqueeze(0)
-            start = None if start is None else start.unsqueeze(0)
-        if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] < 1:
-            raise QtError(f"{what}: path must be [B, frames] or [frames] with B, frames >= 1 (got {list(path.shape)})")
+        _check_device_tensor(what, "path", path, self.device, torch.int64, tail=_NO_FALLBACK)
+        if start is not None:
+            _check_device_tensor(what, "start", start, self.device, torch.int64, tail=_NO_FALLBACK)
+            if start.shape != path.shape:
+                raise QtError(f"{what}: start {list(start.shape)} and path {list(path.shape)} do not belong together")
+        path = _path_batch(what, path)
         B, T = path.shape
-        if B * T > MAX_FRAMES:
-            raise QtError(f"{what}: {B * T} frames; at most {MAX_FRAMES} are handled in one call")
         lengths = self._check_lengths(what, lengths, B)
         path = path.detach().contiguous()
-        start = None if start is None else start.detach().contiguous()
-        desc = PoseDurationDesc(B, T, 1, self.num_states, self.max_duration)
-        L = bind(_lib.lib())
-        ws, ws_bytes = self._room(L.qt_pose_duration_prior_workspace_bytes, desc)
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_duration_prior_count_paths(
-                ctypes.byref(desc), _lib.ptr(path), _lib.ptr(start), T, _lib.ptr(lengths), _lib.ptr(self.counts),
-                _lib.ptr(self.start_counts), _lib.ptr(self.dur_counts), _lib.ptr(self._totals), ws, ws_bytes, _lib.stream_ptr()),
-                "qt_pose_duration_prior_count_paths")
+        start = None if start is None else start.detach().reshape(B, T).contiguous()
+        self._call("qt_pose_duration_prior_count_paths", PoseDurationDesc(B, T, 1, self.num_states, self.max_duration), path,
+                   start, T, lengths, self.counts, self.start_counts, self.dur_counts, self._totals,
+                   workspace="qt_pose_duration_prior_workspace_bytes")
         return self
 
     def update(self):
         """M-step on the device, in place: self.trans, self.dur (with learn_init self.init, with dur_open "suffix_max"
         self.dur_open) are the new int32 tables"""
-        L = bind(_lib.lib())
         init = self.init if self.learn_init else None
         dur_open = self.dur_open if self._learn_open else None
-        with torch.cuda.device(self.device):
-            _lib.check(L.qt_pose_duration_prior_update(
-                self.num_states, self.max_duration, _lib.ptr(self.counts), _lib.ptr(self.start_counts), _lib.ptr(self.dur_counts),
-                _lib.ptr(self.allowed), _lib.ptr(self.dur_allowed), self.pseudo_count, self.dur_pseudo_count, _lib.ptr(self.trans),
-                _lib.ptr(init), _lib.ptr(self.dur), _lib.ptr(self.trans), _lib.ptr(init), _lib.ptr(self.dur), _lib.ptr(dur_open),
-                _lib.stream_ptr()), "qt_pose_duration_prior_update")
+        self._call("qt_pose_duration_prior_update", self.num_states, self.max_duration, self.counts, self.start_counts,
+                   self.dur_counts, self.allowed, self.dur_allowed, self.pseudo_count, self.dur_pseudo_count, self.trans, init,
+                   self.dur, self.trans, init, self.dur, dur_open)
         return self
 
-    def fit(self, videos, iterations):
-        """`iterations` rounds of zero / accumulate every video / update, with no host synchronisation; `videos` is a sequence
-        (it is walked once per round) whose items are probs (f32 [B, n, C] or [n, C]) or pairs (probs, lengths).  The
-        accumulators are left as the last E-step made them: `totals` gives the evidence under the tables BEFORE the last
-        update."""
-        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 0:
-            raise ValueError(f"PoseDurationLearner.fit: iterations must be an integer >= 0 (got {iterations!r})")
-        videos = [v if isinstance(v, (tuple, list)) else (v, None) for v in videos]
-        for _ in range(iterations):
-            self.zero()
-            for probs, lengths in videos:
-                self.accumulate(probs, lengths)
-            self.update()
-        return self
-
-    def totals(self):
-        """(evidence in bits, frames) of what has been accumulated since `zero`: the one host sync"""
-        bits, frames = self._totals.cpu().tolist()
-        return bits, int(frames)
+    def _fit_args(self, video):
+        probs, lengths = video if isinstance(video, (tuple, list)) else (video, None)
+        return probs, lengths
 
     def tables(self):
         """numpy (state_class int32 [S], trans int32 [S, S], init int32 [S] or None, dur int32 [S, D], dur_open int32 [S, D] or

@@ -234,7 +234,7 @@ def test_new_symbols_are_declared_and_exported():
     src = open(os.path.join(ROOT, PKG, "csrc", "pose_duration.hip")).read()
     assert '#include "pose_chain.h"' in src and not re.search(r"_LOG2\[256\]\s*=|\b\w*_FLOOR\s*=(?!=)", re.sub(r"//[^\n]*", "", src))
     assert int(re.search(r"#define QT_POSE_DUR_MAX (\d+)", header).group(1)) == M.DUR_MAX == Q.DUR_MAX == \
-        int(re.search(r"constexpr int PD_MAX_D = (\d+);", src).group(1))
+        int(re.search(r"constexpr int PC_MAX_D = (\d+);", open(os.path.join(ROOT, PKG, "csrc", "pose_duration_chain.h")).read()).group(1))
     P = pkg()
     assert P.PoseDurationDecoder is M.PoseDurationDecoder and P.duration_prior is M.duration_prior
     assert P.hold_prior is M.hold_prior and P.geometric_durations is M.geometric_durations

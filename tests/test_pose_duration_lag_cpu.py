@@ -169,7 +169,7 @@ def test_new_symbols_are_declared_and_exported():
     src = open(os.path.join(ROOT, PKG, "csrc", "pose_duration_lag.hip")).read()
     assert '#include "pose_chain.h"' in src and not re.search(r"_LOG2\[256\]\s*=|\b\w*_FLOOR\s*=(?!=)", re.sub(r"//[^\n]*", "", src))
     assert "getenv" not in src and "qt_env" not in src                                # one route
-    assert "constexpr int PD_MAX_D = 128;" in open(os.path.join(ROOT, PKG, "csrc", "pose_duration.hip")).read()
+    assert "constexpr int PC_MAX_D = 128;" in open(os.path.join(ROOT, PKG, "csrc", "pose_duration_chain.h")).read()
     assert P.PoseDurationLagDecoder is M.PoseDurationLagDecoder and "PoseDurationLagDecoder" in P.__all__
 
 

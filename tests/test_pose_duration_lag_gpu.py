@@ -202,7 +202,7 @@ def test_a_one_call_flush_within_the_lag_is_the_whole_video_kernel(n):
 
 
 # ---- against the integer loops ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C,S", [(1, 1), (2, 2), (12, 12), (12, 17), (64, 64)])
+@pytest.mark.parametrize("C,S", [(1, 1), (2, 2), (12, 12), (12, 16), (12, 17), (64, 64)])
 def test_bits_equal_the_loops(C, S):
     """outputs and the unpacked carry, init given and NULL, dur_open given and NULL, ld > C"""
     dev = _dev()
