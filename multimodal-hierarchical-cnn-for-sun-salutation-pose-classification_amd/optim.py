@@ -33,6 +33,16 @@ clipping) and `opt.last_clip_coef` are 0-dim f32 device tensors afterwards.  One
 UNSCALED, because the scaling happens inside the update.  A clipped step runs serially on the caller's stream (the norm
 needs conv1's weight gradient, the last thing the backward produces).  `grad_norm(parameters)` gives the same norm alone,
 for logging.
+
+The rule, precisely: Adam with the F32-ROUNDED hyper-parameters.  The C ABI carries lr, the betas, eps and the weight decay
+as f32 and the kernel forms `1 - beta` as f32(1) - f32(beta); the bias corrections are computed in double from the same f32
+beta, so the rule is self-consistent (v / (1 - b2^t) = g^2 at step 1).  torch.optim.Adam uses the Python doubles.  At the
+reference's betas (0.9, 0.999) f32(1) - f32(0.999) = 0.00099998713 against torch's 0.001: after one step `exp_avg_sq` is
+1.29e-5 relative below torch's (`exp_avg`: 2.4e-7), a gap that decays as the first steps' terms do, over about
+1 / (1 - beta2) = 1000 steps (both rules' weights sum to 1 in the long run); the parameters differ by under 2e-5 * lr after 2,000
+steps (float64 simulation of both rules).  tests/_adam_ref.py states the rule in float64 and derives per-element bounds
+for the kernels; tests/test_adam_gpu.py holds them to it.  State moves both ways between FusedAdam and torch.optim.Adam
+through state_dict() / load_state_dict(): `step` is a Python int here and is converted when a torch checkpoint is loaded.
 """
 import ctypes
 import math
@@ -129,6 +139,22 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("FusedAdam: every param group must carry the same max_grad_norm")
         return values.pop() if values else None
 
+    def load_state_dict(self, state_dict):
+        """Also takes a torch.optim.Adam checkpoint.  torch saves each parameter's `step` as a tensor; here it is a Python
+        int (it goes into the kernels' descriptor, and step() must not read the device), so it is converted once, now.
+        amsgrad / maximize checkpoints are refused: the kernels do not implement them."""
+        for group in state_dict["param_groups"]:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise ValueError("FusedAdam: cannot resume an amsgrad / maximize checkpoint")
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if "step" in st and type(st["step"]) is not int:
+                step = st["step"]
+                value = float(step.item() if isinstance(step, torch.Tensor) else step)
+                if value != int(value) or value < 0:
+                    raise ValueError(f"FusedAdam: step {value!r} in the loaded state is not a step count")
+                st["step"] = int(value)
+
     def _begin_clip(self, L, max_norm):
         """Everything the clipped step needs before its first update: the gradients of all groups (the norm is global),
         the norm kernel's workspace and the two output floats.  No device work yet."""
@@ -174,6 +200,9 @@ class FusedAdam(torch.optim.Optimizer):
                     created_state = True
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if type(st["step"]) is not int:   # (load_state_dict() converts torch's tensor; nothing here reads the device)
+                    raise _lib.QtError("FusedAdam: state['step'] must be a Python int; load optimizer state with "
+                                       "load_state_dict()")
                 st["step"] += 1
                 todo.append((p, st))
             if not todo:
