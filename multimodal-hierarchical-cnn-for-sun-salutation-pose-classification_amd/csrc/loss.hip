@@ -7,8 +7,8 @@
 // A latency problem (256 x 12 floats), so: one launch per direction whenever the batch fits one workgroup; no atomics, no
 // zero fill, every summation order fixed -> the same bits on every run; nothing allocated, nothing synchronised.
 //
-// Row-to-lane mapping by class count C (LANES lanes own one row, each keeps PER logits in registers, element k of the row
-// sits in lane k % LANES):
+// Row-to-lane mapping by class count C (qt_rowgroup.h: LANES lanes own one row, each keeps PER logits in registers, element
+// k of the row sits in lane k % LANES):
 //     C <= 16    one thread per row           256 rows per workgroup
 //     C <= 64    one 16-lane DPP row per row    16 rows per workgroup
 //     C <= 1024  one wave per row                4 rows per workgroup
@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "qt_common.h"
+#include "qt_rowgroup.h"
 
 namespace {
 
@@ -41,40 +42,6 @@ struct LossArgs {
 };
 
 __device__ __forceinline__ float loss_nan() { return __uint_as_float(0x7fc00000u); }
-
-// ---- reductions over the LANES lanes of one row (every lane receives the result; fixed butterfly order) ---------------
-template <int LANES> __device__ __forceinline__ float group_sum(float v) {
-  if (LANES >= 16) v = qt_row16_sum(v);
-  if (LANES == 64) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-  }
-  return v;
-}
-// a beats b: a NaN beats every number, a larger value beats a smaller one, the lower index wins what is left (a total order,
-// so every lane of the butterfly ends with the same pair)
-__device__ __forceinline__ bool arg_beats(float av, int ai, float bv, int bi) {
-  const bool an = av != av, bn = bv != bv;
-  if (an != bn) return an;
-  if (!an && av != bv) return av > bv;
-  return ai < bi;
-}
-template <int LANES> __device__ __forceinline__ void group_argmax(float& v, int& i) {
-#pragma unroll
-  for (int s = 1; s < LANES; s <<= 1) {
-    const float ov = __shfl_xor(v, s, 64);
-    const int oi = __shfl_xor(i, s, 64);
-    if (arg_beats(ov, oi, v, i)) {
-      v = ov;
-      i = oi;
-    }
-  }
-}
-// the value lane `owner` of this row's group holds
-template <int LANES> __device__ __forceinline__ float group_pick(float v, int owner) {
-  if (LANES == 1) return v;
-  return __shfl(v, (int)((threadIdx.x & 63u) & ~(unsigned)(LANES - 1)) + owner, 64);
-}
 
 // Sum of one double per thread over the workgroup, fixed order: thread t adds slot t + s for s = 128, 64, .. 1.
 // Thread 0 holds the result.
@@ -142,27 +109,15 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(LossArgs a, floa
   const long long y = a.y[row];
 
   float z[PER];
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int k = j * LANES + sub;
-    z[j] = k < C ? zr[k] : 0.f;
-  }
+  qt_row_load<LANES, PER>(zr, C, sub, z);
   const bool ce = a.kind == QT_LOSS_CROSS_ENTROPY;
   const bool ignored = ce && y == a.ignore_index;
   const bool in_range = y >= 0 && y < (long long)C;
   const bool bad = !ignored && !in_range;           // error row: NaN loss, no indexing with y anywhere
 
-  // argmax = torch.max(outputs, 1): first index of the maximum, a NaN wins
-  float bv = z[0];
-  int bi = sub;           // k = sub < C always holds for j = 0 in lane groups that own an element; others are fixed below
-  if (sub >= C) { bv = -INFINITY; bi = INT32_MAX; }
-#pragma unroll
-  for (int j = 1; j < PER; ++j) {
-    const int k = j * LANES + sub;
-    if (k < C && arg_beats(z[j], k, bv, bi)) { bv = z[j]; bi = k; }
-  }
-  group_argmax<LANES>(bv, bi);
-  const float m = bv;
+  float m;   // argmax = torch.max(outputs, 1): first index of the maximum, a NaN wins
+  int bi;
+  qt_row_argmax<LANES, PER>(z, C, sub, m, bi);
 
   // d_k = z_k - m (kept in z), s1 = sum over k != argmax of exp(d_k), and the label's own d_y / w_y by selection
   float s1 = 0.f, dy_l = 0.f, wy_l = 1.f;
@@ -182,11 +137,11 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(LossArgs a, floa
       if (k < C && (long long)k == y) wy_l = a.w[k];
     }
   }
-  s1 = group_sum<LANES>(s1);
+  s1 = qt_group_sum<LANES>(s1);
   const float l = log1pf(s1);
   const int owner = in_range ? (int)(y & (LANES - 1)) : 0;
-  float dy = group_pick<LANES>(dy_l, owner);
-  float wy = group_pick<LANES>(wy_l, owner);
+  float dy = qt_group_pick<LANES>(dy_l, owner);
+  float wy = qt_group_pick<LANES>(wy_l, owner);
   if (bad) dy = wy = loss_nan();
 
   float li, deni = 0.f;
@@ -201,7 +156,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_fwd_kernel(LossArgs a, floa
         const int k = j * LANES + sub;
         if (k < C) sm += (a.w ? a.w[k] : 1.f) * (l - z[j]);
       }
-      sm = group_sum<LANES>(sm);
+      sm = qt_group_sum<LANES>(sm);
       li = (1.f - a.eps) * li + (a.eps / (float)C) * sm;
     }
     if (ignored) li = deni = 0.f;
@@ -265,11 +220,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
   const float scale = g / (float)stats[1];
 
   float z[PER];
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int k = j * LANES + sub;
-    z[j] = k < C ? zr[k] : 0.f;
-  }
+  qt_row_load<LANES, PER>(zr, C, sub, z);
   const bool ce = a.kind == QT_LOSS_CROSS_ENTROPY;
   const bool ignored = ce && y == a.ignore_index;
   const bool in_range = y >= 0 && y < (long long)C;
@@ -290,8 +241,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
     }
   }
   const int owner = in_range ? (int)(y & (LANES - 1)) : 0;
-  float logp = group_pick<LANES>(ly_l, owner);
-  float wy = group_pick<LANES>(wy_l, owner);
+  float logp = qt_group_pick<LANES>(ly_l, owner);
+  float wy = qt_group_pick<LANES>(wy_l, owner);
   if (bad) logp = wy = loss_nan();
   const float pm1 = expm1f(logp);                       // p_y - 1
 
@@ -299,7 +250,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
   if (ce) {
     c1 = wy;
     if (a.eps > 0.f) {
-      W = a.w ? group_sum<LANES>(wsum) : (float)C;
+      W = a.w ? qt_group_sum<LANES>(wsum) : (float)C;
       c1 = (1.f - a.eps) * wy;
       c2 = a.eps / (float)C;
     }
@@ -335,12 +286,8 @@ int check_desc(const qt_loss_desc* d, long long rows, int C, const char* who) {
   QT_CHECK_ARG(d->kind == QT_LOSS_CROSS_ENTROPY || d->kind == QT_LOSS_FOCAL, "%s: unknown loss kind %d", who, d->kind);
   QT_CHECK_ARG(d->reduction == QT_LOSS_REDUCE_MEAN || d->reduction == QT_LOSS_REDUCE_SUM || d->reduction == QT_LOSS_REDUCE_NONE,
                "%s: unknown reduction %d", who, d->reduction);
-  QT_CHECK_ARG(rows >= 1 && C >= 1, "%s: needs rows >= 1 and C >= 1 (got %lld x %d)", who, rows, C);
-  if (C > LOSS_MAX_C) {
-    qt_set_error("%s: C = %d classes; at most %d are handled", who, C, LOSS_MAX_C);
-    return QT_ERR_UNSUPPORTED;
-  }
-  QT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->class_weight) & 3) == 0, "%s: class_weight must be 4-byte aligned", who);
+  if (int rc = qt_check_rows_classes(who, rows, C, LOSS_MAX_C, 0)) return rc;
+  QT_CHECK_ARG(!misaligned(d->class_weight, 3), "%s: class_weight must be 4-byte aligned", who);
   if (d->kind == QT_LOSS_CROSS_ENTROPY) {
     QT_CHECK_ARG(d->label_smoothing >= 0.f && d->label_smoothing <= 1.f, "%s: label_smoothing must be in [0, 1] (got %g)", who,
                  (double)d->label_smoothing);
@@ -355,9 +302,8 @@ int check_desc(const qt_loss_desc* d, long long rows, int C, const char* who) {
   return QT_OK;
 }
 
-inline int loss_lanes(int C) { return C <= 16 ? 1 : C <= 64 ? 16 : 64; }
 inline long long loss_blocks(long long rows, int C) {
-  const int rpb = LOSS_THREADS / loss_lanes(C);
+  const int rpb = LOSS_THREADS / qt_row_lanes(C);
   return (rows + rpb - 1) / rpb;
 }
 
@@ -391,10 +337,8 @@ extern "C" int qt_loss_forward(const qt_loss_desc* desc, const float* logits, lo
   if (int st = check_desc(desc, rows, C, "qt_loss_forward")) return st;
   QT_CHECK_ARG(logits && labels && loss && stats, "qt_loss_forward: null logits / labels / loss / stats");
   QT_CHECK_ARG(ld >= C, "qt_loss_forward: row stride %lld < C = %d", ld, C);
-  QT_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 3) == 0 && (reinterpret_cast<uintptr_t>(loss) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(labels) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(row_state) & 7) == 0 && (reinterpret_cast<uintptr_t>(pred) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(meter) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+  QT_CHECK_ARG(!misaligned(logits, 3) && !misaligned(loss, 3) && !misaligned(labels, 7) && !misaligned(stats, 7) &&
+                   !misaligned(row_state, 7) && !misaligned(pred, 7) && !misaligned(meter, 7) && !misaligned(workspace, 7),
                "qt_loss_forward: f32 buffers must be 4-byte aligned, labels / row_state / stats / pred / meter / workspace 8-byte");
   const long long blocks = loss_blocks(rows, C);
   QT_CHECK_ARG(blocks <= (long long)INT32_MAX, "qt_loss_forward: too many rows for one call");
@@ -406,20 +350,10 @@ extern "C" int qt_loss_forward(const qt_loss_desc* desc, const float* logits, lo
   const LossArgs a = make_args(desc, logits, ld, labels, rows, C);
   double* partial = blocks > 1 ? static_cast<double*>(workspace) : nullptr;
   float2* rs = reinterpret_cast<float2*>(row_state);
-  switch (loss_lanes(C)) {
-    case 1:
-      hipLaunchKernelGGL((loss_fwd_kernel<1, 16>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, loss, rs, stats, pred, meter,
-                         partial);
-      break;
-    case 16:
-      hipLaunchKernelGGL((loss_fwd_kernel<16, 4>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, loss, rs, stats, pred, meter,
-                         partial);
-      break;
-    default:
-      hipLaunchKernelGGL((loss_fwd_kernel<64, 16>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, loss, rs, stats, pred, meter,
-                         partial);
-      break;
-  }
+  qt_by_row_lanes<LOSS_MAX_C>(C, [&](auto L, auto P) {
+    hipLaunchKernelGGL((loss_fwd_kernel<decltype(L)::value, decltype(P)::value>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a,
+                       loss, rs, stats, pred, meter, partial);
+  });
   QT_CHECK_LAUNCH();
   if (partial) {
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, partial, (int)blocks, rows, desc->kind,
@@ -436,29 +370,18 @@ extern "C" int qt_loss_backward(const qt_loss_desc* desc, const float* logits, l
   QT_CHECK_ARG(logits && labels && row_state && stats && grad_out && dlogits,
                "qt_loss_backward: null logits / labels / row_state / stats / grad_out / dlogits");
   QT_CHECK_ARG(ld >= C && ld_d >= C, "qt_loss_backward: row strides %lld / %lld < C = %d", ld, ld_d, C);
-  QT_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 3) == 0 && (reinterpret_cast<uintptr_t>(grad_out) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(dlogits) & 3) == 0 && (reinterpret_cast<uintptr_t>(labels) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(row_state) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,
+  QT_CHECK_ARG(!misaligned(logits, 3) && !misaligned(grad_out, 3) && !misaligned(dlogits, 3) && !misaligned(labels, 7) &&
+                   !misaligned(row_state, 7) && !misaligned(stats, 7),
                "qt_loss_backward: f32 buffers must be 4-byte aligned, labels / row_state / stats 8-byte");
   const long long blocks = loss_blocks(rows, C);
   QT_CHECK_ARG(blocks <= (long long)INT32_MAX, "qt_loss_backward: too many rows for one call");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const LossArgs a = make_args(desc, logits, ld, labels, rows, C);
   const float2* rs = reinterpret_cast<const float2*>(row_state);
-  switch (loss_lanes(C)) {
-    case 1:
-      hipLaunchKernelGGL((loss_bwd_kernel<1, 16>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, rs, stats, grad_out, dlogits,
-                         ld_d);
-      break;
-    case 16:
-      hipLaunchKernelGGL((loss_bwd_kernel<16, 4>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, rs, stats, grad_out, dlogits,
-                         ld_d);
-      break;
-    default:
-      hipLaunchKernelGGL((loss_bwd_kernel<64, 16>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, rs, stats, grad_out, dlogits,
-                         ld_d);
-      break;
-  }
+  qt_by_row_lanes<LOSS_MAX_C>(C, [&](auto L, auto P) {
+    hipLaunchKernelGGL((loss_bwd_kernel<decltype(L)::value, decltype(P)::value>), dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a,
+                       rs, stats, grad_out, dlogits, ld_d);
+  });
   QT_CHECK_LAUNCH();
   return QT_OK;
 }

@@ -6,9 +6,9 @@
 // and one finalize launch turns it into the report (precision / recall / F1 / support per class, accuracy, weighted and
 // macro averages, R^2 of label index against predicted index) in double.
 //
-// Update, one launch per batch.  Rows map to lanes as in loss.hip (LANES lanes own one row, element k sits in lane
-// k % LANES): one thread per row for C <= 16, a 16-lane DPP row for C <= 64, a wave above; the argmax is loss.hip's total
-// order (a NaN beats every number, then the larger value, then the lower index), so pred is what qt_loss_forward writes.
+// Update, one launch per batch.  Rows map to lanes by qt_rowgroup.h's rule (LANES lanes own one row, element k sits in lane
+// k % LANES): one thread per row for C <= 16, a 16-lane DPP row for C <= 64, a wave above; the argmax is qt_row_argmax (a NaN
+// beats every number, then the larger value, then the lower index), loss.hip's too, so pred is what qt_loss_forward writes.
 // A workgroup walks row tiles with a grid stride.  Counting is exact in any order of execution because every add is an
 // integer atomic:
 //     C <= 64   the workgroup's own u32 histogram of C*C cells in LDS (16 KiB), LDS atomics per row, then one 64-bit global
@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "qt_common.h"
+#include "qt_rowgroup.h"
 
 namespace {
 
@@ -45,37 +46,6 @@ struct MetArgs {
   long long* pred_out;            // [rows] or NULL
 };
 
-// ---- the group helpers of loss.hip (same arithmetic, same order) ------------------------------------------------------
-template <int LANES> __device__ __forceinline__ float group_sum(float v) {
-  if (LANES >= 16) v = qt_row16_sum(v);
-  if (LANES == 64) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-  }
-  return v;
-}
-__device__ __forceinline__ bool arg_beats(float av, int ai, float bv, int bi) {
-  const bool an = av != av, bn = bv != bv;
-  if (an != bn) return an;
-  if (!an && av != bv) return av > bv;
-  return ai < bi;
-}
-template <int LANES> __device__ __forceinline__ void group_argmax(float& v, int& i) {
-#pragma unroll
-  for (int s = 1; s < LANES; s <<= 1) {
-    const float ov = __shfl_xor(v, s, 64);
-    const int oi = __shfl_xor(i, s, 64);
-    if (arg_beats(ov, oi, v, i)) {
-      v = ov;
-      i = oi;
-    }
-  }
-}
-template <int LANES> __device__ __forceinline__ float group_pick(float v, int owner) {
-  if (LANES == 1) return v;
-  return __shfl(v, (int)((threadIdx.x & 63u) & ~(unsigned)(LANES - 1)) + owner, 64);
-}
-
 // ---- counting ---------------------------------------------------------------------------------------------------------
 enum { ROW_COUNTED = 0, ROW_IGNORED = 1, ROW_INVALID = 2, ROW_NONE = 3 };
 
@@ -92,11 +62,7 @@ __device__ __forceinline__ void tally(bool active, long long y, long long p, con
     if (LDS_HIST) atomicAdd(&hist[(int)y * a.C + (int)p], 1u);
     else atomicAdd(&a.state[(unsigned long long)y * (unsigned)a.C + (unsigned long long)p], 1ull);
   }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const unsigned long long b = __ballot(cls == k);
-    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&cnt[k], (unsigned)__popcll(b));
-  }
+  qt_count_rows<3>(cls, cnt);
 }
 
 template <bool LDS_HIST> __device__ __forceinline__ void tally_begin(const MetArgs& a, unsigned* hist, unsigned* cnt) {
@@ -137,47 +103,25 @@ __global__ __launch_bounds__(MET_THREADS) void metrics_logits_kernel(MetArgs a) 
     const float* __restrict__ zr = a.z + row * a.ld;
 
     float z[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int k = j * LANES + sub;
-      z[j] = k < C ? zr[k] : 0.f;
-    }
-    // argmax = torch.max(outputs, 1): first index of the maximum, a NaN wins (loss.hip's order)
-    float bv = z[0];
-    int bi = sub;
-    if (sub >= C) { bv = -INFINITY; bi = INT32_MAX; }
-#pragma unroll
-    for (int j = 1; j < PER; ++j) {
-      const int k = j * LANES + sub;
-      if (k < C && arg_beats(z[j], k, bv, bi)) { bv = z[j]; bi = k; }
-    }
-    group_argmax<LANES>(bv, bi);
+    qt_row_load<LANES, PER>(zr, C, sub, z);
+    float bv;   // argmax = torch.max(outputs, 1): first index of the maximum, a NaN wins
+    int bi;
+    qt_row_argmax<LANES, PER>(z, C, sub, bv, bi);
     const bool writer = live && sub == 0;
 
     if (want_p) {
-      const float m = bv;
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < PER; ++j) {
-        const int k = j * LANES + sub;
-        if (k < C) {
-          z[j] = expf(z[j] - m);
-          s += z[j];
-        }
-      }
-      s = group_sum<LANES>(s);
+      qt_row_softmax<LANES, PER>(z, C, sub, bv);
       float conf_l = 0.f;
       float* __restrict__ pr = a.probs ? a.probs + row * a.ld_p : nullptr;
 #pragma unroll
       for (int j = 0; j < PER; ++j) {
         const int k = j * LANES + sub;
         if (k < C) {
-          const float p = z[j] / s;
-          if (pr && live) pr[k] = p;
-          if (k == bi) conf_l = p;
+          if (pr && live) pr[k] = z[j];
+          if (k == bi) conf_l = z[j];
         }
       }
-      const float conf = group_pick<LANES>(conf_l, bi & (LANES - 1));
+      const float conf = qt_group_pick<LANES>(conf_l, bi & (LANES - 1));
       if (writer && a.conf) a.conf[row] = conf;
     }
     if (writer && a.pred_out) a.pred_out[row] = (long long)bi;
@@ -203,19 +147,6 @@ __global__ __launch_bounds__(MET_THREADS) void metrics_pred_kernel(MetArgs a) {
 }
 
 // ---- finalize: one workgroup, counts added as integers (exact), everything else in double --------------------------------
-// Sum of one double per thread, fixed order, every thread receives it.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  __syncthreads();   // the previous call's readers are done
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = MET_THREADS / 2; s >= 1; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  return red[0];
-}
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
   for (int s = 1; s < 64; s <<= 1) {
@@ -291,24 +222,24 @@ __global__ __launch_bounds__(MET_THREADS) void metrics_finalize_kernel(const uns
     n += s;
     isum += s * (double)k;
   }
-  wp = block_sum(wp, red);
-  wr = block_sum(wr, red);
-  wf = block_sum(wf, red);
-  mp = block_sum(mp, red);
-  mr = block_sum(mr, red);
-  mf = block_sum(mf, red);
-  present = block_sum(present, red);
-  correct = block_sum(correct, red);
-  n = block_sum(n, red);
-  isum = block_sum(isum, red);
-  ss_res = block_sum(ss_res, red);
+  wp = qt_block_sum<MET_THREADS>(wp, red);
+  wr = qt_block_sum<MET_THREADS>(wr, red);
+  wf = qt_block_sum<MET_THREADS>(wf, red);
+  mp = qt_block_sum<MET_THREADS>(mp, red);
+  mr = qt_block_sum<MET_THREADS>(mr, red);
+  mf = qt_block_sum<MET_THREADS>(mf, red);
+  present = qt_block_sum<MET_THREADS>(present, red);
+  correct = qt_block_sum<MET_THREADS>(correct, red);
+  n = qt_block_sum<MET_THREADS>(n, red);
+  isum = qt_block_sum<MET_THREADS>(isum, red);
+  ss_res = qt_block_sum<MET_THREADS>(ss_res, red);
   const double mean = n > 0.0 ? isum / n : 0.0;
   double ss_tot = 0.0;
   for (int k = t; k < C; k += MET_THREADS) {
     const double d = (double)k - mean;
     ss_tot += (double)sup[k] * (d * d);
   }
-  ss_tot = block_sum(ss_tot, red);
+  ss_tot = qt_block_sum<MET_THREADS>(ss_tot, red);
   if (t == 0) {
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     double* __restrict__ o = report + 4 * (size_t)C;
@@ -329,8 +260,6 @@ __global__ __launch_bounds__(MET_THREADS) void metrics_finalize_kernel(const uns
     o[11] = present;
   }
 }
-
-inline int met_lanes(int C) { return C <= 16 ? 1 : C <= 64 ? 16 : 64; }
 
 }  // namespace
 
@@ -358,15 +287,7 @@ extern "C" int qt_metrics_update(const qt_metrics_desc* desc, const float* logit
   QT_CHECK_ARG((labels != nullptr) == (state != nullptr), "qt_metrics_update: labels and state go together (got %s only)",
                labels ? "labels" : "a state");
   QT_CHECK_ARG(state || probs || confidence || pred_out, "qt_metrics_update: nothing to produce (no state and no output)");
-  QT_CHECK_ARG(rows >= 1 && C >= 1, "qt_metrics_update: needs rows >= 1 and C >= 1 (got %lld x %d)", rows, C);
-  if (C > MET_MAX_C) {
-    qt_set_error("qt_metrics_update: C = %d classes; at most %d are handled", C, MET_MAX_C);
-    return QT_ERR_UNSUPPORTED;
-  }
-  if (rows > MET_MAX_ROWS) {
-    qt_set_error("qt_metrics_update: %lld rows; at most %lld are handled in one call", rows, MET_MAX_ROWS);
-    return QT_ERR_UNSUPPORTED;
-  }
+  if (int rc = qt_check_rows_classes("qt_metrics_update", rows, C, MET_MAX_C, MET_MAX_ROWS)) return rc;
   QT_CHECK_ARG(!logits || ld >= C, "qt_metrics_update: row stride %lld < C = %d", ld, C);
   QT_CHECK_ARG(!probs || ld_probs >= C, "qt_metrics_update: probs row stride %lld < C = %d", ld_probs, C);
   QT_CHECK_ARG(!misaligned(logits, 3) && !misaligned(probs, 3) && !misaligned(confidence, 3) && !misaligned(pred_in, 7) &&
@@ -388,14 +309,10 @@ extern "C" int qt_metrics_update(const qt_metrics_desc* desc, const float* logit
   a.conf = confidence;
   a.pred_out = pred_out;
   if (logits) {
-    const int lanes = met_lanes(C);
-    const long long tiles = (rows + MET_THREADS / lanes - 1) / (MET_THREADS / lanes);
-    const dim3 grid((unsigned)(tiles < MET_MAX_BLOCKS ? tiles : MET_MAX_BLOCKS));
-    switch (lanes) {
-      case 1: hipLaunchKernelGGL((metrics_logits_kernel<1, 16>), grid, dim3(MET_THREADS), 0, s, a); break;
-      case 16: hipLaunchKernelGGL((metrics_logits_kernel<16, 4>), grid, dim3(MET_THREADS), 0, s, a); break;
-      default: hipLaunchKernelGGL((metrics_logits_kernel<64, 16>), grid, dim3(MET_THREADS), 0, s, a); break;
-    }
+    const dim3 grid((unsigned)qt_grid_for(rows, MET_THREADS / qt_row_lanes(C), MET_MAX_BLOCKS));
+    qt_by_row_lanes<MET_MAX_C>(C, [&](auto L, auto P) {
+      hipLaunchKernelGGL((metrics_logits_kernel<decltype(L)::value, decltype(P)::value>), grid, dim3(MET_THREADS), 0, s, a);
+    });
   } else {
     const dim3 grid((unsigned)qt_grid_for(rows, MET_THREADS, MET_MAX_BLOCKS));
     if (C <= MET_LDS_C) hipLaunchKernelGGL(metrics_pred_kernel<true>, grid, dim3(MET_THREADS), 0, s, a);
@@ -408,10 +325,7 @@ extern "C" int qt_metrics_update(const qt_metrics_desc* desc, const float* logit
 extern "C" int qt_metrics_finalize(const unsigned long long* state, int C, double* report, void* stream) {
   QT_CHECK_ARG(state && report, "qt_metrics_finalize: null state / report");
   QT_CHECK_ARG(C >= 1, "qt_metrics_finalize: needs C >= 1 (got %d)", C);
-  if (C > MET_MAX_C) {
-    qt_set_error("qt_metrics_finalize: C = %d classes; at most %d are handled", C, MET_MAX_C);
-    return QT_ERR_UNSUPPORTED;
-  }
+  if (int rc = qt_check_class_cap("qt_metrics_finalize", C, MET_MAX_C)) return rc;
   QT_CHECK_ARG(!misaligned(state, 7) && !misaligned(report, 7), "qt_metrics_finalize: state and report must be 8-byte aligned");
   hipLaunchKernelGGL(metrics_finalize_kernel, dim3(1), dim3(MET_THREADS), 0, static_cast<hipStream_t>(stream), state, C, report);
   QT_CHECK_LAUNCH();

@@ -138,6 +138,9 @@ __device__ __forceinline__ float qt_row16_sum(float v) {
   return v;
 }
 
+// index of the highest set bit of a non-zero mask (a ballot's last qualifying lane)
+__device__ __forceinline__ int top_bit(unsigned long long m) { return 63 - __clzll((long long)m); }
+
 template <typename T> __device__ __forceinline__ float qt_to_f32(T v);
 template <> __device__ __forceinline__ float qt_to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float qt_to_f32<bf16_t>(bf16_t v) { return (float)v; }

@@ -5,9 +5,9 @@
 //     hist[C][2][K]   counted rows by q(p_k), side 1 = rows whose label is k      rank[C]   counted rows by the true class's rank
 //     cal[M][3]       rows / hits / integer confidence sum per confidence bin     five counters
 //
-// Update, one launch per batch.  Rows map to lanes as in metrics.hip (one thread per row for C <= 16, a 16-lane DPP row
-// above) and the softmax of QT_SCORES_LOGITS is metrics_logits_kernel's: same lane mapping, same summation order, the
-// helpers of qt_rowgroup.h, so p has the bits qt_metrics_update writes to probs.  Two routes to the same integers:
+// Update, one launch per batch.  Rows map to lanes by qt_rowgroup.h's rule (one thread per row for C <= 16, a 16-lane DPP
+// row above) and the softmax of QT_SCORES_LOGITS is metrics_logits_kernel's because both are qt_row_load, qt_row_argmax and
+// qt_row_softmax, so p has the bits qt_metrics_update writes to probs.  Two routes to the same integers:
 //   direct      a workgroup walks row tiles with a grid stride; each lane adds its (k, side, q) cell with one 64-bit global
 //               atomic, the writer lane of a row its rank and calibration cells; the counters go through ballots into LDS
 //               and leave once per workgroup.
@@ -62,8 +62,6 @@ __host__ __device__ inline size_t sc_hist_cells(int C, int K) { return 2 * (size
 __device__ __forceinline__ int sc_q(float p, int K) { return min(K - 1, (int)(p * (float)K)); }
 // the calibration bin of a confidence in [0, 1]: the product is rounded to f32 once
 __device__ __forceinline__ int sc_bin(float conf, int M) { return min(M - 1, (int)(conf * (float)M)); }
-// qt_timeline_decode's integer confidence: rint(clamp(x, 0, 1) * 65536)
-__device__ __forceinline__ unsigned sc_conf_q(float x) { return (unsigned)(int)rintf(fminf(fmaxf(x, 0.f), 1.f) * 65536.0f); }
 
 template <int PER> struct RowEval {
   int cls;          // ROW_*, the same in every lane of the row
@@ -79,42 +77,14 @@ __device__ __forceinline__ void eval_row(const ScArgs& a, long long row, int sub
   const int C = a.C;
   const float* __restrict__ zr = a.s + row * a.ld;
   float z[PER];
+  qt_row_load<LANES, PER>(zr, C, sub, z);
 #pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int k = j * LANES + sub;
-    z[j] = k < C ? zr[k] : 0.f;
-  }
+  for (int j = 0; j < PER; ++j) r.p[j] = z[j];   // (0 in the lanes past C, and the softmax leaves them so)
   if (LOGITS) {
-    // metrics_logits_kernel's softmax: m = z[argmax], e_k = expf(z_k - m), s = sum e_k, p_k = e_k / s
-    float bv = z[0];
-    int bi = sub;
-    if (sub >= C) { bv = -INFINITY; bi = INT32_MAX; }
-#pragma unroll
-    for (int j = 1; j < PER; ++j) {
-      const int k = j * LANES + sub;
-      if (k < C && qt_arg_beats(z[j], k, bv, bi)) { bv = z[j]; bi = k; }
-    }
-    qt_group_argmax<LANES>(bv, bi);
-    const float m = bv;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int k = j * LANES + sub;
-      r.p[j] = 0.f;
-      if (k < C) {
-        r.p[j] = expf(z[j] - m);
-        s += r.p[j];
-      }
-    }
-    s = qt_group_sum<LANES>(s);
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const int k = j * LANES + sub;
-      if (k < C) r.p[j] = r.p[j] / s;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < PER; ++j) r.p[j] = z[j];
+    float m;
+    int at;
+    qt_row_argmax<LANES, PER>(z, C, sub, m, at);
+    qt_row_softmax<LANES, PER>(r.p, C, sub, m);
   }
   bool bad = false;
 #pragma unroll
@@ -145,26 +115,7 @@ __device__ __forceinline__ void eval_row(const ScArgs& a, long long row, int sub
   }
   r.rank = qt_group_sum_int<LANES>(above);
   // pred = argmax of p in the loss head's order, conf = p[pred]
-  float bv = r.p[0];
-  int bi = sub;
-  if (sub >= C) { bv = -INFINITY; bi = INT32_MAX; }
-#pragma unroll
-  for (int j = 1; j < PER; ++j) {
-    const int k = j * LANES + sub;
-    if (k < C && qt_arg_beats(r.p[j], k, bv, bi)) { bv = r.p[j]; bi = k; }
-  }
-  qt_group_argmax<LANES>(bv, bi);
-  r.pred = bi;
-  r.conf = bv;
-}
-
-// the four row counters: one LDS atomic per wave, tile and class.  Every lane of the wave must call it.
-__device__ __forceinline__ void count_rows(int cls, unsigned* cnt) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const unsigned long long b = __ballot(cls == k);
-    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&cnt[k], (unsigned)__popcll(b));
-  }
+  qt_row_argmax<LANES, PER>(r.p, C, sub, r.conf, r.pred);
 }
 
 template <int LANES, int PER, bool LOGITS>
@@ -196,10 +147,10 @@ __global__ __launch_bounds__(SC_THREADS) void scores_direct_kernel(ScArgs a) {
         unsigned long long* __restrict__ cb = cal + 3 * sc_bin(r.conf, a.M);
         atomicAdd(&cb[0], 1ull);
         if (r.pred == r.y) atomicAdd(&cb[1], 1ull);
-        atomicAdd(&cb[2], (unsigned long long)sc_conf_q(r.conf));
+        atomicAdd(&cb[2], (unsigned long long)qt_conf_q(r.conf));
       }
     }
-    count_rows(live && sub == 0 ? r.cls : ROW_NONE, cnt);
+    qt_count_rows<4>(live && sub == 0 ? r.cls : ROW_NONE, cnt);
   }
   __syncthreads();
   unsigned long long* __restrict__ ctr = cal + 3 * a.M;
@@ -243,9 +194,9 @@ __global__ __launch_bounds__(SC_THREADS) void scores_private_kernel(ScArgs a) {
         unsigned* cb = cal_l + 3 * sc_bin(r.conf, a.M);
         atomicAdd(&cb[0], 1u);
         if (r.pred == r.y) atomicAdd(&cb[1], 1u);
-        atomicAdd(&cb[2], sc_conf_q(r.conf));
+        atomicAdd(&cb[2], (unsigned)qt_conf_q(r.conf));
       }
-      count_rows(live && sub == 0 ? r.cls : ROW_NONE, cnt);
+      qt_count_rows<4>(live && sub == 0 ? r.cls : ROW_NONE, cnt);
     }
   }
   __syncthreads();
@@ -295,20 +246,6 @@ __device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long
   }
   return before + inc - v;
 }
-// Sum of one double per thread, fixed order (metrics.hip's tree), every thread receives it.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = SC_THREADS / 2; s >= 1; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __device__ __forceinline__ double sc_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // report: [0, C) auc, [C, 2C) average precision, [2C, 3C) support, [3C, 4C) top-k, [4C, 4C + 3M) calibration count /
@@ -404,7 +341,7 @@ __global__ __launch_bounds__(SC_THREADS) void scores_finalize_kernel(const unsig
       ap += ((double)p / (double)P) * (tp / (tp + fp));
     }
   }
-  ap = block_sum(ap, red);
+  ap = qt_block_sum<SC_THREADS>(ap, red);
   if (t == 0) {
     report[k] = P && N ? (double)A2 / (double)(2ull * P * N) : sc_nan();
     report[C + k] = P ? ap : sc_nan();
@@ -453,10 +390,8 @@ int launch_update(const ScArgs& a, bool privatised, hipStream_t s) {
     const dim3 grid((unsigned)((a.rows + SC_SLICE - 1) / SC_SLICE), (unsigned)a.C);
     hipLaunchKernelGGL((scores_private_kernel<LANES, PER, LOGITS>), grid, dim3(SC_THREADS), lds, s, a);
   } else {
-    constexpr int RPB = SC_THREADS / LANES;
-    const long long tiles = (a.rows + RPB - 1) / RPB;
-    hipLaunchKernelGGL((scores_direct_kernel<LANES, PER, LOGITS>), dim3((unsigned)(tiles < SC_MAX_BLOCKS ? tiles : SC_MAX_BLOCKS)),
-                       dim3(SC_THREADS), 0, s, a);
+    const dim3 grid((unsigned)qt_grid_for(a.rows, SC_THREADS / LANES, SC_MAX_BLOCKS));
+    hipLaunchKernelGGL((scores_direct_kernel<LANES, PER, LOGITS>), grid, dim3(SC_THREADS), 0, s, a);
   }
   QT_CHECK_LAUNCH();
   return QT_OK;
@@ -490,15 +425,7 @@ extern "C" int qt_scores_update(const qt_scores_desc* desc, const float* scores,
   QT_CHECK_ARG(desc->route >= QT_SCORES_ROUTE_AUTO && desc->route <= QT_SCORES_ROUTE_PRIVATE, "qt_scores_update: route %d outside 0 .. 2",
                desc->route);
   QT_CHECK_ARG(scores && labels && state, "qt_scores_update: null scores / labels / state");
-  QT_CHECK_ARG(rows >= 1 && C >= 1, "qt_scores_update: needs rows >= 1 and C >= 1 (got %lld x %d)", rows, C);
-  if (C > SC_MAX_C) {
-    qt_set_error("qt_scores_update: C = %d classes; at most %d are handled", C, SC_MAX_C);
-    return QT_ERR_UNSUPPORTED;
-  }
-  if (rows > SC_MAX_ROWS) {
-    qt_set_error("qt_scores_update: %lld rows; at most %lld are handled in one call", rows, SC_MAX_ROWS);
-    return QT_ERR_UNSUPPORTED;
-  }
+  if (int rc = qt_check_rows_classes("qt_scores_update", rows, C, SC_MAX_C, SC_MAX_ROWS)) return rc;
   QT_CHECK_ARG(ld >= C, "qt_scores_update: row stride %lld < C = %d", ld, C);
   QT_CHECK_ARG(!misaligned(scores, 3) && !misaligned(labels, 7) && !misaligned(state, 7),
                "qt_scores_update: scores must be 4-byte aligned, labels and state 8-byte");
@@ -516,18 +443,17 @@ extern "C" int qt_scores_update(const qt_scores_desc* desc, const float* scores,
   const bool privatised = desc->route == QT_SCORES_ROUTE_AUTO ? rows >= QT_SCORES_AUTO_PRIVATE_ROWS : desc->route == QT_SCORES_ROUTE_PRIVATE;
   const bool logits = desc->kind == QT_SCORES_LOGITS;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (C <= 16) return logits ? launch_update<1, 16, true>(a, privatised, s) : launch_update<1, 16, false>(a, privatised, s);
-  return logits ? launch_update<16, 4, true>(a, privatised, s) : launch_update<16, 4, false>(a, privatised, s);
+  return qt_by_row_lanes<SC_MAX_C>(C, [&](auto L, auto P) {
+    constexpr int LANES = decltype(L)::value, PER = decltype(P)::value;
+    return logits ? launch_update<LANES, PER, true>(a, privatised, s) : launch_update<LANES, PER, false>(a, privatised, s);
+  });
 }
 
 extern "C" int qt_scores_finalize(const unsigned long long* state, int C, int bits, int cal_bins, double* report, long long* curves,
                                   void* stream) {
   QT_CHECK_ARG(state && report, "qt_scores_finalize: null state / report");
   QT_CHECK_ARG(C >= 1, "qt_scores_finalize: needs C >= 1 (got %d)", C);
-  if (C > SC_MAX_C) {
-    qt_set_error("qt_scores_finalize: C = %d classes; at most %d are handled", C, SC_MAX_C);
-    return QT_ERR_UNSUPPORTED;
-  }
+  if (int rc = qt_check_class_cap("qt_scores_finalize", C, SC_MAX_C)) return rc;
   QT_CHECK_ARG(bits >= SC_MIN_BITS && bits <= SC_MAX_BITS, "qt_scores_finalize: bits = %d outside %d .. %d", bits, SC_MIN_BITS, SC_MAX_BITS);
   QT_CHECK_ARG(cal_bins >= 1 && cal_bins <= SC_MAX_M, "qt_scores_finalize: cal_bins = %d outside 1 .. %d", cal_bins, SC_MAX_M);
   QT_CHECK_ARG(!misaligned(state, 7) && !misaligned(report, 7) && !misaligned(curves, 7),

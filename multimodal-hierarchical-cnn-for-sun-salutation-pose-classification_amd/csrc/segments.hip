@@ -70,8 +70,6 @@ struct EncodeArgs {
 };
 
 __device__ __forceinline__ int known_class(long long v, int C) { return v >= 0 && v < (long long)C ? (int)v : -1; }
-// index of the highest set bit of a non-zero mask
-__device__ __forceinline__ int top_bit(unsigned long long m) { return 63 - __clzll((long long)m); }
 __device__ __forceinline__ int video_length(const int* lengths, int b, int T) { return lengths ? min(max(lengths[b], 0), T) : T; }
 
 // The runs of row[0 .. len): put(slot, start, length, class) is called once per run by the thread at its last frame, slots

@@ -13,8 +13,8 @@
 //      thread adds its class's n = min(W, seen + f + 1) values from the oldest row to the newest, afresh for every frame, and
 //      divides once: adds and one IEEE division, nothing for -ffp-contract to fuse.  W C adds per frame are nothing beside
 //      the forward pass, and a running sum would drift, keep a NaN for ever and depend on where a call starts;
-//   3. the argmax runs across the class lanes in loss.hip's total order; the value that travels with the index is the
-//      confidence;
+//   3. the argmax runs across the class lanes in qt_rowgroup.h's total order (qt_group_argmax: the loss head's and the
+//      meters'); the value that travels with the index is the confidence;
 //   4. the workgroup that owns the stream's last frame copies the last W - 1 LDS rows to hist_out (rows in front of an empty
 //      stream are the zeros staged in 1).
 // Decode.  One workgroup of one wave per stream walks its frames in trips of TL_TRIP = 64, lane = frame, the pred /
@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "qt_common.h"
+#include "qt_rowgroup.h"
 
 namespace {
 
@@ -71,42 +72,6 @@ struct DecodeArgs {
   int T, C, min_run, capacity, flush;
   float min_conf;
 };
-
-// ---- the argmax of loss.hip (same total order): a NaN beats every number, then the larger value, then the lower index ----
-__device__ __forceinline__ bool arg_beats(float av, int ai, float bv, int bi) {
-  const bool an = av != av, bn = bv != bv;
-  if (an != bn) return an;
-  if (!an && av != bv) return av > bv;
-  return ai < bi;
-}
-template <int CTRL> __device__ __forceinline__ void arg_dpp(float& v, int& i) {
-  const float ov = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-  const int oi = __builtin_amdgcn_update_dpp(0, i, CTRL, 0xf, 0xf, false);
-  if (arg_beats(ov, oi, v, i)) {
-    v = ov;
-    i = oi;
-  }
-}
-// Over the LANES lanes of a frame, every lane receives the winner.  The order is total, so any tree gives the same pair: the
-// four DPP steps of qt_row16_sum inside a row (no LDS crossbar), then two wave shuffles for LANES == 64.  Every lane of the
-// wave must call it.
-template <int LANES> __device__ __forceinline__ void group_argmax(float& v, int& i) {
-  arg_dpp<0x140>(v, i);   // row_mirror
-  arg_dpp<0x141>(v, i);   // row_half_mirror
-  arg_dpp<0x1b>(v, i);    // quad_perm [3,2,1,0]
-  arg_dpp<0xb1>(v, i);    // quad_perm [1,0,3,2]
-  if (LANES == 64) {
-#pragma unroll
-    for (int s = 16; s < 64; s <<= 1) {
-      const float ov = __shfl_xor(v, s, 64);
-      const int oi = __shfl_xor(i, s, 64);
-      if (arg_beats(ov, oi, v, i)) {
-        v = ov;
-        i = oi;
-      }
-    }
-  }
-}
 
 template <int LANES>
 __global__ __launch_bounds__(TL_THREADS) void timeline_smooth_kernel(SmoothArgs a) {
@@ -166,7 +131,7 @@ __global__ __launch_bounds__(TL_THREADS) void timeline_smooth_kernel(SmoothArgs 
     }
     float bv = m;
     int bi = idx;
-    group_argmax<LANES>(bv, bi);
+    qt_group_argmax<LANES>(bv, bi);
     if (live) {
       const long long at = (long long)b * a.T + t0 + f;
       if (a.smoothed && sub < C) a.smoothed[at * a.ld_s + sub] = m;
@@ -187,14 +152,6 @@ __global__ __launch_bounds__(TL_THREADS) void timeline_smooth_kernel(SmoothArgs 
     if (tid == 0) a.hist_count_out[b] = min(back, seen + a.T);
   }
 }
-
-// q(x) = rint(clamp(x, 0, 1) * 65536), q(NaN) = 0: the product is exact, so is its rounding
-__device__ __forceinline__ int tl_q(float x) {
-  if (x != x) return 0;
-  return (int)rintf(fminf(fmaxf(x, 0.f), 1.f) * 65536.0f);
-}
-// index of the highest set bit of a non-zero mask
-__device__ __forceinline__ int top_bit(unsigned long long m) { return 63 - __clzll((long long)m); }
 
 __device__ __forceinline__ void put_segment(const DecodeArgs& a, int b, long long slot, long long start, long long len,
                                             long long label, long long conf) {
@@ -293,7 +250,7 @@ __global__ __launch_bounds__(TL_TRIP) void timeline_decode_kernel(DecodeArgs a) 
       const int s_prev = from_lane_before(stable, stable_in);
       const bool change = act && stable != s_prev;
       const unsigned long long changes = __ballot(change);
-      const int q = act ? tl_q(conf) : 0;
+      const int q = act ? qt_conf_q(conf) : 0;
       const int incl = wave_prefix_sum(q);   // 64 x 65536 fits
       const int excl = incl - q;
       // the segment in front of this lane: from the last change before it, or from the carry

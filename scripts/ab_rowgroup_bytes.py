@@ -1,0 +1,260 @@
+#!/usr/bin/env python
+"""Two builds of the library, the same bytes (developer aid, not a test: a clean checkout has no second library).
+
+One process loads two builds of libqtcnn_hip.so with ctypes and calls every entry point of loss.hip, metrics.hip, scores.hip,
+timeline.hip and segments.hip in both on the same seeded inputs (tests/_rowgroup_rows.py: ties 16 lanes and 1 lane apart, a
+NaN, two +inf, rows of -inf, logits scaled by 90).  Every output starts from the same byte pattern (0xA5, zeros where the
+contract has the caller zero a state) and is compared as bytes.
+
+    bash scripts/ab_build.sh        # <pkg>/libqtcnn_prev.so = the committed tree, libqtcnn_hip.so = the working tree
+    python scripts/ab_rowgroup_bytes.py [--a <pkg>/libqtcnn_prev.so] [--b <pkg>/libqtcnn_hip.so]
+
+Prints one line per family and the number of buffers compared; exit status 1 if any differ."""
+import argparse
+import ctypes
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+PKG = "multimodal-hierarchical-cnn-for-sun-salutation-pose-classification_amd"
+
+ROWS = (1, 63, 257, 300)
+CLASSES = (1, 12, 16, 17, 64, 65, 1024)
+FILL = 0xA5
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--a", default=os.path.join(ROOT, PKG, "libqtcnn_prev.so"))
+    ap.add_argument("--b", default=os.path.join(ROOT, PKG, "libqtcnn_hip.so"))
+    args = ap.parse_args()
+    import torch
+    import _rowgroup_rows as RR
+    if not torch.cuda.is_available():
+        raise SystemExit("ab_rowgroup_bytes.py compares on the GPU; there is none")
+    dev = torch.device("cuda:0")
+    mods = {n: importlib.import_module(f"{PKG}.{n}") for n in ("loss", "metrics", "scores", "timeline", "segments")}
+    libs = []
+    for path in (args.a, args.b):
+        L = ctypes.CDLL(path)
+        for m in mods.values():
+            m.bind(L)
+        L.qt_last_error.restype = ctypes.c_char_p
+        libs.append(L)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def ptr(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def out(shape, dt, zero=False):
+        t = torch.empty(shape, dtype=dt, device=dev)
+        t.view(torch.uint8).fill_(0 if zero else FILL)
+        return t
+
+    def ok(L, status, what):
+        if status != 0:
+            raise SystemExit(f"{what}: status {status}: {L.qt_last_error().decode(errors='replace')}")
+
+    compared = {}
+    differ = []
+
+    def both(family, what, call):
+        """call(L) -> list of device tensors; run for both libraries and compare every buffer's bytes"""
+        got = [[b.contiguous().view(-1).view(torch.uint8) for b in call(L)] for L in libs]
+        assert len(got[0]) == len(got[1])
+        for i, (x, y) in enumerate(zip(*got)):
+            compared[family] = compared.get(family, 0) + 1
+            if not torch.equal(x, y):
+                differ.append((family, what, i))
+
+    # ---- loss ------------------------------------------------------------------------------------------------------------
+    ML = mods["loss"]
+    for rows in ROWS:
+        for C in CLASSES:
+            z = RR.make_logits(rows, C, seed=rows + C)
+            rng = np.random.default_rng(rows * 1031 + C)
+            y = rng.integers(0, C, rows).astype(np.int64)
+            y[rows // 2] = -100                   # ignored (cross-entropy), out of range (focal)
+            y[rows // 3] = C + 3                  # out of range
+            w = (0.5 + rng.random(C)).astype(np.float32)
+            d_z, d_y, d_w = up(z), up(y), up(w)
+            for kind in (0, 1):
+                for weighted in (False, True):
+                    for eps in ((0.0, 0.1) if kind == 0 else (0.0,)):
+                        for red in (0, 1, 2):
+                            desc = ML.LossDesc(0, kind, red, -100, eps, 2.0, d_w.data_ptr() if weighted else None)
+
+                            def call(L, desc=desc, red=red):
+                                wsb = L.qt_loss_workspace_bytes(rows, C)
+                                ws = out(max(wsb, 8), torch.uint8)
+                                loss = out(rows if red == 2 else 1, torch.float32)
+                                state, stats = out((rows, 2), torch.float32), out(3, torch.float64)
+                                pred, meter = out(rows, torch.int64), out(4, torch.float64, zero=True)
+                                ok(L, L.qt_loss_forward(ctypes.byref(desc), ptr(d_z), C, ptr(d_y), rows, C, ptr(loss), ptr(state),
+                                                        ptr(stats), ptr(pred), ptr(meter), ptr(ws), wsb, stream), "qt_loss_forward")
+                                g = up(np.full(rows if red == 2 else 1, 0.75, np.float32))
+                                dz = out((rows, C + 1), torch.float32)
+                                ok(L, L.qt_loss_backward(ctypes.byref(desc), ptr(d_z), C, ptr(d_y), rows, C, ptr(state), ptr(stats),
+                                                         ptr(g), ptr(dz), C + 1, stream), "qt_loss_backward")
+                                return [loss, state, stats, pred, meter, ws, dz]
+                            both("loss", (rows, C, kind, weighted, eps, red), call)
+
+    # ---- metrics ---------------------------------------------------------------------------------------------------------
+    MM = mods["metrics"]
+    for rows in ROWS:
+        for C in CLASSES:
+            z = RR.make_logits(rows, C, seed=rows + C + 1)
+            rng = np.random.default_rng(rows * 1033 + C)
+            y = rng.integers(0, C, rows).astype(np.int64)
+            y[rows // 2] = -100
+            y[rows // 3] = C
+            p_in = rng.integers(-1, C + 1, rows).astype(np.int64)
+            d_z, d_y, d_p = up(z), up(y), up(p_in)
+            desc = MM.MetricsDesc(0, -100)
+            for outputs in range(8):
+
+                def call(L, outputs=outputs):
+                    state = out(C * C + 4, torch.int64, zero=True)
+                    probs = out((rows, C + 2), torch.float32) if outputs & 1 else None
+                    conf = out(rows, torch.float32) if outputs & 2 else None
+                    pred = out(rows, torch.int64) if outputs & 4 else None
+                    for _ in range(2):   # the state is added to
+                        ok(L, L.qt_metrics_update(ctypes.byref(desc), ptr(d_z), C, None, ptr(d_y), rows, C, ptr(state), ptr(probs),
+                                                  C + 2, ptr(conf), ptr(pred), stream), "qt_metrics_update")
+                    report = out(4 * C + 12, torch.float64)
+                    ok(L, L.qt_metrics_finalize(ptr(state), C, ptr(report), stream), "qt_metrics_finalize")
+                    bufs = [state, report] + [b for b in (probs, conf, pred) if b is not None]
+                    if outputs:   # and without a state
+                        o2 = [out(b.shape, b.dtype) for b in bufs[2:]]
+                        it = iter(o2)
+                        probs2 = next(it) if outputs & 1 else None
+                        conf2 = next(it) if outputs & 2 else None
+                        pred2 = next(it) if outputs & 4 else None
+                        ok(L, L.qt_metrics_update(ctypes.byref(desc), ptr(d_z), C, None, None, rows, C, None, ptr(probs2), C + 2,
+                                                  ptr(conf2), ptr(pred2), stream), "qt_metrics_update (no state)")
+                        bufs += o2
+                    return bufs
+                both("metrics", (rows, C, outputs), call)
+
+            def call_pred(L):
+                state = out(C * C + 4, torch.int64, zero=True)
+                ok(L, L.qt_metrics_update(ctypes.byref(desc), None, 0, ptr(d_p), ptr(d_y), rows, C, ptr(state), None, 0, None, None,
+                                          stream), "qt_metrics_update (pred_in)")
+                report = out(4 * C + 12, torch.float64)
+                ok(L, L.qt_metrics_finalize(ptr(state), C, ptr(report), stream), "qt_metrics_finalize")
+                return [state, report]
+            both("metrics", (rows, C, "pred_in"), call_pred)
+
+    # ---- scores ----------------------------------------------------------------------------------------------------------
+    MS = mods["scores"]
+    M = 15
+    for rows in ROWS:
+        for C in [c for c in CLASSES if c <= 64]:
+            z = RR.make_logits(rows, C, seed=rows + C + 2)
+            rng = np.random.default_rng(rows * 1039 + C)
+            y = rng.integers(0, C, rows).astype(np.int64)
+            y[rows // 2] = -100
+            y[rows // 3] = C
+            with np.errstate(all="ignore"):
+                e = np.exp(z - np.where(np.isfinite(z), z, -np.inf).max(axis=1, keepdims=True))
+                pr = (e / e.sum(axis=1, keepdims=True)).astype(np.float32)   # NaN and out-of-range rows stay in: they are classed
+            d_y = up(y)
+            for kind, data in ((0, up(z)), (1, up(pr))):
+                for route in (1, 2):
+                    for bits in (4, 12, 14):
+                        desc = MS.ScoresDesc(0, kind, bits, M, route, -100)
+
+                        def call(L, desc=desc, data=data, bits=bits):
+                            words = L.qt_scores_state_bytes(C, bits, M) // 8
+                            state = out(words, torch.int64, zero=True)
+                            for _ in range(2):
+                                ok(L, L.qt_scores_update(ctypes.byref(desc), ptr(data), C, ptr(d_y), rows, C, ptr(state), stream),
+                                   "qt_scores_update")
+                            report = out(L.qt_scores_report_bytes(C, M) // 8, torch.float64)
+                            curves = out((C, 2, 1 << bits), torch.int64)
+                            ok(L, L.qt_scores_finalize(ptr(state), C, bits, M, ptr(report), ptr(curves), stream), "qt_scores_finalize")
+                            return [state, report, curves]
+                        both("scores", (rows, C, kind, route, bits), call)
+
+    # ---- timeline --------------------------------------------------------------------------------------------------------
+    MT = mods["timeline"]
+    for rows in ROWS:
+        for C in [c for c in CLASSES if c <= 64]:
+            for W in (1, 5, 64):
+                batch = 2
+                rng = np.random.default_rng(rows * 1049 + C * 7 + W)
+                pr = rng.random((batch, rows, C)).astype(np.float32)
+                pr /= pr.sum(axis=2, keepdims=True)
+                if rows >= 4:
+                    pr[0, rows // 2] = np.nan
+                    pr[1, rows // 3] = np.inf
+                    pr[0, 0] = np.float32(0.125)
+                    if C > 16:
+                        pr[1, rows - 1, [0, 16]] = np.float32(2.0)   # two lanes of the wave, the same lane of two rows
+                    if C > 1:
+                        pr[0, rows - 1, [0, 1]] = np.float32(2.0)
+                d_pr = up(pr)
+                hist = up(rng.random((batch, max(W - 1, 1), C)).astype(np.float32))
+                hcnt = up(np.array([W // 2, W - 1], np.int32))
+                for with_hist in (False, True):
+
+                    def call(L, with_hist=with_hist):
+                        desc = MT.TimelineDesc(batch, rows, C, W, 2, 0.3, 16, 1)
+                        sm = out((batch, rows, C), torch.float32)
+                        pred, conf = out((batch, rows), torch.int64), out((batch, rows), torch.float32)
+                        ho, hc = out((batch, max(W - 1, 1), C), torch.float32), out(batch, torch.int32)
+                        ok(L, L.qt_timeline_smooth(ctypes.byref(desc), ptr(d_pr), C, ptr(hist) if with_hist else None,
+                                                   ptr(hcnt) if with_hist else None, ptr(ho), ptr(hc), ptr(sm), C, ptr(pred),
+                                                   ptr(conf), stream), "qt_timeline_smooth")
+                        state = out((batch, 8), torch.int64, zero=True)
+                        stable, seg = out((batch, rows), torch.int64), out((batch, 16, 4), torch.int64)
+                        ok(L, L.qt_timeline_decode(ctypes.byref(desc), ptr(pred), ptr(conf), ptr(state), ptr(stable), ptr(seg),
+                                                   stream), "qt_timeline_decode")
+                        return [sm, pred, conf, ho, hc, state, stable, seg]
+                    both("timeline", (rows, C, W, with_hist), call)
+
+    # ---- segments --------------------------------------------------------------------------------------------------------
+    MG = mods["segments"]
+    for rows in ROWS:      # frames per video
+        for C in (1, 12, 1024):
+            batch = 3
+            rng = np.random.default_rng(rows * 1051 + C)
+            lab = np.repeat(rng.integers(-1, C, (batch, rows // 5 + 1)), 5, axis=1)[:, :rows].astype(np.int64)
+            prd = lab.copy()
+            flip = rng.random((batch, rows)) < 0.1
+            prd[flip] = rng.integers(0, C, int(flip.sum()))
+            lens = up(np.array([rows, rows // 2, 0], np.int32))
+            d_lab, d_prd = up(lab), up(prd)
+            for with_len in (False, True):
+
+                def call(L, with_len=with_len):
+                    desc = MG.make_desc(batch, rows, C, thresholds=(10, 25, 50), capacity=32)
+                    wsb = L.qt_segments_workspace_bytes(ctypes.byref(desc))
+                    ws = out(wsb, torch.uint8)
+                    state, rec = out(10 + 3, torch.int64, zero=True), out((batch, 5 + 3), torch.int64)
+                    ok(L, L.qt_segments_update(ctypes.byref(desc), ptr(d_prd), rows, ptr(d_lab), rows, ptr(lens) if with_len else None,
+                                               ptr(state), ptr(rec), ptr(ws), wsb, stream), "qt_segments_update")
+                    runs, counts = out((batch, 32, 3), torch.int32), out(batch, torch.int32)
+                    ok(L, L.qt_segments_encode(ctypes.byref(desc), ptr(d_prd), rows, ptr(lens) if with_len else None, ptr(runs),
+                                               ptr(counts), stream), "qt_segments_encode")
+                    return [state, rec, ws, runs, counts]
+                both("segments", (rows, C, with_len), call)
+
+    for fam, n in compared.items():
+        bad = [d for d in differ if d[0] == fam]
+        print(f"{fam:9s} {n:6d} buffers compared, {len(bad)} differ")
+    for d in differ[:40]:
+        print("  differs:", d)
+    print(f"total {sum(compared.values())} buffers, {len(differ)} differ")
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == "__main__":
+    main()
