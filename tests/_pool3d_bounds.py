@@ -41,8 +41,9 @@ Shapes (SHAPES) and why:
   L2  T2 B2 H59 W61 C256 S < n < 2 S: the second row of a trip live for some threads and dead for others
   L3  T3 B2 H59 W61 C256, pool_t 2   2 S < n < 3 S: a second trip whose second row is dead; dropped frame, row and column
 
-NOT reached: the 65 536-block cap of the pool kernels and of qt_pack_clip27 needs more than 16.7 M groups (the full-size config-4
-test is its only cover); QTCNN_PACK3D_TILED=0 and QTCNN_POOL3D_APPLY_LIGHT=0 are read once per process and have no setter."""
+The 65 536-block cap of the pool kernels and of qt_pack_clip27 needs more than 16.7 M groups: tests/test_grid_caps_gpu.py reaches
+it with build(.., dims=) of a slab of 4099 images per frame, repeated along the batch (the table of tests/_grid_caps.py; pool_t = 1,
+the grid class).  NOT reached: QTCNN_PACK3D_TILED=0 and QTCNN_POOL3D_APPLY_LIGHT=0 are read once per process and have no setter."""
 import functools
 
 import torch
@@ -399,10 +400,11 @@ def rounding_share(c):
     return float((unrounded[..., TIE_CH] != c["code"][..., TIE_CH]).double().mean())
 
 
-def build(kind, name, pt, dtn):
-    """one (class, shape, pool_t, type): inputs and every reference, float64 on the CPU"""
+def build(kind, name, pt, dtn, dims=None):
+    """one (class, shape, pool_t, type): inputs and every reference, float64 on the CPU.  dims: a (T, B, H, W, C) of the caller's
+    in place of SHAPES[name], drawn with the name's seed (tests/test_grid_caps_gpu.py: the slab its periodic cases repeat)"""
     dt = DTYPES[dtn]
-    T, B, H, W, C = shape(name, pt)
+    T, B, H, W, C = dims or shape(name, pt)
     To, _, Ho, Wo, _ = pooled_shape(T, B, H, W, C, pt)
     seed = {"grid": 1000, "random": 2000}[kind] + 40 * list(SHAPES).index(name) + 4 * pt + (dt == BF16)
     g = _gen(seed)

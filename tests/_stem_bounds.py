@@ -8,10 +8,11 @@ Geometry is fixed at compile time (112 x 112 x 64 -> 56 x 56 x 64, packed image 
 shape.  BATCHES = 1, 3, 11: 11 is the smallest batch at which the one-launch backward gives a workgroup three tiles (both LDS
 buffers reused), lets a workgroup cross an image boundary, puts a last-row tile (rp == 55, whose second pooled row is not
 loaded) into a reused buffer, caps the grids of the reduce (2048) and sums (1024) kernels and takes the tail of the light sums
-kernel's two-element loop (paths(): the kernels' own formulas, asserted by the CPU test).  NOT covered here: the 16384-block cap
-of qt_stem_pool / qt_stem_pool_bwd / qt_stem_bn_bwd_apply needs B >= 42; the batch-256 model tests are its only cover.  The bf16
-instantiation of the general sums kernel is reachable only through a process-wide environment switch that is read once; it is
-left out too.
+kernel's two-element loop (paths(): the kernels' own formulas, asserted by the CPU test).  Not covered here but in
+tests/test_grid_caps_gpu.py (the table of tests/_grid_caps.py): the 16384-block cap of qt_stem_pool_bwd (B = 42) and of
+qt_stem_pool / qt_stem_bn_bwd_apply (B = 168), on the three images of case(kind, 3) repeated, and the back edge of the light
+sums kernel's two-element loop (B = 16).  The bf16 instantiation of the general sums kernel is reachable only through a
+process-wide environment switch that is read once; it is left out.
 
 Two input classes, everything NHWC:
   grid    y = k / 8 + offset[c], k an integer in [-16, 16], offsets in {0, +-1, +-2, +-6}; scale[c] in {+-1, +-2, +-0.5, 0},

@@ -3,7 +3,9 @@ float64 restatement of the same operation on exactly the values the kernel reads
 own f32 arithmetic (tests/_bounds.py; tests/test_kernel_bounds_cpu.py shows that correct f32 arithmetic meets them).  Shapes are
 the smallest that reach every path: both reductions of the statistics (<= 1024 partial rows directly, above that an f32 fold of
 64 rows first), both BatchNorm-backward apply kernels, a grid-stride loop that takes a second trip for some threads only
-(M = 786433, C = 64), the 7-way unrolled average pool with a tail, the dropped row / column and the tie rule of the quadrant pool.
+(bn_act, and bn_bwd_apply in bf16 without a mask, at M = 786433, C = 64; every other capped launch of these files takes its second
+trip in tests/test_grid_caps_gpu.py, see the table of tests/_grid_caps.py), the 7-way unrolled average pool with a tail, the dropped
+row / column and the tie rule of the quadrant pool.
 Every test prints max(|err| / bound); output buffers are pre-filled with NaN and nothing outside the defined range may change.
 
 Reference behaviour: nn.BatchNorm2d / nn.ReLU / nn.AdaptiveAvgPool2d / nn.MaxPool2d(2, 2) / nn.Dropout and their autograd as

@@ -8,9 +8,9 @@ tests/test_pool3d_bounds_cpu.py shows that correct f32 arithmetic passes the sam
 does not.  Every backward kernel gets the REFERENCE's pooled map and codes, so one kernel's error cannot hide another's.  Output
 buffers are pre-filled with NaN / 0xFF and carry a guard row that must stay as it was; tests print max(|err| / bound).
 
-Not reached here (see _pool3d_bounds.py): the 65 536-block cap of the pool kernels and of qt_pack_clip27 (more than 16.7 M groups;
-the full-size config-4 test is its only cover); QTCNN_PACK3D_TILED=0 and QTCNN_POOL3D_APPLY_LIGHT=0, which are read once per
-process and have no setter.
+Not reached here (see _pool3d_bounds.py): the 65 536-block cap of the pool kernels and of qt_pack_clip27 (more than 16.7 M groups:
+tests/test_grid_caps_gpu.py, on a slab of images repeated along the batch); QTCNN_PACK3D_TILED=0 and QTCNN_POOL3D_APPLY_LIGHT=0,
+which are read once per process and have no setter.
 
 Reference behaviour: BatchNorm3d -> ReLU -> MaxPool3d of a conv block of the reference's Quadtree3DCNN (3dcnn/models.py) and
 their autograd; nn.Conv3d's weight layout."""

@@ -8,8 +8,9 @@ last-row tile in a reused buffer, the reduce / sums grids are capped and the lig
 gets the REFERENCE's inputs (argmax codes, y at the maximum), so one kernel's error cannot hide another's.  Output buffers are
 pre-filled with NaN / 0xFF; every test prints max(|err| / bound).
 
-Not reached here (see _stem_bounds.py): the 16384-block cap of the pool / pool-backward / apply kernels (B >= 42) and the bf16
-instantiation of the general sums kernel (a process-wide switch).
+Not reached here (see _stem_bounds.py): the 16384-block cap of the pool / pool-backward / apply kernels (B >= 42 / 168), which
+tests/test_grid_caps_gpu.py reaches on repeated images, and the bf16 instantiation of the general sums kernel (a process-wide
+switch).
 
 Reference behaviour: bn1 -> relu -> maxpool of torchvision's ResNet-18 stem and their autograd, as the reference's QuadtreeCNN
 runs them (Quadtree_from scratch/models.py:224-226)."""
