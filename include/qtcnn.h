@@ -1530,6 +1530,84 @@ int qt_pose_duration_lag_decode(const qt_pose_duration_lag_desc* desc, const flo
                                 const void* carry_in, void* carry_out, long long* lag_path, long long* lag_start,
                                 long long* filtered, long long* score, void* workspace, long long workspace_bytes,
                                 void* stream);
+/* Fixed-lag pose-order posteriors with hold durations, for a loop that hands over a frame or a few per call: for the frame `lag`
+ * frames ago, the row of posterior, class_posterior and begin that qt_pose_duration_posterior would give on the stream up to
+ * now, and for every new frame the lag-0 row and the evidence, at a cost per step that does not grow with the video.  The
+ * reference has no such step.
+ * From qt_pose_duration_lag_decode, unchanged, bit for bit: the descriptor qt_pose_duration_lag_desc, lag, seen, flush,
+ * frames = n >= 0 (0 with flush only), batch * frames <= 2^20 per call, the emitted span
+ *   g0 = max(0, seen - lag),   g1 = flush ? seen + n : max(0, seen + n - lag),   count = g1 - g0
+ * the two caller-owned carry buffers that are swapped between calls, and no lengths argument: all streams advance together.
+ * From qt_pose_duration_posterior, unchanged, bit for bit: probs, ld and the tables with their clamps, the emission integers
+ * e[f][j], T, Dur, DurOpen (Dur when dur_open is NULL) and start in bits, cum and seg, the levels as doubles, the L rule (the
+ * maximum taken out in double; the terms 2^(x - m), their sum and log2 of the sum f32), and the precision of begin, endp (the
+ * exponent formed in double, rounded to f32, 2^ in f32) and occ (double).
+ * Forward, per stream, f = the count of frames consumed since the stream's start:
+ *   Bt[0][j]      = L_i (start[i] + T[i][j])
+ *   Al[f][j]      = L_{d = 1 .. min(D, f)} (Bt[f - d][j] + len + seg(f, d, j)),   len = DurOpen[j][d - 1] where f - d == 0 (the
+ *                   segment touches the stream's start), else Dur[j][d - 1]: the closed level, what qt_pose_duration_posterior
+ *                   computes for f < T
+ *   Al_open[f][j] = the same L with len = DurOpen[j][d - 1] for every d, as if the stream were cut after frame f: that
+ *                   kernel's Al[T] at T = f (dur_open NULL: Al itself)
+ *   Bt[f][j]      = L_i (Al[f][i] + T[i][j]): always from the closed Al
+ *   Z_f           = L_j Al_open[f][j], in ascending j
+ * Window of an emitted frame g (0-based), with last = seen + n - 1 and F = min(g + lag, last) + 1: the posterior's backward
+ * sweep on the prefix [0, F), from f = F - 1 down to f = g only:
+ *   Be[F][j] = 0
+ *   Bs[f][j] = L_{d = 1 .. min(D, F - f)} (len(j, d, f + d) + seg(f + d, d, j) + Be[f + d][j]),   DurOpen where f + d == F or f == 0
+ *   Be[f][i] = L_j (T[i][j] + Bs[f][j])                                           f > g
+ *   begin[f][j] = 2^(Bt[f][j] + Bs[f][j] - Z_F)
+ *   endp[f][j]  = 2^(Al[f][j] + Be[f][j] - Z_F)   f < F;     endp[F][j] = 2^(Al_open[F][j] - Z_F)
+ *   occ[F - 1][j] = endp[F][j];   occ[t][j] = (occ[t + 1][j] + endp[t + 1][j]) - begin[t + 1][j]     (double, descending t)
+ *   lagged[g][j]       = r[j] / R,   r = max(occ[g], 0),   R = the sum of r[j] in ascending j (double);   R <= 0: 1 / S
+ *   lagged_class[g][c] = the sum of lagged[g][j] over state_class[j] == c, in ascending j (f32)
+ *   lagged_begin[g][j] = begin[g][j]: the probability that a hold of j begins at frame g, given lag frames of look-ahead
+ * which reads Bt[f] at g <= f < F, Al[f] at g < f <= F and the emissions of frames g .. F - 1: at most lag + 1 rows, however
+ * old the stream is.  Per new frame f = seen + 1 .. seen + n: filtered[f - 1] is the row that the window (g = f - 1, F = f)
+ * gives, the lag-0 answer, and log2_evidence[f - 1] = Z_f.
+ *   lagged         f32 [batch][count][S], required when count > 0     lagged_class   f32 [batch][count][C], or NULL
+ *   lagged_begin   f32 [batch][count][S], or NULL                     filtered       f32 [batch][n][S], or NULL
+ *   log2_evidence  double [batch][n], or NULL
+ * Carry.  carry_in (read; not read and may be NULL with seen == 0) and carry_out (written in full, the padding zero) must not
+ * overlap.  Per stream, with end = seen + n of the call that writes it: { int64 cum[S] = cum[end]; double ring[D][S]:
+ * Bt[f][j] - cum[f][j] / 256 at row f mod D for the last D values of f, rows never written zero; double gh[lag][S]: the same
+ * quantity of f = end - lag + k in slot k; double al[lag][S]: the closed Al[f] of f = end - lag + 1 + k; double al_open[S] and
+ * double Z: Al_open[end] and Z_end (a flush with frames == 0 starts its windows there; zeros at end == 0); int16 e[lag][S]: the
+ * emissions of frame end - lag + k }, rounded up to 8 bytes: 8 S + 8 D S + 16 lag S + 8 S + 8 + 2 lag S.  Slots of frames in
+ * front of the stream's start (f < 0; f <= 0 for al) are zeros.  qt_pose_duration_lag_smooth_carry_bytes gives the size of one
+ * buffer.  lag, the tables, D and batch are fixed for the life of a stream.
+ * Levels are absolute doubles, as in the whole-video kernel (which is what lets the bits agree); they lose an ulp of a bit per
+ * 2^20 frames or so at 288 bits a frame, so seen + frames may be at most 2^20, that kernel's own limit (9.7 hours at 30 fps).
+ * Contract.  (1) lagged[g], lagged_class[g] and lagged_begin[g] are the BITS of row g of posterior, class_posterior and begin
+ * of qt_pose_duration_posterior on the stream's first F frames; log2_evidence of frame f - 1 is the bits of its log2_evidence
+ * on the first f frames.  (2) For any split of a stream into calls, flush on the last, every output and the final carry are
+ * the bits of one call (one route, no environment switch); a stream alone gives the bits it has in a batch; every run gives
+ * the same bits.  Hence: lag == 0 makes lagged the rows of filtered; a one-call flush of n <= lag + 1 frames is
+ * qt_pose_duration_posterior on them; with D == 1 and dur all zero lagged is the plain chain's lagged posterior
+ * (qt_pose_lag_smooth's rule, up to f32 rounding).
+ * Two launches.  The first, one workgroup of 256 per stream, is qt_pose_duration_posterior's forward step with both Ls over
+ * the same ring rows, the ring from carry_in (Bt[0] at seen == 0); every new frame's row of Bt - cum / 256, closed Al,
+ * Al_open, cum (double, double, double, int64 [batch][n][S] each), Z_f (double [batch][n]) and int16 emissions ([batch][n][S],
+ * rounded up to 8 bytes) go to the workspace; it writes log2_evidence and then carry_out.  The second, one workgroup per
+ * (stream, emitted frame) and with filtered per (stream, new frame), sweeps its window with the same lane map, so that an L
+ * adds in the posterior's order, which depends on S and D alone; it reads the workspace for the frames of this call and
+ * carry_in for older ones and writes its one row of each output.  Windows share nothing, so a window's bits cannot depend on
+ * the split.  qt_pose_duration_lag_smooth_workspace_bytes: 32 batch n S + 8 batch n + 2 batch n S rounded up to 8; 0 at n == 0
+ * and for a descriptor that would be refused (as the carry query).  No atomics, no host synchronisation, no workgroup waits
+ * for another; inputs, carry_in included, are never written; every workspace slot that is read is written in the same call.
+ *
+ * QT_ERR_INVALID_ARG (before any device call, qt_last_error names the argument): what qt_pose_duration_lag_decode refuses,
+ * with lagged in the place of lag_path; misaligned pointers (4 bytes for f32 and int32; 8 for log2_evidence, the carries and
+ * the workspace); an output (carry_out, lagged, lagged_class, lagged_begin, filtered, log2_evidence, workspace) that overlaps
+ * an input or another output (carry_in overlapping carry_out included).  QT_ERR_UNSUPPORTED for more than 2^20 frames in a
+ * call (batch * frames) and for seen + frames > 2^20. */
+long long qt_pose_duration_lag_smooth_carry_bytes(const qt_pose_duration_lag_desc* desc);
+long long qt_pose_duration_lag_smooth_workspace_bytes(const qt_pose_duration_lag_desc* desc);
+int qt_pose_duration_lag_smooth(const qt_pose_duration_lag_desc* desc, const float* probs, long long ld,
+                                const int* state_class, const int* trans, const int* init, const int* dur, const int* dur_open,
+                                const void* carry_in, void* carry_out, float* lagged, float* lagged_class, float* lagged_begin,
+                                float* filtered, double* log2_evidence, void* workspace, long long workspace_bytes,
+                                void* stream);
 /* Data-gradient operand of a stride-2 conv (k = 3 pad 1, or k = 1 pad 0) split by the parity
  * (ph, pw) of the input pixel: class c = ph*2+pw gets [I][taps_c][O] with only the taps that
  * reach it (k=3: 1,2,2,4 taps; k=1: 1,0,0,0), stored back to back in class order.  Row taps of

@@ -27,7 +27,7 @@ from .pose_order import PoseLagDecoder, PoseLagSmoother  # noqa: F401
 from .pose_order import PoseOrderDecoder, PoseOrderLearner, PosePosterior, cyclic_prior, prob_score  # noqa: F401
 from .pose_order import PoseDurationDecoder, duration_prior, geometric_durations, hold_prior  # noqa: F401
 from .pose_order import PoseDurationPosterior, expected_duration_prior  # noqa: F401
-from .pose_order import PoseDurationLagDecoder  # noqa: F401
+from .pose_order import PoseDurationLagDecoder, PoseDurationLagSmoother  # noqa: F401
 from .pose_order import PoseDurationLearner  # noqa: F401
 
 __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnLstm", "Quadtree3DCNN", "Ji3DCNN", "FusedAdam", "grad_norm",
@@ -38,6 +38,7 @@ __all__ = ["QuadtreeCNN", "StandardResNetCNN", "AttentionHierarchicalCNN", "CnnL
            "FrameAnnotator", "caption_atlas", "POSE_CONNECTIONS", "MAJOR_SEGMENTS", "PoseTimeline",
            "PoseOrderDecoder", "PosePosterior", "PoseOrderLearner", "PoseLagSmoother", "PoseLagDecoder", "cyclic_prior", "prob_score",
            "PoseDurationDecoder", "duration_prior", "hold_prior", "geometric_durations",
-           "PoseDurationPosterior", "expected_duration_prior", "PoseDurationLagDecoder", "PoseDurationLearner",
+           "PoseDurationPosterior", "expected_duration_prior", "PoseDurationLagDecoder", "PoseDurationLagSmoother",
+           "PoseDurationLearner",
            "SegmentMeter", "segment_runs",
            "QtError", "LIB_PATH"]

@@ -1,6 +1,6 @@
 // What the kernels of the chain with hold durations share, on top of pose_chain.h (pose_duration.hip: the best path;
 // pose_duration_lag.hip: its fixed-lag form; pose_duration_sweep.h: the forward-backward that pose_duration_posterior.hip and
-// pose_duration_prior.hip run): the table's width and the descriptor checks, the chain's inputs with the duration tables as one
+// pose_duration_prior.hip run; pose_duration_lag_posterior.hip: its fixed-lag form): the table's width and the descriptor checks, the chain's inputs with the duration tables as one
 // kernel-argument struct, and the walk of one workgroup of PC_DUR_THREADS per stream: the lane map with a state's slices of dur
 // and dur_open in registers, the staging of trans, the start scores, a stream's length, the (max, +) step over the
 // predecessors, the emissions staged PC_DUR_CHUNK frames at a time, the ring of the last D frames and the loop over a lane's

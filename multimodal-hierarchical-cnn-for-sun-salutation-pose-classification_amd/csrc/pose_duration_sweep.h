@@ -1,6 +1,9 @@
 // The stream kernel of the chain with hold durations' forward-backward, shared by the posteriors (pose_duration_posterior.hip,
 // LEARN = false) and the learner's E-step (pose_duration_prior.hip, LEARN = true), so that both walk the very same forward and
 // backward sweeps: Z and the expected duration counts of the two are the same bits.  include/qtcnn.h states the rules in full.
+// The arithmetic of a step (pp_group_L .. pp_class_sum below) stands apart from the kernel as device functions: the fixed-lag
+// posteriors (pose_duration_lag_posterior.hip) walk a stream's forward sweep across calls and a backward sweep per emitted frame
+// with the same functions, which is how their rows are this kernel's bits on the stream's prefix.
 //
 // The walk is pose_duration.hip's, from the pieces of pose_duration_chain.h: one workgroup of 256 per stream, a group of LPS
 // lanes per state (16 for S <= 16, 4 above) with the state's slices of dur and dur_open in registers (lane l the lengths
@@ -76,6 +79,67 @@ __device__ __forceinline__ float pp_group_sum(float v) {
 __device__ __forceinline__ double pp_bits(long long v) { return (double)v * 0x1p-8; }   // exact: |v| < 2^53
 __device__ __forceinline__ float pp_term(double x) { return exp2f((float)x); }
 
+// The arithmetic of the sweeps, one body for every kernel that walks them (pp_stream_kernel below and the fixed-lag posteriors
+// of pose_duration_lag_posterior.hip, whose bits are the whole-video kernel's because they run these very functions).
+// L over the group's share of `n` candidates x(i), i = l, l + LPS, ..: the maximum out in double, the terms and their sum f32
+template <int LPS, typename X>
+__device__ __forceinline__ double pp_group_L(int n, int l, X&& x) {
+  double m = -DBL_MAX;
+  for (int i = l; i < n; i += LPS) m = fmax(m, x(i));
+  m = pp_group_max<LPS>(m);
+  float s = 0.0f;
+  for (int i = l; i < n; i += LPS) s += pp_term(x(i) - m);
+  return m + (double)log2f(pp_group_sum<LPS>(s));
+}
+// L over the state's lengths d = 1 .. dmax, the row of length d of ring [D][S] being row0 - d (forward) or row0 + d (backward),
+// wrapped; dur_open scores the length d_cut, and every length where `cut`
+template <int LPS>
+__device__ __forceinline__ double pp_length_L(const PcDurLane<LPS>& ln, const double* ring, int S, int D, int dmax, int row0,
+                                              bool forward, int d_cut, bool cut) {
+  double x[PcDurLane<LPS>::KMAX];
+  double m = -DBL_MAX;
+  pc_for_lengths<LPS>(dmax, ln.l, [&](int k, int d) {
+    const int r = pc_ring_wrap(forward ? row0 - d : row0 + d, D);
+    x[k] = ring[r * S + ln.jj] + pp_bits((cut || d == d_cut) ? ln.dop[k] : ln.du[k]);
+    m = fmax(m, x[k]);
+  });
+  m = pp_group_max<LPS>(m);
+  float s = 0.0f;
+  pc_for_lengths<LPS>(dmax, ln.l, [&](int k, int) { s += pp_term(x[k] - m); });
+  return m + (double)log2f(pp_group_sum<LPS>(s));
+}
+// Z = L_j lev[j] in ascending j, by one thread
+__device__ __forceinline__ double pp_evidence(const double* lev, int S) {
+  double m = lev[0];
+  for (int s = 1; s < S; ++s) m = fmax(m, lev[s]);
+  float sum = 0.0f;
+  for (int s = 0; s < S; ++s) sum += pp_term(lev[s] - m);
+  return m + (double)log2f(sum);
+}
+// the owner lane's step of the backward sweep at frame f: begin[f] from g[f] and Lh (the cum terms cancel), endp[f + 1] from
+// Al[f + 1] and Be[f + 1]; occ[f + 1] becomes occ[f] (`last`: f is the sweep's last frame) and begin_next begin[f], returned
+__device__ __forceinline__ float pp_owner_step(double g, double lh, double al_next, double be_next, double Z, bool last,
+                                               double& occ, float& begin_next) {
+  const float bg = pp_term(g + lh - Z);
+  const float ep = pp_term(al_next + be_next - Z);
+  occ = last ? (double)ep : occ + (double)ep - (double)begin_next;
+  begin_next = bg;
+  return bg;
+}
+// state j's entry of the posterior row from r = max(occ, 0) [S]: R in ascending j, double
+__device__ __forceinline__ float pp_row(const double* r, int S, int j) {
+  double R = 0.0;
+  for (int i = 0; i < S; ++i) R += r[i];
+  return R > 0.0 ? (float)(r[j] / R) : (float)(1.0 / S);
+}
+// class c's entry of the class posterior from the posterior row pst [S]: ascending j, f32
+__device__ __forceinline__ float pp_class_sum(const float* pst, const int* sc, int S, int c) {
+  float s = 0.0f;
+  for (int i = 0; i < S; ++i)
+    if (sc[i] == c) s += pst[i];
+  return s;
+}
+
 template <bool SMALL, bool LEARN>
 __global__ __launch_bounds__(PC_DUR_THREADS) void pp_stream_kernel(PpArgs a) {
   constexpr int LPS = PC_DUR_LPS<SMALL>;
@@ -101,28 +165,9 @@ __global__ __launch_bounds__(PC_DUR_THREADS) void pp_stream_kernel(PpArgs a) {
   }
   __syncthreads();
 
-  // L over the group's share of `n` candidates x(i), i = l, l + LPS, ..: the maximum out in double, the terms and their sum f32
-  auto group_L = [&](int n, auto x) -> double {
-    double m = -DBL_MAX;
-    for (int i = l; i < n; i += LPS) m = fmax(m, x(i));
-    m = pp_group_max<LPS>(m);
-    float s = 0.0f;
-    for (int i = l; i < n; i += LPS) s += pp_term(x(i) - m);
-    return m + (double)log2f(pp_group_sum<LPS>(s));
-  };
-  // L over the state's lengths d = 1 .. dmax, the ring row of length d being row0 - d (forward) or row0 + d (backward)
+  auto group_L = [&](int n, auto x) -> double { return pp_group_L<LPS>(n, l, x); };
   auto length_L = [&](int dmax, int row0, bool forward, int d_cut, bool cut) -> double {
-    double x[KMAX];
-    double m = -DBL_MAX;
-    pc_for_lengths<LPS>(dmax, l, [&](int k, int d) {
-      const int r = pc_ring_wrap(forward ? row0 - d : row0 + d, D);
-      x[k] = ring[r * S + jj] + pp_bits((cut || d == d_cut) ? ln.dop[k] : ln.du[k]);
-      m = fmax(m, x[k]);
-    });
-    m = pp_group_max<LPS>(m);
-    float s = 0.0f;
-    pc_for_lengths<LPS>(dmax, l, [&](int k, int) { s += pp_term(x[k] - m); });
-    return m + (double)log2f(pp_group_sum<LPS>(s));
+    return pp_length_L<LPS>(ln, ring, S, D, dmax, row0, forward, d_cut, cut);
   };
 
   // ---- forward ---------------------------------------------------------------------------------------------------------------
@@ -149,11 +194,7 @@ __global__ __launch_bounds__(PC_DUR_THREADS) void pp_stream_kernel(PpArgs a) {
         gw[(long long)f * S + j] = gv;
       }
     } else {                                     // Z, by every thread, in ascending j
-      double m = lev[0];
-      for (int s = 1; s < S; ++s) m = fmax(m, lev[s]);
-      float sum = 0.0f;
-      for (int s = 0; s < S; ++s) sum += pp_term(lev[s] - m);
-      Z = m + (double)log2f(sum);
+      Z = pp_evidence(lev, S);
       if (tid == 0 && a.evidence) a.evidence[b] = Z;
     }
     __syncthreads();
@@ -164,12 +205,7 @@ __global__ __launch_bounds__(PC_DUR_THREADS) void pp_stream_kernel(PpArgs a) {
   const long long out_row = (long long)b * a.T;
   // the class posterior of frame t from the posterior row in pst: ascending j, f32
   auto class_row = [&](int t) {
-    if (a.class_posterior && tid < C) {
-      float s = 0.0f;
-      for (int i = 0; i < S; ++i)
-        if (sc[i] == tid) s += pst[i];
-      a.class_posterior[(out_row + t) * C + tid] = s;
-    }
+    if (a.class_posterior && tid < C) a.class_posterior[(out_row + t) * C + tid] = pp_class_sum(pst, sc, S, tid);
   };
   double acc[KMAX];
 #pragma unroll
@@ -190,10 +226,8 @@ __global__ __launch_bounds__(PC_DUR_THREADS) void pp_stream_kernel(PpArgs a) {
     if constexpr (LEARN) {
       if (own) vec[j] = lh - pp_bits(cum);
     } else if (own) {
-      const float bg = pp_term(gw[(long long)f * S + j] + lh - Z);            // Bt[f] + Bs[f] - Z: the cum terms cancel
-      const float ep = pp_term(alw[(long long)f * S + j] + be_next - Z);      // endp[f + 1]
-      occ = f == T - 1 ? (double)ep : occ + (double)ep - (double)begin_next;
-      begin_next = bg;
+      const float bg =
+          pp_owner_step(gw[(long long)f * S + j], lh, alw[(long long)f * S + j], be_next, Z, f == T - 1, occ, begin_next);
       if (a.begin) a.begin[(out_row + f) * S + j] = bg;
       vec[j] = lh - pp_bits(cum);
       lev[j] = fmax(occ, 0.0);
@@ -230,9 +264,7 @@ __global__ __launch_bounds__(PC_DUR_THREADS) void pp_stream_kernel(PpArgs a) {
       }
     }
     if (own && rows_out) {
-      double R = 0.0;
-      for (int i = 0; i < S; ++i) R += lev[i];
-      const float p = R > 0.0 ? (float)(lev[j] / R) : (float)(1.0 / S);
+      const float p = pp_row(lev, S, j);
       pst[j] = p;
       if (a.posterior) a.posterior[(out_row + f) * S + j] = p;
     }

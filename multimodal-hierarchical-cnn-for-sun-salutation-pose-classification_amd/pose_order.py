@@ -112,7 +112,23 @@ stream may run for 2^36 frames); for any split of a stream into pushes, flush on
         held = first + torch.arange(lag_path.shape[1], device=device) - lag_start      # "held for n frames"
     first, lag_path, lag_start = livedur.push(rows[:, :0], flush=True, start=True)     # the last lag frames
 
-PoseDurationLearner (csrc/pose_duration_prior.hip) fits the tables that these three take, trans, init and dur jointly, to whole
+PoseDurationLagSmoother (csrc/pose_duration_lag_posterior.hip) gives the fixed-lag posteriors with durations, what
+PoseLagSmoother gives under the plain chain: `push` returns, for the frames `lag` frames ago, the row of PoseDurationPosterior's
+posterior (and on request its class row and its begin row) on the stream up to now, bit for bit, and for every new frame the
+lag-0 row and the evidence in bits.  The forward step is PoseDurationPosterior's with a closed and an open level per frame; every
+emitted frame then gets a backward sweep of its own over its at most lag + 1 frames, a workgroup each, so a split into pushes
+changes no bit.  lagged_begin is the probability that a hold begins at a frame given only `lag` frames of look-ahead: what a
+loop needs to announce "next pose" once.  Levels are absolute float64, so a stream may run for 2^20 frames (9.7 hours at
+30 fps); `reset()` starts a new one.
+
+    livepost = PoseDurationLagSmoother(state_class, trans, dur, device, lag=16, streams=16)
+    for rows in live:
+        first, lag_path = livedur.push(rows)
+        _, lagged, lagged_begin = livepost.push(rows, begin=True)       # nothing read back
+        confidence = livepost.confidence(lagged, lag_path)              # "Pose: X (0.93)", lag frames behind the camera
+    first, lagged = livepost.push(rows[:, :0], flush=True)              # the last lag frames
+
+PoseDurationLearner (csrc/pose_duration_prior.hip) fits the tables that these four take, trans, init and dur jointly, to whole
 videos whose frames carry class probabilities only: Baum-Welch for the explicit-duration chain, on the device.  PoseOrderLearner's
 tables do not fit here: it learns the plain chain, where trans[j][j] means "stay one more frame", while here that entry joins two
 segments of one step.  The E-step is PoseDurationPosterior's kernel in a second mode (the same sweeps: its evidence and its
@@ -128,7 +144,7 @@ PoseOrderLearner's rule, dur by `expected_duration_prior`'s, dur_open as the suf
             learner.accumulate(probs, lengths)    # E-step, nothing read back
         learner.update()                          # M-step; learner.trans / .init / .dur / .dur_open are the new tables
     bits, frames = learner.totals()               # the one host sync: evidence of the last E-step, frames seen
-    for user in (durdec, durpost, livedur):
+    for user in (durdec, durpost, livedur, livepost):
         user.load_tables(learner.trans, learner.init, learner.dur, learner.dur_open)    # device to device, no host sync
 
 `fit(videos, iterations)` is that loop, `accumulate_paths(path, start)` adds hard counts (PoseDurationDecoder.decode's path and
@@ -140,8 +156,8 @@ diagonal a hold decomposes into one-frame segments joined by trans[j][j], which 
 nothing.  On seeded tracks with holds of 9 frames (tests/test_pose_duration_prior_cpu.py) four iterations from a uniform dur
 raise the evidence at every step and move every step's most likely length to 9.
 
-Not built for the chain with durations: fixed-lag posteriors with durations, D > 128, true minus infinity (a forbidden length is
--65536), videos split across calls in the learner.
+Not built for the chain with durations: D > 128, true minus infinity (a forbidden length is -65536), videos split across calls
+in the learner, expected duration counts from a live stream, re-referenced levels for streams beyond 2^20 frames.
 
 Not built: ragged batches (per-sequence lengths) and videos split across calls in PoseOrderLearner, learning emissions (they are the
 network's), tying rows, true minus-infinity (forbidden) transitions, S > 64, bf16 probabilities, a second level of the
@@ -165,6 +181,7 @@ MAX_FRAMES = 1 << 20
 LAG_MAX = 63                # QT_POSE_LAG_MAX
 DUR_MAX = 128               # QT_POSE_DUR_MAX
 MAX_STREAM_FRAMES = 1 << 36  # qt_pose_duration_lag_decode: seen + frames (absolute int64 scores)
+MAX_SMOOTH_STREAM_FRAMES = 1 << 20  # qt_pose_duration_lag_smooth: seen + frames (absolute float64 levels)
 SCORE_FLOOR = -8192         # q of NaN and of everything below 2^-32
 TRANS_FLOOR = -65536
 # rint(256 log2(1 + (2 i + 1) / 512)), i = 0 .. 255: the table of csrc/pose_chain.h
@@ -259,6 +276,12 @@ def bind(L):
     L.qt_pose_duration_lag_decode.argtypes = [ctypes.POINTER(PoseDurationLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
         [ctypes.c_void_p] * 12 + [ctypes.c_longlong, ctypes.c_void_p]
     L.qt_pose_duration_lag_decode.restype = ctypes.c_int
+    for name in ("qt_pose_duration_lag_smooth_carry_bytes", "qt_pose_duration_lag_smooth_workspace_bytes"):
+        getattr(L, name).argtypes = [ctypes.POINTER(PoseDurationLagDesc)]
+        getattr(L, name).restype = ctypes.c_longlong
+    L.qt_pose_duration_lag_smooth.argtypes = [ctypes.POINTER(PoseDurationLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
+        [ctypes.c_void_p] * 13 + [ctypes.c_longlong, ctypes.c_void_p]
+    L.qt_pose_duration_lag_smooth.restype = ctypes.c_int
     L.qt_pose_duration_prior_workspace_bytes.argtypes = [ctypes.POINTER(PoseDurationDesc)]
     L.qt_pose_duration_prior_workspace_bytes.restype = ctypes.c_longlong
     L.qt_pose_duration_prior_expect.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
@@ -1008,6 +1031,64 @@ class PoseDurationLagDecoder(_LagState, _PoseDurationTables):
                    best if T else None, workspace="qt_pose_duration_lag_workspace_bytes")
         self._advance(T)
         return (first, path) + tuple(t for t in (begin, filt, best) if t is not None)
+
+
+class PoseDurationLagSmoother(_LagState, _PoseDurationTables):
+    """Fixed-lag posteriors with hold durations of `streams` live videos (csrc/pose_duration_lag_posterior.hip): `push` takes
+    the new frames and returns, for the frames `lag` frames ago, the rows that PoseDurationPosterior.smooth would give on the
+    stream up to now, bit for bit.  The tables are PoseDurationDecoder's; the count of frames seen lives on the host (all
+    streams advance together), the two carry buffers are swapped after every push.  Nothing is read back.  See the module
+    text."""
+
+    def __init__(self, state_class, trans, dur, device, lag, streams=1, init=None, dur_open="suffix_max", class_names=None):
+        _check_lag(type(self).__name__, lag)
+        super().__init__(state_class, trans, dur, device, streams, init, dur_open, class_names)
+        self._lag_init(lag, "qt_pose_duration_lag_smooth_carry_bytes",
+                       PoseDurationLagDesc(streams, 1, 1, self.num_states, self.max_duration, int(lag), 0, 0))
+
+    def push(self, probs, flush=False, by_class=False, begin=False, filtered=False, evidence=False):
+        """probs: f32 [streams, frames, C], or [frames, C] when there is one stream, on this object's device; frames may be 0
+        with flush.  Returns (first_frame, lagged f32 [streams, count, S] (or [count, S])), then as asked and in this order the
+        class posterior f32 [..., count, C], lagged_begin f32 [..., count, S] (the probability that a hold of step j begins at
+        that frame, given `lag` frames of look-ahead), the lag-0 rows of the new frames f32 [..., frames, S] and the evidence in
+        bits of the stream cut after each new frame, float64 [..., frames]: lagged[:, k] belongs to frame first_frame + k of the
+        stream, count is frames once the stream is `lag` frames old, 0 before, and with flush also the frames still pending."""
+        what = "PoseDurationLagSmoother.push"
+        probs, flat, T, C = self._check_probs(what, probs, allow_empty=flush)
+        B, S, dev = self.streams, self.num_states, self.device
+        if self.seen + T > MAX_SMOOTH_STREAM_FRAMES:
+            raise QtError(f"{what}: frame {self.seen + T} of a stream; at most {MAX_SMOOTH_STREAM_FRAMES} are handled "
+                          f"(reset() starts a new stream)")
+        first, count = self._span(T, flush)
+        desc = PoseDurationLagDesc(B, T, C, S, self.max_duration, self.lag, int(bool(flush)), self.seen)
+        lead = (lambda n: (n,)) if flat else (lambda n: (B, n))
+        lagged = torch.empty(lead(count) + (S,), dtype=torch.float32, device=dev)
+        cls = torch.empty(lead(count) + (C,), dtype=torch.float32, device=dev) if by_class else None
+        beg = torch.empty(lead(count) + (S,), dtype=torch.float32, device=dev) if begin else None
+        filt = torch.empty(lead(T) + (S,), dtype=torch.float32, device=dev) if filtered else None
+        ev = torch.empty(lead(T), dtype=torch.float64, device=dev) if evidence else None
+        self._call("qt_pose_duration_lag_smooth", desc, probs if T else None, probs.stride(1) if T else C, *self._tables(),
+                   *self._carries(), lagged if count else None, cls if count else None, beg if count else None,
+                   filt if T else None, ev if T else None, workspace="qt_pose_duration_lag_smooth_workspace_bytes")
+        self._advance(T)
+        return (first, lagged) + tuple(t for t in (cls, beg, filt, ev) if t is not None)
+
+    def confidence(self, lagged, lag_path):
+        """f32 [streams, count] (or [count]): the lagged posterior at the states of `lag_path` (a PoseDurationLagDecoder's push
+        of the same frames, int64).  Plain torch, nothing read back."""
+        return _confidence("PoseDurationLagSmoother.confidence", self, lagged, lag_path, "lagged", "lag_path")
+
+    def holds(self, lagged_begin):
+        """float64 [streams, S]: the sum of `lagged_begin` (a push's, [streams, count, S] or [count, S]) over its frames, the
+        expected number of holds of every step that begin in them.  Plain torch, nothing read back."""
+        who = "PoseDurationLagSmoother.holds"
+        _check_device_tensor(who, "lagged_begin", lagged_begin, self.device, torch.float32)
+        if lagged_begin.dim() == 2 and self.streams == 1:
+            lagged_begin = lagged_begin.unsqueeze(0)
+        if lagged_begin.dim() != 3 or lagged_begin.shape[0] != self.streams or lagged_begin.shape[2] != self.num_states:
+            raise QtError(f"{who}: lagged_begin must be [{self.streams}, count, {self.num_states}] "
+                          f"(got {list(lagged_begin.shape)})")
+        return lagged_begin.sum(dim=1, dtype=torch.float64)
 
 
 class _Learner:
