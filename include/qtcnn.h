@@ -2040,8 +2040,25 @@ int qt_plan_tensor_shape(const qt_plan* plan, int i, int* dims4); /* returns ndi
 size_t qt_plan_workspace_bytes(const qt_plan* plan);
 /* byte offset inside the workspace of a named activation / gradient buffer:
  * "stem.pooled", "block<0-7>.out|.a1|.gout", "conv<i>.y|.gy", "fused", "dfused", "hidden";
- * QT_MODEL_ATTENTION also "attention.vectors" (f32 [B][16][64]) and "attention.weights" (f32 [B][16]) */
+ * QT_MODEL_ATTENTION also "attention.vectors" (f32 [B][16][64]) and "attention.weights" (f32 [B][16]);
+ * "conv<i>.dw": the f32 [O][kh][kw][I] slice of the weight-gradient scratch (region "dw") of a convolution whose weight
+ * gradient is accumulated there, QT_ERR_INVALID_ARG for one that has none */
 int qt_plan_find_buffer(const qt_plan* plan, const char* name, size_t* offset);
+/* The workspace layout as a table (tests): every range the plan hands to its launches, in ascending order of offset and
+ * disjoint; qt_plan_num_regions is their number. */
+int qt_plan_num_regions(const qt_plan* plan);
+/* Region i: its name (a short stable string that lives as long as the plan: "stats", "bn7.mean", "conv3.w_dgrad",
+ * "block2.a1_bits", "lstm1.gates", "wgrad_part", ...; a buffer qt_plan_find_buffer knows has that name), its byte offset
+ * (a multiple of 256) and the bytes asked for it.  The bytes from offset + bytes to the next region's offset (the rounding
+ * to 256 and the guard gap) belong to no launch.  The f32 weight-gradient scratch that one memset zeroes per backward is
+ * ONE region, "dw", whatever the number of convolutions that own a slice of it. */
+int qt_plan_region(const qt_plan* plan, int i, const char** name, size_t* offset, size_t* bytes);
+/* Tests: a plan created after this call leaves `bytes` (a multiple of 256, else QT_ERR_INVALID_ARG) unused behind every
+ * region of its workspace, qt_plan_workspace_bytes and qt_plan_find_buffer included, so that a launch running over its
+ * buffer lands in bytes nobody owns instead of in its neighbour.  Process-wide, read by qt_plan_create; 0 (the default)
+ * is the layout without gaps.  Launches, streams and kernel arguments are the same but for the offsets.  The caller's
+ * stream workspace of qt_plan_stream_forward (qt_plan_stream_workspace_bytes) is laid out elsewhere and has no gaps. */
+int qt_set_plan_guard_gap(size_t bytes);
 /* Measurement aid (bench.py roofline): while enabled, every MFMA kernel launch is
  * bracketed by HIP events on its stream; _end sums algorithmic FLOPs, milliseconds
  * and launch counts per kind {0 igemm forward, 1 igemm dgrad, 2 wgrad}. */

@@ -108,6 +108,11 @@ struct qt_plan {
   int fused_ld = 0, img_cols = 0, mlp_col0 = 0, hidden_dim = 0;
   // workspace offsets
   size_t ws_bytes = 0;
+  // every range layout_workspace() handed out, in ascending order: bytes = the size asked for (the 256-byte rounding and
+  // guard_gap lie behind it); guard_gap: qt_set_plan_guard_gap as qt_plan_create found it
+  struct Region { std::string name; size_t offset, bytes; };
+  std::vector<Region> regions;
+  size_t guard_gap = 0;
   size_t xpad = 0, p0 = 0, argmax = 0, g_p0 = 0, ymax = 0;
   size_t q = 0, dq = 0, fused = 0, dfused = 0, h1 = 0, dh1 = 0, hidden = 0, dhidden = 0;
   size_t stats = 0, ones = 0, zeros = 0, gbase_tmp = 0;
@@ -186,12 +191,32 @@ struct qt_plan {
 
 namespace {
 
+// qt_set_plan_guard_gap (tests): unused bytes behind every region of the workspaces laid out from now on; 0 = none
+size_t g_plan_guard_gap = 0;
+
 struct Bump {
+  std::vector<qt_plan::Region>& regions;
+  size_t gap;
   size_t off = 0;
-  size_t take(size_t bytes) {
+  size_t take(const std::string& name, size_t bytes) {
+    size_t o = off;
+    regions.push_back({name, o, bytes});
+    off = align_up(off + bytes) + gap;
+    return o;
+  }
+  // A range the executor addresses as ONE range although several owners have a slice of it: slice() between open() and
+  // close(name, begin) hands out adjacent slices, without a gap inside, and close() records the whole as one region
+  size_t open() const { return off; }
+  size_t slice(size_t bytes) {
     size_t o = off;
     off = align_up(off + bytes);
     return o;
+  }
+  size_t close(const std::string& name, size_t begin) {
+    const size_t end = off;
+    regions.push_back({name, begin, end - begin});
+    off += gap;
+    return end;
   }
 };
 
@@ -362,34 +387,36 @@ size_t dgrad_operand(const qt_plan* p, const ConvL& c) {
 }
 
 void layout_workspace(qt_plan* p) {
-  Bump ws;
+  Bump ws{p->regions, p->guard_gap};
+  const auto idx = [](const char* what, size_t i, const char* field) { return what + std::to_string(i) + "." + field; };
   const size_t B = (size_t)p->d.batch;
   const size_t es = (size_t)p->esz;
   // constants
-  p->ones = ws.take(2048 * 4);
-  p->zeros = ws.take(2048 * 4);
+  p->ones = ws.take("ones", 2048 * 4);
+  p->zeros = ws.take("zeros", 2048 * 4);
   // statistics scratch: the stem has the most partial rows
   {
     const int rows = qt_stats_capacity_rows(qt_cdiv((long long)B * 112 * 112, 128));
     size_t bytes = (size_t)rows * 2 * 64 * 4;
     const size_t bwd = (size_t)qt_stats_capacity_rows(2048) * 2 * 512 * 4;
-    p->stats = ws.take(bytes > bwd ? bytes : bwd);
+    p->stats = ws.take("stats", bytes > bwd ? bytes : bwd);
     // dgrad-epilogue partials: one row per 128-pixel tile (+ the fold rows); layer1 is the largest
     // (... or, larger, the merged stride-2 data gradient of layer2.0 on the patch-resident kernel: one row per 196-pixel
     // tile of the 28x28 gradient map, wave row and parity class = 32 rows per image)
     const size_t ep0 = (size_t)qt_stats_capacity_rows(qt_cdiv((long long)B * 56 * 56, 128) + 8) * 2 * 64 * 4;
     const size_t ep1 = (size_t)qt_stats_capacity_rows((int)(32 * B + 8)) * 2 * 64 * 4;
     const size_t ep = ep0 > ep1 ? ep0 : ep1;
-    p->stats_bn2 = ws.take(ep);
-    p->stats_ds = ws.take(ep);
-    p->stats_bn1 = ws.take(ep);
+    p->stats_bn2 = ws.take("stats_bn2", ep);
+    p->stats_ds = ws.take("stats_ds", ep);
+    p->stats_bn1 = ws.take("stats_bn1", ep);
   }
-  for (auto& b : p->bns) {
-    b.mean = ws.take(b.C * 4);
-    b.invstd = ws.take(b.C * 4);
-    b.scale = ws.take(b.C * 4);
-    b.shift = ws.take(b.C * 4);
-    b.coef = ws.take(3 * b.C * 4);
+  for (size_t i = 0; i < p->bns.size(); ++i) {
+    BnL& b = p->bns[i];
+    b.mean = ws.take(idx("bn", i, "mean"), b.C * 4);
+    b.invstd = ws.take(idx("bn", i, "invstd"), b.C * 4);
+    b.scale = ws.take(idx("bn", i, "scale"), b.C * 4);
+    b.shift = ws.take(idx("bn", i, "shift"), b.C * 4);
+    b.coef = ws.take(idx("bn", i, "coef"), 3 * b.C * 4);
   }
   // packed weights + KRSC gradient scratch
   for (size_t i = 0; i < p->convs.size(); ++i) {
@@ -398,7 +425,7 @@ void layout_workspace(qt_plan* p) {
     if (i > 0 && c.stride == 2)
       qt_pack_dgrad_s2(p->d.dtype, reinterpret_cast<const float*>(8), nullptr, c.cout, c.cin, c.k, c.cls_off, c.cls_kh,
                        c.cls_kw, nullptr);
-    c.w_fwd = ws.take(n * es);
+    c.w_fwd = ws.take(idx("conv", i, "w_fwd"), n * es);
     // 3x3 stride 2: the data-gradient operand holds all four parity classes with 2 x 2 tap slots each (16/9 of the
     // filter, the unused slots zero: qt_pack_dgrad_s2_merged)
     c.merged_dgrad = i > 0 && c.stride == 2 && c.k == 3 && merged_s2_enabled();
@@ -408,13 +435,15 @@ void layout_workspace(qt_plan* p) {
       p->convs[c.slot_conv].slot_conv = -1;
       c.slot_conv = -1;
     }
-    c.w_dgrad = ws.take((c.merged5 ? (size_t)20 * c.cout * c.cin : c.merged_dgrad ? (size_t)16 * c.cout * c.cin : n) * es);
+    c.w_dgrad = ws.take(idx("conv", i, "w_dgrad"),
+                        (c.merged5 ? (size_t)20 * c.cout * c.cin : c.merged_dgrad ? (size_t)16 * c.cout * c.cin : n) * es);
   }
-  // f32 [O][kh][kw][I] weight-gradient scratch, contiguous, zeroed by ONE memset per backward.  Only the convolutions whose
-  // weight gradient is ACCUMULATED into it get a slice: the stem, the region heads (quadrant / sub-quadrant convs) and, in the
-  // f32 build, every 3x3.  The streaming kernels (bf16: 3x3 stride 1, the stride-2 pair of a transition block) write .grad
-  // in OIHW themselves and the generic 1x1 path zeroes .grad itself: round 3 zeroed 45 MB here per step, 11 MB of it needed.
-  p->dw_begin = ws.off;
+  // f32 [O][kh][kw][I] weight-gradient scratch, contiguous, zeroed by ONE memset per backward: one region, "dw", without a guard
+  // gap inside.  Only the convolutions whose weight gradient is ACCUMULATED into it get a slice: the stem and, in the f32 build,
+  // every 3x3 (the region heads, quadrant / sub-quadrant convs, included).  The streaming kernels (bf16: 3x3 stride 1, region
+  // heads, the stride-2 pair of a transition block) write .grad in OIHW themselves and the generic 1x1 path zeroes .grad
+  // itself: round 3 zeroed 45 MB here per step, 11 MB of it needed.
+  p->dw_begin = ws.open();
   for (size_t i = 0; i < p->convs.size(); ++i) {
     ConvL& c = p->convs[i];
     const size_t n = (i == 0) ? (size_t)64 * 8 * 32 : (size_t)c.cout * c.cin * c.k * c.k;
@@ -424,91 +453,92 @@ void layout_workspace(qt_plan* p) {
       const qt_conv_desc d = S == 1 ? conv_desc(p->d.dtype, (int)B, c, QT_CONV_FWD) : region_desc(p->d.dtype, (int)B, c, S, QT_CONV_FWD);
       scratch = qt_conv2d_wgrad_workspace_bytes(&d) == 0;
     }
-    c.dw = scratch ? ws.take(n * 4) : 0;
+    c.dw = scratch ? ws.slice(n * 4) : 0;
   }
-  p->dw_end = ws.off;
+  p->dw_end = ws.close("dw", p->dw_begin);
   // one partial filter per range of positions (at most 256 workgroups x 64 x 9 x 64 f32, whatever the
   // batch): the streaming weight-gradient launches run one after another on the side stream and share it, as do the
   // deterministic stem weight gradient (<= 256 x 64 x 7 x 32 f32) and region-bias column sums (<= 1024 x 128 f32) there
   p->wgrad_part_bytes = (size_t)256 * 64 * 9 * 64 * 4;
-  p->wgrad_part = ws.take(p->wgrad_part_bytes);
+  p->wgrad_part = ws.take("wgrad_part", p->wgrad_part_bytes);
   {
     const int mb = B < 256 ? (int)B : 256;
     const size_t f = qt_linear_workspace_bytes(mb, p->cls0.out, p->cls0.in), g = qt_linear_workspace_bytes(mb, p->cls0.in, p->cls0.out);
     p->lin_ws_bytes = f > g ? f : g;
-    p->lin_ws = ws.take(p->lin_ws_bytes > 0 ? p->lin_ws_bytes : 16);
+    p->lin_ws = ws.take("lin_ws", p->lin_ws_bytes > 0 ? p->lin_ws_bytes : 16);
   }
   for (LinL* l : {&p->cls0}) {
-    l->w_fwd = ws.take((size_t)l->in * l->out * es);
-    l->w_dgrad = ws.take((size_t)l->in * l->out * es);
+    l->w_fwd = ws.take("cls0.w_fwd", (size_t)l->in * l->out * es);
+    l->w_dgrad = ws.take("cls0.w_dgrad", (size_t)l->in * l->out * es);
   }
   if (p->has_image) {
-    p->xpad = ws.take(B * QT_STEM_PAD_H * QT_STEM_PAD_W * 4 * es);
-    p->p0 = ws.take(B * 56 * 56 * 64 * es);
-    p->g_p0 = ws.take(B * 56 * 56 * 64 * es);
-    p->argmax = ws.take(B * 56 * 56 * 64);
-    p->ymax = ws.take(B * 56 * 56 * 64 * es);  // raw conv1 output at the pooling argmax (bn1 backward sums)
+    p->xpad = ws.take("xpad", B * QT_STEM_PAD_H * QT_STEM_PAD_W * 4 * es);
+    p->p0 = ws.take("stem.pooled", B * 56 * 56 * 64 * es);
+    p->g_p0 = ws.take("stem.gpooled", B * 56 * 56 * 64 * es);
+    p->argmax = ws.take("argmax", B * 56 * 56 * 64);
+    p->ymax = ws.take("ymax", B * 56 * 56 * 64 * es);  // raw conv1 output at the pooling argmax (bn1 backward sums)
     for (size_t i = 0; i < p->convs.size(); ++i) {
       ConvL& c = p->convs[i];
       const size_t n = B * c.regions * c.hout * c.hout * c.cout;
-      c.y = ws.take(n * es);
-      c.gy = ws.take(n * es);
+      c.y = ws.take(idx("conv", i, "y"), n * es);
+      c.gy = ws.take(idx("conv", i, "gy"), n * es);
     }
-    for (auto& blk : p->blocks) {
+    for (size_t bi = 0; bi < p->blocks.size(); ++bi) {
+      Block& blk = p->blocks[bi];
       const ConvL& c2 = p->convs[blk.conv2];
       const size_t n = B * c2.hout * c2.hout * c2.cout;
-      blk.a1 = ws.take(n * es);
-      blk.out = ws.take(n * es);
-      blk.gout = ws.take(n * es);
-      blk.a1_bits = ws.take(n / 8);
-      blk.out_bits = ws.take(n / 8);
+      blk.a1 = ws.take(idx("block", bi, "a1"), n * es);
+      blk.out = ws.take(idx("block", bi, "out"), n * es);
+      blk.gout = ws.take(idx("block", bi, "gout"), n * es);
+      blk.a1_bits = ws.take(idx("block", bi, "a1_bits"), n / 8);
+      blk.out_bits = ws.take(idx("block", bi, "out_bits"), n / 8);
       const ConvL& c1 = p->convs[blk.conv1];
-      blk.gtmp = blk.ds >= 0 ? ws.take(B * c1.hin * c1.hin * c1.cin * es) : 0;
+      blk.gtmp = blk.ds >= 0 ? ws.take(idx("block", bi, "gtmp"), B * c1.hin * c1.hin * c1.cin * es) : 0;
     }
-    p->gbase_tmp = ws.take(B * 28 * 28 * 128 * es);  // (>= layer3's 14x14x256 map)
+    p->gbase_tmp = ws.take("gbase_tmp", B * 28 * 28 * 128 * es);  // (>= layer3's 14x14x256 map)
     if (p->attention) {
-      p->gbase_tmp2 = ws.take(B * 28 * 28 * 128 * es);
-      p->vsub = ws.take(B * 16 * 64 * 4);
-      p->dvsub = ws.take(B * 16 * 64 * 4);
-      p->att_act = ws.take(B * 16 * 32 * 4);
-      p->att_dpre = ws.take(B * 16 * 32 * 4);
-      p->att_alpha = ws.take(B * 16 * 4);
-      p->att_ds = ws.take(B * 16 * 4);
+      p->gbase_tmp2 = ws.take("gbase_tmp2", B * 28 * 28 * 128 * es);
+      p->vsub = ws.take("attention.vectors", B * 16 * 64 * 4);
+      p->dvsub = ws.take("attention.dvectors", B * 16 * 64 * 4);
+      p->att_act = ws.take("attention.act", B * 16 * 32 * 4);
+      p->att_dpre = ws.take("attention.dpre", B * 16 * 32 * 4);
+      p->att_alpha = ws.take("attention.weights", B * 16 * 4);
+      p->att_ds = ws.take("attention.ds", B * 16 * 4);
     }
   }
   if (!p->standard) {
     p->q = p->convs[p->quad_conv].y;
     p->dq = p->convs[p->quad_conv].gy;
-    p->h1 = ws.take(B * p->mlp0.out * 4);
-    p->dh1 = ws.take(B * p->mlp0.out * 4);
+    p->h1 = ws.take("h1", B * p->mlp0.out * 4);
+    p->dh1 = ws.take("dh1", B * p->mlp0.out * 4);
   }
   if (p->lstm) {
     const size_t H = (size_t)p->lstm_h;
-    p->h1 = ws.take(B * p->mlp0.out * 4);
-    p->dh1 = ws.take(B * p->mlp0.out * 4);
+    p->h1 = ws.take("h1", B * p->mlp0.out * 4);
+    p->dh1 = ws.take("dh1", B * p->mlp0.out * 4);
     for (int l = 0; l < 2; ++l) {
       qt_plan::LstmL& L = p->lstm_l[l];
-      L.whh_t = ws.take(H * 4 * H * 4);
-      L.wih_t = ws.take((size_t)L.in * 4 * H * 4);
-      L.xproj = ws.take(B * 4 * H * 4);
-      L.gates = ws.take(B * 4 * H * 4);
-      L.dgates = ws.take(B * 4 * H * 4);
-      L.cell = ws.take(B * H * 4);
-      L.hprev = ws.take(B * H * 4);
-      L.hout = ws.take(B * H * 4);
+      L.whh_t = ws.take(idx("lstm", l, "whh_t"), H * 4 * H * 4);
+      L.wih_t = ws.take(idx("lstm", l, "wih_t"), (size_t)L.in * 4 * H * 4);
+      L.xproj = ws.take(idx("lstm", l, "xproj"), B * 4 * H * 4);
+      L.gates = ws.take(idx("lstm", l, "gates"), B * 4 * H * 4);
+      L.dgates = ws.take(idx("lstm", l, "dgates"), B * 4 * H * 4);
+      L.cell = ws.take(idx("lstm", l, "cell"), B * H * 4);
+      L.hprev = ws.take(idx("lstm", l, "hprev"), B * H * 4);
+      L.hout = ws.take(idx("lstm", l, "hout"), B * H * 4);
     }
-    p->lstm_x0 = ws.take(B * p->fused_ld * 4);
-    p->lstm_x1 = ws.take(B * H * 4);
-    p->lstm_dx1 = ws.take(B * H * 4);
-    p->lstm_dlast = ws.take(B * H * 4);
-    p->lstm_hid = ws.take(B * 128 * 4);
-    p->lstm_dhid = ws.take(B * 128 * 4);
-    p->lstm_dz = ws.take(B * 128 * 4);
+    p->lstm_x0 = ws.take("lstm_x0", B * p->fused_ld * 4);
+    p->lstm_x1 = ws.take("lstm_x1", B * H * 4);
+    p->lstm_dx1 = ws.take("lstm_dx1", B * H * 4);
+    p->lstm_dlast = ws.take("lstm_dlast", B * H * 4);
+    p->lstm_hid = ws.take("lstm_hid", B * 128 * 4);
+    p->lstm_dhid = ws.take("lstm_dhid", B * 128 * 4);
+    p->lstm_dz = ws.take("lstm_dz", B * 128 * 4);
   }
-  p->fused = ws.take(B * p->fused_ld * es);
-  p->dfused = ws.take(B * p->fused_ld * es);
-  p->hidden = ws.take(B * p->hidden_dim * es);
-  p->dhidden = ws.take(B * p->hidden_dim * es);
+  p->fused = ws.take("fused", B * p->fused_ld * es);
+  p->dfused = ws.take("dfused", B * p->fused_ld * es);
+  p->hidden = ws.take("hidden", B * p->hidden_dim * es);
+  p->dhidden = ws.take("dhidden", B * p->hidden_dim * es);
   p->ws_bytes = ws.off;
 }
 
@@ -1735,6 +1765,7 @@ extern "C" int qt_plan_create(const qt_plan_desc* desc, qt_plan** out) {
   p->d = *desc;
   p->esz = qt_dtype_size(desc->dtype);
   p->use_side = qt_env_int("QTCNN_SIDE_STREAM", 1) != 0;   // (per plan: read at every qt_plan_create)
+  p->guard_gap = g_plan_guard_gap;
   build_graph(p);
   layout_workspace(p);
   *out = p;
@@ -1761,6 +1792,25 @@ extern "C" int qt_plan_tensor_shape(const qt_plan* p, int i, int* dims) {
   return p->tensors[i].ndim;
 }
 extern "C" size_t qt_plan_workspace_bytes(const qt_plan* p) { return p ? p->ws_bytes : 0; }
+
+// Tests: unused bytes behind every region of the workspaces laid out from now on (a multiple of 256; 0, the default: none)
+extern "C" int qt_set_plan_guard_gap(size_t bytes) {
+  QT_CHECK_ARG(bytes % 256 == 0, "qt_set_plan_guard_gap: %zu is not a multiple of 256", bytes);
+  g_plan_guard_gap = bytes;
+  return QT_OK;
+}
+
+// Every range of the workspace layout, in ascending order of offset: what lies between the end of one and the start of the
+// next (the 256-byte rounding, the guard gap) belongs to no launch
+extern "C" int qt_plan_num_regions(const qt_plan* p) { return p ? (int)p->regions.size() : QT_ERR_INVALID_ARG; }
+extern "C" int qt_plan_region(const qt_plan* p, int i, const char** name, size_t* offset, size_t* bytes) {
+  QT_CHECK_ARG(p && name && offset && bytes, "qt_plan_region: null argument");
+  QT_CHECK_ARG(i >= 0 && i < (int)p->regions.size(), "qt_plan_region: region %d of %d", i, (int)p->regions.size());
+  *name = p->regions[i].name.c_str();
+  *offset = p->regions[i].offset;
+  *bytes = p->regions[i].bytes;
+  return QT_OK;
+}
 
 // Named views into the workspace (tests / Grad-CAM style introspection): the offset of
 // an activation or gradient buffer for the plan's maximum batch.
@@ -1794,6 +1844,7 @@ extern "C" int qt_plan_find_buffer(const qt_plan* p, const char* name, size_t* o
   if (c >= 0 && c < (int)p->convs.size()) {
     if (suffix(".y")) { *offset = p->convs[c].y; return QT_OK; }
     if (suffix(".gy")) { *offset = p->convs[c].gy; return QT_OK; }
+    if (suffix(".dw") && p->convs[c].dw) { *offset = p->convs[c].dw; return QT_OK; }   // its slice of the "dw" region, if any
   }
   qt_set_error("qt_plan_find_buffer: unknown buffer '%s'", name);
   return QT_ERR_INVALID_ARG;

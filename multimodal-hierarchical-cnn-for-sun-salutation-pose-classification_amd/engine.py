@@ -84,6 +84,10 @@ def _bind_api(L):
     L.qt_grad_norm_multi.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
                                      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     L.qt_plan_find_buffer.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t)]
+    L.qt_plan_num_regions.argtypes = [ctypes.c_void_p]
+    L.qt_plan_region.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
+                                 ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+    L.qt_set_plan_guard_gap.argtypes = [ctypes.c_size_t]
     L._plan_bound = True
 
 

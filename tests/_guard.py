@@ -18,7 +18,7 @@ rows belong to qt_bn_finalize's folding, the convolution must not touch them, an
 
 Guard.check() asserts all of it.  Each band is the larger of 64 KiB and 256 payload rows (the tallest pixel tile any kernel
 here writes), rounded up to 256 bytes.  A store farther out than a band stays invisible, and so does one internal buffer of
-a workspace running into the next: the bands sit at the two ends only.
+a workspace running into the next: the bands sit at the two ends only (the plan workspace: tests/_plan_gaps.py).
 """
 import math
 

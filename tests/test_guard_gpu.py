@@ -7,8 +7,8 @@ memory properties; the guarded results must equal the plain ones -- bit for bit 
 shows the bits are reproducible, inside that test's documented bound where the kernel uses atomics.  Shapes are the existing
 tests' smallest per dispatch branch.  Byte outputs run with payload fills 0xFF and 0x00 and must agree.
 
-The guards observe memory after ordinary calls.  A store farther out than a band, and an internal buffer of the plan
-workspace running into the next one, stay invisible (tests/test_plan_layout_cpu.py owns that layout)."""
+The guards observe memory after ordinary calls.  A store farther out than a band stays invisible; an internal buffer of the plan
+workspace running into the next one is the business of tests/test_plan_gaps_gpu.py."""
 import ctypes
 
 import numpy as np
@@ -21,6 +21,7 @@ import _gradcam_ref as GR
 import _loss_ref as LR
 import _stem_bounds as Sb
 from _guard import POISON, Guard
+from _plan_gaps import compare_twins, plan_run, rehome
 from _util import pkg, rel_err
 from test_clip_adam_gpu import ADAM_TOL, HYPER, LISTS, _tensors
 
@@ -644,8 +645,7 @@ def test_unpack_weight_gradients():
 # ======================================================================================================================
 def _quadtree(dt, guard):
     """QuadtreeCNN at max_batch = 2 with its engine built; guard: the workspace is exactly qt_plan_workspace_bytes of NaN
-    between two bands.  csrc/plan.hip keeps offsets, never a pointer into a workspace (every entry point takes the
-    workspace as an argument), so the engine's own attributes are enough to move it."""
+    between two bands (tests/_plan_gaps.py::rehome)."""
     P, synth = pkg(), pkg("synth")
     dev = _dev()
     m = P.QuadtreeCNN(12, dropout_rate=0.0, compute_dtype=dt, max_batch=2)
@@ -653,62 +653,17 @@ def _quadtree(dt, guard):
     m = m.to(dev).train()
     eng = m._ensure_engine(2, dev)
     if guard is not None:
-        L = pkg("_lib")
-        ws = guard.workspace("plan workspace", eng.workspace_bytes)
-        assert ws.data_ptr() % 256 == 0 and ws.numel() == eng.L.qt_plan_workspace_bytes(eng.handle)
-        eng.workspace = ws
-        eng.ws_ptr = ctypes.c_void_p(ws.data_ptr())
-        L.check(eng.L.qt_plan_init_workspace(eng.handle, eng.ws_ptr, L.stream_ptr()), "qt_plan_init_workspace")
-        eng._packed_version = None
-        eng._weights_stale = True
+        rehome(eng, guard)
     return m
 
 
 def _plan_run(models, checks, share_grads):
-    """Both twins in step: eval forward at B = 2 and B = 1, a train step without and one with max_grad_norm, a forward on the
-    re-packed operands; checks[i]() after every call of twin i.  share_grads: twin 1 steps twin 0's gradients -- the f32
-    backward is not bit-reproducible from run to run, and Adam turns a last-bit difference of a near-zero gradient into a visible
-    one (tests/test_clip_adam_gpu.py::_compare_twins)."""
-    P, synth = pkg(), pkg("synth")
+    """tests/_plan_gaps.py::plan_run at B = 2 and B = 1"""
+    synth = pkg("synth")
     dev = _dev()
-    x, f = synth.synth_images(2, salt=5).to(dev), synth.synth_pose_features(2, salt=5).to(dev)
-    y = synth.synth_labels(2, 12, salt=5).to(dev)
-    outs = [{} for _ in models]
-
-    def forward(tag, xb, fb):
-        for m, check, out in zip(models, checks, outs):
-            m.eval()
-            with torch.no_grad():
-                out[tag] = m(xb, fb).float().clone()
-            check()
-            m.train()
-
-    forward("eval2", x, f)
-    forward("eval1", x[:1], f[:1])
-    for tag, max_norm in (("plain", None), ("clipped", 0.05)):
-        opts = [P.FusedAdam(m.parameters(), lr=1e-3, weight_decay=1e-4, model=m, max_grad_norm=max_norm) for m in models]
-        for m, opt, check, out in zip(models, opts, checks, outs):
-            opt.zero_grad(set_to_none=True)
-            logits = m(x, f)
-            check()
-            F.cross_entropy(logits, y).backward()
-            check()
-            out[tag + "/logits"] = logits.detach().float().clone()
-            for n, p in m.named_parameters():
-                if p.grad is not None:
-                    out[f"{tag}/grad/{n}"] = p.grad.clone()
-        if share_grads:
-            for p, q in zip(models[0].parameters(), models[1].parameters()):
-                assert (p.grad is None) == (q.grad is None)
-                if p.grad is not None:
-                    q.grad.copy_(p.grad)
-        for m, opt, check, out in zip(models, opts, checks, outs):
-            opt.step()
-            check()
-            for n, p in m.named_parameters():
-                out[f"{tag}/param/{n}"] = p.detach().clone()
-    forward("after", x, f)
-    return outs
+    data = (synth.synth_images(2, salt=5).to(dev), synth.synth_pose_features(2, salt=5).to(dev),
+            synth.synth_labels(2, 12, salt=5).to(dev))
+    return plan_run(models, checks, share_grads, data, small=1)
 
 
 @pytest.mark.parametrize("dt", [BF16, F32], ids=["bf16", "f32"])
@@ -721,17 +676,5 @@ def test_plan_on_a_guarded_workspace(dt):
     # the engine was not rebuilt on the way: every call above ran on the guarded workspace
     eng = models[1]._engine
     assert eng.workspace is ws and eng.ws_ptr.value == ws.data_ptr() and ws.numel() == eng.workspace_bytes
-    assert want.keys() == got.keys() and any("/grad/" in k for k in want)
-    for k in want:
-        assert bool(torch.isfinite(got[k]).all()), k
-        if dt == BF16:        # the bf16 build is bit-reproducible (tests/test_clip_adam_gpu.py)
-            assert torch.equal(want[k], got[k]), k
-        elif "/param/" in k:  # f32: the bounds tests/test_clip_adam_gpu.py uses for twins
-            assert float((want[k] - got[k]).abs().max()) <= ADAM_TOL * float(want[k].abs().max()), k
-        elif "/grad/" in k:
-            # Recorded before twin 0's gradients are copied over.  Two runs of the f32 backward differ in the order in which
-            # atomics add partial tiles, nothing else; each is held to 1e-3 of max|ref| against the oracle (DESIGN.md section 2,
-            # the f32 build's tolerance for the train step), so that is what two of them may differ by at the very most.
-            assert rel_err(got[k].cpu(), want[k].cpu()) <= 1e-3, k
-        else:
-            assert rel_err(got[k].cpu(), want[k].cpu()) <= 1e-5, k
+    # bf16: bit for bit; f32: ADAM_TOL for the stepped parameters, 1e-3 for the gradients, 1e-5 for the rest
+    compare_twins(want, got, dt)
