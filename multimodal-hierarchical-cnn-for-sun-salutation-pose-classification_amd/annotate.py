@@ -26,6 +26,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._abi import AnnotateDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 
 NUM_LANDMARKS = 33             # QT_POSE_LANDMARKS
@@ -42,25 +43,6 @@ MAJOR_SEGMENTS = ((11, 12), (23, 24), (11, 23), (12, 24), (11, 13), (12, 14), (1
                   (25, 27), (26, 28))
 
 _U8x3 = ctypes.c_ubyte * 3
-
-
-class AnnotateDesc(ctypes.Structure):   # qt_annotate_desc
-    _fields_ = [("batch", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("n_segments", ctypes.c_int),
-                ("min_visibility", ctypes.c_float), ("thick_major", ctypes.c_int), ("thick_minor", ctypes.c_int),
-                ("radius_hi", ctypes.c_int), ("radius_lo", ctypes.c_int),
-                ("line_hi", _U8x3), ("line_lo", _U8x3), ("point_hi", _U8x3), ("point_lo", _U8x3),
-                ("num_classes", ctypes.c_int), ("glyph_h", ctypes.c_int), ("glyph_w", ctypes.c_int),
-                ("ox", ctypes.c_int), ("oy", ctypes.c_int), ("caption_colour", _U8x3)]
-
-
-def bind(L):
-    """argtypes of the entry point (idempotent)"""
-    if getattr(L, "_annotate_bound", False):
-        return L
-    L.qt_annotate_u8.argtypes = [ctypes.POINTER(AnnotateDesc)] + [ctypes.c_void_p] * 10
-    L.qt_annotate_u8.restype = ctypes.c_int
-    L._annotate_bound = True
-    return L
 
 
 def caption_atlas(class_names, prefix="Pose: ", height=24, font=None):
@@ -230,7 +212,7 @@ class FrameAnnotator:
             raise QtError(f"{what}: confidence belongs to pred")
         desc = AnnotateDesc.from_buffer_copy(self._desc)
         desc.batch, desc.H, desc.W = batch, H, W
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             _lib.check(L.qt_annotate_u8(ctypes.byref(desc), _lib.ptr(frames), _lib.ptr(landmarks), _lib.ptr(detected),
                                         _lib.ptr(segments if landmarks is not None else None), _lib.ptr(pred),

@@ -22,32 +22,13 @@ import math
 import torch
 
 from . import _lib
+from ._abi import AugmentDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 from .preprocess import IMAGENET_MEAN, IMAGENET_STD, _one_batch_dim, _triple
 
 PARAMS = 12          # QT_AUGMENT_PARAMS
 MAX_BLUR = 15        # largest blur kernel per axis (csrc/augment.hip)
 OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE = 0, 1, 2, 3
-
-
-class AugmentDesc(ctypes.Structure):   # qt_augment_desc
-    _fields_ = [("batch", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int),
-                ("src_image_stride", ctypes.c_longlong), ("dst_image_stride", ctypes.c_longlong),
-                ("blur_kx", ctypes.c_int), ("blur_ky", ctypes.c_int),
-                ("mean", ctypes.c_float * 3), ("inv_std", ctypes.c_float * 3), ("use_contrast", ctypes.c_int)]
-
-
-def bind(L):
-    """argtypes of the entry points (idempotent)"""
-    if getattr(L, "_augment_bound", False):
-        return L
-    L.qt_augment_f32.argtypes = [ctypes.POINTER(AugmentDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.qt_augment_f32.restype = ctypes.c_int
-    L.qt_augment_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.qt_augment_workspace_bytes.restype = ctypes.c_size_t
-    L._augment_bound = True
-    return L
 
 
 def _amount(v, what, limit=None):
@@ -168,11 +149,11 @@ class FrameAugmenter:
             f = images.contiguous().view(n, 3, h, w)
         src_stride = f.stride(0) if n > 1 else 3 * h * w
         use_contrast = int(self.contrast > 0.0)
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             ws, ws_bytes = None, 0
             if use_contrast:
-                ws_bytes = int(L.qt_augment_workspace_bytes(n, 1))
+                ws_bytes = L.qt_augment_workspace_bytes(n, 1)
                 ws = self._workspace.get(dev)
                 if ws is None or ws.numel() * 4 < ws_bytes:
                     ws = self._workspace[dev] = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)

@@ -1305,9 +1305,13 @@ extern "C" int qt_col_sum(int dtype, const void* x, long long rows, int cols, in
 // Deterministic form: row chunks of 128 rows (at most 1024 chunks), each chunk's column sums written to the workspace, then
 // added in chunk order (the same bits on every run; qt_col_sum's atomics depend on the order the chunks finish in)
 constexpr int kColSumMaxParts = 1024;
+// (the division stays in 64 bits: qt_cdiv's int result wraps to 0 parts from 2^38 rows on)
+static inline int col_sum_parts(long long rows) {
+  const long long chunks = (rows + 127) / 128;
+  return (int)(chunks < 1 ? 1 : (chunks < kColSumMaxParts ? chunks : kColSumMaxParts));
+}
 extern "C" size_t qt_col_sum_workspace_bytes(long long rows, int cols) {
-  const long long nparts = rows < 1 ? 1 : (qt_cdiv(rows, 128) < kColSumMaxParts ? qt_cdiv(rows, 128) : kColSumMaxParts);
-  return (size_t)nparts * (cols < 1 ? 1 : cols) * 4;
+  return (size_t)col_sum_parts(rows) * (cols < 1 ? 1 : cols) * 4;
 }
 
 extern "C" int qt_col_sum_ws(int dtype, const void* x, long long rows, int cols, int ld, float* out, int accumulate,
@@ -1317,7 +1321,7 @@ extern "C" int qt_col_sum_ws(int dtype, const void* x, long long rows, int cols,
   QT_CHECK_ARG(workspace_bytes >= qt_col_sum_workspace_bytes(rows, cols), "qt_col_sum_ws: workspace of %zu bytes < %zu",
                workspace_bytes, qt_col_sum_workspace_bytes(rows, cols));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nparts = qt_cdiv(rows, 128) < kColSumMaxParts ? qt_cdiv(rows, 128) : kColSumMaxParts;
+  const int nparts = col_sum_parts(rows);
   const int rpb = qt_cdiv(rows, nparts);
   float* part = static_cast<float*>(workspace);
   qt_by_dtype(dtype, [&](auto* t) {

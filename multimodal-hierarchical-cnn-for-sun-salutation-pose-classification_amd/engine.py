@@ -11,20 +11,12 @@ import os
 import torch
 
 from . import _lib
+from ._abi import AdamDesc, AdamItem, PlanDesc, bind as _bind_api  # noqa: F401  (old names stay importable)
 from ._lib import QtError
 
 QT_MODEL_QUADTREE, QT_MODEL_STANDARD_RESNET, QT_MODEL_ATTENTION, QT_MODEL_CNN_LSTM = 0, 1, 2, 3
 MODES = {"fusion": 0, "image_only": 1, "numerical_only": 2}
 QT_BWD_HEAD, QT_BWD_LAYER4, QT_BWD_LAYER32, QT_BWD_LAYER1, QT_BWD_ALL = 1, 2, 4, 8, 15
-
-
-class PlanDesc(ctypes.Structure):
-    _fields_ = [
-        ("dtype", ctypes.c_int), ("batch", ctypes.c_int), ("num_classes", ctypes.c_int),
-        ("model", ctypes.c_int), ("mode", ctypes.c_int), ("numerical_dim", ctypes.c_int),
-        ("dropout_p", ctypes.c_float), ("bn_eps", ctypes.c_float), ("bn_momentum", ctypes.c_float),
-        ("seq_len", ctypes.c_int), ("lstm_hidden", ctypes.c_int),
-    ]
 
 
 def default_compute_dtype():
@@ -38,66 +30,12 @@ def default_compute_dtype():
     raise QtError(f"QTCNN_DTYPE={name!r}: expected bf16 or f32")
 
 
-class AdamDesc(ctypes.Structure):   # qt_adam_desc
-    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
-                ("weight_decay", ctypes.c_float), ("grad_scale", ctypes.c_float), ("step", ctypes.c_int)]
-
-
-class AdamItem(ctypes.Structure):   # qt_adam_item
-    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
-                ("exp_avg_sq", ctypes.c_void_p), ("numel", ctypes.c_longlong)]
-
-
-def _bind_api(L):
-    if getattr(L, "_plan_bound", False):
-        return
-    L.qt_plan_create.argtypes = [ctypes.POINTER(PlanDesc), ctypes.POINTER(ctypes.c_void_p)]
-    L.qt_plan_destroy.argtypes = [ctypes.c_void_p]
-    L.qt_plan_destroy.restype = None
-    L.qt_plan_num_tensors.argtypes = [ctypes.c_void_p]
-    L.qt_plan_tensor_name.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.qt_plan_tensor_name.restype = ctypes.c_char_p
-    L.qt_plan_tensor_kind.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.qt_plan_tensor_shape.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    L.qt_plan_workspace_bytes.argtypes = [ctypes.c_void_p]
-    L.qt_plan_workspace_bytes.restype = ctypes.c_size_t
-    L.qt_plan_init_workspace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_plan_pack_weights.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    L.qt_plan_forward.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_void_p]
-    L.qt_plan_backward.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    L.qt_plan_backward_dx.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_plan_side_fence.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_plan_adam_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.POINTER(AdamDesc), ctypes.c_int, ctypes.c_void_p]
-    L.qt_plan_adam_step_overlapped.argtypes = L.qt_plan_adam_step.argtypes + [ctypes.POINTER(ctypes.c_int)]
-    L.qt_plan_adam_step_clipped.argtypes = L.qt_plan_adam_step.argtypes[:-1] + [
-        ctypes.c_float, ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-        ctypes.c_void_p]
-    L.qt_adam_multi.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.POINTER(AdamDesc), ctypes.c_void_p]
-    L.qt_adam_multi_scaled.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.POINTER(AdamDesc), ctypes.c_void_p,
-                                       ctypes.c_void_p]
-    L.qt_grad_norm_workspace_bytes.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int]
-    L.qt_grad_norm_workspace_bytes.restype = ctypes.c_size_t
-    L.qt_grad_norm_multi.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
-                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_plan_find_buffer.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t)]
-    L.qt_plan_num_regions.argtypes = [ctypes.c_void_p]
-    L.qt_plan_region.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
-                                 ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
-    L.qt_set_plan_guard_gap.argtypes = [ctypes.c_size_t]
-    L._plan_bound = True
-
-
 class PlanEngine:
     """One qt_plan + its workspace for one (model variant, device, dtype, max batch)."""
 
     def __init__(self, model_kind, mode, num_classes, numerical_dim, dropout_p, batch, dtype, device, seq_len=0,
                  lstm_hidden=0):
         self.L = _lib.lib()
-        _bind_api(self.L)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise QtError("the QuadtreeCNN plan runs on an AMD GPU only (device must be cuda:N); no CPU fallback")
@@ -273,7 +211,7 @@ class PlanEngine:
         logits = torch.empty(batch // self.rows_per_logit, self.num_classes, dtype=torch.float32, device=self.device)
         _lib.check(self.L.qt_plan_forward(self.handle, self.ws_ptr, self._tensor_ptrs,
                                           _lib.ptr(image), _lib.ptr(numerical), _lib.ptr(logits), batch,
-                                          int(training), ctypes.c_ulonglong(seed), _lib.stream_ptr()),
+                                          int(training), seed, _lib.stream_ptr()),
                    "qt_plan_forward")
         self.fwd_counter += 1
         self._handed_out = None

@@ -25,34 +25,17 @@ COLORMAP_JET table and has not been compared with it (OpenCV is not a dependency
 Not built: a one-hot backward that skips the weight gradients (the model's ordinary backward runs), temporal upsampling of
 a clip's [t,h,w] map, other colour maps as built-ins, guided Grad-CAM.  There is no torch fallback.
 """
-import ctypes
 
 import torch
 
 from . import _lib
+from ._abi import bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 from .preprocess import FramePreprocessor
 from .quadtree import QuadtreeCNN, StandardResNetCNN
 from .video3d import Quadtree3DCNN
 
 MAX_POSITIONS = 4096   # QT_GRADCAM_MAX_POSITIONS
-
-
-def bind(L):
-    """argtypes of the entry points (idempotent)"""
-    if getattr(L, "_gradcam_bound", False):
-        return L
-    L.qt_gradcam_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.qt_gradcam_workspace_bytes.restype = ctypes.c_size_t
-    L.qt_gradcam_map.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.qt_gradcam_map.restype = ctypes.c_int
-    L.qt_gradcam_overlay_u8.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_gradcam_overlay_u8.restype = ctypes.c_int
-    L._gradcam_bound = True
-    return L
 
 
 def jet_lut(order="bgr"):
@@ -100,11 +83,11 @@ def gradcam_map(act, grad):
     B, C = int(act.shape[0]), int(act.shape[1])
     P = act[0, 0].numel()
     act, grad = act.contiguous(), grad.contiguous()
-    L = bind(_lib.lib())
+    L = _lib.lib()
     with torch.cuda.device(act.device):
         cam = torch.empty((B,) + tuple(act.shape[2:]), dtype=torch.float32, device=act.device)
         peak = torch.empty(B, dtype=torch.float32, device=act.device)
-        ws_bytes = int(L.qt_gradcam_workspace_bytes(B, C, min(P, MAX_POSITIONS)))
+        ws_bytes = L.qt_gradcam_workspace_bytes(B, C, min(P, MAX_POSITIONS))
         ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=act.device) if ws_bytes else None
         _lib.check(L.qt_gradcam_map(act.data_ptr(), grad.data_ptr(), B, C, P, cam.data_ptr(), peak.data_ptr(), _lib.ptr(ws),
                                     ws_bytes, _lib.stream_ptr()), "qt_gradcam_map")
@@ -224,7 +207,7 @@ class GradCAM:
                 if tuple(t.shape) != (B, H, W) or not t.is_contiguous():
                     raise ValueError(f"GradCAM: {name} must be a contiguous [{B},{H},{W}] tensor")
         frames_u8, cam = frames_u8.contiguous(), cam.contiguous()
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             out = torch.empty_like(frames_u8)
             _lib.check(L.qt_gradcam_overlay_u8(cam.data_ptr(), int(cam.shape[1]), int(cam.shape[2]), frames_u8.data_ptr(), B, H, W,

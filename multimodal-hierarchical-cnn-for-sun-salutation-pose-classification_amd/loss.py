@@ -23,33 +23,12 @@ import ctypes
 import torch
 
 from . import _lib
+from ._abi import LossDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 
 QT_LOSS_CROSS_ENTROPY, QT_LOSS_FOCAL = 0, 1
 _REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
 MAX_CLASSES = 1024
-
-
-class LossDesc(ctypes.Structure):   # qt_loss_desc
-    _fields_ = [("dtype", ctypes.c_int), ("kind", ctypes.c_int), ("reduction", ctypes.c_int),
-                ("ignore_index", ctypes.c_longlong), ("label_smoothing", ctypes.c_float), ("gamma", ctypes.c_float),
-                ("class_weight", ctypes.c_void_p)]
-
-
-def bind(L):
-    """argtypes of the three entry points (idempotent)"""
-    if getattr(L, "_loss_bound", False):
-        return L
-    L.qt_loss_workspace_bytes.argtypes = [ctypes.c_longlong, ctypes.c_int]
-    L.qt_loss_workspace_bytes.restype = ctypes.c_size_t
-    L.qt_loss_forward.argtypes = [ctypes.POINTER(LossDesc), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                  ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.qt_loss_backward.argtypes = [ctypes.POINTER(LossDesc), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                   ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                   ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
-    L._loss_bound = True
-    return L
 
 
 class LossMeter:
@@ -106,7 +85,7 @@ class _LossFn(torch.autograd.Function):
         y = labels.contiguous()
         rows, C = z.shape
         dev = z.device
-        L = bind(_lib.lib())
+        L = _lib.lib()
         desc = LossDesc(_lib.QT_F32, kind, reduction, ignore_index, smoothing, gamma, _lib.ptr(weight))
         keep = ctx.needs_input_grad[0]
         with torch.cuda.device(dev):
@@ -137,7 +116,7 @@ class _LossFn(torch.autograd.Function):
         if grad_loss.device != z.device:
             raise QtError("loss backward: the upstream gradient must be on the logits' device")
         g = grad_loss.to(torch.float32).contiguous()
-        L = bind(_lib.lib())
+        L = _lib.lib()
         desc = LossDesc(_lib.QT_F32, kind, reduction, ignore_index, smoothing, gamma, _lib.ptr(weight))
         with torch.cuda.device(z.device):
             dz = torch.empty(rows, C, dtype=torch.float32, device=z.device)

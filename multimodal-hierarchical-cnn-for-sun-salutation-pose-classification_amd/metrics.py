@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._abi import MetricsDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 from .loss import _row_major
 
@@ -34,28 +35,6 @@ MAX_CLASSES = 1024          # QT_METRICS_MAX_CLASSES
 MAX_ROWS = 1 << 22
 SCALARS = ("accuracy", "weighted_precision", "weighted_recall", "weighted_f1", "macro_precision", "macro_recall", "macro_f1",
            "r2", "samples", "ignored", "invalid", "classes_present")
-
-
-class MetricsDesc(ctypes.Structure):   # qt_metrics_desc
-    _fields_ = [("dtype", ctypes.c_int), ("ignore_index", ctypes.c_longlong)]
-
-
-def bind(L):
-    """argtypes of the four entry points (idempotent)"""
-    if getattr(L, "_metrics_bound", False):
-        return L
-    L.qt_metrics_state_bytes.argtypes = [ctypes.c_int]
-    L.qt_metrics_state_bytes.restype = ctypes.c_size_t
-    L.qt_metrics_report_bytes.argtypes = [ctypes.c_int]
-    L.qt_metrics_report_bytes.restype = ctypes.c_size_t
-    L.qt_metrics_update.argtypes = [ctypes.POINTER(MetricsDesc), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_metrics_update.restype = ctypes.c_int
-    L.qt_metrics_finalize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_metrics_finalize.restype = ctypes.c_int
-    L._metrics_bound = True
-    return L
 
 
 def _check_logits(logits, what, C=None):
@@ -88,7 +67,7 @@ def _check_index_vector(t, name, rows, dev, what):
 
 def _update(logits, predictions, labels, state, C, ignore_index, want_probs):
     """one qt_metrics_update launch on checked operands; returns (probs, confidence, pred) or None"""
-    L = bind(_lib.lib())
+    L = _lib.lib()
     z = None if logits is None else _row_major(logits.detach())
     rows, dev = (z.shape[0], z.device) if z is not None else (predictions.shape[0], predictions.device)
     with torch.cuda.device(dev):
@@ -173,7 +152,7 @@ class EvalMeter:
 
     def _read(self):
         """finalize launch, then one copy: (counts int64 [C*C + 4], report float64 [4C + 12]) as numpy arrays"""
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(self.state.device):
             _lib.check(L.qt_metrics_finalize(_lib.ptr(self.state), self.num_classes, _lib.ptr(self._report),
                                              _lib.stream_ptr()), "qt_metrics_finalize")

@@ -51,7 +51,7 @@ import os
 import torch
 
 from . import _lib
-from .engine import AdamDesc, AdamItem, _bind_api
+from .engine import AdamDesc, AdamItem
 
 
 # Parameter updates made through raw pointers (qt_adam_multi) do not bump torch's version counters: consumers that cache
@@ -106,7 +106,6 @@ def grad_norm(parameters):
         raise _lib.QtError("grad_norm: no parameter has a gradient")
     grads = [g.contiguous() for g in grads]
     L = _lib.lib()
-    _bind_api(L)
     items = _norm_items(grads)
     dev = grads[0].device
     with torch.cuda.device(dev):
@@ -158,7 +157,6 @@ class FusedAdam(torch.optim.Optimizer):
     def _begin_clip(self, L, max_norm):
         """Everything the clipped step needs before its first update: the gradients of all groups (the norm is global),
         the norm kernel's workspace and the two output floats.  No device work yet."""
-        _bind_api(L)
         grads = [(id(p), p.grad.contiguous()) for group in self.param_groups for p in group["params"] if p.grad is not None]
         self.last_grad_norm = self.last_clip_coef = None
         if not grads:
@@ -182,7 +180,6 @@ class FusedAdam(torch.optim.Optimizer):
         if engine is not None and self._model._param_list is not None:
             plan_index = {id(p): i for p, i in zip(self._model._param_list, self._model._param_plan_index) if i >= 0}
         L = _lib.lib()
-        L.qt_adam_multi.argtypes = [ctypes.POINTER(AdamItem), ctypes.c_int, ctypes.POINTER(AdamDesc), ctypes.c_void_p]
         max_norm = self._max_grad_norm()
         clip = self._begin_clip(L, max_norm) if max_norm is not None else None
         fused_groups = 0

@@ -27,6 +27,7 @@ import json
 import torch
 
 from . import _lib
+from ._abi import PoseDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 
 NUM_LANDMARKS, NUM_FEATURES = 33, 47   # QT_POSE_LANDMARKS, QT_POSE_FEATURES
@@ -40,21 +41,6 @@ FEATURE_NAMES = tuple(
        "RIGHT_KNEE_ANGLE", "LEFT_HIP_ANGLE", "RIGHT_HIP_ANGLE", "TORSO_VERTICAL_ANGLE", "TORSO_HORIZONTAL_ALIGNMENT",
        "DIST_LR_WRIST_NORM", "DIST_LR_ANKLE_NORM", "DIST_L_WRIST_HIP_NORM", "TORSO_VAR_XY_RATIO"])
 assert len(FEATURE_NAMES) == NUM_FEATURES
-
-
-class PoseDesc(ctypes.Structure):   # qt_pose_desc
-    _fields_ = [("rows", ctypes.c_longlong), ("mode", ctypes.c_int), ("rows_per_label", ctypes.c_int),
-                ("num_classes", ctypes.c_int)]
-
-
-def bind(L):
-    """argtypes of the entry point (idempotent)"""
-    if getattr(L, "_pose_bound", False):
-        return L
-    L.qt_pose_features.argtypes = [ctypes.POINTER(PoseDesc)] + [ctypes.c_void_p] * 8
-    L.qt_pose_features.restype = ctypes.c_int
-    L._pose_bound = True
-    return L
 
 
 def _device_tensor(t, name, dtype, dev=None):
@@ -172,7 +158,7 @@ class PoseFeatures:
             stds = None if self.stds is None else _device_tensor(self.stds, "stds", torch.float32, dev)
         else:
             labels = means = stds = None
-        L = bind(_lib.lib())
+        L = _lib.lib()
         desc = PoseDesc(rows, _MODES[self.mode], rows_per_label, int(means.shape[0]) if by_class else 0)
         with torch.cuda.device(dev):
             _lib.check(L.qt_pose_features(ctypes.byref(desc), _lib.ptr(landmarks), _lib.ptr(detected), _lib.ptr(raw),

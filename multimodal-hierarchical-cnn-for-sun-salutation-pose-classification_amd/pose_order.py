@@ -171,6 +171,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._abi import PoseDurationDesc, PoseDurationLagDesc, PoseLagDesc, PoseOrderDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 
 TILE = 64                   # QT_POSE_ORDER_TILE
@@ -202,100 +203,6 @@ LOG2_TABLE = (
     220, 221, 222, 222, 223, 224, 225, 226, 226, 227, 228, 229, 229, 230, 231, 232,
     233, 233, 234, 235, 236, 236, 237, 238, 239, 239, 240, 241, 242, 242, 243, 244,
     245, 245, 246, 247, 248, 248, 249, 250, 251, 251, 252, 253, 253, 254, 255, 256)
-
-
-class PoseOrderDesc(ctypes.Structure):   # qt_pose_order_desc
-    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int)]
-
-
-class PoseLagDesc(ctypes.Structure):     # qt_pose_lag_desc
-    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
-                ("lag", ctypes.c_int), ("flush", ctypes.c_int), ("seen", ctypes.c_longlong)]
-
-
-class PoseDurationDesc(ctypes.Structure):   # qt_pose_duration_desc
-    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
-                ("max_duration", ctypes.c_int)]
-
-
-class PoseDurationLagDesc(ctypes.Structure):   # qt_pose_duration_lag_desc
-    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_states", ctypes.c_int),
-                ("max_duration", ctypes.c_int), ("lag", ctypes.c_int), ("flush", ctypes.c_int), ("seen", ctypes.c_longlong)]
-
-
-def bind(L):
-    """argtypes of the entry points (idempotent)"""
-    if getattr(L, "_pose_order_bound", False):
-        return L
-    L.qt_pose_order_workspace_bytes.argtypes = [ctypes.POINTER(PoseOrderDesc)]
-    L.qt_pose_order_workspace_bytes.restype = ctypes.c_longlong
-    L.qt_pose_order_decode.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 8 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_order_decode.restype = ctypes.c_int
-    L.qt_pose_posterior_workspace_bytes.argtypes = [ctypes.POINTER(PoseOrderDesc)]
-    L.qt_pose_posterior_workspace_bytes.restype = ctypes.c_longlong
-    L.qt_pose_posterior.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 9 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_posterior.restype = ctypes.c_int
-    L.qt_pose_prior_workspace_bytes.argtypes = [ctypes.POINTER(PoseOrderDesc)]
-    L.qt_pose_prior_workspace_bytes.restype = ctypes.c_longlong
-    L.qt_pose_prior_expect.argtypes = [ctypes.POINTER(PoseOrderDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 7 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_prior_expect.restype = ctypes.c_int
-    L.qt_pose_prior_count_paths.argtypes = [ctypes.POINTER(PoseOrderDesc)] + [ctypes.c_void_p] * 5 + \
-        [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_prior_count_paths.restype = ctypes.c_int
-    L.qt_pose_prior_update.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 5
-    L.qt_pose_prior_update.restype = ctypes.c_int
-    for name in ("qt_pose_lag_smooth_carry_bytes", "qt_pose_lag_smooth_workspace_bytes", "qt_pose_lag_decode_carry_bytes",
-                 "qt_pose_lag_decode_workspace_bytes"):
-        getattr(L, name).argtypes = [ctypes.POINTER(PoseLagDesc)]
-        getattr(L, name).restype = ctypes.c_longlong
-    L.qt_pose_lag_smooth.argtypes = [ctypes.POINTER(PoseLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 10 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_lag_smooth.restype = ctypes.c_int
-    L.qt_pose_lag_decode.argtypes = [ctypes.POINTER(PoseLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 8 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_lag_decode.restype = ctypes.c_int
-    L.qt_pose_duration_workspace_bytes.argtypes = [ctypes.POINTER(PoseDurationDesc)]
-    L.qt_pose_duration_workspace_bytes.restype = ctypes.c_longlong
-    L.qt_pose_duration_decode.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 10 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_duration_decode.restype = ctypes.c_int
-    L.qt_pose_duration_count.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 3
-    L.qt_pose_duration_count.restype = ctypes.c_int
-    L.qt_pose_duration_posterior_workspace_bytes.argtypes = [ctypes.POINTER(PoseDurationDesc)]
-    L.qt_pose_duration_posterior_workspace_bytes.restype = ctypes.c_longlong
-    L.qt_pose_duration_posterior.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 12 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_duration_posterior.restype = ctypes.c_int
-    for name in ("qt_pose_duration_lag_carry_bytes", "qt_pose_duration_lag_workspace_bytes"):
-        getattr(L, name).argtypes = [ctypes.POINTER(PoseDurationLagDesc)]
-        getattr(L, name).restype = ctypes.c_longlong
-    L.qt_pose_duration_lag_decode.argtypes = [ctypes.POINTER(PoseDurationLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 12 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_duration_lag_decode.restype = ctypes.c_int
-    for name in ("qt_pose_duration_lag_smooth_carry_bytes", "qt_pose_duration_lag_smooth_workspace_bytes"):
-        getattr(L, name).argtypes = [ctypes.POINTER(PoseDurationLagDesc)]
-        getattr(L, name).restype = ctypes.c_longlong
-    L.qt_pose_duration_lag_smooth.argtypes = [ctypes.POINTER(PoseDurationLagDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 13 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_duration_lag_smooth.restype = ctypes.c_int
-    L.qt_pose_duration_prior_workspace_bytes.argtypes = [ctypes.POINTER(PoseDurationDesc)]
-    L.qt_pose_duration_prior_workspace_bytes.restype = ctypes.c_longlong
-    L.qt_pose_duration_prior_expect.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_longlong] + \
-        [ctypes.c_void_p] * 11 + [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_duration_prior_expect.restype = ctypes.c_int
-    L.qt_pose_duration_prior_count_paths.argtypes = [ctypes.POINTER(PoseDurationDesc), ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_longlong] + [ctypes.c_void_p] * 6 + \
-        [ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_pose_duration_prior_count_paths.restype = ctypes.c_int
-    L.qt_pose_duration_prior_update.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + \
-        [ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 8
-    L.qt_pose_duration_prior_update.restype = ctypes.c_int
-    L._pose_order_bound = True
-    return L
 
 
 def scan_trip_tiles(num_states):
@@ -476,7 +383,7 @@ class _PoseTables:
         """the entry point `name` on this object's device and torch's current stream: `desc` (a descriptor, passed by
         reference, or the leading number of an entry point without one), then `args` (tensors as their addresses, None and
         numbers as they are), then, where `workspace` names the size query, the workspace and its size, then the stream"""
-        L = bind(_lib.lib())
+        L = _lib.lib()
         room = self._room(getattr(L, workspace), desc) if workspace else ()
         args = [a if a is None or a.__class__ in _NUMBERS else a.data_ptr() for a in args]   # (this runs once per live frame)
         with torch.cuda.device(self.device):
@@ -904,7 +811,7 @@ class _LagState:
     def _lag_init(self, lag, carry_query, desc):
         """desc: the descriptor of one frame, which `carry_query` takes"""
         self.lag, self.seen = int(lag), 0
-        nbytes = int(getattr(bind(_lib.lib()), carry_query)(ctypes.byref(desc)))
+        nbytes = getattr(_lib.lib(), carry_query)(ctypes.byref(desc))
         self._carry = [torch.zeros(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]  # [0]: the next call's carry_in
 
     def reset(self):

@@ -31,6 +31,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._abi import PoseSeqDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 from .pose import NUM_LANDMARKS, QT_POSE_RAW, QT_POSE_ZERO
 
@@ -47,21 +48,6 @@ SEQUENCE_FEATURE_NAMES = tuple(
     + [f"LM{j}_{c}_px" for j in range(NUM_LANDMARKS) for c in ("vx", "vy", "vz", "ax", "ay", "az")]
     + ["TORSO_VAR_XY_RATIO"])
 assert len(SEQUENCE_FEATURE_NAMES) == NUM_SEQUENCE_FEATURES
-
-
-class PoseSeqDesc(ctypes.Structure):   # qt_pose_seq_desc
-    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int),
-                ("mode", ctypes.c_int)]
-
-
-def bind(L):
-    """argtypes of the entry point (idempotent)"""
-    if getattr(L, "_pose_seq_bound", False):
-        return L
-    L.qt_pose_sequence_features.argtypes = [ctypes.POINTER(PoseSeqDesc)] + [ctypes.c_void_p] * 9
-    L.qt_pose_sequence_features.restype = ctypes.c_int
-    L._pose_seq_bound = True
-    return L
 
 
 def _device_tensor(t, name, dtype, dev=None):
@@ -173,7 +159,7 @@ class SequencePoseFeatures:
         out = torch.empty(lead + (NUM_SEQUENCE_FEATURES,), dtype=torch.float32, device=dev)
         w, h = self.frame_size if self.frame_size is not None else (0, 0)
         desc = PoseSeqDesc(B, T, w, h, _MODES[self.mode])
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             _lib.check(L.qt_pose_sequence_features(ctypes.byref(desc), _lib.ptr(landmarks), _lib.ptr(detected), _lib.ptr(sizes),
                                                    _lib.ptr(hist_in), _lib.ptr(count_in), _lib.ptr(hist_out),

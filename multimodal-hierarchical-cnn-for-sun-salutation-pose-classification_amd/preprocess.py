@@ -21,29 +21,12 @@ import math
 import torch
 
 from . import _lib
+from ._abi import PreprocessDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 
 MAX_DOWNSCALE = 24   # per axis, frame size / output size (csrc/preprocess.hip)
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-
-
-class PreprocessDesc(ctypes.Structure):   # qt_preprocess_desc
-    _fields_ = [("batch", ctypes.c_int), ("src_h", ctypes.c_int), ("src_w", ctypes.c_int),
-                ("src_row_stride", ctypes.c_longlong), ("src_image_stride", ctypes.c_longlong),
-                ("out_h", ctypes.c_int), ("out_w", ctypes.c_int), ("bgr", ctypes.c_int),
-                ("mean", ctypes.c_float * 3), ("inv_std", ctypes.c_float * 3)]
-
-
-def bind(L):
-    """argtypes of the entry point (idempotent)"""
-    if getattr(L, "_preprocess_bound", False):
-        return L
-    L.qt_preprocess_u8.argtypes = [ctypes.POINTER(PreprocessDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                   ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
-    L.qt_preprocess_u8.restype = ctypes.c_int
-    L._preprocess_bound = True
-    return L
 
 
 def _triple(v, what):
@@ -120,7 +103,7 @@ class FramePreprocessor:
             f = frames.contiguous().view(n, H, W, 3)
         row_stride = f.stride(1)
         image_stride = f.stride(0) if n > 1 else H * row_stride
-        L = bind(_lib.lib())
+        L = _lib.lib()
         desc = PreprocessDesc(n, H, W, row_stride, image_stride, h, w, int(self.channel_order == "bgr"),
                               (ctypes.c_float * 3)(*self.mean), (ctypes.c_float * 3)(*self.inv_std))
         with torch.cuda.device(dev):

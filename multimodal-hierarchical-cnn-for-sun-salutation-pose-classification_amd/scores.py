@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._abi import ScoresDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 from .loss import _row_major
 from .metrics import MAX_ROWS, _check_index_vector
@@ -33,29 +34,6 @@ ROUTE_AUTO, ROUTE_DIRECT, ROUTE_PRIVATE = 0, 1, 2
 COUNTERS = ("samples", "ignored", "invalid", "nan_rows", "updates")
 SCALARS = ("macro_auc", "weighted_auc", "macro_ap", "weighted_ap", "ece", "mce", "samples", "ignored", "invalid", "nan_rows",
            "classes_scored", "updates")
-
-
-class ScoresDesc(ctypes.Structure):   # qt_scores_desc
-    _fields_ = [("dtype", ctypes.c_int), ("kind", ctypes.c_int), ("bits", ctypes.c_int), ("cal_bins", ctypes.c_int),
-                ("route", ctypes.c_int), ("ignore_index", ctypes.c_longlong)]
-
-
-def bind(L):
-    """argtypes of the four entry points (idempotent)"""
-    if getattr(L, "_scores_bound", False):
-        return L
-    L.qt_scores_state_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.qt_scores_state_bytes.restype = ctypes.c_size_t
-    L.qt_scores_report_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.qt_scores_report_bytes.restype = ctypes.c_size_t
-    L.qt_scores_update.argtypes = [ctypes.POINTER(ScoresDesc), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                   ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_scores_update.restype = ctypes.c_int
-    L.qt_scores_finalize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p]
-    L.qt_scores_finalize.restype = ctypes.c_int
-    L._scores_bound = True
-    return L
 
 
 def _int_in(value, lo, hi, what):
@@ -130,14 +108,14 @@ class ScoreMeter:
             raise QtError(f"{what}: needs {name} [rows, {C}] with 1 <= rows <= {MAX_ROWS} (got {tuple(s.shape)})")
         labels = _check_index_vector(labels, "labels", s.shape[0], dev, what)
         s = _row_major(s.detach())
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             desc = ScoresDesc(_lib.QT_F32, kind, self.bits, self.cal_bins, self.route, self.ignore_index)
             _lib.check(L.qt_scores_update(ctypes.byref(desc), _lib.ptr(s), s.stride(0), _lib.ptr(labels), s.shape[0], C,
                                           _lib.ptr(self.state), _lib.stream_ptr()), "qt_scores_update")
 
     def _finalize(self, curves):
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(self.state.device):
             _lib.check(L.qt_scores_finalize(_lib.ptr(self.state), self.num_classes, self.bits, self.cal_bins,
                                             _lib.ptr(self._report), _lib.ptr(self._curves) if curves else None,

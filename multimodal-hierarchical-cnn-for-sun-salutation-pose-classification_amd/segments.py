@@ -34,6 +34,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._abi import SegmentsDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 
 MAX_SEGMENTS = 1024         # QT_SEGMENTS_MAX
@@ -46,28 +47,6 @@ EDIT_ONE = 1 << 32          # edit_q counts a video's edit score in units of 2^-
 RECORD_FIELDS = ("m", "n", "edit_distance", "frames_labelled", "frames_correct")
 STATE_FIELDS = ("videos", "videos_overflow", "videos_empty", "seg_pred", "seg_true", "edit_dist", "edit_max", "edit_q",
                 "frames_labelled", "frames_correct")
-
-
-class SegmentsDesc(ctypes.Structure):   # qt_segments_desc
-    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("num_thresholds", ctypes.c_int),
-                ("pct", ctypes.c_int * 8), ("capacity", ctypes.c_int)]
-
-
-def bind(L):
-    """argtypes of the three entry points (idempotent)"""
-    if getattr(L, "_segments_bound", False):
-        return L
-    L.qt_segments_workspace_bytes.argtypes = [ctypes.POINTER(SegmentsDesc)]
-    L.qt_segments_workspace_bytes.restype = ctypes.c_size_t
-    L.qt_segments_update.argtypes = [ctypes.POINTER(SegmentsDesc), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                     ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_size_t, ctypes.c_void_p]
-    L.qt_segments_update.restype = ctypes.c_int
-    L.qt_segments_encode.argtypes = [ctypes.POINTER(SegmentsDesc), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_segments_encode.restype = ctypes.c_int
-    L._segments_bound = True
-    return L
 
 
 def make_desc(batch, frames, num_classes, thresholds=(50,), capacity=0):
@@ -198,7 +177,7 @@ class SegmentMeter:
         lengths = _check_lengths(lengths, B, self.device, what)
         K = len(self.thresholds)
         desc = make_desc(B, T, self.num_classes, self.thresholds)
-        L = bind(_lib.lib())
+        L = _lib.lib()
         need = L.qt_segments_workspace_bytes(ctypes.byref(desc))
         if self._work is None or self._work.numel() * 8 < need:
             self._work = torch.empty(need // 8, dtype=torch.int64, device=self.device)   # (kept: the stream orders its reuse)
@@ -232,7 +211,7 @@ def segment_runs(values, num_classes, lengths=None, capacity=None):
     runs = torch.empty(B, capacity, 3, dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     desc = make_desc(B, T, num_classes, capacity=capacity)
-    L = bind(_lib.lib())
+    L = _lib.lib()
     with torch.cuda.device(dev):
         _lib.check(L.qt_segments_encode(ctypes.byref(desc), _lib.ptr(values), _row_stride(values), _lib.ptr(lengths),
                                         _lib.ptr(runs) if capacity else None, _lib.ptr(counts), _lib.stream_ptr()),

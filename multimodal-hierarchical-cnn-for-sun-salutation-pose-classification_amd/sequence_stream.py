@@ -20,11 +20,11 @@ Not built: training through the stream, image gradients, streams that advance by
 clip models (their temporal convolutions pad at window edges, so frames are not shareable), captured graphs of the live
 step.  There is no torch fallback: CPU tensors raise QtError.
 """
-import ctypes
 
 import torch
 
 from . import _lib
+from ._abi import bind  # noqa: F401  (<module>.bind is _abi.bind)
 from . import quadtree as _quadtree
 from ._lib import QtError
 
@@ -32,27 +32,6 @@ TILE = 8                    # QT_LSTM_STREAM_TILE: consecutive windows of one st
 MAX_WINDOW = 64
 HIDDEN_SIZES = (256, 64)
 IMAGE_HW = _quadtree.IMAGE_HW
-
-
-def bind(L):
-    """argtypes of the stream entry points (idempotent)"""
-    if getattr(L, "_lstm_stream_bound", False):
-        return L
-    P, I, LL, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t
-    L.qt_lstm_stream_workspace_bytes.argtypes = [I, I, I, I]
-    L.qt_lstm_stream_workspace_bytes.restype = Z
-    L.qt_lstm_stream_forward.argtypes = [P] * 9 + [P, Z, LL, I, I, I, I, P]
-    L.qt_lstm_stream_forward.restype = I
-    L.qt_lstm_stream_stage.argtypes = [P, P, P, I, I, I, I, P]
-    L.qt_lstm_stream_stage.restype = I
-    L.qt_plan_features.argtypes = [P, P, P, P, P, I, P]
-    L.qt_plan_features.restype = I
-    L.qt_plan_stream_workspace_bytes.argtypes = [P, I, I, I]
-    L.qt_plan_stream_workspace_bytes.restype = Z
-    L.qt_plan_stream_forward.argtypes = [P] * 8 + [P, Z, LL, I, I, I, P]
-    L.qt_plan_stream_forward.restype = I
-    L._lstm_stream_bound = True
-    return L
 
 
 class CnnLstmStream:
@@ -120,7 +99,7 @@ class CnnLstmStream:
         H = m.lstm_hidden_size
         with torch.cuda.device(device):
             eng = self._plan(S * n, device)
-            L = bind(eng.L)
+            L = eng.L
             if T > 1 and (self._carry is None or self._carry.device != device):
                 self._carry = torch.empty(2, S, T - 1, 4 * H, dtype=torch.float32, device=device)
                 self.seen = 0

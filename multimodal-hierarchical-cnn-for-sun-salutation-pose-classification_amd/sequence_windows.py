@@ -35,6 +35,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._abi import SeqFeaturesDesc, SeqGatherDesc, SeqWindowsDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 from .pose import _MODES, class_stats
 
@@ -43,37 +44,6 @@ MAX_FRAMES = 1 << 22
 MAX_SEQ_LEN = 64
 MAX_FEATURES = 1024
 _RULES = {"uniform": QT_SEQ_LABEL_UNIFORM, "last": QT_SEQ_LABEL_LAST}
-
-
-class SeqWindowsDesc(ctypes.Structure):   # qt_seq_windows_desc
-    _fields_ = [("frames", ctypes.c_int), ("clips", ctypes.c_int), ("seq_len", ctypes.c_int), ("stride", ctypes.c_int),
-                ("num_classes", ctypes.c_int), ("capacity", ctypes.c_int), ("rule", ctypes.c_int)]
-
-
-class SeqGatherDesc(ctypes.Structure):    # qt_seq_gather_desc
-    _fields_ = [("src_rows", ctypes.c_longlong), ("row_bytes", ctypes.c_longlong), ("windows", ctypes.c_int),
-                ("seq_len", ctypes.c_int)]
-
-
-class SeqFeaturesDesc(ctypes.Structure):  # qt_seq_features_desc
-    _fields_ = [("src_rows", ctypes.c_longlong), ("features", ctypes.c_int), ("windows", ctypes.c_int),
-                ("seq_len", ctypes.c_int), ("mode", ctypes.c_int), ("num_classes", ctypes.c_int)]
-
-
-def bind(L):
-    """argtypes of the entry points (idempotent)"""
-    if getattr(L, "_seq_windows_bound", False):
-        return L
-    L.qt_seq_windows_workspace_bytes.argtypes = [ctypes.POINTER(SeqWindowsDesc)]
-    L.qt_seq_windows_workspace_bytes.restype = ctypes.c_size_t
-    L.qt_seq_windows_plan.argtypes = [ctypes.POINTER(SeqWindowsDesc)] + [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]
-    L.qt_seq_windows_plan.restype = ctypes.c_int
-    L.qt_seq_gather_rows.argtypes = [ctypes.POINTER(SeqGatherDesc)] + [ctypes.c_void_p] * 4
-    L.qt_seq_gather_rows.restype = ctypes.c_int
-    L.qt_seq_gather_features.argtypes = [ctypes.POINTER(SeqFeaturesDesc)] + [ctypes.c_void_p] * 7
-    L.qt_seq_gather_features.restype = ctypes.c_int
-    L._seq_windows_bound = True
-    return L
 
 
 def _device_tensor(t, name, dtype=None, dev=None):
@@ -184,9 +154,9 @@ class SequenceWindows:
         starts = torch.empty(capacity, dtype=torch.int32, device=dev)
         labels = torch.empty(capacity, dtype=torch.int64, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
-        L = bind(_lib.lib())
+        L = _lib.lib()
         desc = SeqWindowsDesc(N, len(lengths), self.seq_len, self.stride, self.num_classes, capacity, _RULES[self.label])
-        nbytes = int(L.qt_seq_windows_workspace_bytes(ctypes.byref(desc)))
+        nbytes = L.qt_seq_windows_workspace_bytes(ctypes.byref(desc))
         workspace = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             _lib.check(L.qt_seq_windows_plan(ctypes.byref(desc), _lib.ptr(frame_labels), _lib.ptr(offsets), _lib.ptr(starts),
@@ -233,7 +203,7 @@ class SequenceWindows:
         B = int(starts.shape[0])
         out = self._out(out, (B, self.seq_len) + tuple(src.shape[1:]), src.dtype, dev, what)
         desc = SeqGatherDesc(int(src.shape[0]), src.numel() // src.shape[0] * src.element_size(), B, self.seq_len)
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             _lib.check(L.qt_seq_gather_rows(ctypes.byref(desc), _lib.ptr(src), _lib.ptr(starts), _lib.ptr(out),
                                             _lib.stream_ptr()), "qt_seq_gather_rows")
@@ -270,7 +240,7 @@ class SequenceWindows:
         B = int(starts.shape[0])
         out = self._out(out, (B, self.seq_len, F), torch.float32, dev, what)
         desc = SeqFeaturesDesc(int(raw.shape[0]), F, B, self.seq_len, _MODES[mode], K)
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             _lib.check(L.qt_seq_gather_features(ctypes.byref(desc), _lib.ptr(raw), _lib.ptr(starts), _lib.ptr(labels),
                                                 _lib.ptr(means if need_means else None), _lib.ptr(stds if need_stds else None),

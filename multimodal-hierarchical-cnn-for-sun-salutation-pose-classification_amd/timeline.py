@@ -30,6 +30,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._abi import TimelineDesc, bind  # noqa: F401  (<module>.bind is _abi.bind)
 from ._lib import QtError
 
 MAX_CLASSES = 64            # QT_TIMELINE_MAX_CLASSES
@@ -40,25 +41,6 @@ STATE = 8                   # QT_TIMELINE_STATE
 MAX_FRAMES = 1 << 22
 CONF_ONE = 65536            # q(1.0): seg_conf_sum counts confidences in units of 1 / 65536
 STATE_FIELDS = ("frames_seen", "stable_plus_1", "cand_plus_1", "run", "seg_start", "seg_len", "seg_conf_sum", "segments_total")
-
-
-class TimelineDesc(ctypes.Structure):   # qt_timeline_desc
-    _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_classes", ctypes.c_int), ("window", ctypes.c_int),
-                ("min_run", ctypes.c_int), ("min_confidence", ctypes.c_float), ("capacity", ctypes.c_int), ("flush", ctypes.c_int)]
-
-
-def bind(L):
-    """argtypes of the two entry points (idempotent)"""
-    if getattr(L, "_timeline_bound", False):
-        return L
-    L.qt_timeline_smooth.argtypes = [ctypes.POINTER(TimelineDesc), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.qt_timeline_smooth.restype = ctypes.c_int
-    L.qt_timeline_decode.argtypes = [ctypes.POINTER(TimelineDesc)] + [ctypes.c_void_p] * 6
-    L.qt_timeline_decode.restype = ctypes.c_int
-    L._timeline_bound = True
-    return L
 
 
 def _int_in(name, v, lo, hi=None):
@@ -148,7 +130,7 @@ class PoseTimeline:
         else:
             hist = (None, None, None, None)
         desc = self._desc(T, False)
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(dev):
             _lib.check(L.qt_timeline_smooth(ctypes.byref(desc), _lib.ptr(probs), probs.stride(1), *(_lib.ptr(t) for t in hist),
                                             _lib.ptr(rows), C, _lib.ptr(pred), _lib.ptr(conf), _lib.stream_ptr()),
@@ -162,7 +144,7 @@ class PoseTimeline:
     def finish(self):
         """end of the video: close every stream's open segment (one launch, nothing read back; calling it twice adds nothing)"""
         desc = self._desc(0, True)
-        L = bind(_lib.lib())
+        L = _lib.lib()
         with torch.cuda.device(self.device):
             _lib.check(L.qt_timeline_decode(ctypes.byref(desc), None, None, _lib.ptr(self.state), None, _lib.ptr(self.records),
                                             _lib.stream_ptr()), "qt_timeline_decode")

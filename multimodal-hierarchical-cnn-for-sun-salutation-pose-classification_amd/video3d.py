@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._abi import BnEvalItem as _BnEvalItem, GemmSmallDesc as _GemmDesc
 from . import modules as M
 from . import optim as _optim
 from ._lib import QtError
@@ -34,20 +35,6 @@ from .engine import default_compute_dtype
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 _c = ctypes
-
-
-class _GemmDesc(ctypes.Structure):   # qt_gemm_small_desc
-    _fields_ = [("M", _c.c_int), ("N", _c.c_int), ("K", _c.c_int),
-                ("a_dtype", _c.c_int), ("b_dtype", _c.c_int), ("c_dtype", _c.c_int),
-                ("a_row_stride", _c.c_longlong), ("a_k_stride", _c.c_longlong),
-                ("b_row_stride", _c.c_longlong), ("b_k_stride", _c.c_longlong),
-                ("c_row_stride", _c.c_longlong), ("relu", _c.c_int), ("accumulate", _c.c_int)]
-
-
-class _BnEvalItem(ctypes.Structure):   # qt_bn_eval_item
-    _fields_ = [("gamma", _c.c_void_p), ("beta", _c.c_void_p), ("running_mean", _c.c_void_p), ("running_var", _c.c_void_p),
-                ("scale", _c.c_void_p), ("shift", _c.c_void_p), ("C", _c.c_int), ("mean", _c.c_void_p),
-                ("invstd", _c.c_void_p)]
 
 
 def _ptr(t, byte_offset=0):
@@ -58,14 +45,7 @@ class _Ops:
     """ctypes view of the C ABI used by the clip models; every call checks its status."""
 
     def __init__(self):
-        self.L = L = _lib.lib()
-        # every return type that is not ctypes' default int (a byte count would be cut to 32 bits) and every 64-bit argument
-        # of a function called with plain Python ints: declared here, once, for all call sites
-        for fn in (L.qt_conv2d_wgrad_workspace_bytes, L.qt_conv3d_c32_dgrad_scratch_bytes, L.qt_conv3d_c32_wgrad_workspace_bytes,
-                   L.qt_conv3d_first_wgrad_workspace_bytes):
-            fn.restype = _c.c_size_t
-        L.qt_bn_stats_rows.argtypes = [_c.c_longlong, _c.c_int]
-        L.qt_bn_bwd_partial_rows.argtypes = [_c.c_longlong, _c.c_int]
+        self.L = _lib.lib()
         self._wgrad_ws = None
         self.timed = None   # list while bench.py profiles: (start event, end event, algorithmic flops, bytes, mode) per conv launch
 
@@ -111,15 +91,15 @@ class _Ops:
         if nbytes > 0:
             if self._wgrad_ws is None or self._wgrad_ws.numel() < nbytes or self._wgrad_ws.device != dw.device:
                 self._wgrad_ws = torch.empty(nbytes, dtype=torch.uint8, device=dw.device)
-            self.check(self.L.qt_conv2d_wgrad_ws(_c.byref(d), dy, x, _ptr(dw), _ptr(self._wgrad_ws), _c.c_size_t(nbytes),
+            self.check(self.L.qt_conv2d_wgrad_ws(_c.byref(d), dy, x, _ptr(dw), _ptr(self._wgrad_ws), nbytes,
                                                  _lib.stream_ptr()), "qt_conv2d_wgrad_ws")
         else:
             self.check(self.L.qt_conv2d_wgrad(_c.byref(d), dy, x, _ptr(dw), _lib.stream_ptr()), "qt_conv2d_wgrad")
 
     def bn_finalize(self, part, prow, Mrows, C, gamma, beta, rmean, rvar, nbt, dev):
         out = torch.empty(4, C, dtype=torch.float32, device=dev)   # mean, invstd, scale, shift
-        self.check(self.L.qt_bn_finalize(_ptr(part), prow, C, _c.c_longlong(Mrows), _ptr(gamma), _ptr(beta), _ptr(rmean),
-                                         _ptr(rvar), _ptr(nbt), _c.c_float(BN_MOMENTUM), _c.c_float(BN_EPS),
+        self.check(self.L.qt_bn_finalize(_ptr(part), prow, C, Mrows, _ptr(gamma), _ptr(beta), _ptr(rmean),
+                                         _ptr(rvar), _ptr(nbt), BN_MOMENTUM, BN_EPS,
                                          _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _lib.stream_ptr()),
                    "qt_bn_finalize")
         return out
@@ -134,9 +114,9 @@ class _Ops:
 
     # ---- BatchNorm / activation / pooling -------------------------------------------------------------------
     def bn_train(self, dt, y, Mrows, C, gamma, beta, rmean, rvar, nbt, dev):
-        rows = self.L.qt_bn_stats_rows(_c.c_longlong(Mrows), C)
+        rows = self.L.qt_bn_stats_rows(Mrows, C)
         part = torch.empty(self.L.qt_stats_capacity_rows(rows), 2, C, dtype=torch.float32, device=dev)
-        self.check(self.L.qt_bn_stats(_lib.qt_dtype(dt), _ptr(y), _c.c_longlong(Mrows), C, _ptr(part), _lib.stream_ptr()),
+        self.check(self.L.qt_bn_stats(_lib.qt_dtype(dt), _ptr(y), Mrows, C, _ptr(part), _lib.stream_ptr()),
                    "qt_bn_stats")
         return self.bn_finalize(part, rows, Mrows, C, gamma, beta, rmean, rvar, nbt, dev)
 
@@ -144,31 +124,31 @@ class _Ops:
         out = torch.empty(4, C, dtype=torch.float32, device=dev)   # running mean, 1/sqrt(running var + eps), scale, shift
         item = _BnEvalItem(_ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar), _ptr(out[2]), _ptr(out[3]), C, _ptr(out[0]),
                            _ptr(out[1]))
-        self.check(self.L.qt_bn_eval_affine_batched(_c.byref(item), 1, _c.c_float(BN_EPS), _lib.stream_ptr()),
+        self.check(self.L.qt_bn_eval_affine_batched(_c.byref(item), 1, BN_EPS, _lib.stream_ptr()),
                    "qt_bn_eval_affine_batched")
         return out
 
     def bn_act(self, dt, y, stats, out, Mrows, C):
         self.check(self.L.qt_bn_act(_lib.qt_dtype(dt), _ptr(y), _ptr(stats[2]), _ptr(stats[3]), None, None, None, 1, _ptr(out),
-                                    _c.c_longlong(Mrows), C, _lib.stream_ptr()), "qt_bn_act")
+                                    Mrows, C, _lib.stream_ptr()), "qt_bn_act")
 
     def bn_backward(self, dt, g, act, y, stats, gamma, Mrows, C, dev, batch_stats):
         """g = d/d(relu(bn(y))) -> (dy, dgamma, dbeta); `act` is the ReLU output (its mask)."""
         coef, dgamma, dbeta = self._bn_bwd_coef(dt, g, act, y, stats, gamma, Mrows, Mrows, C, dev, batch_stats)
         dy = torch.empty_like(y)
         self.check(self.L.qt_bn_bwd_apply(_lib.qt_dtype(dt), _ptr(g), _ptr(act), _ptr(y), _ptr(stats[0]), _ptr(stats[1]), _ptr(coef),
-                                          _ptr(dy), None, _c.c_longlong(Mrows), C, _lib.stream_ptr()), "qt_bn_bwd_apply")
+                                          _ptr(dy), None, Mrows, C, _lib.stream_ptr()), "qt_bn_bwd_apply")
         return dy, dgamma, dbeta
 
     def _bn_bwd_coef(self, dt, g, mask, y, stats, gamma, n, Mrows, C, dev, batch_stats):
         """the BatchNorm backward's sums over the n rows of g -> (coefficients [3][C], dgamma, dbeta); Mrows: the batch's count"""
-        rows = self.L.qt_bn_bwd_partial_rows(_c.c_longlong(n), C)
+        rows = self.L.qt_bn_bwd_partial_rows(n, C)
         part = torch.empty(self.L.qt_stats_capacity_rows(rows), 2, C, dtype=torch.float32, device=dev)
         self.check(self.L.qt_bn_bwd_reduce(_lib.qt_dtype(dt), _ptr(g), _ptr(mask), _ptr(y), _ptr(stats[0]), _ptr(stats[1]), _ptr(part),
-                                           _c.c_longlong(n), C, _lib.stream_ptr()), "qt_bn_bwd_reduce")
+                                           n, C, _lib.stream_ptr()), "qt_bn_bwd_reduce")
         dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
         coef = torch.empty(3, C, dtype=torch.float32, device=dev)
-        self.check(self.L.qt_bn_bwd_finalize(_ptr(part), rows, C, _c.c_longlong(Mrows if batch_stats else 0), _ptr(gamma),
+        self.check(self.L.qt_bn_bwd_finalize(_ptr(part), rows, C, (Mrows if batch_stats else 0), _ptr(gamma),
                                              _ptr(stats[1]), _ptr(dgb[0]), _ptr(dgb[1]), 0, _ptr(coef), _lib.stream_ptr()),
                    "qt_bn_bwd_finalize")
         return coef, dgb[0], dgb[1]
@@ -194,7 +174,7 @@ class _Ops:
 
     def conv3d_c32_dgrad(self, dt, dy, wd, dx, dxc, scr, nscr, B, T, H, W, flops=0.0, nbytes=0.0):
         with self._timed(_lib.QT_CONV_DGRAD, flops, nbytes):
-            self.check(self.L.qt_conv3d_c32_dgrad(_lib.qt_dtype(dt), _ptr(dy), _ptr(wd), _ptr(dx), dxc, _ptr(scr), _c.c_size_t(nscr), B,
+            self.check(self.L.qt_conv3d_c32_dgrad(_lib.qt_dtype(dt), _ptr(dy), _ptr(wd), _ptr(dx), dxc, _ptr(scr), nscr, B,
                                                   T, H, W, _lib.stream_ptr()), "qt_conv3d_c32_dgrad")
 
     def pool(self, dt, x, out, arg, T, B, H, W, C, pt):
@@ -240,7 +220,7 @@ class _Ops:
                                             _lib.stream_ptr()), "qt_pool3d_max_bwd")
 
     def col_sum(self, dt, x, rows, cols, ld, out):
-        self.check(self.L.qt_col_sum(_lib.qt_dtype(dt), _ptr(x), _c.c_longlong(rows), cols, ld, _ptr(out), 0, _lib.stream_ptr()),
+        self.check(self.L.qt_col_sum(_lib.qt_dtype(dt), _ptr(x), rows, cols, ld, _ptr(out), 0, _lib.stream_ptr()),
                    "qt_col_sum")
 
     # ---- thin dense products (f32) --------------------------------------------------------------------------
@@ -250,8 +230,8 @@ class _Ops:
                                         _lib.stream_ptr()), "qt_gemm_small")
 
     def dropout(self, x, rows, cols, ld, off, seed, p):
-        self.check(self.L.qt_dropout(_lib.QT_F32, _ptr(x, off * 4), _c.c_longlong(rows), cols, ld, _c.c_ulonglong(seed),
-                                     _c.c_float(p), _lib.stream_ptr()), "qt_dropout")
+        self.check(self.L.qt_dropout(_lib.QT_F32, _ptr(x, off * 4), rows, cols, ld, seed,
+                                     p, _lib.stream_ptr()), "qt_dropout")
 
 
 # QTCNN_POOL3D_FUSED (default 1): conv blocks with a pool run BatchNorm3d + ReLU + MaxPool3d as one pass forward and one
@@ -580,7 +560,7 @@ class _ConvBlock:
         T, B, H, W = s.shape
         # conv3d_block1 from the clip: dy in 32-channel rows for the raw weight-gradient kernel, or formed inside it
         # (fused_dy: pool_bn_backward returns the coefficients in dy's place); a width that kernel does not take: packed rows
-        raw_ws = int(o.L.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W)) if r.kernel == RAW else 0
+        raw_ws = o.L.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W) if r.kernel == RAW else 0
         fused_dy = bool(FIRST_WGRAD_FUSED and raw_ws and self.pool_t == 1 and dt == torch.bfloat16 and dout.data_ptr() % 16 == 0)
         cd = (32 if raw_ws else self.cout_p) if r.kernel == RAW else None
         dy, dgamma, dbeta = self._bn_pool_backward(dt, dout, s, cd, not fused_dy)
@@ -628,18 +608,18 @@ class _ConvBlock:
         T, B, H, W = s.shape
         q, st = _lib.qt_dtype(dt), _lib.stream_ptr()
         dW = torch.empty_like(self.conv.weight)
-        nws = raw_ws or (int(o.L.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W)) if slab and x.data_ptr() % 16 == 0 else 0)
+        nws = raw_ws or (o.L.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W) if slab and x.data_ptr() % 16 == 0 else 0)
         if nws:
             ws = torch.empty(nws, dtype=torch.uint8, device=dev)
             if coef is not None:   # dy = the pool / ReLU / BatchNorm3d backward of dout, formed inside the kernel
                 o.check(o.L.qt_conv3d_first_wgrad_fused(q, _ptr(x), _ptr(s.y), _ptr(dout), _ptr(s.arg), dout.shape[1], _ptr(s.stats[0]),
                                                         _ptr(s.stats[1]), _ptr(s.stats[2]), _ptr(s.stats[3]), _ptr(coef), _ptr(dW),
-                                                        _ptr(ws), _c.c_size_t(nws), B, T, H, W, st), "qt_conv3d_first_wgrad_fused")
+                                                        _ptr(ws), nws, B, T, H, W, st), "qt_conv3d_first_wgrad_fused")
             elif raw_ws:
-                o.check(o.L.qt_conv3d_first_wgrad(q, _ptr(x), _ptr(dy), _ptr(dW), _ptr(ws), _c.c_size_t(nws), B, T, H, W, st),
+                o.check(o.L.qt_conv3d_first_wgrad(q, _ptr(x), _ptr(dy), _ptr(dW), _ptr(ws), nws, B, T, H, W, st),
                         "qt_conv3d_first_wgrad")
             else:   # conv3d_block2: weight gradient on the slab-resident kernel (csrc/conv3d_slab.hip)
-                o.check(o.L.qt_conv3d_c32_wgrad(q, _ptr(x), x.shape[1], _ptr(dy), _ptr(dW), _ptr(ws), _c.c_size_t(nws), B, T, H, W, st),
+                o.check(o.L.qt_conv3d_c32_wgrad(q, _ptr(x), x.shape[1], _ptr(dy), _ptr(dW), _ptr(ws), nws, B, T, H, W, st),
                         "qt_conv3d_c32_wgrad")
             return dW
         if self.first:
@@ -684,7 +664,7 @@ class _ConvBlock:
         rows, esz = T * B * H * W, 2 if dt == torch.bfloat16 else 4
         fl = 2.0 * rows * 27 * self.cin * self.cout
         dx = torch.empty(rows, s.x.shape[1], dtype=dt, device=dev)   # (rows as wide as the input's: the previous block's pooled map)
-        nscr = int(o.L.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W)) if slab else 0
+        nscr = o.L.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W) if slab else 0
         if nscr:
             scr = torch.empty(nscr, dtype=torch.uint8, device=dev)
             o.conv3d_c32_dgrad(dt, dy, self.wd, dx, dx.shape[1], scr, nscr, B, T, H, W, flops=fl,
@@ -757,8 +737,8 @@ class _Lstm:
                 o.gemm(B * T, I, 4 * H, dgates, 4 * H, 1, w_ih, 1, I, dx, I)      # dgates W_ih
                 pk = self.saved[k - 1][5]
                 if pk > 0:   # through the inter-layer dropout: from the dropped activations themselves
-                    o.check(o.L.qt_scale_by_nonzero(_ptr(dx), _ptr(self.saved[k - 1][4]), _c.c_longlong(B * T * I),
-                                                    _c.c_float(1.0 / (1.0 - pk)), _lib.stream_ptr()), "qt_scale_by_nonzero")
+                    o.check(o.L.qt_scale_by_nonzero(_ptr(dx), _ptr(self.saved[k - 1][4]), B * T * I,
+                                                    1.0 / (1.0 - pk), _lib.stream_ptr()), "qt_scale_by_nonzero")
                 dh_all = dx
         return grads
 
@@ -998,7 +978,7 @@ class _Head:
     def relu_dropout_bwd(g, act, n, mul=1.0):
         """g = act > 0 ? g * mul : 0 (ReLU followed by dropout: `act` is the dropped output, mul = 1/(1-p))"""
         o = ops()
-        o.check(o.L.qt_relu_mask_scale(_lib.QT_F32, _ptr(g), _ptr(act), _c.c_longlong(n), _c.c_float(mul), _lib.stream_ptr()),
+        o.check(o.L.qt_relu_mask_scale(_lib.QT_F32, _ptr(g), _ptr(act), n, mul, _lib.stream_ptr()),
                 "qt_relu_mask_scale")
 
 

@@ -37,14 +37,9 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("ab_rowgroup_bytes.py compares on the GPU; there is none")
     dev = torch.device("cuda:0")
+    abi = importlib.import_module(f"{PKG}._abi")
     mods = {n: importlib.import_module(f"{PKG}.{n}") for n in ("loss", "metrics", "scores", "timeline", "segments")}
-    libs = []
-    for path in (args.a, args.b):
-        L = ctypes.CDLL(path)
-        for m in mods.values():
-            m.bind(L)
-        L.qt_last_error.restype = ctypes.c_char_p
-        libs.append(L)
+    libs = [abi.bind(ctypes.CDLL(path)) for path in (args.a, args.b)]
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def ptr(t):

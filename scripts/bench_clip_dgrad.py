@@ -2,7 +2,7 @@
 224 x 224 (bf16 dy) beside a device-to-device copy of the same bytes (the HBM floor of this box), and what d(loss)/d(clip) adds
 to a bf16 Quadtree3DCNN forward + backward at that size.
     python scripts/bench_clip_dgrad.py [--iters N] [--clips B]"""
-import argparse, ctypes, json, os, sys, torch
+import argparse, json, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from _util import pkg
@@ -25,8 +25,6 @@ def timed(fn, iters, warm=3):
 
 
 out = {"clips": B, "frames": T, "hw": HW}
-lib.qt_conv3d_first_dgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
 w = torch.randn(32, 3, 3, 3, 3, device=dev) * 0.15
 dy = torch.randn(T, B, HW, HW, 32, device=dev).to(torch.bfloat16)
 dx = torch.empty(B, T, 3, HW, HW, device=dev)

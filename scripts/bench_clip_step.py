@@ -6,7 +6,7 @@ cross-entropy, backward, optimizer step), and the norm kernel (qt_grad_norm_mult
 Three models on one GPU, random data, rounds interleaved a, b, c, a, b, c, ...: drift hits all three alike.  Per variant
 the median over the rounds and their spread (max - min); (b) is "not slower" if it is within (a)'s spread.
     python scripts/bench_clip_step.py [--iters N] [--rounds R]"""
-import argparse, ctypes, json, os, statistics, sys, torch
+import argparse, json, os, statistics, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.setdefault("QTCNN_RESNET18_WEIGHTS", "none")
@@ -17,7 +17,6 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--batch", type=int, default=256)
 args = ap.parse_args()
 L = pkg("_lib"); lib = L.lib(); eng = pkg("engine"); synth = pkg("synth"); P = pkg()
-eng._bind_api(lib)
 dev = torch.device("cuda:0"); B = args.batch
 HBM_PEAK = 8.0e12   # MI355X HBM3E, bytes/s
 

@@ -15,7 +15,6 @@ Window T = 16, hidden 256, bf16 build, synthetic weights and frames, timed with 
 
 Prints one JSON line.  No threshold rests on it."""
 import argparse
-import ctypes
 import importlib
 import json
 import os
@@ -44,8 +43,7 @@ def main():
     P = importlib.import_module(PKG)
     synth = importlib.import_module(PKG + ".synth")
     Lm = importlib.import_module(PKG + "._lib")
-    L = importlib.import_module(PKG + ".sequence_stream").bind(Lm.lib())
-    L.qt_lstm_forward.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
+    L = Lm.lib()
     dev = torch.device("cuda:0")
 
     def timed(fn, repeats, warmup=1):

@@ -36,11 +36,10 @@ def bench(kind, B, H, Cin, Cout, k, s, p, dt=torch.bfloat16, workspace=False):
         dw = torch.zeros(Cout, k * k, Cin, device=dev)
         fn = lambda: L.check(L.lib().qt_conv2d_wgrad(ctypes.byref(d), L.ptr(dy), L.ptr(x), L.ptr(dw), st))
         if workspace:
-            L.lib().qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
             nb = L.lib().qt_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
             wsb = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
             fn = lambda: L.check(L.lib().qt_conv2d_wgrad_ws(ctypes.byref(d), L.ptr(dy), L.ptr(x), L.ptr(dw), L.ptr(wsb),
-                                                          ctypes.c_size_t(nb), st))
+                                                          nb, st))
             kind = "wgradW"
     else:
         mode = L.QT_CONV_FWD if kind == "fwd" else L.QT_CONV_DGRAD

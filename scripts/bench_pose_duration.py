@@ -56,7 +56,7 @@ def main():
     import _pose_order_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
 
     def timed(variants):
@@ -99,10 +99,10 @@ def main():
         carry = torch.zeros(B, S + 2, dtype=torch.int64, device=dev)
         sink = torch.empty_like(probs)
         desc = M.PoseDurationDesc(B, T, C, S, D)
-        need = int(L.qt_pose_duration_workspace_bytes(ctypes.byref(desc)))
+        need = L.qt_pose_duration_workspace_bytes(ctypes.byref(desc))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         plain_desc = M.PoseOrderDesc(B, T, C, S)
-        plain_need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(plain_desc)))
+        plain_need = L.qt_pose_order_workspace_bytes(ctypes.byref(plain_desc))
         plain_ws = torch.empty(max(plain_need, 8), dtype=torch.uint8, device=dev)
 
         def duration():

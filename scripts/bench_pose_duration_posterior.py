@@ -58,7 +58,7 @@ def main():
     import _pose_order_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
 
     def timed(variants):
@@ -101,7 +101,7 @@ def main():
         counts = torch.zeros(S, D, dtype=torch.float64, device=dev)
         sink = torch.empty_like(probs)
         desc = M.PoseDurationDesc(B, T, C, S, D)
-        need = int(L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc)))
+        need = L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
 
         def call(p, c, b, e, n):

@@ -59,7 +59,7 @@ def main():
     import _pose_order_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
 
     def timed(variants):
@@ -104,8 +104,8 @@ def main():
         counts = f64(S, D)
         sink = torch.empty_like(probs)
         desc = M.PoseDurationDesc(B, T, C, S, D)
-        need = int(L.qt_pose_duration_prior_workspace_bytes(ctypes.byref(desc)))
-        assert need >= int(L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc)))
+        need = L.qt_pose_duration_prior_workspace_bytes(ctypes.byref(desc))
+        assert need >= L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
 
         def expect(frames_desc=desc, p=probs, ln=d_len):

@@ -56,7 +56,7 @@ def main():
     import _pose_lag_ref as G
     import _pose_order_ref as O
     M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
     os.environ.pop(SWITCH, None)
 
@@ -171,7 +171,7 @@ def main():
         carry = torch.zeros(B, S + 2, dtype=torch.float64, device=dev)
         post, filt = (torch.empty(B, T, S, dtype=torch.float32, device=dev) for _ in range(2))
         cls, ev = torch.empty(B, T, C, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float64, device=dev)
-        need = int(L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc)))
+        need = L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc))
         ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
 
         def posterior():
@@ -183,7 +183,7 @@ def main():
         d_carry = torch.zeros(B, S + 2, dtype=torch.int64, device=dev)
         path, d_filt = (torch.empty(B, T, dtype=torch.int64, device=dev) for _ in range(2))
         emis = torch.empty(B, T, S, dtype=torch.int32, device=dev)
-        d_need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(desc)))
+        d_need = L.qt_pose_order_workspace_bytes(ctypes.byref(desc))
         d_ws = torch.empty(max(d_need, 8), dtype=torch.uint8, device=dev)
 
         def order_decode():

@@ -60,7 +60,7 @@ def main():
     import _pose_order_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
     os.environ.pop(SWITCH, None)
 
@@ -102,7 +102,7 @@ def main():
         emis = torch.empty(B, T, S, dtype=torch.int32, device=dev)
         sink = torch.empty_like(probs)
         desc = M.PoseOrderDesc(B, T, C, S)
-        need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(desc)))
+        need = L.qt_pose_order_workspace_bytes(ctypes.byref(desc))
         ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
 
         def decode(form=None):

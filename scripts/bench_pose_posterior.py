@@ -57,7 +57,7 @@ def main():
     import _pose_posterior_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
     os.environ.pop(SWITCH, None)
 
@@ -102,7 +102,7 @@ def main():
         ev = torch.empty(B, dtype=torch.float64, device=dev)
         sink = torch.empty_like(probs)
         desc = M.PoseOrderDesc(B, T, C, S)
-        need = int(L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc)))
+        need = L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc))
         ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
 
         def posterior(one_wave=False):
@@ -120,7 +120,7 @@ def main():
         path = torch.empty(B, T, dtype=torch.int64, device=dev)
         d_filt = torch.empty(B, T, dtype=torch.int64, device=dev)
         emis = torch.empty(B, T, S, dtype=torch.int32, device=dev)
-        d_need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(desc)))
+        d_need = L.qt_pose_order_workspace_bytes(ctypes.byref(desc))
         d_ws = torch.empty(max(d_need, 8), dtype=torch.uint8, device=dev)
 
         def decode():

@@ -54,7 +54,7 @@ def main():
     import _pose_prior_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".pose_order"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
 
     def timed(variants):
@@ -89,7 +89,7 @@ def main():
         start = torch.zeros(S, dtype=torch.float64, device=dev)
         totals = torch.zeros(2, dtype=torch.float64, device=dev)
         desc = M.PoseOrderDesc(B, T, C, S)
-        need = int(L.qt_pose_prior_workspace_bytes(ctypes.byref(desc)))
+        need = L.qt_pose_prior_workspace_bytes(ctypes.byref(desc))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
 
         def expect():
@@ -98,7 +98,7 @@ def main():
 
         carry = torch.zeros(B, S + 2, dtype=torch.float64, device=dev)
         post = torch.empty(B, T, S, dtype=torch.float32, device=dev)
-        p_need = int(L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc)))
+        p_need = L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc))
         p_ws = torch.empty(max(p_need, 8), dtype=torch.uint8, device=dev)
 
         def posterior():

@@ -55,7 +55,7 @@ def main():
     hist = seq.history(B, dev)
     out = seq.from_landmarks(lm, det)
     lm_sink, out_sink = torch.empty_like(lm), torch.empty_like(out)
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     desc = M.PoseSeqDesc(B, T, 640, 480, M.QT_POSE_ZERO)
 
     def kernel():

@@ -73,7 +73,7 @@ def main():
     import _segments_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".segments"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
 
     pred_np, label_np = R.make_batch(11, VIDEOS, FRAMES, C, mean_run=24, flicker=0.02, unknown=0.01)

@@ -113,7 +113,7 @@ def main():
     # the three launches alone: qt_seq_windows_plan through ctypes into preallocated buffers
     import ctypes
     M, Lm = importlib.import_module(PKG + ".sequence_windows"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     capacity = M.candidate_count(lengths, 4, 2)
     offsets = torch.tensor([0] + lengths, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
     starts, window_labels = torch.empty(capacity, dtype=torch.int32, device=dev), torch.empty(capacity, dtype=torch.int64, device=dev)

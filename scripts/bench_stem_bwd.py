@@ -15,11 +15,10 @@ am = torch.randint(0, 9, (B, 56, 56, 64), dtype=torch.uint8, device=dev)
 v = [torch.rand(64, device=dev) + 0.5 for _ in range(4)]
 coef = torch.rand(3, 64, device=dev)
 dw = torch.zeros(64, 7, 32, device=dev)
-lib.qt_stem_bn_bwd_wgrad_workspace_bytes.restype = ctypes.c_size_t
 nws = lib.qt_stem_bn_bwd_wgrad_workspace_bytes(B)
 ws = torch.empty(nws // 4, device=dev)
 fn = lambda: L.check(lib.qt_stem_bn_bwd_wgrad_ws(qdt, L.ptr(dp), L.ptr(am), L.ptr(y), L.ptr(v[0]), L.ptr(v[1]), L.ptr(v[2]), L.ptr(v[3]),
-                                                 L.ptr(coef), L.ptr(xpad), L.ptr(dw), L.ptr(ws), ctypes.c_size_t(nws), B, st), "fused")
+                                                 L.ptr(coef), L.ptr(xpad), L.ptr(dw), L.ptr(ws), nws, B, st), "fused")
 for _ in range(3): fn()
 torch.cuda.synchronize()
 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

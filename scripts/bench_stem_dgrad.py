@@ -1,7 +1,7 @@
 """Developer aid: conv1's data gradient down to the image (qt_stem_dgrad) alone at B = 256, and what d(loss)/d(image) adds
 to a B = 256 bf16 QuadtreeCNN train step (forward + backward, no optimizer) with a trainable and with a frozen backbone.
     python scripts/bench_stem_dgrad.py [--iters N]"""
-import argparse, ctypes, json, os, sys, torch
+import argparse, json, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.setdefault("QTCNN_RESNET18_WEIGHTS", "none")
@@ -25,7 +25,6 @@ def timed(fn, iters, warm=3):
 
 
 out = {}
-lib.qt_stem_dgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
 w = torch.randn(64, 3, 7, 7, device=dev) * 0.05
 dx = torch.empty(B, 3, 224, 224, device=dev)
 for dt in (torch.bfloat16, torch.float32):

@@ -51,7 +51,7 @@ def main():
     import _timeline_ref as R
     P = importlib.import_module(PKG)
     M, Lm = importlib.import_module(PKG + ".timeline"), importlib.import_module(PKG + "._lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     dev = torch.device("cuda:0")
 
     def timed(variants, iters):

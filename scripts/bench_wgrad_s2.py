@@ -17,7 +17,6 @@ lib = L.lib()
 dev = torch.device("cuda:0")
 dt = torch.bfloat16
 B = int(os.environ.get("B", "256"))
-lib.qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
 
 
 def timed(fn, n=20):
@@ -51,7 +50,7 @@ for Cin, Cout, H, k in ((64, 128, 56, 3), (128, 256, 28, 3), (256, 512, 14, 3), 
         if nbytes:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             fn = lambda: L.check(lib.qt_conv2d_wgrad_oihw(ctypes.byref(d), L.ptr(dy), L.ptr(x), L.ptr(g), L.ptr(ws),
-                                                          ctypes.c_size_t(nbytes), L.stream_ptr()), "wgrad_oihw")
+                                                          nbytes, L.stream_ptr()), "wgrad_oihw")
         else:
             dw = torch.empty(Cout, k * k, Cin, dtype=torch.float32, device=dev)
 

@@ -43,7 +43,6 @@ END = "the end of the workspace"
 # ---- the region table ---------------------------------------------------------------------------------------------------
 def bound_lib():
     L = pkg("_lib").lib()
-    pkg("engine")._bind_api(L)
     return L
 
 

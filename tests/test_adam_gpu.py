@@ -38,21 +38,13 @@ def _dev():
     return torch.device("cuda:0")
 
 
-class _PackItem(ctypes.Structure):   # qt_pack_item
-    _fields_ = [("w", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgrad", ctypes.c_void_p),
-                ("O", ctypes.c_int), ("I", ctypes.c_int), ("k", ctypes.c_int), ("s2", ctypes.c_int)]
+_PackItem = pkg("_abi").PackItem   # qt_pack_item
 
 
 def _api():
     L = pkg("_lib")
     lib = L.lib()
     eng = pkg("engine")
-    eng._bind_api(lib)
-    lib.qt_pack_weights_batched.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.qt_adam_pack_weights_batched.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_int, ctypes.c_void_p]
-    lib.qt_adam_pack_weights_batched_scaled.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     return L, lib, eng
 
 

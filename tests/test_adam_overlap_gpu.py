@@ -218,9 +218,7 @@ def test_eligibility_predicate(monkeypatch):
     torch.cuda.synchronize()
 
 
-class _PackItem(ctypes.Structure):   # qt_pack_item
-    _fields_ = [("w", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgrad", ctypes.c_void_p),
-                ("O", ctypes.c_int), ("I", ctypes.c_int), ("k", ctypes.c_int), ("s2", ctypes.c_int)]
+_PackItem = pkg("_abi").PackItem   # qt_pack_item
 
 
 @gpu
@@ -237,10 +235,6 @@ def test_fused_adam_pack_equals_plain_adam_then_pack(dt):
     shapes = [(64, 64, 3, 0), (128, 192, 1, 0), (128, 64, 3, 1), (128, 64, 1, 1), (128, 64, 3, 2), (256, 128, 3, 3),
               (256, 128, 1, 4)]
     qdt, st = L.qt_dtype(dt), L.stream_ptr()
-    lib.qt_pack_weights_batched.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.qt_adam_pack_weights_batched.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_int, ctypes.c_void_p]
-    lib.qt_adam_multi.argtypes = [ctypes.POINTER(eng.AdamItem), ctypes.c_int, ctypes.POINTER(eng.AdamDesc), ctypes.c_void_p]
 
     def side(fused):
         n = len(shapes)

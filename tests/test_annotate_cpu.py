@@ -61,8 +61,7 @@ def _desc(M, **kw):
 def test_host_side_argument_checks_need_no_device():
     """every refusal below comes before the first device call: the pointers are never dereferenced"""
     M = pkg("annotate")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     fr, lm, det, seg, pr, cf, at, wd, out = (0x100000 * k for k in range(1, 10))
 
     def call(desc, frames=fr, landmarks=lm, detected=None, segments=seg, pred=pr, confidence=cf, atlas=at, widths=wd, dst=out):

@@ -69,7 +69,7 @@ def run(dev, case, out_fill=0xFF, in_place=False, off_out=0, off_src=0, n_segmen
     """qt_annotate_u8 through ctypes, every operand between guard bands: out (or the frames drawn on in place) must keep
     its bands, every input its bytes.  Returns out as numpy."""
     M, Lm = pkg("annotate"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     G = Guard(dev)
     frames = torch.tensor(case["frames"])            # (a copy: the shared arrays are read-only)
     B, H, W, _ = frames.shape

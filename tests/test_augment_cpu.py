@@ -214,7 +214,7 @@ def _desc(M, **kw):
 def test_descriptor_validation_needs_no_device():
     """every refusal comes with a message and before any HIP call: the pointers are never dereferenced"""
     M, Lm = pkg("augment"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     src, par, dst, ws = (ctypes.c_void_p(1 << 20), ctypes.c_void_p(2 << 20), ctypes.c_void_p(3 << 20), ctypes.c_void_p(4 << 20))
     need = L.qt_augment_workspace_bytes(2, 1)
     assert need == 2 * 16 * 4 and L.qt_augment_workspace_bytes(2, 0) == 0

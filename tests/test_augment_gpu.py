@@ -24,7 +24,7 @@ def run(dev, images, params, kx=1, ky=1, norm=R.NO_NORM, use_contrast=1, src_pad
     (and one poisoned image after the last).  spare_ws: a poisoned workspace handed over although use_contrast is 0.
     Returns the CPU result and the status."""
     M, Lm = pkg("augment"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     N, _, h, w = images.shape
     image = 3 * h * w
     src = torch.full((N, image + src_pad), POISON, device=dev)
@@ -32,7 +32,7 @@ def run(dev, images, params, kx=1, ky=1, norm=R.NO_NORM, use_contrast=1, src_pad
     src0 = src.clone()
     par = params.to(dev)
     dst = torch.full((N + 1, image + dst_pad), POISON, device=dev)
-    ws_bytes = int(L.qt_augment_workspace_bytes(N, use_contrast))
+    ws_bytes = L.qt_augment_workspace_bytes(N, use_contrast)
     ws = torch.full((ws_bytes // 4 + 4,), POISON, device=dev) if ws_bytes else spare_ws
     desc = M.AugmentDesc(N, h, w, image + src_pad, image + dst_pad, kx, ky, (ctypes.c_float * 3)(*norm[0]),
                          (ctypes.c_float * 3)(*norm[1]), use_contrast)
@@ -185,7 +185,7 @@ def test_without_contrast_one_kernel_is_launched():
     assert bool((spare == POISON).all())
     _within(got, ref, bound, "use_contrast = 0")
     M, Lm = pkg("augment"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     desc = M.AugmentDesc(3, 18, 70, 3 * 18 * 70, 3 * 18 * 70, 5, 9, (ctypes.c_float * 3)(0, 0, 0), (ctypes.c_float * 3)(1, 1, 1), 1)
     src, par, dst = img.to(dev), p.to(dev), torch.empty(3, 3, 18, 70, device=dev)
     Lm.check(L.qt_augment_f32(ctypes.byref(desc), src.data_ptr(), par.data_ptr(), dst.data_ptr(), spare.data_ptr(), 4 * 3 * R.PARTS,

@@ -134,8 +134,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(lib_path)
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, missing
-    lib.qt_version.restype = ctypes.c_int
-    assert lib.qt_version() >= 100
+    assert pkg("_abi").bind(lib).qt_version() >= 100
 
 
 def test_plan_tensor_table_matches_module_tree():
@@ -143,7 +142,6 @@ def test_plan_tensor_table_matches_module_tree():
     P = pkg()
     eng = pkg("engine")
     L = pkg("_lib").lib()
-    eng._bind_api(L)
     for kind, model in ((0, P.QuadtreeCNN(12)), (1, P.StandardResNetCNN(12)), (2, P.AttentionHierarchicalCNN(12)),
                         (3, P.CnnLstm(12))):
         desc = eng.PlanDesc(1, 8, 12, kind, 0, 47, 0.5, 1e-5, 0.1, 4, 256)
@@ -165,7 +163,6 @@ def test_plan_tensor_table_matches_module_tree():
         L.qt_plan_destroy(h)
     bad = eng.PlanDesc(5, 8, 12, 0, 0, 47, 0.5, 1e-5, 0.1)
     assert L.qt_plan_create(ctypes.byref(bad), ctypes.byref(h)) == -1
-    L.qt_last_error.restype = ctypes.c_char_p
     assert b"dtype" in L.qt_last_error()
 
 
@@ -176,7 +173,6 @@ def test_gradient_buckets_are_the_surveyed_sizes():
     P = pkg()
     eng = pkg("engine")
     L = pkg("_lib").lib()
-    eng._bind_api(L)
     model = P.QuadtreeCNN(12)
     desc = eng.PlanDesc(1, 8, 12, 0, 0, 47, 0.5, 1e-5, 0.1, 0, 0)
     h = ctypes.c_void_p()
@@ -204,7 +200,6 @@ def test_conv_descriptor_validation_needs_no_device():
     message and before any HIP call: runs on the CPU box, the pointers are never dereferenced."""
     Lm = pkg("_lib")
     L = Lm.lib()
-    L.qt_last_error.restype = ctypes.c_char_p
     d = Lm.ConvDesc()
     d.dtype, d.mode, d.batch = Lm.qt_dtype(torch.bfloat16), Lm.QT_CONV_FWD, 2
     d.in_h = d.in_w = d.out_h = d.out_w = 14

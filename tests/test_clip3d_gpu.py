@@ -110,7 +110,7 @@ def test_fused_bn_relu_maxpool3d_equals_separate_kernels(dt, pt, T, H):
 
     # separate kernels
     a = torch.empty_like(yd)
-    L.check(lib.qt_bn_act(q, L.ptr(yd), L.ptr(sc), L.ptr(sh), None, None, None, 1, L.ptr(a), ctypes.c_longlong(M), C, st), "act")
+    L.check(lib.qt_bn_act(q, L.ptr(yd), L.ptr(sc), L.ptr(sh), None, None, None, 1, L.ptr(a), M, C, st), "act")
     out0 = torch.empty(To, B, Ho, Wo, C, dtype=dt, device=dev)
     arg0 = torch.empty(To, B, Ho, Wo, C, dtype=torch.uint8, device=dev)
     L.check(lib.qt_pool3d_max(q, L.ptr(a), L.ptr(out0), L.ptr(arg0), T, B, H, W, C, pt, st), "pool")
@@ -132,25 +132,25 @@ def test_fused_bn_relu_maxpool3d_equals_separate_kernels(dt, pt, T, H):
     def finalize(part, rows):
         dgb = torch.empty(2, C, device=dev)
         coef = torch.empty(3, C, device=dev)
-        L.check(lib.qt_bn_bwd_finalize(L.ptr(part), rows, C, ctypes.c_longlong(M), L.ptr(gm), L.ptr(isd), L.ptr(dgb[0]), L.ptr(dgb[1]),
+        L.check(lib.qt_bn_bwd_finalize(L.ptr(part), rows, C, M, L.ptr(gm), L.ptr(isd), L.ptr(dgb[0]), L.ptr(dgb[1]),
                                        0, L.ptr(coef), st), "finalize")
         return dgb, coef
 
     # separate backward
     da = torch.empty_like(yd)
     L.check(lib.qt_pool3d_max_bwd(q, L.ptr(dd), L.ptr(arg0), L.ptr(da), T, B, H, W, C, pt, st), "pool bwd")
-    rows0 = lib.qt_bn_bwd_partial_rows(ctypes.c_longlong(M), C)
+    rows0 = lib.qt_bn_bwd_partial_rows(M, C)
     part0 = torch.empty(lib.qt_stats_capacity_rows(rows0), 2, C, device=dev)
-    L.check(lib.qt_bn_bwd_reduce(q, L.ptr(da), L.ptr(a), L.ptr(yd), L.ptr(mu), L.ptr(isd), L.ptr(part0), ctypes.c_longlong(M), C, st),
+    L.check(lib.qt_bn_bwd_reduce(q, L.ptr(da), L.ptr(a), L.ptr(yd), L.ptr(mu), L.ptr(isd), L.ptr(part0), M, C, st),
             "reduce")
     dgb0, coef0 = finalize(part0, rows0)
     dy0 = torch.empty_like(yd)
     L.check(lib.qt_bn_bwd_apply(q, L.ptr(da), L.ptr(a), L.ptr(yd), L.ptr(mu), L.ptr(isd), L.ptr(coef0), L.ptr(dy0), None,
-                                ctypes.c_longlong(M), C, st), "apply")
+                                M, C, st), "apply")
     # fused backward
-    rows1 = lib.qt_bn_bwd_partial_rows(ctypes.c_longlong(cells), C)
+    rows1 = lib.qt_bn_bwd_partial_rows(cells, C)
     part1 = torch.empty(lib.qt_stats_capacity_rows(rows1), 2, C, device=dev)
-    L.check(lib.qt_bn_bwd_reduce(q, L.ptr(dd), L.ptr(out1), L.ptr(ymax), L.ptr(mu), L.ptr(isd), L.ptr(part1), ctypes.c_longlong(cells),
+    L.check(lib.qt_bn_bwd_reduce(q, L.ptr(dd), L.ptr(out1), L.ptr(ymax), L.ptr(mu), L.ptr(isd), L.ptr(part1), cells,
                                  C, st), "reduce (pooled side)")
     dgb1, coef1 = finalize(part1, rows1)
     dy1 = torch.full_like(yd, 7.0)
@@ -168,11 +168,11 @@ def test_fused_bn_relu_maxpool3d_equals_separate_kernels(dt, pt, T, H):
     assert torch.equal(dy0, dy2)
 
     if dt == torch.bfloat16:   # the resident-grid form the large maps take (round 4): the same arithmetic, bit for bit
-        lib.qt_set_pool3d_apply_light_min(ctypes.c_longlong(1))
+        lib.qt_set_pool3d_apply_light_min(1)
         dy5 = torch.full_like(yd, 7.0)
         L.check(lib.qt_pool3d_bn_bwd_apply(q, L.ptr(dd), L.ptr(arg1), L.ptr(out1), L.ptr(yd), L.ptr(mu), L.ptr(isd), L.ptr(coef1),
                                            L.ptr(dy5), T, B, H, W, C, C, C, pt, st), "fused apply, resident grid")
-        lib.qt_set_pool3d_apply_light_min(ctypes.c_longlong(0))
+        lib.qt_set_pool3d_apply_light_min(0)
         torch.cuda.synchronize()
         assert torch.equal(dy1, dy5)
 
@@ -215,13 +215,12 @@ def test_bn_stats_pack_and_avgpool(dt):
     dev = _dev()
     L = pkg("_lib")
     lib = L.lib()
-    lib.qt_bn_stats_rows.argtypes = [ctypes.c_longlong, ctypes.c_int]
     g = torch.Generator().manual_seed(6)
     for M, C in ((70001, 64), (513, 1024), (255, 8)):
         y = torch.randn(M, C, generator=g).to(dt)
         rows = lib.qt_bn_stats_rows(M, C)
         part = torch.zeros(rows, 2, C, device=dev)
-        L.check(lib.qt_bn_stats(L.qt_dtype(dt), L.ptr(y.to(dev)), ctypes.c_longlong(M), C, L.ptr(part), L.stream_ptr()), "bn_stats")
+        L.check(lib.qt_bn_stats(L.qt_dtype(dt), L.ptr(y.to(dev)), M, C, L.ptr(part), L.stream_ptr()), "bn_stats")
         s = part.sum(0).cpu()
         yd = y.double()
         assert rel_err(s[0], yd.sum(0)) <= 1e-4 and rel_err(s[1], (yd * yd).sum(0)) <= 1e-5
@@ -306,8 +305,7 @@ def test_first_conv3d_from_the_f32_clip(cfg):
         torch.cuda.synchronize()
         assert torch.equal(pooled[..., :32], want) and (pooled[..., 32:] == 0).all()
     # weight gradient from the clip and a 32-channel-row gradient map, in nn.Conv3d's layout; deterministic
-    lib.qt_conv3d_first_wgrad_workspace_bytes.restype = ctypes.c_size_t
-    nws = int(lib.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W))
+    nws = lib.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W)
     assert (nws > 0) == (W % 32 == 0)
     if nws:
         dyt = torch.randn(T, B, H, W, 32, generator=g).to(dt)
@@ -319,7 +317,7 @@ def test_first_conv3d_from_the_f32_clip(cfg):
         outs = []
         for _ in range(2):
             dw = torch.full((32, 3, 3, 3, 3), float("nan"), device=dev)
-            L.check(lib.qt_conv3d_first_wgrad(L.qt_dtype(dt), L.ptr(cd), L.ptr(dyd), L.ptr(dw), L.ptr(ws), ctypes.c_size_t(nws), B, T, H,
+            L.check(lib.qt_conv3d_first_wgrad(L.qt_dtype(dt), L.ptr(cd), L.ptr(dyd), L.ptr(dw), L.ptr(ws), nws, B, T, H,
                                               W, L.stream_ptr()), "qt_conv3d_first_wgrad")
             torch.cuda.synchronize()
             outs.append(dw.cpu())
@@ -342,19 +340,19 @@ def test_first_conv3d_from_the_f32_clip(cfg):
                                                L.ptr(invstd), L.ptr(coef), L.ptr(dy), T, B, H, W, cp, 32, 32, 1, L.stream_ptr()),
                     "qt_pool3d_bn_bwd_apply")
             dw_ref = torch.full((32, 3, 3, 3, 3), float("nan"), device=dev)
-            L.check(lib.qt_conv3d_first_wgrad(L.qt_dtype(dt), L.ptr(cd), L.ptr(dy), L.ptr(dw_ref), L.ptr(ws), ctypes.c_size_t(nws), B, T,
+            L.check(lib.qt_conv3d_first_wgrad(L.qt_dtype(dt), L.ptr(cd), L.ptr(dy), L.ptr(dw_ref), L.ptr(ws), nws, B, T,
                                               H, W, L.stream_ptr()), "qt_conv3d_first_wgrad")
             dw_f = torch.full((32, 3, 3, 3, 3), float("nan"), device=dev)
             L.check(lib.qt_conv3d_first_wgrad_fused(L.qt_dtype(dt), L.ptr(cd), L.ptr(y), L.ptr(dout), L.ptr(arg), cp, L.ptr(mean),
                                                     L.ptr(invstd), L.ptr(sc), L.ptr(sh), L.ptr(coef), L.ptr(dw_f), L.ptr(ws),
-                                                    ctypes.c_size_t(nws), B, T, H, W, L.stream_ptr()), "qt_conv3d_first_wgrad_fused")
+                                                    nws, B, T, H, W, L.stream_ptr()), "qt_conv3d_first_wgrad_fused")
             torch.cuda.synchronize()
             assert torch.isfinite(dw_f).all()
             # (dy = ka g + kb - y kc in the fused form against a (g - b - (y - mean) invstd c): single bf16 roundings differ)
             assert rel_err(dw_f.cpu(), dw_ref.cpu()) <= 2e-3, (cp, rel_err(dw_f.cpu(), dw_ref.cpu()))
         assert lib.qt_conv3d_first_wgrad_fused(L.qt_dtype(dt), L.ptr(cd), L.ptr(y), L.ptr(dout), L.ptr(arg), 48, L.ptr(mean),
                                                L.ptr(invstd), L.ptr(sc), L.ptr(sh), L.ptr(coef), L.ptr(dw_f), L.ptr(ws),
-                                               ctypes.c_size_t(nws), B, T, H, W, L.stream_ptr()) == -1
+                                               nws, B, T, H, W, L.stream_ptr()) == -1
     # not covered: f32, a width that is not a multiple of 16, a height that is not a multiple of 4
     assert lib.qt_conv3d_first_fwd(L.QT_F32, L.ptr(cd), L.ptr(wp), L.ptr(y), None, None, 0, None, B, T, H, W, L.stream_ptr()) == -3
     assert lib.qt_conv3d_first_stats_rows(B, T, H, W + 8) == 0 and lib.qt_conv3d_first_stats_rows(B, T, H + 2, W) == 0
@@ -410,31 +408,29 @@ def test_second_conv3d_with_frame_slabs_in_lds(cfg):
     wdp = torch.full((64, 27, 64), 3.0, dtype=dt)                                     # rows 32..63 (padding input channels): garbage
     wdp[:32] = w.permute(1, 2, 3, 4, 0).reshape(32, 27, 64).to(dt)
     wdp = wdp.to(dev)
-    lib.qt_conv3d_c32_dgrad_scratch_bytes.restype = ctypes.c_size_t
-    nscr = int(lib.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W))
+    nscr = lib.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W)
     assert nscr == T * B * H * W * 32 * 4
     scr = torch.empty(nscr, dtype=torch.uint8, device=dev)
     dyd = dyt.to(dev)
     for dxc in (64, 32):   # rows padded to 64 channels (32..63 written as zeros), and 32-channel rows (round 4)
         dx = torch.full((T, B, H, W, dxc), float("nan"), dtype=dt, device=dev)
-        L.check(lib.qt_conv3d_c32_dgrad(L.qt_dtype(dt), L.ptr(dyd), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), ctypes.c_size_t(nscr), B, T,
+        L.check(lib.qt_conv3d_c32_dgrad(L.qt_dtype(dt), L.ptr(dyd), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), nscr, B, T,
                                         H, W, L.stream_ptr()), "qt_conv3d_c32_dgrad")
         torch.cuda.synchronize()
         assert rel_err(dx[..., :32].float().cpu(), xr.grad.permute(2, 0, 3, 4, 1)) <= 1e-2
         assert (dx[..., 32:] == 0).all()
-    assert lib.qt_conv3d_c32_dgrad(L.qt_dtype(dt), L.ptr(dyd), L.ptr(wdp), L.ptr(dx), 48, L.ptr(scr), ctypes.c_size_t(nscr), B, T, H, W,
+    assert lib.qt_conv3d_c32_dgrad(L.qt_dtype(dt), L.ptr(dyd), L.ptr(wdp), L.ptr(dx), 48, L.ptr(scr), nscr, B, T, H, W,
                                    L.stream_ptr()) == -1
     # the weight gradient: contraction over positions, nn.Conv3d's layout, deterministic
     wr = w.clone().requires_grad_(True)
     F.conv3d(x, wr, None, 1, 1).backward(dyt.float().permute(1, 4, 0, 2, 3))
-    lib.qt_conv3d_c32_wgrad_workspace_bytes.restype = ctypes.c_size_t
-    nws = int(lib.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W))
+    nws = lib.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W)
     assert nws > 0
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
     outs = []
     for _ in range(2):
         dwt = torch.full((64, 32, 3, 3, 3), float("nan"), device=dev)
-        L.check(lib.qt_conv3d_c32_wgrad(L.qt_dtype(dt), L.ptr(xd), xc, L.ptr(dyd), L.ptr(dwt), L.ptr(ws), ctypes.c_size_t(nws), B, T, H, W,
+        L.check(lib.qt_conv3d_c32_wgrad(L.qt_dtype(dt), L.ptr(xd), xc, L.ptr(dyd), L.ptr(dwt), L.ptr(ws), nws, B, T, H, W,
                                         L.stream_ptr()), "qt_conv3d_c32_wgrad")
         torch.cuda.synchronize()
         outs.append(dwt.cpu())
@@ -557,7 +553,6 @@ def test_walking_several_items_per_workgroup_changes_no_result(block, cfg):
     wp, wdp = wp.to(dev), wdp.to(dev)
     sc, sh = (torch.rand(64, generator=g) + 0.5).to(dev), (torch.randn(64, generator=g) * 0.3).to(dev)
     dyd = torch.randn(T, B, H, W, 64, generator=g).to(dt).to(dev)
-    lib.qt_conv3d_c32_dgrad_scratch_bytes.restype = ctypes.c_size_t
 
     def run(b0, nb):
         xs = xd[:, b0:b0 + nb].contiguous()
@@ -567,12 +562,12 @@ def test_walking_several_items_per_workgroup_changes_no_result(block, cfg):
         L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xs), xc, L.ptr(wp), L.ptr(yp), None, None, 0, None, nb, T, H, W, st), "plain")
         L.check(lib.qt_conv3d_c32_fwd(qdt, L.ptr(xs), xc, L.ptr(wp), L.ptr(ya), L.ptr(sc), L.ptr(sh), 1, None, nb, T, H, W, st), "affine")
         dy = dyd[:, b0:b0 + nb].contiguous()
-        nscr = int(lib.qt_conv3d_c32_dgrad_scratch_bytes(nb, T, H, W))
+        nscr = lib.qt_conv3d_c32_dgrad_scratch_bytes(nb, T, H, W)
         dxs = []
         for dxc in (64, 32):
             scr = torch.full((nscr // 4,), float("nan"), device=dev)
             dx = nan(T, nb, H, W, dxc)
-            L.check(lib.qt_conv3d_c32_dgrad(qdt, L.ptr(dy), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), ctypes.c_size_t(nscr), nb, T, H, W, st),
+            L.check(lib.qt_conv3d_c32_dgrad(qdt, L.ptr(dy), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), nscr, nb, T, H, W, st),
                     "qt_conv3d_c32_dgrad")
             dxs.append(dx)
         return y, yp, ya, dxs[0], dxs[1], part

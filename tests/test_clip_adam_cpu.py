@@ -18,7 +18,6 @@ QT_ERR_INVALID_ARG = -1
 
 def _lib():
     L = pkg("_lib").lib()
-    pkg("engine")._bind_api(L)
     return L
 
 
@@ -56,7 +55,6 @@ def test_workspace_size_counts_one_float_per_chunk():
 
 def test_grad_norm_argument_checks():
     L = _lib()
-    L.qt_last_error.restype = ctypes.c_char_p
     items = _items([100, 20000])
     need = L.qt_grad_norm_workspace_bytes(items, 2)
     assert need == 4 * 4

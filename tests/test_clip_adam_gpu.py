@@ -35,7 +35,6 @@ def _dev():
 def _api():
     L = pkg("_lib")
     lib = L.lib()
-    pkg("engine")._bind_api(lib)
     return L, lib, pkg("engine")
 
 

@@ -14,9 +14,6 @@ def _lib():
         import __graft_entry__ as g
         g.build()
     L = pkg("_lib").lib()
-    L.qt_conv3d_first_dgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    L.qt_last_error.restype = ctypes.c_char_p
     return L
 
 

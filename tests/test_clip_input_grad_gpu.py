@@ -8,7 +8,6 @@ the products are exact, only the summation order differs -- the bound tests/test
 gradient to), 1e-5 for f32.  The clip gradient of a whole model passes through every ReLU / max-pool decision of the conv
 blocks, so it is held to the bars tests/test_input_grad_gpu.py applies to the 2-D image gradient: f32 build cosine >= 0.999
 and max error <= 6e-2 of max|ref|; bf16 build cosine >= 0.85."""
-import ctypes
 import functools
 import sys
 
@@ -45,8 +44,6 @@ def _run_kernel(dt, B, T, H, W):
     dev = _dev()
     L = pkg("_lib")
     lib = L.lib()
-    lib.qt_conv3d_first_dgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     g = torch.Generator().manual_seed(1000 * T + H + W)
     dy = torch.randn(B, 32, T, H, W, generator=g).to(dt).float()             # d(loss)/d(conv output), rounded to dt
     w = torch.randn(32, 3, 3, 3, 3, generator=g) * (2.0 / 81) ** 0.5

@@ -97,7 +97,7 @@ def test_features_at_a_batch_that_is_no_multiple_of_seq_len(dt):
     six = fused[:6].float().cpu()
     fused.fill_(float("nan"))
     L = pkg("_lib")
-    lib = pkg("sequence_stream").bind(eng.L)
+    lib = eng.L
     images, poses = x.view(6, 3, 224, 224)[:5].contiguous(), f.view(6, 47)[:5].contiguous()
     L.check(lib.qt_plan_features(eng.handle, eng.ws_ptr, eng._tensor_ptrs, L.ptr(images), L.ptr(poses), 5, L.stream_ptr()),
             "qt_plan_features")

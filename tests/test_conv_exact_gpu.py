@@ -503,7 +503,6 @@ def test_weight_gradient_is_bit_exact(row, dt):
     d = _desc(L, dt, L.QT_CONV_FWD, B, (H, W), (Ho, Wo), Cin, Cout, k, s, p, quad)
     if strides:
         d.src_img_stride, d.src_row_stride, d.src_pix_stride = strides
-    lib.qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
     args = (B, (H, W), (Ho, Wo), Cin, Cout, k, k, s, p)
 
     def streaming_entry_points(what):
@@ -515,7 +514,7 @@ def test_weight_gradient_is_bit_exact(row, dt):
         ws = [gd.workspace(f"ws{j}", nbytes) for j in range(2)]       # exactly the queried size
         gr = [gd.output(f"grad{j}", (Cout, Cin, k, k), torch.float32) for j in range(3)]
         L.check(lib.qt_conv2d_wgrad_oihw(ctypes.byref(d), L.ptr(g_dy), L.ptr(g_x), L.ptr(gr[0]), L.ptr(ws[0]),
-                                         ctypes.c_size_t(nbytes), L.stream_ptr()), "qt_conv2d_wgrad_oihw")
+                                         nbytes, L.stream_ptr()), "qt_conv2d_wgrad_oihw")
         torch.cuda.synchronize()
         _same(gr[0], c["dw"], F32, (what, "oihw"))
         side = torch.cuda.Stream()
@@ -525,7 +524,7 @@ def test_weight_gradient_is_bit_exact(row, dt):
         torch.cuda.synchronize()
         for j in (0, 1):
             L.check(lib.qt_conv2d_wgrad_oihw_on(ctypes.byref(d), L.ptr(g_dy), L.ptr(g_x), L.ptr(gr[1 + j]), L.ptr(ws[j]),
-                                                ctypes.c_size_t(nbytes), L.stream_ptr(), ctypes.c_void_p(side.cuda_stream)),
+                                                nbytes, L.stream_ptr(), ctypes.c_void_p(side.cuda_stream)),
                     "qt_conv2d_wgrad_oihw_on")
         gd.check()
         _same(gr[1], c["dw"], F32, (what, "oihw_on, first"))
@@ -595,14 +594,13 @@ def test_linear_splitk_is_bit_exact(row):
     c = E.gemm_data(row)
     E.gemm_conditions(c, BF)
     M, N, K = row["cfg"]
-    lib.qt_linear_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.qt_linear_workspace_bytes(M, N, K)
     gd = Guard(dev)
     ws = gd.workspace("ws", nbytes)
     y = gd.output("y", (M, N), BF)
     xd, wd = gd.input("x", c["x"].to(BF)), gd.input("w", c["w"].to(BF))
     bd = gd.input("bias", c["bias"].float() if c["bias"] is not None else None)
-    L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), row["relu"], L.ptr(y), M, N, K, L.ptr(ws), ctypes.c_size_t(nbytes),
+    L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), row["relu"], L.ptr(y), M, N, K, L.ptr(ws), nbytes,
                                L.stream_ptr()), "qt_linear_bf16")
     gd.check()
     _same(y, c["out"], BF, "qt_linear_bf16")
@@ -753,15 +751,14 @@ def test_first_conv3d_is_bit_exact(row, dt):
         _same(dx.cpu().permute(0, 2, 1, 3, 4), c["dx"], F32, "qt_conv3d_first_dgrad")
     if "wgrad" in row["only"]:
         E.c3_conditions(c, F32, "wgrad")
-        lib.qt_conv3d_first_wgrad_workspace_bytes.restype = ctypes.c_size_t
-        nws = int(lib.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W))
+        nws = lib.qt_conv3d_first_wgrad_workspace_bytes(B, T, H, W)
         assert nws > 0
         gd = Guard(dev)
         cd1 = gd.input("clip", c["x1"].permute(0, 2, 1, 3, 4).contiguous().float())
         dyd = gd.input("dy", _tb(c["dy"]).to(dt))
         ws = gd.workspace("ws", nws)
         dw = gd.output("dw", (32, 3, 3, 3, 3), torch.float32)
-        L.check(lib.qt_conv3d_first_wgrad(qdt, L.ptr(cd1), L.ptr(dyd), L.ptr(dw), L.ptr(ws), ctypes.c_size_t(nws), B, T, H, W, st),
+        L.check(lib.qt_conv3d_first_wgrad(qdt, L.ptr(cd1), L.ptr(dyd), L.ptr(dw), L.ptr(ws), nws, B, T, H, W, st),
                 "qt_conv3d_first_wgrad")
         gd.check()
         _same(dw, c["dw"], F32, "qt_conv3d_first_wgrad")
@@ -781,11 +778,11 @@ def test_first_conv3d_is_bit_exact(row, dt):
             dwf = gd.output("dw_fused", (32, 3, 3, 3, 3), torch.float32)
             L.check(lib.qt_conv3d_first_wgrad_fused(qdt, L.ptr(cd1), L.ptr(yd), L.ptr(dout), L.ptr(arg), cp, L.ptr(mean),
                                                     L.ptr(invstd), L.ptr(sc), L.ptr(sh), L.ptr(coef), L.ptr(dwf), L.ptr(ws),
-                                                    ctypes.c_size_t(nws), B, T, H, W, st), "qt_conv3d_first_wgrad_fused")
+                                                    nws, B, T, H, W, st), "qt_conv3d_first_wgrad_fused")
             # the unfused kernel on the reference's dy: the same contraction
             dyd = gd.input("dy", _tb(f["dy"]).to(dt))
             dwu = gd.output("dw_unfused", (32, 3, 3, 3, 3), torch.float32)
-            L.check(lib.qt_conv3d_first_wgrad(qdt, L.ptr(cd1), L.ptr(dyd), L.ptr(dwu), L.ptr(ws), ctypes.c_size_t(nws), B, T, H, W, st),
+            L.check(lib.qt_conv3d_first_wgrad(qdt, L.ptr(cd1), L.ptr(dyd), L.ptr(dwu), L.ptr(ws), nws, B, T, H, W, st),
                     "qt_conv3d_first_wgrad")
             gd.check()
             _same(dwu, f["dw"], F32, ("qt_conv3d_first_wgrad on the formed dy", cp))
@@ -842,12 +839,11 @@ def test_second_conv3d_is_bit_exact(row, dt):
         wdp = torch.full((64, 27, 64), 3.0, dtype=dt)                              # [I padded][tap][O]
         wdp[:32] = c["wg"].permute(1, 2, 3, 4, 0).reshape(32, 27, 64).to(dt)
         wdp = gd.input("w", wdp)
-        lib.qt_conv3d_c32_dgrad_scratch_bytes.restype = ctypes.c_size_t
-        nscr = int(lib.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W))
+        nscr = lib.qt_conv3d_c32_dgrad_scratch_bytes(B, T, H, W)
         for dxc in (64, 32):
             scr = gd.workspace(f"scratch{dxc}", nscr)                              # exactly the queried size, NaN
             dx = gd.output(f"dx{dxc}", (T, B, H, W, dxc), dt)
-            L.check(lib.qt_conv3d_c32_dgrad(qdt, L.ptr(dyd), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), ctypes.c_size_t(nscr), B, T, H, W, st),
+            L.check(lib.qt_conv3d_c32_dgrad(qdt, L.ptr(dyd), L.ptr(wdp), L.ptr(dx), dxc, L.ptr(scr), nscr, B, T, H, W, st),
                     "qt_conv3d_c32_dgrad")
             gd.check()
             _same(_ncthw(dx, 32), c["dx"], dt, ("qt_conv3d_c32_dgrad", dxc))
@@ -857,12 +853,11 @@ def test_second_conv3d_is_bit_exact(row, dt):
         gd = Guard(dev)
         xd1 = gd.input("x", rows_of(c["x1"]))
         dyd = gd.input("dy", _tb(c["dy"]).to(dt))
-        lib.qt_conv3d_c32_wgrad_workspace_bytes.restype = ctypes.c_size_t
-        nws = int(lib.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W))
+        nws = lib.qt_conv3d_c32_wgrad_workspace_bytes(B, T, H, W)
         assert nws > 0
         ws = gd.workspace("ws", nws)
         dwt = gd.output("dw", (64, 32, 3, 3, 3), torch.float32)
-        L.check(lib.qt_conv3d_c32_wgrad(qdt, L.ptr(xd1), xc, L.ptr(dyd), L.ptr(dwt), L.ptr(ws), ctypes.c_size_t(nws), B, T, H, W, st),
+        L.check(lib.qt_conv3d_c32_wgrad(qdt, L.ptr(xd1), xc, L.ptr(dyd), L.ptr(dwt), L.ptr(ws), nws, B, T, H, W, st),
                 "qt_conv3d_c32_wgrad")
         gd.check()
         _same(dwt, c["dw"], F32, "qt_conv3d_c32_wgrad")

@@ -226,12 +226,11 @@ def run_wgrad(L, dt, dy_nhwc, x_nhwc, B, in_hw, out_hw, k_per_tap, n_out, kh, kw
     # zeros, not NaN: include/qtcnn.h has both entry points ACCUMULATE into dw (`dw += ...`)
     dw = gd.output("dw", (n_out, kh * kw, k_per_tap), torch.float32, fill=0)
     if workspace:
-        L.lib().qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
         nbytes = L.lib().qt_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
         assert nbytes > 0, "this shape was expected to use the partial-filter workspace"
         ws = gd.workspace("ws", nbytes)  # exactly the queried size, NaN: must be fully overwritten before it is read
         L.check(L.lib().qt_conv2d_wgrad_ws(ctypes.byref(d), L.ptr(dy_nhwc), L.ptr(x_nhwc), L.ptr(dw), L.ptr(ws),
-                                           ctypes.c_size_t(nbytes), L.stream_ptr()), "qt_conv2d_wgrad_ws")
+                                           nbytes, L.stream_ptr()), "qt_conv2d_wgrad_ws")
     else:
         L.check(L.lib().qt_conv2d_wgrad(ctypes.byref(d), L.ptr(dy_nhwc), L.ptr(x_nhwc), L.ptr(dw), L.stream_ptr()),
                 "qt_conv2d_wgrad")
@@ -302,14 +301,13 @@ def test_conv_wgrad_streaming_kernel(cfg, variant):
     d.in_h = d.in_w = d.out_h = d.out_w = H
     d.k_per_tap, d.n_out, d.kh, d.kw, d.stride, d.pad = Cin, Cout, 3, 3, 1, 1
     d.src_img_stride, d.src_row_stride, d.src_pix_stride = H * H * Cin, H * Cin, Cin
-    lib.qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
     g_oihw = torch.full((Cout, Cin, 3, 3), float("nan"), dtype=torch.float32, device=dev)
     try:
         lib.qt_set_wgrad_patch_min_width(7)
         nbytes = lib.qt_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
         wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         L.check(lib.qt_conv2d_wgrad_oihw(ctypes.byref(d), L.ptr(dyd), L.ptr(xd), L.ptr(g_oihw), L.ptr(wsb),
-                                         ctypes.c_size_t(nbytes), L.stream_ptr()), "qt_conv2d_wgrad_oihw")
+                                         nbytes, L.stream_ptr()), "qt_conv2d_wgrad_oihw")
     finally:
         lib.qt_set_wgrad_patch_min_width(-1)
         lib.qt_set_wgrad_patch_variant(-1)
@@ -386,7 +384,6 @@ def test_conv_wgrad_stride2_on_parity_planes(cfg):
     d.in_h, d.in_w, d.out_h, d.out_w = H, W, Ho, Wo
     d.k_per_tap, d.n_out, d.kh, d.kw, d.stride, d.pad = Cin, Cout, k, k, 2, pad
     d.src_img_stride, d.src_row_stride, d.src_pix_stride = H * W * Cin, W * Cin, Cin
-    lib.qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.qt_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
     assert nbytes > 0
     outs = []
@@ -394,7 +391,7 @@ def test_conv_wgrad_stride2_on_parity_planes(cfg):
         wsb = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev)
         g_oihw = torch.full((Cout, Cin, k, k), float("nan"), dtype=torch.float32, device=dev)
         L.check(lib.qt_conv2d_wgrad_oihw(ctypes.byref(d), L.ptr(dyd), L.ptr(xd), L.ptr(g_oihw), L.ptr(wsb),
-                                         ctypes.c_size_t(nbytes), L.stream_ptr()), "qt_conv2d_wgrad_oihw")
+                                         nbytes, L.stream_ptr()), "qt_conv2d_wgrad_oihw")
         torch.cuda.synchronize()
         outs.append(g_oihw.cpu())
     assert rel_err(outs[0], ref) <= 3e-5
@@ -421,8 +418,6 @@ def test_linear_wgrad_is_written_not_accumulated(dt, cfg):
     x = torch.randn(rows, inn, generator=g).to(dt).float()
     ref = (dy.double().t() @ x.double()).float()
     dw = torch.full((out, inn), float("nan"), dtype=torch.float32, device=dev)
-    L.lib().qt_linear_wgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     dyd, xd = dy.to(dev, dt), x.to(dev, dt)
     for _ in range(2):   # (a second call over the first result: nothing is accumulated)
         L.check(L.lib().qt_linear_wgrad(L.qt_dtype(dt), L.ptr(dyd), L.ptr(xd), L.ptr(dw), rows, out, inn,
@@ -496,7 +491,6 @@ def test_region_wgrad_on_the_tile_kernel(cfg):
     d.k_per_tap, d.n_out, d.kh, d.kw, d.stride, d.pad = C, N, 3, 3, 1, 1
     d.src_img_stride, d.src_row_stride, d.src_pix_stride = H * H * C, H * C, C
     d.quad = S
-    lib.qt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.qt_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
     assert nbytes > 0
     outs = []
@@ -504,7 +498,7 @@ def test_region_wgrad_on_the_tile_kernel(cfg):
         wsb = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev)
         g_oihw = torch.full((N, C, 3, 3), float("nan"), dtype=torch.float32, device=dev)
         L.check(lib.qt_conv2d_wgrad_oihw(ctypes.byref(d), L.ptr(dyd), L.ptr(xd), L.ptr(g_oihw), L.ptr(wsb),
-                                         ctypes.c_size_t(nbytes), L.stream_ptr()), "qt_conv2d_wgrad_oihw")
+                                         nbytes, L.stream_ptr()), "qt_conv2d_wgrad_oihw")
         torch.cuda.synchronize()
         outs.append(g_oihw.cpu())
     assert rel_err(outs[0], ref) <= 3e-5
@@ -597,9 +591,7 @@ def test_stride2_dgrad_merged_classes(dt, cfg):
     assert lib.qt_conv2d_igemm(ctypes.byref(d), ctypes.byref(io), L.stream_ptr()) != 0
 
 
-class PackItem(ctypes.Structure):   # qt_pack_item
-    _fields_ = [("w_oihw", ctypes.c_void_p), ("w_fwd", ctypes.c_void_p), ("w_dgrad", ctypes.c_void_p),
-                ("O", ctypes.c_int), ("I", ctypes.c_int), ("k", ctypes.c_int), ("stride2_dgrad", ctypes.c_int)]
+PackItem = pkg("_abi").PackItem   # qt_pack_item
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
@@ -632,7 +624,6 @@ def test_stride2_dgrad_merged_with_the_downsample_as_fifth_tap_slot(dt, cfg):
     wdev, wddev = w.to(dev).contiguous(), wd.to(dev).contiguous()
     items = (PackItem * 2)(PackItem(wdev.data_ptr(), None, op.data_ptr(), Cout, Cin, 3, 3),
                            PackItem(wddev.data_ptr(), None, op.data_ptr(), Cout, Cin, 1, 4))
-    lib.qt_pack_weights_batched.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     L.check(lib.qt_pack_weights_batched(L.qt_dtype(dt), items, 2, L.stream_ptr()), "qt_pack_weights_batched")
     # both gradient maps in ONE allocation (any two device tensors would do: the kernel takes their distance)
     maps = torch.empty(2, B, Ho, Ho, Cout, dtype=dt, device=dev)
@@ -731,17 +722,13 @@ def test_batched_weight_pack_matches_per_layer_packing(dt):
     L = pkg("_lib")
     lib = L.lib()
 
-    class Item(ctypes.Structure):
-        _fields_ = [("w", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgrad", ctypes.c_void_p),
-                    ("O", ctypes.c_int), ("I", ctypes.c_int), ("k", ctypes.c_int), ("s2", ctypes.c_int)]
-
     g = torch.Generator().manual_seed(31)
     # (O, I, k, stride2_dgrad): 1 = parity-class layout, 2 = merged layout (3x3 only; zero tap slots zeroed beforehand)
     shapes = [(64, 64, 3, 0), (128, 64, 3, 1), (128, 64, 1, 1), (512, 256, 3, 1), (128, 192, 1, 0), (2688, 5376, 1, 0),
               (128, 64, 3, 2), (512, 256, 3, 2)]
     qdt = L.qt_dtype(dt)
     st = L.stream_ptr()
-    items = (Item * len(shapes))()
+    items = (PackItem * len(shapes))()
     keep, want = [], []
     for j, (O, I, k, s2) in enumerate(shapes):
         w = torch.randn(O, I, k, k, generator=g).to(dev)
@@ -756,7 +743,7 @@ def test_batched_weight_pack_matches_per_layer_packing(dt):
             L.check(lib.qt_pack_dgrad_s2(qdt, L.ptr(w), L.ptr(rd), O, I, k, None, None, None, st), "qt_pack_dgrad_s2")
         else:
             L.check(lib.qt_pack_conv_weight(qdt, L.ptr(w), L.ptr(rf), L.ptr(rd), O, I, k, k, st), "qt_pack_conv_weight")
-        items[j] = Item(w.data_ptr(), fwd.data_ptr(), dg.data_ptr(), O, I, k, s2)
+        items[j] = PackItem(w.data_ptr(), fwd.data_ptr(), dg.data_ptr(), O, I, k, s2)
         keep.append((w, fwd, dg))
         want.append((rf, rd))
     L.check(lib.qt_pack_weights_batched(qdt, items, len(shapes), st), "qt_pack_weights_batched")
@@ -765,7 +752,7 @@ def test_batched_weight_pack_matches_per_layer_packing(dt):
         assert torch.equal(fwd, rf), shp
         assert torch.equal(dg, rd), shp
     # bad shapes are refused, not mangled
-    bad = (Item * 1)(Item(keep[0][0].data_ptr(), keep[0][1].data_ptr(), None, 48, 64, 3, 0))
+    bad = (PackItem * 1)(PackItem(keep[0][0].data_ptr(), keep[0][1].data_ptr(), None, 48, 64, 3, 0))
     assert lib.qt_pack_weights_batched(qdt, bad, 1, st) == -1 and b"multiples of" in lib.qt_last_error()
 
 
@@ -789,19 +776,18 @@ def test_linear_splitk_bf16(cfg):
     ref = torch.nn.functional.linear(x.float(), w.float(), b)
     if relu:
         ref = torch.relu(ref)
-    lib.qt_linear_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.qt_linear_workspace_bytes(M, N, K)
     assert nbytes >= M * N * 4
     ws = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev)
     y = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     xd, wd = x.to(dev), w.to(dev)
     bd = b.to(dev) if b is not None else None
-    L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), relu, L.ptr(y), M, N, K, L.ptr(ws), ctypes.c_size_t(nbytes),
+    L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), relu, L.ptr(y), M, N, K, L.ptr(ws), nbytes,
                                L.stream_ptr()), "qt_linear_bf16")
     torch.cuda.synchronize()
     assert rel_err(y.float().cpu(), ref) <= 4e-3   # one bf16 rounding of the output
     # uncovered shapes are reported, not mangled
-    assert lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), relu, L.ptr(y), 300, N, K, L.ptr(ws), ctypes.c_size_t(nbytes),
+    assert lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), relu, L.ptr(y), 300, N, K, L.ptr(ws), nbytes,
                               L.stream_ptr()) == -3   # QT_ERR_UNSUPPORTED
 
 
@@ -817,23 +803,22 @@ def test_col_sum_ws_is_deterministic(dt, rows, cols, ld):
     g = torch.Generator().manual_seed(5)
     x = torch.randn(rows, ld, generator=g).to(dt).to(dev)
     ref = x[:, :cols].double().sum(0).cpu()
-    lib.qt_col_sum_workspace_bytes.restype = ctypes.c_size_t
-    nws = lib.qt_col_sum_workspace_bytes(ctypes.c_longlong(rows), cols)
+    nws = lib.qt_col_sum_workspace_bytes(rows, cols)
     assert nws == min(-(-rows // 128), 1024) * cols * 4
     runs = []
     for acc in (0, 0, 1):
         ws = torch.full((nws // 4,), float("nan"), device=dev)
         out = torch.ones(cols, device=dev)
-        L.check(lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(x), ctypes.c_longlong(rows), cols, ld, L.ptr(out), acc, L.ptr(ws),
-                                  ctypes.c_size_t(nws), st), "qt_col_sum_ws")
+        L.check(lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(x), rows, cols, ld, L.ptr(out), acc, L.ptr(ws),
+                                  nws, st), "qt_col_sum_ws")
         torch.cuda.synchronize()
         runs.append(out.cpu())
     assert torch.equal(runs[0], runs[1])
     assert torch.equal(runs[2], runs[0] + 1)
     assert rel_err(runs[0], ref) <= 1e-5
     atomic = torch.empty(cols, device=dev)
-    L.check(lib.qt_col_sum(L.qt_dtype(dt), L.ptr(x), ctypes.c_longlong(rows), cols, ld, L.ptr(atomic), 0, st), "qt_col_sum")
+    L.check(lib.qt_col_sum(L.qt_dtype(dt), L.ptr(x), rows, cols, ld, L.ptr(atomic), 0, st), "qt_col_sum")
     torch.cuda.synchronize()
     assert rel_err(runs[0], atomic.cpu()) <= 1e-5
-    assert lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(x), ctypes.c_longlong(rows), cols, ld, L.ptr(atomic), 0, L.ptr(ws),
-                             ctypes.c_size_t(nws - 4), st) != 0
+    assert lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(x), rows, cols, ld, L.ptr(atomic), 0, L.ptr(ws),
+                             nws - 4, st) != 0

@@ -10,7 +10,6 @@ Every test prints max(|err| / bound); output buffers are pre-filled with NaN and
 
 Reference behaviour: nn.BatchNorm2d / nn.ReLU / nn.AdaptiveAvgPool2d / nn.MaxPool2d(2, 2) / nn.Dropout and their autograd as
 wired by the reference's QuadtreeCNN (Quadtree_from scratch/models.py:222-294)."""
-import ctypes
 import functools
 
 import pytest
@@ -21,8 +20,6 @@ from _util import pkg
 
 pytestmark = pytest.mark.gpu
 
-LL = ctypes.c_longlong
-CF = ctypes.c_float
 NAN = float("nan")
 QT_ERR_INVALID_ARG = -1
 
@@ -52,10 +49,7 @@ def _report(name, r):
     assert r <= 1.0, (name, r)
 
 
-class BnEvalItem(ctypes.Structure):   # qt_bn_eval_item
-    _fields_ = [("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("running_mean", ctypes.c_void_p),
-                ("running_var", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("C", ctypes.c_int),
-                ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p)]
+BnEvalItem = pkg("_abi").BnEvalItem   # qt_bn_eval_item
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -73,8 +67,8 @@ def _run_finalize(L, lib, dev, partial, count, gamma, beta, rmean, rvar):
         rm, rv = _nan((C + 8,), torch.float32, dev), _nan((C + 8,), torch.float32, dev)
         rm[:C], rv[:C] = rmean, rvar
     nbt = torch.tensor([41, -7], dtype=torch.int64, device=dev)
-    L.check(lib.qt_bn_finalize(L.ptr(buf), rows, C, LL(count), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt),
-                               CF(0.1), CF(1e-5), L.ptr(outs["mean"]), L.ptr(outs["invstd"]), L.ptr(outs["scale"]),
+    L.check(lib.qt_bn_finalize(L.ptr(buf), rows, C, count, L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt),
+                               0.1, 1e-5, L.ptr(outs["mean"]), L.ptr(outs["invstd"]), L.ptr(outs["scale"]),
                                L.ptr(outs["shift"]), L.stream_ptr()), "qt_bn_finalize")
     torch.cuda.synchronize()
     assert nbt.tolist() == [42, -7]
@@ -130,7 +124,7 @@ def test_bn_finalize_count_one_uses_the_biased_variance():
     for k, (r, b) in Bd.bn_finalize_ref(partial, count, gamma, beta, rmean, rvar, folded=False).items():
         _report(f"bn_finalize count=1 {k}", Bd.ratio(got[k], r, b))
     # a lone running statistic is refused
-    st = lib.qt_bn_finalize(L.ptr(partial.clone()), 1, C, LL(1), None, None, L.ptr(rmean.clone()), None, None, CF(0.1), CF(1e-5),
+    st = lib.qt_bn_finalize(L.ptr(partial.clone()), 1, C, 1, None, None, L.ptr(rmean.clone()), None, None, 0.1, 1e-5,
                             L.ptr(got["mean"].clone()), L.ptr(got["invstd"].clone()), L.ptr(got["scale"].clone()),
                             L.ptr(got["shift"].clone()), L.stream_ptr())
     assert st == QT_ERR_INVALID_ARG
@@ -156,9 +150,9 @@ def _check_bn_act(L, lib, dev, dt, M, C, ins, residual, relu):
     bits = torch.full((M + 1, C // 8), 0xAA, dtype=torch.uint8, device=dev)
     st = L.stream_ptr()
     L.check(lib.qt_bn_act(L.qt_dtype(dt), L.ptr(y), L.ptr(sc), L.ptr(sh), L.ptr(res), L.ptr(rs), L.ptr(rb), relu, L.ptr(out0),
-                          LL(M), C, st), "qt_bn_act")
+                          M, C, st), "qt_bn_act")
     L.check(lib.qt_bn_act_mask(L.qt_dtype(dt), L.ptr(y), L.ptr(sc), L.ptr(sh), L.ptr(res), L.ptr(rs), L.ptr(rb), relu,
-                               L.ptr(out1), L.ptr(bits), LL(M), C, st), "qt_bn_act_mask")
+                               L.ptr(out1), L.ptr(bits), M, C, st), "qt_bn_act_mask")
     torch.cuda.synchronize()
     assert _all_nan(out0[M]) and _all_nan(out1[M]) and bool((bits[M] == 0xAA).all())   # rows past M
     assert torch.equal(out0[:M], out1[:M])
@@ -181,7 +175,7 @@ def test_bn_act_vs_float64(dt, shape):
     # half a pair of residual coefficients is refused
     o = _nan((M, C), dt, dev)
     assert lib.qt_bn_act(L.qt_dtype(dt), L.ptr(ins[0]), L.ptr(ins[2]), L.ptr(ins[3]), L.ptr(ins[1]), L.ptr(ins[4]), None, 1,
-                         L.ptr(o), LL(M), C, L.stream_ptr()) == QT_ERR_INVALID_ARG
+                         L.ptr(o), M, C, L.stream_ptr()) == QT_ERR_INVALID_ARG
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
@@ -204,10 +198,10 @@ def _check_reduce(L, lib, dev, dt, M, C, ins, with_mask):
     g, mask, y, mean, invstd, _ = ins
     if not with_mask:
         mask = None
-    rows = lib.qt_bn_bwd_partial_rows(LL(M), C)
+    rows = lib.qt_bn_bwd_partial_rows(M, C)
     assert 0 < rows <= 2048
     part = _nan((rows + 3, 2, C), torch.float32, dev)
-    L.check(lib.qt_bn_bwd_reduce(L.qt_dtype(dt), L.ptr(g), L.ptr(mask), L.ptr(y), L.ptr(mean), L.ptr(invstd), L.ptr(part), LL(M),
+    L.check(lib.qt_bn_bwd_reduce(L.qt_dtype(dt), L.ptr(g), L.ptr(mask), L.ptr(y), L.ptr(mean), L.ptr(invstd), L.ptr(part), M,
                                  C, L.stream_ptr()), "qt_bn_bwd_reduce")
     torch.cuda.synchronize()
     assert _all_nan(part[rows:])
@@ -239,8 +233,8 @@ def test_bn_bwd_partial_rows_and_reduce_accept_the_same_channel_counts(C):
     M = 64
     g, _, y, mean, invstd, _ = Bd.bwd_inputs(M, C, torch.float32, False, 3, dev)
     part = torch.zeros(64, 2, C, device=dev)
-    rows = lib.qt_bn_bwd_partial_rows(LL(M), C)
-    st = lib.qt_bn_bwd_reduce(0, L.ptr(g), None, L.ptr(y), L.ptr(mean), L.ptr(invstd), L.ptr(part), LL(M), C, L.stream_ptr())
+    rows = lib.qt_bn_bwd_partial_rows(M, C)
+    st = lib.qt_bn_bwd_reduce(0, L.ptr(g), None, L.ptr(y), L.ptr(mean), L.ptr(invstd), L.ptr(part), M, C, L.stream_ptr())
     torch.cuda.synchronize()
     accepted = 256 % (C // 8) == 0
     assert (rows > 0) == accepted and (st == 0) == accepted
@@ -268,7 +262,7 @@ def test_bn_bwd_finalize_vs_float64(case):
     dgamma, dbeta = _nan((C + 8,), torch.float32, dev), _nan((C + 8,), torch.float32, dev)
     dgamma[:C], dbeta[:C] = pre_g, pre_b
     coef = _nan((3 * C + 8,), torch.float32, dev)
-    L.check(lib.qt_bn_bwd_finalize(L.ptr(buf), rows, C, LL(count), L.ptr(gamma), L.ptr(invstd), L.ptr(dgamma) if grads else None,
+    L.check(lib.qt_bn_bwd_finalize(L.ptr(buf), rows, C, count, L.ptr(gamma), L.ptr(invstd), L.ptr(dgamma) if grads else None,
                                    L.ptr(dbeta) if grads else None, acc, L.ptr(coef), L.stream_ptr()), "qt_bn_bwd_finalize")
     torch.cuda.synchronize()
     assert torch.equal(buf[:rows], partial) and _all_nan(coef[3 * C:]) and _all_nan(dgamma[C:]) and _all_nan(dbeta[C:])
@@ -292,7 +286,7 @@ def _check_apply(L, lib, dev, dt, M, C, ins, with_mask, with_gout):
     dy = _nan((M + 1, C), dt, dev)
     gout = _nan((M + 1, C), dt, dev) if with_gout else None
     L.check(lib.qt_bn_bwd_apply(L.qt_dtype(dt), L.ptr(g), L.ptr(mask), L.ptr(y), L.ptr(mean), L.ptr(invstd), L.ptr(coef), L.ptr(dy),
-                                L.ptr(gout), LL(M), C, L.stream_ptr()), "qt_bn_bwd_apply")
+                                L.ptr(gout), M, C, L.stream_ptr()), "qt_bn_bwd_apply")
     torch.cuda.synchronize()
     light = Bd.light_route(M, C, dt, mask, gout)
     ref, bound, gm = Bd.bwd_apply_ref(g, mask, y, mean, invstd, coef, dt, light)
@@ -356,11 +350,11 @@ def test_bn_eval_affine_vs_float64(n):
         arr[j] = BnEvalItem(gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), o["scale"].data_ptr(),
                             o["shift"].data_ptr(), C, o["mean"].data_ptr() if pair else None,
                             o["invstd"].data_ptr() if pair else None)
-    L.check(lib.qt_bn_eval_affine_batched(arr, n, CF(1e-5), L.stream_ptr()), "qt_bn_eval_affine_batched")
+    L.check(lib.qt_bn_eval_affine_batched(arr, n, 1e-5, L.stream_ptr()), "qt_bn_eval_affine_batched")
     singles = []
     for C, (gamma, beta, rmean, rvar), _ in items[:3]:
         s, t = _nan((C + 8,), torch.float32, dev), _nan((C + 8,), torch.float32, dev)
-        L.check(lib.qt_bn_eval_affine(L.ptr(gamma), L.ptr(beta), L.ptr(rmean), L.ptr(rvar), CF(1e-5), C, L.ptr(s), L.ptr(t),
+        L.check(lib.qt_bn_eval_affine(L.ptr(gamma), L.ptr(beta), L.ptr(rmean), L.ptr(rvar), 1e-5, C, L.ptr(s), L.ptr(t),
                                       L.stream_ptr()), "qt_bn_eval_affine")
         singles.append((s, t))
     torch.cuda.synchronize()
@@ -391,11 +385,11 @@ def test_bn_eval_affine_batched_rejections():
     for j in range(33):
         arr[j] = BnEvalItem(gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), o[0].data_ptr(), o[1].data_ptr(),
                             C, None, None)
-    assert lib.qt_bn_eval_affine_batched(arr, 33, CF(1e-5), L.stream_ptr()) == QT_ERR_INVALID_ARG
+    assert lib.qt_bn_eval_affine_batched(arr, 33, 1e-5, L.stream_ptr()) == QT_ERR_INVALID_ARG
     arr[0].mean = o[2].data_ptr()   # mean without invstd
-    assert lib.qt_bn_eval_affine_batched(arr, 1, CF(1e-5), L.stream_ptr()) == QT_ERR_INVALID_ARG
+    assert lib.qt_bn_eval_affine_batched(arr, 1, 1e-5, L.stream_ptr()) == QT_ERR_INVALID_ARG
     arr[0].invstd = o[3].data_ptr()
-    assert lib.qt_bn_eval_affine_batched(arr, 1, CF(1e-5), L.stream_ptr()) == 0
+    assert lib.qt_bn_eval_affine_batched(arr, 1, 1e-5, L.stream_ptr()) == 0
     torch.cuda.synchronize()
 
 
@@ -483,7 +477,7 @@ def _dropout(L, lib, dev, dt, p, seed, pad=0):
     rows, cols = Bd.DROP_ROWS, Bd.DROP_COLS
     x = _nan((rows, cols + pad), dt, dev)
     x[:, :cols] = 1.0
-    L.check(lib.qt_dropout(L.qt_dtype(dt), L.ptr(x), LL(rows), cols, cols + pad, ctypes.c_ulonglong(seed), CF(p), L.stream_ptr()),
+    L.check(lib.qt_dropout(L.qt_dtype(dt), L.ptr(x), rows, cols, cols + pad, seed, p, L.stream_ptr()),
             "qt_dropout")
     torch.cuda.synchronize()
     return x
@@ -510,10 +504,10 @@ def test_dropout_p0_is_the_identity(dt):
     dev, L, lib = _env()
     x = torch.randn(37, 50, device=dev).to(dt)
     y = x.clone()
-    L.check(lib.qt_dropout(L.qt_dtype(dt), L.ptr(y), LL(37), 48, 50, ctypes.c_ulonglong(5), CF(0.0), L.stream_ptr()), "qt_dropout")
+    L.check(lib.qt_dropout(L.qt_dtype(dt), L.ptr(y), 37, 48, 50, 5, 0.0, L.stream_ptr()), "qt_dropout")
     torch.cuda.synchronize()
     assert torch.equal(x, y)
-    assert lib.qt_dropout(L.qt_dtype(dt), L.ptr(y), LL(37), 48, 50, ctypes.c_ulonglong(5), CF(1.0), L.stream_ptr()) == QT_ERR_INVALID_ARG
+    assert lib.qt_dropout(L.qt_dtype(dt), L.ptr(y), 37, 48, 50, 5, 1.0, L.stream_ptr()) == QT_ERR_INVALID_ARG
 
 
 def test_dropout_backward_pair_bit_exact():
@@ -523,11 +517,11 @@ def test_dropout_backward_pair_bit_exact():
     gen = torch.Generator().manual_seed(8)
     act = torch.relu(torch.randn(rows, cols, generator=gen)).to(dev)
     positive = act > 0
-    L.check(lib.qt_dropout(0, L.ptr(act), LL(rows), cols, cols, ctypes.c_ulonglong(77), CF(p), L.stream_ptr()), "qt_dropout")
+    L.check(lib.qt_dropout(0, L.ptr(act), rows, cols, cols, 77, p, L.stream_ptr()), "qt_dropout")
     g = torch.randn(rows * cols + 5, generator=gen).to(dev)
     g0 = g.clone()
     mul = torch.tensor(1.0 / (1.0 - p), dtype=torch.float32)
-    L.check(lib.qt_relu_mask_scale(0, L.ptr(g), L.ptr(act), LL(rows * cols), CF(float(mul)), L.stream_ptr()), "qt_relu_mask_scale")
+    L.check(lib.qt_relu_mask_scale(0, L.ptr(g), L.ptr(act), rows * cols, float(mul), L.stream_ptr()), "qt_relu_mask_scale")
     torch.cuda.synchronize()
     kept = (act != 0).flatten()
     npos = int(positive.sum())
@@ -549,9 +543,9 @@ def test_relu_mask_scale_and_cast_bit_exact(dt, n):
     act[1::7] = -0.0
     act, g = act.to(dev, dt), torch.randn(n + 3, generator=gen).to(dev, dt)
     g0 = g.clone()
-    L.check(lib.qt_relu_mask_scale(L.qt_dtype(dt), L.ptr(g), L.ptr(act), LL(n), CF(1.25), L.stream_ptr()), "qt_relu_mask_scale")
+    L.check(lib.qt_relu_mask_scale(L.qt_dtype(dt), L.ptr(g), L.ptr(act), n, 1.25, L.stream_ptr()), "qt_relu_mask_scale")
     out = _nan((n + 3,), torch.float32, dev)
-    L.check(lib.qt_cast_f32(L.qt_dtype(dt), L.ptr(g0), L.ptr(out), LL(n), L.stream_ptr()), "qt_cast_f32")
+    L.check(lib.qt_cast_f32(L.qt_dtype(dt), L.ptr(g0), L.ptr(out), n, L.stream_ptr()), "qt_cast_f32")
     torch.cuda.synchronize()
     want = torch.where(act[:n].float() > 0, g0[:n].float() * 1.25, torch.zeros((), device=dev)).to(dt)   # one f32 product, one store
     assert torch.equal(g[:n], want) and torch.equal(g[n:], g0[n:])
@@ -567,7 +561,7 @@ def test_scale_by_nonzero_bit_exact(n):
     x[1::9] = -0.0
     x, g = x.to(dev), torch.randn(n + 3, generator=gen).to(dev)
     g0 = g.clone()
-    L.check(lib.qt_scale_by_nonzero(L.ptr(g), L.ptr(x), LL(n), CF(2.0 / 3.0), L.stream_ptr()), "qt_scale_by_nonzero")
+    L.check(lib.qt_scale_by_nonzero(L.ptr(g), L.ptr(x), n, 2.0 / 3.0, L.stream_ptr()), "qt_scale_by_nonzero")
     torch.cuda.synchronize()
     mul = torch.tensor(2.0 / 3.0, dtype=torch.float32, device=dev)
     want = torch.where(x[:n] != 0, g0[:n] * mul, torch.zeros((), device=dev))
@@ -586,11 +580,11 @@ def test_relu_mask_cols_bit_exact(dt, shape):
     act[:, ::4] = 0.0
     act, d = act.to(dev, dt), torch.randn(rows, ld, generator=gen).to(dev, dt)
     out = _nan((rows * cols + 3,), torch.float32, dev)
-    L.check(lib.qt_relu_mask_cols(L.qt_dtype(dt), L.ptr(d), L.ptr(act), L.ptr(out), LL(rows), cols, ld, col0, CF(1.5),
+    L.check(lib.qt_relu_mask_cols(L.qt_dtype(dt), L.ptr(d), L.ptr(act), L.ptr(out), rows, cols, ld, col0, 1.5,
                                   L.stream_ptr()), "qt_relu_mask_cols")
     torch.cuda.synchronize()
     sl = slice(col0, col0 + cols)
     want = torch.where(act[:, sl].float() > 0, d[:, sl].float() * 1.5, torch.zeros((), device=dev))
     assert torch.equal(out[:rows * cols].view(rows, cols), want) and _all_nan(out[rows * cols:])
-    assert lib.qt_relu_mask_cols(L.qt_dtype(dt), L.ptr(d), L.ptr(act), L.ptr(out), LL(rows), cols, ld, ld - cols + 1, CF(1.5),
+    assert lib.qt_relu_mask_cols(L.qt_dtype(dt), L.ptr(d), L.ptr(act), L.ptr(out), rows, cols, ld, ld - cols + 1, 1.5,
                                  L.stream_ptr()) == QT_ERR_INVALID_ARG

@@ -19,12 +19,7 @@ pytestmark = pytest.mark.gpu
 QT_ERR_INVALID_ARG = -1
 
 
-class GemmSmallDesc(ctypes.Structure):   # qt_gemm_small_desc
-    _fields_ = [("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int),
-                ("a_dtype", ctypes.c_int), ("b_dtype", ctypes.c_int), ("c_dtype", ctypes.c_int),
-                ("a_row_stride", ctypes.c_longlong), ("a_k_stride", ctypes.c_longlong),
-                ("b_row_stride", ctypes.c_longlong), ("b_k_stride", ctypes.c_longlong),
-                ("c_row_stride", ctypes.c_longlong), ("relu", ctypes.c_int), ("accumulate", ctypes.c_int)]
+GemmSmallDesc = pkg("_abi").GemmSmallDesc   # qt_gemm_small_desc
 
 
 def _dev():

@@ -154,7 +154,7 @@ def test_argument_errors_without_a_gpu():
 def test_c_abi_refuses_before_any_launch():
     """every refusal below comes before the first device call: the pointers are not device memory"""
     G, Lm = pkg("gradcam"), pkg("_lib")
-    L = G.bind(Lm.lib())
+    L = Lm.lib()
     buf = (ctypes.c_float * 64)()
     p = ctypes.addressof(buf)
     limit = G.MAX_POSITIONS

@@ -24,13 +24,13 @@ def run_map(dev, act, grad):
     """qt_gradcam_map through ctypes.  The map, the peaks and the workspace are followed by poisoned floats that must stay
     as they are, and the inputs must not be written.  Returns (cam [B,P], peak [B]) as f32 numpy."""
     G, Lm = pkg("gradcam"), pkg("_lib")
-    L = G.bind(Lm.lib())
+    L = Lm.lib()
     B, C, P = act.shape
     a, g = torch.from_numpy(act).to(dev), torch.from_numpy(grad).to(dev)
     a0, g0 = a.clone(), g.clone()
     cam = torch.full((B * P + 64,), POISON, device=dev)
     peak = torch.full((B + 64,), POISON, device=dev)
-    ws_bytes = int(L.qt_gradcam_workspace_bytes(B, C, P))
+    ws_bytes = L.qt_gradcam_workspace_bytes(B, C, P)
     ws = torch.full((ws_bytes // 4 + 64,), POISON, device=dev)
     Lm.check(L.qt_gradcam_map(a.data_ptr(), g.data_ptr(), B, C, P, cam.data_ptr(), peak.data_ptr(),
                               Lm.ptr(ws) if ws_bytes else None, ws_bytes, Lm.stream_ptr()), "qt_gradcam_map")
@@ -118,7 +118,7 @@ def run_overlay(dev, cam, frames, alpha, planes=False, off_out=0, off_src=0, off
     poisoned allocation and are followed by poison, which must stay; with planes=False the two planes are handed over as
     NULL and a poisoned stand-in shows that nothing else was written either.  Returns (out, heat, index) as numpy."""
     G, Lm = pkg("gradcam"), pkg("_lib")
-    L = G.bind(Lm.lib())
+    L = Lm.lib()
     B, H, W, _ = frames.shape
     n = B * H * W
     c = torch.from_numpy(cam).to(dev)

@@ -35,8 +35,6 @@ from _util import pkg
 
 pytestmark = pytest.mark.gpu
 
-LL = ctypes.c_longlong
-CF = ctypes.c_float
 NAN = float("nan")
 F32, BF16 = torch.float32, torch.bfloat16
 DTS = pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
@@ -101,7 +99,7 @@ def _apply_ratio(L, lib, dev, dt, M, C, with_mask, with_gout, seed):
     dy = _nan((M + 1, C), dt, dev)
     gout = _nan((M + 1, C), dt, dev) if with_gout else None
     L.check(lib.qt_bn_bwd_apply(L.qt_dtype(dt), L.ptr(g), L.ptr(mask), L.ptr(y), L.ptr(mean), L.ptr(invstd), L.ptr(coef), L.ptr(dy),
-                                L.ptr(gout), LL(M), C, L.stream_ptr()), "qt_bn_bwd_apply")
+                                L.ptr(gout), M, C, L.stream_ptr()), "qt_bn_bwd_apply")
     torch.cuda.synchronize()
     light = Bd.light_route(M, C, dt, mask, gout)
     assert _all_nan(dy[M]) and (gout is None or _all_nan(gout[M]))
@@ -333,7 +331,7 @@ def test_dropout(p, dt):
     rows, cols, pad, seed = s["rows"], s["cols"], 24, 0x1234567887654321
     x0 = (torch.randn(rows, cols + pad, generator=torch.Generator().manual_seed(44)) + 3.0).to(dt)    # (no zeros among the inputs)
     x = x0.to(dev)
-    L.check(lib.qt_dropout(L.qt_dtype(dt), L.ptr(x), LL(rows), cols, cols + pad, ctypes.c_ulonglong(seed), CF(p), L.stream_ptr()),
+    L.check(lib.qt_dropout(L.qt_dtype(dt), L.ptr(x), rows, cols, cols + pad, seed, p, L.stream_ptr()),
             "qt_dropout")
     torch.cuda.synchronize()
     pf = np.float32(p)
@@ -364,7 +362,7 @@ def test_relu_mask_scale(dt):
     n = _shape("test_relu_mask_scale")["n"]
     act, g = _act_and_grad(n, dt, dev, 45)
     g0 = g.clone()
-    L.check(lib.qt_relu_mask_scale(L.qt_dtype(dt), L.ptr(g), L.ptr(act), LL(n), CF(1.25), L.stream_ptr()), "qt_relu_mask_scale")
+    L.check(lib.qt_relu_mask_scale(L.qt_dtype(dt), L.ptr(g), L.ptr(act), n, 1.25, L.stream_ptr()), "qt_relu_mask_scale")
     torch.cuda.synchronize()
     want = torch.where(act[:n].float() > 0, g0[:n].float() * 1.25, torch.zeros((), device=dev)).to(dt)
     assert torch.equal(g[:n], want) and torch.equal(g[n:], g0[n:])
@@ -377,7 +375,7 @@ def test_cast_f32(dt):
     n = _shape("test_cast_f32")["n"]
     _, g = _act_and_grad(n, dt, dev, 46)
     out = _nan((n + 3,), F32, dev)
-    L.check(lib.qt_cast_f32(L.qt_dtype(dt), L.ptr(g), L.ptr(out), LL(n), L.stream_ptr()), "qt_cast_f32")
+    L.check(lib.qt_cast_f32(L.qt_dtype(dt), L.ptr(g), L.ptr(out), n, L.stream_ptr()), "qt_cast_f32")
     torch.cuda.synchronize()
     assert torch.equal(out[:n], g[:n].float()) and _all_nan(out[n:])
     _say("test_cast_f32")
@@ -388,7 +386,7 @@ def test_scale_by_nonzero():
     n = _shape("test_scale_by_nonzero")["n"]
     x, g = _act_and_grad(n, F32, dev, 47)
     g0 = g.clone()
-    L.check(lib.qt_scale_by_nonzero(L.ptr(g), L.ptr(x), LL(n), CF(2.0 / 3.0), L.stream_ptr()), "qt_scale_by_nonzero")
+    L.check(lib.qt_scale_by_nonzero(L.ptr(g), L.ptr(x), n, 2.0 / 3.0, L.stream_ptr()), "qt_scale_by_nonzero")
     torch.cuda.synchronize()
     mul = torch.tensor(2.0 / 3.0, dtype=F32, device=dev)
     want = torch.where(x[:n] != 0, g0[:n] * mul, torch.zeros((), device=dev))
@@ -406,7 +404,7 @@ def test_relu_mask_cols(dt):
     act[:, ::4] = 0.0
     act, d = act.to(dt), torch.randn(rows, ld, generator=gen, device=dev).to(dt)
     out = _nan((rows * cols + 3,), F32, dev)
-    L.check(lib.qt_relu_mask_cols(L.qt_dtype(dt), L.ptr(d), L.ptr(act), L.ptr(out), LL(rows), cols, ld, col0, CF(1.5), L.stream_ptr()),
+    L.check(lib.qt_relu_mask_cols(L.qt_dtype(dt), L.ptr(d), L.ptr(act), L.ptr(out), rows, cols, ld, col0, 1.5, L.stream_ptr()),
             "qt_relu_mask_cols")
     torch.cuda.synchronize()
     sl = slice(col0, col0 + cols)
@@ -466,7 +464,7 @@ def test_pack_dgrad_s2(dt):
     w = _weights(O, I, k, dev, 51)
     n = O * I * 9
     dst = _nan((n + 8,), dt, dev)
-    offs, khs, kws = (LL * 4)(), (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
+    offs, khs, kws = (ctypes.c_longlong * 4)(), (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
     L.check(lib.qt_pack_dgrad_s2(L.qt_dtype(dt), L.ptr(w), L.ptr(dst), O, I, k, offs, khs, kws, L.stream_ptr()), "qt_pack_dgrad_s2")
     torch.cuda.synchronize()
     base = 0
@@ -643,7 +641,7 @@ def _edge_rows(rows, rpb, cap=2048):
 
 def _metrics_call(dev, C, z=None, pred_in=None, y=None, state=None, outputs=False):
     M, lib = pkg("metrics"), pkg("_lib")
-    L = M.bind(lib.lib())
+    L = lib.lib()
     rows = len(y)
     yt = torch.from_numpy(y).to(dev)
     zt = pt = probs = conf = pred = None
@@ -732,7 +730,7 @@ def test_metrics_pred_in(i):
 
 def _scores_call(dev, s, y, C, bits, M, state=None):
     S, lib = pkg("scores"), pkg("_lib")
-    L = S.bind(lib.lib())
+    L = lib.lib()
     rows = len(y)
     st = torch.full((rows, C + 3), NAN, device=dev)
     st[:, :C] = torch.from_numpy(s).to(dev)

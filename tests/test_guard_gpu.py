@@ -94,8 +94,7 @@ def test_col_sum(dt, rows, cols, ld):
     """qt_col_sum_ws (both stages, write and accumulate) bit for bit; the atomic qt_col_sum inside the 1e-5 that
     tests/test_conv_gpu.py::test_col_sum_ws_is_deterministic holds it to"""
     L, lib = _L()
-    lib.qt_col_sum_workspace_bytes.restype = ctypes.c_size_t
-    nws = lib.qt_col_sum_workspace_bytes(ctypes.c_longlong(rows), cols)
+    nws = lib.qt_col_sum_workspace_bytes(rows, cols)
     assert nws == min(-(-rows // 128), 1024) * cols * 4
     x = torch.randn(rows, ld, generator=torch.Generator().manual_seed(5)).to(dt)
     ref = x[:, :cols].double().sum(0)
@@ -106,11 +105,11 @@ def test_col_sum(dt, rows, cols, ld):
         for acc in (0, 1):
             ws = A.workspace(f"ws{acc}", nws)
             out = A.output(f"out{acc}", (cols,), F32, fill=0) if acc else A.output(f"out{acc}", (cols,), F32)
-            L.check(lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(xd), ctypes.c_longlong(rows), cols, ld, L.ptr(out), acc, L.ptr(ws),
-                                      ctypes.c_size_t(nws), L.stream_ptr()), "qt_col_sum_ws")
+            L.check(lib.qt_col_sum_ws(L.qt_dtype(dt), L.ptr(xd), rows, cols, ld, L.ptr(out), acc, L.ptr(ws),
+                                      nws, L.stream_ptr()), "qt_col_sum_ws")
             outs.append(out)
         atomic = A.output("atomic", (cols,), F32)
-        L.check(lib.qt_col_sum(L.qt_dtype(dt), L.ptr(xd), ctypes.c_longlong(rows), cols, ld, L.ptr(atomic), 0, L.stream_ptr()),
+        L.check(lib.qt_col_sum(L.qt_dtype(dt), L.ptr(xd), rows, cols, ld, L.ptr(atomic), 0, L.stream_ptr()),
                 "qt_col_sum")
         return outs + [atomic]
 
@@ -132,14 +131,13 @@ def test_linear_workspace(M, N, K, with_bias, relu):
     x = torch.randn(M, K, generator=g).to(BF16)
     w = (torch.randn(N, K, generator=g) * 0.05).to(BF16)
     b = torch.randn(N, generator=g) if with_bias else None
-    lib.qt_linear_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.qt_linear_workspace_bytes(M, N, K)
     assert nbytes >= M * N * 4
 
     def case(A):
         xd, wd, bd = A.input("x", x), A.input("w", w), A.input("bias", b)
         ws, y = A.workspace("ws", nbytes), A.output("y", (M, N), BF16)
-        L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), relu, L.ptr(y), M, N, K, L.ptr(ws), ctypes.c_size_t(nbytes),
+        L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), relu, L.ptr(y), M, N, K, L.ptr(ws), nbytes,
                                    L.stream_ptr()), "qt_linear_bf16")
         return y
 
@@ -152,7 +150,7 @@ def test_linear_workspace(M, N, K, with_bias, relu):
 class _LossCase:
     def __init__(self, kind, rows, C, red):
         self.M, self.lib = pkg("loss"), pkg("_lib")
-        self.L = self.M.bind(self.lib.lib())
+        self.L = self.lib.lib()
         self.kind, self.rows, self.C, self.red = kind, rows, C, red
         seed = 7 + rows + C
         self.z = LR.make_logits(rows, C, "x1", seed=seed)
@@ -212,7 +210,7 @@ def test_augment_workspace(name):
     bound of tests/_augment_ref.py"""
     _dev()
     M, Lm = pkg("augment"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     if name == "jitter":
         h, w = AR.SHAPES[0]
         img, p = AR.make_images(24, h, w, 11), AR.jitter_rows()
@@ -228,7 +226,7 @@ def test_augment_workspace(name):
         p = AR.rows([AR.row(deg=a) for a in AR.ANGLES] + [AR.row()])
         kx, ky, norm, contrast = 1, 1, AR.NO_NORM, 0
     N, image = img.shape[0], 3 * h * w
-    need = int(L.qt_augment_workspace_bytes(N, contrast))
+    need = L.qt_augment_workspace_bytes(N, contrast)
     assert (need > 0) == bool(contrast)
 
     def case(A):
@@ -255,9 +253,9 @@ def test_gradcam_map_workspace(B, C, P):
     """qt_gradcam_map: the same bits as on plain buffers (tests/test_gradcam_gpu.py::test_map_edge_cases: reproducible)"""
     _dev()
     G, Lm = pkg("gradcam"), pkg("_lib")
-    L = G.bind(Lm.lib())
+    L = Lm.lib()
     act, grad = GR.make_inputs(B, C, P, "noisy", seed=0)
-    need = int(L.qt_gradcam_workspace_bytes(B, C, P))
+    need = L.qt_gradcam_workspace_bytes(B, C, P)
     assert (need > 0) == (C > 32)
 
     def case(A):
@@ -281,7 +279,7 @@ def test_gradcam_overlay_byte_outputs():
     """qt_gradcam_overlay_u8 writes bytes, which may be 0xFF: payload fills 0xFF and 0x00 give the same overlay and index"""
     _dev()
     G, Lm = pkg("gradcam"), pkg("_lib")
-    L = G.bind(Lm.lib())
+    L = Lm.lib()
     B, H, W = 2, 37, 61
     cam, frames, lut = GR.make_cam(B, 5, 3, seed=9), GR.make_frames(B, H, W, seed=10), G.jet_lut().numpy()
 
@@ -309,7 +307,6 @@ def test_stem_bn_bwd_wgrad_workspace(B):
     L, lib = _L()
     c = Sb.case("grid", B)
     d, coef, image, dw_ref, _ = Sb.sparse_probe(B)
-    lib.qt_stem_bn_bwd_wgrad_workspace_bytes.restype = ctypes.c_size_t
     nws = lib.qt_stem_bn_bwd_wgrad_workspace_bytes(B)
     assert nws == min(B * 56, 256) * 64 * 7 * 32 * 4
     f = lambda t: t.float().contiguous()
@@ -323,7 +320,7 @@ def test_stem_bn_bwd_wgrad_workspace(B):
         dw = A.output("dw", (64, 7, 8, 4), F32, fill=0)    # zeros: include/qtcnn.h has the caller zero dw (dw += ...)
         rc = lib.qt_stem_bn_bwd_wgrad_ws(L.qt_dtype(BF16), L.ptr(t["d"]), L.ptr(t["code"]), L.ptr(t["y"]), L.ptr(t["scale"]),
                                          L.ptr(t["shift"]), L.ptr(t["mean"]), L.ptr(t["invstd"]), L.ptr(t["coef"]), L.ptr(xpad),
-                                         L.ptr(dw), L.ptr(ws), ctypes.c_size_t(nws), B, L.stream_ptr())
+                                         L.ptr(dw), L.ptr(ws), nws, B, L.stream_ptr())
         assert rc == 0, lib.qt_last_error()
         return dw
 
@@ -353,7 +350,6 @@ def _list_tensors(name):
 def _engine_api():
     L, lib = _L()
     eng = pkg("engine")
-    eng._bind_api(lib)
     return L, lib, eng
 
 
@@ -439,9 +435,7 @@ def state_view(gd, name):
     return next(b.t for b in gd.bufs if b.name == name)
 
 
-class _PackItem(ctypes.Structure):   # qt_pack_item
-    _fields_ = [("w", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgrad", ctypes.c_void_p),
-                ("O", ctypes.c_int), ("I", ctypes.c_int), ("k", ctypes.c_int), ("s2", ctypes.c_int)]
+_PackItem = pkg("_abi").PackItem   # qt_pack_item
 
 
 # (O, I, k, stride2_dgrad): a 3x3 stride 1, a 3x3 stride 2 in the 4-slot merged form, a 3x3 stride 2 in the 5-slot form with its
@@ -493,11 +487,6 @@ def test_batched_packers(entry, dt):
     grs = [(torch.randn(O, I, k, k, generator=g) * 0.01) for (O, I, k, _) in PACK_SHAPES]
     coef = torch.tensor([0.375])
     n = len(PACK_SHAPES)
-    lib.qt_pack_weights_batched.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.qt_adam_pack_weights_batched.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                 ctypes.c_void_p]
-    lib.qt_adam_pack_weights_batched_scaled.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     desc = eng.AdamDesc(1e-3, 0.9, 0.999, 1e-8, 1e-4, 1.0, 1)
     gd = Guard(dev)
     items, state, keep = (_PackItem * n)(), (eng.AdamItem * n)(), []

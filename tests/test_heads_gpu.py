@@ -13,7 +13,6 @@ Every case prints max(|err| / bound) and asserts <= 1; outputs are pre-filled wi
 
 Reference behaviour: nn.LSTM, the attention head of AttentionHierarchicalCNN (Quadtree_from scratch/models.py:34-38, 62-89),
 nn.AdaptiveAvgPool2d / nn.AdaptiveAvgPool3d and nn.BatchNorm3d's batch statistics."""
-import ctypes
 
 import pytest
 import torch
@@ -23,7 +22,6 @@ from _util import pkg
 
 pytestmark = pytest.mark.gpu
 
-LL = ctypes.c_longlong
 NAN = float("nan")
 QT_ERR_INVALID_ARG, QT_ERR_UNSUPPORTED = -1, -3
 F32, BF16 = torch.float32, torch.bfloat16
@@ -255,13 +253,12 @@ def test_avgpool_tb_refuses_what_its_siblings_refuse(C, col0, dt):
 def test_bn_stats_per_row_vs_float64(shape, dt):
     dev, L, lib = _env()
     M, C = shape
-    lib.qt_bn_stats_rows.argtypes = [LL, ctypes.c_int]
     rows = lib.qt_bn_stats_rows(M, C)
     assert rows == Hb.bn_stats_rows(M)
     y = Hb.bn_inputs(M, C, dt)
     yd = y.to(dev)
     part = _nan((rows + 1, 2, C), F32, dev)
-    L.check(lib.qt_bn_stats(L.qt_dtype(dt), L.ptr(yd), LL(M), C, L.ptr(part), L.stream_ptr()), "qt_bn_stats")
+    L.check(lib.qt_bn_stats(L.qt_dtype(dt), L.ptr(yd), M, C, L.ptr(part), L.stream_ptr()), "qt_bn_stats")
     part = part.cpu()
     assert _all_nan(part[rows:])
     if M == 262145:
@@ -275,6 +272,6 @@ def test_bn_stats_refuses_channel_counts(C):
     M = 16
     y = torch.randn(M, C).to(dev)
     part = _nan((1, 2, C), F32, dev)
-    st = lib.qt_bn_stats(L.qt_dtype(F32), L.ptr(y), LL(M), C, L.ptr(part), L.stream_ptr())
+    st = lib.qt_bn_stats(L.qt_dtype(F32), L.ptr(y), M, C, L.ptr(part), L.stream_ptr())
     torch.cuda.synchronize()
     assert st == QT_ERR_INVALID_ARG and _all_nan(part)

@@ -25,8 +25,6 @@ def test_image_gradient_entry_points_are_declared_and_exported():
 
 def test_stem_dgrad_refuses_bad_arguments_without_a_device():
     L = _lib()
-    L.qt_stem_dgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                ctypes.c_void_p]
     fake = ctypes.c_void_p(1 << 20)   # never dereferenced: every call below returns before a launch
     assert L.qt_stem_dgrad(1, None, fake, fake, 2, None) == QT_ERR_INVALID_ARG
     assert L.qt_stem_dgrad(1, fake, fake, fake, 0, None) == QT_ERR_INVALID_ARG
@@ -38,7 +36,6 @@ def test_stem_dgrad_refuses_bad_arguments_without_a_device():
 def test_plan_backward_dx_needs_a_recorded_forward():
     eng = pkg("engine")
     L = _lib()
-    eng._bind_api(L)
     desc = eng.PlanDesc(0, 2, 12, 0, 0, 47, 0.5, 1e-5, 0.1, 0, 0)
     h = ctypes.c_void_p()
     assert L.qt_plan_create(ctypes.byref(desc), ctypes.byref(h)) == 0

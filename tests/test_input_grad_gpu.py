@@ -76,8 +76,6 @@ def test_stem_dgrad_kernel_matches_conv2d_input(dt, B):
                                      padding=3)
     dyd, wd = dy.to(dev), w.to(dev)
     dx = torch.full((B, 3, 224, 224), float("nan"), device=dev)
-    L.qt_stem_dgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                ctypes.c_void_p]
     st = L.qt_stem_dgrad(pkg("_lib").qt_dtype(dt), dyd.data_ptr(), wd.data_ptr(), dx.data_ptr(), B,
                          pkg("_lib").stream_ptr())
     assert st == 0, L.qt_last_error()

@@ -140,8 +140,7 @@ def test_new_symbols_are_declared_and_exported():
 
 def test_host_side_argument_checks_need_no_device():
     M = pkg("loss")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     assert L.qt_loss_workspace_bytes(256, 12) == 0 and L.qt_loss_workspace_bytes(257, 12) == 2 * 24
     assert L.qt_loss_workspace_bytes(16, 17) == 0 and L.qt_loss_workspace_bytes(17, 64) == 2 * 24
     assert L.qt_loss_workspace_bytes(4, 65) == 0 and L.qt_loss_workspace_bytes(5, 1024) == 2 * 24

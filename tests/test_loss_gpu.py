@@ -27,7 +27,7 @@ class Op:
     def __init__(self, dev):
         self.M = pkg("loss")
         self.lib = pkg("_lib")
-        self.L = self.M.bind(self.lib.lib())
+        self.L = self.lib.lib()
         self.dev = dev
 
     def run(self, kind, z, y, w, eps, gamma, reduction, gout, ignore_index=R.IGNORE, meter=None, want_pred=True):

@@ -22,7 +22,7 @@ assert STREAM.TILE == R.TILE and STREAM.MAX_WINDOW == 64 and STREAM.HIDDEN_SIZES
 
 
 def _lib():
-    return STREAM.bind(pkg("_lib").lib())
+    return pkg("_lib").lib()
 
 
 def _last_error(L):
@@ -91,7 +91,6 @@ def test_workspace_is_bounded_by_a_constant_times_the_input_products():
             assert ws <= 1 * S * (T - 1 + n) * 4 * H * 4, (H, S, n, T, ws)
     # the plan's: the input products themselves plus the kernel's
     eng = pkg("engine")
-    eng._bind_api(L)
     desc = eng.PlanDesc(1, 64, 12, eng.QT_MODEL_CNN_LSTM, 0, 47, 0.5, 1e-5, 0.1, 4, 256)
     h = P()
     assert L.qt_plan_create(ctypes.byref(desc), ctypes.byref(h)) == 0
@@ -146,7 +145,6 @@ def test_lstm_stream_stage_refusals():
 
 def _plan(L, kind, batch=8):
     eng = pkg("engine")
-    eng._bind_api(L)
     desc = eng.PlanDesc(1, batch, 12, kind, 0, 47, 0.5, 1e-5, 0.1, 4, 256)
     h = P()
     assert L.qt_plan_create(ctypes.byref(desc), ctypes.byref(h)) == 0

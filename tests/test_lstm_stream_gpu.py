@@ -10,7 +10,6 @@ their errors are of one size; 4x covers the spread of a maximum over a small sam
 exactly 0; a wrong gate, row or weight index shows at 1e-2 or more.  One stream of 3 x 35 frames per (H, T, regime) is
 computed once by both references; a case (S, n, seen) is a slice of it.
 """
-import ctypes
 import functools
 
 import numpy as np
@@ -35,7 +34,7 @@ def _dev():
 
 def _lib():
     L = pkg("_lib")
-    return L, pkg("sequence_stream").bind(L.lib())
+    return L, L.lib()
 
 
 def _n_values(T):
@@ -109,7 +108,6 @@ def _world(H, T, regime):
     """inputs, weights on the device and both references of one (H, T, regime), computed once"""
     dev = torch.device("cuda:0")
     L, lib = _lib()
-    lib.qt_lstm_forward.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
     w = R.weights(H)
     rows = R.stream_rows(H, 3, FRAMES, regime)
     W = _Weights(w, dev)

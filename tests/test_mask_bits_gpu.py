@@ -45,9 +45,9 @@ def test_bn_act_mask_writes_the_sign_of_its_output(dt, cfg):
     bits = torch.full((M, C // 8), 0xAA, dtype=torch.uint8, device=dev)
     st = L.stream_ptr()
     L.check(lib.qt_bn_act(L.qt_dtype(dt), L.ptr(y), L.ptr(sc), L.ptr(sh), L.ptr(res), None, None, 1, L.ptr(out0),
-                          ctypes.c_longlong(M), C, st), "qt_bn_act")
+                          M, C, st), "qt_bn_act")
     L.check(lib.qt_bn_act_mask(L.qt_dtype(dt), L.ptr(y), L.ptr(sc), L.ptr(sh), L.ptr(res), None, None, 1, L.ptr(out1),
-                               L.ptr(bits), ctypes.c_longlong(M), C, st), "qt_bn_act_mask")
+                               L.ptr(bits), M, C, st), "qt_bn_act_mask")
     torch.cuda.synchronize()
     assert torch.equal(out0, out1)
     # a positive f32 value never rounds to a bf16 zero (same exponent range), so the bit is the sign of the stored value

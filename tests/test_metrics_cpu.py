@@ -144,7 +144,7 @@ def test_new_symbols_are_declared_and_exported():
 
 def test_size_queries():
     M = pkg("metrics")
-    L = M.bind(pkg("_lib").lib())
+    L = pkg("_lib").lib()
     for C in (1, 2, 12, 64, 65, 1024):
         assert L.qt_metrics_state_bytes(C) == 8 * (C * C + 4)
         assert L.qt_metrics_report_bytes(C) == 8 * (4 * C + 12)
@@ -154,8 +154,7 @@ def test_size_queries():
 
 def test_host_side_argument_checks_need_no_device():
     M = pkg("metrics")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     z, p_in, y, st, pr, cf, po, rp = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000, 0x70000, 0x80000   # never dereferenced
     good = M.MetricsDesc(0, -100)
     base = dict(desc=good, logits=z, ld=12, pred_in=None, labels=y, rows=4, C=12, state=st, probs=pr, ld_probs=12, conf=cf,

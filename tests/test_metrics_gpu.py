@@ -29,7 +29,7 @@ class Op:
     def __init__(self, dev):
         self.M = pkg("metrics")
         self.lib = pkg("_lib")
-        self.L = self.M.bind(self.lib.lib())
+        self.L = self.lib.lib()
         self.dev = dev
 
     # vectors are guarded as [n][1]: a band is 256 payload rows, and the whole vector is not one row
@@ -97,7 +97,7 @@ class Op:
     def loss_pred(self, zt, y):
         """qt_loss_forward's `pred` on the same device buffer"""
         LM = pkg("loss")
-        L = LM.bind(self.lib.lib())
+        L = self.lib.lib()
         rows, C = zt.shape
         dev = self.dev
         yd = torch.from_numpy(np.asarray(y, np.int64)).to(dev)

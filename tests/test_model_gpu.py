@@ -353,7 +353,6 @@ def test_adam_multi_kernel_matches_torch_single_tensor_adam():
     mine = [p.clone().to(dev) for p in ps]
     ms = [torch.zeros_like(p) for p in mine]
     vs = [torch.zeros_like(p) for p in mine]
-    lib.qt_adam_multi.argtypes = [ctypes.POINTER(eng.AdamItem), ctypes.c_int, ctypes.POINTER(eng.AdamDesc), ctypes.c_void_p]
     for step in range(1, 4):
         grads = [torch.randn(s, generator=g) for s in shapes]
         for r, gr in zip(ref, grads):

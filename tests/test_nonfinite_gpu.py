@@ -24,8 +24,6 @@ from test_gemm_small_gpu import GemmSmallDesc
 
 pytestmark = pytest.mark.gpu
 
-LL = ctypes.c_longlong
-CF = ctypes.c_float
 SENTINEL = -1.5e38          # representable in bf16; no raw sum and no ReLU output comes near it
 LOGIT_TOL = {F32: 1e-3, BF: 4e-2}
 
@@ -315,12 +313,11 @@ def test_linear_relu_nonfinite():
     clean = c["clean"]
     N.conditions(c["raw_c"], c["pre_c"], c["act"], c["images"])
     M, Nn, K = c["row"]["cfg"]
-    lib.qt_linear_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.qt_linear_workspace_bytes(M, Nn, K)
     ws = torch.full((max(nbytes, 1),), 0xFF, dtype=torch.uint8, device=dev)
     y = _out((M, Nn), BF, dev)
     xd, wd, bd = c["x"].to(BF).to(dev), clean["w"].to(BF).to(dev), clean["bias"].float().to(dev)
-    L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), 1, L.ptr(y), M, Nn, K, L.ptr(ws), ctypes.c_size_t(nbytes),
+    L.check(lib.qt_linear_bf16(L.ptr(xd), L.ptr(wd), L.ptr(bd), 1, L.ptr(y), M, Nn, K, L.ptr(ws), nbytes,
                                L.stream_ptr()), "qt_linear_bf16")
     torch.cuda.synchronize()
     _agree(y, c["act"], BF, "qt_linear_bf16 relu=1")
@@ -368,8 +365,8 @@ def test_bn_act_nonfinite(dt, residual):
         bits = torch.zeros((M, C // 8), dtype=torch.uint8, device=dev)
         args = (L.qt_dtype(dt), L.ptr(y), L.ptr(sc), L.ptr(sh), L.ptr(res) if residual != "none" else None,
                 L.ptr(rs), L.ptr(rb), relu)
-        L.check(lib.qt_bn_act(*args, L.ptr(out), LL(M), C, L.stream_ptr()), "qt_bn_act")
-        L.check(lib.qt_bn_act_mask(*args, L.ptr(out1), L.ptr(bits), LL(M), C, L.stream_ptr()), "qt_bn_act_mask")
+        L.check(lib.qt_bn_act(*args, L.ptr(out), M, C, L.stream_ptr()), "qt_bn_act")
+        L.check(lib.qt_bn_act_mask(*args, L.ptr(out1), L.ptr(bits), M, C, L.stream_ptr()), "qt_bn_act_mask")
         torch.cuda.synchronize()
         _agree(out, ref, dt, ("qt_bn_act", residual, relu))
         _agree(out1, ref, dt, ("qt_bn_act_mask", residual, relu))
@@ -419,8 +416,8 @@ def test_bn_finalize_nonfinite():
     rm, rv = c["rmean"].to(dev), c["rvar"].to(dev)
     gamma, beta = c["gamma"].to(dev), c["beta"].to(dev)
     nbt = torch.zeros(1, dtype=torch.int64, device=dev)
-    L.check(lib.qt_bn_finalize(L.ptr(partial), rows, C, LL(c["count"]), L.ptr(gamma), L.ptr(beta),
-                               L.ptr(rm), L.ptr(rv), L.ptr(nbt), CF(0.1), CF(1e-5), L.ptr(outs["mean"]), L.ptr(outs["invstd"]),
+    L.check(lib.qt_bn_finalize(L.ptr(partial), rows, C, c["count"], L.ptr(gamma), L.ptr(beta),
+                               L.ptr(rm), L.ptr(rv), L.ptr(nbt), 0.1, 1e-5, L.ptr(outs["mean"]), L.ptr(outs["invstd"]),
                                L.ptr(outs["scale"]), L.ptr(outs["shift"]), L.stream_ptr()), "qt_bn_finalize")
     torch.cuda.synchronize()
     outs["running_mean"], outs["running_var"] = rm, rv

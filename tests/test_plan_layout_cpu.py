@@ -41,7 +41,6 @@ def buffer_names(num_convs, attention):
 def plan_layout(L):
     """{"<model>/<dtype>": {"tensors": [[name, kind, [dims]]...], "workspace_bytes": n, "buffers": {name: offset}}}"""
     eng = pkg("engine")
-    eng._bind_api(L)
     out = {}
     for mname, model in MODELS:
         for dname, dtype in DTYPES:
@@ -83,7 +82,6 @@ def test_plan_graph_and_workspace_layout_match_the_recorded_ones():
 # ---- the region table -----------------------------------------------------------------------------------------------------
 def _create(L, model, dtype, batch):
     eng = pkg("engine")
-    eng._bind_api(L)
     seq = {256: 16, 18: 3}[batch] if model == 3 else 0      # CnnLstm: whole sequences
     desc = eng.PlanDesc(dtype, batch, 12, model, 0, 47, 0.5, 1e-5, 0.1, seq, 256 if model == 3 else 0)
     h = ctypes.c_void_p()
@@ -166,7 +164,6 @@ def test_region_table_with_and_without_the_guard_gap(mname, model, dname, dtype,
 
 def test_guard_gap_setter_takes_multiples_of_256_and_resets():
     L = _lib()
-    pkg("engine")._bind_api(L)
     assert L.qt_set_plan_guard_gap(100) != 0 and L.qt_set_plan_guard_gap(257) != 0
     with plan_guard_gap(GAP_BYTES):
         h = _create(L, 0, 1, 18)

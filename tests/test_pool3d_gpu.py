@@ -14,7 +14,6 @@ which are read once per process and have no setter.
 
 Reference behaviour: BatchNorm3d -> ReLU -> MaxPool3d of a conv block of the reference's Quadtree3DCNN (3dcnn/models.py) and
 their autograd; nn.Conv3d's weight layout."""
-import ctypes
 import math
 
 import pytest
@@ -27,7 +26,6 @@ pytestmark = pytest.mark.gpu
 
 F32, BF16 = torch.float32, torch.bfloat16
 NAN = float("nan")
-LL = ctypes.c_longlong
 QT_ERR_INVALID_ARG = -1
 KINDS = ["grid", "random"]
 POOL_RUNS = [("c1", 1, "f32"), ("c1", 1, "bf16"), ("c1", 2, "f32"), ("c1", 2, "bf16"), ("c2", 1, "bf16"), ("c2", 2, "f32"),
@@ -86,7 +84,7 @@ def _apply(L, lib, t, c, dev, Cy=None, Cd=None, light_min=None):
     Cy, Cd = C if Cy is None else Cy, C if Cd is None else Cd
     dy = _Out((T, B, H, W, Cd), c["dt"], dev)
     if light_min is not None:
-        lib.qt_set_pool3d_apply_light_min(LL(light_min))
+        lib.qt_set_pool3d_apply_light_min(light_min)
     try:
         L.check(lib.qt_pool3d_bn_bwd_apply(L.qt_dtype(c["dt"]), L.ptr(t["d"]), L.ptr(t["code"]), L.ptr(t["pooled"]), L.ptr(t["y"]),
                                            L.ptr(t["mean"]), L.ptr(t["invstd"]), L.ptr(t["coef"]), L.ptr(dy.t), T, B, H, W, C, Cy, Cd,
@@ -94,7 +92,7 @@ def _apply(L, lib, t, c, dev, Cy=None, Cd=None, light_min=None):
         torch.cuda.synchronize()
     finally:
         if light_min is not None:
-            lib.qt_set_pool3d_apply_light_min(LL(0))
+            lib.qt_set_pool3d_apply_light_min(0)
     return dy.cpu()
 
 
@@ -209,14 +207,14 @@ def test_bn_backward_sums_from_the_pooled_side_vs_float64(name, pt, dtn):
     T, B, H, W, C = c["shape"]
     q, st = L.qt_dtype(c["dt"]), L.stream_ptr()
     cells, M = c["d"].numel() // C, T * B * H * W
-    rows = lib.qt_bn_bwd_partial_rows(LL(cells), C)
+    rows = lib.qt_bn_bwd_partial_rows(cells, C)
     assert rows > 0
     part = _Out((lib.qt_stats_capacity_rows(rows), 2, C), F32, dev)
     L.check(lib.qt_bn_bwd_reduce(q, L.ptr(t["d"]), L.ptr(t["pooled"]), L.ptr(t["ymax"]), L.ptr(t["mean"]), L.ptr(t["invstd"]),
-                                 L.ptr(part.t), LL(cells), C, st), "qt_bn_bwd_reduce (pooled side)")
+                                 L.ptr(part.t), cells, C, st), "qt_bn_bwd_reduce (pooled side)")
     gamma = c["gamma"].float().to(dev)
     dgamma, dbeta, coef = _Out((C,), F32, dev), _Out((C,), F32, dev), _Out((3, C), F32, dev)
-    L.check(lib.qt_bn_bwd_finalize(L.ptr(part.t), rows, C, LL(M), L.ptr(gamma), L.ptr(t["invstd"]), L.ptr(dgamma.t), L.ptr(dbeta.t),
+    L.check(lib.qt_bn_bwd_finalize(L.ptr(part.t), rows, C, M, L.ptr(gamma), L.ptr(t["invstd"]), L.ptr(dgamma.t), L.ptr(dbeta.t),
                                    0, L.ptr(coef.t), st), "qt_bn_bwd_finalize")
     torch.cuda.synchronize()
     p = part.cpu()

@@ -126,8 +126,7 @@ def test_new_symbols_are_declared_and_exported():
 def test_host_side_argument_checks_need_no_device():
     """every refusal below comes before the first device call: the pointers are never dereferenced"""
     M = pkg("pose")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     lm, det, raw, lab, mean, std, out = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000, 0x70000
 
     def call(desc, landmarks=lm, detected=None, rawv=None, labels=None, means=None, stds=None, dst=out):

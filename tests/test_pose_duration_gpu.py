@@ -28,7 +28,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def chain(S, C):
@@ -70,7 +70,7 @@ def run(dev, probs, sc, tr, dur, init=None, dur_open=None, lengths=None, ld=None
     d_start = G.output("start", (B, T), torch.int64) if want_start else None
     d_score = G.output("score", (B,), torch.int64) if want_score else None
     desc = M.PoseDurationDesc(B, T, C, S, D)
-    need = int(L.qt_pose_duration_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_workspace_bytes(ctypes.byref(desc))
     assert need == (B * T * S * 2 + 7) // 8 * 8
     d_ws = G.workspace("workspace", need)
     Lm.check(L.qt_pose_duration_decode(ctypes.byref(desc), Lm.ptr(d_probs), ld, Lm.ptr(d_sc), Lm.ptr(d_tr), Lm.ptr(d_init),

@@ -149,8 +149,7 @@ def test_the_live_path_with_durations_beats_the_plain_live_path():
 # ---- the library -------------------------------------------------------------------------------------------------------------------
 def _lib():
     M = pkg("pose_order")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     return M, L
 
 

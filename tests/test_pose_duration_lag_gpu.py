@@ -36,7 +36,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def chain(S, C):
@@ -103,7 +103,7 @@ def run(dev, probs, tab, lag, seen=0, flush=True, carry=None, pad=0, want=(True,
     d_dur, d_open = gd.input("dur", i32(dur)), gd.input("dur_open", i32(open_))
     desc = M.PoseDurationLagDesc(B, n, C, S, D, lag, int(flush), seen)
     stride = DL.carry_stride(S, D, lag)
-    assert int(L.qt_pose_duration_lag_carry_bytes(ctypes.byref(desc))) == B * stride
+    assert L.qt_pose_duration_lag_carry_bytes(ctypes.byref(desc)) == B * stride
     d_cin = None
     if seen:
         assert carry.shape == (B, stride)
@@ -112,7 +112,7 @@ def run(dev, probs, tab, lag, seen=0, flush=True, carry=None, pad=0, want=(True,
     outs = [gd.output("lag_path", (B, count), torch.int64)]
     outs += [gd.output(name, (B, m), torch.int64) if w else None
              for name, m, w in (("lag_start", count, want[0]), ("filtered", n, want[1]), ("score", n, want[2]))]
-    need = int(L.qt_pose_duration_lag_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_lag_workspace_bytes(ctypes.byref(desc))
     assert need == DL.workspace_bytes(B, n, S)
     d_ws = gd.workspace("workspace", need) if need else None
     at = lambda t, m: Lm.ptr(t) if t is not None and m else None
@@ -165,7 +165,7 @@ def whole_video(dev, probs, tab, lengths):
     path, start = (torch.empty((B, T), dtype=torch.int64, device=dev) for _ in range(2))
     score = torch.empty(B, dtype=torch.int64, device=dev)
     desc = M.PoseDurationDesc(B, T, C, S, D)
-    need = int(L.qt_pose_duration_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_workspace_bytes(ctypes.byref(desc))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     Lm.check(L.qt_pose_duration_decode(ctypes.byref(desc), Lm.ptr(d[0]), C, *[Lm.ptr(t) for t in d[1:]], Lm.ptr(path),
                                        Lm.ptr(start), Lm.ptr(score), Lm.ptr(ws), need, Lm.stream_ptr()), "qt_pose_duration_decode")
@@ -286,8 +286,8 @@ def plain_lag(dev, probs, sc, tr, init, lag):
     desc = M.PoseLagDesc(B, T, C, S, lag, 1, 0)
     up = lambda a: None if a is None else i32(a).to(dev)
     d_probs, d_sc, d_tr, d_init = torch.from_numpy(np.array(probs)).to(dev), up(sc), up(tr), up(init)
-    cout = torch.empty(int(L.qt_pose_lag_decode_carry_bytes(ctypes.byref(desc))), dtype=torch.uint8, device=dev)
-    need = int(L.qt_pose_lag_decode_workspace_bytes(ctypes.byref(desc)))
+    cout = torch.empty(L.qt_pose_lag_decode_carry_bytes(ctypes.byref(desc)), dtype=torch.uint8, device=dev)
+    need = L.qt_pose_lag_decode_workspace_bytes(ctypes.byref(desc))
     ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     path, filt = (torch.empty((B, T), dtype=torch.int64, device=dev) for _ in range(2))
     Lm.check(L.qt_pose_lag_decode(ctypes.byref(desc), Lm.ptr(d_probs), C, Lm.ptr(d_sc), Lm.ptr(d_tr), Lm.ptr(d_init), None,

@@ -160,8 +160,7 @@ def test_the_lagged_posterior_follows_the_lagged_path(seed):
 # ---- the library -------------------------------------------------------------------------------------------------------------------
 def _lib():
     M = pkg("pose_order")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     return M, L
 
 

@@ -42,7 +42,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def i32(a):
@@ -68,7 +68,7 @@ def run(dev, probs, tab, lag, seen=0, flush=True, carry=None, pad=0, want=ALL):
     d_dur, d_open = gd.input("dur", i32(dur)), gd.input("dur_open", i32(open_))
     desc = M.PoseDurationLagDesc(B, n, C, S, D, lag, int(flush), seen)
     stride = LS.carry_stride(S, D, lag)
-    assert int(L.qt_pose_duration_lag_smooth_carry_bytes(ctypes.byref(desc))) == B * stride
+    assert L.qt_pose_duration_lag_smooth_carry_bytes(ctypes.byref(desc)) == B * stride
     d_cin = None
     if seen:
         assert carry.shape == (B, stride)
@@ -80,7 +80,7 @@ def run(dev, probs, tab, lag, seen=0, flush=True, carry=None, pad=0, want=ALL):
                                         ("lagged_begin", (B, count, S), torch.float32, want[1]),
                                         ("filtered", (B, n, S), torch.float32, want[2]),
                                         ("log2_evidence", (B, n), torch.float64, want[3]))]
-    need = int(L.qt_pose_duration_lag_smooth_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_lag_smooth_workspace_bytes(ctypes.byref(desc))
     assert need == LS.workspace_bytes(B, n, S)
     d_ws = gd.workspace("workspace", need) if need else None
     at = lambda t, m: Lm.ptr(t) if t is not None and m else None
@@ -121,7 +121,7 @@ def whole_video(dev, probs, tab, lengths):
     cls = torch.empty((B, T, C), dtype=torch.float32, device=dev)
     ev = torch.empty(B, dtype=torch.float64, device=dev)
     desc = M.PoseDurationDesc(B, T, C, S, D)
-    need = int(L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     Lm.check(L.qt_pose_duration_posterior(ctypes.byref(desc), Lm.ptr(d[0]), C, *[Lm.ptr(t) for t in d[1:]], Lm.ptr(post),
                                           Lm.ptr(cls), Lm.ptr(begin), Lm.ptr(ev), None, Lm.ptr(ws), need, Lm.stream_ptr()),

@@ -33,7 +33,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def chain(S, C):
@@ -77,7 +77,7 @@ def run(dev, probs, sc, tr, dur, init=None, dur_open=None, lengths=None, ld=None
     if counts is not None:
         d_counts.copy_(torch.from_numpy(np.ascontiguousarray(counts, np.float64)))
     desc = M.PoseDurationDesc(B, T, C, S, D)
-    need = int(L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc))
     assert need == 8 * (2 * B * T * S + B * S * D)
     d_ws = G.workspace("workspace", need)
     Lm.check(L.qt_pose_duration_posterior(ctypes.byref(desc), Lm.ptr(d_probs), ld, Lm.ptr(d_sc), Lm.ptr(d_tr), Lm.ptr(d_init),

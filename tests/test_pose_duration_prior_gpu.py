@@ -37,7 +37,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def chain(S, C):
@@ -92,7 +92,7 @@ def run(dev, probs, sc, tr, dur, init=None, dur_open=None, lengths=None, ld=None
     d_dur, d_open, d_len = G.input("dur", _i32(dur)), G.input("dur_open", _i32(dur_open)), G.input("lengths", _i32(lengths))
     acc = _accumulators(G, S, D, before, start_counts)
     desc = M.PoseDurationDesc(B, T, C, S, D)
-    need = int(L.qt_pose_duration_prior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_prior_workspace_bytes(ctypes.byref(desc))
     assert need == 8 * (2 * B * T * S + B * (S * S + S + S * D + 1))
     d_ws = G.workspace("workspace", need)
     Lm.check(L.qt_pose_duration_prior_expect(ctypes.byref(desc), Lm.ptr(d_probs), ld, Lm.ptr(d_sc), Lm.ptr(d_tr), Lm.ptr(d_init),
@@ -113,7 +113,7 @@ def run_posterior(dev, probs, sc, tr, dur, init=None, dur_open=None, lengths=Non
     ev = torch.empty(B, dtype=torch.float64, device=dev)
     counts = torch.zeros(S, D, dtype=torch.float64, device=dev)
     desc = M.PoseDurationDesc(B, T, C, S, D)
-    need = int(L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_posterior_workspace_bytes(ctypes.byref(desc))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     Lm.check(L.qt_pose_duration_posterior(ctypes.byref(desc), Lm.ptr(d_probs), C, *[Lm.ptr(t) for t in tabs], None, None, None,
                                           Lm.ptr(ev), Lm.ptr(counts), Lm.ptr(ws), need, Lm.stream_ptr()),
@@ -241,7 +241,7 @@ def run_count(dev, path, S, D, start=None, lengths=None, ld=None, before=None):
     d_path, d_start, d_len = G.input("path", padded(path)), G.input("start", padded(start)), G.input("lengths", _i32(lengths))
     acc = _accumulators(G, S, D, before)
     desc = M.PoseDurationDesc(B, T, 1, S, D)
-    need = int(L.qt_pose_duration_prior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_duration_prior_workspace_bytes(ctypes.byref(desc))
     d_ws = G.workspace("workspace", need)
     Lm.check(L.qt_pose_duration_prior_count_paths(ctypes.byref(desc), Lm.ptr(d_path), Lm.ptr(d_start), ld, Lm.ptr(d_len),
                                                   *[Lm.ptr(t) for t in acc], Lm.ptr(d_ws), need, Lm.stream_ptr()),

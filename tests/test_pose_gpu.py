@@ -77,7 +77,7 @@ def run(dev, rows, mode=R.RAW, lm=None, det=None, raw=None, labels=None, means=N
     """qt_pose_features through ctypes.  The output starts `shift` floats into its buffer (shift 1, 2, 3: a head of 3, 2, 1
     single floats) between poisoned floats that must stay as they are; the inputs must not be written."""
     M, Lm = pkg("pose"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     t = lambda a: None if a is None else torch.from_numpy(np.array(a)).to(dev)      # (a copy: the shared arrays are read-only)
     d_lm, d_det, d_lab, d_mean, d_std = t(lm), t(det), t(labels), t(means), t(stds)
     n = rows * 47

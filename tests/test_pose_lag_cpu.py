@@ -121,8 +121,7 @@ def test_the_emitted_span():
 
 def _lib():
     M = pkg("pose_order")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     return M, L
 
 

@@ -41,7 +41,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 class route:

@@ -27,7 +27,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def prior(S, C=None):
@@ -85,7 +85,7 @@ def run(dev, probs, sc, tr, init=None, carry=None, ld=None, want_filtered=True, 
     d_filt = G.output("filtered", (B, T), torch.int64) if want_filtered else None
     d_em = G.output("emissions", (B, T, S), torch.int32) if want_emissions else None
     desc = M.PoseOrderDesc(B, T, C, S)
-    need = int(L.qt_pose_order_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_order_workspace_bytes(ctypes.byref(desc))
     assert (need == 0) == (T <= TILE), (T, need)
     d_ws = G.workspace("workspace", need) if need else None
     Lm.check(L.qt_pose_order_decode(ctypes.byref(desc), Lm.ptr(d_probs), ld, Lm.ptr(d_sc), Lm.ptr(d_tr), Lm.ptr(d_init),

@@ -121,8 +121,7 @@ def test_new_symbols_are_declared_and_exported():
 
 def _lib():
     M = pkg("pose_order")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     return M, L
 
 

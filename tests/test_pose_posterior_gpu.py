@@ -32,7 +32,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("pose_order"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def classes_for(S, C):
@@ -102,7 +102,7 @@ def run(dev, probs, sc, tr, init=None, carry=None, ld=None, optional=True):
     d_cls = G.output("class_posterior", (B, T, C), torch.float32) if optional else None
     d_ev = G.output("log2_evidence", (B,), torch.float64) if optional else None
     desc = M.PoseOrderDesc(B, T, C, S)
-    need = int(L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_posterior_workspace_bytes(ctypes.byref(desc))
     assert (need == 0) == (T <= TILE), (T, need)
     d_ws = G.workspace("workspace", need) if need else None
     Lm.check(L.qt_pose_posterior(ctypes.byref(desc), Lm.ptr(d_probs), ld, Lm.ptr(d_sc), Lm.ptr(d_tr), Lm.ptr(d_init),

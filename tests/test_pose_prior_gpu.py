@@ -67,7 +67,7 @@ def run(dev, probs, sc, tr, init=None, ld=None, into=None):
         for d, h in zip(acc, into):
             d.copy_(torch.from_numpy(np.ascontiguousarray(h, np.float64)))
     desc = M.PoseOrderDesc(B, T, C, S)
-    need = int(L.qt_pose_prior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_prior_workspace_bytes(ctypes.byref(desc))
     assert need > 0
     d_ws = G.workspace("workspace", need)
     Lm.check(L.qt_pose_prior_expect(ctypes.byref(desc), Lm.ptr(d_probs), ld, Lm.ptr(d_sc), Lm.ptr(d_tr), Lm.ptr(d_init),
@@ -175,7 +175,7 @@ def count(dev, path, S, into=None):
         for d, h in zip(acc, into):
             d.copy_(torch.from_numpy(np.ascontiguousarray(h, np.float64)))
     desc = M.PoseOrderDesc(B, T, 1, S)
-    need = int(L.qt_pose_prior_workspace_bytes(ctypes.byref(desc)))
+    need = L.qt_pose_prior_workspace_bytes(ctypes.byref(desc))
     d_ws = G.workspace("workspace", need)
     Lm.check(L.qt_pose_prior_count_paths(ctypes.byref(desc), Lm.ptr(d_path), Lm.ptr(acc[0]), Lm.ptr(acc[1]), Lm.ptr(acc[2]),
                                          Lm.ptr(d_ws), need, Lm.stream_ptr()), "qt_pose_prior_count_paths")

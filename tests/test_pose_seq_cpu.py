@@ -227,8 +227,7 @@ def test_new_symbol_is_declared_and_exported():
 def test_host_side_argument_checks_need_no_device():
     """every refusal below comes before the first device call: the pointers are never dereferenced"""
     M = pkg("pose_sequence")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     lm, det, sz, hin, cin, hout, cout, out = (0x10000 * k for k in range(1, 9))
 
     def call(desc, landmarks=lm, detected=det, sizes=None, hist_in=None, count_in=None, hist_out=None, count_out=None, dst=out):

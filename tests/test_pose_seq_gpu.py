@@ -48,7 +48,7 @@ def run(dev, lm, det=None, size=(640, 480), sizes=None, mode=S.RAW, hist=None, c
     not be written, and in mode zero every output element must have been written.  Returns (out [B,T,443], history or
     None)."""
     M, Lm = pkg("pose_sequence"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     B, T = lm.shape[:2]
     G = Guard(dev)
     t = lambda name, a, dt=None: None if a is None else G.input(name, torch.from_numpy(np.array(a, dtype=dt)))

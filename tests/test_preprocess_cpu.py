@@ -114,7 +114,7 @@ def _desc(M, **kw):
 def test_descriptor_validation_needs_no_device():
     """every refusal comes with a message and before any HIP call: the pointers are never dereferenced"""
     M, Lm = pkg("preprocess"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     fake = ctypes.c_void_p(4096)
     stride = 3 * 24 * 24
 

@@ -24,7 +24,7 @@ def run(dev, frames, boxes, flips, hw, bgr=False, dst_pad=0, check=True):
     """qt_preprocess_u8 through ctypes on `frames` (a uint8 [N,H,W,3] CPU view with any row / image stride, copied to the
     device with its padding); the destination has dst_pad poisoned floats after every image.  Returns the CPU result."""
     M, Lm = pkg("preprocess"), pkg("_lib")
-    L = M.bind(Lm.lib())
+    L = Lm.lib()
     N, H, W, _ = frames.shape
     h, w = hw
     ims, rs = frames.stride(0), frames.stride(1)

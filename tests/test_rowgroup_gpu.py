@@ -41,7 +41,7 @@ def run(C):
     dev = _dev()
     Lm = pkg("_lib")
     ML, MM, MT = pkg("loss"), pkg("metrics"), pkg("timeline")
-    L = MT.bind(MM.bind(ML.bind(Lm.lib())))
+    L = Lm.lib()
     z = RR.make_logits(ROWS, C, seed=C)
     labels = np.random.default_rng(C).integers(0, C, ROWS).astype(np.int64)
     d_z, d_y = torch.from_numpy(z).to(dev), torch.from_numpy(labels).to(dev)

@@ -156,7 +156,7 @@ def test_new_symbols_are_declared_and_exported():
 
 def test_size_queries():
     S = pkg("scores")
-    L = S.bind(pkg("_lib").lib())
+    L = pkg("_lib").lib()
     for C in (1, 2, 12, 64):
         for bits in (4, 12, 14):
             for M in (1, 15, 64):
@@ -170,8 +170,7 @@ def test_size_queries():
 
 def test_host_side_argument_checks_need_no_device():
     S = pkg("scores")
-    L = S.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     z, y, st, rp, cv = 0x10000, 0x30000, 0x40000, 0x80000, 0x90000   # never dereferenced
 
     def desc(dtype=0, kind=0, bits=12, cal_bins=15, route=0, ignore=-100):

@@ -48,7 +48,7 @@ class Op:
     def __init__(self, dev):
         self.S = pkg("scores")
         self.lib = pkg("_lib")
-        self.L = self.S.bind(self.lib.lib())
+        self.L = self.lib.lib()
         self.dev = dev
 
     # vectors are guarded as [n][1]: a band is 256 payload rows, and the whole vector is not one row

@@ -29,7 +29,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("segments"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 def _poisoned(values, C, lengths, pad):

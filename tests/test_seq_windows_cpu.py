@@ -153,8 +153,7 @@ def test_new_symbols_are_declared_and_exported():
 
 def _lib():
     M = pkg("sequence_windows")
-    L = M.bind(pkg("_lib").lib())
-    L.qt_last_error.restype = ctypes.c_char_p
+    L = pkg("_lib").lib()
     return M, L
 
 

@@ -34,7 +34,7 @@ def fixture():
 
 def _api():
     M, Lm = pkg("sequence_windows"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 # ---- the plan -------------------------------------------------------------------------------------------------------------------

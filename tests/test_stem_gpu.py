@@ -81,7 +81,7 @@ def test_stem_pool_and_fused_backward(dt, tol):
         dgam = torch.empty(C, **f32)
         dbet = torch.empty(C, **f32)
         coef = torch.empty(3, C, **f32)
-        L.check(lib.qt_bn_bwd_finalize(L.ptr(partial), rows, C, ctypes.c_longlong(M), L.ptr(gam), L.ptr(isd), L.ptr(dgam),
+        L.check(lib.qt_bn_bwd_finalize(L.ptr(partial), rows, C, M, L.ptr(gam), L.ptr(isd), L.ptr(dgam),
                                        L.ptr(dbet), 0, L.ptr(coef), st), "qt_bn_bwd_finalize")
         return dgam, dbet, coef
 
@@ -112,7 +112,7 @@ def test_stem_pool_and_fused_backward(dt, tol):
             "qt_stem_pool_bwd")
     dy3 = torch.empty_like(dy)
     L.check(lib.qt_bn_bwd_apply(qdt, L.ptr(gfull), None, L.ptr(yd), L.ptr(mu), L.ptr(isd), L.ptr(coef), L.ptr(dy3), None,
-                                ctypes.c_longlong(M), C, st), "qt_bn_bwd_apply")
+                                M, C, st), "qt_bn_bwd_apply")
     torch.cuda.synchronize()
     ref = yr.grad
     assert rel_err(dy.float().cpu().permute(0, 3, 1, 2), ref) <= tol
@@ -132,7 +132,6 @@ def test_stem_pool_and_fused_backward(dt, tol):
     dw_ref = torch.zeros(64, 7, 32, **f32)
     L.check(lib.qt_conv2d_wgrad(ctypes.byref(d), L.ptr(dy), L.ptr(xpad), L.ptr(dw_ref), st), "qt_conv2d_wgrad")
     # (partial filters per workgroup in a workspace, summed in workgroup order: the same sums, the same bits on every run)
-    lib.qt_stem_bn_bwd_wgrad_workspace_bytes.restype = ctypes.c_size_t
     nws = lib.qt_stem_bn_bwd_wgrad_workspace_bytes(B)
     assert nws == min(B * 56, 256) * 64 * 7 * 32 * 4
 
@@ -140,7 +139,7 @@ def test_stem_pool_and_fused_backward(dt, tol):
         ws = torch.full((nws // 4,), float("nan"), **f32)
         dw = torch.zeros(64, 7, 32, **f32)
         rc = lib.qt_stem_bn_bwd_wgrad_ws(qdt, L.ptr(dpd), L.ptr(argmax), L.ptr(yd), L.ptr(sc), L.ptr(sh), L.ptr(mu), L.ptr(isd),
-                                         L.ptr(coef), L.ptr(xpad), L.ptr(dw), L.ptr(ws), ctypes.c_size_t(ws_bytes), B, st)
+                                         L.ptr(coef), L.ptr(xpad), L.ptr(dw), L.ptr(ws), ws_bytes, B, st)
         torch.cuda.synchronize()
         return rc, dw.cpu()
 

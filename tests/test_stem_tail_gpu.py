@@ -179,14 +179,13 @@ def test_stem_bn_bwd_apply_vs_float64(kind, B, dt):
 # the one-launch stem backward (bf16)
 # ----------------------------------------------------------------------------------------------------------------------
 def _fused(L, lib, t, xpad, B, dev, short=0, dt=BF16):
-    lib.qt_stem_bn_bwd_wgrad_workspace_bytes.restype = ctypes.c_size_t
     nws = lib.qt_stem_bn_bwd_wgrad_workspace_bytes(B)
     assert nws == min(B * 56, 256) * 64 * 7 * 32 * 4
     ws = _nan((nws // 4,), F32, dev)
     dw = torch.zeros(C, 7, 8, 4, dtype=F32, device=dev)
     rc = lib.qt_stem_bn_bwd_wgrad_ws(L.qt_dtype(dt), L.ptr(t["d"]), L.ptr(t["code"]), L.ptr(t["y"]), L.ptr(t["scale"]),
                                      L.ptr(t["shift"]), L.ptr(t["mean"]), L.ptr(t["invstd"]), L.ptr(t["coef"]), L.ptr(xpad),
-                                     L.ptr(dw), L.ptr(ws), ctypes.c_size_t(nws - short), B, L.stream_ptr())
+                                     L.ptr(dw), L.ptr(ws), nws - short, B, L.stream_ptr())
     torch.cuda.synchronize()
     return rc, dw.cpu()
 

@@ -28,7 +28,7 @@ def _dev():
 
 def _api():
     M, Lm = pkg("timeline"), pkg("_lib")
-    return M, Lm, M.bind(Lm.lib())
+    return M, Lm, Lm.lib()
 
 
 @functools.lru_cache(maxsize=None)
